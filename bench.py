@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hashes.yaml SHA-512 pass on MI355X, BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: one rank per GPU over RCCL.  Under an outer launcher -- torch.distributed.run sets WORLD_SIZE / RANK /
      LOCAL_RANK -- this process IS a rank; without one the plain command starts its N ranks itself, as child
      processes, before anything in the parent has touched a GPU: self_launch)
@@ -28,6 +28,8 @@ Prints ONE JSON line on rank 0.  Beside the two above:
   configs       BASELINE configs 1, 3 and 5 on this GPU: HBM-resident GPU-only pass (roofline per config), the DEFAULT
                 configuration from host memory, the CPU port beside it, sampled parity vs hashlib
   cpu_baseline  the oracle (C restatement of the reference's serial loop) over the same on-disk tree on one core (every N)
+  dump_outputs  with --dump-outputs DIR: what the last timed step returned (hashes.yaml, its digests and sizes) as
+                DIR/<name>.npy in float32 / float64, 64 MiB at most; the tree's bytes, names and modes are the same every run
 """
 import argparse
 import ctypes
@@ -63,7 +65,14 @@ def parse_args():
     ap.add_argument("--legs", default="auto", choices=["auto", "off", "full"],
                     help="auto = every leg for the default C2 run at N = 1, buffers_sharded only otherwise")
     ap.add_argument("--resident-steps", type=int, default=12, help="launches of the HBM-resident (roofline) pass")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (hashes.yaml and its digests) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ------------------------------------------------------------------------------------------
@@ -118,6 +127,59 @@ def yaml_digest_of(yaml_bytes, name):
     at = yaml_bytes.index(key)
     line = yaml_bytes.index(b"  sha512: ", at)
     return yaml_bytes[line + 10:line + 138].decode()
+
+
+DUMP_LIMIT = 64 << 20       # --dump-outputs: bytes of .npy payload in all
+DUMP_YAML_BYTES = 8 << 20   # hashes.yaml kept whole up to this size (32 MiB as float32); beyond it a seeded sample of blocks
+DUMP_YAML_BLOCK = 4096
+DUMP_FILE_ROWS = (30 << 20) // (64 * 4 + 8 + 8)  # file records kept whole up to this count; beyond it a seeded sample
+
+
+def dump_outputs(out_dir, y):
+    """--dump-outputs: what the timed path's last step handed its caller, as float arrays that two builds can compare
+    output for output.  hashes.yaml itself (byte values), its archive digest, and every file record's size and digest in
+    the order the YAML lists them.  A larger output is cut to a fixed sample (seed 0) and the kept rows are named."""
+    os.makedirs(out_dir, exist_ok=True)
+    archive, sizes, digests, size = None, [], [], None
+    for ln in y.split(b"\n"):
+        if ln.startswith(b"archive-sha512: "):
+            archive = bytes.fromhex(ln[16:].decode())
+        elif ln.startswith(b"- name: "):
+            size = None
+        elif ln.startswith(b"  size: "):
+            size = int(ln[8:])
+        elif ln.startswith(b"  sha512: "):
+            sizes.append(size)
+            digests.append(bytes.fromhex(ln[10:].decode()))
+    if archive is None:
+        raise SystemExit("--dump-outputs: hashes.yaml carries no archive-sha512 line")
+    rng = np.random.default_rng(0)
+    arrays = {"archive_sha512": np.frombuffer(archive, dtype=np.uint8).astype(np.float32),
+              "hashes_yaml_sha512": np.frombuffer(hashlib.sha512(y).digest(), dtype=np.uint8).astype(np.float32)}
+    raw = np.frombuffer(y, dtype=np.uint8)
+    if len(raw) <= DUMP_YAML_BYTES:
+        arrays["hashes_yaml"] = raw.astype(np.float32)
+    else:
+        blocks = np.zeros(-(-len(raw) // DUMP_YAML_BLOCK) * DUMP_YAML_BLOCK, dtype=np.uint8)
+        blocks[:len(raw)] = raw
+        blocks = blocks.reshape(-1, DUMP_YAML_BLOCK)
+        keep = np.sort(rng.choice(len(blocks), DUMP_YAML_BYTES // DUMP_YAML_BLOCK, replace=False))
+        arrays["hashes_yaml_blocks"] = blocks[keep].astype(np.float32)
+        arrays["hashes_yaml_block_index"] = keep.astype(np.float64)
+    rows = np.arange(len(digests))
+    if len(rows) > DUMP_FILE_ROWS:
+        rows = np.sort(rng.choice(len(rows), DUMP_FILE_ROWS, replace=False))
+    arrays["file_row"] = rows.astype(np.float64)
+    arrays["file_size"] = np.array([sizes[i] for i in rows], dtype=np.float64)
+    arrays["file_sha512"] = (np.frombuffer(b"".join(digests[i] for i in rows), dtype=np.uint8).reshape(-1, 64).astype(np.float32)
+                             if len(rows) else np.zeros((0, 64), dtype=np.float32))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": total,
+            "file_records": len(digests), "file_records_kept": len(rows), "yaml_bytes": len(y)}
 
 
 # ------------------------------------------------------------------------------------------
@@ -907,9 +969,11 @@ def main():
             d = os.path.dirname(p)
             if d not in made:
                 os.makedirs(d, exist_ok=True)
+                os.chmod(d, 0o755)  # the modes hashes.yaml records do not depend on the caller's umask
                 made.add(d)
             with open(p, "wb") as f:
                 f.truncate(int(sizes[i]))
+            os.chmod(p, 0o644)
         with open(os.path.join(tmp, "data.tar.gz"), "wb") as f:
             f.truncate(int(sizes[n_files]))
     tmp = bcast_obj(tmp)
@@ -970,6 +1034,7 @@ def main():
             step_ms.append((time.perf_counter() - ts) * 1e3)  # (this rank's own view of each step: reported beside the mean)
         fence()
         elapsed = allmax(time.perf_counter() - t0)
+        dumped = dump_outputs(args.dump_outputs, last["yaml"]) if args.dump_outputs and rank == 0 else None
         e_st = ectx.stats()
         per_rank_step = gather_obj({"streams": len(my_paths), "bytes": int(my_lens.sum()), "h2d_ms": round(e_st["h2d_ms"], 2),
                                     "kernel_ms": round(e_st["kernel_ms"], 2), "launches": int(e_st["launches"])})
@@ -1154,6 +1219,8 @@ def main():
                 line["configs"] = configs
             if cpu is not None:
                 line["cpu_baseline"] = cpu
+            if dumped is not None:
+                line["dump_outputs"] = dumped
     finally:
         if use_dist:
             try:
