@@ -62,7 +62,9 @@ enum {
     SNAPHASH_EMODE = -5,    /* "Unknown file mode" (hashes.go:47): device, fifo, socket */
     SNAPHASH_ENAME = -6,    /* file name outside the plain-scalar set the YAML emitter reproduces */
     SNAPHASH_EPARSE = -7,   /* hashes.yaml text not understood */
-    SNAPHASH_EMISMATCH = -8 /* snaphash_verify: tree differs from hashes.yaml */
+    SNAPHASH_EMISMATCH = -8, /* snaphash_verify: tree differs from hashes.yaml */
+    SNAPHASH_EFORMAT = -9,   /* not a valid gzip, DEFLATE or tar stream, or a CRC-32 / ISIZE mismatch */
+    SNAPHASH_ECONTENT = -10  /* snaphash_tar_unpack: a member name with "..", or a member type it does not unpack */
 };
 
 enum { /* snaphash_config.kernel */
@@ -311,6 +313,45 @@ int snaphash_tar_create_fn(snaphash_ctx *ctx, const char *tarname, const char *s
 /* The compressor alone: one gzip member (RFC 1952) of a host buffer; *gz_out is malloc'd (snaphash_free). */
 int snaphash_gzip_buffer(snaphash_ctx *ctx, const void *data, size_t n, void **gz_out, size_t *gz_len);
 void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out);
+
+/* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
+
+typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack */
+    uint32_t struct_size;   /* in: sizeof(snaphash_unpack_stats) */
+    uint32_t reserved;
+    uint64_t gz_bytes;      /* compressed input */
+    uint64_t tar_bytes;     /* decoded output */
+    uint64_t members;       /* tar members (0 for snaphash_gunzip_buffer) */
+    uint64_t segments;      /* stretches the stream was decoded in: linked GPU segments + host stretches */
+    uint64_t gpu_segments;  /* of those, decoded by the inflate kernel */
+    uint64_t host_bytes;    /* output bytes the host decoder produced (stretches without flush points, gaps) */
+    double inflate_ms;      /* inflate kernels (scan, decode, fill, concat), HIP events */
+    double wall_ms;
+} snaphash_unpack_stats;
+
+/* The inverse of snaphash_gzip_buffer: every member of gz[0..n) (RFC 1952; concatenated members are read one after
+ * another, as Go's gzip.Reader does), each member's CRC-32 and ISIZE checked.  *out is malloc'd (snaphash_free).
+ * The DEFLATE stream is cut at its flush points (the empty stored block of Z_SYNC_FLUSH, which the producer writes after
+ * every 64 KiB chunk, and stored blocks) and the segments are decoded side by side -- on host threads in the default
+ * configuration (measured faster), by the GPU inflate kernel under SNAPHASH_FLAG_GPU_ONLY; a stretch without flush points
+ * (zlib's or Go's plain output) and any segment the kernel gives up on are decoded by the host decoder.
+ * SNAPHASH_EFORMAT: not a gzip / DEFLATE stream, or a CRC-32 / ISIZE mismatch. */
+int snaphash_gunzip_buffer(snaphash_ctx *ctx, const void *gz, size_t n, void **out, size_t *out_len);
+
+/* ClickDeb.Unpack (clickdeb/deb.go:188-203) of data.tar.gz into target_dir: helpers.UnpackTar (helpers/helpers.go:74-147)
+ * with clickVerifyContentFn (deb.go:96-103) -- every name through filepath.Clean, any that still contains ".." refused
+ * (SNAPHASH_ECONTENT); MkdirAll(dir, 0777) for every member; a directory Mkdir'ed with its mode (an error ignored); a
+ * symlink created; a regular file opened O_WRONLY|O_TRUNC|O_CREAT with its mode (the umask applies); PAX extended headers
+ * and GNU long names read as archive/tar reads them; any other member type refused (SNAPHASH_ECONTENT); the first error
+ * stops the call.  yaml != NULL also does the install-time Verify of hashes.yaml (click.go:955-970) without reading a
+ * file back: every regular member is hashed from the decoded stream in HBM (long ones on host threads, as the producer
+ * plans them; SNAPHASH_FLAG_GPU_ONLY keeps them on the kernels), the archive digest is taken over the compressed bytes,
+ * and the result is 0 or SNAPHASH_EMISMATCH with the kind and name snaphash_verify reports on the unpacked tree.
+ * archive_digest (may be NULL): the 64 raw bytes of SHA-512(data_tar_gz). */
+int snaphash_tar_unpack(snaphash_ctx *ctx, const char *data_tar_gz, const char *target_dir, const char *yaml, size_t yaml_len,
+                        snaphash_mismatch *first, uint8_t *archive_digest);
+/* out->struct_size in; SNAPHASH_EINVAL if it is smaller than the ABI 5 struct. */
+int snaphash_get_unpack_stats(const snaphash_ctx *ctx, snaphash_unpack_stats *out);
 
 /* ---- neighbouring scan: helpers.FilesAreEqual / DirUpdated -------- */
 

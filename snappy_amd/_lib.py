@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNAPHASH_LIB") or os.path.join(_HERE, "libsnaphash.so")
 
 OK, EINVAL, ENOMEM, EIO, EDEVICE, EMODE, ENAME, EPARSE, EMISMATCH = 0, -1, -2, -3, -4, -5, -6, -7, -8
+EFORMAT, ECONTENT = -9, -10
 KERNEL_AUTO, KERNEL_WIDE, KERNEL_SPLIT, KERNEL_PAIR, KERNEL_QUAD = 0, 1, 2, 3, 4
 KERNEL_NAMES = {KERNEL_WIDE: "sha512_wide_kernel", KERNEL_SPLIT: "sha512_split_kernel<false>",
                 KERNEL_PAIR: "sha512_split_kernel<true>", KERNEL_QUAD: "sha512_quad_kernel"}
@@ -37,6 +38,8 @@ EXPORTS = [
     "snaphash_shard_set_local_ranks", "snaphash_shard_fingerprint", "snaphash_get_plan_model", "snaphash_calib_observe_call",
     "snaphash_shard_list", "snaphash_shard_plan_from",
     "snaphash_calib_observe", "snaphash_calib_apply", "snaphash_get_calib",
+    # the install side (row f5)
+    "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats",
 ]
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
 
@@ -93,6 +96,13 @@ class TargzStats(ctypes.Structure):
     _fields_ = [("tar_bytes", ctypes.c_uint64), ("gz_bytes", ctypes.c_uint64), ("members", ctypes.c_uint64),
                 ("chunks", ctypes.c_uint64), ("stored_chunks", ctypes.c_uint64), ("deflate_ms", ctypes.c_double),
                 ("fill_ms", ctypes.c_double), ("wall_ms", ctypes.c_double)]
+
+
+class UnpackStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("gz_bytes", ctypes.c_uint64),
+                ("tar_bytes", ctypes.c_uint64), ("members", ctypes.c_uint64), ("segments", ctypes.c_uint64),
+                ("gpu_segments", ctypes.c_uint64), ("host_bytes", ctypes.c_uint64), ("inflate_ms", ctypes.c_double),
+                ("wall_ms", ctypes.c_double)]
 
 
 class Mismatch(ctypes.Structure):
@@ -182,6 +192,9 @@ def lib():
     L.snaphash_gzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_get_targz_stats.argtypes = [vp, ctypes.POINTER(TargzStats)]
     L.snaphash_get_targz_stats.restype = None
+    L.snaphash_gunzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_get_unpack_stats.argtypes = [vp, ctypes.POINTER(UnpackStats)]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -388,6 +401,35 @@ class Context:
         finally:
             if with_hashes:
                 lib().snaphash_free(p)
+
+    def gunzip_buffer(self, gz):
+        """The inverse of gzip_buffer: every member of `gz` decoded, DEFLATE segments on the GPU (row f5)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        gz = bytes(gz)
+        self._check(lib().snaphash_gunzip_buffer(self._h, ctypes.cast(ctypes.c_char_p(gz), ctypes.c_void_p), len(gz),
+                                                 ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def tar_unpack(self, data_tar_gz, target_dir, yaml_bytes=None):
+        """ClickDeb.Unpack of data.tar.gz into target_dir (clickdeb/deb.go:188-203); with yaml_bytes also the install-time
+        Verify from the decoded bytes.  -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
+        m = Mismatch()
+        dig = ctypes.create_string_buffer(64)
+        rc = lib().snaphash_tar_unpack(self._h, os.fsencode(data_tar_gz), os.fsencode(target_dir), yaml_bytes,
+                                       len(yaml_bytes) if yaml_bytes is not None else 0, ctypes.byref(m), dig)
+        if rc == EMISMATCH:
+            return (m.kind, m.name.decode(errors="replace")), dig.raw
+        self._check(rc)
+        return None, dig.raw
+
+    def unpack_stats(self):
+        s = UnpackStats()
+        s.struct_size = ctypes.sizeof(UnpackStats)
+        self._check(lib().snaphash_get_unpack_stats(self._h, ctypes.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in UnpackStats._fields_ if f[0] not in ("struct_size", "reserved")}
 
     def targz_stats(self):
         s = TargzStats()

@@ -1,4 +1,4 @@
-"""clickdeb.tarCreate, GPU-backed (reference clickdeb/deb.go:261-344).
+"""clickdeb.tarCreate and ClickDeb.Unpack, GPU-backed (reference clickdeb/deb.go:261-344, 188-203).
 
 Same name, argument meaning and error behaviour as the Go function: tarCreate(tarname, sourceDir, fn) walks
 sourceDir, asks fn(path) for every regular file, symlink and directory (False leaves it out; None keeps all),
@@ -13,3 +13,12 @@ def tarCreate(tarname, sourceDir, fn=None, ctx=None):
     """-> the 64-byte SHA-512 of the archive written (the Go function returns only the error)."""
     _, digest = (ctx or default_context()).tar_create_fn(tarname, sourceDir, fn)
     return digest
+
+
+def Unpack(dataTarGz, targetDir, hashesYaml=None, ctx=None):
+    """ClickDeb.Unpack (clickdeb/deb.go:188-203) of the package's data.tar.gz into targetDir: helpers.UnpackTar with
+    clickVerifyContentFn, raising on the first error (SnaphashError: EFORMAT for a corrupt stream, ECONTENT for a ".."
+    name or an unsupported member type).  hashesYaml (bytes): also the install-time Verify, from the decoded bytes.
+    -> None, or (kind, name) of the first mismatch against hashesYaml."""
+    mismatch, _ = (ctx or default_context()).tar_unpack(dataTarGz, targetDir, hashesYaml)
+    return mismatch

@@ -25,12 +25,14 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // types only: the library is dlopen'ed when a ctx owns several devices
 
 #include <condition_variable>
+#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -39,6 +41,8 @@
 #include "hostfill.h"
 #include "hostpass.h"
 #include "hostsha.h"
+#include "inflate_host.h"
+#include "inflate_kernels.h"
 #include "member_hashers.h"
 #include "planner.h"
 #include "sha512_core.h"
@@ -141,6 +145,26 @@ struct DevCtx {
     std::vector<hipEvent_t> z_part_ev;       // "part k of the pass's first slot is in HBM" (targz.inc)
     size_t z_chunks = 0;
 
+    // GPU inflate scratch (row f5, unpack.inc): the compressed piece, its candidates, the speculative segments' slots and
+    // results, the linked chain, the window in front of the piece, the decoded bytes
+    hipStream_t f_stream = nullptr;
+    uint8_t* d_fin = nullptr;
+    uint64_t fin_cap = 0;
+    uint32_t* d_fcand = nullptr; // [0] count, then the candidates
+    uint32_t* h_fcand = nullptr; // pinned
+    uint64_t fcand_cap = 0;
+    uint16_t* d_fslots = nullptr;
+    InflateSegRes* d_fres = nullptr;
+    InflateSegRes* h_fres = nullptr; // pinned
+    InflateLink* d_flinks = nullptr;
+    InflateLink* h_flinks = nullptr; // pinned
+    uint32_t fslots_cap = 0;
+    uint32_t* d_fflags = nullptr;
+    uint32_t* h_fflags = nullptr; // pinned
+    uint8_t* d_fwin = nullptr;
+    uint8_t* d_fout = nullptr;
+    uint64_t fout_cap = 0;
+
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;
     bool pending = false;
@@ -200,6 +224,7 @@ struct snaphash_ctx {
     snaphash_stats stats{};
     snaphash_stats_ex ex{};
     snaphash_targz_stats targz{};
+    snaphash_unpack_stats unpack{};
     std::string last_error;
     snaphash_batch* open_batch = nullptr;
     DevCtx* d0() const { return dev[0].get(); }
@@ -1367,10 +1392,13 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+static void free_inflate(DevCtx* c);
+
 static void destroy_dev(DevCtx* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    free_inflate(c);
     for (Slot& s : c->slot) {
         if (s.h_buf) (void)hipHostFree(s.h_buf);
         if (s.d_buf) (void)hipFree(s.d_buf);
@@ -1839,11 +1867,13 @@ static int mismatch(snaphash_ctx* c, snaphash_mismatch* m, int kind, const std::
     return fail(c, SNAPHASH_EMISMATCH, name + ": " + what[kind]);
 }
 
-int snaphash_verify(snaphash_ctx* x, const char* inst_dir, const char* data_tar, const char* yaml, size_t yaml_len,
-                    snaphash_mismatch* first)
-try {
-    if (!x || !inst_dir || !yaml) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
+// Verify's comparison.  have_digest (may be empty): the digest of a regular record that the caller already holds (the
+// unpack pass: hashed from the decoded archive), true if it wrote it; the other regular records are hashed from disk.
+// archive_digest: the archive's digest, already taken (then data_tar is only a flag that it is to be checked).
+static int verify_impl(snaphash_ctx* x, const char* inst_dir, const char* data_tar, const uint8_t* archive_digest, const char* yaml,
+                       size_t yaml_len, snaphash_mismatch* first, const std::function<bool(const Record&, uint8_t*)>& have_digest)
+{
+    const double t_top0_ = now_ms();
     ParsedHashes ph;
     int rc = parse_yaml(yaml, yaml_len, ph);
     if (rc) return fail(x, rc, "hashes.yaml: parse error");
@@ -1882,21 +1912,40 @@ try {
     std::vector<const char*> paths;
     std::vector<int64_t> sizes;
     std::vector<size_t> owner;
-    if (data_tar) { paths.push_back(data_tar); sizes.push_back(-1); owner.push_back((size_t)-1); }
-    for (size_t k = 0; k < recs.size(); ++k)
-        if (recs[k].is_regular) { paths.push_back(recs[k].path.c_str()); sizes.push_back(recs[k].size); owner.push_back(k); }
+    std::vector<uint8_t> held(recs.size() * 64 + 64), is_held(recs.size() + 1, 0); // digests the caller supplied
+    if (data_tar && !archive_digest) { paths.push_back(data_tar); sizes.push_back(-1); owner.push_back((size_t)-1); }
+    for (size_t k = 0; k < recs.size(); ++k) {
+        if (!recs[k].is_regular) continue;
+        if (have_digest && have_digest(recs[k], held.data() + 64 * k)) { is_held[k] = 1; continue; }
+        paths.push_back(recs[k].path.c_str()); sizes.push_back(recs[k].size); owner.push_back(k);
+    }
     std::vector<uint8_t> dig(paths.size() * 64 + 64);
-    rc = hash_paths(x, paths.data(), paths.size(), sizes.data(), dig.data(), nullptr);
+    rc = (paths.empty() && have_digest) ? 0 : hash_paths(x, paths.data(), paths.size(), sizes.data(), dig.data(), nullptr);
     end_top(x, t_top0_);
     if (rc) return rc;
+    if (data_tar && archive_digest && !digest_matches_hex(archive_digest, ph.archive_hex)) return mismatch(x, first, 6, "archive-sha512");
+    std::vector<const uint8_t*> of(recs.size(), nullptr); // every regular record's digest, checked in walk order
     for (size_t q = 0; q < paths.size(); ++q) {
         if (owner[q] == (size_t)-1) {
             if (!digest_matches_hex(dig.data() + 64 * q, ph.archive_hex)) return mismatch(x, first, 6, "archive-sha512");
-        } else if (!digest_matches_hex(dig.data() + 64 * q, ph.files[owner[q]].sha512_hex)) {
-            return mismatch(x, first, 4, recs[owner[q]].name);
+        } else {
+            of[owner[q]] = dig.data() + 64 * q;
         }
     }
+    for (size_t k = 0; k < recs.size(); ++k) {
+        if (is_held[k]) of[k] = held.data() + 64 * k;
+        if (of[k] && !digest_matches_hex(of[k], ph.files[k].sha512_hex)) return mismatch(x, first, 4, recs[k].name);
+    }
     return SNAPHASH_OK;
+}
+
+int snaphash_verify(snaphash_ctx* x, const char* inst_dir, const char* data_tar, const char* yaml, size_t yaml_len,
+                    snaphash_mismatch* first)
+try {
+    if (!x || !inst_dir || !yaml) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    (void)t_top0_;
+    return verify_impl(x, inst_dir, data_tar, nullptr, yaml, yaml_len, first, {});
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -2531,6 +2580,7 @@ void snaphash_batch_abort(snaphash_batch* b)
 } // extern "C"
 
 #include "targz.inc"
+#include "unpack.inc"
 
 // ---- helpers.FilesAreEqual / DirUpdated (row f4) ----------------------------------------------
 
@@ -3024,6 +3074,8 @@ const char* snaphash_strerror(int code)
     case SNAPHASH_ENAME: return "file name outside the plain YAML scalar set";
     case SNAPHASH_EPARSE: return "hashes.yaml parse error";
     case SNAPHASH_EMISMATCH: return "tree does not match hashes.yaml";
+    case SNAPHASH_EFORMAT: return "not a valid gzip, DEFLATE or tar stream";
+    case SNAPHASH_ECONTENT: return "archive member refused (\"..\" in its name or an unsupported type)";
     default: return "unknown error";
     }
 }

@@ -1,0 +1,708 @@
+// unpack.inc -- the install side (SURVEY sec. 8 row f5), textually part of snaphash_api.cpp (it uses the engine's
+// streams, events, the hashing kernels and Verify's comparison).
+//
+// The reference unpacks a package with ClickDeb.Unpack (clickdeb/deb.go:188-203): gzip.NewReader (deb.go:427) -- one Go
+// inflate on one core -- into helpers.UnpackTar (helpers/helpers.go:74-147) with clickVerifyContentFn (deb.go:96-103);
+// the Verify hook (snappy/click.go:955-970) then reads every file of the unpacked tree again.  Here the archive is
+// decoded by the GPU inflate (inflate_kernels.hip) into HBM, written out from there, and -- with hashes.yaml -- every
+// regular member is hashed out of the decoded stream that is already in HBM: nothing is read back from disk.
+
+namespace {
+
+void free_inflate_bufs(DevCtx* c)
+{
+    if (c->d_fin) (void)hipFree(c->d_fin);
+    if (c->d_fcand) (void)hipFree(c->d_fcand);
+    if (c->h_fcand) (void)hipHostFree(c->h_fcand);
+    if (c->d_fslots) (void)hipFree(c->d_fslots);
+    if (c->d_fres) (void)hipFree(c->d_fres);
+    if (c->h_fres) (void)hipHostFree(c->h_fres);
+    if (c->d_flinks) (void)hipFree(c->d_flinks);
+    if (c->h_flinks) (void)hipHostFree(c->h_flinks);
+    if (c->d_fflags) (void)hipFree(c->d_fflags);
+    if (c->h_fflags) (void)hipHostFree(c->h_fflags);
+    if (c->d_fwin) (void)hipFree(c->d_fwin);
+    if (c->d_fout) (void)hipFree(c->d_fout);
+    if (c->f_stream) (void)hipStreamDestroy(c->f_stream);
+    c->d_fin = nullptr; c->d_fcand = nullptr; c->h_fcand = nullptr; c->d_fslots = nullptr; c->d_fres = nullptr; c->h_fres = nullptr;
+    c->d_flinks = nullptr; c->h_flinks = nullptr; c->d_fflags = nullptr; c->h_fflags = nullptr; c->d_fwin = nullptr; c->d_fout = nullptr;
+    c->f_stream = nullptr;
+    c->fin_cap = 0; c->fcand_cap = 0; c->fslots_cap = 0; c->fout_cap = 0;
+}
+
+// the compressed piece (and its candidates) and the segments a launch decodes
+int ensure_inflate(DevCtx* c, uint64_t piece, uint32_t slots)
+{
+    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    if (!c->d_fflags) HIP_TRY(c, hipMalloc((void**)&c->d_fflags, 16));
+    if (!c->h_fflags) HIP_TRY(c, host_alloc(c, (void**)&c->h_fflags, 16));
+    if (!c->d_fwin) HIP_TRY(c, hipMalloc((void**)&c->d_fwin, kInfWindow));
+    if (c->fin_cap < piece) {
+        if (c->d_fin) (void)hipFree(c->d_fin);
+        if (c->d_fcand) (void)hipFree(c->d_fcand);
+        if (c->h_fcand) (void)hipHostFree(c->h_fcand);
+        c->d_fin = nullptr; c->d_fcand = nullptr; c->h_fcand = nullptr; c->fin_cap = 0;
+        const uint64_t cand = piece / 4 + 16; // (a candidate per 4 bytes at most that the launch takes; more are counted, not kept)
+        HIP_TRY(c, hipMalloc((void**)&c->d_fin, piece + 16));
+        HIP_TRY(c, hipMalloc((void**)&c->d_fcand, (cand + 2) * 4)); // (the count, the candidates, the piece start)
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_fcand, (cand + 2) * 4));
+        c->fin_cap = piece;
+        c->fcand_cap = cand;
+    }
+    if (c->fslots_cap < slots) {
+        if (c->d_fslots) (void)hipFree(c->d_fslots);
+        if (c->d_fres) (void)hipFree(c->d_fres);
+        if (c->h_fres) (void)hipHostFree(c->h_fres);
+        if (c->d_flinks) (void)hipFree(c->d_flinks);
+        if (c->h_flinks) (void)hipHostFree(c->h_flinks);
+        c->d_fslots = nullptr; c->d_fres = nullptr; c->h_fres = nullptr; c->d_flinks = nullptr; c->h_flinks = nullptr; c->fslots_cap = 0;
+        HIP_TRY(c, hipMalloc((void**)&c->d_fslots, (size_t)slots * kInflateSlotSyms * 2));
+        HIP_TRY(c, hipMalloc((void**)&c->d_fres, (size_t)slots * sizeof(InflateSegRes)));
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_fres, (size_t)slots * sizeof(InflateSegRes)));
+        HIP_TRY(c, hipMalloc((void**)&c->d_flinks, (size_t)slots * sizeof(InflateLink)));
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_flinks, (size_t)slots * sizeof(InflateLink)));
+        c->fslots_cap = slots;
+    }
+    return SNAPHASH_OK;
+}
+
+// the decoded bytes in HBM: `keep` bytes of what is there are kept when it grows
+int ensure_fout(DevCtx* c, uint64_t need, uint64_t keep)
+{
+    if (c->fout_cap >= need) return SNAPHASH_OK;
+    uint64_t cap = std::max<uint64_t>(need, c->fout_cap + c->fout_cap / 2);
+    cap = (cap + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1);
+    uint8_t* p = nullptr;
+    HIP_TRY(c, hipMalloc((void**)&p, cap));
+    if (keep && c->d_fout) {
+        const hipError_t e = hipMemcpyAsync(p, c->d_fout, keep, hipMemcpyDeviceToDevice, c->f_stream);
+        if (e == hipSuccess) (void)hipStreamSynchronize(c->f_stream);
+        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(c, e); }
+    }
+    if (c->d_fout) (void)hipFree(c->d_fout);
+    c->d_fout = p;
+    c->fout_cap = cap;
+    return SNAPHASH_OK;
+}
+
+#define INF_TRY(expr) HIP_TRY(c, (expr))
+
+// Decodes every gzip member of gz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
+// c->d_fout[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
+// member's last 32 KiB of output travel to the next as its window.
+int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
+                  snaphash_unpack_stats& st)
+{
+    if (n == 0) return fail(c, SNAPHASH_EFORMAT, "gzip: empty stream");
+    const uint64_t P = std::min<uint64_t>(std::max<uint64_t>(c->staging, 64u << 10), 64ull << 20);
+    const uint32_t S = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(64, P / 16384));
+    int rc = ensure_inflate(c, std::min<uint64_t>(P, n), (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(64, n / 4096 + 1)));
+    if (rc) return rc;
+    const uint32_t slots = c->fslots_cap;
+    static const bool trace = getenv("SNAPHASH_TRACE_INFLATE") != nullptr; // the pieces and their chains on stderr
+    const bool host_mode = !x->gpu_only;
+    constexpr uint64_t kHostPiece = 8u << 20; // compressed bytes a piece of the host-thread decode takes (its slots: 2 B a symbol)
+    std::vector<uint16_t> hslots;
+    std::vector<uint8_t> hbytes;
+    float kms = 0;
+    auto timed = [&](EventPair* ev) {
+        float ms = 0;
+        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
+    };
+    if (n >= 18) { // the output in one allocation: ISIZE of the last member (exact for a single member under 4 GiB)
+        const uint64_t isize = gz[n - 4] | (uint64_t)gz[n - 3] << 8 | (uint64_t)gz[n - 2] << 16 | (uint64_t)gz[n - 1] << 24;
+        if (isize <= (uint64_t)n * 1032) out.reserve(out.size() + (size_t)isize);
+    }
+    size_t at = 0;
+    while (at < n) {
+        size_t h = 0;
+        if (gzip_header(gz + at, n - at, &h)) return fail(c, SNAPHASH_EFORMAT, "gzip: bad member header");
+        const uint8_t* z = gz + at + h;
+        const uint64_t zn = n - at - h;
+        const size_t m0 = out.size();
+        uint64_t cur = 0; // byte offset in z where the next segment starts
+        uint64_t final_bit = 0;
+        bool ended = false;
+        // the host decoder from cur to the next segment end (or the member's end)
+        auto host_run = [&]() -> int {
+            const size_t o0 = out.size();
+            const InflateRun r = inflate_host_append(z, zn, cur * 8, out, m0, true);
+            if (r.status != kInfFinal && r.status != kInfFlush) return fail(c, SNAPHASH_EFORMAT, "gzip: corrupt DEFLATE stream");
+            st.segments++;
+            st.host_bytes += out.size() - o0;
+            if (keep_dev && out.size() > o0) {
+                int e = ensure_fout(c, out.size(), o0);
+                if (e) return e;
+                INF_TRY(hipMemcpyAsync(c->d_fout + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+                INF_TRY(hipStreamSynchronize(c->f_stream));
+            }
+            if (r.status == kInfFinal) { ended = true; final_bit = r.end_bit; }
+            else cur = r.end_bit >> 3;
+            return 0;
+        };
+        while (!ended) {
+            // the default configuration decodes the segments on host threads (measured faster than the kernel:
+            // DESIGN.md sec. 14); SNAPHASH_FLAG_GPU_ONLY sends every linked segment through the kernel
+            const uint64_t pn = std::min<uint64_t>(host_mode ? kHostPiece : P, zn - cur);
+            std::vector<uint32_t> cand;
+            if (host_mode) {
+                for (uint64_t v : flush_candidates(z + cur, pn)) cand.push_back((uint32_t)v);
+            } else {
+                INF_TRY(hipMemcpyAsync(c->d_fin, z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
+                INF_TRY(hipMemsetAsync(c->d_fcand, 0, 4, c->f_stream));
+                EventPair* ev = next_events(c, 2);
+                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+                INF_TRY(hipEventRecord(ev->a, c->f_stream));
+                INF_TRY(launch_inflate_scan(c->d_fin, pn, c->d_fcand + 1, c->d_fcand, (uint32_t)c->fcand_cap, c->f_stream));
+                INF_TRY(hipEventRecord(ev->b, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->h_fcand, c->d_fcand, 4, hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipStreamSynchronize(c->f_stream));
+                timed(ev);
+                const uint64_t ncand = std::min<uint64_t>(c->h_fcand[0], c->fcand_cap);
+                if (ncand) {
+                    INF_TRY(hipMemcpyAsync(c->h_fcand + 1, c->d_fcand + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
+                    INF_TRY(hipStreamSynchronize(c->f_stream));
+                }
+                cand.assign(c->h_fcand + 1, c->h_fcand + 1 + ncand);
+            }
+            // candidate starts in order, the piece's own start first (past the launch's slots the piece is cut)
+            cand.push_back(0);
+            std::sort(cand.begin(), cand.end());
+            cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+            if (cand.size() > (host_mode ? std::min<uint32_t>(slots, 512) : slots)) cand.resize(host_mode ? std::min<uint32_t>(slots, 512) : slots);
+            if (cand.size() == 1 && pn == zn - cur) { // no flush point ahead: the host's stretch
+                rc = host_run();
+                if (rc) return rc;
+                continue;
+            }
+            const uint32_t K = (uint32_t)cand.size();
+            if (host_mode) {
+                // the kernel's work on host threads: every candidate decoded speculatively into a slot by the workers, in
+                // order, while this thread links the chain and fills each linked segment's holes as soon as it is decoded
+                // (in chain order: the bytes in front of a segment are final when it is filled)
+                hslots.resize((size_t)K * kInflateSlotSyms);
+                hbytes.resize((size_t)K * kInflateSlotSyms);
+                std::unique_ptr<std::atomic<uint32_t>[]> done(new std::atomic<uint32_t>[K]);
+                for (uint32_t i = 0; i < K; ++i) done[i].store(0, std::memory_order_relaxed);
+                std::atomic<uint32_t> next{0};
+                auto work = [&]() {
+                    InflateTables t;
+                    for (;;) {
+                        const uint32_t i = next.fetch_add(1);
+                        if (i >= K) return;
+                        const InflateRun r = inflate_run<uint16_t>(z + cur, pn, (uint64_t)cand[i] * 8, hslots.data() + (size_t)i * kInflateSlotSyms,
+                                                                   0, kInflateSlotSyms, true, true, t);
+                        // the bytes that are no holes, narrowed here in parallel; the holes are left to the linking thread
+                        const uint16_t* sy = hslots.data() + (size_t)i * kInflateSlotSyms;
+                        uint8_t* by = hbytes.data() + (size_t)i * kInflateSlotSyms;
+                        uint32_t last = 0;
+                        for (uint32_t q = 0; q < (uint32_t)r.out_len; ++q) {
+                            by[q] = (uint8_t)sy[q];
+                            last = sy[q] >= kInfHole ? q + 1 : last;
+                        }
+                        c->h_fres[i] = InflateSegRes{r.end_bit, (uint32_t)r.out_len, last, r.status, 0};
+                        done[i].store(1, std::memory_order_release);
+                    }
+                };
+                const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, x->cpus_call ? x->cpus_call : x->cpus) - 1);
+                ThreadJoiner th;
+                for (unsigned k = 0; k < T; ++k) th.spawn(work);
+                const size_t o0 = out.size();
+                uint64_t pos = 0;
+                uint32_t nl = 0;
+                bool fin = false, bad = false;
+                for (;;) {
+                    const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
+                    if (it == cand.end() || *it != pos) break;
+                    const uint32_t i = (uint32_t)(it - cand.begin());
+                    while (!done[i].load(std::memory_order_acquire)) std::this_thread::yield();
+                    const InflateSegRes& r = c->h_fres[i];
+                    if (r.status != kInfFlush && r.status != kInfFinal) break;
+                    const size_t base = out.size();
+                    out.resize(base + r.out_len);
+                    memcpy(out.data() + base, hbytes.data() + (size_t)i * kInflateSlotSyms, r.out_len);
+                    if (!fill_holes_host(hslots.data() + (size_t)i * kInflateSlotSyms, r.hole_end, out.data() + base, base - m0)) { bad = true; break; }
+                    ++nl;
+                    if (r.status == kInfFinal) { fin = true; final_bit = r.end_bit + cur * 8; break; }
+                    pos = r.end_bit >> 3;
+                    if (pos >= pn) break;
+                }
+                next.store(K); // (what is left of the piece is decoded again as the next piece)
+                th.join_all();
+                if (bad) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
+                if (nl == 0) {
+                    rc = host_run();
+                    if (rc) return rc;
+                    continue;
+                }
+                if (keep_dev && out.size() > o0) {
+                    rc = ensure_fout(c, out.size(), o0);
+                    if (rc) return rc;
+                    INF_TRY(hipMemcpyAsync(c->d_fout + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+                    INF_TRY(hipStreamSynchronize(c->f_stream));
+                }
+                st.segments += nl;
+                if (fin) ended = true;
+                else cur += pos;
+                continue;
+            } else {
+                memcpy(c->h_fcand + 1, cand.data(), (size_t)K * 4);
+                INF_TRY(hipMemcpyAsync(c->d_fcand + 1, c->h_fcand + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
+                EventPair* ev = next_events(c, 2);
+                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+                INF_TRY(hipEventRecord(ev->a, c->f_stream));
+                INF_TRY(launch_inflate_decode(c->d_fin, pn, c->d_fcand + 1, K, c->d_fslots, c->d_fres, c->f_stream));
+                INF_TRY(hipEventRecord(ev->b, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->h_fres, c->d_fres, (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipStreamSynchronize(c->f_stream));
+                timed(ev);
+            }
+            // link: from the piece's start, each segment where the one before ended
+            uint32_t nl = 0;
+            uint64_t pos = 0, off = 0;
+            bool fin = false;
+            for (;;) {
+                const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
+                if (it == cand.end() || *it != pos) break;
+                const uint32_t i = (uint32_t)(it - cand.begin());
+                const InflateSegRes& r = c->h_fres[i];
+                if (r.status != kInfFlush && r.status != kInfFinal) break;
+                InflateLink& L = c->h_flinks[nl++];
+                L.off = off;
+                L.slot = i;
+                L.len = r.out_len;
+                L.hole_end = r.hole_end;
+                L.pad = 0;
+                off += r.out_len;
+                if (r.status == kInfFinal) { fin = true; final_bit = r.end_bit + cur * 8; break; }
+                pos = r.end_bit >> 3;
+                if (pos >= pn) break;
+            }
+            if (trace) {
+                const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
+                const int why = (it == cand.end() || *it != pos) ? -1 : c->h_fres[it - cand.begin()].status;
+                fprintf(stderr, "snaphash inflate: piece at %llu, %llu bytes, %u candidates, chain of %u, stopped at %llu (%d)\n",
+                        (unsigned long long)cur, (unsigned long long)pn, K, nl, (unsigned long long)pos, fin ? 100 : why);
+            }
+            if (nl == 0) { // the segment at the piece's start is not the kernel's (too long for a slot, or a gap): the host's
+                rc = host_run();
+                if (rc) return rc;
+                continue;
+            }
+            const size_t o0 = out.size();
+            const uint32_t wlen = (uint32_t)std::min<size_t>(kInfWindow, o0 - m0);
+            if (wlen) INF_TRY(hipMemcpyAsync(c->d_fwin, out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
+            INF_TRY(hipMemcpyAsync(c->d_flinks, c->h_flinks, (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
+            // one pass over every segment at once, then -- if holes are left (chains of holes through the segments) -- the
+            // segments that hold them one after another in order, and a last pass that counts what is left (nothing)
+            bool filled = false;
+            EventPair* ev = nullptr;
+            for (int pass = 0; pass < 2 && !filled; ++pass) {
+                INF_TRY(hipMemsetAsync(c->d_fflags, 0, 8, c->f_stream));
+                ev = next_events(c, 2);
+                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+                INF_TRY(hipEventRecord(ev->a, c->f_stream));
+                if (pass == 1)
+                    for (uint32_t j = 0; j < nl; ++j)
+                        if (c->h_flinks[j].hole_end) INF_TRY(launch_inflate_fill(c->d_fslots, c->d_flinks, j, 1, c->d_fwin, wlen, c->d_fflags, c->f_stream));
+                if (pass == 1) INF_TRY(hipMemsetAsync(c->d_fflags, 0, 8, c->f_stream));
+                INF_TRY(launch_inflate_fill(c->d_fslots, c->d_flinks, 0, nl, c->d_fwin, wlen, c->d_fflags, c->f_stream));
+                INF_TRY(hipEventRecord(ev->b, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->h_fflags, c->d_fflags, 8, hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipStreamSynchronize(c->f_stream));
+                timed(ev);
+                if (c->h_fflags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
+                filled = c->h_fflags[0] == 0;
+                if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->h_fflags[0]);
+            }
+            if (!filled) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
+                rc = host_run();
+                if (rc) return rc;
+                continue;
+            }
+            rc = ensure_fout(c, keep_dev ? o0 + off : off, keep_dev ? o0 : 0);
+            if (rc) return rc;
+            uint8_t* dst = c->d_fout + (keep_dev ? o0 : 0);
+            ev = next_events(c, 2);
+            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            INF_TRY(hipEventRecord(ev->a, c->f_stream));
+            INF_TRY(launch_inflate_concat(c->d_fslots, c->d_flinks, nl, dst, c->f_stream));
+            INF_TRY(hipEventRecord(ev->b, c->f_stream));
+            out.resize(o0 + off);
+            INF_TRY(hipMemcpyAsync(out.data() + o0, dst, off, hipMemcpyDeviceToHost, c->f_stream));
+            INF_TRY(hipStreamSynchronize(c->f_stream));
+            timed(ev);
+            st.segments += nl;
+            st.gpu_segments += nl;
+            if (fin) ended = true;
+            else cur += pos;
+            c->ev_used = 0;
+        }
+        c->ev_used = 0;
+        const uint32_t crc = crc_parallel(out.data() + m0, out.size() - m0);
+        size_t next = 0;
+        if (gzip_trailer(z, zn, final_bit, crc, out.size() - m0, &next)) return fail(c, SNAPHASH_EFORMAT, "gzip: CRC-32 or ISIZE mismatch");
+        at += h + next;
+    }
+    st.inflate_ms += kms;
+    return SNAPHASH_OK;
+}
+
+// ---- the tar side: archive/tar's reader as UnpackTar drives it ---------------------------------------------------------
+
+struct TarEntry {
+    std::string name;     // after clickVerifyContentFn (filepath.Clean)
+    std::string linkname;
+    char type = '0';
+    uint32_t mode = 0;    // permission and set-id bits
+    uint64_t size = 0;
+    uint64_t data_off = 0;
+};
+
+// Go's filepath.Clean (path/filepath, Unix)
+std::string go_clean(const std::string& p)
+{
+    if (p.empty()) return ".";
+    const bool rooted = p[0] == '/';
+    std::vector<std::string> parts;
+    size_t i = 0;
+    while (i < p.size()) {
+        size_t j = p.find('/', i);
+        if (j == std::string::npos) j = p.size();
+        const std::string e = p.substr(i, j - i);
+        i = j + 1;
+        if (e.empty() || e == ".") continue;
+        if (e == "..") {
+            if (!parts.empty() && parts.back() != "..") parts.pop_back();
+            else if (!rooted) parts.push_back("..");
+            continue;
+        }
+        parts.push_back(e);
+    }
+    std::string r = rooted ? "/" : "";
+    for (size_t k = 0; k < parts.size(); ++k) r += (k ? "/" : "") + parts[k];
+    return r.empty() ? "." : r;
+}
+
+bool tar_octal(const uint8_t* f, size_t w, uint64_t* v)
+{
+    if (f[0] & 0x80) { // base-256 (archive/tar's parseNumeric)
+        uint64_t x = f[0] & 0x7f;
+        for (size_t i = 1; i < w; ++i) { if (x >> 55) return false; x = x << 8 | f[i]; }
+        *v = x;
+        return true;
+    }
+    size_t i = 0;
+    while (i < w && (f[i] == ' ' || f[i] == 0)) ++i;
+    uint64_t x = 0;
+    for (; i < w && f[i] >= '0' && f[i] <= '7'; ++i) { if (x >> 60) return false; x = x * 8 + (f[i] - '0'); }
+    for (; i < w; ++i) if (f[i] != ' ' && f[i] != 0) return false;
+    *v = x;
+    return true;
+}
+
+std::string tar_str(const uint8_t* f, size_t w)
+{
+    size_t k = 0;
+    while (k < w && f[k]) ++k;
+    return std::string((const char*)f, k);
+}
+
+// the members of the tar stream t[0..n); SNAPHASH_EFORMAT for a stream archive/tar refuses, SNAPHASH_ECONTENT for a
+// name with ".." or a member type UnpackTar does not create
+int tar_read(const uint8_t* t, uint64_t n, std::vector<TarEntry>& ents, std::string& why)
+{
+    uint64_t at = 0;
+    std::string pax_path, pax_link, gnu_name, gnu_link;
+    bool pax_size = false;
+    uint64_t pax_sz = 0;
+    static const uint8_t zero[512] = {0};
+    for (;;) {
+        if (at == n) return 0; // (io.EOF at a record boundary)
+        if (at + 512 > n) { why = "tar: truncated header"; return SNAPHASH_EFORMAT; }
+        const uint8_t* hd = t + at;
+        if (!memcmp(hd, zero, 512)) {
+            if (at + 1024 <= n && memcmp(hd + 512, zero, 512)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
+            return 0;
+        }
+        uint64_t chk = 0;
+        if (!tar_octal(hd + 148, 8, &chk)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
+        int64_t su = 0, ss = 0;
+        for (int i = 0; i < 512; ++i) {
+            const uint8_t b = (i >= 148 && i < 156) ? ' ' : hd[i];
+            su += b;
+            ss += (int8_t)b;
+        }
+        if ((int64_t)chk != su && (int64_t)chk != ss) { why = "tar: header checksum"; return SNAPHASH_EFORMAT; }
+        uint64_t size = 0, mode = 0;
+        if (!tar_octal(hd + 124, 12, &size) || !tar_octal(hd + 100, 8, &mode)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
+        const char type = (char)hd[156];
+        if (pax_size) size = pax_sz;
+        const uint64_t data = at + 512;
+        const bool has_data = type == '0' || type == 0 || type == '7' || type == 'x' || type == 'L' || type == 'K' || type == 'g';
+        const uint64_t padded = has_data ? (size + 511) & ~(uint64_t)511 : 0; // (links, devices, directories: no content)
+        if (data + padded > n) { why = "tar: truncated member"; return SNAPHASH_EFORMAT; }
+        if (type == 'x' || type == 'L' || type == 'K') {
+            const std::string body((const char*)t + data, (size_t)size);
+            if (type == 'L') gnu_name = tar_str((const uint8_t*)body.data(), body.size());
+            else if (type == 'K') gnu_link = tar_str((const uint8_t*)body.data(), body.size());
+            else { // records "<len> <key>=<value>\n" (archive/tar parsePAX)
+                size_t p = 0;
+                while (p < body.size()) {
+                    size_t sp = body.find(' ', p);
+                    if (sp == std::string::npos) { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
+                    const uint64_t len = strtoull(body.substr(p, sp - p).c_str(), nullptr, 10);
+                    if (len < sp - p + 3 || p + len > body.size() || body[p + len - 1] != '\n') { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
+                    const std::string kv = body.substr(sp + 1, p + len - 1 - (sp + 1));
+                    const size_t eq = kv.find('=');
+                    if (eq == std::string::npos) { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
+                    const std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
+                    if (k == "path") pax_path = v;
+                    else if (k == "linkpath") pax_link = v;
+                    else if (k == "size") { pax_size = true; pax_sz = strtoull(v.c_str(), nullptr, 10); }
+                    p += len;
+                }
+            }
+            at = data + padded;
+            continue;
+        }
+        TarEntry e;
+        std::string name = tar_str(hd, 100);
+        if (!memcmp(hd + 257, "ustar", 5)) {
+            const std::string prefix = tar_str(hd + 345, 155);
+            if (!prefix.empty()) name = prefix + "/" + name;
+        }
+        if (!gnu_name.empty()) name = gnu_name;
+        if (!pax_path.empty()) name = pax_path;
+        e.linkname = tar_str(hd + 157, 100);
+        if (!gnu_link.empty()) e.linkname = gnu_link;
+        if (!pax_link.empty()) e.linkname = pax_link;
+        pax_path.clear(); pax_link.clear(); gnu_name.clear(); gnu_link.clear();
+        pax_size = false;
+        e.name = go_clean(name);
+        if (e.name.find("..") != std::string::npos) { why = "tar: " + name + ": invalid content"; return SNAPHASH_ECONTENT; }
+        e.type = type == 0 || type == '7' ? '0' : type;
+        if (e.type != '0' && e.type != '2' && e.type != '5') { why = "tar: " + name + ": unsupported member type"; return SNAPHASH_ECONTENT; }
+        e.mode = (uint32_t)(mode & 07777);
+        e.size = e.type == '0' ? size : 0;
+        e.data_off = data;
+        ents.push_back(e);
+        at = data + padded;
+    }
+}
+
+int mkdir_all(const std::string& dir)
+{
+    struct stat s;
+    if (stat(dir.c_str(), &s) == 0) return S_ISDIR(s.st_mode) ? 0 : ENOTDIR;
+    const size_t sl = dir.find_last_of('/');
+    if (sl != std::string::npos && sl > 0) {
+        const int e = mkdir_all(dir.substr(0, sl));
+        if (e) return e;
+    }
+    if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) return errno;
+    return 0;
+}
+
+// UnpackTar's loop: the members of the decoded stream into target (helpers.go:106-142)
+int unpack_members(DevCtx* c, const std::vector<TarEntry>& ents, const uint8_t* tar, const std::string& target)
+{
+    for (const TarEntry& e : ents) {
+        const std::string path = go_clean(target + "/" + e.name);
+        const size_t sl = path.find_last_of('/');
+        const std::string dir = sl == std::string::npos ? "." : (sl == 0 ? "/" : path.substr(0, sl));
+        if (int er = mkdir_all(dir)) return fail(c, SNAPHASH_EIO, dir + ": " + strerror(er));
+        if (e.type == '5') {
+            (void)mkdir(path.c_str(), e.mode); // (an error here is ignored, as in the reference)
+        } else if (e.type == '2') {
+            if (symlink(e.linkname.c_str(), path.c_str()) != 0) return fail(c, SNAPHASH_EIO, path + ": " + strerror(errno));
+        } else {
+            const int fd = open(path.c_str(), O_WRONLY | O_TRUNC | O_CREAT | O_CLOEXEC, e.mode);
+            if (fd < 0) return fail(c, SNAPHASH_EIO, path + ": " + strerror(errno));
+            uint64_t off = 0;
+            while (off < e.size) {
+                const ssize_t w = write(fd, tar + e.data_off + off, (size_t)std::min<uint64_t>(e.size - off, 1u << 30));
+                if (w < 0) {
+                    if (errno == EINTR) continue;
+                    const int er = errno;
+                    close(fd);
+                    return fail(c, SNAPHASH_EIO, path + ": " + strerror(er));
+                }
+                off += (uint64_t)w;
+            }
+            if (close(fd) != 0) return fail(c, SNAPHASH_EIO, path + ": " + strerror(errno));
+        }
+    }
+    return SNAPHASH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int snaphash_gunzip_buffer(snaphash_ctx* x, const void* gz, size_t n, void** out, size_t* out_len)
+try {
+    if (!x || (!gz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *out = nullptr;
+    *out_len = 0;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    snaphash_unpack_stats st{};
+    st.struct_size = sizeof st;
+    st.gz_bytes = n;
+    std::vector<uint8_t> o;
+    const int rc = gunzip_engine(x, c, (const uint8_t*)gz, n, o, false, st);
+    c->ev_used = 0;
+    st.tar_bytes = o.size();
+    st.wall_ms = now_ms() - t_top0_;
+    x->unpack = st;
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(o.size() ? o.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    if (!o.empty()) memcpy(p, o.data(), o.size());
+    *out = p;
+    *out_len = o.size();
+    return SNAPHASH_OK;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_unpack(snaphash_ctx* x, const char* data_tar_gz, const char* target_dir, const char* yaml, size_t yaml_len,
+                        snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!x || !data_tar_gz || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    snaphash_unpack_stats st{};
+    st.struct_size = sizeof st;
+    // the archive, read once
+    std::vector<uint8_t> gz;
+    {
+        const int fd = open(data_tar_gz, O_RDONLY | O_CLOEXEC);
+        if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(data_tar_gz) + ": " + strerror(errno));
+        struct stat sb;
+        if (fstat(fd, &sb) != 0) { const int er = errno; close(fd); return fail(x, SNAPHASH_EIO, strerror(er)); }
+        gz.resize((size_t)sb.st_size);
+        size_t got = 0;
+        while (got < gz.size()) {
+            const ssize_t r = pread(fd, gz.data() + got, gz.size() - got, (off_t)got);
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) { const int er = r < 0 ? errno : EIO; close(fd); return fail(x, SNAPHASH_EIO, std::string(data_tar_gz) + ": " + strerror(er)); }
+            got += (size_t)r;
+        }
+        close(fd);
+    }
+    st.gz_bytes = gz.size();
+    // the archive digest over the compressed bytes, on a host core beside the decode
+    uint8_t adig[64];
+    std::thread dig_th([&] {
+        HostSha s;
+        host_sha512_init(s);
+        host_sha512_update(s, gz.data(), gz.size());
+        host_sha512_final(s, adig);
+    });
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{dig_th};
+    std::vector<uint8_t> tar;
+    const bool want_verify = yaml != nullptr;
+    int rc = gunzip_engine(x, c, gz.data(), gz.size(), tar, want_verify, st);
+    c->ev_used = 0;
+    st.tar_bytes = tar.size();
+    std::vector<TarEntry> ents;
+    std::string why;
+    if (!rc) {
+        rc = tar_read(tar.data(), tar.size(), ents, why);
+        if (rc) rc = fail(c, rc, why);
+    }
+    st.members = ents.size();
+    if (!rc) rc = unpack_members(c, ents, tar.data(), target_dir);
+    dig_th.join();
+    if (archive_digest) memcpy(archive_digest, adig, 64);
+    if (rc) {
+        st.wall_ms = now_ms() - t_top0_;
+        x->unpack = st;
+        end_top(x, t_top0_);
+        return lift(x, c, rc);
+    }
+    if (want_verify) {
+        // the regular members' digests out of the decoded stream: the last member of a name is what is on disk
+        std::unordered_map<std::string, size_t> last;
+        for (size_t k = 0; k < ents.size(); ++k) last[ents[k].name] = k;
+        std::vector<size_t> reg; // members hashed
+        for (const auto& kv : last)
+            if (ents[kv.second].type == '0') reg.push_back(kv.second);
+        std::sort(reg.begin(), reg.end());
+        std::vector<uint8_t> dig(reg.size() * 64 + 64);
+        std::vector<uint8_t> on_host(reg.size(), 0);
+        // long members on host threads, as the producer plans them (targz.inc); SNAPHASH_FLAG_GPU_ONLY: all on the kernels
+        MemberHashers mh;
+        std::vector<size_t> hosted;
+        if (!x->gpu_only && !reg.empty()) {
+            const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
+            const double pass_s = std::max(0.008, (double)tar.size() / 4.5e9);
+            const uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s);
+            std::vector<uint64_t> sizes;
+            for (size_t q = 0; q < reg.size(); ++q)
+                if (long_from == 0 || ents[reg[q]].size > long_from) { on_host[q] = 1; hosted.push_back(q); sizes.push_back(ents[reg[q]].size); }
+            if (!hosted.empty()) {
+                mh.start(sizes, std::max(1u, std::min(6u, cpus / 3u)));
+                std::vector<MemberHashers::Task> ts;
+                for (size_t h = 0; h < hosted.size(); ++h) {
+                    const TarEntry& e = ents[reg[hosted[h]]];
+                    ts.push_back(MemberHashers::Task{(uint32_t)h, tar.data() + e.data_off, e.size, true, true, 0});
+                }
+                mh.give_all(ts);
+            }
+        }
+        std::vector<uint64_t> offs, lens;
+        std::vector<size_t> dev_q;
+        for (size_t q = 0; q < reg.size(); ++q)
+            if (!on_host[q]) { offs.push_back(ents[reg[q]].data_off); lens.push_back(ents[reg[q]].size); dev_q.push_back(q); }
+        if (!dev_q.empty()) {
+            uint8_t* d_dig = nullptr;
+            HIP_TRY(c, hipMalloc((void**)&d_dig, dev_q.size() * 64));
+            struct DevFree { uint8_t* p; ~DevFree() { if (p) (void)hipFree(p); } } dfree{d_dig};
+            rc = snaphash_sha512_device(x, c->d_fout, offs.data(), lens.data(), dev_q.size(), d_dig);
+            if (!rc) rc = snaphash_sync(x);
+            std::vector<uint8_t> hd(dev_q.size() * 64);
+            if (!rc && hipMemcpy(hd.data(), d_dig, hd.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(x, SNAPHASH_EDEVICE, "D2H of digests failed");
+            if (rc) return rc;
+            for (size_t k = 0; k < dev_q.size(); ++k) memcpy(dig.data() + 64 * dev_q[k], hd.data() + 64 * k, 64);
+        }
+        if (!hosted.empty()) {
+            mh.wait_all();
+            mh.stop();
+            for (size_t h = 0; h < hosted.size(); ++h) memcpy(dig.data() + 64 * hosted[h], mh.digests.data() + 64 * h, 64);
+        }
+        std::unordered_map<std::string, size_t> dig_of;
+        for (size_t q = 0; q < reg.size(); ++q) dig_of[ents[reg[q]].name] = q;
+        // Verify's own comparison on the unpacked tree (its walk is Lstat only: the modes as they are on disk); a record
+        // whose bytes came from the archive takes their digest, anything else there was before is hashed from disk
+        rc = verify_impl(x, target_dir, data_tar_gz, adig, yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
+            const auto it = dig_of.find(r.name);
+            if (it == dig_of.end() || (int64_t)ents[reg[it->second]].size != r.size) return false;
+            memcpy(d, dig.data() + 64 * it->second, 64);
+            return true;
+        });
+    }
+    st.wall_ms = now_ms() - t_top0_;
+    x->unpack = st;
+    end_top(x, t_top0_);
+    return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_get_unpack_stats(const snaphash_ctx* x, snaphash_unpack_stats* out)
+{
+    if (!x || !out || out->struct_size < sizeof(snaphash_unpack_stats)) return SNAPHASH_EINVAL;
+    *out = x->unpack;
+    out->struct_size = sizeof(snaphash_unpack_stats);
+    return SNAPHASH_OK;
+}
+
+} // extern "C"
+
+static void free_inflate(DevCtx* c) { free_inflate_bufs(c); }
