@@ -63,8 +63,8 @@ enum {
     SNAPHASH_ENAME = -6,    /* file name outside the plain-scalar set the YAML emitter reproduces */
     SNAPHASH_EPARSE = -7,   /* hashes.yaml text not understood */
     SNAPHASH_EMISMATCH = -8, /* snaphash_verify: tree differs from hashes.yaml */
-    SNAPHASH_EFORMAT = -9,   /* not a valid gzip, DEFLATE or tar stream, or a CRC-32 / ISIZE mismatch */
-    SNAPHASH_ECONTENT = -10  /* snaphash_tar_unpack: a member name with "..", or a member type it does not unpack */
+    SNAPHASH_EFORMAT = -9,   /* not a valid gzip, DEFLATE, bzip2 or tar stream, or a CRC-32 / ISIZE mismatch */
+    SNAPHASH_ECONTENT = -10  /* snaphash_tar_unpack(_bz2): a member name with "..", or a member type it does not unpack */
 };
 
 enum { /* snaphash_config.kernel */
@@ -316,16 +316,20 @@ void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out
 
 /* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
 
-typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack */
+typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack, or of the
+                                        * bzip2 calls (snaphash_bunzip2_buffer / snaphash_tar_unpack_bz2), where the fields
+                                        * mean what the comment after each one's semicolon says */
     uint32_t struct_size;   /* in: sizeof(snaphash_unpack_stats) */
     uint32_t reserved;
-    uint64_t gz_bytes;      /* compressed input */
+    uint64_t gz_bytes;      /* compressed input (bzip2: the same) */
     uint64_t tar_bytes;     /* decoded output */
     uint64_t members;       /* tar members (0 for snaphash_gunzip_buffer) */
-    uint64_t segments;      /* stretches the stream was decoded in: linked GPU segments + host stretches */
-    uint64_t gpu_segments;  /* of those, decoded by the inflate kernel */
-    uint64_t host_bytes;    /* output bytes the host decoder produced (stretches without flush points, gaps) */
-    double inflate_ms;      /* inflate kernels (scan, decode, fill, concat), HIP events */
+    uint64_t segments;      /* stretches the stream was decoded in: linked GPU segments + host stretches (bzip2: blocks) */
+    uint64_t gpu_segments;  /* of those, decoded by the inflate kernel (bzip2: blocks the bzip2 kernels decoded) */
+    uint64_t host_bytes;    /* output bytes the host decoder produced (stretches without flush points, gaps; bzip2: the
+                               blocks decoded on host threads) */
+    double inflate_ms;      /* inflate kernels (scan, decode, fill, concat), HIP events (bzip2: the decode kernels --
+                               scan, symbols, inverse BWT, RLE1) */
     double wall_ms;
 } snaphash_unpack_stats;
 
@@ -352,6 +356,22 @@ int snaphash_tar_unpack(snaphash_ctx *ctx, const char *data_tar_gz, const char *
                         snaphash_mismatch *first, uint8_t *archive_digest);
 /* out->struct_size in; SNAPHASH_EINVAL if it is smaller than the ABI 5 struct. */
 int snaphash_get_unpack_stats(const snaphash_ctx *ctx, snaphash_unpack_stats *out);
+
+/* ---- the install side for data.tar.bz2 (skipToArMember's ".bz2" branch, clickdeb/deb.go:408-441) ----------------- */
+
+/* Every stream of bz[0..n) ("BZh" + level 1-9; concatenated streams read one after another, pbzip2's output among
+ * them), every block CRC and each stream's combined CRC checked.  *out is malloc'd (snaphash_free).  bzip2 blocks need
+ * nothing from each other: they are decoded side by side -- on host threads in the default configuration (measured
+ * faster than one core of libbz2), by the GPU bzip2 kernels under SNAPHASH_FLAG_GPU_ONLY (block scan,
+ * Huffman + MTF decode, inverse BWT, RLE1 undo), any block the kernels give up on by the host decoder.
+ * SNAPHASH_EFORMAT, as Go's compress/bzip2 refuses them: not a bzip2 stream, n == 0, a block or combined CRC mismatch,
+ * the randomised bit set, origPtr out of range, a block longer than its level allows, trailing bytes that are not
+ * another stream. */
+int snaphash_bunzip2_buffer(snaphash_ctx *ctx, const void *bz, size_t n, void **out, size_t *out_len);
+/* snaphash_tar_unpack for a data.tar.bz2: the same UnpackTar rules, errors and in-pass Verify, from the bzip2-decoded
+ * stream; archive_digest (may be NULL): the 64 raw bytes of SHA-512(data_tar_bz2). */
+int snaphash_tar_unpack_bz2(snaphash_ctx *ctx, const char *data_tar_bz2, const char *target_dir, const char *yaml,
+                            size_t yaml_len, snaphash_mismatch *first, uint8_t *archive_digest);
 
 /* ---- neighbouring scan: helpers.FilesAreEqual / DirUpdated -------- */
 

@@ -40,6 +40,8 @@ EXPORTS = [
     "snaphash_calib_observe", "snaphash_calib_apply", "snaphash_get_calib",
     # the install side (row f5)
     "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats",
+    # data.tar.bz2
+    "snaphash_bunzip2_buffer", "snaphash_tar_unpack_bz2",
 ]
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
 
@@ -195,6 +197,8 @@ def lib():
     L.snaphash_gunzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_get_unpack_stats.argtypes = [vp, ctypes.POINTER(UnpackStats)]
+    L.snaphash_bunzip2_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_unpack_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -420,6 +424,28 @@ class Context:
         dig = ctypes.create_string_buffer(64)
         rc = lib().snaphash_tar_unpack(self._h, os.fsencode(data_tar_gz), os.fsencode(target_dir), yaml_bytes,
                                        len(yaml_bytes) if yaml_bytes is not None else 0, ctypes.byref(m), dig)
+        if rc == EMISMATCH:
+            return (m.kind, m.name.decode(errors="replace")), dig.raw
+        self._check(rc)
+        return None, dig.raw
+
+    def bunzip2_buffer(self, bz):
+        """Every stream of `bz` (bzip2) decoded, blocks side by side (host threads, or the GPU kernels with FLAG_GPU_ONLY)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        bz = bytes(bz)
+        self._check(lib().snaphash_bunzip2_buffer(self._h, ctypes.cast(ctypes.c_char_p(bz), ctypes.c_void_p), len(bz),
+                                                  ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def tar_unpack_bz2(self, data_tar_bz2, target_dir, yaml_bytes=None):
+        """tar_unpack for a data.tar.bz2.  -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
+        m = Mismatch()
+        dig = ctypes.create_string_buffer(64)
+        rc = lib().snaphash_tar_unpack_bz2(self._h, os.fsencode(data_tar_bz2), os.fsencode(target_dir), yaml_bytes,
+                                           len(yaml_bytes) if yaml_bytes is not None else 0, ctypes.byref(m), dig)
         if rc == EMISMATCH:
             return (m.kind, m.name.decode(errors="replace")), dig.raw
         self._check(rc)

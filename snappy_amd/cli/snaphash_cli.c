@@ -10,6 +10,8 @@
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
  *   snaphash [options] gunzip IN.gz OUT          the inverse: every member decoded (GPU inflate)
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
+ *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
+ *   snaphash [options] unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML]
  *                                      ClickDeb.Unpack (clickdeb/deb.go:188-203) into DIR; with HASHES_YAML also the
  *                                      install-time Verify from the decoded bytes; exit 1 on mismatch
  *   snaphash [options] cmp A B [A B ...]         helpers.FilesAreEqual per pair; exit 1 if any pair differs
@@ -36,7 +38,8 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
-                    "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
+                    "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
+                    "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
                     "       -z DEPTH: effort of `build` / `gzip` (hash-chain links per position; default 96 = gzip -9's bytes, 32 = gzip -6's)\n");
@@ -182,37 +185,39 @@ int main(int argc, char **argv)
         }
         snaphash_free(z);
         free(in);
-    } else if (!strcmp(argv[1], "gunzip") && argc == 4) {
+    } else if ((!strcmp(argv[1], "gunzip") || !strcmp(argv[1], "bunzip2")) && argc == 4) {
+        const int bz = !strcmp(argv[1], "bunzip2");
         size_t len = 0, ol = 0;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *o = NULL;
-        rc = snaphash_gunzip_buffer(c, in, len, &o, &ol);
-        if (rc) ret = die(c, rc, "gunzip");
+        rc = bz ? snaphash_bunzip2_buffer(c, in, len, &o, &ol) : snaphash_gunzip_buffer(c, in, len, &o, &ol);
+        if (rc) ret = die(c, rc, argv[1]);
         else {
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(o, 1, ol, f) != ol || fclose(f)) { perror(argv[3]); ret = 2; }
         }
         snaphash_free(o);
         free(in);
-    } else if (!strcmp(argv[1], "unpack") && (argc == 4 || argc == 5)) {
+    } else if ((!strcmp(argv[1], "unpack") || !strcmp(argv[1], "unpack-bz2")) && (argc == 4 || argc == 5)) {
+        const int bz = !strcmp(argv[1], "unpack-bz2");
         size_t len = 0;
         char *y = NULL;
         if (argc == 5 && !(y = slurp(argv[4], &len))) { snaphash_destroy(c); return 2; }
         snaphash_mismatch m;
         uint8_t dig[64];
-        rc = snaphash_tar_unpack(c, argv[2], argv[3], y, len, &m, dig);
-        if (rc) ret = die(c, rc, "unpack");
+        rc = bz ? snaphash_tar_unpack_bz2(c, argv[2], argv[3], y, len, &m, dig) : snaphash_tar_unpack(c, argv[2], argv[3], y, len, &m, dig);
+        if (rc) ret = die(c, rc, argv[1]);
         else printf("OK\n");
         if (show_stats) {
             snaphash_unpack_stats us;
             us.struct_size = sizeof us;
             if (!snaphash_get_unpack_stats(c, &us))
-                fprintf(stderr, "unpack: %llu gz bytes -> %llu tar bytes, %llu members, %llu segments (%llu on the GPU), %llu bytes decoded on "
-                                "the host, inflate kernels %.2f ms, wall %.2f ms\n",
-                        (unsigned long long)us.gz_bytes, (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
-                        (unsigned long long)us.segments, (unsigned long long)us.gpu_segments, (unsigned long long)us.host_bytes,
-                        us.inflate_ms, us.wall_ms);
+                fprintf(stderr, "%s: %llu %s bytes -> %llu tar bytes, %llu members, %llu %s (%llu on the GPU), %llu bytes decoded on "
+                                "the host, %s kernels %.2f ms, wall %.2f ms\n",
+                        argv[1], (unsigned long long)us.gz_bytes, bz ? "bz2" : "gz", (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
+                        (unsigned long long)us.segments, bz ? "blocks" : "segments", (unsigned long long)us.gpu_segments,
+                        (unsigned long long)us.host_bytes, bz ? "bzip2" : "inflate", us.inflate_ms, us.wall_ms);
         }
         free(y);
     } else if (!strcmp(argv[1], "cmp") && argc >= 4 && argc % 2 == 0) {

@@ -41,6 +41,8 @@
 #include "hostfill.h"
 #include "hostpass.h"
 #include "hostsha.h"
+#include "bzip2_host.h"
+#include "bzip2_kernels.h"
 #include "inflate_host.h"
 #include "inflate_kernels.h"
 #include "member_hashers.h"
@@ -164,6 +166,24 @@ struct DevCtx {
     uint8_t* d_fwin = nullptr;
     uint8_t* d_fout = nullptr;
     uint64_t fout_cap = 0;
+
+    // GPU bzip2 scratch (unbz2.inc): the compressed piece and its candidates, the candidates' slots (BWT bytes, then the
+    // inverse BWT's output), the T vectors, the RLE1 chunk states, the symbol stage's results and the linked blocks
+    uint8_t* d_bin = nullptr;
+    uint64_t bin_cap = 0;
+    uint64_t* d_bcand = nullptr; // the candidates (the count lives in d_bcount)
+    uint64_t* h_bcand = nullptr; // pinned
+    uint32_t* d_bcount = nullptr;
+    uint32_t* h_bcount = nullptr; // pinned
+    uint64_t bcand_cap = 0;
+    uint8_t* d_bslots = nullptr;
+    uint32_t* d_btt = nullptr;
+    uint64_t* d_bchunks = nullptr;
+    BzBlockRes* d_bres = nullptr;
+    BzBlockRes* h_bres = nullptr; // pinned
+    BzGpuBlock* d_bblk = nullptr;
+    BzGpuBlock* h_bblk = nullptr; // pinned
+    uint32_t bslots_cap = 0;
 
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;
@@ -2581,6 +2601,7 @@ void snaphash_batch_abort(snaphash_batch* b)
 
 #include "targz.inc"
 #include "unpack.inc"
+#include "unbz2.inc"
 
 // ---- helpers.FilesAreEqual / DirUpdated (row f4) ----------------------------------------------
 

@@ -1,0 +1,357 @@
+// unbz2.inc -- the data.tar.bz2 side of the install path, textually part of snaphash_api.cpp (after unpack.inc, whose
+// tar reader, member writer and Verify tail it shares).
+//
+// The reference's ClickDeb.Unpack takes data.tar.{gz,bz2,xz} (clickdeb/deb.go:185); skipToArMember (deb.go:408-441)
+// reads the .bz2 member with Go's compress/bzip2, in-process on one core.  Here a bzip2 stream is decoded block by block
+// side by side -- on host threads in the default configuration, by the GPU kernels (bzip2_kernels.hip) under
+// SNAPHASH_FLAG_GPU_ONLY -- and the decoded stream goes through the same unpack and in-pass Verify as data.tar.gz.
+
+namespace {
+
+void free_bzip2_bufs(DevCtx* c)
+{
+    if (c->d_bin) (void)hipFree(c->d_bin);
+    if (c->d_bcand) (void)hipFree(c->d_bcand);
+    if (c->h_bcand) (void)hipHostFree(c->h_bcand);
+    if (c->d_bcount) (void)hipFree(c->d_bcount);
+    if (c->h_bcount) (void)hipHostFree(c->h_bcount);
+    if (c->d_bslots) (void)hipFree(c->d_bslots);
+    if (c->d_btt) (void)hipFree(c->d_btt);
+    if (c->d_bchunks) (void)hipFree(c->d_bchunks);
+    if (c->d_bres) (void)hipFree(c->d_bres);
+    if (c->h_bres) (void)hipHostFree(c->h_bres);
+    if (c->d_bblk) (void)hipFree(c->d_bblk);
+    if (c->h_bblk) (void)hipHostFree(c->h_bblk);
+    c->d_bin = nullptr; c->d_bcand = nullptr; c->h_bcand = nullptr; c->d_bcount = nullptr; c->h_bcount = nullptr;
+    c->d_bslots = nullptr; c->d_btt = nullptr; c->d_bchunks = nullptr; c->d_bres = nullptr; c->h_bres = nullptr;
+    c->d_bblk = nullptr; c->h_bblk = nullptr;
+    c->bin_cap = 0; c->bcand_cap = 0; c->bslots_cap = 0;
+}
+
+// A launch's slots hold the BWT bytes (then the inverse BWT's output), the T vector and the RLE1 chunk states of one
+// block each: 4.5 MB.  kBzLaunchSlots of them (1.2 GB) bound the scratch whatever the input; a larger input takes more
+// launches.  The piece (compressed bytes a launch's candidates come from) is at most the staging size, 64 MiB.
+constexpr uint32_t kBzLaunchSlots = 256;
+
+int ensure_bzip2_try(DevCtx* c, uint64_t piece, uint32_t slots)
+{
+    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    if (!c->d_bcount) HIP_TRY(c, hipMalloc((void**)&c->d_bcount, 16));
+    if (!c->h_bcount) HIP_TRY(c, host_alloc(c, (void**)&c->h_bcount, 16));
+    if (c->bin_cap < piece) {
+        if (c->d_bin) (void)hipFree(c->d_bin);
+        if (c->d_bcand) (void)hipFree(c->d_bcand);
+        if (c->h_bcand) (void)hipHostFree(c->h_bcand);
+        c->d_bin = nullptr; c->d_bcand = nullptr; c->h_bcand = nullptr; c->bin_cap = 0; c->bcand_cap = 0;
+        const uint64_t cand = bz_candidate_cap(piece);
+        HIP_TRY(c, hipMalloc((void**)&c->d_bin, piece + 16));
+        HIP_TRY(c, hipMalloc((void**)&c->d_bcand, cand * 8));
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_bcand, cand * 8));
+        c->bin_cap = piece;
+        c->bcand_cap = cand;
+    }
+    if (c->bslots_cap < slots) {
+        if (c->d_bslots) (void)hipFree(c->d_bslots);
+        if (c->d_btt) (void)hipFree(c->d_btt);
+        if (c->d_bchunks) (void)hipFree(c->d_bchunks);
+        if (c->d_bres) (void)hipFree(c->d_bres);
+        if (c->h_bres) (void)hipHostFree(c->h_bres);
+        if (c->d_bblk) (void)hipFree(c->d_bblk);
+        if (c->h_bblk) (void)hipHostFree(c->h_bblk);
+        c->d_bslots = nullptr; c->d_btt = nullptr; c->d_bchunks = nullptr; c->d_bres = nullptr; c->h_bres = nullptr;
+        c->d_bblk = nullptr; c->h_bblk = nullptr; c->bslots_cap = 0;
+        HIP_TRY(c, hipMalloc((void**)&c->d_bslots, (size_t)slots * kBzMaxBlock));
+        HIP_TRY(c, hipMalloc((void**)&c->d_btt, (size_t)slots * kBzMaxBlock * 4));
+        HIP_TRY(c, hipMalloc((void**)&c->d_bchunks, (size_t)slots * kBzChunks * 8));
+        HIP_TRY(c, hipMalloc((void**)&c->d_bres, (size_t)slots * sizeof(BzBlockRes)));
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_bres, (size_t)slots * sizeof(BzBlockRes)));
+        HIP_TRY(c, hipMalloc((void**)&c->d_bblk, (size_t)slots * sizeof(BzGpuBlock)));
+        HIP_TRY(c, host_alloc(c, (void**)&c->h_bblk, (size_t)slots * sizeof(BzGpuBlock)));
+        c->bslots_cap = slots;
+    }
+    return SNAPHASH_OK;
+}
+
+// the scratch of a job, sized for it; on any allocation failure none is left behind
+int ensure_bzip2(DevCtx* c, uint64_t piece, uint32_t slots)
+{
+    const int rc = ensure_bzip2_try(c, piece, slots);
+    if (rc) free_bzip2_bufs(c);
+    return rc;
+}
+
+#define BZ_TRY(expr) HIP_TRY(c, (expr))
+
+// The later stages of the nb linked blocks in c->h_bblk (their stored CRCs in crcs): the inverse BWT and the RLE1 count,
+// the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->d_fout (after the decoded
+// stream so far when keep_dev), the bytes back to out, and every block's CRC checked on host threads, one block each
+// (bz_crc_block runs at about 0.4 GB/s a core: the host threads keep pace with the kernels; DESIGN.md sec. 15).
+int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uint32_t>& crcs, std::vector<uint8_t>& out, bool keep_dev,
+                  snaphash_unpack_stats& st, float& kms)
+{
+    auto timed = [&](EventPair* ev) {
+        float ms = 0;
+        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
+    };
+    BZ_TRY(hipMemcpyAsync(c->d_bblk, c->h_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    EventPair* ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    BZ_TRY(hipEventRecord(ev->a, c->f_stream));
+    BZ_TRY(launch_bz_ibwt(c->d_bslots, c->d_btt, c->d_bblk, nb, c->f_stream));
+    BZ_TRY(launch_bz_rle1_count(c->d_bslots, c->d_bblk, c->d_bchunks, nb, c->f_stream));
+    BZ_TRY(hipEventRecord(ev->b, c->f_stream));
+    BZ_TRY(hipMemcpyAsync(c->h_bblk, c->d_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
+    BZ_TRY(hipStreamSynchronize(c->f_stream));
+    timed(ev);
+    const size_t o0 = out.size();
+    const uint64_t base = keep_dev ? o0 : 0;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        // (the inverse BWT of a valid block is one cycle through every position: anything else is a corrupt block)
+        if (c->h_bblk[i].status != kBzOk) return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt block (inverse BWT)");
+        c->h_bblk[i].out_off = base + total;
+        total += c->h_bblk[i].out_len;
+    }
+    int rc = ensure_fout(c, base + total, keep_dev ? o0 : 0);
+    if (rc) return rc;
+    BZ_TRY(hipMemcpyAsync(c->d_bblk, c->h_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    BZ_TRY(hipEventRecord(ev->a, c->f_stream));
+    BZ_TRY(launch_bz_rle1_write(c->d_bslots, c->d_bblk, c->d_bchunks, nb, c->d_fout, c->f_stream));
+    BZ_TRY(hipEventRecord(ev->b, c->f_stream));
+    out.resize(o0 + total);
+    BZ_TRY(hipMemcpyAsync(out.data() + o0, c->d_fout + base, total, hipMemcpyDeviceToHost, c->f_stream));
+    BZ_TRY(hipStreamSynchronize(c->f_stream));
+    timed(ev);
+    std::atomic<uint32_t> next{0}, bad{0};
+    auto work = [&]() {
+        for (;;) {
+            const uint32_t i = next.fetch_add(1);
+            if (i >= nb) return;
+            const BzGpuBlock& B = c->h_bblk[i];
+            if (bz_crc_block(out.data() + o0 + (B.out_off - base), B.out_len) != crcs[i]) bad.store(1);
+        }
+    };
+    {
+        const unsigned T = (unsigned)std::min<uint64_t>(nb, std::max(1u, x->cpus_call ? x->cpus_call : x->cpus));
+        ThreadJoiner th;
+        for (unsigned k = 1; k < T; ++k) th.spawn(work);
+        work();
+        th.join_all();
+    }
+    if (bad.load()) return fail(c, SNAPHASH_EFORMAT, "bzip2: block CRC mismatch");
+    st.segments += nb;
+    st.gpu_segments += nb;
+    c->ev_used = 0;
+    return SNAPHASH_OK;
+}
+
+// Decodes every stream of bz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
+// c->d_fout[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
+int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
+                   snaphash_unpack_stats& st)
+{
+    if (n == 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: empty stream");
+    const unsigned cpus = std::max(1u, x->cpus_call ? x->cpus_call : x->cpus);
+    const size_t o_start = out.size();
+    auto to_dev = [&](size_t from) -> int { // host-decoded bytes out[from..) into c->d_fout at the same offset
+        if (!keep_dev || out.size() <= from) return SNAPHASH_OK;
+        if (!c->f_stream) BZ_TRY(hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+        int e = ensure_fout(c, out.size(), from);
+        if (e) return e;
+        BZ_TRY(hipMemcpyAsync(c->d_fout + from, out.data() + from, out.size() - from, hipMemcpyHostToDevice, c->f_stream));
+        BZ_TRY(hipStreamSynchronize(c->f_stream));
+        return SNAPHASH_OK;
+    };
+    if (!x->gpu_only && cpus >= 2) {
+        // the default configuration: the blocks on host threads wherever two cores are there to take them (measured
+        // 7.5-11x one core of libbz2 with 16 cores, the kernels 2.6-5.7x: DESIGN.md sec. 15); on one core the kernels,
+        // which beat it; SNAPHASH_FLAG_GPU_ONLY sends every linked block through the kernels
+        uint64_t blocks = 0;
+        if (bzip2_host_threads(bz, n, out, cpus, &blocks)) {
+            out.resize(o_start);
+            return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt stream");
+        }
+        st.segments += blocks;
+        st.host_bytes += out.size() - o_start;
+        return to_dev(o_start);
+    }
+    BzCursor cur;
+    cur.in = bz;
+    cur.n = n;
+    if (bz_cursor_stream(cur, 0)) return fail(c, SNAPHASH_EFORMAT, "bzip2: not a bzip2 stream");
+    const uint64_t P = std::min<uint64_t>(std::max<uint64_t>(c->staging, 4u << 20), 64ull << 20);
+    int rc = ensure_bzip2(c, std::min<uint64_t>(P, n), 8);
+    if (rc) return rc;
+    std::unique_ptr<BzScratch> hs; // the host decoder's, for a block the kernels do not take
+    float kms = 0;
+    auto timed = [&](EventPair* ev) {
+        float ms = 0;
+        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
+    };
+    auto host_block = [&]() -> int { // the block at cur.bit by the host decoder
+        if (!hs) hs.reset(new BzScratch);
+        const size_t o0 = out.size();
+        const BzBlockRes r = bz_block_host(bz, n, cur.bit, cur.level * 100000u, *hs, out);
+        if (r.status != kBzOk) return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt block");
+        bz_cursor_take(cur, r.end_bit, r.crc);
+        st.segments++;
+        st.host_bytes += out.size() - o0;
+        return to_dev(o0);
+    };
+    bool chain_order = false; // more candidates than the cap: one block a launch, in chain order
+    for (;;) {
+        int k = bz_cursor_next(cur);
+        if (k < 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: bad stream framing or combined CRC");
+        if (k == 0) break;
+        // a piece: the compressed bytes from the byte that holds the next block's first bit
+        const uint64_t pb = cur.bit >> 3;
+        const uint64_t pn = std::min<uint64_t>(chain_order ? std::min<uint64_t>(P, 4u << 20) : P, n - pb);
+        BZ_TRY(hipMemcpyAsync(c->d_bin, bz + pb, pn, hipMemcpyHostToDevice, c->f_stream));
+        std::vector<uint64_t> cand;
+        if (!chain_order) {
+            BZ_TRY(hipMemsetAsync(c->d_bcount, 0, 4, c->f_stream));
+            EventPair* ev = next_events(c, 2);
+            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            BZ_TRY(hipEventRecord(ev->a, c->f_stream));
+            BZ_TRY(launch_bz_scan(c->d_bin, pn, c->d_bcand, c->d_bcount, (uint32_t)c->bcand_cap, c->f_stream));
+            BZ_TRY(hipEventRecord(ev->b, c->f_stream));
+            BZ_TRY(hipMemcpyAsync(c->h_bcount, c->d_bcount, 4, hipMemcpyDeviceToHost, c->f_stream));
+            BZ_TRY(hipStreamSynchronize(c->f_stream));
+            timed(ev);
+            if (c->h_bcount[0] > c->bcand_cap) {
+                chain_order = true;
+            } else if (c->h_bcount[0]) {
+                BZ_TRY(hipMemcpyAsync(c->h_bcand, c->d_bcand, (size_t)c->h_bcount[0] * 8, hipMemcpyDeviceToHost, c->f_stream));
+                BZ_TRY(hipStreamSynchronize(c->f_stream));
+                cand.assign(c->h_bcand, c->h_bcand + c->h_bcount[0]);
+                std::sort(cand.begin(), cand.end());
+            }
+        }
+        const uint64_t rel0 = cur.bit - pb * 8;
+        if (chain_order) cand.assign(1, rel0);
+        size_t idx = (size_t)(std::lower_bound(cand.begin(), cand.end(), rel0) - cand.begin());
+        if (idx == cand.size() || cand[idx] != rel0) { // (the chain's block is no candidate: cannot happen below the cap)
+            rc = host_block();
+            if (rc) return rc;
+            continue;
+        }
+        bool piece_done = false, finished = false;
+        while (!piece_done && !finished) {
+            // the symbol stage of the next launch's candidates, from the one the chain is at
+            const uint32_t K = (uint32_t)std::min<size_t>(cand.size() - idx, kBzLaunchSlots);
+            rc = ensure_bzip2(c, std::min<uint64_t>(P, n), std::max<uint32_t>(K, 8));
+            if (rc) return rc;
+            memcpy(c->h_bcand, cand.data() + idx, (size_t)K * 8);
+            BZ_TRY(hipMemcpyAsync(c->d_bcand, c->h_bcand, (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
+            EventPair* ev = next_events(c, 2);
+            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            BZ_TRY(hipEventRecord(ev->a, c->f_stream));
+            BZ_TRY(launch_bz_symbols(c->d_bin, pn, c->d_bcand, K, c->d_bslots, c->d_bres, c->f_stream));
+            BZ_TRY(hipEventRecord(ev->b, c->f_stream));
+            BZ_TRY(hipMemcpyAsync(c->h_bres, c->d_bres, (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
+            BZ_TRY(hipStreamSynchronize(c->f_stream));
+            timed(ev);
+            const uint64_t* lc = cand.data() + idx;
+            for (;;) { // link what this launch decoded, then run the linked blocks through the later stages
+                uint32_t nb = 0;
+                std::vector<uint32_t> crcs;
+                bool host_next = false;
+                for (;;) {
+                    k = bz_cursor_next(cur);
+                    if (k < 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: bad stream framing or combined CRC");
+                    if (k == 0) { finished = true; break; }
+                    const uint64_t rel = cur.bit - pb * 8;
+                    const uint64_t* it = std::lower_bound(lc, lc + K, rel);
+                    if (cur.bit < pb * 8 || it == lc + K || *it != rel) { // past this launch: the next launch or piece
+                        const size_t at = (size_t)(std::lower_bound(cand.begin(), cand.end(), rel) - cand.begin());
+                        if (cur.bit >= pb * 8 && at < cand.size() && cand[at] == rel) idx = at;
+                        else piece_done = true;
+                        break;
+                    }
+                    const uint32_t j = (uint32_t)(it - lc);
+                    const BzBlockRes& r = c->h_bres[j];
+                    if (r.status != kBzOk || r.n > cur.level * 100000u) {
+                        // a block the piece cuts off starts the next piece; anything else is the host decoder's
+                        if (r.status == kBzTruncated && pb + pn < n && rel > 7) { piece_done = true; break; }
+                        host_next = true;
+                        break;
+                    }
+                    BzGpuBlock& B = c->h_bblk[nb++];
+                    B.out_off = 0; B.out_len = 0; B.slot = j; B.n = r.n; B.orig_ptr = r.orig_ptr; B.status = kBzOk;
+                    crcs.push_back(r.crc);
+                    bz_cursor_take(cur, r.end_bit + pb * 8, r.crc);
+                }
+                if (nb) {
+                    rc = bunzip2_batch(x, c, nb, crcs, out, keep_dev, st, kms);
+                    if (rc) return rc;
+                }
+                if (!host_next) break;
+                rc = host_block();
+                if (rc) return rc;
+            }
+            if (!finished && !piece_done && idx >= cand.size()) piece_done = true;
+        }
+        if (finished) break;
+    }
+    c->ev_used = 0;
+    st.inflate_ms += kms;
+    return SNAPHASH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int snaphash_bunzip2_buffer(snaphash_ctx* x, const void* bz, size_t n, void** out, size_t* out_len)
+try {
+    if (!x || (!bz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *out = nullptr;
+    *out_len = 0;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    snaphash_unpack_stats st{};
+    st.struct_size = sizeof st;
+    st.gz_bytes = n;
+    std::vector<uint8_t> o;
+    const int rc = bunzip2_engine(x, c, (const uint8_t*)bz, n, o, false, st);
+    c->ev_used = 0;
+    st.tar_bytes = o.size();
+    st.wall_ms = now_ms() - t_top0_;
+    x->unpack = st;
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(o.size() ? o.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    if (!o.empty()) memcpy(p, o.data(), o.size());
+    *out = p;
+    *out_len = o.size();
+    return SNAPHASH_OK;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_unpack_bz2(snaphash_ctx* x, const char* data_tar_bz2, const char* target_dir, const char* yaml, size_t yaml_len,
+                            snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!x || !data_tar_bz2 || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    return tar_unpack_common(x, c, t_top0_, data_tar_bz2, target_dir, yaml, yaml_len, first, archive_digest,
+                             [&](const uint8_t* bz, size_t n, std::vector<uint8_t>& tar, bool keep_dev, snaphash_unpack_stats& st) {
+                                 return bunzip2_engine(x, c, bz, n, tar, keep_dev, st);
+                             });
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+} // extern "C"
+
+static void free_inflate(DevCtx* c)
+{
+    free_inflate_bufs(c);
+    free_bzip2_bufs(c);
+}

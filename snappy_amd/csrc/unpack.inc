@@ -536,53 +536,21 @@ int unpack_members(DevCtx* c, const std::vector<TarEntry>& ents, const uint8_t* 
     return SNAPHASH_OK;
 }
 
-} // namespace
+// ClickDeb.Unpack after the choice of decoder, for both data-member formats: the archive read once, its digest on a host
+// core beside the decode, `decode` into the tar stream (kept in c->d_fout too when hashes.yaml asks for Verify), then
+// tar_read, unpack_members, the members' digests (host / GPU split) and verify_impl.
+using UnpackDecode = std::function<int(const uint8_t*, size_t, std::vector<uint8_t>&, bool, snaphash_unpack_stats&)>;
 
-extern "C" {
-
-int snaphash_gunzip_buffer(snaphash_ctx* x, const void* gz, size_t n, void** out, size_t* out_len)
-try {
-    if (!x || (!gz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    *out = nullptr;
-    *out_len = 0;
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    snaphash_unpack_stats st{};
-    st.struct_size = sizeof st;
-    st.gz_bytes = n;
-    std::vector<uint8_t> o;
-    const int rc = gunzip_engine(x, c, (const uint8_t*)gz, n, o, false, st);
-    c->ev_used = 0;
-    st.tar_bytes = o.size();
-    st.wall_ms = now_ms() - t_top0_;
-    x->unpack = st;
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(o.size() ? o.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    if (!o.empty()) memcpy(p, o.data(), o.size());
-    *out = p;
-    *out_len = o.size();
-    return SNAPHASH_OK;
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
-}
-
-int snaphash_tar_unpack(snaphash_ctx* x, const char* data_tar_gz, const char* target_dir, const char* yaml, size_t yaml_len,
-                        snaphash_mismatch* first, uint8_t* archive_digest)
-try {
-    if (!x || !data_tar_gz || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
+int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* archive, const char* target_dir, const char* yaml,
+                      size_t yaml_len, snaphash_mismatch* first, uint8_t* archive_digest, const UnpackDecode& decode)
+{
     snaphash_unpack_stats st{};
     st.struct_size = sizeof st;
     // the archive, read once
-    std::vector<uint8_t> gz;
+    std::vector<uint8_t> gz; // (the compressed archive)
     {
-        const int fd = open(data_tar_gz, O_RDONLY | O_CLOEXEC);
-        if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(data_tar_gz) + ": " + strerror(errno));
+        const int fd = open(archive, O_RDONLY | O_CLOEXEC);
+        if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(archive) + ": " + strerror(errno));
         struct stat sb;
         if (fstat(fd, &sb) != 0) { const int er = errno; close(fd); return fail(x, SNAPHASH_EIO, strerror(er)); }
         gz.resize((size_t)sb.st_size);
@@ -590,7 +558,7 @@ try {
         while (got < gz.size()) {
             const ssize_t r = pread(fd, gz.data() + got, gz.size() - got, (off_t)got);
             if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) { const int er = r < 0 ? errno : EIO; close(fd); return fail(x, SNAPHASH_EIO, std::string(data_tar_gz) + ": " + strerror(er)); }
+            if (r <= 0) { const int er = r < 0 ? errno : EIO; close(fd); return fail(x, SNAPHASH_EIO, std::string(archive) + ": " + strerror(er)); }
             got += (size_t)r;
         }
         close(fd);
@@ -607,7 +575,7 @@ try {
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{dig_th};
     std::vector<uint8_t> tar;
     const bool want_verify = yaml != nullptr;
-    int rc = gunzip_engine(x, c, gz.data(), gz.size(), tar, want_verify, st);
+    int rc = decode(gz.data(), gz.size(), tar, want_verify, st);
     c->ev_used = 0;
     st.tar_bytes = tar.size();
     std::vector<TarEntry> ents;
@@ -680,7 +648,7 @@ try {
         for (size_t q = 0; q < reg.size(); ++q) dig_of[ents[reg[q]].name] = q;
         // Verify's own comparison on the unpacked tree (its walk is Lstat only: the modes as they are on disk); a record
         // whose bytes came from the archive takes their digest, anything else there was before is hashed from disk
-        rc = verify_impl(x, target_dir, data_tar_gz, adig, yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
+        rc = verify_impl(x, target_dir, archive, adig, yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
             const auto it = dig_of.find(r.name);
             if (it == dig_of.end() || (int64_t)ents[reg[it->second]].size != r.size) return false;
             memcpy(d, dig.data() + 64 * it->second, 64);
@@ -691,6 +659,52 @@ try {
     x->unpack = st;
     end_top(x, t_top0_);
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int snaphash_gunzip_buffer(snaphash_ctx* x, const void* gz, size_t n, void** out, size_t* out_len)
+try {
+    if (!x || (!gz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *out = nullptr;
+    *out_len = 0;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    snaphash_unpack_stats st{};
+    st.struct_size = sizeof st;
+    st.gz_bytes = n;
+    std::vector<uint8_t> o;
+    const int rc = gunzip_engine(x, c, (const uint8_t*)gz, n, o, false, st);
+    c->ev_used = 0;
+    st.tar_bytes = o.size();
+    st.wall_ms = now_ms() - t_top0_;
+    x->unpack = st;
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(o.size() ? o.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    if (!o.empty()) memcpy(p, o.data(), o.size());
+    *out = p;
+    *out_len = o.size();
+    return SNAPHASH_OK;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_unpack(snaphash_ctx* x, const char* data_tar_gz, const char* target_dir, const char* yaml, size_t yaml_len,
+                        snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!x || !data_tar_gz || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    return tar_unpack_common(x, c, t_top0_, data_tar_gz, target_dir, yaml, yaml_len, first, archive_digest,
+                             [&](const uint8_t* gz, size_t n, std::vector<uint8_t>& tar, bool keep_dev, snaphash_unpack_stats& st) {
+                                 return gunzip_engine(x, c, gz, n, tar, keep_dev, st);
+                             });
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -704,5 +718,3 @@ int snaphash_get_unpack_stats(const snaphash_ctx* x, snaphash_unpack_stats* out)
 }
 
 } // extern "C"
-
-static void free_inflate(DevCtx* c) { free_inflate_bufs(c); }

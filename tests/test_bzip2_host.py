@@ -1,0 +1,260 @@
+"""data.tar.bz2 on the CPU: the bzip2 decoder (snappy_amd/csrc/bzip2_core.h, bzip2_host.cpp) checked against Python's
+bz2 (libbz2) -- every level, RLE1 at its edges, concatenated streams -- its block-parallel form on host threads against
+the serial decode, the block scan, and the rules that make a stream SNAPHASH_EFORMAT (those of Go's compress/bzip2).
+The GPU kernels that run the same routines are checked in tests/test_gpu_bunzip2.py."""
+import bz2
+import ctypes
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+HARNESS = os.path.join(ROOT, "tests", "bzip2_host_harness.cpp")
+EFORMAT = -9
+BLOCK_MAGIC = 0x314159265359
+
+
+@pytest.fixture(scope="module")
+def bh(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("bh") / "libbzip2host.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
+    L = ctypes.CDLL(so)
+    P = ctypes.POINTER
+    L.bh_serial.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_int), P(ctypes.c_uint64)]
+    L.bh_serial.restype = ctypes.c_void_p
+    L.bh_threads.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint, P(ctypes.c_size_t), P(ctypes.c_int), P(ctypes.c_uint64)]
+    L.bh_threads.restype = ctypes.c_void_p
+    L.bh_link.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_uint, P(ctypes.c_size_t),
+                          P(ctypes.c_int)]
+    L.bh_link.restype = ctypes.c_void_p
+    L.bh_candidates.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, P(ctypes.c_uint64)]
+    L.bh_candidates.restype = ctypes.c_uint64
+    L.bh_chain.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_uint64), ctypes.c_size_t]
+    L.bh_chain.restype = ctypes.c_int64
+    L.bh_crc.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    L.bh_crc.restype = ctypes.c_uint32
+    L.bh_free.argtypes = [ctypes.c_void_p]
+    return L
+
+
+def _take(L, p, n):
+    b = ctypes.string_at(p, n)
+    L.bh_free(p)
+    return b
+
+
+def serial(L, z):
+    n, rc, b = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_uint64()
+    out = _take(L, L.bh_serial(z, len(z), ctypes.byref(n), ctypes.byref(rc), ctypes.byref(b)), n.value)
+    return rc.value, out
+
+
+def threads(L, z, t=4):
+    n, rc, b = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_uint64()
+    out = _take(L, L.bh_threads(z, len(z), t, ctypes.byref(n), ctypes.byref(rc), ctypes.byref(b)), n.value)
+    return rc.value, out
+
+
+def link(L, z, cand, t=3):
+    arr = (ctypes.c_uint64 * max(len(cand), 1))(*cand)
+    n, rc = ctypes.c_size_t(), ctypes.c_int()
+    out = _take(L, L.bh_link(z, len(z), arr, len(cand), t, ctypes.byref(n), ctypes.byref(rc)), n.value)
+    return rc.value, out
+
+
+def candidates(L, z, cap=1 << 16):
+    arr = (ctypes.c_uint64 * cap)()
+    total = L.bh_candidates(z, len(z), cap, arr)
+    return total, list(arr[: min(total, cap)])
+
+
+def chain(L, z):
+    arr = (ctypes.c_uint64 * 4096)()
+    k = L.bh_chain(z, len(z), arr, 4096)
+    assert k >= 0, k
+    return list(arr[:k])
+
+
+def both(L, z):
+    """The serial decode and the threaded one must agree; returns (rc, out)."""
+    a, b = serial(L, z), threads(L, z)
+    assert a[0] == b[0] and (a[0] != 0 or a[1] == b[1])
+    return a
+
+
+def text(n, seed=0):
+    rng = np.random.default_rng(seed)
+    words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 9)), dtype=np.uint8)) for _ in range(1500)]
+    base = b" ".join(words[int(i)] for i in rng.integers(0, 1500, size=n // 5 + 10))
+    return base[:n]
+
+
+def test_empty_and_one_byte(bh):
+    for d in (b"", b"x", b"\0"):
+        for lv in (1, 9):
+            assert both(bh, bz2.compress(d, lv)) == (0, d)
+
+
+def test_every_level_and_every_byte_value(bh):
+    d = text(400000, 1) + bytes(range(256)) * 40 + bytes(range(255, -1, -1)) * 7
+    for lv in range(1, 10):
+        assert both(bh, bz2.compress(d, lv)) == (0, d), lv
+
+
+def test_rle1_edges(bh):
+    r = random.Random(3)
+    for k in (1, 2, 3, 4, 5, 6, 7, 8, 9, 255, 256, 257, 258, 259, 260, 1000, 4096):
+        for v in (0, 0x41, 0xff):
+            d = bytes([v]) * k
+            assert both(bh, bz2.compress(d, 9)) == (0, d), (k, v)
+            d2 = b"ab" + bytes([v]) * k + b"c" + bytes([v ^ 1]) * (k + 1)
+            assert both(bh, bz2.compress(d2, 1)) == (0, d2), (k, v)
+    parts = []
+    for _ in range(3000):
+        parts.append(bytes([r.randrange(4)]) * r.choice([1, 2, 3, 4, 5, 8, 250, 259, 300]))
+    d = b"".join(parts)
+    for lv in (1, 9):
+        assert both(bh, bz2.compress(d, lv)) == (0, d)
+
+
+def test_random_text_and_zeros(bh):
+    rnd = np.random.default_rng(5).integers(0, 256, size=1 << 20, dtype=np.uint8).tobytes()
+    t = text(3 << 20, 6)
+    for d in (rnd, t):
+        for lv in (1, 9):
+            assert both(bh, bz2.compress(d, lv)) == (0, d)
+    # one block of near-maximal expansion: 43 MiB of zeros are ~885k RLE1 symbols, 51x
+    z = bytes(43 << 20)
+    c = bz2.compress(z, 9)
+    rc, out = threads(bh, c, 4)
+    assert rc == 0 and out == z
+    assert len(chain(bh, c)) == 1
+
+
+def test_concatenated_streams_of_different_levels(bh):
+    a, b, c = text(250000, 7), bytes(range(256)) * 900, text(1300000, 8)
+    z = bz2.compress(a, 1) + bz2.compress(b, 5) + bz2.compress(c, 9)
+    assert bz2.decompress(z) == a + b + c
+    assert both(bh, z) == (0, a + b + c)
+    assert both(bh, bz2.compress(b"", 3) + bz2.compress(a, 2)) == (0, a)
+
+
+def test_block_starts_are_among_the_candidates_at_odd_bits(bh):
+    d = text(6 << 20, 9)
+    z = bz2.compress(d, 1)
+    starts = chain(bh, z)
+    assert len(starts) >= 50
+    total, cand = candidates(bh, z)
+    assert total == len(cand) and set(starts) <= set(cand)
+    assert any(s % 8 for s in starts), "every block start byte aligned: the bit scan is not exercised"
+    for s in cand:  # every candidate is the magic at that bit
+        word = int.from_bytes(z[s // 8: s // 8 + 8].ljust(8, b"\0"), "big")
+        assert (word << (s % 8) & (1 << 64) - 1) >> 16 == BLOCK_MAGIC
+
+
+def test_linking_with_false_candidates(bh):
+    d = text(3 << 20, 10)
+    z = bz2.compress(d, 2)
+    starts = chain(bh, z)
+    r = random.Random(12)
+    false = sorted(set(r.randrange(32, len(z) * 8 - 64) for _ in range(300)) - set(starts))
+    for cand in (sorted(starts + false), sorted(starts[::2] + false[:40]), []):
+        rc, out = link(bh, z, cand, r.choice([2, 4]))
+        assert rc == 0 and out == d
+
+
+def _set_bits(z, bit, width, value):
+    b = bytearray(z)
+    for k in range(width):
+        pos = bit + k
+        v = (value >> (width - 1 - k)) & 1
+        if v:
+            b[pos // 8] |= 0x80 >> (pos % 8)
+        else:
+            b[pos // 8] &= ~(0x80 >> (pos % 8)) & 0xff
+    return bytes(b)
+
+
+def _eos_bit(z):
+    v = int.from_bytes(z, "big")
+    for bit in range(len(z) * 8 - 80, len(z) * 8 - 96, -1):
+        if (v >> (len(z) * 8 - bit - 48)) & ((1 << 48) - 1) == 0x177245385090:
+            return bit
+    raise AssertionError("no end-of-stream magic")
+
+
+def test_malformed_streams_are_eformat(bh):
+    d = text(300000, 13)
+    z = bz2.compress(d, 9)
+    assert both(bh, b"")[0] == EFORMAT
+    for cut in (1, 3, 4, 5, 10, 20, 100, len(z) // 2, len(z) - 11, len(z) - 10, len(z) - 5, len(z) - 1):
+        assert both(bh, z[:cut])[0] == EFORMAT, cut
+    assert both(bh, b"BZh0" + z[4:])[0] == EFORMAT
+    assert both(bh, b"BZhA" + z[4:])[0] == EFORMAT
+    assert both(bh, z + b"junk")[0] == EFORMAT
+    assert both(bh, z + b"\0")[0] == EFORMAT
+    assert both(bh, z + b"BZh")[0] == EFORMAT
+    # the first block starts at bit 32: magic 48, CRC 32, randomised 1, origPtr 24
+    rand = _set_bits(z, 32 + 48 + 32, 1, 1)
+    assert both(bh, rand)[0] == EFORMAT
+    assert both(bh, _set_bits(z, 32 + 48 + 33, 24, 300000))[0] == EFORMAT  # origPtr >= the block's symbol count
+    assert both(bh, _set_bits(z, 32 + 48, 32, 0x12345678))[0] == EFORMAT   # block CRC
+    eos = _eos_bit(z)  # combined CRC: the 32 bits after the end-of-stream magic
+    assert both(bh, _set_bits(z, eos + 48, 32, 0x12345678))[0] == EFORMAT
+    # a block longer than its level allows: a level-9 block relabelled as level 1
+    assert both(bh, b"BZh1" + z[4:])[0] == EFORMAT
+
+
+def test_single_bit_flips_are_caught(bh):
+    d = text(120000, 14)
+    z = bz2.compress(d, 9)
+    r = random.Random(15)
+    for _ in range(400):
+        bit = r.randrange(0, len(z) * 8)
+        m = bytearray(z)
+        m[bit // 8] ^= 0x80 >> (bit % 8)
+        rc, out = both(bh, bytes(m))
+        assert rc in (0, EFORMAT)
+        if rc == 0:  # (a flip in the padding bits: the stream is still what libbz2 reads)
+            assert out == d and bz2.decompress(bytes(m)) == d
+
+
+def test_planted_magics_past_the_cap(bh):
+    d = text(2 << 20, 16)
+    z = bz2.compress(d, 1)
+    magic = BLOCK_MAGIC.to_bytes(6, "big")
+    planted = z + magic * 200000  # more magics than the candidate cap of the whole input
+    total, _ = candidates(bh, planted, 16)
+    assert total > len(planted) // 32 + 64
+    assert both(bh, planted)[0] == EFORMAT
+    mid = len(z) // 2
+    inside = z[:mid] + magic * 100000 + z[mid:]
+    assert both(bh, inside)[0] == EFORMAT
+    assert both(bh, z) == (0, d)
+
+
+def test_crc_is_crc32_bzip2(bh):
+    # bzip2's CRC is the MSB-first one: its value for "123456789" is the CRC-32/BZIP2 check value
+    assert bh.bh_crc(b"123456789", 9) == 0xFC891918
+
+
+def test_bzip2_host_code_under_asan_and_ubsan(bh, tmp_path):
+    exe = str(tmp_path / "bh_fuzz")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DBH_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-o", exe, HARNESS, "-pthread"])
+    d = text(40000, 17) + bytes(range(256)) * 20 + bytes(3000)
+    z = bz2.compress(d[:30000], 1) + bz2.compress(d, 9)
+    f = tmp_path / "in.bz2"
+    f.write_bytes(z)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([exe, str(f), "3000", "7"], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-4000:]
+    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    planted = tmp_path / "planted.bz2"
+    planted.write_bytes(z + BLOCK_MAGIC.to_bytes(6, "big") * 5000)
+    out = subprocess.run([exe, str(planted), "40", "8"], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-4000:]
