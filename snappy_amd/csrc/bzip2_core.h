@@ -9,6 +9,8 @@
 //   bz_block_symbols  the header (CRC, origPtr, used-byte map, Huffman tables, selectors) and the Huffman + RUNA/RUNB +
 //                     MTF decode into the block's BWT bytes (and their 256 counts)
 //   bz_ibwt           the inverse Burrows-Wheeler transform (the T vector by a counting sort, then the walk from origPtr)
+//   bz_samples ..     the same walk split at sampled positions, as the kernels run it in parallel (the sample geometry,
+//   bz_sample_write   one piece's walk, the link of the pieces through origPtr, one piece's output)
 //   bz_rle1_step      one byte of the undo of the initial run-length stage (four equal bytes, then a count 0-255)
 //   bz_crc_*          bzip2's CRC-32 (MSB first, not reflected), over a block's output after RLE1 is undone
 //
@@ -300,6 +302,90 @@ BZ_HD void bz_ibwt(const uint8_t* bwt, uint32_t n, const uint32_t* counts, uint3
         const uint32_t e = tt[p];
         out[k] = (uint8_t)e;
         p = e >> 8;
+    }
+}
+
+// The same walk split at sampled positions, the way the kernels run it (bz_ibwt_kernel; tests/bzip2_host_harness.cpp
+// runs these helpers serially).  The samples are the multiples of `stride` plus origPtr; tt[j] is bz_ibwt's entry with
+// kBzMark set on every sampled j.  Each sample's piece runs from it to the next sample; the pieces from origPtr's
+// sample around to it again are the cycle of the permutation through origPtr, L steps.  That cycle need not pass every
+// position: a block that is exactly periodic after RLE1 (u^k, k >= 2; "aa", 255 * m zero bytes) gives k cycles, each
+// spelling u.  bz_ibwt's n steps from origPtr go round the cycle, so out[k] = out[k % L] -- also when L does not divide
+// n, as for a corrupt block whose CRC then refuses it (libbz2 and Go walk the same way).
+constexpr uint32_t kBzWalkers = 2048;       // sampled positions at the multiples of stride (1024 lanes, two each)
+constexpr uint32_t kBzMark = 0x80000000u;   // a sampled position (tt's spare top bit)
+constexpr uint32_t kBzIdx = 0xfffffu;       // tt[j] >> 8: a position < kBzMaxBlock < 2^20
+constexpr uint32_t kBzNoPiece = ~0u;        // the offset of a sample off origPtr's cycle (it writes nothing)
+
+struct BzSamples {
+    uint32_t n, op;
+    uint32_t stride; // ceil(n / kBzWalkers)
+    uint32_t ns;     // samples at 0, stride, 2 stride, ... < n
+    uint32_t extra;  // 1 when origPtr is no multiple of stride: sample ns
+    uint32_t nsamp;  // ns + extra <= kBzWalkers + 1
+};
+
+BZ_HD BzSamples bz_samples(uint32_t n, uint32_t op) // n >= 1
+{
+    BzSamples g;
+    g.n = n;
+    g.op = op;
+    g.stride = (n + kBzWalkers - 1) / kBzWalkers;
+    g.ns = (n + g.stride - 1) / g.stride;
+    g.extra = op % g.stride ? 1u : 0u;
+    g.nsamp = g.ns + g.extra;
+    return g;
+}
+BZ_HD bool bz_is_sample(const BzSamples& g, uint32_t j) { return j % g.stride == 0 || j == g.op; }
+BZ_HD uint32_t bz_sample_pos(const BzSamples& g, uint32_t s) { return s < g.ns ? s * g.stride : g.op; }
+BZ_HD uint32_t bz_sample_id(const BzSamples& g, uint32_t q) { return (q == g.op && g.extra) ? g.ns : q / g.stride; } // q a sample
+
+// Sample s's piece: its length in steps (~0u: the walk left [0, n) or ran n steps without meeting a sample), and the
+// id of the sample it ends at into *next.
+BZ_HD uint32_t bz_sample_walk(const BzSamples& g, const uint32_t* tt, uint32_t s, uint32_t* next)
+{
+    uint32_t q = bz_sample_pos(g, s), v = tt[q], len = 0;
+    for (;;) {
+        q = (v >> 8) & kBzIdx;
+        if (q >= g.n || len >= g.n) {
+            *next = 0;
+            return ~0u;
+        }
+        v = tt[q];
+        ++len;
+        if (v & kBzMark) break;
+    }
+    *next = bz_sample_id(g, q);
+    return len;
+}
+
+// Links the pieces from origPtr's sample until the walk is back at it: soff[s] is each piece's offset in the output, or
+// kBzNoPiece for a sample off that cycle.  Returns the cycle's length L (1 <= L <= n), or 0 when a piece is broken or
+// the links do not come back (neither happens for a T vector built by the counting sort: it is a permutation).
+BZ_HD uint32_t bz_link_samples(const BzSamples& g, const uint32_t* slen, const uint32_t* snext, uint32_t* soff)
+{
+    for (uint32_t s = 0; s < g.nsamp; ++s) soff[s] = kBzNoPiece;
+    const uint32_t s0 = bz_sample_id(g, g.op);
+    uint32_t s = s0;
+    uint64_t off = 0;
+    do {
+        if (s >= g.nsamp || slen[s] == ~0u || soff[s] != kBzNoPiece) return 0;
+        soff[s] = (uint32_t)off;
+        off += slen[s];
+        if (off > g.n) return 0;
+        s = snext[s];
+    } while (s != s0);
+    return (uint32_t)off;
+}
+
+// Sample s's piece written at out[0..len) (out: the output at the piece's offset).
+BZ_HD void bz_sample_write(const BzSamples& g, const uint32_t* tt, uint32_t s, uint32_t len, uint8_t* out)
+{
+    uint32_t q = bz_sample_pos(g, s), v = tt[q];
+    for (uint32_t k = 0; k < len; ++k) {
+        q = (v >> 8) & kBzIdx;
+        v = tt[q];
+        out[k] = (uint8_t)v;
     }
 }
 

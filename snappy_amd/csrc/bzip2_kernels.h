@@ -18,7 +18,6 @@ struct BzGpuBlock {
     int32_t status;
 };
 
-constexpr uint32_t kBzWalkers = 2048; // sampled positions the inverse BWT's walk is split at (1024 lanes, two each)
 constexpr uint32_t kBzChunks = 1024;  // RLE1 chunks of a block at most (one lane each)
 
 // Bit offsets of every block magic in d_in[0..n), appended unordered to d_cand; *d_count counts them all, at most cap
@@ -29,7 +28,8 @@ hipError_t launch_bz_scan(const uint8_t* d_in, uint64_t n, uint64_t* d_cand, uin
 hipError_t launch_bz_symbols(const uint8_t* d_in, uint64_t n, const uint64_t* d_starts, uint32_t count, uint8_t* d_slots,
                              BzBlockRes* d_res, hipStream_t s);
 // The inverse BWT of each block, 1024 lanes each: the T vector into d_tt (kBzMaxBlock words a slot) by a stable counting
-// sort, then the walk from origPtr split at kBzWalkers sampled positions; the output replaces the BWT bytes in the slot.
+// sort, then the walk from origPtr split at kBzWalkers sampled positions (bzip2_core.h); the output replaces the BWT
+// bytes in the slot.  The status is kBzBad only for a walk that breaks, which a T vector built by the sort cannot do.
 hipError_t launch_bz_ibwt(uint8_t* d_slots, uint32_t* d_tt, BzGpuBlock* d_blocks, uint32_t count, hipStream_t s);
 // RLE1, first pass: every chunk of every block run from each of the five entry states, the chunks linked; out_len of
 // each block and each chunk's entry state and output offset (d_chunks, kBzChunks a slot).

@@ -8,9 +8,11 @@
 //            out, a block that fails goes to the host decoder
 //   ibwt     1024 lanes a linked block: the byte histogram per wave, a prefix, a stable scatter (a wave ranks equal
 //            bytes among its 64 lanes with eight ballots) into the T vector; then the permutation walk from origPtr
-//            split at 2048 sampled positions -- each lane walks from its samples to the next marked position, lane 0
-//            links the pieces, and the walk runs again writing at the known offsets.  One walker would take n dependent
-//            loads of a 3.6 MB vector; here each takes about n / 2048
+//            split at 2048 sampled positions (bzip2_core.h's bz_samples .. bz_sample_write) -- each lane walks from
+//            its samples to the next marked position, lane 0 links the pieces of the cycle through origPtr, and the walk
+//            runs again writing them at the known offsets.  One walker would take n dependent loads of a 3.6 MB vector;
+//            here each takes about n / 2048.  A block that is periodic after RLE1 (u^k) has k cycles: the one through
+//            origPtr spells u, and the n-step walk repeats it, so its L bytes are copied on to fill the block
 //   rle1     1024 chunks a block: each chunk run from every one of the five entry states of the RLE1 undo, the chunks
 //            linked by lane 0, the block sizes prefix-summed on the host, then every chunk writes at its final offset.
 // Integer work with data-dependent control flow: no MFMA.
@@ -23,9 +25,6 @@
 namespace snaphash {
 
 namespace {
-
-constexpr uint32_t kMark = 0x80000000u; // a sampled position of the walk (tt's spare top bit)
-constexpr uint32_t kIdx = 0xfffffu;     // tt[j] >> 8: a position < kBzMaxBlock < 2^20
 
 __global__ void __launch_bounds__(256) bz_scan_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t* cand, uint32_t* count, uint32_t cap)
 {
@@ -56,7 +55,7 @@ __global__ void __launch_bounds__(1024) bz_ibwt_kernel(uint8_t* slots, uint32_t*
 {
     __shared__ uint32_t hist[16][256];
     __shared__ uint32_t slen[kBzWalkers + 1], snext[kBzWalkers + 1], soff[kBzWalkers + 1];
-    __shared__ int32_t ok;
+    __shared__ uint32_t cyc;
     BzGpuBlock& B = blocks[blockIdx.x];
     const uint32_t n = B.n, op = B.orig_ptr;
     if (n == 0 || n > kBzMaxBlock || op >= n) { // (the host links no such block)
@@ -116,54 +115,24 @@ __global__ void __launch_bounds__(1024) bz_ibwt_kernel(uint8_t* slots, uint32_t*
     }
     __syncthreads();
     // each position's own byte in the low bits, the sampled positions marked
-    const uint32_t stride = (n + kBzWalkers - 1) / kBzWalkers;
-    const uint32_t ns = (n + stride - 1) / stride; // samples at the multiples of stride ...
-    const uint32_t extra = op % stride ? 1u : 0u;   // ... and origPtr, where the output starts
-    const uint32_t nsamp = ns + extra;
-    for (uint32_t j = tid; j < n; j += 1024) tt[j] |= bwt[j] | ((j % stride == 0 || j == op) ? kMark : 0u);
+    const BzSamples g = bz_samples(n, op);
+    for (uint32_t j = tid; j < n; j += 1024) tt[j] |= bwt[j] | (bz_is_sample(g, j) ? kBzMark : 0u);
     __syncthreads();
-    auto sample_pos = [&](uint32_t s) { return s < ns ? s * stride : op; };
-    auto sample_id = [&](uint32_t q) { return (q == op && extra) ? ns : q / stride; };
-    for (uint32_t s = tid; s < nsamp; s += 1024) {
-        uint32_t q = sample_pos(s), v = tt[q], len = 0;
-        for (;;) {
-            q = (v >> 8) & kIdx;
-            if (q >= n || len >= n) { len = ~0u; break; }
-            v = tt[q];
-            ++len;
-            if (v & kMark) break;
-        }
-        slen[s] = len;
-        snext[s] = len == ~0u ? 0 : sample_id(q);
+    for (uint32_t s = tid; s < g.nsamp; s += 1024) slen[s] = bz_sample_walk(g, tt, s, &snext[s]);
+    __syncthreads();
+    if (tid == 0) { // the pieces of the cycle through origPtr, in walk order
+        cyc = bz_link_samples(g, slen, snext, soff);
+        B.status = cyc ? kBzOk : kBzBad;
     }
     __syncthreads();
-    if (tid == 0) { // link the pieces from origPtr's: one cycle through every sample, n steps in all
-        const uint32_t s0 = sample_id(op);
-        uint32_t s = s0, cnt = 0;
-        uint64_t off = 0;
-        bool good = true;
-        do {
-            if (slen[s] == ~0u) { good = false; break; }
-            soff[s] = (uint32_t)off;
-            off += slen[s];
-            s = snext[s];
-            ++cnt;
-        } while (s != s0 && cnt <= nsamp);
-        ok = good && s == s0 && cnt == nsamp && off == n;
-        B.status = ok ? kBzOk : kBzBad;
-    }
+    const uint32_t L = cyc;
+    if (!L) return;
+    for (uint32_t s = tid; s < g.nsamp; s += 1024)
+        if (soff[s] != kBzNoPiece) bz_sample_write(g, tt, s, slen[s], bwt + soff[s]);
+    if (L == n) return;
     __syncthreads();
-    if (!ok) return;
-    for (uint32_t s = tid; s < nsamp; s += 1024) {
-        uint32_t q = sample_pos(s), v = tt[q];
-        uint8_t* o = bwt + soff[s];
-        const uint32_t len = slen[s];
-        for (uint32_t k = 0; k < len; ++k) {
-            q = (v >> 8) & kIdx;
-            v = tt[q];
-            o[k] = (uint8_t)v;
-        }
-    }
+    // a shorter cycle (a periodic block): the n steps from origPtr go round it, so its L bytes repeat
+    for (uint32_t k = L + tid; k < n; k += 1024) bwt[k] = bwt[k % L];
 }
 
 __device__ inline uint32_t chunk_size(uint32_t n) { return max(64u, (n + kBzChunks - 1) / kBzChunks); }

@@ -107,7 +107,7 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
     const uint64_t base = keep_dev ? o0 : 0;
     uint64_t total = 0;
     for (uint32_t i = 0; i < nb; ++i) {
-        // (the inverse BWT of a valid block is one cycle through every position: anything else is a corrupt block)
+        // (a broken inverse BWT walk; a corrupt block that walks leaves it to the block CRC, as libbz2 and Go do)
         if (c->h_bblk[i].status != kBzOk) return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt block (inverse BWT)");
         c->h_bblk[i].out_off = base + total;
         total += c->h_bblk[i].out_len;

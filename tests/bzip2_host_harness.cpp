@@ -83,6 +83,58 @@ int64_t bh_chain(const uint8_t* in, size_t n, uint64_t* out, size_t cap)
 
 uint32_t bh_crc(const uint8_t* p, size_t n) { return bz_crc_block(p, n); }
 
+// The BWT bytes and origPtr of the block at `bit` (the symbol stage alone, cap kBzMaxBlock): its symbol count, or a
+// negative status.
+int64_t bh_block_bwt(const uint8_t* in, size_t n, uint64_t bit, uint8_t* bwt, uint32_t* orig_ptr)
+{
+    std::unique_ptr<BzTables> t(new BzTables);
+    const BzBlockRes r = bz_block_symbols(in, n, bit, bwt, kBzMaxBlock, nullptr, *t);
+    *orig_ptr = r.orig_ptr;
+    return r.status == kBzOk ? (int64_t)r.n : -(int64_t)r.status;
+}
+
+static void counts_of(const uint8_t* bwt, uint32_t n, uint32_t* counts)
+{
+    for (uint32_t c = 0; c < 256; ++c) counts[c] = 0;
+    for (uint32_t i = 0; i < n; ++i) counts[bwt[i]]++;
+}
+
+// bz_ibwt: the serial walk of n steps from origPtr (1 <= n <= kBzMaxBlock, orig_ptr < n)
+void bh_ibwt(const uint8_t* bwt, uint32_t n, uint32_t orig_ptr, uint8_t* out)
+{
+    uint32_t counts[256];
+    counts_of(bwt, n, counts);
+    std::vector<uint32_t> tt(n);
+    bz_ibwt(bwt, n, counts, orig_ptr, tt.data(), out);
+}
+
+// The kernels' inverse BWT (bz_ibwt_kernel) with its lanes run one after another: the T vector as bz_ibwt builds it,
+// the samples marked, every sample's piece walked, the pieces of origPtr's cycle linked and written, the cycle copied on
+// to n bytes.  Returns 0, or kBzBad where the kernel would refuse the block; *cycle: the linked cycle's length.
+int bh_ibwt_sampled(const uint8_t* bwt, uint32_t n, uint32_t orig_ptr, uint8_t* out, uint32_t* cycle)
+{
+    uint32_t cft[256];
+    counts_of(bwt, n, cft);
+    for (uint32_t c = 0, sum = 0; c < 256; ++c) {
+        const uint32_t v = cft[c];
+        cft[c] = sum;
+        sum += v;
+    }
+    std::vector<uint32_t> tt(n);
+    for (uint32_t i = 0; i < n; ++i) tt[cft[bwt[i]]++] = i << 8;
+    const BzSamples g = bz_samples(n, orig_ptr);
+    for (uint32_t j = 0; j < n; ++j) tt[j] |= bwt[j] | (bz_is_sample(g, j) ? kBzMark : 0u);
+    std::vector<uint32_t> slen(kBzWalkers + 1), snext(kBzWalkers + 1), soff(kBzWalkers + 1);
+    for (uint32_t s = 0; s < g.nsamp; ++s) slen[s] = bz_sample_walk(g, tt.data(), s, &snext[s]);
+    const uint32_t L = bz_link_samples(g, slen.data(), snext.data(), soff.data());
+    *cycle = L;
+    if (!L) return kBzBad;
+    for (uint32_t s = 0; s < g.nsamp; ++s)
+        if (soff[s] != kBzNoPiece) bz_sample_write(g, tt.data(), s, slen[s], out + soff[s]);
+    for (uint32_t k = L; k < n; ++k) out[k] = out[k % L];
+    return 0;
+}
+
 void bh_free(void* p) { free(p); }
 
 } // extern "C"

@@ -1,7 +1,9 @@
 """data.tar.bz2 on the CPU: the bzip2 decoder (snappy_amd/csrc/bzip2_core.h, bzip2_host.cpp) checked against Python's
-bz2 (libbz2) -- every level, RLE1 at its edges, concatenated streams -- its block-parallel form on host threads against
-the serial decode, the block scan, and the rules that make a stream SNAPHASH_EFORMAT (those of Go's compress/bzip2).
-The GPU kernels that run the same routines are checked in tests/test_gpu_bunzip2.py."""
+bz2 (libbz2) -- every level, RLE1 at its edges, concatenated streams, blocks that are periodic after RLE1 -- its
+block-parallel form on host threads against the serial decode, the block scan, the rules that make a stream
+SNAPHASH_EFORMAT (those of Go's compress/bzip2), and the kernels' sampled inverse BWT (bzip2_core.h's bz_samples ..
+bz_sample_write, run serially) against the serial walk.  The GPU kernels that run the same routines are checked in
+tests/test_gpu_bunzip2.py and tests/test_gpu_bzip2_edges.py."""
 import bz2
 import ctypes
 import os
@@ -38,6 +40,12 @@ def bh(tmp_path_factory):
     L.bh_crc.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     L.bh_crc.restype = ctypes.c_uint32
     L.bh_free.argtypes = [ctypes.c_void_p]
+    L.bh_block_bwt.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_char_p, P(ctypes.c_uint32)]
+    L.bh_block_bwt.restype = ctypes.c_int64
+    L.bh_ibwt.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p]
+    L.bh_ibwt.restype = None
+    L.bh_ibwt_sampled.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, P(ctypes.c_uint32)]
+    L.bh_ibwt_sampled.restype = ctypes.c_int
     return L
 
 
@@ -258,3 +266,133 @@ def test_bzip2_host_code_under_asan_and_ubsan(bh, tmp_path):
     planted.write_bytes(z + BLOCK_MAGIC.to_bytes(6, "big") * 5000)
     out = subprocess.run([exe, str(planted), "40", "8"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]
+
+
+def run_free(n, seed):
+    """n random bytes, each different from the one before: no run, so RLE1 leaves them as they are."""
+    rng = np.random.default_rng(seed)
+    return (np.cumsum(rng.integers(1, 256, size=n)) % 256).astype(np.uint8).tobytes()
+
+
+def periodic_unit(size, seed):
+    """A run-free unit u whose last byte differs from its first: u * k is run-free and has period exactly |u|."""
+    rng = np.random.default_rng(seed)
+    while True:
+        u = (np.cumsum(rng.integers(1, 256, size=size)) % 256).astype(np.uint8).tobytes()
+        if size == 1 or (u[0] != u[-1] and len(set(u)) > 1):
+            return u
+
+
+SAMPLE_NS = (1, 2, 3, 63, 64, 65, 2047, 2048, 2049, 4095, 4096, 4097, 99981, 899981)
+UNIT_SIZES = (1, 2, 3, 5, 16, 1000)
+
+
+def block_bwt(L, data, level=9):
+    """libbz2's BWT bytes and origPtr of `data`, which must be one block: the symbol stage of bz2.compress's output."""
+    z = bz2.compress(data, level)
+    bwt = ctypes.create_string_buffer(900000)
+    op = ctypes.c_uint32()
+    n = L.bh_block_bwt(z, len(z), 32, bwt, ctypes.byref(op))
+    assert n > 0 and len(chain(L, z)) == 1, n
+    return bwt.raw[:n], op.value
+
+
+def ibwt_both(L, bwt, op):
+    """(the sampled walk's status, its output, its cycle length, the serial walk's output) for (bwt, origPtr)."""
+    n = len(bwt)
+    a, b, cyc = ctypes.create_string_buffer(n), ctypes.create_string_buffer(n), ctypes.c_uint32()
+    rc = L.bh_ibwt_sampled(bwt, n, op, a, ctypes.byref(cyc))
+    L.bh_ibwt(bwt, n, op, b)
+    return rc, a.raw, cyc.value, b.raw
+
+
+def orig_ptr_classes(n, op):
+    """origPtr itself, 0, n - 1, a multiple of the kernels' sample stride and (where the stride is > 1) no multiple."""
+    stride = -(-n // 2048)
+    ns = -(-n // stride)
+    ops = {op, 0, n - 1, stride * (ns // 2)}
+    if stride > 1:
+        ops |= {stride * (ns // 3) + 1, n - 2 if (n - 2) % stride else n - 3}
+    return sorted(o for o in ops if 0 <= o < n)
+
+
+def check_sampled(L, bwt, op, cycle=None):
+    for o in orig_ptr_classes(len(bwt), op):
+        rc, got, cyc, want = ibwt_both(L, bwt, o)
+        assert rc == 0 and got == want, (len(bwt), o, cyc)
+        if cycle is not None:
+            assert cyc == cycle, (len(bwt), o, cyc, cycle)
+
+
+def test_sampled_ibwt_on_primitive_blocks(bh):
+    for n in SAMPLE_NS:
+        data = run_free(n, n)
+        bwt, op = block_bwt(bh, data)
+        assert len(bwt) == n
+        rc, got, cyc, want = ibwt_both(bh, bwt, op)
+        assert rc == 0 and got == want == data and cyc == n, (n, cyc)
+        check_sampled(bh, bwt, op, n)
+
+
+def test_sampled_ibwt_on_periodic_blocks(bh):
+    """u^k after RLE1: the permutation has k cycles of |u|, and the n steps from origPtr go round one of them k times.
+    The kernels once required one cycle through every sample and refused every such block."""
+    seen = set()
+    for size in UNIT_SIZES:
+        for n in SAMPLE_NS:  # at each n where k is an integer, else at the largest multiple of |u| below it
+            n -= n % size
+            if n // size < 2 or (size, n) in seen:
+                continue
+            u = periodic_unit(size, size * 7 + n)
+            data = u * (n // size)
+            if size == 1:  # a run: its RLE1 form is no longer u^k, but a block of one byte value is its own BWT
+                bwt, op = data, n // 3
+            else:
+                bwt, op = block_bwt(bh, data)
+                assert len(bwt) == n
+            rc, got, cyc, want = ibwt_both(bh, bwt, op)
+            assert rc == 0 and got == want == data and cyc == size, (size, n, cyc)
+            check_sampled(bh, bwt, op, size)
+            seen.add((size, n))
+    assert len(seen) >= 45
+
+
+def test_sampled_ibwt_on_arbitrary_permutations(bh):
+    """(bwt, origPtr) pairs that are the BWT of nothing: several cycles of unequal length, L need not divide n.  The
+    output is still the n-step walk (a corrupt block: its CRC refuses it)."""
+    r = random.Random(21)
+    rng = np.random.default_rng(22)
+    short = 0
+    for it in range(400):
+        n = r.choice([r.randrange(1, 70), r.randrange(1, 5000), r.randrange(2040, 4200), r.randrange(1, 300000)])
+        if it < 4:
+            n = (899981, 900000, 99981, 4097)[it]
+        bwt = rng.integers(0, r.choice([1, 2, 3, 4, 17, 256]), size=n, dtype=np.uint8).tobytes()
+        op = r.choice([0, n - 1, r.randrange(n)])
+        rc, got, cyc, want = ibwt_both(bh, bwt, op)
+        assert rc == 0 and got == want and 1 <= cyc <= n, (n, op, cyc)
+        short += cyc < n and n % cyc != 0
+    assert short >= 50, short  # many cycles whose length does not divide n
+
+
+def periodic_streams():
+    """Streams of one block each that is exactly periodic after RLE1 (tests/test_gpu_bzip2_edges.py runs them on the
+    kernels): (data, level)."""
+    out = []
+    for k in (2, 3):
+        for v in (0, 0x41, 0xff):
+            out.append((bytes([v]) * k, 9))
+    for m in (2, 3, 409, 3529, 179996):  # RLE1: b"\0\0\0\0\xfb" * m
+        out.append((bytes(255 * m), 9))
+    for size in (2, 3, 16, 1000):
+        u = periodic_unit(size, size)
+        for cap in (2048, 4096, 99981, 899981):
+            out.append((u * (cap // size), 1 if cap <= 99981 else 9))
+    return out
+
+
+def test_periodic_blocks_on_the_host(bh):
+    for data, lv in periodic_streams():
+        z = bz2.compress(data, lv)
+        assert len(chain(bh, z)) == 1, len(data)
+        assert both(bh, z) == (0, data), len(data)
