@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hashes.yaml SHA-512 pass on MI355X, BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL.  Under an outer launcher -- torch.distributed.run sets WORLD_SIZE / RANK /
      LOCAL_RANK -- this process IS a rank; without one the plain command starts its N ranks itself, as child
      processes, before anything in the parent has touched a GPU: self_launch)
@@ -18,18 +18,23 @@ The metric is "GiB/s hashed (whole node), bit-exact hashes.yaml" on the 10 000 x
        dominant kernel's algorithmic bytes over its HIP-event time against the 8 TB/s HBM-read roofline.  This rate is
        stream-count-bound and flat in N by construction; it is reported, it is not `value`.
 
-Prints ONE JSON line on rank 0.  Beside the two above:
+Prints ONE JSON line on rank 0.  A plain run does what `value` needs and no more: it lays out the tree, warms up, times
+the K steps, writes --dump-outputs and prints the line.  Beside `value` and `ms_per_step` the line of every run carries:
+  config.ranks  world size, backend, launcher and every rank's GPU by PCI bus id: N distinct GPUs, or the line says so
+  dump_outputs  with --dump-outputs DIR: what the last timed step returned (hashes.yaml, its digests and sizes) as
+                DIR/<name>.npy in float32 / float64, 64 MiB at most; the tree's bytes, names and modes are the same every run
+With --full the run then measures and checks everything else (about two minutes more at N = 1):
+  roofline, hbm_resident, ceilings  (i) above: --resident-steps launches of the HBM-resident pass
   parity        hashes.yaml of the timed path byte-identical to the oracle's (every N; at N > 1 also to the single-GPU
                 pass), and a hashlib sample
-  config.ranks  world size, backend, launcher and every rank's GPU by PCI bus id: N distinct GPUs, or the line says so
   end_to_end    buffers_sharded (host buffers -> digests, every N); N = 1 also: tree_default (the library's DEFAULT
                 configuration: the planner may give host cores a share), package, build (rows f2 + f3, with the
                 reference-shaped and the all-cores zlib baselines), breakeven (small calls against the reference's loop)
   configs       BASELINE configs 1, 3 and 5 on this GPU: HBM-resident GPU-only pass (roofline per config), the DEFAULT
                 configuration from host memory, the CPU port beside it, sampled parity vs hashlib
   cpu_baseline  the oracle (C restatement of the reference's serial loop) over the same on-disk tree on one core (every N)
-  dump_outputs  with --dump-outputs DIR: what the last timed step returned (hashes.yaml, its digests and sizes) as
-                DIR/<name>.npy in float32 / float64, 64 MiB at most; the tree's bytes, names and modes are the same every run
+  in_library_multi_gpu  N > 1: the same tree through ONE process and the C ABI's device list (tools/inlib_multigpu.py)
+  planner       every planned leg's modelled makespan beside the measured one
 """
 import argparse
 import ctypes
@@ -60,11 +65,15 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C2", choices=["C1", "C2", "C5"], help="the tree of the timed pass (BASELINE's metric: C2)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "wide", "split", "pair", "quad"])
-    ap.add_argument("--cpu-seconds", type=float, default=20.0,
-                    help="0 = skip the cpu_baseline leg (the oracle's serial pass over the whole tree, ~21 s for C2)")
-    ap.add_argument("--legs", default="auto", choices=["auto", "off", "full"],
-                    help="auto = every leg for the default C2 run at N = 1, buffers_sharded only otherwise")
-    ap.add_argument("--resident-steps", type=int, default=12, help="launches of the HBM-resident (roofline) pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything else too: the HBM-resident (roofline) pass, "
+                         "parity against hashlib and the oracle, cpu_baseline, the end_to_end legs, BASELINE configs 1/3/5 "
+                         "(N = 1) and the in-library multi-GPU pass (N > 1); without it the run times `value` and nothing more")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="(--full) 0 = skip the cpu_baseline leg (the oracle's serial pass over the whole tree, ~21 s for C2); default 20")
+    ap.add_argument("--legs", default=None, choices=["auto", "off", "full"],
+                    help="(--full) auto = every leg for the default C2 run at N = 1, buffers_sharded only otherwise; default auto")
+    ap.add_argument("--resident-steps", type=int, default=None, help="(--full) launches of the HBM-resident (roofline) pass; default 12")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (hashes.yaml and its digests) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -72,6 +81,13 @@ def parse_args():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    full_only = [o for o, v in (("--cpu-seconds", args.cpu_seconds), ("--legs", args.legs), ("--resident-steps", args.resident_steps))
+                 if v is not None]
+    if full_only and not args.full:
+        ap.error("%s configure%s what --full adds: give --full as well" % (" / ".join(full_only), "s" if len(full_only) == 1 else ""))
+    args.cpu_seconds = 20.0 if args.cpu_seconds is None else args.cpu_seconds
+    args.legs = args.legs or "auto"
+    args.resident_steps = 12 if args.resident_steps is None else args.resident_steps
     return args
 
 
@@ -1001,12 +1017,13 @@ def main():
         for k, p in enumerate(my_paths):
             host[int(my_off[k]):int(my_off[k]) + int(my_lens[k])].tofile(p)
 
-        # ---- (i) kernel-resident: this rank's streams already in HBM -> roofline ---------------------------------
-        slab = torch.zeros((max(plan.rows, 1), 64), dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        k_ms, r_wall, r_st = resident_pass(rctx, data.data_ptr(), my_off, my_lens, slab.data_ptr(), args.resident_steps, 3)
-        my_want = slab[:len(my_paths)].cpu().numpy()
-        r_wall = allmax(r_wall)
+        # ---- (i) kernel-resident (--full): this rank's streams already in HBM -> roofline ---------------------------
+        if args.full:
+            slab = torch.zeros((max(plan.rows, 1), 64), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            k_ms, r_wall, r_st = resident_pass(rctx, data.data_ptr(), my_off, my_lens, slab.data_ptr(), args.resident_steps, 3)
+            my_want = slab[:len(my_paths)].cpu().numpy()
+            r_wall = allmax(r_wall)
         del data
         torch.cuda.empty_cache()
 
@@ -1045,10 +1062,11 @@ def main():
         rank_ids = gather_obj({"rank": rank, "local_rank": local_rank, "device": device, "pci_bus_id": e_info["pci_bus_id"],
                                "numa_node": e_info["numa_node"], "pid": os.getpid(), "host": os.uname().nodename})
 
-        # ---- parity of the timed path, outside the timed region ----------------------------------------------------
+        # ---- --full: parity of the timed path, outside the timed region --------------------------------------------
         parity, cpu, oracle_yaml = None, None, None
-        full_legs = rank == 0 and world == 1 and not force_dist and (args.legs == "full" or (args.legs == "auto" and args.workload == "C2"))
-        if rank == 0:
+        full_legs = (args.full and rank == 0 and world == 1 and not force_dist and
+                     (args.legs == "full" or (args.legs == "auto" and args.workload == "C2")))
+        if rank == 0 and args.full:
             y = last["yaml"]
             rng = np.random.default_rng(1)
             sample = sorted(set([0, n_files - 1] + [int(x) for x in rng.integers(0, n_files, size=14)]))
@@ -1082,7 +1100,7 @@ def main():
             elif "result" not in parity:
                 parity["result"] = parity.get("single_gpu", "hashlib sample only") + " (--cpu-seconds 0: no oracle pass)"
 
-        # ---- end_to_end legs ------------------------------------------------------------------------------------------
+        # ---- --full: end_to_end legs ----------------------------------------------------------------------------------
         end_to_end, configs = {}, None
 
         def leg(store, name, fn):
@@ -1096,7 +1114,7 @@ def main():
                 store[name] = r
             except Exception as e:  # noqa: BLE001
                 store[name] = {"error": repr(e)[:300]}
-        if args.legs != "off":
+        if args.full and args.legs != "off":
             bctx = Context(device=device, kernel=kern, flags=_lib.FLAG_GPU_ONLY)
             r = e2e_buffers_sharded(bctx, host, my_off, my_lens, my_want, total_bytes, world, fence, allmax, gather_obj)
             bctx.close()
@@ -1199,20 +1217,23 @@ def main():
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "strong",
                 "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-                "config": {"workload": wl, "files": n_files + 1, "bytes": total_bytes, "kernel": _lib.KERNEL_NAMES.get(r_st["kernel_used"], "?"),
+                "config": {"workload": wl, "files": n_files + 1, "bytes": total_bytes, "kernel": _lib.KERNEL_NAMES.get((r_st if args.full else e_st)["kernel_used"], "?"),
                            "ranks": ranks, "per_rank": per_rank_step, "tree_placement": numa_note, "tree_home": tree_home,
                            "step_ms_rank0": {"min": round(min(step_ms), 2), "median": round(sorted(step_ms)[len(step_ms) // 2], 2), "max": round(max(step_ms), 2)}},
-                "roofline": roofline_of(k_ms, int(my_lens.sum()), r_st, args.workload, world, streams=len(my_paths)),
-                "hbm_resident": {"what": "the same streams already in HBM (snaphash_sha512_device), every rank its share; wall per pass, MAX over ranks",
-                                 "ms_per_pass": round(r_wall * 1e3, 4), "GiBps": round(total_bytes / GiB / r_wall, 3),
-                                 "launches_timed": args.resident_steps,
-                                 "note": "stream-count-bound: 10 001 streams advance no faster on 8 GPUs than on one, so this rate is "
-                                         "flat in N by construction (DESIGN.md sec. 5)"},
-                "parity": parity,
-                "ceilings": {"hbm_GBps": HBM_PEAK_GBPS, "valu_saturated_GBps_measured": VALU_SATURATED_GBPS,
-                             "per_stream_MBps_here": round(int(my_lens.sum()) / (k_ms * 1e-3) / 1e6 / max(len(my_paths), 1), 2),
-                             "pcie_link_GBps_measured": 55.3, "source": "profiles/ (regime sweep, saturated-launch PMC, r04_shard_probe)"},
             }
+            if args.full:
+                line.update({
+                    "roofline": roofline_of(k_ms, int(my_lens.sum()), r_st, args.workload, world, streams=len(my_paths)),
+                    "hbm_resident": {"what": "the same streams already in HBM (snaphash_sha512_device), every rank its share; wall per pass, MAX over ranks",
+                                     "ms_per_pass": round(r_wall * 1e3, 4), "GiBps": round(total_bytes / GiB / r_wall, 3),
+                                     "launches_timed": args.resident_steps,
+                                     "note": "stream-count-bound: 10 001 streams advance no faster on 8 GPUs than on one, so this rate is "
+                                             "flat in N by construction (DESIGN.md sec. 5)"},
+                    "parity": parity,
+                    "ceilings": {"hbm_GBps": HBM_PEAK_GBPS, "valu_saturated_GBps_measured": VALU_SATURATED_GBPS,
+                                 "per_stream_MBps_here": round(int(my_lens.sum()) / (k_ms * 1e-3) / 1e6 / max(len(my_paths), 1), 2),
+                                 "pcie_link_GBps_measured": 55.3, "source": "profiles/ (regime sweep, saturated-launch PMC, r04_shard_probe)"},
+                })
             if end_to_end:
                 line["end_to_end"] = end_to_end
             if configs:
@@ -1232,10 +1253,10 @@ def main():
     if use_dist:
         dist.destroy_process_group()
     if rank == 0 and line is not None:
-        # ---- N > 1: the same tree through ONE process and the C ABI's device list (what the Go caller reaches over
+        # ---- --full, N > 1: the same tree through ONE process and the C ABI's device list (what the Go caller reaches over
         # cgo): in-library LPT shards, one NUMA-placed staging engine per GPU, single-process RCCL gather.  Run when
         # the ranks have let go of their GPUs, in a child process with a time limit: the line never depends on it. ----
-        if world > 1 and not same_gpu and os.environ.get("SNAPHASH_BENCH_NO_INLIB") != "1":
+        if args.full and world > 1 and not same_gpu and os.environ.get("SNAPHASH_BENCH_NO_INLIB") != "1":
             import subprocess
             torch.cuda.empty_cache()
             try:

@@ -52,3 +52,21 @@ def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=60)
     assert r.returncode == 2 and r.stdout == b"" and b"--steps must be at least 1" in r.stderr
+
+
+def test_full_only_options_ask_for_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "off", "--cpu-seconds", "0"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=60)
+    assert r.returncode == 2 and r.stdout == b"" and b"--cpu-seconds / --legs configure what --full adds" in r.stderr
+
+
+def test_plain_run_is_the_default_and_full_keeps_its_defaults(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse_args()
+    assert not a.full and (a.cpu_seconds, a.legs, a.resident_steps) == (20.0, "auto", 12)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse_args()
+    assert a.full and (a.cpu_seconds, a.legs, a.resident_steps) == (20.0, "auto", 12)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--legs", "off", "--cpu-seconds", "0", "--resident-steps", "2"])
+    a = bench.parse_args()
+    assert a.full and (a.cpu_seconds, a.legs, a.resident_steps) == (0.0, "off", 2)
