@@ -468,8 +468,10 @@ typedef struct snaphash_engine_info {
     uint32_t n_cpus;       /* CPUs of numa_node the fill threads are bound to (0 = not bound) */
     char pci_bus_id[32];
     /* ---- ABI 4 (filled when struct_size covers them; an ABI 3 caller's shorter struct is still accepted) ---- */
-    uint64_t pinned_bytes; /* pinned host memory the engine holds right now (staging slots, job arrays, deflate buffers) */
-    uint64_t hbm_bytes;    /* device memory it holds (staging slots, chaining values, digests, scratch, gather buffer) */
+    uint64_t pinned_bytes; /* pinned host memory the engine holds right now (staging slots, job arrays, comparison tables, DEFLATE,
+                            * inflate and bzip2 scratch) */
+    uint64_t hbm_bytes;    /* device memory it holds (staging slots, job arrays, chaining values, digests, comparison tables,
+                            * DEFLATE, inflate and bzip2 scratch including the decoded stream, gather buffer) */
 } snaphash_engine_info;
 int snaphash_get_engine_info(const snaphash_ctx *ctx, uint32_t i, snaphash_engine_info *out);
 /* The CPUs engine i's fill threads are bound to (ABI 4): engines on one NUMA node get disjoint slices of its CPUs (whole

@@ -1,0 +1,197 @@
+// engine_bufs.h -- an engine's scratch (DevCtx, snaphash_api.cpp), grouped by the code that uses it.  Internal.
+//
+// A group's ensure() sizes every buffer of the group for a job, or on any failure leaves every one of them empty; each()
+// lists the group's buffers once, for the engine's release and its footprint (snaphash_get_engine_info).  Pinned
+// buffers take the engine's NUMA node, or -1 where the runtime places them (hipHostMallocDefault).
+#pragma once
+#include <algorithm>
+
+#include "bzip2_host.h"
+#include "bzip2_kernels.h"
+#include "deflate_kernels.h"
+#include "devbuf.h"
+#include "inflate_core.h"
+#include "inflate_kernels.h"
+#include "sha512_kernels.h"
+
+namespace snaphash {
+
+// a table built in pinned memory and its HBM twin, n entries each
+template <class T> struct Twin {
+    HostBuf<T> h;
+    DevBuf<T> d;
+    size_t size() const { return d.size(); }
+    hipError_t ensure(size_t n)
+    {
+        hipError_t e = h.reserve(n, -1);
+        if (!e) e = d.reserve(n);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { f(h); f(d); }
+};
+
+// job arrays hold 1024 jobs at least
+struct JobBufs : Twin<Job> {
+    hipError_t ensure(size_t n) { return Twin::ensure(std::max<size_t>(n, 1024)); }
+};
+
+// A staging buffer (pinned, and its HBM twin with 256 bytes of slack: the deflate kernel peeks 3 bytes past a chunk) and
+// the job array of the batch staged in it.
+struct Slot {
+    HostBuf<uint8_t> h_buf;
+    DevBuf<uint8_t> d_buf;
+    JobBufs jobs;
+    hipEvent_t done = nullptr;   // kernel of the batch staged in this slot has finished
+    hipEvent_t copied = nullptr; // H2D of this slot's data + jobs has finished
+    bool busy = false;
+    uint64_t cap() const { return h_buf.size(); } // bytes both hold (the engine's staging size, or less while only small jobs have come by)
+    hipError_t ensure(uint64_t bytes, int node)
+    {
+        hipError_t e = h_buf.reserve(bytes, node);
+        if (!e) e = d_buf.reserve(bytes + 256);
+        if (e) { h_buf.reset(); d_buf.reset(); }
+        return e;
+    }
+    template <class F> void each(F&& f) { f(h_buf); f(d_buf); jobs.each(f); }
+};
+
+// A batch of the hashing engine lives in a sub-slot: a piece of one of the engine's staging buffers with its own job
+// array and events.  A job of several buffers' worth is cut into batches much smaller than a buffer (hash_sources):
+// when the streams' own rate is about the link's (a rank's shard of config 4: 1 250 streams x 44 MB/s = 55 GB/s), fill,
+// copy and kernel are three stages of equal length and only many small batches in flight keep all three busy.
+struct SubSlot {
+    JobBufs jobs;
+    hipEvent_t done = nullptr;   // kernel of the batch staged here has finished
+    hipEvent_t copied = nullptr; // H2D of this batch's jobs has finished
+    bool busy = false;
+};
+
+// hashing: the chaining values and digests of a call's streams (64 bytes each), the device-resident entry point's jobs
+struct HashBufs {
+    JobBufs jobs;
+    DevBuf<uint64_t> d_state;
+    DevBuf<uint8_t> d_digests;
+    // njobs = 0: the job array as it is
+    hipError_t ensure(size_t streams, bool with_digests, size_t njobs = 0)
+    {
+        hipError_t e = d_state.reserve(streams * 8);
+        if (!e && with_digests) e = d_digests.reserve(streams * 64);
+        if (!e && njobs) e = jobs.ensure(njobs);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { jobs.each(f); f(d_state); f(d_digests); }
+};
+
+// block-parallel DEFLATE (row f3, targz.inc), per chunk of a staging slot: output slots, the parse, sizes, offsets,
+// the compacted piece, and its way back to the host
+struct DeflateBufs {
+    DevBuf<uint8_t> d_slots, d_out;
+    DevBuf<uint32_t> d_toks; // the deflate kernel's parse, kDeflateTokWords a chunk
+    DevBuf<uint32_t> d_sizes;
+    DevBuf<uint64_t> d_prefix;
+    HostBuf<uint32_t> h_sizes;
+    HostBuf<uint64_t> h_prefix;
+    HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next D2H fills the other
+    size_t chunks() const { return d_sizes.size(); }
+    hipError_t ensure(size_t nch, int node)
+    {
+        hipError_t e = d_slots.reserve(nch * kDeflateSlot);
+        if (!e) e = d_out.reserve(nch * kDeflateSlot);
+        if (!e) e = d_toks.reserve(nch * kDeflateTokWords);
+        if (!e) e = d_sizes.reserve(nch);
+        if (!e) e = d_prefix.reserve(nch);
+        if (!e) e = h_sizes.reserve(nch, node);
+        if (!e) e = h_prefix.reserve(nch, node);
+        for (HostBuf<uint8_t>& b : h_out)
+            if (!e) e = b.reserve(nch * kDeflateSlot, node);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { f(d_slots); f(d_out); f(d_toks); f(d_sizes); f(d_prefix); f(h_sizes); f(h_prefix); f(h_out[0]); f(h_out[1]); }
+};
+
+// GPU inflate (row f5, unpack.inc): the compressed piece (+16 bytes the bit reader may read past it) and its candidates,
+// the speculative segments' slots and results, the linked chain, the hole counters, the window in front of the piece,
+// and the decoded bytes (grown by ensure_fout; the bzip2 decode writes there too)
+struct InflateBufs {
+    DevBuf<uint8_t> d_in;
+    DevBuf<uint32_t> d_cand; // the count, the candidates, the piece start
+    HostBuf<uint32_t> h_cand;
+    DevBuf<uint16_t> d_slots; // kInflateSlotSyms symbols a segment
+    DevBuf<InflateSegRes> d_res;
+    HostBuf<InflateSegRes> h_res;
+    DevBuf<InflateLink> d_links;
+    HostBuf<InflateLink> h_links;
+    DevBuf<uint32_t> d_flags;
+    HostBuf<uint32_t> h_flags;
+    DevBuf<uint8_t> d_win;
+    DevBuf<uint8_t> d_out;
+    uint64_t cand_cap() const { return d_cand.size() - 2; }
+    uint32_t nslots() const { return (uint32_t)d_res.size(); }
+    hipError_t ensure(uint64_t piece, uint32_t slots, int node)
+    {
+        const uint64_t cand = piece / 4 + 16; // (a candidate per 4 bytes at most that the launch takes; more are counted, not kept)
+        hipError_t e = d_flags.reserve(4);
+        if (!e) e = h_flags.reserve(4, node);
+        if (!e) e = d_win.reserve(kInfWindow);
+        if (!e) e = d_in.reserve(piece + 16);
+        if (!e) e = d_cand.reserve(cand + 2);
+        if (!e) e = h_cand.reserve(cand + 2, node);
+        if (!e) e = d_slots.reserve((size_t)slots * kInflateSlotSyms);
+        if (!e) e = d_res.reserve(slots);
+        if (!e) e = h_res.reserve(slots, node);
+        if (!e) e = d_links.reserve(slots);
+        if (!e) e = h_links.reserve(slots, node);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f)
+    {
+        f(d_in); f(d_cand); f(h_cand); f(d_slots); f(d_res); f(h_res); f(d_links); f(h_links); f(d_flags); f(h_flags); f(d_win); f(d_out);
+    }
+};
+
+// GPU bzip2 (unbz2.inc): the compressed piece (+16) and its candidates and their count, the candidates' slots (BWT bytes,
+// then the inverse BWT's output), the T vectors, the RLE1 chunk states, the symbol stage's results and the linked blocks
+struct Bzip2Bufs {
+    DevBuf<uint8_t> d_in;
+    DevBuf<uint64_t> d_cand;
+    HostBuf<uint64_t> h_cand;
+    DevBuf<uint32_t> d_count;
+    HostBuf<uint32_t> h_count;
+    DevBuf<uint8_t> d_slots; // kBzMaxBlock bytes a slot
+    DevBuf<uint32_t> d_tt;   // kBzMaxBlock words a slot
+    DevBuf<uint64_t> d_chunks; // kBzChunks a slot
+    DevBuf<BzBlockRes> d_res;
+    HostBuf<BzBlockRes> h_res;
+    DevBuf<BzGpuBlock> d_blk;
+    HostBuf<BzGpuBlock> h_blk;
+    uint64_t cand_cap() const { return d_cand.size(); }
+    uint32_t nslots() const { return (uint32_t)d_res.size(); }
+    hipError_t ensure(uint64_t piece, uint32_t slots, int node)
+    {
+        const uint64_t cand = bz_candidate_cap(piece);
+        hipError_t e = d_count.reserve(4);
+        if (!e) e = h_count.reserve(4, node);
+        if (!e) e = d_in.reserve(piece + 16);
+        if (!e) e = d_cand.reserve(cand);
+        if (!e) e = h_cand.reserve(cand, node);
+        if (!e) e = d_slots.reserve((size_t)slots * kBzMaxBlock);
+        if (!e) e = d_tt.reserve((size_t)slots * kBzMaxBlock);
+        if (!e) e = d_chunks.reserve((size_t)slots * kBzChunks);
+        if (!e) e = d_res.reserve(slots);
+        if (!e) e = h_res.reserve(slots, node);
+        if (!e) e = d_blk.reserve(slots);
+        if (!e) e = h_blk.reserve(slots, node);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f)
+    {
+        f(d_in); f(d_cand); f(h_cand); f(d_count); f(h_count); f(d_slots); f(d_tt); f(d_chunks); f(d_res); f(h_res); f(d_blk); f(h_blk);
+    }
+};
+
+} // namespace snaphash

@@ -37,14 +37,11 @@
 #include <memory>
 #include <mutex>
 
-#include "deflate_kernels.h"
+#include "engine_bufs.h"
 #include "hostfill.h"
 #include "hostpass.h"
 #include "hostsha.h"
-#include "bzip2_host.h"
-#include "bzip2_kernels.h"
 #include "inflate_host.h"
-#include "inflate_kernels.h"
 #include "member_hashers.h"
 #include "planner.h"
 #include "sha512_core.h"
@@ -64,31 +61,6 @@ constexpr uint64_t kMinSegmentMem = 16u << 10; // the same for a stream in calle
 constexpr uint32_t kTargetStreams = 4096; // streams per batch the engine aims for (keeps the kernel ahead of PCIe)
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; int kind = 0; }; // kind 0 SHA-512 kernels, 1 h2d, 2 deflate kernels
-
-struct Slot {
-    uint8_t* h_buf = nullptr; // pinned host
-    uint8_t* d_buf = nullptr; // HBM
-    uint64_t cap = 0;         // bytes both hold (the engine's staging size, or less while only small jobs have come by)
-    Job* h_jobs = nullptr;    // pinned
-    Job* d_jobs = nullptr;
-    size_t jobs_cap = 0;
-    hipEvent_t done = nullptr;   // kernel of the batch staged in this slot has finished
-    hipEvent_t copied = nullptr; // H2D of this slot's data + jobs has finished
-    bool busy = false;
-};
-
-// A batch of the hashing engine lives in a sub-slot: a piece of one of the engine's staging buffers with its own job
-// array and events.  A job of several buffers' worth is cut into batches much smaller than a buffer (hash_sources):
-// when the streams' own rate is about the link's (a rank's shard of config 4: 1 250 streams x 44 MB/s = 55 GB/s), fill,
-// copy and kernel are three stages of equal length and only many small batches in flight keep all three busy.
-struct SubSlot {
-    Job* h_jobs = nullptr; // pinned
-    Job* d_jobs = nullptr;
-    size_t jobs_cap = 0;
-    hipEvent_t done = nullptr;   // kernel of the batch staged here has finished
-    hipEvent_t copied = nullptr; // H2D of this batch's jobs has finished
-    bool busy = false;
-};
 
 double now_ms()
 {
@@ -117,73 +89,16 @@ struct DevCtx {
     Slot slot[3]; // [0], [1]: every staging user; [2]: a third buffer for the hashing engine alone, allocated when a call
                   // has more than two buffers' worth of bytes (fill k+2 then overlaps kernel k: with two, a job whose
                   // kernels take as long as its copies -- one rank's shard of config 4 -- idles between batches)
-    // device-resident entry point
-    Job* h_jobs = nullptr; // pinned
-    Job* d_jobs = nullptr;
-    size_t jobs_cap = 0;
-    uint64_t* d_state = nullptr;
-    size_t state_cap = 0; // streams
-    uint8_t* d_digests = nullptr;
-    size_t digests_cap = 0; // streams
-
-    CmpChunk* h_chunks = nullptr; // pinned (range comparison)
-    CmpChunk* d_chunks = nullptr;
-    size_t chunks_cap = 0;
-    uint8_t* d_equal = nullptr;
-    size_t equal_cap = 0;
-
-    // block-parallel DEFLATE scratch (row f3): per-chunk output slots, sizes, offsets, compacted output
-    uint8_t* d_zslots = nullptr;
-    uint8_t* d_zout = nullptr;
-    uint32_t* d_ztoks = nullptr; // the deflate kernel's parse, one word per staged byte
-    uint32_t* d_zsizes = nullptr;
-    uint64_t* d_zprefix = nullptr;
-    uint32_t* h_zsizes = nullptr; // pinned
-    uint64_t* h_zprefix = nullptr;
-    uint8_t* h_zout[2] = {nullptr, nullptr}; // pinned, double-buffered: the consumers read one while the next D2H fills the other
+    HashBufs hash;
+    Twin<CmpChunk> cmp; // the range comparison's chunk tables, in two halves (ensure_chunks)
+    DeflateBufs z;
     hipStream_t z_stream = nullptr;          // the compressor's stream
     hipStream_t z2_stream = nullptr;         // concatenation of a finished piece and its way back to the host
     std::vector<hipEvent_t> z_ev;            // "the sizes of piece k are on the host"
     std::vector<hipEvent_t> z_part_ev;       // "part k of the pass's first slot is in HBM" (targz.inc)
-    size_t z_chunks = 0;
-
-    // GPU inflate scratch (row f5, unpack.inc): the compressed piece, its candidates, the speculative segments' slots and
-    // results, the linked chain, the window in front of the piece, the decoded bytes
-    hipStream_t f_stream = nullptr;
-    uint8_t* d_fin = nullptr;
-    uint64_t fin_cap = 0;
-    uint32_t* d_fcand = nullptr; // [0] count, then the candidates
-    uint32_t* h_fcand = nullptr; // pinned
-    uint64_t fcand_cap = 0;
-    uint16_t* d_fslots = nullptr;
-    InflateSegRes* d_fres = nullptr;
-    InflateSegRes* h_fres = nullptr; // pinned
-    InflateLink* d_flinks = nullptr;
-    InflateLink* h_flinks = nullptr; // pinned
-    uint32_t fslots_cap = 0;
-    uint32_t* d_fflags = nullptr;
-    uint32_t* h_fflags = nullptr; // pinned
-    uint8_t* d_fwin = nullptr;
-    uint8_t* d_fout = nullptr;
-    uint64_t fout_cap = 0;
-
-    // GPU bzip2 scratch (unbz2.inc): the compressed piece and its candidates, the candidates' slots (BWT bytes, then the
-    // inverse BWT's output), the T vectors, the RLE1 chunk states, the symbol stage's results and the linked blocks
-    uint8_t* d_bin = nullptr;
-    uint64_t bin_cap = 0;
-    uint64_t* d_bcand = nullptr; // the candidates (the count lives in d_bcount)
-    uint64_t* h_bcand = nullptr; // pinned
-    uint32_t* d_bcount = nullptr;
-    uint32_t* h_bcount = nullptr; // pinned
-    uint64_t bcand_cap = 0;
-    uint8_t* d_bslots = nullptr;
-    uint32_t* d_btt = nullptr;
-    uint64_t* d_bchunks = nullptr;
-    BzBlockRes* d_bres = nullptr;
-    BzBlockRes* h_bres = nullptr; // pinned
-    BzGpuBlock* d_bblk = nullptr;
-    BzGpuBlock* h_bblk = nullptr; // pinned
-    uint32_t bslots_cap = 0;
+    InflateBufs inf;
+    Bzip2Bufs bz;
+    hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
 
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;
@@ -207,6 +122,17 @@ struct DevCtx {
     snaphash_stats stats{};
     double t_call0 = 0;
     std::string last_error;
+
+    template <class F> void each_buf(F&& f)
+    {
+        for (Slot& s : slot) s.each(f);
+        for (SubSlot& q : sub) q.jobs.each(f);
+        hash.each(f);
+        cmp.each(f);
+        z.each(f);
+        inf.each(f);
+        bz.each(f);
+    }
 };
 
 namespace {
@@ -239,8 +165,7 @@ struct snaphash_ctx {
     std::mutex calib_mu;       // (the engines of a multi-device ctx report from their own threads)
     uint32_t flags = 0;
     Rccl rccl;
-    std::vector<uint8_t*> d_gather; // per device: n_devices * kmax * 64 bytes
-    size_t gather_cap = 0;          // rows (kmax) the gather buffers hold
+    std::vector<DevBuf<uint8_t>> d_gather; // per device: n_devices * kmax * 64 bytes
     snaphash_stats stats{};
     snaphash_stats_ex ex{};
     snaphash_targz_stats targz{};
@@ -307,43 +232,16 @@ void collect_events(DevCtx* c)
     c->ev_used = 0;
 }
 
-int ensure_state(DevCtx* c, size_t n, bool want_digests)
-{
-    if (n > c->state_cap) {
-        if (c->d_state) (void)hipFree(c->d_state);
-        c->d_state = nullptr; c->state_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_state, n * 64));
-        c->state_cap = n;
-    }
-    if (want_digests && n > c->digests_cap) {
-        if (c->d_digests) (void)hipFree(c->d_digests);
-        c->d_digests = nullptr; c->digests_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_digests, n * 64));
-        c->digests_cap = n;
-    }
-    return SNAPHASH_OK;
-}
+} // namespace
 
-int ensure_jobs(DevCtx* c, Job** h, Job** d, size_t* cap, size_t n)
+// The library's allocator for devbuf.h.  Pinned host memory for an engine goes on the GPU's NUMA node when it is known
+// (the calling thread's memory policy prefers that node for the duration of the allocation and hipHostMallocNumaUser
+// tells the runtime to honour it), wherever the runtime puts it otherwise.
+hipError_t snaphash::devbuf_alloc(Mem kind, void** p, size_t bytes, int numa_node)
 {
-    if (n <= *cap) return SNAPHASH_OK;
-    size_t want = std::max<size_t>(n, 1024);
-    if (*h) (void)hipHostFree(*h);
-    if (*d) (void)hipFree(*d);
-    *h = nullptr; *d = nullptr; *cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)h, want * sizeof(Job), hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc((void**)d, want * sizeof(Job)));
-    *cap = want;
-    return SNAPHASH_OK;
-}
-
-// Pinned host memory for an engine: on the GPU's NUMA node when it is known (the calling thread's memory policy
-// prefers that node for the duration of the allocation and hipHostMallocNumaUser tells the runtime to honour it),
-// wherever the runtime puts it otherwise.
-hipError_t host_alloc(DevCtx* c, void** p, size_t bytes)
-{
+    if (kind == Mem::Hbm) return hipMalloc(p, bytes);
     SavedMemPolicy saved;
-    if (c->numa_node >= 0 && numa_prefer_node(c->numa_node, &saved)) {
+    if (numa_node >= 0 && numa_prefer_node(numa_node, &saved)) {
         const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocNumaUser);
         numa_restore_policy(saved);
         if (e == hipSuccess) return e;
@@ -352,6 +250,14 @@ hipError_t host_alloc(DevCtx* c, void** p, size_t bytes)
     return hipHostMalloc(p, bytes, hipHostMallocDefault);
 }
 
+void snaphash::devbuf_free(Mem kind, void* p)
+{
+    if (kind == Mem::Hbm) (void)hipFree(p);
+    else (void)hipHostFree(p);
+}
+
+namespace {
+
 // want = 0: the engine's full staging size (every user but the hashing engine, which asks for what its job needs:
 // pinning 2 x 256 MiB costs ~40 ms, which a one-shot `snappy build` of a small tree would pay for nothing).
 int ensure_slots(DevCtx* c, int nslots = 2, uint64_t want = 0)
@@ -359,15 +265,8 @@ int ensure_slots(DevCtx* c, int nslots = 2, uint64_t want = 0)
     if (want == 0 || want > c->staging) want = c->staging;
     for (int k = 0; k < nslots; ++k) {
         Slot& s = c->slot[k];
-        if (s.cap < want) {
-            if (s.h_buf) (void)hipHostFree(s.h_buf);
-            if (s.d_buf) (void)hipFree(s.d_buf);
-            s.h_buf = nullptr; s.d_buf = nullptr; s.cap = 0;
-            HIP_TRY(c, host_alloc(c, (void**)&s.h_buf, want));
-            if (c->staging_node < 0) { s.h_buf[0] = 0; c->staging_node = numa_node_of_address(s.h_buf); }
-            HIP_TRY(c, hipMalloc((void**)&s.d_buf, want + 256)); // slack: the deflate kernel peeks 3 bytes past a chunk
-            s.cap = want;
-        }
+        HIP_TRY(c, s.ensure(want, c->numa_node));
+        if (c->staging_node < 0) { s.h_buf[0] = 0; c->staging_node = numa_node_of_address(s.h_buf.data()); }
         if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         if (!s.copied) HIP_TRY(c, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
     }
@@ -391,10 +290,10 @@ uint64_t job_blocks(const Job& j) { return (j.nbytes >> 7) + 1; }
 
 hipError_t launch_kernel(uint32_t k, const Job* d_jobs, size_t n, DevCtx* c, uint8_t* d_digests, bool staged)
 {
-    if (k == SNAPHASH_KERNEL_QUAD) return launch_quad(d_jobs, (uint32_t)n, c->d_state, d_digests, c->stream);
-    if (k == SNAPHASH_KERNEL_PAIR) return launch_pair(d_jobs, (uint32_t)n, c->d_state, d_digests, c->stream, staged);
-    if (k == SNAPHASH_KERNEL_SPLIT) return launch_split(d_jobs, (uint32_t)n, c->d_state, d_digests, c->stream);
-    return launch_wide(d_jobs, (uint32_t)n, c->d_state, d_digests, c->stream);
+    if (k == SNAPHASH_KERNEL_QUAD) return launch_quad(d_jobs, (uint32_t)n, c->hash.d_state.data(), d_digests, c->stream);
+    if (k == SNAPHASH_KERNEL_PAIR) return launch_pair(d_jobs, (uint32_t)n, c->hash.d_state.data(), d_digests, c->stream, staged);
+    if (k == SNAPHASH_KERNEL_SPLIT) return launch_split(d_jobs, (uint32_t)n, c->hash.d_state.data(), d_digests, c->stream);
+    return launch_wide(d_jobs, (uint32_t)n, c->hash.d_state.data(), d_digests, c->stream);
 }
 
 // h_jobs is sorted longest first.  Returns how many leading jobs go to the
@@ -607,11 +506,10 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
     uint64_t slot_bytes = std::min<uint64_t>(c->staging, 8u << 20);
     while (slot_bytes < c->staging && slot_bytes < job_bytes / 2 + kAlign * n) slot_bytes <<= 1;
     slot_bytes = std::min(slot_bytes, c->staging);
-    for (unsigned k = 0; k < nslots; ++k) slot_bytes = std::max(slot_bytes, std::min(c->slot[k].cap, c->staging)); // what is there already is used
+    for (unsigned k = 0; k < nslots; ++k) slot_bytes = std::max(slot_bytes, std::min(c->slot[k].cap(), c->staging)); // what is there already is used
     int rc = ensure_slots(c, (int)nslots, slot_bytes);
     if (rc) return rc;
-    rc = ensure_state(c, n, true);
-    if (rc) return rc;
+    HIP_TRY(c, c->hash.ensure(n, true));
 
     c->fill_thread_s = 0;
     c->fill_bytes = 0;
@@ -673,8 +571,8 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
     while (!active.empty()) {
         const unsigned q = batch % nsub;
         SubSlot& sl = c->sub[q];
-        uint8_t* const sl_h = c->slot[q / per_slot].h_buf + (uint64_t)(q % per_slot) * S_full;
-        uint8_t* const sl_d = c->slot[q / per_slot].d_buf + (uint64_t)(q % per_slot) * S_full;
+        uint8_t* const sl_h = c->slot[q / per_slot].h_buf.data() + (uint64_t)(q % per_slot) * S_full;
+        uint8_t* const sl_d = c->slot[q / per_slot].d_buf.data() + (uint64_t)(q % per_slot) * S_full;
         const double tb0 = now_ms();
         if (sl.busy) { HIP_TRY(c, hipEventSynchronize(sl.done)); sl.busy = false; }
         const double tb1 = now_ms();
@@ -736,8 +634,7 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         // 6, 114 ms for a job whose copies take 92; profiles/r04_shard_trace.txt).
         const uint64_t pad = kAlign * (uint64_t)active.size();
         const uint64_t S_share = pad < S / 2 ? S - pad : S;
-        rc = ensure_jobs(c, &sl.h_jobs, &sl.d_jobs, &sl.jobs_cap, active.size());
-        if (rc) return rc;
+        HIP_TRY(c, sl.jobs.ensure(active.size()));
 
         ops.clear();
         size_t nj = 0;
@@ -792,7 +689,7 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
             j.total_prev = done[id];
             j.idx = id;
             j.flags = (done[id] == 0 ? kJobFirst : 0u) | (fin ? kJobFinal : 0u);
-            sl.h_jobs[nj++] = j;
+            sl.jobs.h[nj++] = j;
             if (take) ops.push_back(ReadOp{id, done[id], take, sl_h + at, fin && src[id].path != nullptr});
             used = at + take;
             done[id] += take;
@@ -805,7 +702,7 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         static const bool trace_batches = getenv("SNAPHASH_TRACE_BATCHES") != nullptr; // (read once, not once a batch)
         if (trace_batches) {
             uint64_t mx = 0;
-            for (size_t k = 0; k < nj; ++k) mx = std::max<uint64_t>(mx, sl.h_jobs[k].nbytes);
+            for (size_t k = 0; k < nj; ++k) mx = std::max<uint64_t>(mx, sl.jobs.h[k].nbytes);
             fprintf(stderr, "snaphash engine %d: batch %u: S %llu, %zu segments, %llu bytes, largest share %llu, %zu streams left behind\n", c->index, batch,
                     (unsigned long long)S, nj, (unsigned long long)used, (unsigned long long)mx, active.size());
         }
@@ -829,7 +726,7 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
             HIP_TRY(c, hipMemcpyAsync(sl_d, sl_h, used, hipMemcpyHostToDevice, c->copy_stream));
             HIP_TRY(c, hipEventRecord(ev->b, c->copy_stream));
         }
-        rc = launch_jobs(c, sl.h_jobs, sl.d_jobs, nj, c->d_digests, sl.copied);
+        rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), nj, c->hash.d_digests.data(), sl.copied);
         if (rc) return rc;
         HIP_TRY(c, hipEventRecord(sl.done, c->stream));
         sl.busy = true;
@@ -871,8 +768,8 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         return fail(c, SNAPHASH_EIO,
                     std::string(s >= 0 && src[s].path ? src[s].path : "<buffer>") + ": " + strerror(first_err.load()));
     }
-    if (digests) HIP_TRY(c, hipMemcpy(digests, c->d_digests, n * 64, hipMemcpyDeviceToHost));
-    if (states) HIP_TRY(c, hipMemcpy(states, c->d_state, n * 64, hipMemcpyDeviceToHost));
+    if (digests) HIP_TRY(c, hipMemcpy(digests, c->hash.d_digests.data(), n * 64, hipMemcpyDeviceToHost));
+    if (states) HIP_TRY(c, hipMemcpy(states, c->hash.d_state.data(), n * 64, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) c->stats.bytes_hashed += src[i].gpu_len;
     c->stats.streams = n;
     if (c->owner) { // what this call says about the box: the copies' own rate (HIP events) and what a fill thread moved
@@ -937,31 +834,20 @@ int gather_digest_slabs(snaphash_ctx* x, const std::vector<size_t>& cnt, size_t 
     const double t0 = now_ms();
     bool use_rccl = !(x->flags & SNAPHASH_FLAG_NO_RCCL) && rccl_load(x);
     if (use_rccl) {
-        if (kmax > x->gather_cap) {
-            for (size_t d = 0; d < x->d_gather.size(); ++d)
-                if (x->d_gather[d]) { (void)hipSetDevice(x->dev[d]->device); (void)hipFree(x->d_gather[d]); }
-            x->d_gather.assign(nd, nullptr);
-            x->gather_cap = 0;
-            for (size_t d = 0; d < nd; ++d) {
-                DevCtx* c = x->dev[d].get();
-                HIP_TRY(c, hipSetDevice(c->device));
-                if (hipMalloc((void**)&x->d_gather[d], nd * kmax * 64) != hipSuccess)
-                    return fail(x, SNAPHASH_ENOMEM, "hipMalloc of the gather buffer failed");
-            }
-            x->gather_cap = kmax;
-        }
-        for (size_t d = 0; d < nd; ++d) { // already sized by the caller before hashing (a growth here would drop the digests)
+        x->d_gather.resize(nd);
+        for (size_t d = 0; d < nd; ++d) {
             DevCtx* c = x->dev[d].get();
             HIP_TRY(c, hipSetDevice(c->device));
-            int rc = ensure_state(c, kmax, true);
-            if (rc) return lift(x, c, rc);
+            if (x->d_gather[d].reserve(nd * kmax * 64) != hipSuccess)
+                return fail(x, SNAPHASH_ENOMEM, "hipMalloc of the gather buffer failed");
+            HIP_TRY(x, c->hash.ensure(kmax, true)); // already sized by the caller before hashing (a growth here would drop the digests)
         }
         Rccl& r = x->rccl;
         ncclResult_t e = r.GroupStart();
         for (size_t d = 0; d < nd && e == ncclSuccess; ++d) {
             DevCtx* c = x->dev[d].get();
             (void)hipSetDevice(c->device);
-            e = r.AllGather(c->d_digests, x->d_gather[d], kmax * 64, ncclUint8, r.comms[d], c->stream);
+            e = r.AllGather(c->hash.d_digests.data(), x->d_gather[d].data(), kmax * 64, ncclUint8, r.comms[d], c->stream);
         }
         const ncclResult_t e2 = r.GroupEnd();
         if (e == ncclSuccess) e = e2;
@@ -983,14 +869,14 @@ int gather_digest_slabs(snaphash_ctx* x, const std::vector<size_t>& cnt, size_t 
         }
         DevCtx* c0 = x->d0();
         HIP_TRY(c0, hipSetDevice(c0->device));
-        HIP_TRY(c0, hipMemcpy(rows.data(), x->d_gather[0], nd * kmax * 64, hipMemcpyDeviceToHost));
+        HIP_TRY(c0, hipMemcpy(rows.data(), x->d_gather[0].data(), nd * kmax * 64, hipMemcpyDeviceToHost));
         x->ex.gather_kind = 1;
         if (x->flags & SNAPHASH_FLAG_CHECK_GATHER) { // the collective's parity check: per-device copies
             std::vector<uint8_t> own(kmax * 64);
             for (size_t d = 0; d < nd; ++d) {
                 DevCtx* c = x->dev[d].get();
                 HIP_TRY(c, hipSetDevice(c->device));
-                if (cnt[d]) HIP_TRY(c, hipMemcpy(own.data(), c->d_digests, cnt[d] * 64, hipMemcpyDeviceToHost));
+                if (cnt[d]) HIP_TRY(c, hipMemcpy(own.data(), c->hash.d_digests.data(), cnt[d] * 64, hipMemcpyDeviceToHost));
                 if (memcmp(own.data(), rows.data() + d * kmax * 64, cnt[d] * 64) != 0)
                     return fail(x, SNAPHASH_EDEVICE, "RCCL-gathered digest slab differs from the device's own copy");
             }
@@ -1000,7 +886,7 @@ int gather_digest_slabs(snaphash_ctx* x, const std::vector<size_t>& cnt, size_t 
         for (size_t d = 0; d < nd; ++d) {
             DevCtx* c = x->dev[d].get();
             HIP_TRY(c, hipSetDevice(c->device));
-            if (cnt[d]) HIP_TRY(c, hipMemcpy(rows.data() + d * kmax * 64, c->d_digests, cnt[d] * 64, hipMemcpyDeviceToHost));
+            if (cnt[d]) HIP_TRY(c, hipMemcpy(rows.data() + d * kmax * 64, c->hash.d_digests.data(), cnt[d] * 64, hipMemcpyDeviceToHost));
         }
         x->ex.gather_kind = 2;
     }
@@ -1153,8 +1039,7 @@ int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests
         for (size_t d = 0; d < nd; ++d) {
             DevCtx* c = x->dev[d].get();
             HIP_TRY(c, hipSetDevice(c->device));
-            const int rc = ensure_state(c, kmax, true);
-            if (rc) return lift(x, c, rc);
+            HIP_TRY(x, c->hash.ensure(kmax, true));
         }
     }
     struct DevJob { std::vector<Source> sub; std::vector<uint8_t> dig; int rc = 0, err_no = 0; int64_t err_src = -1; };
@@ -1412,45 +1297,24 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
-static void free_inflate(DevCtx* c);
-
 static void destroy_dev(DevCtx* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_inflate(c);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    c->each_buf(Release());
     for (Slot& s : c->slot) {
-        if (s.h_buf) (void)hipHostFree(s.h_buf);
-        if (s.d_buf) (void)hipFree(s.d_buf);
-        if (s.h_jobs) (void)hipHostFree(s.h_jobs);
-        if (s.d_jobs) (void)hipFree(s.d_jobs);
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.copied) (void)hipEventDestroy(s.copied);
     }
     for (SubSlot& q : c->sub) {
-        if (q.h_jobs) (void)hipHostFree(q.h_jobs);
-        if (q.d_jobs) (void)hipFree(q.d_jobs);
         if (q.done) (void)hipEventDestroy(q.done);
         if (q.copied) (void)hipEventDestroy(q.copied);
     }
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    if (c->h_chunks) (void)hipHostFree(c->h_chunks);
-    if (c->d_chunks) (void)hipFree(c->d_chunks);
-    if (c->d_equal) (void)hipFree(c->d_equal);
-    if (c->h_jobs) (void)hipHostFree(c->h_jobs);
-    if (c->d_jobs) (void)hipFree(c->d_jobs);
-    if (c->d_state) (void)hipFree(c->d_state);
-    if (c->d_digests) (void)hipFree(c->d_digests);
-    if (c->d_zslots) (void)hipFree(c->d_zslots);
-    if (c->d_zout) (void)hipFree(c->d_zout);
-    if (c->d_ztoks) (void)hipFree(c->d_ztoks);
-    if (c->d_zsizes) (void)hipFree(c->d_zsizes);
-    if (c->d_zprefix) (void)hipFree(c->d_zprefix);
-    if (c->h_zsizes) (void)hipHostFree(c->h_zsizes);
-    if (c->h_zprefix) (void)hipHostFree(c->h_zprefix);
-    for (uint8_t* z : c->h_zout) if (z) (void)hipHostFree(z);
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->z_stream) (void)hipStreamDestroy(c->z_stream);
     if (c->z2_stream) (void)hipStreamDestroy(c->z2_stream);
+    if (c->f_stream) (void)hipStreamDestroy(c->f_stream);
     for (hipEvent_t e : c->z_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->z_part_ev) (void)hipEventDestroy(e);
     for (EventPair& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1477,11 +1341,11 @@ static void calibrate_at_init(snaphash_ctx* x)
     bool ok = true;
     for (hipEvent_t& ev : e) ok = ok && hipEventCreate(&ev) == hipSuccess;
     if (ok) {
-        ok = hipMemcpyAsync(s.d_buf, s.h_buf, small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess; // warm: the first copy of a stream pays for its set-up
+        ok = hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess; // warm: the first copy of a stream pays for its set-up
         ok = ok && hipEventRecord(e[0], c->copy_stream) == hipSuccess;
-        ok = ok && hipMemcpyAsync(s.d_buf, s.h_buf, small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
         ok = ok && hipEventRecord(e[1], c->copy_stream) == hipSuccess;
-        ok = ok && hipMemcpyAsync(s.d_buf, s.h_buf, big, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), big, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
         ok = ok && hipEventRecord(e[2], c->copy_stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(c->copy_stream) == hipSuccess;
         float t_small = 0, t_big = 0;
@@ -1662,7 +1526,7 @@ void snaphash_destroy(snaphash_ctx* x)
     if (!x) return;
     if (x->open_batch) snaphash_batch_abort(x->open_batch);
     for (size_t d = 0; d < x->d_gather.size(); ++d)
-        if (x->d_gather[d]) { (void)hipSetDevice(x->dev[d]->device); (void)hipFree(x->d_gather[d]); }
+        if (x->d_gather[d].data()) { (void)hipSetDevice(x->dev[d]->device); x->d_gather[d].reset(); }
     if (x->rccl.ok)
         for (ncclComm_t c : x->rccl.comms) if (c) (void)x->rccl.CommDestroy(c);
     for (auto& d : x->dev) destroy_dev(d.get());
@@ -1721,14 +1585,11 @@ try {
     begin_top(x);
     begin_call(c);
     if (n == 0) return SNAPHASH_OK;
-    rc = ensure_state(c, n, false);
-    if (rc) return lift(x, c, rc);
-    rc = ensure_jobs(c, &c->h_jobs, &c->d_jobs, &c->jobs_cap, n);
-    if (rc) return lift(x, c, rc);
+    HIP_TRY(x, c->hash.ensure(n, false, n));
     for (size_t i = 0; i < n; ++i) {
         if (offsets[i] & 15) return fail(x, SNAPHASH_EINVAL, "offsets must be 16-byte aligned");
         if (lens[i] >> 35) return fail(x, SNAPHASH_EINVAL, "a resident stream is limited to 32 GiB per call (32-bit block counters)");
-        Job& j = c->h_jobs[i];
+        Job& j = c->hash.jobs.h[i];
         j.data = (uint64_t)(uintptr_t)d_base + offsets[i];
         j.nbytes = lens[i];
         j.total_prev = 0;
@@ -1738,7 +1599,7 @@ try {
         c->stats.blocks += padded_blocks(lens[i], true);
     }
     c->stats.streams = n;
-    return lift(x, c, launch_jobs(c, c->h_jobs, c->d_jobs, n, (uint8_t*)d_digests));
+    return lift(x, c, launch_jobs(c, c->hash.jobs.h.data(), c->hash.jobs.d.data(), n, (uint8_t*)d_digests));
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -2412,10 +2273,10 @@ int batch_flush(snaphash_batch* b)
         EventPair* ev = next_events(c, 1);
         if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
         HIP_TRY(c, hipEventRecord(ev->a, c->copy_stream));
-        HIP_TRY(c, hipMemcpyAsync(sl.d_buf, sl.h_buf, b->used, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), b->used, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(c, hipEventRecord(ev->b, c->copy_stream));
     }
-    int rc = launch_jobs(c, sl.h_jobs, sl.d_jobs, b->nj, c->d_digests, sl.copied);
+    int rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), b->nj, c->hash.d_digests.data(), sl.copied);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(sl.done, c->stream));
     sl.busy = true;
@@ -2426,7 +2287,8 @@ int batch_flush(snaphash_batch* b)
     b->nj = 0;
     Slot& nx = cur_slot(b);
     if (nx.busy) { HIP_TRY(c, hipEventSynchronize(nx.done)); nx.busy = false; }
-    return ensure_jobs(c, &nx.h_jobs, &nx.d_jobs, &nx.jobs_cap, std::max<size_t>(b->n, 1024));
+    HIP_TRY(c, nx.jobs.ensure(b->n));
+    return SNAPHASH_OK;
 }
 
 // Places `n` bytes (p1[0..n1) then p2[0..n-n1)) of stream s into staging as (part of) a job.
@@ -2442,8 +2304,8 @@ int batch_place(snaphash_batch* b, size_t s, const uint8_t* p1, size_t n1, const
         const size_t left = left1 + left2;
         bool extend = false;
         if (st.job >= 0) {
-            const Job& j = sl.h_jobs[st.job];
-            const uint64_t end = (j.data - (uint64_t)(uintptr_t)sl.d_buf) + j.nbytes;
+            const Job& j = sl.jobs.h[st.job];
+            const uint64_t end = (j.data - (uint64_t)(uintptr_t)sl.d_buf.data()) + j.nbytes;
             if ((size_t)st.job == b->nj - 1 && end == b->used) extend = true; // contiguous with its own last bytes
             else { int rc = batch_flush(b); if (rc) return rc; continue; }   // one segment per stream per launch
         }
@@ -2456,27 +2318,27 @@ int batch_place(snaphash_batch* b, size_t s, const uint8_t* p1, size_t n1, const
             if (rc) return rc;
             continue;
         }
-        if (!extend && b->nj >= cur_slot(b).jobs_cap) { int rc = batch_flush(b); if (rc) return rc; continue; }
+        if (!extend && b->nj >= cur_slot(b).jobs.size()) { int rc = batch_flush(b); if (rc) return rc; continue; }
         const bool fin = final && take == left;
-        uint8_t* dst = sl.h_buf + at;
+        uint8_t* dst = sl.h_buf.data() + at;
         size_t t1 = std::min<size_t>(left1, take), t2 = (size_t)take - t1;
         if (t1) memcpy(dst, p1 + (n1 - left1), t1);
         if (t2) memcpy(dst + t1, p2 + (n2 - left2), t2);
         left1 -= t1;
         left2 -= t2;
         if (extend) {
-            Job& j = sl.h_jobs[st.job];
+            Job& j = sl.jobs.h[st.job];
             j.nbytes += take;
             if (fin) j.flags |= kJobFinal;
         } else {
             Job j;
-            j.data = (uint64_t)(uintptr_t)(sl.d_buf + at);
+            j.data = (uint64_t)(uintptr_t)(sl.d_buf.data() + at);
             j.nbytes = take;
             j.total_prev = st.done;
             j.idx = (uint32_t)s;
             j.flags = (st.done == 0 ? kJobFirst : 0u) | (fin ? kJobFinal : 0u);
             st.job = (int64_t)b->nj;
-            sl.h_jobs[b->nj++] = j;
+            sl.jobs.h[b->nj++] = j;
             b->in_slot.push_back((uint32_t)s);
         }
         c->stats.blocks += (take >> 7) + (fin ? padded_blocks(take & 127, true) : 0);
@@ -2498,10 +2360,10 @@ try {
     if (n_streams > 0xffffffffull) return fail(x, SNAPHASH_EINVAL, "too many streams");
     TOP_ENTER(x);
     DevCtx* c = x->d0();
-    int rc = ensure_slots(c);
-    if (!rc) rc = ensure_state(c, std::max<size_t>(n_streams, 1), true);
-    if (!rc) rc = ensure_jobs(c, &c->slot[0].h_jobs, &c->slot[0].d_jobs, &c->slot[0].jobs_cap, std::max<size_t>(n_streams, 1024));
+    const int rc = ensure_slots(c);
     if (rc) return lift(x, c, rc);
+    HIP_TRY(x, c->hash.ensure(std::max<size_t>(n_streams, 1), true));
+    HIP_TRY(x, c->slot[0].jobs.ensure(n_streams));
     snaphash_batch* b = new (std::nothrow) snaphash_batch();
     if (!b) return fail(x, SNAPHASH_ENOMEM, "new");
     b->x = x;
@@ -2572,7 +2434,7 @@ try {
     if (!rc) rc = lift(x, c, batch_flush(b));
     if (!rc) rc = lift(x, c, sync_ctx(c));
     c->slot[0].busy = c->slot[1].busy = false;
-    if (!rc && b->n && hipMemcpy(digests, c->d_digests, b->n * 64, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!rc && b->n && hipMemcpy(digests, c->hash.d_digests.data(), b->n * 64, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(x, SNAPHASH_EDEVICE, "D2H of the digests failed");
     c->stats.streams = b->n;
     merge_stats(x);
@@ -2611,15 +2473,9 @@ namespace {
 // and uploaded while the kernel of batch k still reads its own.
 int ensure_chunks(DevCtx* c, size_t n)
 {
-    if (n <= c->chunks_cap) return SNAPHASH_OK;
-    const size_t want = std::max<size_t>(n, 4096);
+    if (2 * n <= c->cmp.size()) return SNAPHASH_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // nothing may still read the old tables
-    if (c->h_chunks) (void)hipHostFree(c->h_chunks);
-    if (c->d_chunks) (void)hipFree(c->d_chunks);
-    c->h_chunks = nullptr; c->d_chunks = nullptr; c->chunks_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_chunks, 2 * want * sizeof(CmpChunk), hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc((void**)&c->d_chunks, 2 * want * sizeof(CmpChunk)));
-    c->chunks_cap = want;
+    HIP_TRY(c, c->cmp.ensure(2 * std::max<size_t>(n, 4096)));
     return SNAPHASH_OK;
 }
 
@@ -2633,8 +2489,8 @@ int launch_compare_ranges(DevCtx* c, const std::vector<uint64_t>& a, const std::
     if (nchunks > 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many comparison chunks");
     int rc = ensure_chunks(c, nchunks);
     if (rc) return rc;
-    CmpChunk* h_tab = c->h_chunks + (size_t)half * c->chunks_cap;
-    CmpChunk* d_tab = c->d_chunks + (size_t)half * c->chunks_cap;
+    CmpChunk* h_tab = c->cmp.h.data() + (size_t)half * (c->cmp.size() / 2);
+    CmpChunk* d_tab = c->cmp.d.data() + (size_t)half * (c->cmp.size() / 2);
     size_t k = 0;
     for (size_t i = 0; i < n; ++i)
         for (uint64_t off = 0; off < lens[i]; off += kCmpChunk) {
@@ -2733,7 +2589,7 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
     uint64_t slot_want = 8u << 20;
     while (slot_want < c->staging && slot_want < 2 * total) slot_want <<= 1;
     slot_want = std::min<uint64_t>(slot_want, c->staging);
-    for (const Slot& sl : c->slot) slot_want = std::max<uint64_t>(slot_want, std::min<uint64_t>(sl.cap, c->staging));
+    for (const Slot& sl : c->slot) slot_want = std::max<uint64_t>(slot_want, std::min<uint64_t>(sl.cap(), c->staging));
     int rc = ensure_slots(c, 2, slot_want);
     if (rc) return rc;
     for (const CmpPair& p : todo) equal[p.idx] = 1; // AND-ed down batch by batch
@@ -2745,9 +2601,8 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
     struct Half {
         std::vector<Seg> segs;
         std::vector<uint8_t> ok;
-        uint8_t* h_res = nullptr; // pinned
-        uint8_t* d_eq = nullptr;
-        size_t cap = 0;
+        HostBuf<uint8_t> h_res;
+        DevBuf<uint8_t> d_eq;
         hipEvent_t done = nullptr, copied = nullptr;
         bool busy = false;
     } hf[2];
@@ -2761,8 +2616,6 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
     };
     auto cleanup = [&]() {
         for (Half& h : hf) {
-            if (h.h_res) (void)hipHostFree(h.h_res);
-            if (h.d_eq) (void)hipFree(h.d_eq);
             if (h.done) (void)hipEventDestroy(h.done);
             if (h.copied) (void)hipEventDestroy(h.copied);
         }
@@ -2793,19 +2646,14 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
         c->pool.parallel_for(h.segs.size(), (unsigned)std::min<size_t>(c->fill_cap, std::max<size_t>(1, h.segs.size() / 2)), [&](size_t i) {
             const Seg& g = h.segs[i];
             const CmpPair& p = todo[g.t];
-            if (!read_exact(a[p.idx], g.off, g.n, c->slot[0].h_buf + g.at) ||
-                !read_exact(b[p.idx], g.off, g.n, c->slot[1].h_buf + g.at))
+            if (!read_exact(a[p.idx], g.off, g.n, c->slot[0].h_buf.data() + g.at) ||
+                !read_exact(b[p.idx], g.off, g.n, c->slot[1].h_buf.data() + g.at))
                 h.ok[i] = 0;
         });
-        if (h.segs.size() > h.cap) {
-            if (h.h_res) (void)hipHostFree(h.h_res);
-            if (h.d_eq) (void)hipFree(h.d_eq);
-            h.h_res = nullptr; h.d_eq = nullptr;
-            h.cap = std::max<size_t>(h.segs.size(), 4096);
-            if (hipMalloc((void**)&h.d_eq, h.cap) != hipSuccess || hipHostMalloc((void**)&h.h_res, h.cap, hipHostMallocDefault) != hipSuccess) {
-                rc = fail(c, SNAPHASH_ENOMEM, "allocation of the verdict buffers failed");
-                break;
-            }
+        const size_t verdicts = std::max<size_t>(h.segs.size(), 4096);
+        if (h.d_eq.reserve(verdicts) != hipSuccess || h.h_res.reserve(verdicts, -1) != hipSuccess) {
+            rc = fail(c, SNAPHASH_ENOMEM, "allocation of the verdict buffers failed");
+            break;
         }
         if (!h.done && (hipEventCreateWithFlags(&h.done, hipEventDisableTiming) != hipSuccess ||
                         hipEventCreateWithFlags(&h.copied, hipEventDisableTiming) != hipSuccess)) {
@@ -2815,8 +2663,8 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
         EventPair* ev = next_events(c, 1);
         if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
         if (hipEventRecord(ev->a, c->copy_stream) != hipSuccess ||
-            hipMemcpyAsync(c->slot[0].d_buf + base, c->slot[0].h_buf + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
-            hipMemcpyAsync(c->slot[1].d_buf + base, c->slot[1].h_buf + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
+            hipMemcpyAsync(c->slot[0].d_buf.data() + base, c->slot[0].h_buf.data() + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
+            hipMemcpyAsync(c->slot[1].d_buf.data() + base, c->slot[1].h_buf.data() + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
             hipEventRecord(ev->b, c->copy_stream) != hipSuccess || hipEventRecord(h.copied, c->copy_stream) != hipSuccess ||
             hipStreamWaitEvent(c->stream, h.copied, 0) != hipSuccess) {
             rc = fail(c, SNAPHASH_EDEVICE, "H2D of a comparison batch failed");
@@ -2824,13 +2672,13 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
         }
         std::vector<uint64_t> va(h.segs.size()), vb(h.segs.size()), vl(h.segs.size());
         for (size_t i = 0; i < h.segs.size(); ++i) {
-            va[i] = (uint64_t)(uintptr_t)(c->slot[0].d_buf + h.segs[i].at);
-            vb[i] = (uint64_t)(uintptr_t)(c->slot[1].d_buf + h.segs[i].at);
+            va[i] = (uint64_t)(uintptr_t)(c->slot[0].d_buf.data() + h.segs[i].at);
+            vb[i] = (uint64_t)(uintptr_t)(c->slot[1].d_buf.data() + h.segs[i].at);
             vl[i] = h.segs[i].n;
         }
-        rc = launch_compare_ranges(c, va, vb, vl, h.d_eq, (int)(batch & 1));
+        rc = launch_compare_ranges(c, va, vb, vl, h.d_eq.data(), (int)(batch & 1));
         if (rc) break;
-        if (hipMemcpyAsync(h.h_res, h.d_eq, h.segs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        if (hipMemcpyAsync(h.h_res.data(), h.d_eq.data(), h.segs.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipEventRecord(h.done, c->stream) != hipSuccess) {
             rc = fail(c, SNAPHASH_EDEVICE, "D2H of the verdicts failed");
             break;
@@ -3062,11 +2910,12 @@ try {
     if (n == 0) return SNAPHASH_OK;
     DevCtx* c = x->d0();
     HIP_TRY(c, hipSetDevice(c->device));
-    uint64_t* d = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d, 3 * n * sizeof(uint64_t)));
+    DevBuf<uint64_t> buf;
+    HIP_TRY(c, buf.reserve(3 * n));
+    uint64_t* d = buf.data();
     uint64_t maxlen = 0;
     for (size_t i = 0; i < n; ++i) {
-        if (offsets[i] & 7) { (void)hipFree(d); return fail(x, SNAPHASH_EINVAL, "offsets must be 8-byte aligned"); }
+        if (offsets[i] & 7) return fail(x, SNAPHASH_EINVAL, "offsets must be 8-byte aligned");
         maxlen = std::max(maxlen, lens[i]);
     }
     hipError_t e = hipMemcpyAsync(d, offsets, n * 8, hipMemcpyHostToDevice, c->stream);
@@ -3074,7 +2923,6 @@ try {
     if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * n, file_index, n * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_fill_synthetic((uint8_t*)d_base, d, d + n, d + 2 * n, (uint32_t)n, maxlen, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(x, SNAPHASH_EDEVICE, std::string("fill_synthetic: ") + hipGetErrorString(e));
     return SNAPHASH_OK;
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
@@ -3122,32 +2970,15 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
-// what an engine holds right now: pinned host bytes and HBM bytes (staging slots, job arrays, chaining values, digests,
-// comparison and deflate scratch)
+// what an engine holds right now: pinned host bytes and HBM bytes (every buffer of DevCtx::each_buf, and its share of the
+// gather buffers)
 static void engine_footprint(const snaphash_ctx* x, size_t i, uint64_t* pinned, uint64_t* hbm)
 {
-    const DevCtx* d = x->dev[i].get();
-    uint64_t p = 0, h = 0;
-    for (const Slot& s : d->slot) {
-        if (s.h_buf) p += s.cap;
-        if (s.d_buf) h += s.cap + 256;
-        p += s.jobs_cap * sizeof(Job);
-        h += s.jobs_cap * sizeof(Job);
-    }
-    for (const SubSlot& q : d->sub) { // the job arrays of the batches in flight (pinned and HBM twins)
-        p += q.jobs_cap * sizeof(Job);
-        h += q.jobs_cap * sizeof(Job);
-    }
-    p += d->jobs_cap * sizeof(Job) + d->chunks_cap * sizeof(CmpChunk);
-    h += d->jobs_cap * sizeof(Job) + d->chunks_cap * sizeof(CmpChunk) + d->state_cap * 64 + d->digests_cap * 64 + d->equal_cap;
-    if (d->z_chunks) { // deflate scratch (targz.inc ensure_deflate)
-        const uint64_t nch = d->z_chunks;
-        h += 2 * nch * (uint64_t)kDeflateSlot + nch * (uint64_t)kDeflateTokWords * 4 + nch * 4 + (nch + 1) * 8;
-        p += nch * 4 + (nch + 1) * 8 + 2 * nch * (uint64_t)kDeflateSlot;
-    }
-    if (i < x->d_gather.size() && x->d_gather[i]) h += (uint64_t)x->dev.size() * x->gather_cap * 64;
-    *pinned = p;
-    *hbm = h;
+    Footprint f;
+    x->dev[i]->each_buf(f);
+    if (i < x->d_gather.size()) f(x->d_gather[i]);
+    *pinned = f.pinned;
+    *hbm = f.hbm;
 }
 
 int snaphash_get_engine_info(const snaphash_ctx* c, uint32_t i, snaphash_engine_info* out)

@@ -22,7 +22,7 @@ namespace {
         }                                                                                            \
     }
 
-// One piece of output on its way to the consumers.  buf >= 0: the bytes lie in the pinned buffer h_zout[buf], which
+// One piece of output on its way to the consumers.  buf >= 0: the bytes lie in the pinned buffer z.h_out[buf], which
 // the producer reuses once every consumer has let go of it; buf < 0: a small piece the item owns.
 struct GzItem {
     const uint8_t* p = nullptr;
@@ -46,7 +46,7 @@ struct GzPipe {
     std::mutex mu;
     std::condition_variable cv;
     std::queue<GzItem> q_sha, q_wr;
-    int inflight[2] = {0, 0};    // consumers still reading h_zout[b]
+    int inflight[2] = {0, 0};    // consumers still reading z.h_out[b]
     int write_err = 0;
     bool closing = false;
     double busy_ms[2] = {0, 0}, wait_ms[2] = {0, 0}; // per consumer (digest, writer): working / waiting for the producer
@@ -91,31 +91,12 @@ int ensure_deflate(DevCtx* c, uint64_t slot_bytes)
         HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
     }
     if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking)); // concatenation + the way back
-    if (c->z_chunks >= nch) return SNAPHASH_OK;
-    // (grown: what a smaller job left behind goes first; a call that fails half-way keeps what it got and the next call
-    // allocates only what is still missing)
-    if (c->z_chunks != 0) {
-        (void)hipFree(c->d_zslots); (void)hipFree(c->d_zout); (void)hipFree(c->d_ztoks); (void)hipFree(c->d_zsizes); (void)hipFree(c->d_zprefix);
-        (void)hipHostFree(c->h_zsizes); (void)hipHostFree(c->h_zprefix);
-        for (int b = 0; b < 2; ++b) { (void)hipHostFree(c->h_zout[b]); c->h_zout[b] = nullptr; }
-        c->d_zslots = nullptr; c->d_zout = nullptr; c->d_ztoks = nullptr; c->d_zsizes = nullptr; c->d_zprefix = nullptr;
-        c->h_zsizes = nullptr; c->h_zprefix = nullptr;
-        c->z_chunks = 0;
-    }
-    if (!c->d_zslots) HIP_TRY(c, hipMalloc((void**)&c->d_zslots, nch * (size_t)kDeflateSlot));
-    if (!c->d_zout) HIP_TRY(c, hipMalloc((void**)&c->d_zout, nch * (size_t)kDeflateSlot));
-    if (!c->d_ztoks) HIP_TRY(c, hipMalloc((void**)&c->d_ztoks, nch * (size_t)kDeflateTokWords * 4));
-    if (!c->d_zsizes) HIP_TRY(c, hipMalloc((void**)&c->d_zsizes, nch * 4));
-    if (!c->d_zprefix) HIP_TRY(c, hipMalloc((void**)&c->d_zprefix, nch * 8));
-    if (!c->h_zsizes) HIP_TRY(c, host_alloc(c, (void**)&c->h_zsizes, nch * 4));
-    if (!c->h_zprefix) HIP_TRY(c, host_alloc(c, (void**)&c->h_zprefix, nch * 8));
-    for (int b = 0; b < 2; ++b)
-        if (!c->h_zout[b]) HIP_TRY(c, host_alloc(c, (void**)&c->h_zout[b], nch * (size_t)kDeflateSlot));
-    c->z_chunks = nch;
+    // (grown: what a smaller job left behind goes first; a failure leaves none of it, and the next call allocates it all)
+    HIP_TRY(c, c->z.ensure(nch, c->numa_node));
     return SNAPHASH_OK;
 }
 
-// buf >= 0: p points into h_zout[buf] (stays valid until gz_wait_buf(buf) returns); buf < 0: p is copied.
+// buf >= 0: p points into z.h_out[buf] (stays valid until gz_wait_buf(buf) returns); buf < 0: p is copied.
 void gz_emit(GzPipe& g, const uint8_t* p, size_t n, int buf)
 {
     if (n == 0) return;
@@ -216,7 +197,7 @@ uint32_t crc_parallel(const uint8_t* p, size_t n)
     return crc;
 }
 
-// A slot's bytes -> deflate chunks -> concatenation -> pinned h_zout[zbuf] -> the consumers.
+// A slot's bytes -> deflate chunks -> concatenation -> pinned z.h_out[zbuf] -> the consumers.
 // The slot is compressed in pieces of kZPiece chunks: all chunk kernels are enqueued at once on the compressor's
 // stream; as each piece's sizes arrive its bytes are concatenated and brought back on a second stream and handed to
 // the consumers, while the later pieces are still being compressed -- the archive digest (the stream that bounds the
@@ -250,7 +231,7 @@ struct ZPieces {
 
 // One slot on its way through the compressor, in three steps so that the pass's first slot can be compressed while it
 // is still being filled: begin (cut into pieces), launch (the pieces whose bytes are in HBM), consume (sizes -> prefix
-// -> concatenation -> pinned h_zout -> the consumers).
+// -> concatenation -> pinned z.h_out -> the consumers).
 int gz_slot_begin(GzPipe& g, uint64_t n, bool is_first, bool is_last)
 {
     DevCtx* c = g.c;
@@ -281,9 +262,9 @@ int gz_slot_launch(GzPipe& g, Slot& sl, uint64_t n, uint64_t bytes_ready, hipEve
         const uint32_t c0 = g.z_pieces[g.z_launched].first, cnt = g.z_pieces[g.z_launched].second;
         if (bytes_ready < n && (uint64_t)(c0 + cnt) * kDeflateChunk > bytes_ready) break;
         if (ready && !waited) { HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0)); waited = true; }
-        const hipError_t e = launch_deflate_chunks(sl.d_buf, n, c->d_zslots, c->d_zsizes, c->d_ztoks, c0, cnt, g.z_nch, c->n_xcd, c->deflate_depth, zs);
+        const hipError_t e = launch_deflate_chunks(sl.d_buf.data(), n, c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_toks.data(), c0, cnt, g.z_nch, c->n_xcd, c->deflate_depth, zs);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("deflate launch: ") + hipGetErrorString(e));
-        HIP_TRY(c, hipMemcpyAsync(c->h_zsizes + c0, c->d_zsizes + c0, (size_t)cnt * 4, hipMemcpyDeviceToHost, zs));
+        HIP_TRY(c, hipMemcpyAsync(c->z.h_sizes.data() + c0, c->z.d_sizes.data() + c0, (size_t)cnt * 4, hipMemcpyDeviceToHost, zs));
         HIP_TRY(c, hipEventRecord(c->z_ev[g.z_launched], zs));
         if (++g.z_launched == g.z_pieces.size()) HIP_TRY(c, hipEventRecord(g.z_evpair.b, zs));
     }
@@ -300,7 +281,7 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
     struct CrcJob { // joined on every way out
         std::future<uint32_t> f;
         ~CrcJob() { if (f.valid()) f.wait(); }
-    } crc_job{std::async(std::launch::async, crc_parallel, (const uint8_t*)sl.h_buf, (size_t)n)};
+    } crc_job{std::async(std::launch::async, crc_parallel, (const uint8_t*)sl.h_buf.data(), (size_t)n)};
     gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
     uint64_t total = 0;
     for (uint32_t k = 0; k < g.z_pieces.size(); ++k) {
@@ -308,21 +289,21 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
         HIP_TRY(c, hipEventSynchronize(c->z_ev[k]));
         const uint64_t base = total;
         for (uint32_t i = c0; i < c0 + cnt; ++i) {
-            c->h_zprefix[i] = total;
-            if (c->h_zsizes[i] > kDeflateSlot) return fail(c, SNAPHASH_EDEVICE, "deflate kernel reported an impossible chunk size");
-            if (c->h_zsizes[i] == deflate_stored_size((uint32_t)std::min<uint64_t>(kDeflateChunk, n - (uint64_t)i * kDeflateChunk))) g.st.stored_chunks++;
-            total += c->h_zsizes[i];
+            c->z.h_prefix[i] = total;
+            if (c->z.h_sizes[i] > kDeflateSlot) return fail(c, SNAPHASH_EDEVICE, "deflate kernel reported an impossible chunk size");
+            if (c->z.h_sizes[i] == deflate_stored_size((uint32_t)std::min<uint64_t>(kDeflateChunk, n - (uint64_t)i * kDeflateChunk))) g.st.stored_chunks++;
+            total += c->z.h_sizes[i];
         }
-        HIP_TRY(c, hipMemcpyAsync(c->d_zprefix + c0, c->h_zprefix + c0, (size_t)cnt * 8, hipMemcpyHostToDevice, z2));
+        HIP_TRY(c, hipMemcpyAsync(c->z.d_prefix.data() + c0, c->z.h_prefix.data() + c0, (size_t)cnt * 8, hipMemcpyHostToDevice, z2));
         EventPair* ev2 = next_events(c, 2);
         if (!ev2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
         HIP_TRY(c, hipEventRecord(ev2->a, z2));
-        const hipError_t e = launch_deflate_compact(c->d_zslots, c->d_zsizes, c->d_zprefix, c->d_zout, c0, cnt, z2);
+        const hipError_t e = launch_deflate_compact(c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_prefix.data(), c->z.d_out.data(), c0, cnt, z2);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("compact launch: ") + hipGetErrorString(e));
         HIP_TRY(c, hipEventRecord(ev2->b, z2));
-        HIP_TRY(c, hipMemcpyAsync(c->h_zout[zbuf] + base, c->d_zout + base, total - base, hipMemcpyDeviceToHost, z2));
+        HIP_TRY(c, hipMemcpyAsync(c->z.h_out[zbuf].data() + base, c->z.d_out.data() + base, total - base, hipMemcpyDeviceToHost, z2));
         HIP_TRY(c, hipStreamSynchronize(z2));
-        gz_emit(g, c->h_zout[zbuf] + base, total - base, zbuf);
+        gz_emit(g, c->z.h_out[zbuf].data() + base, total - base, zbuf);
     }
     HIP_TRY(c, hipStreamSynchronize(zs));
     const uint32_t crc = crc_job.f.get();
@@ -332,7 +313,7 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
     return SNAPHASH_OK;
 }
 
-// The slot's first n bytes (in sl.h_buf, and in sl.d_buf once `ready` has fired; ready == nullptr: already ordered on the
+// The slot's first n bytes (in sl.h_buf.data(), and in sl.d_buf.data() once `ready` has fired; ready == nullptr: already ordered on the
 // compressor's stream), all three steps.
 int gz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first = false, bool is_last = false)
 {
@@ -406,11 +387,11 @@ try {
     const double t0 = now_ms();
     for (uint64_t off = 0; off < n && !rc; off += S) {
         const uint64_t take = std::min<uint64_t>(S, n - off);
-        memcpy(sl.h_buf, (const uint8_t*)data + off, take);
+        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
         EventPair* ev = next_events(c, 1);
         if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
         if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
-            hipMemcpyAsync(sl.d_buf, sl.h_buf, take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
+            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
             hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
         rc = gz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
     }
@@ -507,15 +488,12 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
     const uint64_t S = producer_slot_bytes(c, plan.total); // a multiple of 512 and of the deflate chunk
     rc = ensure_slots(c, 2, S);
     if (!rc) rc = ensure_deflate(c, S);
-    if (!rc && nstreams) rc = ensure_state(c, nstreams, true);
     if (rc) return lift(x, c, rc);
+    if (nstreams) HIP_TRY(x, c->hash.ensure(nstreams, true));
 
     std::vector<Source> srcs(plan.members.size());
     for (size_t k = 0; k < plan.members.size(); ++k) { srcs[k].path = plan.members[k].path.c_str(); srcs[k].len = (uint64_t)plan.members[k].size; }
-    for (Slot& sl : c->slot) {
-        rc = ensure_jobs(c, &sl.h_jobs, &sl.d_jobs, &sl.jobs_cap, std::max<size_t>(nstreams, 1024));
-        if (rc) return lift(x, c, rc);
-    }
+    for (Slot& sl : c->slot) HIP_TRY(x, sl.jobs.ensure(nstreams));
 
     const double t_planned = now_ms();
     struct FdGuard { int fd; ~FdGuard() { if (fd >= 0) close(fd); } } fdg{open(tarname, O_WRONLY | O_CREAT | O_CLOEXEC, 0666)}; // os.Create, with the truncation moved to the END of the pass:
@@ -563,16 +541,16 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
             const uint64_t end = m.data_off + (((uint64_t)m.size + 511) & ~(uint64_t)511);
             if (m.first_off() >= s0 + n) break;
             if (!m.pax.empty() && m.hdr_off > s0) { // the PAX extended header in front of the member: record, data, padding
-                if (m.pax_off >= s0) tar_pax_header(m, sl.h_buf + (m.pax_off - s0));
+                if (m.pax_off >= s0) tar_pax_header(m, sl.h_buf.data() + (m.pax_off - s0));
                 const uint64_t x0 = m.pax_off + 512, x1 = x0 + m.pax.size(), xe = m.hdr_off; // data [x0, x1), zeros [x1, xe)
                 const uint64_t c0 = std::max(x0, s0), c1 = std::min(x1, s0 + n);
-                if (c1 > c0) memcpy(sl.h_buf + (c0 - s0), m.pax.data() + (c0 - x0), c1 - c0);
+                if (c1 > c0) memcpy(sl.h_buf.data() + (c0 - s0), m.pax.data() + (c0 - x0), c1 - c0);
                 const uint64_t z0 = std::max(x1, s0), z1 = std::min(xe, s0 + n);
-                if (z1 > z0) memset(sl.h_buf + (z0 - s0), 0, z1 - z0);
+                if (z1 > z0) memset(sl.h_buf.data() + (z0 - s0), 0, z1 - z0);
                 if (m.hdr_off >= s0 + n) break; // the member's own header starts in the next slot
             }
             if (m.hdr_off >= s0) { // header record (never straddles: offsets and S are multiples of 512)
-                f.rc = tar_header(m, sl.h_buf + (m.hdr_off - s0));
+                f.rc = tar_header(m, sl.h_buf.data() + (m.hdr_off - s0));
                 if (f.rc) {
                     f.err = "member does not fit a tar header: " + m.name;
                     return f;
@@ -580,21 +558,21 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
             }
             const uint64_t d0 = std::max<uint64_t>(m.data_off, s0), d1 = std::min<uint64_t>(m.data_off + (uint64_t)m.size, s0 + n);
             if (m.typeflag == '0' && d1 > d0)
-                ops.push_back(ReadOp{(uint32_t)mi, d0 - m.data_off, d1 - d0, sl.h_buf + (d0 - s0), d1 == m.data_off + (uint64_t)m.size});
+                ops.push_back(ReadOp{(uint32_t)mi, d0 - m.data_off, d1 - d0, sl.h_buf.data() + (d0 - s0), d1 == m.data_off + (uint64_t)m.size});
             const uint64_t p0 = std::max<uint64_t>(m.data_off + (uint64_t)m.size, s0), p1 = std::min<uint64_t>(end, s0 + n);
-            if (p1 > p0) memset(sl.h_buf + (p0 - s0), 0, p1 - p0); // padding to the 512-byte record
+            if (p1 > p0) memset(sl.h_buf.data() + (p0 - s0), 0, p1 - p0); // padding to the 512-byte record
             if (fused && hosted_of[mi] != 0xffffffffu) {
                 if (d1 > d0 || (m.size == 0 && m.hdr_off >= s0)) // (an empty member: one task of no bytes, where its header lies)
-                    host_tasks.push_back(MemberHashers::Task{hosted_of[mi], sl.h_buf + (d1 > d0 ? d0 - s0 : 0), d1 > d0 ? d1 - d0 : 0, d0 == m.data_off || m.size == 0,
+                    host_tasks.push_back(MemberHashers::Task{hosted_of[mi], sl.h_buf.data() + (d1 > d0 ? d0 - s0 : 0), d1 > d0 ? d1 - d0 : 0, d0 == m.data_off || m.size == 0,
                                                              d1 == m.data_off + (uint64_t)m.size || m.size == 0, slot_no});
             } else if (fused && stream_of[mi] != 0xffffffffu && (d1 > d0 || (m.size == 0 && m.hdr_off >= s0))) {
                 Job j; // the file's bytes where they lie in the staged tar stream
-                j.data = (uint64_t)(uintptr_t)(sl.d_buf + (d0 - s0));
+                j.data = (uint64_t)(uintptr_t)(sl.d_buf.data() + (d0 - s0));
                 j.nbytes = d1 > d0 ? d1 - d0 : 0;
                 j.total_prev = d0 - m.data_off;
                 j.idx = stream_of[mi];
                 j.flags = (d0 == m.data_off ? kJobFirst : 0u) | (d1 == m.data_off + (uint64_t)m.size ? kJobFinal : 0u);
-                sl.h_jobs[f.nj++] = j;
+                sl.jobs.h[f.nj++] = j;
                 f.blocks += padded_blocks(j.nbytes, (j.flags & kJobFinal) != 0);
                 f.bytes += j.nbytes;
             }
@@ -603,7 +581,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
         }
         if (s0 + n > plan.total - 1024) { // tar.Writer.Close: two zero records
             const uint64_t z0 = std::max<uint64_t>(plan.total - 1024, s0);
-            memset(sl.h_buf + (z0 - s0), 0, s0 + n - z0);
+            memset(sl.h_buf.data() + (z0 - s0), 0, s0 + n - z0);
         }
         if (in_parts) {
             if (hipSetDevice(c->device) != hipSuccess || hipEventRecord(ev.a, c->copy_stream) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "H2D failed"; return f; }
@@ -615,7 +593,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
             for (uint64_t b = 0; b < n; b += kPart, ++k) {
                 const uint64_t e = std::min(b + kPart, n);
                 part.clear();
-                while (o < ops.size() && (uint64_t)(ops[o].dst - sl.h_buf) < e) part.push_back(ops[o++]); // (a member that straddles e is read whole: its rest travels with the next part)
+                while (o < ops.size() && (uint64_t)(ops[o].dst - sl.h_buf.data()) < e) part.push_back(ops[o++]); // (a member that straddles e is read whole: its rest travels with the next part)
                 run_reads(c, srcs, part, first_err, first_err_src);
                 if (first_err.load()) break;
                 while (c->z_part_ev.size() <= k) {
@@ -623,7 +601,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
                     if (hipEventCreateWithFlags(&pe, hipEventDisableTiming) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "hipEventCreate failed"; return f; }
                     c->z_part_ev.push_back(pe);
                 }
-                if (hipMemcpyAsync(sl.d_buf + b, sl.h_buf + b, e - b, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
+                if (hipMemcpyAsync(sl.d_buf.data() + b, sl.h_buf.data() + b, e - b, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
                     hipEventRecord(c->z_part_ev[k], c->copy_stream) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "H2D failed"; return f; }
                 f.rc = gz_slot_launch(g, sl, n, e, c->z_part_ev[k]);
                 if (f.rc) { f.err = c->last_error; return f; }
@@ -639,7 +617,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
         // the slot's HBM was last read by the hashing kernels of two slots ago (its compression has been waited for)
         if (hipSetDevice(c->device) != hipSuccess || (sl.busy && hipStreamWaitEvent(c->copy_stream, sl.done, 0) != hipSuccess) ||
             hipEventRecord(ev.a, c->copy_stream) != hipSuccess ||
-            hipMemcpyAsync(sl.d_buf, sl.h_buf, n, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
+            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), n, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
             hipEventRecord(ev.b, c->copy_stream) != hipSuccess) {
             f.rc = SNAPHASH_EDEVICE;
             f.err = "H2D failed";
@@ -668,7 +646,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
         c->stats.blocks += f.blocks;
         c->stats.bytes_hashed += f.bytes;
         if (f.nj) { // SHA-512 of the files, from the same staged bytes; records sl.copied behind the job list's copy
-            rc = launch_jobs(c, sl.h_jobs, sl.d_jobs, f.nj, c->d_digests, sl.copied);
+            rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), f.nj, c->hash.d_digests.data(), sl.copied);
             if (rc) break;
             HIP_TRY_BREAK(hipEventRecord(sl.done, c->stream));
             sl.busy = true;
@@ -716,7 +694,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
     collect_targz_events(c, g);
     c->pending = false;
     std::vector<uint8_t> dig(nstreams * 64 + 64);
-    if (!rc && nstreams && hipMemcpy(dig.data(), c->d_digests, nstreams * 64, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!rc && nstreams && hipMemcpy(dig.data(), c->hash.d_digests.data(), nstreams * 64, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(c, SNAPHASH_EDEVICE, "D2H of the digests failed");
     if (!hosted_sizes.empty()) { // the long members' digests, from their host threads
         if (!rc) mh.wait_all();

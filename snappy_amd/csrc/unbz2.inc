@@ -8,82 +8,23 @@
 
 namespace {
 
-void free_bzip2_bufs(DevCtx* c)
-{
-    if (c->d_bin) (void)hipFree(c->d_bin);
-    if (c->d_bcand) (void)hipFree(c->d_bcand);
-    if (c->h_bcand) (void)hipHostFree(c->h_bcand);
-    if (c->d_bcount) (void)hipFree(c->d_bcount);
-    if (c->h_bcount) (void)hipHostFree(c->h_bcount);
-    if (c->d_bslots) (void)hipFree(c->d_bslots);
-    if (c->d_btt) (void)hipFree(c->d_btt);
-    if (c->d_bchunks) (void)hipFree(c->d_bchunks);
-    if (c->d_bres) (void)hipFree(c->d_bres);
-    if (c->h_bres) (void)hipHostFree(c->h_bres);
-    if (c->d_bblk) (void)hipFree(c->d_bblk);
-    if (c->h_bblk) (void)hipHostFree(c->h_bblk);
-    c->d_bin = nullptr; c->d_bcand = nullptr; c->h_bcand = nullptr; c->d_bcount = nullptr; c->h_bcount = nullptr;
-    c->d_bslots = nullptr; c->d_btt = nullptr; c->d_bchunks = nullptr; c->d_bres = nullptr; c->h_bres = nullptr;
-    c->d_bblk = nullptr; c->h_bblk = nullptr;
-    c->bin_cap = 0; c->bcand_cap = 0; c->bslots_cap = 0;
-}
-
 // A launch's slots hold the BWT bytes (then the inverse BWT's output), the T vector and the RLE1 chunk states of one
 // block each: 4.5 MB.  kBzLaunchSlots of them (1.2 GB) bound the scratch whatever the input; a larger input takes more
 // launches.  The piece (compressed bytes a launch's candidates come from) is at most the staging size, 64 MiB.
 constexpr uint32_t kBzLaunchSlots = 256;
 
-int ensure_bzip2_try(DevCtx* c, uint64_t piece, uint32_t slots)
-{
-    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
-    if (!c->d_bcount) HIP_TRY(c, hipMalloc((void**)&c->d_bcount, 16));
-    if (!c->h_bcount) HIP_TRY(c, host_alloc(c, (void**)&c->h_bcount, 16));
-    if (c->bin_cap < piece) {
-        if (c->d_bin) (void)hipFree(c->d_bin);
-        if (c->d_bcand) (void)hipFree(c->d_bcand);
-        if (c->h_bcand) (void)hipHostFree(c->h_bcand);
-        c->d_bin = nullptr; c->d_bcand = nullptr; c->h_bcand = nullptr; c->bin_cap = 0; c->bcand_cap = 0;
-        const uint64_t cand = bz_candidate_cap(piece);
-        HIP_TRY(c, hipMalloc((void**)&c->d_bin, piece + 16));
-        HIP_TRY(c, hipMalloc((void**)&c->d_bcand, cand * 8));
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_bcand, cand * 8));
-        c->bin_cap = piece;
-        c->bcand_cap = cand;
-    }
-    if (c->bslots_cap < slots) {
-        if (c->d_bslots) (void)hipFree(c->d_bslots);
-        if (c->d_btt) (void)hipFree(c->d_btt);
-        if (c->d_bchunks) (void)hipFree(c->d_bchunks);
-        if (c->d_bres) (void)hipFree(c->d_bres);
-        if (c->h_bres) (void)hipHostFree(c->h_bres);
-        if (c->d_bblk) (void)hipFree(c->d_bblk);
-        if (c->h_bblk) (void)hipHostFree(c->h_bblk);
-        c->d_bslots = nullptr; c->d_btt = nullptr; c->d_bchunks = nullptr; c->d_bres = nullptr; c->h_bres = nullptr;
-        c->d_bblk = nullptr; c->h_bblk = nullptr; c->bslots_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_bslots, (size_t)slots * kBzMaxBlock));
-        HIP_TRY(c, hipMalloc((void**)&c->d_btt, (size_t)slots * kBzMaxBlock * 4));
-        HIP_TRY(c, hipMalloc((void**)&c->d_bchunks, (size_t)slots * kBzChunks * 8));
-        HIP_TRY(c, hipMalloc((void**)&c->d_bres, (size_t)slots * sizeof(BzBlockRes)));
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_bres, (size_t)slots * sizeof(BzBlockRes)));
-        HIP_TRY(c, hipMalloc((void**)&c->d_bblk, (size_t)slots * sizeof(BzGpuBlock)));
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_bblk, (size_t)slots * sizeof(BzGpuBlock)));
-        c->bslots_cap = slots;
-    }
-    return SNAPHASH_OK;
-}
-
 // the scratch of a job, sized for it; on any allocation failure none is left behind
 int ensure_bzip2(DevCtx* c, uint64_t piece, uint32_t slots)
 {
-    const int rc = ensure_bzip2_try(c, piece, slots);
-    if (rc) free_bzip2_bufs(c);
-    return rc;
+    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    HIP_TRY(c, c->bz.ensure(piece, slots, c->numa_node));
+    return SNAPHASH_OK;
 }
 
 #define BZ_TRY(expr) HIP_TRY(c, (expr))
 
-// The later stages of the nb linked blocks in c->h_bblk (their stored CRCs in crcs): the inverse BWT and the RLE1 count,
-// the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->d_fout (after the decoded
+// The later stages of the nb linked blocks in c->bz.h_blk (their stored CRCs in crcs): the inverse BWT and the RLE1 count,
+// the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->inf.d_out (after the decoded
 // stream so far when keep_dev), the bytes back to out, and every block's CRC checked on host threads, one block each
 // (bz_crc_block runs at about 0.4 GB/s a core: the host threads keep pace with the kernels; DESIGN.md sec. 15).
 int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uint32_t>& crcs, std::vector<uint8_t>& out, bool keep_dev,
@@ -93,14 +34,14 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         float ms = 0;
         if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
     };
-    BZ_TRY(hipMemcpyAsync(c->d_bblk, c->h_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    BZ_TRY(hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
     EventPair* ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-    BZ_TRY(launch_bz_ibwt(c->d_bslots, c->d_btt, c->d_bblk, nb, c->f_stream));
-    BZ_TRY(launch_bz_rle1_count(c->d_bslots, c->d_bblk, c->d_bchunks, nb, c->f_stream));
+    BZ_TRY(launch_bz_ibwt(c->bz.d_slots.data(), c->bz.d_tt.data(), c->bz.d_blk.data(), nb, c->f_stream));
+    BZ_TRY(launch_bz_rle1_count(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->f_stream));
     BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-    BZ_TRY(hipMemcpyAsync(c->h_bblk, c->d_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
+    BZ_TRY(hipMemcpyAsync(c->bz.h_blk.data(), c->bz.d_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
     BZ_TRY(hipStreamSynchronize(c->f_stream));
     timed(ev);
     const size_t o0 = out.size();
@@ -108,20 +49,20 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
     uint64_t total = 0;
     for (uint32_t i = 0; i < nb; ++i) {
         // (a broken inverse BWT walk; a corrupt block that walks leaves it to the block CRC, as libbz2 and Go do)
-        if (c->h_bblk[i].status != kBzOk) return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt block (inverse BWT)");
-        c->h_bblk[i].out_off = base + total;
-        total += c->h_bblk[i].out_len;
+        if (c->bz.h_blk[i].status != kBzOk) return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt block (inverse BWT)");
+        c->bz.h_blk[i].out_off = base + total;
+        total += c->bz.h_blk[i].out_len;
     }
     int rc = ensure_fout(c, base + total, keep_dev ? o0 : 0);
     if (rc) return rc;
-    BZ_TRY(hipMemcpyAsync(c->d_bblk, c->h_bblk, (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    BZ_TRY(hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
     ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-    BZ_TRY(launch_bz_rle1_write(c->d_bslots, c->d_bblk, c->d_bchunks, nb, c->d_fout, c->f_stream));
+    BZ_TRY(launch_bz_rle1_write(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->inf.d_out.data(), c->f_stream));
     BZ_TRY(hipEventRecord(ev->b, c->f_stream));
     out.resize(o0 + total);
-    BZ_TRY(hipMemcpyAsync(out.data() + o0, c->d_fout + base, total, hipMemcpyDeviceToHost, c->f_stream));
+    BZ_TRY(hipMemcpyAsync(out.data() + o0, c->inf.d_out.data() + base, total, hipMemcpyDeviceToHost, c->f_stream));
     BZ_TRY(hipStreamSynchronize(c->f_stream));
     timed(ev);
     std::atomic<uint32_t> next{0}, bad{0};
@@ -129,7 +70,7 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         for (;;) {
             const uint32_t i = next.fetch_add(1);
             if (i >= nb) return;
-            const BzGpuBlock& B = c->h_bblk[i];
+            const BzGpuBlock& B = c->bz.h_blk[i];
             if (bz_crc_block(out.data() + o0 + (B.out_off - base), B.out_len) != crcs[i]) bad.store(1);
         }
     };
@@ -148,19 +89,19 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
 }
 
 // Decodes every stream of bz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
-// c->d_fout[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
+// c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
 int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
                    snaphash_unpack_stats& st)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: empty stream");
     const unsigned cpus = std::max(1u, x->cpus_call ? x->cpus_call : x->cpus);
     const size_t o_start = out.size();
-    auto to_dev = [&](size_t from) -> int { // host-decoded bytes out[from..) into c->d_fout at the same offset
+    auto to_dev = [&](size_t from) -> int { // host-decoded bytes out[from..) into c->inf.d_out.data() at the same offset
         if (!keep_dev || out.size() <= from) return SNAPHASH_OK;
         if (!c->f_stream) BZ_TRY(hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
         int e = ensure_fout(c, out.size(), from);
         if (e) return e;
-        BZ_TRY(hipMemcpyAsync(c->d_fout + from, out.data() + from, out.size() - from, hipMemcpyHostToDevice, c->f_stream));
+        BZ_TRY(hipMemcpyAsync(c->inf.d_out.data() + from, out.data() + from, out.size() - from, hipMemcpyHostToDevice, c->f_stream));
         BZ_TRY(hipStreamSynchronize(c->f_stream));
         return SNAPHASH_OK;
     };
@@ -208,24 +149,24 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
         // a piece: the compressed bytes from the byte that holds the next block's first bit
         const uint64_t pb = cur.bit >> 3;
         const uint64_t pn = std::min<uint64_t>(chain_order ? std::min<uint64_t>(P, 4u << 20) : P, n - pb);
-        BZ_TRY(hipMemcpyAsync(c->d_bin, bz + pb, pn, hipMemcpyHostToDevice, c->f_stream));
+        BZ_TRY(hipMemcpyAsync(c->bz.d_in.data(), bz + pb, pn, hipMemcpyHostToDevice, c->f_stream));
         std::vector<uint64_t> cand;
         if (!chain_order) {
-            BZ_TRY(hipMemsetAsync(c->d_bcount, 0, 4, c->f_stream));
+            BZ_TRY(hipMemsetAsync(c->bz.d_count.data(), 0, 4, c->f_stream));
             EventPair* ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-            BZ_TRY(launch_bz_scan(c->d_bin, pn, c->d_bcand, c->d_bcount, (uint32_t)c->bcand_cap, c->f_stream));
+            BZ_TRY(launch_bz_scan(c->bz.d_in.data(), pn, c->bz.d_cand.data(), c->bz.d_count.data(), (uint32_t)c->bz.cand_cap(), c->f_stream));
             BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-            BZ_TRY(hipMemcpyAsync(c->h_bcount, c->d_bcount, 4, hipMemcpyDeviceToHost, c->f_stream));
+            BZ_TRY(hipMemcpyAsync(c->bz.h_count.data(), c->bz.d_count.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
             BZ_TRY(hipStreamSynchronize(c->f_stream));
             timed(ev);
-            if (c->h_bcount[0] > c->bcand_cap) {
+            if (c->bz.h_count[0] > c->bz.cand_cap()) {
                 chain_order = true;
-            } else if (c->h_bcount[0]) {
-                BZ_TRY(hipMemcpyAsync(c->h_bcand, c->d_bcand, (size_t)c->h_bcount[0] * 8, hipMemcpyDeviceToHost, c->f_stream));
+            } else if (c->bz.h_count[0]) {
+                BZ_TRY(hipMemcpyAsync(c->bz.h_cand.data(), c->bz.d_cand.data(), (size_t)c->bz.h_count[0] * 8, hipMemcpyDeviceToHost, c->f_stream));
                 BZ_TRY(hipStreamSynchronize(c->f_stream));
-                cand.assign(c->h_bcand, c->h_bcand + c->h_bcount[0]);
+                cand.assign(c->bz.h_cand.data(), c->bz.h_cand.data() + c->bz.h_count[0]);
                 std::sort(cand.begin(), cand.end());
             }
         }
@@ -243,14 +184,14 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
             const uint32_t K = (uint32_t)std::min<size_t>(cand.size() - idx, kBzLaunchSlots);
             rc = ensure_bzip2(c, std::min<uint64_t>(P, n), std::max<uint32_t>(K, 8));
             if (rc) return rc;
-            memcpy(c->h_bcand, cand.data() + idx, (size_t)K * 8);
-            BZ_TRY(hipMemcpyAsync(c->d_bcand, c->h_bcand, (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
+            memcpy(c->bz.h_cand.data(), cand.data() + idx, (size_t)K * 8);
+            BZ_TRY(hipMemcpyAsync(c->bz.d_cand.data(), c->bz.h_cand.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
             EventPair* ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-            BZ_TRY(launch_bz_symbols(c->d_bin, pn, c->d_bcand, K, c->d_bslots, c->d_bres, c->f_stream));
+            BZ_TRY(launch_bz_symbols(c->bz.d_in.data(), pn, c->bz.d_cand.data(), K, c->bz.d_slots.data(), c->bz.d_res.data(), c->f_stream));
             BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-            BZ_TRY(hipMemcpyAsync(c->h_bres, c->d_bres, (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
+            BZ_TRY(hipMemcpyAsync(c->bz.h_res.data(), c->bz.d_res.data(), (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
             BZ_TRY(hipStreamSynchronize(c->f_stream));
             timed(ev);
             const uint64_t* lc = cand.data() + idx;
@@ -271,14 +212,14 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
                         break;
                     }
                     const uint32_t j = (uint32_t)(it - lc);
-                    const BzBlockRes& r = c->h_bres[j];
+                    const BzBlockRes& r = c->bz.h_res[j];
                     if (r.status != kBzOk || r.n > cur.level * 100000u) {
                         // a block the piece cuts off starts the next piece; anything else is the host decoder's
                         if (r.status == kBzTruncated && pb + pn < n && rel > 7) { piece_done = true; break; }
                         host_next = true;
                         break;
                     }
-                    BzGpuBlock& B = c->h_bblk[nb++];
+                    BzGpuBlock& B = c->bz.h_blk[nb++];
                     B.out_off = 0; B.out_len = 0; B.slot = j; B.n = r.n; B.orig_ptr = r.orig_ptr; B.status = kBzOk;
                     crcs.push_back(r.crc);
                     bz_cursor_take(cur, r.end_bit + pb * 8, r.crc);
@@ -349,9 +290,3 @@ try {
 }
 
 } // extern "C"
-
-static void free_inflate(DevCtx* c)
-{
-    free_inflate_bufs(c);
-    free_bzip2_bufs(c);
-}

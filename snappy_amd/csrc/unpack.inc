@@ -9,86 +9,36 @@
 
 namespace {
 
-void free_inflate_bufs(DevCtx* c)
-{
-    if (c->d_fin) (void)hipFree(c->d_fin);
-    if (c->d_fcand) (void)hipFree(c->d_fcand);
-    if (c->h_fcand) (void)hipHostFree(c->h_fcand);
-    if (c->d_fslots) (void)hipFree(c->d_fslots);
-    if (c->d_fres) (void)hipFree(c->d_fres);
-    if (c->h_fres) (void)hipHostFree(c->h_fres);
-    if (c->d_flinks) (void)hipFree(c->d_flinks);
-    if (c->h_flinks) (void)hipHostFree(c->h_flinks);
-    if (c->d_fflags) (void)hipFree(c->d_fflags);
-    if (c->h_fflags) (void)hipHostFree(c->h_fflags);
-    if (c->d_fwin) (void)hipFree(c->d_fwin);
-    if (c->d_fout) (void)hipFree(c->d_fout);
-    if (c->f_stream) (void)hipStreamDestroy(c->f_stream);
-    c->d_fin = nullptr; c->d_fcand = nullptr; c->h_fcand = nullptr; c->d_fslots = nullptr; c->d_fres = nullptr; c->h_fres = nullptr;
-    c->d_flinks = nullptr; c->h_flinks = nullptr; c->d_fflags = nullptr; c->h_fflags = nullptr; c->d_fwin = nullptr; c->d_fout = nullptr;
-    c->f_stream = nullptr;
-    c->fin_cap = 0; c->fcand_cap = 0; c->fslots_cap = 0; c->fout_cap = 0;
-}
-
 // the compressed piece (and its candidates) and the segments a launch decodes
 int ensure_inflate(DevCtx* c, uint64_t piece, uint32_t slots)
 {
     if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
-    if (!c->d_fflags) HIP_TRY(c, hipMalloc((void**)&c->d_fflags, 16));
-    if (!c->h_fflags) HIP_TRY(c, host_alloc(c, (void**)&c->h_fflags, 16));
-    if (!c->d_fwin) HIP_TRY(c, hipMalloc((void**)&c->d_fwin, kInfWindow));
-    if (c->fin_cap < piece) {
-        if (c->d_fin) (void)hipFree(c->d_fin);
-        if (c->d_fcand) (void)hipFree(c->d_fcand);
-        if (c->h_fcand) (void)hipHostFree(c->h_fcand);
-        c->d_fin = nullptr; c->d_fcand = nullptr; c->h_fcand = nullptr; c->fin_cap = 0;
-        const uint64_t cand = piece / 4 + 16; // (a candidate per 4 bytes at most that the launch takes; more are counted, not kept)
-        HIP_TRY(c, hipMalloc((void**)&c->d_fin, piece + 16));
-        HIP_TRY(c, hipMalloc((void**)&c->d_fcand, (cand + 2) * 4)); // (the count, the candidates, the piece start)
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_fcand, (cand + 2) * 4));
-        c->fin_cap = piece;
-        c->fcand_cap = cand;
-    }
-    if (c->fslots_cap < slots) {
-        if (c->d_fslots) (void)hipFree(c->d_fslots);
-        if (c->d_fres) (void)hipFree(c->d_fres);
-        if (c->h_fres) (void)hipHostFree(c->h_fres);
-        if (c->d_flinks) (void)hipFree(c->d_flinks);
-        if (c->h_flinks) (void)hipHostFree(c->h_flinks);
-        c->d_fslots = nullptr; c->d_fres = nullptr; c->h_fres = nullptr; c->d_flinks = nullptr; c->h_flinks = nullptr; c->fslots_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_fslots, (size_t)slots * kInflateSlotSyms * 2));
-        HIP_TRY(c, hipMalloc((void**)&c->d_fres, (size_t)slots * sizeof(InflateSegRes)));
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_fres, (size_t)slots * sizeof(InflateSegRes)));
-        HIP_TRY(c, hipMalloc((void**)&c->d_flinks, (size_t)slots * sizeof(InflateLink)));
-        HIP_TRY(c, host_alloc(c, (void**)&c->h_flinks, (size_t)slots * sizeof(InflateLink)));
-        c->fslots_cap = slots;
-    }
+    HIP_TRY(c, c->inf.ensure(piece, slots, c->numa_node));
     return SNAPHASH_OK;
 }
 
 // the decoded bytes in HBM: `keep` bytes of what is there are kept when it grows
 int ensure_fout(DevCtx* c, uint64_t need, uint64_t keep)
 {
-    if (c->fout_cap >= need) return SNAPHASH_OK;
-    uint64_t cap = std::max<uint64_t>(need, c->fout_cap + c->fout_cap / 2);
+    DevBuf<uint8_t>& out = c->inf.d_out;
+    if (out.size() >= need) return SNAPHASH_OK;
+    uint64_t cap = std::max<uint64_t>(need, out.size() + out.size() / 2);
     cap = (cap + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1);
-    uint8_t* p = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&p, cap));
-    if (keep && c->d_fout) {
-        const hipError_t e = hipMemcpyAsync(p, c->d_fout, keep, hipMemcpyDeviceToDevice, c->f_stream);
+    DevBuf<uint8_t> p;
+    HIP_TRY(c, p.reserve(cap));
+    if (keep && out.data()) {
+        const hipError_t e = hipMemcpyAsync(p.data(), out.data(), keep, hipMemcpyDeviceToDevice, c->f_stream);
         if (e == hipSuccess) (void)hipStreamSynchronize(c->f_stream);
-        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(c, e); }
+        HIP_TRY(c, e);
     }
-    if (c->d_fout) (void)hipFree(c->d_fout);
-    c->d_fout = p;
-    c->fout_cap = cap;
+    out = std::move(p);
     return SNAPHASH_OK;
 }
 
 #define INF_TRY(expr) HIP_TRY(c, (expr))
 
 // Decodes every gzip member of gz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
-// c->d_fout[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
+// c->inf.d_out[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
 // member's last 32 KiB of output travel to the next as its window.
 int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
                   snaphash_unpack_stats& st)
@@ -98,7 +48,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
     const uint32_t S = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(64, P / 16384));
     int rc = ensure_inflate(c, std::min<uint64_t>(P, n), (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(64, n / 4096 + 1)));
     if (rc) return rc;
-    const uint32_t slots = c->fslots_cap;
+    const uint32_t slots = c->inf.nslots();
     static const bool trace = getenv("SNAPHASH_TRACE_INFLATE") != nullptr; // the pieces and their chains on stderr
     const bool host_mode = !x->gpu_only;
     constexpr uint64_t kHostPiece = 8u << 20; // compressed bytes a piece of the host-thread decode takes (its slots: 2 B a symbol)
@@ -133,7 +83,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             if (keep_dev && out.size() > o0) {
                 int e = ensure_fout(c, out.size(), o0);
                 if (e) return e;
-                INF_TRY(hipMemcpyAsync(c->d_fout + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
                 INF_TRY(hipStreamSynchronize(c->f_stream));
             }
             if (r.status == kInfFinal) { ended = true; final_bit = r.end_bit; }
@@ -148,22 +98,22 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             if (host_mode) {
                 for (uint64_t v : flush_candidates(z + cur, pn)) cand.push_back((uint32_t)v);
             } else {
-                INF_TRY(hipMemcpyAsync(c->d_fin, z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
-                INF_TRY(hipMemsetAsync(c->d_fcand, 0, 4, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->inf.d_in.data(), z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
+                INF_TRY(hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
                 EventPair* ev = next_events(c, 2);
                 if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
                 INF_TRY(hipEventRecord(ev->a, c->f_stream));
-                INF_TRY(launch_inflate_scan(c->d_fin, pn, c->d_fcand + 1, c->d_fcand, (uint32_t)c->fcand_cap, c->f_stream));
+                INF_TRY(launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
                 INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->h_fcand, c->d_fcand, 4, hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
                 INF_TRY(hipStreamSynchronize(c->f_stream));
                 timed(ev);
-                const uint64_t ncand = std::min<uint64_t>(c->h_fcand[0], c->fcand_cap);
+                const uint64_t ncand = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
                 if (ncand) {
-                    INF_TRY(hipMemcpyAsync(c->h_fcand + 1, c->d_fcand + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
+                    INF_TRY(hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
                     INF_TRY(hipStreamSynchronize(c->f_stream));
                 }
-                cand.assign(c->h_fcand + 1, c->h_fcand + 1 + ncand);
+                cand.assign(c->inf.h_cand.data() + 1, c->inf.h_cand.data() + 1 + ncand);
             }
             // candidate starts in order, the piece's own start first (past the launch's slots the piece is cut)
             cand.push_back(0);
@@ -200,7 +150,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                             by[q] = (uint8_t)sy[q];
                             last = sy[q] >= kInfHole ? q + 1 : last;
                         }
-                        c->h_fres[i] = InflateSegRes{r.end_bit, (uint32_t)r.out_len, last, r.status, 0};
+                        c->inf.h_res[i] = InflateSegRes{r.end_bit, (uint32_t)r.out_len, last, r.status, 0};
                         done[i].store(1, std::memory_order_release);
                     }
                 };
@@ -216,7 +166,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                     if (it == cand.end() || *it != pos) break;
                     const uint32_t i = (uint32_t)(it - cand.begin());
                     while (!done[i].load(std::memory_order_acquire)) std::this_thread::yield();
-                    const InflateSegRes& r = c->h_fres[i];
+                    const InflateSegRes& r = c->inf.h_res[i];
                     if (r.status != kInfFlush && r.status != kInfFinal) break;
                     const size_t base = out.size();
                     out.resize(base + r.out_len);
@@ -238,7 +188,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                 if (keep_dev && out.size() > o0) {
                     rc = ensure_fout(c, out.size(), o0);
                     if (rc) return rc;
-                    INF_TRY(hipMemcpyAsync(c->d_fout + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+                    INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
                     INF_TRY(hipStreamSynchronize(c->f_stream));
                 }
                 st.segments += nl;
@@ -246,14 +196,14 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                 else cur += pos;
                 continue;
             } else {
-                memcpy(c->h_fcand + 1, cand.data(), (size_t)K * 4);
-                INF_TRY(hipMemcpyAsync(c->d_fcand + 1, c->h_fcand + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
+                memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
+                INF_TRY(hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
                 EventPair* ev = next_events(c, 2);
                 if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
                 INF_TRY(hipEventRecord(ev->a, c->f_stream));
-                INF_TRY(launch_inflate_decode(c->d_fin, pn, c->d_fcand + 1, K, c->d_fslots, c->d_fres, c->f_stream));
+                INF_TRY(launch_inflate_decode(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
                 INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->h_fres, c->d_fres, (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
                 INF_TRY(hipStreamSynchronize(c->f_stream));
                 timed(ev);
             }
@@ -265,9 +215,9 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                 const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
                 if (it == cand.end() || *it != pos) break;
                 const uint32_t i = (uint32_t)(it - cand.begin());
-                const InflateSegRes& r = c->h_fres[i];
+                const InflateSegRes& r = c->inf.h_res[i];
                 if (r.status != kInfFlush && r.status != kInfFinal) break;
-                InflateLink& L = c->h_flinks[nl++];
+                InflateLink& L = c->inf.h_links[nl++];
                 L.off = off;
                 L.slot = i;
                 L.len = r.out_len;
@@ -280,7 +230,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             }
             if (trace) {
                 const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
-                const int why = (it == cand.end() || *it != pos) ? -1 : c->h_fres[it - cand.begin()].status;
+                const int why = (it == cand.end() || *it != pos) ? -1 : c->inf.h_res[it - cand.begin()].status;
                 fprintf(stderr, "snaphash inflate: piece at %llu, %llu bytes, %u candidates, chain of %u, stopped at %llu (%d)\n",
                         (unsigned long long)cur, (unsigned long long)pn, K, nl, (unsigned long long)pos, fin ? 100 : why);
             }
@@ -291,29 +241,29 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             }
             const size_t o0 = out.size();
             const uint32_t wlen = (uint32_t)std::min<size_t>(kInfWindow, o0 - m0);
-            if (wlen) INF_TRY(hipMemcpyAsync(c->d_fwin, out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
-            INF_TRY(hipMemcpyAsync(c->d_flinks, c->h_flinks, (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
+            if (wlen) INF_TRY(hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
+            INF_TRY(hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
             // one pass over every segment at once, then -- if holes are left (chains of holes through the segments) -- the
             // segments that hold them one after another in order, and a last pass that counts what is left (nothing)
             bool filled = false;
             EventPair* ev = nullptr;
             for (int pass = 0; pass < 2 && !filled; ++pass) {
-                INF_TRY(hipMemsetAsync(c->d_fflags, 0, 8, c->f_stream));
+                INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
                 ev = next_events(c, 2);
                 if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
                 INF_TRY(hipEventRecord(ev->a, c->f_stream));
                 if (pass == 1)
                     for (uint32_t j = 0; j < nl; ++j)
-                        if (c->h_flinks[j].hole_end) INF_TRY(launch_inflate_fill(c->d_fslots, c->d_flinks, j, 1, c->d_fwin, wlen, c->d_fflags, c->f_stream));
-                if (pass == 1) INF_TRY(hipMemsetAsync(c->d_fflags, 0, 8, c->f_stream));
-                INF_TRY(launch_inflate_fill(c->d_fslots, c->d_flinks, 0, nl, c->d_fwin, wlen, c->d_fflags, c->f_stream));
+                        if (c->inf.h_links[j].hole_end) INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
+                if (pass == 1) INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
+                INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
                 INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->h_fflags, c->d_fflags, 8, hipMemcpyDeviceToHost, c->f_stream));
+                INF_TRY(hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
                 INF_TRY(hipStreamSynchronize(c->f_stream));
                 timed(ev);
-                if (c->h_fflags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
-                filled = c->h_fflags[0] == 0;
-                if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->h_fflags[0]);
+                if (c->inf.h_flags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
+                filled = c->inf.h_flags[0] == 0;
+                if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->inf.h_flags[0]);
             }
             if (!filled) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
                 rc = host_run();
@@ -322,11 +272,11 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             }
             rc = ensure_fout(c, keep_dev ? o0 + off : off, keep_dev ? o0 : 0);
             if (rc) return rc;
-            uint8_t* dst = c->d_fout + (keep_dev ? o0 : 0);
+            uint8_t* dst = c->inf.d_out.data() + (keep_dev ? o0 : 0);
             ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             INF_TRY(hipEventRecord(ev->a, c->f_stream));
-            INF_TRY(launch_inflate_concat(c->d_fslots, c->d_flinks, nl, dst, c->f_stream));
+            INF_TRY(launch_inflate_concat(c->inf.d_slots.data(), c->inf.d_links.data(), nl, dst, c->f_stream));
             INF_TRY(hipEventRecord(ev->b, c->f_stream));
             out.resize(o0 + off);
             INF_TRY(hipMemcpyAsync(out.data() + o0, dst, off, hipMemcpyDeviceToHost, c->f_stream));
@@ -537,7 +487,7 @@ int unpack_members(DevCtx* c, const std::vector<TarEntry>& ents, const uint8_t* 
 }
 
 // ClickDeb.Unpack after the choice of decoder, for both data-member formats: the archive read once, its digest on a host
-// core beside the decode, `decode` into the tar stream (kept in c->d_fout too when hashes.yaml asks for Verify), then
+// core beside the decode, `decode` into the tar stream (kept in c->inf.d_out.data() too when hashes.yaml asks for Verify), then
 // tar_read, unpack_members, the members' digests (host / GPU split) and verify_impl.
 using UnpackDecode = std::function<int(const uint8_t*, size_t, std::vector<uint8_t>&, bool, snaphash_unpack_stats&)>;
 
@@ -629,13 +579,12 @@ int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* ar
         for (size_t q = 0; q < reg.size(); ++q)
             if (!on_host[q]) { offs.push_back(ents[reg[q]].data_off); lens.push_back(ents[reg[q]].size); dev_q.push_back(q); }
         if (!dev_q.empty()) {
-            uint8_t* d_dig = nullptr;
-            HIP_TRY(c, hipMalloc((void**)&d_dig, dev_q.size() * 64));
-            struct DevFree { uint8_t* p; ~DevFree() { if (p) (void)hipFree(p); } } dfree{d_dig};
-            rc = snaphash_sha512_device(x, c->d_fout, offs.data(), lens.data(), dev_q.size(), d_dig);
+            DevBuf<uint8_t> d_dig;
+            HIP_TRY(c, d_dig.reserve(dev_q.size() * 64));
+            rc = snaphash_sha512_device(x, c->inf.d_out.data(), offs.data(), lens.data(), dev_q.size(), d_dig.data());
             if (!rc) rc = snaphash_sync(x);
             std::vector<uint8_t> hd(dev_q.size() * 64);
-            if (!rc && hipMemcpy(hd.data(), d_dig, hd.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(x, SNAPHASH_EDEVICE, "D2H of digests failed");
+            if (!rc && hipMemcpy(hd.data(), d_dig.data(), hd.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(x, SNAPHASH_EDEVICE, "D2H of digests failed");
             if (rc) return rc;
             for (size_t k = 0; k < dev_q.size(); ++k) memcpy(dig.data() + 64 * dev_q[k], hd.data() + 64 * k, 64);
         }

@@ -202,8 +202,12 @@ def test_unpack_verify_matches_snaphash_verify(snaphash_mode, tmp_path, umask_02
     arc = str(tmp_path / "data.tar.gz")
     with Context(device=0) as c:
         yaml, digest = c.tar_create(arc, build, build + "/DEBIAN", with_hashes=True)
+        hbm0 = c.engine_info(0)["hbm_bytes"]
         mis, _ = c.tar_unpack(arc, str(tmp_path / "ok"), yaml)
         assert mis is None
+        if snaphash_mode == "gpu_only":  # the decoded tar stays in HBM for Verify: the engine's footprint counts it
+            tar_len = len(gzip.decompress(open(arc, "rb").read()))
+            assert c.engine_info(0)["hbm_bytes"] - hbm0 >= tar_len, (hbm0, c.engine_info(0), tar_len)
         lines = yaml.split(b"\n")
 
         def edit(pred, fn):
