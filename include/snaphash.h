@@ -90,9 +90,14 @@ enum { /* snaphash_config.flags */
                                        roofline runs and the parity tests of the kernels); host_threads is ignored */
     SNAPHASH_FLAG_NO_NUMA = 16,     /* do not place staging memory and fill threads on the GPU's NUMA node */
     /* ---- ABI 4 ---- */
-    SNAPHASH_FLAG_KEEP_RLIMIT = 32  /* leave RLIMIT_NOFILE as it is (an application that select()s on descriptors must stay
+    SNAPHASH_FLAG_KEEP_RLIMIT = 32, /* leave RLIMIT_NOFILE as it is (an application that select()s on descriptors must stay
                                        below FD_SETSIZE): files are then kept open between batches only within the soft
                                        limit found, the rest are opened segment by segment.  Also: SNAPHASH_KEEP_RLIMIT=1 */
+    /* ---- ABI 5 ---- */
+    SNAPHASH_FLAG_SPLIT_BLOCKS = 64 /* snaphash_gunzip_buffer / snaphash_tar_unpack: also cut a DEFLATE stream WITHOUT flush
+                                       points (zlib's, Go's gzip.Writer: what click build, dpkg-deb and snappy build write)
+                                       at its block boundaries, found by a GPU scan of every bit offset, and decode the
+                                       blocks side by side (see snaphash_gunzip_buffer) */
 };
 
 typedef struct snaphash_config {
@@ -341,6 +346,17 @@ typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buf
  * (zlib's or Go's plain output) and any segment the kernel gives up on are decoded by the host decoder.
  * SNAPHASH_EFORMAT: not a gzip / DEFLATE stream, or a CRC-32 / ISIZE mismatch. */
 int snaphash_gunzip_buffer(snaphash_ctx *ctx, const void *gz, size_t n, void **out, size_t *out_len);
+/* SNAPHASH_FLAG_SPLIT_BLOCKS (opt-in; the same bytes out, or the same error): a member that starts with at least 1 MiB
+ * of the stream left is cut at its DEFLATE block boundaries too, not only at flush points (a member's length is not
+ * known before it is decoded: its first piece is 1 MiB, later ones the engine's piece size).  A GPU kernel
+ * tests every bit offset for a dynamic-Huffman block header that the decoder accepts; those starts, the stored-block
+ * ends and the piece's start are decoded side by side as above (host threads / the inflate kernel, from any bit), each
+ * segment stopping at the first block end after 16 Ki output symbols where a dynamic block follows or a stored block
+ * ended; the chain is linked from the member's start, a false start drops out.  Where the chain breaks (a block longer
+ * than a slot, a run of fixed blocks at a piece's start) the host decoder takes the stretch to the next block the scan
+ * can find, and the chain resumes there.  The unpack statistics keep their meaning: host_bytes counts only that host
+ * decoder's output; snaphash_get_block_scan_stats tells what the scan and the link did.  A member with less than 1 MiB
+ * of the stream left, and every stream without the flag, take the route above. */
 
 /* ClickDeb.Unpack (clickdeb/deb.go:188-203) of data.tar.gz into target_dir: helpers.UnpackTar (helpers/helpers.go:74-147)
  * with clickVerifyContentFn (deb.go:96-103) -- every name through filepath.Clean, any that still contains ".." refused
@@ -356,6 +372,21 @@ int snaphash_tar_unpack(snaphash_ctx *ctx, const char *data_tar_gz, const char *
                         snaphash_mismatch *first, uint8_t *archive_digest);
 /* out->struct_size in; SNAPHASH_EINVAL if it is smaller than the ABI 5 struct. */
 int snaphash_get_unpack_stats(const snaphash_ctx *ctx, snaphash_unpack_stats *out);
+
+typedef struct snaphash_block_scan_stats { /* SNAPHASH_FLAG_SPLIT_BLOCKS: of the most recent snaphash_gunzip_buffer /
+                                            * snaphash_tar_unpack (all zero without the flag, or when every member
+                                            * started with less than 1 MiB of the stream left) */
+    uint32_t struct_size;    /* in: sizeof(snaphash_block_scan_stats) */
+    uint32_t reserved;
+    uint64_t bits_scanned;   /* bit offsets the block scan tested (a piece's tail the chain did not reach is scanned again) */
+    uint64_t candidates;     /* offsets the scan accepted: dynamic-Huffman block headers the decoder accepts */
+    uint64_t linked;         /* segments linked from a block candidate */
+    uint64_t unreached;      /* candidates the link never reached: false ones, or inside a segment (candidates - linked) */
+    uint64_t host_blocks;    /* stretches the host decoder took because the chain broke */
+    double scan_ms;          /* block scan kernel time, HIP events */
+} snaphash_block_scan_stats;
+/* out->struct_size in; SNAPHASH_EINVAL if it is smaller than this struct. */
+int snaphash_get_block_scan_stats(const snaphash_ctx *ctx, snaphash_block_scan_stats *out);
 
 /* ---- the install side for data.tar.bz2 (skipToArMember's ".bz2" branch, clickdeb/deb.go:408-441) ----------------- */
 

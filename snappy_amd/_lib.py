@@ -39,11 +39,12 @@ EXPORTS = [
     "snaphash_shard_list", "snaphash_shard_plan_from",
     "snaphash_calib_observe", "snaphash_calib_apply", "snaphash_get_calib",
     # the install side (row f5)
-    "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats",
+    "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats", "snaphash_get_block_scan_stats",
     # data.tar.bz2
     "snaphash_bunzip2_buffer", "snaphash_tar_unpack_bz2",
 ]
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
+FLAG_SPLIT_BLOCKS = 64  # gunzip_buffer / tar_unpack: cut streams without flush points at their DEFLATE blocks too
 
 
 class Config(ctypes.Structure):
@@ -105,6 +106,12 @@ class UnpackStats(ctypes.Structure):
                 ("tar_bytes", ctypes.c_uint64), ("members", ctypes.c_uint64), ("segments", ctypes.c_uint64),
                 ("gpu_segments", ctypes.c_uint64), ("host_bytes", ctypes.c_uint64), ("inflate_ms", ctypes.c_double),
                 ("wall_ms", ctypes.c_double)]
+
+
+class BlockScanStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("bits_scanned", ctypes.c_uint64),
+                ("candidates", ctypes.c_uint64), ("linked", ctypes.c_uint64), ("unreached", ctypes.c_uint64),
+                ("host_blocks", ctypes.c_uint64), ("scan_ms", ctypes.c_double)]
 
 
 class Mismatch(ctypes.Structure):
@@ -197,6 +204,7 @@ def lib():
     L.snaphash_gunzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_get_unpack_stats.argtypes = [vp, ctypes.POINTER(UnpackStats)]
+    L.snaphash_get_block_scan_stats.argtypes = [vp, ctypes.POINTER(BlockScanStats)]
     L.snaphash_bunzip2_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
@@ -456,6 +464,13 @@ class Context:
         s.struct_size = ctypes.sizeof(UnpackStats)
         self._check(lib().snaphash_get_unpack_stats(self._h, ctypes.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in UnpackStats._fields_ if f[0] not in ("struct_size", "reserved")}
+
+    def block_scan_stats(self):
+        """What the block scan and the link did in the last gunzip_buffer / tar_unpack (FLAG_SPLIT_BLOCKS)."""
+        s = BlockScanStats()
+        s.struct_size = ctypes.sizeof(BlockScanStats)
+        self._check(lib().snaphash_get_block_scan_stats(self._h, ctypes.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in BlockScanStats._fields_ if f[0] not in ("struct_size", "reserved")}
 
     def targz_stats(self):
         s = TargzStats()

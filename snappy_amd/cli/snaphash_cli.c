@@ -18,6 +18,8 @@
  *   snaphash [options] dirupdated DIR_A DIR_B [PREFIX]   helpers.DirUpdated
  * options: -d DEV[,DEV...]  engines (default: the current device; -1 = all visible)
  *          -t N             hybrid scheduling: oversize streams finish on N host threads
+ *          -b               gunzip / unpack: also cut streams without flush points at their DEFLATE blocks
+ *                           (SNAPHASH_FLAG_SPLIT_BLOCKS); -s then prints the block scan's statistics too
  *          -s               print the statistics of the call on stderr
  * without -d/-t the environment may name them: SNAPHASH_DEVICES=all|0,1,...  SNAPHASH_HOST_THREADS=N
  * Pure C against include/snaphash.h: it is also the smallest example of the ABI. */
@@ -36,14 +38,27 @@ static int die(snaphash_ctx *c, int rc, const char *what)
 
 static int usage(void)
 {
-    fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
+    fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
+                    "       -b: gunzip / unpack also split streams without flush points at their blocks (SNAPHASH_FLAG_SPLIT_BLOCKS)\n"
                     "       -z DEPTH: effort of `build` / `gzip` (hash-chain links per position; default 96 = gzip -9's bytes, 32 = gzip -6's)\n");
     return 2;
+}
+
+/* -b -s: what the block scan and the link did in the last gunzip / unpack */
+static void print_block_stats(snaphash_ctx *c, const char *what)
+{
+    snaphash_block_scan_stats b;
+    b.struct_size = sizeof b;
+    if (!snaphash_get_block_scan_stats(c, &b))
+        fprintf(stderr, "%s: block scan: %llu bit offsets, %llu candidates, %llu segments linked from them, %llu unreached, "
+                        "%llu host stretches, scan %.2f ms\n",
+                what, (unsigned long long)b.bits_scanned, (unsigned long long)b.candidates, (unsigned long long)b.linked,
+                (unsigned long long)b.unreached, (unsigned long long)b.host_blocks, b.scan_ms);
 }
 
 static char *slurp(const char *path, size_t *len)
@@ -72,6 +87,7 @@ int main(int argc, char **argv)
     for (; a < argc && argv[a][0] == '-' && argv[a][1]; a++) {
         if (!strcmp(argv[a], "-s")) show_stats = 1;
         else if (!strcmp(argv[a], "-g")) cfg.flags |= SNAPHASH_FLAG_GPU_ONLY;
+        else if (!strcmp(argv[a], "-b")) cfg.flags |= SNAPHASH_FLAG_SPLIT_BLOCKS;
         else if (!strcmp(argv[a], "-z") && a + 1 < argc) cfg.deflate_depth = (uint32_t)strtoul(argv[++a], NULL, 10);
         else if (!strcmp(argv[a], "-t") && a + 1 < argc) cfg.host_threads = (uint32_t)strtoul(argv[++a], NULL, 10);
         else if (!strcmp(argv[a], "-d") && a + 1 < argc) {
@@ -197,6 +213,7 @@ int main(int argc, char **argv)
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(o, 1, ol, f) != ol || fclose(f)) { perror(argv[3]); ret = 2; }
         }
+        if (show_stats && !bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         snaphash_free(o);
         free(in);
     } else if ((!strcmp(argv[1], "unpack") || !strcmp(argv[1], "unpack-bz2")) && (argc == 4 || argc == 5)) {
@@ -218,6 +235,7 @@ int main(int argc, char **argv)
                         argv[1], (unsigned long long)us.gz_bytes, bz ? "bz2" : "gz", (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
                         (unsigned long long)us.segments, bz ? "blocks" : "segments", (unsigned long long)us.gpu_segments,
                         (unsigned long long)us.host_bytes, bz ? "bzip2" : "inflate", us.inflate_ms, us.wall_ms);
+            if (!bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         }
         free(y);
     } else if (!strcmp(argv[1], "cmp") && argc >= 4 && argc % 2 == 0) {

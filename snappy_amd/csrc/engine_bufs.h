@@ -119,7 +119,9 @@ struct InflateBufs {
     DevBuf<uint8_t> d_in;
     DevBuf<uint32_t> d_cand; // the count, the candidates, the piece start
     HostBuf<uint32_t> h_cand;
-    DevBuf<uint16_t> d_slots; // kInflateSlotSyms symbols a segment
+    DevBuf<uint32_t> d_bcand; // block mode: the count and the block scan's candidates (bit offsets)
+    HostBuf<uint32_t> h_bcand;
+    DevBuf<uint16_t> d_slots; // kInflateSlotSyms symbols a segment (block mode: kInflateBlockSlotSyms)
     DevBuf<InflateSegRes> d_res;
     HostBuf<InflateSegRes> h_res;
     DevBuf<InflateLink> d_links;
@@ -128,9 +130,15 @@ struct InflateBufs {
     HostBuf<uint32_t> h_flags;
     DevBuf<uint8_t> d_win;
     DevBuf<uint8_t> d_out;
+    HostBuf<uint16_t> h_bslots; // block mode, default configuration: the host workers' slots (kInflateBlockSlotSyms each)
+    HostBuf<uint8_t> h_bbytes;  // and their symbols narrowed to bytes
     uint64_t cand_cap() const { return d_cand.size() - 2; }
+    uint64_t bcand_cap() const { return d_bcand.size() ? d_bcand.size() - 1 : 0; }
     uint32_t nslots() const { return (uint32_t)d_res.size(); }
-    hipError_t ensure(uint64_t piece, uint32_t slots, int node)
+    uint32_t nslots(uint32_t slot_syms) const { return (uint32_t)std::min<size_t>(d_res.size(), d_slots.size() / slot_syms); }
+    // bcand: room for the block scan's candidates (0: flush mode, none); host_bslots: the host workers' block slots
+    hipError_t ensure(uint64_t piece, uint32_t slots, int node, uint32_t slot_syms = kInflateSlotSyms, uint64_t bcand = 0,
+                      uint32_t host_bslots = 0)
     {
         const uint64_t cand = piece / 4 + 16; // (a candidate per 4 bytes at most that the launch takes; more are counted, not kept)
         hipError_t e = d_flags.reserve(4);
@@ -139,17 +147,22 @@ struct InflateBufs {
         if (!e) e = d_in.reserve(piece + 16);
         if (!e) e = d_cand.reserve(cand + 2);
         if (!e) e = h_cand.reserve(cand + 2, node);
-        if (!e) e = d_slots.reserve((size_t)slots * kInflateSlotSyms);
+        if (!e && bcand) e = d_bcand.reserve(bcand + 1);
+        if (!e && bcand) e = h_bcand.reserve(bcand + 1, node);
+        if (!e) e = d_slots.reserve((size_t)slots * slot_syms);
         if (!e) e = d_res.reserve(slots);
         if (!e) e = h_res.reserve(slots, node);
         if (!e) e = d_links.reserve(slots);
         if (!e) e = h_links.reserve(slots, node);
+        if (!e && host_bslots) e = h_bslots.reserve((size_t)host_bslots * kInflateBlockSlotSyms, node);
+        if (!e && host_bslots) e = h_bbytes.reserve((size_t)host_bslots * kInflateBlockSlotSyms, node);
         if (e) each(Release());
         return e;
     }
     template <class F> void each(F&& f)
     {
-        f(d_in); f(d_cand); f(h_cand); f(d_slots); f(d_res); f(h_res); f(d_links); f(h_links); f(d_flags); f(h_flags); f(d_win); f(d_out);
+        f(d_in); f(d_cand); f(h_cand); f(d_bcand); f(h_bcand); f(d_slots); f(d_res); f(h_res); f(d_links); f(h_links); f(d_flags); f(h_flags);
+        f(d_win); f(d_out); f(h_bslots); f(h_bbytes);
     }
 };
 

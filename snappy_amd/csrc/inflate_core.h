@@ -36,13 +36,22 @@ enum : int32_t {
     kInfTruncated = 2, // the input ended first
     kInfOverflow = 3,  // the output would pass cap
     kInfBad = 4,       // not a valid DEFLATE stream (or, without holes, a reference in front of the window)
+    kInfBlock = 5,     // block mode: stopped at a block end (any bit alignment); end_bit is the next block's first bit
 };
+
+// Block mode (block_min != kInfNoBlockStop): the run stops at the first block end at or after block_min output symbols
+// where the next block can start a segment -- a dynamic-Huffman header follows (the block scan finds it), or the block
+// that ended was stored (a byte-aligned end, a stored-block candidate).  A fixed or stored block after such an end is
+// decoded on into, so that it does not break the chain.  When the output passes cap or the input ends, a run that has
+// passed such an end reports the last one instead: status kInfBlock, `cut` = the status it was cut from.
+constexpr uint64_t kInfNoBlockStop = ~0ull;
 
 struct InflateRun {
     uint64_t end_bit = 0;  // first bit after what was decoded
     uint64_t out_len = 0;  // output symbols written
     uint32_t hole_end = 0; // 1 + the last output position that holds a hole (0: none)
     int32_t status = kInfBad;
+    int32_t cut = 0;       // block mode: kInfOverflow / kInfTruncated if the run was rolled back to its last block end
 };
 
 // A canonical Huffman code: counts per length, symbols in code order, and a first-level table of
@@ -191,11 +200,138 @@ IF_HD bool inf_dynamic(InfBits& b, InflateTables& t)
     return inf_build(t.lit, t.lens, nlen, true);
 }
 
+// ---- the block-boundary scan's test (inflate_kernels.hip inflate_block_scan_kernel) --------------------------------
+// inf_dynamic_ok(in, n, bit): does a block with BTYPE = 2 start at `bit` whose header inf_dynamic accepts, read from
+// in[0..n) with the bytes past n as zeros, and does that header end within the n bytes?  The same answer as inf_dynamic,
+// without its tables: the code-length ("precode") code is kept as 19 packed 3-bit lengths and decoded by its canonical
+// order; the literal/length and distance codes only need counts, so a Kraft sum (in units of 2^-15), the largest length
+// and the number of used lengths stand in for inf_build.  Registers only.
+// Bits read from `bit` at most: 3 + 14 + 19 * 3 = 74 for the block and precode headers, then at most 286 + 30 = 316
+// code lengths at most 7 bits each (a repeat code spends at most 14 bits on 3 or more lengths), so 74 + 316 * 7 = 2286.
+constexpr uint32_t kInfHeaderMaxBits = 2286;
+
+// 64 bits of in[0..n) from bit `at` on (zeros past n); the first 57 are always whole
+IF_HD uint64_t inf_peek64(const uint8_t* in, uint64_t n, uint64_t at)
+{
+    const uint64_t p = at >> 3;
+    uint64_t v = 0;
+    for (uint32_t k = 0; k < 8; ++k) v |= (uint64_t)(p + k < n ? in[p + k] : 0) << (8 * k);
+    return v >> (at & 7);
+}
+
+struct InfDynHead {
+    uint64_t cl;   // the 19 precode lengths, 3 bits each, by symbol
+    uint64_t cnt;  // precode lengths per length 1..7, 8 bits each (byte l)
+    uint32_t nlen, ndist;
+    uint64_t next; // the first bit after the precode lengths
+};
+
+// The cheap half: BTYPE, HLIT, HDIST, HCLEN and a complete precode (inf_build of 19 lengths, no single code allowed; an
+// all-zero precode builds, then fails at the first length, so it is refused here).
+IF_HD bool inf_dynamic_head(const uint8_t* in, uint64_t n, uint64_t bit, InfDynHead& h)
+{
+    const uint64_t w = inf_peek64(in, n, bit);
+    if (((w >> 1) & 3) != 2) return false;
+    h.nlen = (uint32_t)((w >> 3) & 31) + 257;
+    h.ndist = (uint32_t)((w >> 8) & 31) + 1;
+    const uint32_t ncode = (uint32_t)((w >> 13) & 15) + 4;
+    if (h.nlen > 286 || h.ndist > 30) return false;
+    const uint64_t v = inf_peek64(in, n, bit + 17); // the precode lengths in stream order: 57 bits at most
+    const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    h.cl = 0;
+    h.cnt = 0;
+    uint32_t kraft = 0; // in units of 2^-7
+    for (uint32_t i = 0; i < ncode; ++i) {
+        const uint32_t l = (uint32_t)(v >> (3 * i)) & 7;
+        h.cl |= (uint64_t)l << (3 * order[i]);
+        if (l) {
+            kraft += 128u >> l;
+            h.cnt += 1ull << (8 * l);
+        }
+    }
+    h.next = bit + 17 + 3 * ncode;
+    return kraft == 128;
+}
+
+// The code-length walk after inf_dynamic_head: every rule of inf_dynamic and inf_build.
+IF_HD bool inf_dynamic_lengths(const uint8_t* in, uint64_t n, const InfDynHead& h)
+{
+    const uint32_t total = h.nlen + h.ndist;
+    uint64_t at = h.next;
+    uint32_t i = 0, prev = 0, at256 = 0;
+    uint32_t lk = 0, dk = 0, lmax = 0, dmax = 0, dused = 0; // Kraft sums in units of 2^-15, largest lengths, used codes
+    while (i < total) {
+        if (at > n * 8) return false; // (inf_dynamic's ib_over before each symbol)
+        uint64_t w = inf_peek64(in, n, at);
+        // canonical decode of the complete precode (RFC 1951 sec. 3.2.2): at most 7 bits
+        uint32_t code = 0, first = 0, s = 19, l = 1;
+        for (; l <= 7; ++l) {
+            code |= (uint32_t)(w >> (l - 1)) & 1;
+            const uint32_t c = (uint32_t)(h.cnt >> (8 * l)) & 255;
+            if (code - first < c) { // the (code - first)-th symbol of length l, in symbol order
+                uint32_t k = code - first;
+                for (uint32_t q = 0; q < 19; ++q)
+                    if (((h.cl >> (3 * q)) & 7) == l) {
+                        if (k == 0) { s = q; break; }
+                        --k;
+                    }
+                break;
+            }
+            first = (first + c) << 1;
+            code <<= 1;
+        }
+        if (s == 19) return false; // (cannot happen: the precode is complete)
+        w >>= l;
+        at += l;
+        uint32_t rep, val;
+        if (s < 16) {
+            rep = 1;
+            val = s;
+        } else if (s == 16) {
+            if (i == 0) return false;
+            rep = 3 + ((uint32_t)w & 3);
+            val = prev;
+            at += 2;
+        } else if (s == 17) {
+            rep = 3 + ((uint32_t)w & 7);
+            val = 0;
+            at += 3;
+        } else {
+            rep = 11 + ((uint32_t)w & 127);
+            val = 0;
+            at += 7;
+        }
+        if (i + rep > total) return false;
+        if (val) { // the lengths i .. i+rep-1: literal/length code below nlen, distance code from there
+            const uint32_t nl = i < h.nlen ? (i + rep < h.nlen ? rep : h.nlen - i) : 0;
+            lk += nl << (15 - val);
+            dk += (rep - nl) << (15 - val);
+            if (nl) lmax = lmax > val ? lmax : val;
+            if (rep - nl) { dmax = dmax > val ? dmax : val; dused += rep - nl; }
+            if (lk > 32768 || dk > 32768) return false; // over-subscribed: only grows
+            if (i <= 256 && 256 < i + rep) at256 = 1;
+        }
+        prev = val;
+        i += rep;
+    }
+    if (!at256) return false;                                       // no end-of-block code
+    if (at > n * 8) return false;                                   // the header runs past the piece
+    if (dused && dk < 32768 && dmax != 1) return false;             // incomplete distance code, not a single code
+    return lk == 32768 || lmax == 1;                                // (lens[256] != 0: the literal code is not empty)
+}
+
+IF_HD bool inf_dynamic_ok(const uint8_t* in, uint64_t n, uint64_t bit)
+{
+    InfDynHead h;
+    return inf_dynamic_head(in, n, bit, h) && inf_dynamic_lengths(in, n, h);
+}
+
 // Decodes in[0..n) from start_bit into out[0..cap).  T = uint8_t: out[-hist..-1] is the window; T = uint16_t with holes:
-// a reference in front of out[0] becomes a hole symbol.  Stops as described at the top of the file.
+// a reference in front of out[0] becomes a hole symbol.  Stops as described at the top of the file, or in block mode
+// (block_min, see kInfNoBlockStop).
 template <typename T>
 IF_HD InflateRun inflate_run(const uint8_t* in, uint64_t n, uint64_t start_bit, T* out, uint64_t hist, uint64_t cap, bool holes,
-                             bool stop_at_flush, InflateTables& t)
+                             bool stop_at_flush, InflateTables& t, uint64_t block_min = kInfNoBlockStop)
 {
     const uint16_t lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
     const uint8_t lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
@@ -221,18 +357,41 @@ IF_HD InflateRun inflate_run(const uint8_t* in, uint64_t n, uint64_t start_bit, 
         r.end_bit = ib_consumed(b);      \
         return r;                        \
     }
+    // block mode: the last block end a segment may stop at (see kInfNoBlockStop), for a run that is cut short
+    bool have_end = false;
+    uint64_t end_bit = 0, end_out = 0;
+#define IF_STOP(st)                                                                              \
+    {                                                                                            \
+        if (!have_end) IF_END(st);                                                               \
+        r.status = kInfBlock;                                                                    \
+        r.cut = (st);                                                                            \
+        r.out_len = end_out;                                                                     \
+        r.end_bit = end_bit;                                                                     \
+        if (r.hole_end > end_out) r.hole_end = (uint32_t)end_out;                                \
+        return r;                                                                                \
+    }
+#define IF_BLOCK_END(stored)                                                                     \
+    if (block_min != kInfNoBlockStop) {                                                          \
+        ib_fill(b);                                                                              \
+        if ((stored) || ((b.buf >> 1) & 3) == 2) {                                               \
+            if (o >= block_min) IF_END(kInfBlock);                                               \
+            have_end = true;                                                                     \
+            end_bit = ib_consumed(b);                                                            \
+            end_out = o;                                                                         \
+        }                                                                                        \
+    }
     for (;;) {
         ib_fill(b);
         const uint32_t final = ib_take(b, 1), type = ib_take(b, 2);
-        if (ib_over(b)) IF_END(kInfTruncated);
+        if (ib_over(b)) IF_STOP(kInfTruncated);
         if (type == 0) {
             ib_take(b, b.cnt & 7); // to the byte boundary
             const uint64_t at = ib_consumed(b) >> 3;
-            if (at + 4 > n) IF_END(kInfTruncated);
+            if (at + 4 > n) IF_STOP(kInfTruncated);
             const uint32_t len = in[at] | (uint32_t)in[at + 1] << 8, nlen = in[at + 2] | (uint32_t)in[at + 3] << 8;
             if (len != (~nlen & 0xffffu)) IF_END(kInfBad);
-            if (at + 4 + len > n) IF_END(kInfTruncated);
-            if (o + len > cap) IF_END(kInfOverflow);
+            if (at + 4 + len > n) IF_STOP(kInfTruncated);
+            if (o + len > cap) IF_STOP(kInfOverflow);
             for (uint32_t i = 0; i < len; ++i) out[o + i] = (T)in[at + 4 + i];
             o += len;
             b.pos = at + 4 + len;
@@ -241,22 +400,26 @@ IF_HD InflateRun inflate_run(const uint8_t* in, uint64_t n, uint64_t start_bit, 
             ib_fill(b);
             if (final) IF_END(kInfFinal);
             if (stop_at_flush) IF_END(kInfFlush);
+            IF_BLOCK_END(true);
             continue;
         }
         if (type == 1) {
             inf_fixed(t);
         } else if (type == 2) {
-            if (!inf_dynamic(b, t)) IF_END(ib_over(b) ? kInfTruncated : kInfBad);
+            if (!inf_dynamic(b, t)) {
+                if (ib_over(b)) IF_STOP(kInfTruncated);
+                IF_END(kInfBad);
+            }
         } else {
             IF_END(kInfBad);
         }
         for (;;) {
             ib_fill(b);
             const int32_t s = inf_decode(b, t.lit);
-            if (ib_over(b)) IF_END(kInfTruncated);
+            if (ib_over(b)) IF_STOP(kInfTruncated);
             if (s < 0) IF_END(kInfBad);
             if (s < 256) {
-                if (o >= cap) IF_END(kInfOverflow);
+                if (o >= cap) IF_STOP(kInfOverflow);
                 out[o++] = (T)s;
                 continue;
             }
@@ -266,8 +429,8 @@ IF_HD InflateRun inflate_run(const uint8_t* in, uint64_t n, uint64_t start_bit, 
             const int32_t ds = inf_decode(b, t.dist);
             if (ds < 0 || ds > 29) IF_END(kInfBad);
             const uint32_t d = dbase[ds] + ib_take(b, dext[ds]);
-            if (ib_over(b)) IF_END(kInfTruncated);
-            if (o + len > cap) IF_END(kInfOverflow);
+            if (ib_over(b)) IF_STOP(kInfTruncated);
+            if (o + len > cap) IF_STOP(kInfOverflow);
             // a hole copied from inside the segment is a hole too: what may hold one ends at o + len
             if (holes && (int64_t)o - (int64_t)d < (int64_t)r.hole_end) r.hole_end = (uint32_t)(o + len);
             if (o >= d) {
@@ -298,7 +461,10 @@ IF_HD InflateRun inflate_run(const uint8_t* in, uint64_t n, uint64_t start_bit, 
             o += len;
         }
         if (final) IF_END(kInfFinal);
+        IF_BLOCK_END(false);
     }
+#undef IF_BLOCK_END
+#undef IF_STOP
 #undef IF_END
 }
 

@@ -53,7 +53,7 @@ int gzip_trailer(const uint8_t* p, size_t n, uint64_t end_bit, uint32_t crc, uin
 }
 
 InflateRun inflate_host_append(const uint8_t* in, size_t n, uint64_t start_bit, std::vector<uint8_t>& out, size_t member_start,
-                               bool stop_at_flush)
+                               bool stop_at_flush, uint64_t block_min)
 {
     InflateTables t;
     const size_t base = out.size();
@@ -61,8 +61,8 @@ InflateRun inflate_host_append(const uint8_t* in, size_t n, uint64_t start_bit, 
     size_t cap = std::max<size_t>((size_t)(n - std::min<uint64_t>(n, start_bit >> 3)) * 4, 1u << 16);
     for (;;) {
         out.resize(base + cap);
-        InflateRun r = inflate_run<uint8_t>(in, n, start_bit, out.data() + base, base - member_start, cap, false, stop_at_flush, t);
-        if (r.status != kInfOverflow) {
+        InflateRun r = inflate_run<uint8_t>(in, n, start_bit, out.data() + base, base - member_start, cap, false, stop_at_flush, t, block_min);
+        if (r.status != kInfOverflow && r.cut != kInfOverflow) {
             out.resize(base + (size_t)r.out_len);
             return r;
         }

@@ -27,9 +27,10 @@ int gzip_trailer(const uint8_t* p, size_t n, uint64_t end_bit, uint32_t crc, uin
 int gunzip_serial(const uint8_t* gz, size_t n, std::vector<uint8_t>& out);
 
 // The host decode of one stretch: in[0..n) from start_bit, appended to out, whose bytes from member_start on are the
-// member's output so far (the window).  stop_at_flush: as inflate_run.  The output buffer grows as needed.
+// member's output so far (the window).  stop_at_flush, block_min: as inflate_run (block mode is never cut short here: the
+// output buffer grows as needed).
 InflateRun inflate_host_append(const uint8_t* in, size_t n, uint64_t start_bit, std::vector<uint8_t>& out, size_t member_start,
-                               bool stop_at_flush);
+                               bool stop_at_flush, uint64_t block_min = kInfNoBlockStop);
 
 // Byte offsets that follow the bytes 00 00 FF FF in in[0..n): where a segment may start (the LEN/NLEN of an empty
 // stored block; false ones -- the same bytes inside stored data -- fall out when the segments are linked).

@@ -170,6 +170,7 @@ struct snaphash_ctx {
     snaphash_stats_ex ex{};
     snaphash_targz_stats targz{};
     snaphash_unpack_stats unpack{};
+    snaphash_block_scan_stats block_scan{};
     std::string last_error;
     snaphash_batch* open_batch = nullptr;
     DevCtx* d0() const { return dev[0].get(); }

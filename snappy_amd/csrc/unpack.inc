@@ -10,10 +10,11 @@
 namespace {
 
 // the compressed piece (and its candidates) and the segments a launch decodes
-int ensure_inflate(DevCtx* c, uint64_t piece, uint32_t slots)
+int ensure_inflate(DevCtx* c, uint64_t piece, uint32_t slots, uint32_t slot_syms = kInflateSlotSyms, uint64_t bcand = 0,
+                   uint32_t host_bslots = 0)
 {
     if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
-    HIP_TRY(c, c->inf.ensure(piece, slots, c->numa_node));
+    HIP_TRY(c, c->inf.ensure(piece, slots, c->numa_node, slot_syms, bcand, host_bslots));
     return SNAPHASH_OK;
 }
 
@@ -37,6 +38,267 @@ int ensure_fout(DevCtx* c, uint64_t need, uint64_t keep)
 
 #define INF_TRY(expr) HIP_TRY(c, (expr))
 
+// ---- block mode (SNAPHASH_FLAG_SPLIT_BLOCKS, DESIGN.md sec. 14) ----------------------------------------------------------
+
+// A member that starts with less than this left of the stream takes the serial route.  A member's length is not known
+// before it is decoded, so block mode begins each member with a piece of this size, then takes full pieces: a small
+// member followed by others costs one such scan, not a scan of the rest of the stream.  (Doubling from here instead cost
+// the GPU-only decode a launch per step, each as long as its slowest block: measured slower than the serial route.)  (A choice: at this size
+// the block route already beats the serial one, DESIGN.md sec. 14; smaller sizes were not measured.)
+constexpr uint64_t kSplitMinBytes = 1u << 20;
+constexpr uint64_t kInflateBlockScratch = 1200000000; // the block slots and the piece in HBM (GPU-only), at most
+constexpr uint32_t kHostBlockSlots = 256;             // candidates a piece of the host-thread decode takes (InflateBufs h_bslots)
+constexpr uint64_t kBlockPiecePerSlot = 16u << 10;    // compressed bytes a slot stands for: zlib's blocks took 12-31 KB
+
+// The linked segments' holes filled on the GPU (one pass over all, then -- if holes are left -- the segments that hold them
+// in order) and their symbols laid end to end into the decoded bytes: out[o0 .. o0 + total) and, with keep_dev, HBM.
+// 1: holes are left (cannot happen after the ordered sweep: the caller falls back to the host decoder).
+int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, std::vector<uint8_t>& out, size_t m0, bool keep_dev,
+                    bool trace, const std::function<void(EventPair*)>& timed)
+{
+    const size_t o0 = out.size();
+    const uint32_t wlen = (uint32_t)std::min<size_t>(kInfWindow, o0 - m0);
+    if (wlen) INF_TRY(hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
+    INF_TRY(hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
+    bool filled = false;
+    EventPair* ev = nullptr;
+    for (int pass = 0; pass < 2 && !filled; ++pass) {
+        INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
+        ev = next_events(c, 2);
+        if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        INF_TRY(hipEventRecord(ev->a, c->f_stream));
+        if (pass == 1)
+            for (uint32_t j = 0; j < nl; ++j)
+                if (c->inf.h_links[j].hole_end) INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
+        if (pass == 1) INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
+        INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
+        INF_TRY(hipEventRecord(ev->b, c->f_stream));
+        INF_TRY(hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
+        INF_TRY(hipStreamSynchronize(c->f_stream));
+        timed(ev);
+        if (c->inf.h_flags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
+        filled = c->inf.h_flags[0] == 0;
+        if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->inf.h_flags[0]);
+    }
+    if (!filled) return 1;
+    int rc = ensure_fout(c, keep_dev ? o0 + total : total, keep_dev ? o0 : 0);
+    if (rc) return rc;
+    uint8_t* dst = c->inf.d_out.data() + (keep_dev ? o0 : 0);
+    ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    INF_TRY(hipEventRecord(ev->a, c->f_stream));
+    INF_TRY(launch_inflate_concat(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), nl, dst, c->f_stream));
+    INF_TRY(hipEventRecord(ev->b, c->f_stream));
+    out.resize(o0 + total);
+    INF_TRY(hipMemcpyAsync(out.data() + o0, dst, total, hipMemcpyDeviceToHost, c->f_stream));
+    INF_TRY(hipStreamSynchronize(c->f_stream));
+    timed(ev);
+    return 0;
+}
+
+// One member's raw DEFLATE stream z[0..zn) in block mode, appended to out (the member's output starts at m0).  Pieces
+// start at any bit: the block scan and the stored-block scan on the GPU give the candidates, every candidate is decoded
+// into a slot (the inflate kernel under SNAPHASH_FLAG_GPU_ONLY, host threads otherwise), the chain is linked from the
+// piece's start bit and filled in order.  Where it breaks at the piece's start the host decoder takes the stretch to the
+// next block the scan can find.  *final_bit: where the final block ended.
+int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std::vector<uint8_t>& out, size_t m0, bool keep_dev,
+                  snaphash_unpack_stats& st, float& kms, uint64_t* final_bit)
+{
+    snaphash_block_scan_stats& bs = x->block_scan;
+    const bool host_mode = !x->gpu_only;
+    static const bool trace = getenv("SNAPHASH_TRACE_INFLATE") != nullptr;
+    const uint64_t P0 = std::min<uint64_t>(std::max<uint64_t>(c->staging, 64u << 10), kInflateBlockPieceMax);
+    // the slots within the scratch cap (the piece and its candidates come first), and the piece from the slots
+    const uint64_t per_slot = 2ull * kInflateBlockSlotSyms + 2 * sizeof(InflateSegRes) + 2 * sizeof(InflateLink);
+    // (and no more than the stream needs: blocks take 15 KB of input or more, a slot per 4 KiB leaves room for false starts)
+    const uint32_t S = host_mode ? kHostBlockSlots
+                                 : (uint32_t)std::min<uint64_t>({4096, (kInflateBlockScratch - 2 * P0) / per_slot, std::min(zn, P0) / 4096 + 64});
+    const uint64_t P = std::min<uint64_t>(P0, (uint64_t)S * kBlockPiecePerSlot);
+    const uint64_t bcap = P / 64 + 4096;
+    int rc = ensure_inflate(c, std::min<uint64_t>(P, zn), host_mode ? 64 : S, host_mode ? kInflateSlotSyms : kInflateBlockSlotSyms, bcap,
+                            host_mode ? kHostBlockSlots : 0);
+    if (rc) return rc;
+    const uint32_t slots = host_mode ? kHostBlockSlots : c->inf.nslots(kInflateBlockSlotSyms);
+    auto timed = [&](EventPair* ev) {
+        float ms = 0;
+        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
+    };
+    const std::function<void(EventPair*)> timed_f = timed;
+    uint16_t* hsl = c->inf.h_bslots.data(); // host mode: the slots (symbols) and the bytes narrowed from them
+    uint8_t* hby = c->inf.h_bbytes.data();
+    std::vector<InflateSegRes> hres(host_mode ? kHostBlockSlots : 0);
+    uint64_t cur = 0;                                // bit in z where the next segment starts
+    uint64_t piece = std::min<uint64_t>(P, kSplitMinBytes); // the member's first piece: its end is not known yet
+    for (;;) {
+        const uint64_t b0 = cur >> 3, sb = cur & 7, pn = std::min<uint64_t>(piece, zn - b0);
+        piece = P;
+        // the scans: block headers at every bit, stored-block ends at every byte
+        INF_TRY(hipMemcpyAsync(c->inf.d_in.data(), z + b0, pn, hipMemcpyHostToDevice, c->f_stream));
+        INF_TRY(hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
+        INF_TRY(hipMemsetAsync(c->inf.d_bcand.data(), 0, 4, c->f_stream));
+        // (both pairs taken before either is used: taking one may grow the pool and move the other)
+        if (!next_events(c, 2) || !next_events(c, 2)) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        EventPair* ev = &c->ev_pool[c->ev_used - 2];
+        EventPair* evb = &c->ev_pool[c->ev_used - 1];
+        INF_TRY(hipEventRecord(ev->a, c->f_stream));
+        INF_TRY(launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
+        INF_TRY(hipEventRecord(evb->a, c->f_stream));
+        INF_TRY(launch_inflate_block_scan(c->inf.d_in.data(), pn, c->inf.d_bcand.data() + 1, c->inf.d_bcand.data(), (uint32_t)c->inf.bcand_cap(), c->f_stream));
+        INF_TRY(hipEventRecord(evb->b, c->f_stream));
+        INF_TRY(hipEventRecord(ev->b, c->f_stream));
+        INF_TRY(hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+        INF_TRY(hipMemcpyAsync(c->inf.h_bcand.data(), c->inf.d_bcand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+        INF_TRY(hipStreamSynchronize(c->f_stream));
+        timed(ev);
+        float sms = 0;
+        if (hipEventElapsedTime(&sms, evb->a, evb->b) == hipSuccess) bs.scan_ms += sms;
+        const uint64_t ns = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
+        const uint64_t nb = std::min<uint64_t>(c->inf.h_bcand[0], c->inf.bcand_cap());
+        if (ns) INF_TRY(hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ns * 4, hipMemcpyDeviceToHost, c->f_stream));
+        if (nb) INF_TRY(hipMemcpyAsync(c->inf.h_bcand.data() + 1, c->inf.d_bcand.data() + 1, nb * 4, hipMemcpyDeviceToHost, c->f_stream));
+        INF_TRY(hipStreamSynchronize(c->f_stream));
+        bs.bits_scanned += pn * 8;
+        bs.candidates += c->inf.h_bcand[0];
+        // the candidates in order from the piece's start bit: block starts, stored-block ends, the start itself
+        std::vector<uint32_t> blocks(c->inf.h_bcand.data() + 1, c->inf.h_bcand.data() + 1 + nb);
+        std::sort(blocks.begin(), blocks.end());
+        std::vector<uint32_t> cand;
+        cand.reserve(nb + ns + 1);
+        cand.push_back((uint32_t)sb);
+        for (uint32_t v : blocks)
+            if (v > sb) cand.push_back(v);
+        for (uint64_t k = 0; k < ns; ++k)
+            if (c->inf.h_cand[1 + k] > 0) cand.push_back(c->inf.h_cand[1 + k] * 8);
+        std::sort(cand.begin(), cand.end());
+        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+        if (cand.size() > slots) cand.resize(slots); // (past the launch's slots the piece is cut)
+        const uint32_t K = (uint32_t)cand.size();
+        auto is_block = [&](uint64_t bit) { return std::binary_search(blocks.begin(), blocks.end(), (uint32_t)bit); };
+        uint32_t nl = 0, from_block = 0;
+        uint64_t pos = sb;
+        bool fin = false;
+        if (host_mode) {
+            // as the flush mode's host path: workers decode every candidate into its slot, this thread links and fills
+            std::unique_ptr<std::atomic<uint32_t>[]> done(new std::atomic<uint32_t>[K]);
+            for (uint32_t i = 0; i < K; ++i) done[i].store(0, std::memory_order_relaxed);
+            std::atomic<uint32_t> next{0};
+            const uint8_t* zp = z + b0;
+            auto work = [&]() {
+                InflateTables t;
+                for (;;) {
+                    const uint32_t i = next.fetch_add(1);
+                    if (i >= K) return;
+                    uint16_t* sy = hsl + (size_t)i * kInflateBlockSlotSyms;
+                    const InflateRun r = inflate_run<uint16_t>(zp, pn, cand[i], sy, 0, kInflateBlockSlotSyms, true, false, t, kInflateBlockMinOut);
+                    uint8_t* by = hby + (size_t)i * kInflateBlockSlotSyms;
+                    uint32_t last = 0;
+                    for (uint32_t q = 0; q < (uint32_t)r.out_len; ++q) {
+                        by[q] = (uint8_t)sy[q];
+                        last = sy[q] >= kInfHole ? q + 1 : last;
+                    }
+                    hres[i] = InflateSegRes{r.end_bit, (uint32_t)r.out_len, last, r.status, (uint32_t)r.cut};
+                    done[i].store(1, std::memory_order_release);
+                }
+            };
+            const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, x->cpus_call ? x->cpus_call : x->cpus) - 1);
+            ThreadJoiner th;
+            for (unsigned k = 0; k < T; ++k) th.spawn(work);
+            const size_t o0 = out.size();
+            bool bad = false;
+            for (;;) {
+                const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
+                if (it == cand.end() || *it != pos) break;
+                const uint32_t i = (uint32_t)(it - cand.begin());
+                while (!done[i].load(std::memory_order_acquire)) std::this_thread::yield();
+                const InflateSegRes& r = hres[i];
+                if (r.status != kInfBlock && r.status != kInfFinal) break;
+                const size_t base = out.size();
+                out.resize(base + r.out_len);
+                memcpy(out.data() + base, hby + (size_t)i * kInflateBlockSlotSyms, r.out_len);
+                if (!fill_holes_host(hsl + (size_t)i * kInflateBlockSlotSyms, r.hole_end, out.data() + base, base - m0)) { bad = true; break; }
+                ++nl;
+                from_block += is_block(pos);
+                if (r.status == kInfFinal) { fin = true; *final_bit = r.end_bit + b0 * 8; break; }
+                pos = r.end_bit;
+                if (pos >= pn * 8) break;
+            }
+            next.store(K); // (what is left of the piece is scanned and decoded again as the next piece)
+            th.join_all();
+            if (bad) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
+            if (nl && keep_dev && out.size() > o0) {
+                rc = ensure_fout(c, out.size(), o0);
+                if (rc) return rc;
+                INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+                INF_TRY(hipStreamSynchronize(c->f_stream));
+            }
+        } else {
+            memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
+            INF_TRY(hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
+            ev = next_events(c, 2);
+            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            INF_TRY(hipEventRecord(ev->a, c->f_stream));
+            INF_TRY(launch_inflate_decode_blocks(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
+            INF_TRY(hipEventRecord(ev->b, c->f_stream));
+            INF_TRY(hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
+            INF_TRY(hipStreamSynchronize(c->f_stream));
+            timed(ev);
+            uint64_t off = 0;
+            for (;;) {
+                const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
+                if (it == cand.end() || *it != pos) break;
+                const uint32_t i = (uint32_t)(it - cand.begin());
+                const InflateSegRes& r = c->inf.h_res[i];
+                if (r.status != kInfBlock && r.status != kInfFinal) break;
+                InflateLink& L = c->inf.h_links[nl++];
+                L.off = off;
+                L.slot = i;
+                L.len = r.out_len;
+                L.hole_end = r.hole_end;
+                L.pad = 0;
+                off += r.out_len;
+                from_block += is_block(pos);
+                if (r.status == kInfFinal) { fin = true; *final_bit = r.end_bit + b0 * 8; break; }
+                pos = r.end_bit;
+                if (pos >= pn * 8) break;
+            }
+            if (nl) {
+                rc = gpu_fill_concat(c, nl, off, kInflateBlockSlotSyms, out, m0, keep_dev, trace, timed_f);
+                if (rc < 0) return rc;
+                if (rc) { nl = 0; fin = false; } // (holes left: the host decoder takes over from the piece's start)
+                else st.gpu_segments += nl;
+            }
+        }
+        if (trace)
+            fprintf(stderr, "snaphash inflate blocks: piece at bit %llu, %llu bytes, %llu block + %llu stored candidates, chain of %u, stopped at bit %llu%s\n",
+                    (unsigned long long)cur, (unsigned long long)pn, (unsigned long long)nb, (unsigned long long)ns, nl,
+                    (unsigned long long)pos, fin ? " (final)" : "");
+        bs.linked += from_block;
+        bs.unreached += c->inf.h_bcand[0] - from_block;
+        st.segments += nl;
+        c->ev_used = 0;
+        if (fin) return 0;
+        if (nl) {
+            cur = b0 * 8 + pos;
+            continue;
+        }
+        // the chain breaks at the piece's start: the host decoder to the next block end a segment can start from
+        const size_t o0 = out.size();
+        const InflateRun r = inflate_host_append(z, zn, cur, out, m0, false, 0);
+        if (r.status != kInfFinal && !(r.status == kInfBlock && r.end_bit > cur)) return fail(c, SNAPHASH_EFORMAT, "gzip: corrupt DEFLATE stream");
+        st.segments++;
+        st.host_bytes += out.size() - o0;
+        bs.host_blocks++;
+        if (keep_dev && out.size() > o0) {
+            rc = ensure_fout(c, out.size(), o0);
+            if (rc) return rc;
+            INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
+            INF_TRY(hipStreamSynchronize(c->f_stream));
+        }
+        if (r.status == kInfFinal) { *final_bit = r.end_bit; return 0; }
+        cur = r.end_bit;
+    }
+}
+
 // Decodes every gzip member of gz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
 // c->inf.d_out[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
 // member's last 32 KiB of output travel to the next as its window.
@@ -44,6 +306,9 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                   snaphash_unpack_stats& st)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "gzip: empty stream");
+    x->block_scan = snaphash_block_scan_stats{};
+    x->block_scan.struct_size = sizeof(snaphash_block_scan_stats);
+    const bool split = (x->flags & SNAPHASH_FLAG_SPLIT_BLOCKS) != 0;
     const uint64_t P = std::min<uint64_t>(std::max<uint64_t>(c->staging, 64u << 10), 64ull << 20);
     const uint32_t S = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(64, P / 16384));
     int rc = ensure_inflate(c, std::min<uint64_t>(P, n), (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(64, n / 4096 + 1)));
@@ -59,6 +324,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
         float ms = 0;
         if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
     };
+    const std::function<void(EventPair*)> timed_f = timed;
     if (n >= 18) { // the output in one allocation: ISIZE of the last member (exact for a single member under 4 GiB)
         const uint64_t isize = gz[n - 4] | (uint64_t)gz[n - 3] << 8 | (uint64_t)gz[n - 2] << 16 | (uint64_t)gz[n - 1] << 24;
         if (isize <= (uint64_t)n * 1032) out.reserve(out.size() + (size_t)isize);
@@ -90,6 +356,11 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             else cur = r.end_bit >> 3;
             return 0;
         };
+        if (split && zn >= kSplitMinBytes) { // block mode: the whole member
+            rc = gunzip_blocks(x, c, z, zn, out, m0, keep_dev, st, kms, &final_bit);
+            if (rc) return rc;
+            ended = true;
+        }
         while (!ended) {
             // the default configuration decodes the segments on host threads (measured faster than the kernel:
             // DESIGN.md sec. 14); SNAPHASH_FLAG_GPU_ONLY sends every linked segment through the kernel
@@ -239,49 +510,13 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                 if (rc) return rc;
                 continue;
             }
-            const size_t o0 = out.size();
-            const uint32_t wlen = (uint32_t)std::min<size_t>(kInfWindow, o0 - m0);
-            if (wlen) INF_TRY(hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
-            INF_TRY(hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
-            // one pass over every segment at once, then -- if holes are left (chains of holes through the segments) -- the
-            // segments that hold them one after another in order, and a last pass that counts what is left (nothing)
-            bool filled = false;
-            EventPair* ev = nullptr;
-            for (int pass = 0; pass < 2 && !filled; ++pass) {
-                INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
-                ev = next_events(c, 2);
-                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-                INF_TRY(hipEventRecord(ev->a, c->f_stream));
-                if (pass == 1)
-                    for (uint32_t j = 0; j < nl; ++j)
-                        if (c->inf.h_links[j].hole_end) INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
-                if (pass == 1) INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
-                INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
-                INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
-                INF_TRY(hipStreamSynchronize(c->f_stream));
-                timed(ev);
-                if (c->inf.h_flags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
-                filled = c->inf.h_flags[0] == 0;
-                if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->inf.h_flags[0]);
-            }
-            if (!filled) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
+            rc = gpu_fill_concat(c, nl, off, kInflateSlotSyms, out, m0, keep_dev, trace, timed_f);
+            if (rc < 0) return rc;
+            if (rc) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
                 rc = host_run();
                 if (rc) return rc;
                 continue;
             }
-            rc = ensure_fout(c, keep_dev ? o0 + off : off, keep_dev ? o0 : 0);
-            if (rc) return rc;
-            uint8_t* dst = c->inf.d_out.data() + (keep_dev ? o0 : 0);
-            ev = next_events(c, 2);
-            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            INF_TRY(hipEventRecord(ev->a, c->f_stream));
-            INF_TRY(launch_inflate_concat(c->inf.d_slots.data(), c->inf.d_links.data(), nl, dst, c->f_stream));
-            INF_TRY(hipEventRecord(ev->b, c->f_stream));
-            out.resize(o0 + off);
-            INF_TRY(hipMemcpyAsync(out.data() + o0, dst, off, hipMemcpyDeviceToHost, c->f_stream));
-            INF_TRY(hipStreamSynchronize(c->f_stream));
-            timed(ev);
             st.segments += nl;
             st.gpu_segments += nl;
             if (fin) ended = true;
@@ -663,6 +898,14 @@ int snaphash_get_unpack_stats(const snaphash_ctx* x, snaphash_unpack_stats* out)
     if (!x || !out || out->struct_size < sizeof(snaphash_unpack_stats)) return SNAPHASH_EINVAL;
     *out = x->unpack;
     out->struct_size = sizeof(snaphash_unpack_stats);
+    return SNAPHASH_OK;
+}
+
+int snaphash_get_block_scan_stats(const snaphash_ctx* x, snaphash_block_scan_stats* out)
+{
+    if (!x || !out || out->struct_size < sizeof(snaphash_block_scan_stats)) return SNAPHASH_EINVAL;
+    *out = x->block_scan;
+    out->struct_size = sizeof(snaphash_block_scan_stats);
     return SNAPHASH_OK;
 }
 
