@@ -1,6 +1,8 @@
 """Row f5 on the GPU: snaphash_gunzip_buffer (the GPU inflate: segments decoded side by side, holes filled, the host
 decoder for stretches without flush points) and snaphash_tar_unpack (ClickDeb.Unpack with the install-time Verify from
-the decoded bytes in HBM), in both configurations (conftest.py snaphash_mode)."""
+the decoded bytes in HBM), in both configurations (conftest.py snaphash_mode).  The kernels' and the driver's own edges
+(far holes, tiny segments, the window in front of a piece, slot capacity, pieces cut inside a segment) are in
+tests/test_gpu_inflate_edges.py."""
 import gzip
 import io
 import os

@@ -1,7 +1,8 @@
 """Row f5 on the CPU: the install side's decoder (snappy_amd/csrc/inflate_core.h, inflate_host.cpp) checked against
 Python's zlib -- every block type, flush points, the gzip framing -- and its segmented form (each segment decoded on its
 own with holes, then the holes filled) against the serial decode.  The GPU kernel that runs the same routine is checked
-in tests/test_gpu_unpack.py."""
+in tests/test_gpu_unpack.py and, at its edges, in tests/test_gpu_inflate_edges.py (streams: tests/inflate_edge_streams.py,
+their shape on the CPU: tests/test_inflate_edges_host.py)."""
 import ctypes
 import gzip
 import os
