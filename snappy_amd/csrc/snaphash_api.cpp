@@ -37,6 +37,7 @@
 #include <memory>
 #include <mutex>
 
+#include "batchplan.h"
 #include "engine_bufs.h"
 #include "hostfill.h"
 #include "hostpass.h"
@@ -54,11 +55,6 @@ using namespace snaphash;
 namespace {
 
 constexpr uint64_t kDefaultStaging = 256ull << 20;
-constexpr uint64_t kAlign = 256;          // placement of a segment inside a staging buffer
-constexpr uint64_t kMinSegment = 32u << 10;    // least a FILE stream is given of a slot, unless it ends there (a pread per segment; an open + close
-                                               // too once the call holds more descriptors than its budget, FdCache)
-constexpr uint64_t kMinSegmentMem = 16u << 10; // the same for a stream in caller memory (a copy has no such cost)
-constexpr uint32_t kTargetStreams = 4096; // streams per batch the engine aims for (keeps the kernel ahead of PCIe)
 
 struct EventPair { hipEvent_t a = nullptr, b = nullptr; int kind = 0; }; // kind 0 SHA-512 kernels, 1 h2d, 2 deflate kernels
 
@@ -376,16 +372,6 @@ void begin_call(DevCtx* c)
 
 // ---- streaming engine: host sources -> staged chunks -> kernels -----------------
 
-struct Source {
-    const char* path = nullptr;   // file source
-    const uint8_t* mem = nullptr; // memory source
-    uint64_t len = 0;
-    uint64_t gpu_len = 0;         // bytes this engine hashes: == len (whole stream, digest out) or a multiple of
-                                  // 128 below len (prefix only: the chaining value is handed to a host thread)
-};
-
-struct ReadOp { uint32_t src; uint64_t off; uint64_t n; uint8_t* dst; bool to_eof; };
-
 // Descriptors a hashing call keeps open between the batches a file appears in: a file of several batches is opened once,
 // not once per segment (10 001 x 1 MiB in 64 KiB segments: 160 000 open/close pairs, a third of the fill threads' time).
 // A stream has one read operation per batch and batches are filled one after the other, so a slot is touched by one
@@ -487,10 +473,35 @@ void run_reads(DevCtx* c, const std::vector<Source>& src, const std::vector<Read
     });
 }
 
+// SNAPHASH_TRACE_TREE: the GPU side of a call from its events, once both streams have drained.
+struct EngineSpans { float gpu = 0, copy_busy = 0, copy = 0; }; // first copy's start -> last kernel's end; the copies' own time; first copy's start -> last copy's end
+EngineSpans engine_spans(DevCtx* c)
+{
+    EngineSpans sp;
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    (void)hipStreamSynchronize(c->stream);
+    size_t first_copy = c->ev_used, last_copy = 0, last_kernel = 0;
+    for (size_t i = 0; i < c->ev_used; ++i) {
+        float ms = 0;
+        if (c->ev_pool[i].kind == 1) {
+            if (first_copy == c->ev_used) first_copy = i;
+            last_copy = i;
+            if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) == hipSuccess) sp.copy_busy += ms;
+        } else if (c->ev_pool[i].kind == 0) last_kernel = i;
+    }
+    if (first_copy < c->ev_used) {
+        (void)hipEventElapsedTime(&sp.gpu, c->ev_pool[first_copy].a, c->ev_pool[last_kernel].b);
+        (void)hipEventElapsedTime(&sp.copy, c->ev_pool[first_copy].a, c->ev_pool[last_copy].b);
+    }
+    return sp;
+}
+
 // Hashes src[i].gpu_len bytes of every source on this engine's device.  digests (host, n*64, may be NULL):
 // receives the digests of whole streams; with NULL they stay in c->d_digests (row i = source i) for the
 // multi-device gather.  states (host, n*8 u64, may be NULL): receives the chaining values, needed for
 // prefix-only sources.  err_src: index of the failing source.
+// The mechanism only: what each batch holds is planned in batchplan.cpp; here its sub-slot is waited for, filled, copied
+// and its kernels launched.
 int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, uint64_t* states, int* err_no,
                  int64_t* err_src)
 {
@@ -501,212 +512,46 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t job_bytes = 0;
     for (const Source& sc : src) job_bytes += sc.gpu_len;
-    const unsigned nslots = job_bytes > 2 * c->staging ? 3u : 2u;
-    // slots as large as the job needs, in powers of two from 8 MiB up to the engine's staging size (they grow when a
-    // larger job comes by, and never shrink)
-    uint64_t slot_bytes = std::min<uint64_t>(c->staging, 8u << 20);
-    while (slot_bytes < c->staging && slot_bytes < job_bytes / 2 + kAlign * n) slot_bytes <<= 1;
-    slot_bytes = std::min(slot_bytes, c->staging);
-    for (unsigned k = 0; k < nslots; ++k) slot_bytes = std::max(slot_bytes, std::min(c->slot[k].cap(), c->staging)); // what is there already is used
-    int rc = ensure_slots(c, (int)nslots, slot_bytes);
+    const bool from_memory = src[0].mem != nullptr;
+    const uint64_t slot_caps[3] = {c->slot[0].cap(), c->slot[1].cap(), c->slot[2].cap()};
+    const BatchGeometry g = batch_geometry(job_bytes, n, c->staging, slot_caps, from_memory);
+    int rc = ensure_slots(c, (int)g.nslots, g.slot_bytes);
     if (rc) return rc;
     HIP_TRY(c, c->hash.ensure(n, true));
-
-    c->fill_thread_s = 0;
-    c->fill_bytes = 0;
-    std::vector<uint64_t> done(n, 0);
-    std::vector<uint32_t> active;
-    active.reserve(n);
-    for (size_t i = 0; i < n; ++i)
-        if (src[i].gpu_len > 0 || src[i].len == 0) active.push_back((uint32_t)i); // a prefix of 0 bytes needs no launch
-    // longest first: the streams that set the makespan are served in every batch from the first one on
-    std::stable_sort(active.begin(), active.end(), [&](uint32_t a, uint32_t b) { return src[a].gpu_len > src[b].gpu_len; });
-    std::atomic<int> first_err{0};
-    std::atomic<int64_t> first_err_src{-1};
-    std::vector<ReadOp> ops;
-    const bool from_memory = src[0].mem != nullptr;
-    FdCache fds(from_memory ? 0 : n, c->fd_call_budget >= 0 ? std::min(c->fd_call_budget, c->fd_budget) : c->fd_budget);
-    const uint64_t seg_floor = from_memory ? kMinSegmentMem : kMinSegment;
-    // The batch: a job of more than a buffer is cut into about two dozen batches (32 MiB at least, a buffer at most, and
-    // room for every stream's floor), each in a sub-slot of the buffers; so many are in flight that the fill runs
-    // ahead of the copy engine and the copy engine ahead of the kernels.
-    uint64_t S_full = slot_bytes;
-    if (job_bytes + kAlign * n > slot_bytes && (slot_bytes & (slot_bytes - 1)) == 0 && slot_bytes > (32u << 20)) {
-        S_full = 32u << 20;
-        while (S_full < slot_bytes && (S_full < job_bytes / 24 || S_full < (seg_floor + kAlign) * std::min<uint64_t>(n, kTargetStreams))) S_full <<= 1;
-    }
-    const unsigned per_slot = (unsigned)(slot_bytes / S_full), nsub = nslots * per_slot;
-    if (c->sub.size() < nsub) c->sub.resize(nsub);
-    for (unsigned q = 0; q < nsub; ++q) {
+    if (c->sub.size() < g.nsub) c->sub.resize(g.nsub);
+    for (unsigned q = 0; q < g.nsub; ++q) {
         SubSlot& ss = c->sub[q];
         if (!ss.done) HIP_TRY(c, hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
         if (!ss.copied) HIP_TRY(c, hipEventCreateWithFlags(&ss.copied, hipEventDisableTiming));
         ss.busy = false;
     }
-    const size_t n_active0 = active.size();
-    // lab knobs, read once a CALL (so that one process can alternate settings between passes: tools/ramp_ab.py)
-    const size_t new_cap = [] { // streams a batch may BEGIN (file sources, trees of more than 2 048 streams); SNAPHASH_NEW_PER_BATCH=0: no cap
-        const char* e = getenv("SNAPHASH_NEW_PER_BATCH");
-        return e ? (size_t)strtoul(e, nullptr, 10) : (size_t)1024;
-    }();
-    const bool hold_back_on = [] { const char* e = getenv("SNAPHASH_HOLD_BACK"); return !e || atoi(e) != 0; }();
-    bool held_back = false; // the last batch of a link-bound job has been cut in two (below)
-    const unsigned ramp_shift = [] { // the first batch of a large job is S_full >> this
-        const char* e = getenv("SNAPHASH_RAMP_SHIFT");
-        const unsigned long v = e ? strtoul(e, nullptr, 10) : 3ul;
-        return (unsigned)std::min<unsigned long>(std::max<unsigned long>(v, 1), 8);
-    }();
-    // ... of a job of many streams (link-bound), "first fraction in 1/64ths, growth per batch in percent": 24,115 = three
-    // eighths of a batch first, 15 % more each time (below)
-    unsigned ramp_first64 = 24, ramp_growth_pct = 115;
-    if (const char* e = getenv("SNAPHASH_RAMP_MANY")) {
-        unsigned a = 0, b = 0;
-        if (sscanf(e, "%u,%u", &a, &b) == 2 && a >= 1 && a <= 64 && b >= 100 && b <= 400) { ramp_first64 = a; ramp_growth_pct = b; }
-    }
-    unsigned batch = 0;
+
+    c->fill_thread_s = 0;
+    c->fill_bytes = 0;
+    BatchPlanner plan(src.data(), n, job_bytes, g.S_full, BatchKnobs::from_env());
+    std::atomic<int> first_err{0};
+    std::atomic<int64_t> first_err_src{-1};
+    std::vector<ReadOp> ops;
+    FdCache fds(from_memory ? 0 : n, c->fd_call_budget >= 0 ? std::min(c->fd_call_budget, c->fd_budget) : c->fd_budget);
     double t_wait = 0, t_plan = 0, t_read = 0, t_launch = 0; // where the host side of the engine spends its time (SNAPHASH_TRACE_TREE)
     const double t_engine0 = now_ms();
     double t_first_copy = 0; // host clock: the first H2D is enqueued this long after the engine started
     size_t n_copies = 0;     // H2D copies of this call (what its link observation is worth: planner.h PlanCalib::observe_call)
 
-    while (!active.empty()) {
-        const unsigned q = batch % nsub;
+    while (!plan.active.empty()) {
+        const unsigned batch = plan.batch, q = batch % g.nsub;
         SubSlot& sl = c->sub[q];
-        uint8_t* const sl_h = c->slot[q / per_slot].h_buf.data() + (uint64_t)(q % per_slot) * S_full;
-        uint8_t* const sl_d = c->slot[q / per_slot].d_buf.data() + (uint64_t)(q % per_slot) * S_full;
+        uint8_t* const sl_h = c->slot[q / g.per_slot].h_buf.data() + (uint64_t)(q % g.per_slot) * g.S_full;
+        uint8_t* const sl_d = c->slot[q / g.per_slot].d_buf.data() + (uint64_t)(q % g.per_slot) * g.S_full;
         const double tb0 = now_ms();
         if (sl.busy) { HIP_TRY(c, hipEventSynchronize(sl.done)); sl.busy = false; }
         const double tb1 = now_ms();
         t_wait += tb1 - tb0;
-        // What a stream gets of this slot: its share by remaining length (so that long and short streams end in the
-        // same batch -- a long stream served a fixed slice per batch would still be running, alone, long after the
-        // others: the per-stream rate of the kernels is what it is), but at least a floor (a file is opened once per
-        // batch it appears in).  Equal streams (config 2) fill a slot kTargetStreams at a time, as before.
-        // Both ends of a job of several slots are tapered: nothing overlaps the first fill and the
-        // first copy, and nothing overlaps the last copy and the last kernel, so the first batches are 1/8, 1/4, 1/2 of
-        // a slot and the last ones halve what is left -- invisible on a 10 GiB job, a fifth of the time of the 1.3 GiB
-        // shard one of eight ranks gets.  A job that fits one slot is one batch.
-        long double total_rem = 0;
-        size_t n_started = 0;
-        for (uint32_t id : active) { total_rem += (long double)(src[id].gpu_len - done[id]); n_started += done[id] != 0; }
-        uint64_t S = S_full;
-        if (job_bytes + kAlign * n > S_full) {
-            if (n_active0 > 2048 && ramp_growth_pct > 100) {
-                // Many streams: the link is the bound, and the fill threads are only ~1.3 x as fast as the link (75 against
-                // 57 GB/s).  The link idles while the first batch is filled, and again before every batch that takes longer
-                // to fill than its predecessor takes to copy -- doubling batches (rounds 1-4: 1/8, 1/4, 1/2, 1) lose
-                // S x (2 / 75 - 1 / 57 GB/s) at every step: 3.5 ms in all on config 2, measured 3.6
-                // (profiles/r05_tree_events_before.txt).  A batch that grows by less than fill rate / link rate a step never
-                // makes the link wait: three eighths of a batch first, 15 % more each time (tools/ramp_ab.py; profiles/r05_ramp.txt:
-                // the link idle 1.4 + 1.1 ms at the start instead of 1.0 + 4.8).
-                double f = (double)ramp_first64 / 64.0;
-                for (unsigned k = 0; k < batch && f < 1.0; ++k) f *= (double)ramp_growth_pct / 100.0;
-                if (f < 1.0) S = std::max<uint64_t>((uint64_t)((double)S_full * f) & ~(uint64_t)(kAlign - 1), std::min<uint64_t>(S_full, 1u << 20));
-            } else if (batch < ramp_shift) {
-                // ... but never so small that only some streams get their floor: a batch costs the kernel chain its LARGEST
-                // share's time, so 256 streams at 32 KiB cost what all 1 250 at 32 KiB would (the file-source shard's first
-                // three batches: 0.75 ms of kernel each for 8, 16 and 32 MiB; profiles/r04_shard_trace.txt)
-                // (That is a concern of jobs bound by their kernel chain: up to ~2 000 streams, whose 44 MB/s each do not
-                // outrun the link.  With more streams the link is the bound and the first copy should start early: the C2
-                // tree's first batch was a whole 256 MiB buffer, 4 ms of fill with the link idle.)
-                // (Finer steps -- x 1.4 a batch from 16 MiB, eight of them -- were tried for that regime and left the link idle
-                // MORE, 4.5 ms against 3.5: every batch costs ~0.4 ms of planning and hand-over whatever its size.)
-                const uint64_t every = active.size() <= 2048 ? std::min<uint64_t>(S_full, (seg_floor + kAlign) * (uint64_t)active.size()) : 0;
-                S = std::max<uint64_t>({(S_full >> (ramp_shift - batch)) & ~(uint64_t)(kAlign - 1), every & ~(uint64_t)(kAlign - 1), std::min<uint64_t>(S_full, 1u << 20)});
-            }
-            if (total_rem < 2 * (long double)S) { // the end: half of what is left, while every stream can still get its floor
-                const uint64_t half = ((uint64_t)(total_rem / 2) + kAlign * active.size()) & ~(uint64_t)(kAlign - 1);
-                const uint64_t least = std::max<uint64_t>(S_full >> 5, (seg_floor + kAlign) * active.size());
-                if (half >= least) S = std::min(S, half);
-            }
-        }
-        // A file's FIRST segment costs an open(), and every open of a process takes the lock of its one descriptor table
-        // (~3 us alone, ~19 us each with twelve threads at it).  A tree of many files used to begin all of
-        // them within its first four batches -- config 2: 10 001 opens in the first 480 MiB, whose fills ran at 40-50 GB/s
-        // where later ones run at 76, and the link idled 6 ms of the ramp (profiles/r05_tree_events_before.txt).  So a
-        // batch begins at most new_cap streams; the rest of it goes to streams already open (kept descriptors: a pread
-        // each).  Streams nobody has begun go in front of those served at the floor, so every batch begins its share.
-        const bool cap_new = new_cap != 0 && !from_memory && n_active0 > 2048;
-        const size_t n_serve = cap_new ? std::min<size_t>(kTargetStreams, n_started + std::min<size_t>(new_cap, active.size() - n_started)) : kTargetStreams;
-        const uint64_t floor_q = std::max<uint64_t>(seg_floor, (S / std::max<size_t>(1, n_serve)) & ~(uint64_t)(kAlign - 1));
-        // What the shares are taken of: the batch less the alignment every segment may cost.  Without that the shares of
-        // ALL streams came to a whole batch, the padding pushed the last dozen streams of the list out of every batch, and
-        // they were hashed at the end, alone, at 44 MB/s each (5 000 x 1 MiB: the last four kernels took 26 ms instead of
-        // 6, 114 ms for a job whose copies take 92; profiles/r04_shard_trace.txt).
-        const uint64_t pad = kAlign * (uint64_t)active.size();
-        const uint64_t S_share = pad < S / 2 ? S - pad : S;
-        HIP_TRY(c, sl.jobs.ensure(active.size()));
-
-        ops.clear();
-        size_t nj = 0;
-        uint64_t used = 0;
-        // Who is served next time.  A batch cannot always serve every stream (more streams than it has floors for: 5 000 x
-        // 1 MiB at a floor of 64 KiB, 100 000 small files); round 3 then served the SAME leading streams batch after batch and
-        // the ones behind them only when those were done -- 904 of 5 000 streams hashed at the end, alone, 290 KiB a batch
-        // at 44 MB/s: kernels of 6-9 ms behind copies of 4.7 (profiles/r04_shard_trace.txt).  Now the streams a batch had
-        // no room for go FIRST in the next one, in front of those that were served at the floor; streams whose share by
-        // length exceeds the floor (the long ones that set the makespan) stay in front of both and are served every time.
-        std::vector<uint32_t> still, skipped, floor_still;
-        still.reserve(active.size());
-        // The last batch of a link-bound job: nothing overlaps its kernel, which takes what its LARGEST share takes at a
-        // stream's 44 MB/s -- 64 KiB shares: 1.5-1.7 ms behind the last copy (profiles/r05_tree_events_before.txt).  So the batch
-        // that would be the last leaves 16 KiB of every stream behind for one more, whose kernel is 0.4 ms.
-        constexpr uint64_t kHold = 16u << 10;
-        // (... of streams that HAVE that much left -- more than the 24 KiB below which a stream goes to the batch behind whole, on
-        // average: 5 000 x 8 KiB made the batch in front of the last an EMPTY one, profiles/r05_small_files.txt.  Config 2's last
-        // batch has 26 KiB a stream: a first version of this test asked for 32 and switched the hold-back off for it, +1.5 ms.)
-        const bool hold_back = hold_back_on && !held_back && n_active0 > 2048 && total_rem <= (long double)S_share && total_rem > (long double)(8u << 20) &&
-                               total_rem > (long double)(kHold + kHold / 2) * (long double)active.size();
-        if (hold_back) held_back = true;
-        bool full = false;
-        size_t n_new = 0;
-        // (one division a batch, not one a stream: the engine's thread plans 4 096 segments a batch between two fills, and in
-        // the ramp nothing hides that)
-        const bool share_all = total_rem > (long double)S;
-        const long double share_ratio = share_all ? (long double)S_share / total_rem : 1.0L;
-        for (size_t ai = 0; ai < active.size(); ++ai) {
-            const uint32_t id = active[ai];
-            if (full) { skipped.insert(skipped.end(), active.begin() + (ptrdiff_t)ai, active.end()); break; } // nobody behind a full batch is looked at
-            if (cap_new && done[id] == 0 && src[id].gpu_len != 0) {
-                if (n_new >= new_cap) { skipped.push_back(id); continue; } // begun by a later batch
-                ++n_new;
-            }
-            const uint64_t rem = src[id].gpu_len - done[id];
-            uint64_t quota = share_all ? (uint64_t)((long double)rem * share_ratio) : rem;
-            const bool at_floor = (quota & ~(uint64_t)(kAlign - 1)) < floor_q;
-            quota = std::max(quota & ~(uint64_t)(kAlign - 1), floor_q); // a multiple of 128: segments are whole blocks
-            uint64_t take = rem <= quota ? rem : quota;
-            if (hold_back) {
-                if (rem <= kHold + kHold / 2) { skipped.push_back(id); continue; } // all of it in the batch behind this one
-                take = std::min<uint64_t>(take, (rem - kHold) & ~(uint64_t)(kAlign - 1));
-            }
-            const uint64_t at = (used + kAlign - 1) & ~(uint64_t)(kAlign - 1);
-            if (at + take > S) { full = true; skipped.push_back(id); continue; }
-            const bool last = take == rem;
-            const bool fin = last && src[id].gpu_len == src[id].len;
-            Job j;
-            j.data = (uint64_t)(uintptr_t)(sl_d + at);
-            j.nbytes = take;
-            j.total_prev = done[id];
-            j.idx = id;
-            j.flags = (done[id] == 0 ? kJobFirst : 0u) | (fin ? kJobFinal : 0u);
-            sl.jobs.h[nj++] = j;
-            if (take) ops.push_back(ReadOp{id, done[id], take, sl_h + at, fin && src[id].path != nullptr});
-            used = at + take;
-            done[id] += take;
-            c->stats.blocks += padded_blocks(take, fin);
-            if (!last) (at_floor ? floor_still : still).push_back(id);
-        }
-        still.insert(still.end(), skipped.begin(), skipped.end());
-        still.insert(still.end(), floor_still.begin(), floor_still.end());
-        active.swap(still);
+        HIP_TRY(c, sl.jobs.ensure(plan.active.size()));
+        const Batch b = plan.next(sl.jobs.h.data(), ops, (uint64_t)(uintptr_t)sl_h, (uint64_t)(uintptr_t)sl_d);
+        c->stats.blocks += b.blocks;
         static const bool trace_batches = getenv("SNAPHASH_TRACE_BATCHES") != nullptr; // (read once, not once a batch)
-        if (trace_batches) {
-            uint64_t mx = 0;
-            for (size_t k = 0; k < nj; ++k) mx = std::max<uint64_t>(mx, sl.jobs.h[k].nbytes);
-            fprintf(stderr, "snaphash engine %d: batch %u: S %llu, %zu segments, %llu bytes, largest share %llu, %zu streams left behind\n", c->index, batch,
-                    (unsigned long long)S, nj, (unsigned long long)used, (unsigned long long)mx, active.size());
-        }
+        if (trace_batches) trace_batch(stderr, c->index, batch, b, sl.jobs.h.data(), (uint64_t)(uintptr_t)sl_d, plan.active.size());
         const double tb2 = now_ms();
         t_plan += tb2 - tb1;
 
@@ -716,50 +561,32 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         t_read += tb3 - tb2;
         if (trace_batches)
             fprintf(stderr, "snaphash engine %d: batch %u: at %.2f ms: waited %.2f, planned %.2f, filled %.2f ms (%zu streams begun, %.1f GB/s)\n", c->index, batch,
-                    tb0 - t_engine0, tb1 - tb0, tb2 - tb1, tb3 - tb2, n_new, (double)used / ((tb3 - tb2) * 1e6 + 1e-9));
+                    tb0 - t_engine0, tb1 - tb0, tb2 - tb1, tb3 - tb2, b.n_new, (double)b.used / ((tb3 - tb2) * 1e6 + 1e-9));
 
-        if (used) { // copy stream: the slot's previous kernel was already waited for above
+        if (b.used) { // copy stream: the slot's previous kernel was already waited for above
             if (batch == 0) t_first_copy = now_ms() - t_engine0;
             ++n_copies;
             EventPair* ev = next_events(c, 1);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             HIP_TRY(c, hipEventRecord(ev->a, c->copy_stream));
-            HIP_TRY(c, hipMemcpyAsync(sl_d, sl_h, used, hipMemcpyHostToDevice, c->copy_stream));
+            HIP_TRY(c, hipMemcpyAsync(sl_d, sl_h, b.used, hipMemcpyHostToDevice, c->copy_stream));
             HIP_TRY(c, hipEventRecord(ev->b, c->copy_stream));
         }
-        rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), nj, c->hash.d_digests.data(), sl.copied);
+        rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), b.nj, c->hash.d_digests.data(), sl.copied);
         if (rc) return rc;
         HIP_TRY(c, hipEventRecord(sl.done, c->stream));
         sl.busy = true;
-        ++batch;
         t_launch += now_ms() - tb3;
     }
 
     const double ts0 = now_ms();
     static const bool trace_tree = getenv("SNAPHASH_TRACE_TREE") != nullptr;
-    float gpu_span = 0, copy_busy = 0, copy_span = 0; // first copy's start -> last kernel's end; the copies' own time; first copy's start -> last copy's end
-    if (trace_tree && c->ev_used > 1) {
-        if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamSynchronize(c->stream);
-        size_t first_copy = c->ev_used, last_copy = 0, last_kernel = 0;
-        for (size_t i = 0; i < c->ev_used; ++i) {
-            float ms = 0;
-            if (c->ev_pool[i].kind == 1) {
-                if (first_copy == c->ev_used) first_copy = i;
-                last_copy = i;
-                if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) == hipSuccess) copy_busy += ms;
-            } else if (c->ev_pool[i].kind == 0) last_kernel = i;
-        }
-        if (first_copy < c->ev_used) {
-            (void)hipEventElapsedTime(&gpu_span, c->ev_pool[first_copy].a, c->ev_pool[last_kernel].b);
-            (void)hipEventElapsedTime(&copy_span, c->ev_pool[first_copy].a, c->ev_pool[last_copy].b);
-        }
-    }
+    const EngineSpans sp = trace_tree && c->ev_used > 1 ? engine_spans(c) : EngineSpans{};
     rc = sync_ctx(c);
     if (trace_tree)
         fprintf(stderr, "snaphash engine %d: %u batches; waiting for a slot %.1f ms, planning %.1f ms, reads %.1f ms, enqueue %.1f ms, drain %.1f ms; "
                         "first copy enqueued at %.2f ms, copies busy %.2f of %.2f ms, first copy -> last kernel %.2f ms, engine %.2f ms\n",
-                c->index, batch, t_wait, t_plan, t_read, t_launch, now_ms() - ts0, t_first_copy, copy_busy, copy_span, gpu_span, now_ms() - t_engine0);
+                c->index, plan.batch, t_wait, t_plan, t_read, t_launch, now_ms() - ts0, t_first_copy, sp.copy_busy, sp.copy, sp.gpu, now_ms() - t_engine0);
     for (SubSlot& ss : c->sub) ss.busy = false;
     if (rc) return rc;
     if (first_err.load()) {

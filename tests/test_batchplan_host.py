@@ -1,0 +1,183 @@
+"""The staging engine's batch policy on the CPU (snappy_amd/csrc/batchplan.cpp, built with g++ into
+tests/batchplan_host_harness.cpp).  The harness plans a call the way hash_sources does and checks every segment itself:
+each stream's segments cover [0, gpu_len) once and in order, total_prev is the sum before, the first flag on the first
+only, the final flag iff the last segment of a stream hashed whole, to_eof iff final and a file, every segment but a
+stream's last a multiple of 128 bytes, an empty stream exactly one empty segment, a prefix of 0 bytes of a non-empty
+stream none; in a batch offsets are multiples of kAlign, nothing overlaps, end <= S <= S_full, no stream twice; the
+planner terminates; a job that fits one slot is one batch; the hold-back (told by its segments: nobody ends in the batch,
+every stream served stops kHold short of its end) happens at most once a call and agrees with the planner's flag.  What it prints is
+the engine's own trace line (SNAPHASH_TRACE_BATCHES), which the tests below read.
+
+tests/golden/batch_traces.json holds the batches the commit BEFORE this file existed planned on the MI355X for the
+shapes of tests/batch_shapes.py: every field of every batch must be equal, the checksum over the segments included.
+
+(A finding, not asserted: where streams begun are capped -- more than 2 048 FILES -- a tree that fits one slot still takes
+ceil(n / new_cap) batches: 3 000 x 1 KiB is three.  None of the shapes here is one.)"""
+import json
+import os
+import re
+import subprocess
+
+import pytest
+
+import batch_shapes
+from conftest import GOLDEN, ROOT
+
+HARNESS = os.path.join(ROOT, "tests", "batchplan_host_harness.cpp")
+# the runtime's headers, for the types in sha512_kernels.h alone: the harness is a host program and links none of the runtime
+RUNTIME_HEADERS = ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")]
+MiB = 1 << 20
+
+
+def build_harness(exe, *flags):
+    subprocess.check_call(["g++", "-std=c++17", *flags, *RUNTIME_HEADERS, "-o", exe, HARNESS])
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("batchplan") / "batchplan_host")
+    build_harness(exe, "-O2", "-Wall", "-Wextra", "-Werror")
+    return exe
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(os.path.join(GOLDEN, "batch_traces.json")) as f:
+        return json.load(f)["shapes"]
+
+
+def plan(exe, tmp_path, source, staging, lens, gpu_lens=None, knobs=None, slot_caps=(0, 0, 0), env=None):
+    """Plans one call -> (batches, geometry, summary); the harness fails on any segment out of place."""
+    k = dict(batch_shapes.DEFAULT_KNOBS, **(knobs or {}))
+    gpu_lens = lens if gpu_lens is None else gpu_lens
+    spec = str(tmp_path / "spec.txt")
+    with open(spec, "w") as f:
+        f.write("%d %d %d %d %d\n" % (staging, source == "memory", *slot_caps))
+        f.write("%d %d %d %d %d\n%d\n" % (k["new_cap"], k["hold_back"], k["ramp_shift"], k["ramp_first64"], k["ramp_growth_pct"], len(lens)))
+        f.write("".join("%d %d\n" % p for p in zip(lens, gpu_lens)))
+    r = subprocess.run([exe, "plan", spec], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "plan ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    calls = batch_shapes.parse_batches(r.stdout)
+    assert len(calls) == 1
+    geometry = dict((m.group(1), int(m.group(2))) for m in re.finditer(r"(\w+) (\d+)", r.stdout.split("\n", 1)[0]))
+    summary = [int(x) for x in re.search(r"summary: (\d+) batches, (\d+) hold-backs, most streams begun by a batch (\d+)", r.stdout).groups()]
+    assert summary[0] == len(calls[0])
+    return calls[0], geometry, dict(zip(("batches", "hold_backs", "max_begun"), summary))
+
+
+def plan_shape(exe, tmp_path, p, **over):
+    args = dict(source=p["source"], staging=p["staging"], lens=batch_shapes.lengths(p["lens"]), knobs=batch_shapes.knobs_of(p.get("env", {})),
+                slot_caps=p.get("slot_caps", (0, 0, 0)))
+    args.update(over)
+    return plan(exe, tmp_path, **args)
+
+
+@pytest.mark.parametrize("name", list(batch_shapes.SHAPES))
+def test_batches_equal_the_parent_commits(harness, golden, tmp_path, name):
+    """Every recorded shape replayed through the planner: S, segments, bytes, largest share, streams left behind and the
+    checksum over (idx, offset, nbytes, total_prev, flags) of every batch are what the engine planned before the policy
+    was moved out of it.  Equality, no tolerance."""
+    rec = golden[name]
+    assert rec["params"] == json.loads(json.dumps(batch_shapes.SHAPES[name])), "the fixture was recorded from other parameters"
+    batches, _, _ = plan_shape(harness, tmp_path, rec["params"])
+    got = [[b[f] for f in batch_shapes.FIELDS] + [b["checksum"]] for b in batches]
+    assert len(got) == len(rec["batches"]), (len(got), len(rec["batches"]))
+    for k, (g, w) in enumerate(zip(got, rec["batches"])):
+        assert g == w, "batch %d: planned %s, recorded %s" % (k, g, w)
+
+
+def test_no_stream_is_left_for_the_end_cpu_twin(harness, tmp_path):
+    """What tests/test_gpu_api2.py::test_no_stream_is_left_for_the_end asserts of the engine's trace on the GPU, of the
+    planner alone: 5 000 x 256 KiB from memory at 64 MiB of staging."""
+    batches, _, _ = plan_shape(harness, tmp_path, batch_shapes.SHAPES["mem_5000x256k"])
+    assert len(batches) >= 15
+    shares = [b["largest_share"] for b in batches]
+    segments = [b["segments"] for b in batches]
+    assert max(shares) <= 2 * (16 << 10), shares
+    s_max = max(b["S"] for b in batches)
+    steady = [b["segments"] for b in batches[:-3] if b["S"] == s_max]
+    assert len(steady) >= 8 and max(segments) <= 4096 + 1 and min(steady) >= 3500, segments
+    assert batches[-1]["left_behind"] == 0
+
+
+@pytest.mark.parametrize("name", ["c2_files", "files_100000x8k", "files_5000x8k"])
+def test_a_batch_begins_at_most_new_cap_files(harness, tmp_path, name):
+    """File sources, more than 2 048 streams: no batch begins more than new_cap streams (the harness checks each batch);
+    new_cap = 0 lifts that; the last batch is cut in two at most once a call, and never with hold_back off."""
+    p = batch_shapes.SHAPES[name]
+    _, _, capped = plan_shape(harness, tmp_path, p)
+    assert 0 < capped["max_begun"] <= 1024 and capped["hold_backs"] <= 1
+    _, _, few = plan_shape(harness, tmp_path, p, knobs={"new_cap": 100})
+    assert 0 < few["max_begun"] <= 100 and few["batches"] >= p["lens"]["n"] / 100
+    _, _, lifted = plan_shape(harness, tmp_path, p, knobs={"new_cap": 0})
+    assert lifted["max_begun"] > 1024
+    _, _, off = plan_shape(harness, tmp_path, p, knobs={"hold_back": 0})
+    assert off["hold_backs"] == 0 and off["batches"] <= capped["batches"]
+
+
+def test_hold_back_at_its_edge(harness, tmp_path):
+    """Config 2's last batch has 26 KiB a stream and is cut in two; 5 000 x 8 KiB has less than the 24 KiB a stream the
+    cut asks for, and must not get an empty batch in front of its last (profiles/r05_small_files.txt)."""
+    _, _, c2 = plan_shape(harness, tmp_path, batch_shapes.SHAPES["c2_files"])
+    assert c2["hold_backs"] == 1
+    batches, _, small = plan_shape(harness, tmp_path, batch_shapes.SHAPES["files_5000x8k"])
+    assert small["hold_backs"] == 0 and all(b["segments"] > 0 for b in batches)
+
+
+def test_prefix_only_sources(harness, tmp_path):
+    """gpu_len < len (a multiple of 128, some 0): the prefix is planned, no segment carries the final flag, a prefix of 0
+    bytes gets no segment while an empty stream gets its one.  The public API reaches no such call with every byte on the
+    GPU, so the fixture holds none and the harness's own checks of every segment (each stream covered to gpu_len exactly) are
+    this shape's only guard; here only that the call is large enough to be cut into batches."""
+    lens = batch_shapes.lengths({"kind": "ragged", "n": 2500, "seed": 11, "top": 1 << 20, "zeros": 9})
+    gpu_lens = [ln if i % 3 == 0 else (ln // 2) & ~127 if i % 3 == 1 else 0 for i, ln in enumerate(lens)]
+    assert any(g == 0 and ln > 0 for g, ln in zip(gpu_lens, lens)) and any(ln == 0 for ln in lens)
+    for source in ("memory", "files"):
+        batches, _, _ = plan(harness, tmp_path, source, 32 * MiB, lens, gpu_lens)
+        assert len(batches) > 4
+
+
+def test_geometry(harness, tmp_path):
+    """Slots in powers of two from 8 MiB up to the staging size, a third one beyond two buffers' worth; what is there
+    already is used whole; a job that fits one slot is one batch, a large one is cut into sub-slots."""
+    _, g, s = plan(harness, tmp_path, "memory", 256 * MiB, [1000] * 10)
+    assert (g["nslots"], g["slot_bytes"], g["S_full"], g["nsub"], s["batches"]) == (2, 8 * MiB, 8 * MiB, 2, 1)
+    # 1 250 MiB: three buffers of 256 MiB; batches of 1 250 / 24 = 52 -> 64 MiB, four to a buffer
+    _, g, _ = plan_shape(harness, tmp_path, batch_shapes.SHAPES["files_1250x1m"])
+    assert (g["nslots"], g["slot_bytes"], g["S_full"], g["per_slot"], g["nsub"]) == (3, 256 * MiB, 64 * MiB, 4, 12)
+    p = batch_shapes.SHAPES["slots_there"]
+    _, g, s = plan_shape(harness, tmp_path, p)
+    assert (g["slot_bytes"], s["batches"]) == (256 * MiB, 1)
+    _, g, s = plan_shape(harness, tmp_path, p, slot_caps=(0, 0, 0))
+    assert g["slot_bytes"] == 64 * MiB and s["batches"] > 1
+    # the slots its prior call leaves are the ones recorded for it
+    _, g, _ = plan(harness, tmp_path, p["source"], p["staging"], batch_shapes.lengths(p["prior"]))
+    assert [g["slot_bytes"]] * g["nslots"] + [0] * (3 - g["nslots"]) == p["slot_caps"]
+
+
+def test_knobs_from_the_environment(harness):
+    """Same names, ranges and defaults as before the move: out of range or malformed falls back (RAMP_MANY) or clamps
+    (RAMP_SHIFT)."""
+    def knobs(**env):
+        clean = {k: v for k, v in os.environ.items() if not k.startswith("SNAPHASH_")}
+        r = subprocess.run([harness, "knobs"], capture_output=True, text=True, timeout=60, env=dict(clean, **env))
+        assert r.returncode == 0 and "knobs ok" in r.stdout, r.stdout + r.stderr
+        return dict((m.group(1), int(m.group(2))) for m in re.finditer(r"(\w+) (\d+)", r.stdout))
+    assert knobs() == batch_shapes.DEFAULT_KNOBS
+    env = batch_shapes.SHAPES["knobs_files"]["env"]
+    assert knobs(**env) == batch_shapes.knobs_of(env) == dict(batch_shapes.DEFAULT_KNOBS, new_cap=0, hold_back=0, ramp_first64=8, ramp_growth_pct=100)
+    assert knobs(SNAPHASH_RAMP_SHIFT="0")["ramp_shift"] == 1 and knobs(SNAPHASH_RAMP_SHIFT="99")["ramp_shift"] == 8
+    for bad in ("0,115", "65,115", "24,99", "24,401", "24", "x"):
+        k = knobs(SNAPHASH_RAMP_MANY=bad)
+        assert (k["ramp_first64"], k["ramp_growth_pct"]) == (24, 115), bad
+    assert knobs(SNAPHASH_HOLD_BACK="2")["hold_back"] == 1 and knobs(SNAPHASH_NEW_PER_BATCH="77")["new_cap"] == 77
+
+
+def test_batchplan_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "batchplan_asan")
+    build_harness(exe, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    lens = batch_shapes.lengths({"kind": "ragged", "n": 2500, "seed": 11, "top": 1 << 20, "zeros": 9})
+    for name in ("mem_5000x256k", "files_5000x8k", "zipf_mem", "ragged_files", "knobs_files", "slots_there"):
+        plan_shape(exe, tmp_path, batch_shapes.SHAPES[name], env=env)
+    plan(exe, tmp_path, "files", 32 * MiB, lens, [(ln // 2) & ~127 for ln in lens], env=env)

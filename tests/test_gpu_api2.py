@@ -533,6 +533,21 @@ def test_no_stream_is_left_for_the_end(built_lib):
 
 
 @pytest.mark.kernels_only("names the configuration of every Context it makes")
+@pytest.mark.parametrize("name", ["mem_5000x256k", "files_5000x8k"])
+def test_engine_plans_the_recorded_batches(built_lib, name):
+    """The engine and the planner it asks (batchplan.cpp) cannot drift apart: two of the shapes of
+    tests/golden/batch_traces.json through the library itself, every field of every batch of its trace equal to the
+    record -- the same record tests/test_batchplan_host.py holds the planner alone to on the CPU."""
+    import json
+    import batch_shapes
+    assert name in batch_shapes.GPU_TEST_SHAPES
+    with open(os.path.join(GOLDEN, "batch_traces.json")) as f:
+        rec = json.load(f)["shapes"][name]
+    got = [[b[k] for k in batch_shapes.FIELDS] + [b["checksum"]] for b in batch_shapes.library_batches(name)]
+    assert got == rec["batches"]
+
+
+@pytest.mark.kernels_only("names the configuration of every Context it makes")
 def test_descriptor_budget_smaller_than_the_tree(built_lib, oracle, tmp_path):
     """The engine keeps a file's descriptor between the batches the file appears in (FdCache) only within what
     RLIMIT_NOFILE leaves: with a budget far below the number of files the rest is opened segment by segment, as round 3
