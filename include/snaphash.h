@@ -415,8 +415,9 @@ int snaphash_files_equal(snaphash_ctx *ctx, const char *const *a, const char *co
 
 /* The same for byte ranges already resident in HBM: [d_a+off_a[i], +lens[i]) against
  * [d_b+off_b[i], +lens[i]).  Offsets (host arrays) and bases 16-byte aligned; d_equal is device
- * memory, n bytes.  Enqueues on the ctx stream; snaphash_sync waits.  HBM-bound: 2 bytes read
- * per byte compared. */
+ * memory, n bytes.  The kernel reads the whole 16-byte piece that holds a range's last byte: on
+ * both sides the bytes up to the next 16-byte boundary must be readable; their values are ignored.
+ * Enqueues on the ctx stream; snaphash_sync waits.  HBM-bound: 2 bytes read per byte compared. */
 int snaphash_ranges_equal_device(snaphash_ctx *ctx, const void *d_a, const uint64_t *off_a,
                                  const void *d_b, const uint64_t *off_b, const uint64_t *lens,
                                  size_t n, void *d_equal);
