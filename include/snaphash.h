@@ -404,6 +404,70 @@ int snaphash_bunzip2_buffer(snaphash_ctx *ctx, const void *bz, size_t n, void **
 int snaphash_tar_unpack_bz2(snaphash_ctx *ctx, const char *data_tar_bz2, const char *target_dir, const char *yaml,
                             size_t yaml_len, snaphash_mismatch *first, uint8_t *archive_digest);
 
+/* ---- the .snap itself: the ar container, its two tars, audit and unpack (clickdeb/deb.go:108-203, 408-441) ------------ */
+
+/* CRC-32 of byte ranges resident in HBM (the CRC kernels, crc_kernels.hip; for callers who hold decoded bytes there).
+ * kind: 0 = gzip / zlib CRC-32, 1 = bzip2's.  offsets/lens are host arrays; any byte alignment, any length (0: the CRC
+ * is 0); ranges may overlap; crcs: host, n values.  Synchronous: the values are there when the call returns. */
+int snaphash_crc32_device(snaphash_ctx *ctx, int kind, const void *d_base, const uint64_t *offsets,
+                          const uint64_t *lens, size_t n, uint32_t *crcs);
+
+/* A session on one .snap file.  It belongs to ctx and follows its rule (one call in flight; the ctx must outlive it).
+ *
+ * The container: the global magic "!<arch>\n", 60-byte member headers (name[16], the size in decimal at bytes 48..57,
+ * fmag "`\n"), data padded to an even offset.  The reference reads it with an ar library that is not part of its tree,
+ * so a member's name is defined HERE: its 16 bytes with trailing spaces removed.  A GNU long-name table ("//") is not
+ * supported.  SNAPHASH_EFORMAT: a wrong magic or fmag, a size field that is not digits then spaces, a header or a member
+ * the end of the file cuts off.
+ * Member lookup is skipToArMember's (deb.go:408-441): the FIRST member whose name starts with "control.tar" /
+ * "data.tar"; ".gz" takes the gzip engine, ".bz2" the bzip2 engine, ".xz" and anything else SNAPHASH_EINVAL with the
+ * reference's text "Can not handle NAME" (as snaphash_tar_create answers a name that is not ".gz"); no such member is
+ * SNAPHASH_EFORMAT with the prefix in the message.
+ * open reads the file once and decodes nothing.  Each of the two tars is decoded at most once per session, by the
+ * first call that needs it; the decoded stream and its member list stay in the session (the reference decodes
+ * data.tar.gz once per MetaMember call and once more in Unpack). */
+typedef struct snaphash_snap snaphash_snap;
+int  snaphash_snap_open(snaphash_ctx *ctx, const char *snap_path, snaphash_snap **out);   /* ClickDeb.Open */
+void snaphash_snap_close(snaphash_snap *s);
+size_t snaphash_snap_members(const snaphash_snap *s);
+/* name: owned by the session; offset: of the member's data in the file */
+int  snaphash_snap_member_info(const snaphash_snap *s, size_t i, const char **name, uint64_t *offset, uint64_t *size);
+/* ClickDeb.ControlMember / MetaMember (deb.go:141-183): the LAST tar member with filepath.Clean(hdr.Name) == name
+ * ("meta/" joined in front for meta_member); *content malloc'd (snaphash_free), *len 0 and *content NULL when absent */
+int  snaphash_snap_control_member(snaphash_snap *s, const char *name, void **content, size_t *len);
+int  snaphash_snap_meta_member(snaphash_snap *s, const char *name, void **content, size_t *len);
+/* ClickDeb.Unpack (deb.go:188-203) with snaphash_tar_unpack's rules, from the member in memory (no temporary file);
+ * verify != 0: also the install-time Verify, against the package's OWN hashes.yaml out of control.tar.* (none there:
+ * SNAPHASH_EMISMATCH kind 1, name "hashes.yaml").  archive_digest (may be NULL) and archive-sha512: over the bytes of
+ * the data.tar.* member alone.  snaphash_get_unpack_stats then describes the data.tar.* decode of this session. */
+int  snaphash_snap_unpack(snaphash_snap *s, const char *target_dir, int verify, snaphash_mismatch *first, uint8_t *archive_digest);
+/* Nothing is written: every check the package carries, made on the decoded bytes.  These semantics are this library's
+ * (the reference checks nothing of the kind at install time), the first failure in this order:
+ *   1. decoding: every gzip member's CRC-32 and ISIZE, every bzip2 block CRC and combined CRC, the tar framing:
+ *      SNAPHASH_EFORMAT (SNAPHASH_ECONTENT for what unpack would refuse);
+ *   2. archive-sha512 against the data.tar.* member's bytes: SNAPHASH_EMISMATCH kind 6;
+ *   3. the records of hashes.yaml in yaml order, each against the LAST tar member of its name (names after filepath.Clean,
+ *      which drops a leading "./"; an EARLIER member of the name is not looked at, though an unpack would keep the mode
+ *      it created the file with): none is kind 1; the type letter or the low nine mode bits of the TAR HEADER differ:
+ *      kind 5; for regular files the size: kind 3, then the SHA-512: kind 4;
+ *   4. the tar members in tar order: one without a record is kind 2 (the root entry "." is not one).
+ * A package without hashes.yaml: kind 1, name "hashes.yaml".  Under SNAPHASH_FLAG_GPU_ONLY the CRCs of (1) are taken by the
+ * CRC kernels out of the decoded stream in HBM (a range per gzip member / per bzip2 block; the bzip2 combined CRC is
+ * folded from them on the host) and the digests by the SHA-512 kernels out of the same buffer; in the default
+ * configuration the CRCs stay on host threads.  The verdict is the same in both. */
+int  snaphash_snap_audit(snaphash_snap *s, snaphash_mismatch *first, uint8_t *archive_digest);
+
+typedef struct snaphash_snap_stats { /* of the session so far */
+    uint32_t struct_size;       /* in: sizeof(snaphash_snap_stats) */
+    uint32_t reserved;
+    uint64_t data_decodes;      /* times data.tar.* was decoded (at most 1) */
+    uint64_t control_decodes;   /* times control.tar.* was decoded (at most 1) */
+    uint64_t device_crc_ranges; /* CRCs the CRC kernels took (gzip members, bzip2 blocks) */
+    uint64_t host_crc_ranges;   /* CRCs host threads took */
+    double device_crc_ms;       /* the CRC kernels, HIP events */
+} snaphash_snap_stats;
+int snaphash_snap_get_stats(const snaphash_snap *s, snaphash_snap_stats *out);
+
 /* ---- neighbouring scan: helpers.FilesAreEqual / DirUpdated -------- */
 
 /* helpers.FilesAreEqual (helpers/cmp.go:31-60), batched: equal[i] = 1 iff a[i] and b[i] both

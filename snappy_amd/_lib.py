@@ -42,7 +42,12 @@ EXPORTS = [
     "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats", "snaphash_get_block_scan_stats",
     # data.tar.bz2
     "snaphash_bunzip2_buffer", "snaphash_tar_unpack_bz2",
+    # the .snap itself: CRCs in HBM, the ar container, audit and unpack
+    "snaphash_crc32_device", "snaphash_snap_open", "snaphash_snap_close", "snaphash_snap_members", "snaphash_snap_member_info",
+    "snaphash_snap_control_member", "snaphash_snap_meta_member", "snaphash_snap_unpack", "snaphash_snap_audit",
+    "snaphash_snap_get_stats",
 ]
+CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
 FLAG_SPLIT_BLOCKS = 64  # gunzip_buffer / tar_unpack: cut streams without flush points at their DEFLATE blocks too
 
@@ -112,6 +117,12 @@ class BlockScanStats(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("bits_scanned", ctypes.c_uint64),
                 ("candidates", ctypes.c_uint64), ("linked", ctypes.c_uint64), ("unreached", ctypes.c_uint64),
                 ("host_blocks", ctypes.c_uint64), ("scan_ms", ctypes.c_double)]
+
+
+class SnapStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("data_decodes", ctypes.c_uint64),
+                ("control_decodes", ctypes.c_uint64), ("device_crc_ranges", ctypes.c_uint64), ("host_crc_ranges", ctypes.c_uint64),
+                ("device_crc_ms", ctypes.c_double)]
 
 
 class Mismatch(ctypes.Structure):
@@ -207,6 +218,18 @@ def lib():
     L.snaphash_get_block_scan_stats.argtypes = [vp, ctypes.POINTER(BlockScanStats)]
     L.snaphash_bunzip2_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_crc32_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, sz, vp]
+    L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.snaphash_snap_close.argtypes = [vp]
+    L.snaphash_snap_close.restype = None
+    L.snaphash_snap_members.argtypes = [vp]
+    L.snaphash_snap_members.restype = sz
+    L.snaphash_snap_member_info.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_char_p), u64p, u64p]
+    L.snaphash_snap_control_member.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_snap_meta_member.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_snap_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_snap_audit.argtypes = [vp, ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_snap_get_stats.argtypes = [vp, ctypes.POINTER(SnapStats)]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -459,6 +482,19 @@ class Context:
         self._check(rc)
         return None, dig.raw
 
+    def crc32_device(self, kind, d_base, offsets, lens):
+        """CRC-32s (kind: CRC_GZIP / CRC_BZIP2) of byte ranges resident in HBM.  d_base: device address (int); offsets /
+        lens: contiguous numpy uint64 arrays, any alignment.  -> numpy uint32 array."""
+        import numpy as np
+        n = len(offsets)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(lib().snaphash_crc32_device(self._h, kind, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
+    def snap_open(self, snap_path):
+        """A session on a .snap file (ClickDeb.Open): see Snap."""
+        return Snap(self, snap_path)
+
     def unpack_stats(self):
         s = UnpackStats()
         s.struct_size = ctypes.sizeof(UnpackStats)
@@ -563,6 +599,78 @@ class Context:
         out = {f[0]: getattr(s, f[0]) for f in Stats._fields_}
         out["device"] = d.value
         return out
+
+
+class Snap:
+    """snaphash_snap_*: one .snap file read once, its ar members, and its two tars decoded at most once each."""
+
+    def __init__(self, ctx, snap_path):
+        self._ctx = ctx
+        h = ctypes.c_void_p()
+        ctx._check(lib().snaphash_snap_open(ctx._h, os.fsencode(snap_path), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().snaphash_snap_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def members(self):
+        """-> [(name, offset of the data in the file, size)] in file order."""
+        out = []
+        name, off, size = ctypes.c_char_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        for i in range(lib().snaphash_snap_members(self._h)):
+            self._ctx._check(lib().snaphash_snap_member_info(self._h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(size)))
+            out.append((name.value.decode(errors="surrogateescape"), off.value, size.value))
+        return out
+
+    def _member(self, fn, name):
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._ctx._check(fn(self._h, os.fsencode(name), ctypes.byref(p), ctypes.byref(n)))
+        if not p.value:
+            return None
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def control_member(self, name):
+        """ClickDeb.ControlMember -> bytes, or None when control.tar.* has no such member."""
+        return self._member(lib().snaphash_snap_control_member, name)
+
+    def meta_member(self, name):
+        """ClickDeb.MetaMember -> bytes of meta/<name> in data.tar.*, or None."""
+        return self._member(lib().snaphash_snap_meta_member, name)
+
+    def _verdict(self, rc, m, dig):
+        if rc == EMISMATCH:
+            return (m.kind, m.name.decode(errors="replace")), dig.raw
+        self._ctx._check(rc)
+        return None, dig.raw
+
+    def unpack(self, target_dir, verify=True):
+        """ClickDeb.Unpack into target_dir; verify: also the install-time Verify against the package's own hashes.yaml.
+        -> (None or (kind, name) of the first mismatch, SHA-512 of the data.tar.* member (64 bytes))."""
+        m, dig = Mismatch(), ctypes.create_string_buffer(64)
+        return self._verdict(lib().snaphash_snap_unpack(self._h, os.fsencode(target_dir), 1 if verify else 0, ctypes.byref(m), dig), m, dig)
+
+    def audit(self):
+        """Every check the package carries, nothing written.  -> (None or (kind, name), SHA-512 of the data.tar.* member)."""
+        m, dig = Mismatch(), ctypes.create_string_buffer(64)
+        return self._verdict(lib().snaphash_snap_audit(self._h, ctypes.byref(m), dig), m, dig)
+
+    def stats(self):
+        s = SnapStats(ctypes.sizeof(SnapStats))
+        self._ctx._check(lib().snaphash_snap_get_stats(self._h, ctypes.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in SnapStats._fields_ if f[0] not in ("struct_size", "reserved")}
 
 
 class Batch:

@@ -14,6 +14,12 @@
  *   snaphash [options] unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML]
  *                                      ClickDeb.Unpack (clickdeb/deb.go:188-203) into DIR; with HASHES_YAML also the
  *                                      install-time Verify from the decoded bytes; exit 1 on mismatch
+ *   snaphash [options] snap ls FILE.snap         the ar members of the package: size, offset, name
+ *   snaphash [options] snap cat-control NAME FILE.snap   ClickDeb.ControlMember on stdout (exit 1 when absent)
+ *   snaphash [options] snap cat-meta NAME FILE.snap      ClickDeb.MetaMember on stdout (exit 1 when absent)
+ *   snaphash [options] snap audit FILE.snap      every check the package carries, nothing written; exit 1 on mismatch
+ *   snaphash [options] snap unpack DIR FILE.snap ClickDeb.Unpack + Verify against the package's own hashes.yaml;
+ *                                      exit 1 on mismatch; -s prints the unpack and session statistics
  *   snaphash [options] cmp A B [A B ...]         helpers.FilesAreEqual per pair; exit 1 if any pair differs
  *   snaphash [options] dirupdated DIR_A DIR_B [PREFIX]   helpers.DirUpdated
  * options: -d DEV[,DEV...]  engines (default: the current device; -1 = all visible)
@@ -42,6 +48,7 @@ static int usage(void)
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
+                    "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
                     "       -b: gunzip / unpack also split streams without flush points at their blocks (SNAPHASH_FLAG_SPLIT_BLOCKS)\n"
@@ -238,6 +245,52 @@ int main(int argc, char **argv)
             if (!bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         }
         free(y);
+    } else if (!strcmp(argv[1], "snap") && argc >= 4) {
+        const char *verb = argv[2], *file = argv[argc - 1];
+        const int takes_arg = !strcmp(verb, "cat-control") || !strcmp(verb, "cat-meta") || !strcmp(verb, "unpack");
+        const int known = takes_arg || !strcmp(verb, "ls") || !strcmp(verb, "audit");
+        snaphash_snap *sn = NULL;
+        if (!known || argc != (takes_arg ? 5 : 4)) ret = usage();
+        else if ((rc = snaphash_snap_open(c, file, &sn)) != 0) ret = die(c, rc, "snap");
+        else if (!strcmp(verb, "ls")) {
+            for (size_t i = 0; i < snaphash_snap_members(sn); i++) {
+                const char *nm;
+                uint64_t off, sz;
+                snaphash_snap_member_info(sn, i, &nm, &off, &sz);
+                printf("%10llu %10llu %s\n", (unsigned long long)sz, (unsigned long long)off, nm);
+            }
+        } else if (!strcmp(verb, "cat-control") || !strcmp(verb, "cat-meta")) {
+            void *p = NULL;
+            size_t len = 0;
+            rc = verb[4] == 'c' ? snaphash_snap_control_member(sn, argv[3], &p, &len) : snaphash_snap_meta_member(sn, argv[3], &p, &len);
+            if (rc) ret = die(c, rc, verb);
+            else if (!p) { fprintf(stderr, "snaphash: %s: no member %s\n", verb, argv[3]); ret = 1; }
+            else fwrite(p, 1, len, stdout);
+            snaphash_free(p);
+        } else {
+            snaphash_mismatch m;
+            uint8_t dig[64];
+            rc = !strcmp(verb, "audit") ? snaphash_snap_audit(sn, &m, dig) : snaphash_snap_unpack(sn, argv[3], 1, &m, dig);
+            if (rc) ret = die(c, rc, verb);
+            else printf("OK\n");
+            if (show_stats) {
+                snaphash_unpack_stats us;
+                snaphash_snap_stats ss;
+                us.struct_size = sizeof us;
+                ss.struct_size = sizeof ss;
+                if (!snaphash_get_unpack_stats(c, &us))
+                    fprintf(stderr, "snap %s: %llu compressed bytes -> %llu tar bytes, %llu members, %llu segments (%llu on the GPU), "
+                                    "%llu bytes decoded on the host, decode kernels %.2f ms, wall %.2f ms\n",
+                            verb, (unsigned long long)us.gz_bytes, (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
+                            (unsigned long long)us.segments, (unsigned long long)us.gpu_segments, (unsigned long long)us.host_bytes,
+                            us.inflate_ms, us.wall_ms);
+                if (!snaphash_snap_get_stats(sn, &ss))
+                    fprintf(stderr, "snap %s: data.tar decoded %llu time(s), control.tar %llu; CRCs: %llu on the device (%.3f ms), %llu on host threads\n",
+                            verb, (unsigned long long)ss.data_decodes, (unsigned long long)ss.control_decodes,
+                            (unsigned long long)ss.device_crc_ranges, ss.device_crc_ms, (unsigned long long)ss.host_crc_ranges);
+            }
+        }
+        snaphash_snap_close(sn);
     } else if (!strcmp(argv[1], "cmp") && argc >= 4 && argc % 2 == 0) {
         size_t n = ((size_t)argc - 2) / 2;
         const char **pa = malloc(n * sizeof *pa), **pb = malloc(n * sizeof *pb);

@@ -4,7 +4,7 @@ Same name, argument meaning and error behaviour as the Go function: tarCreate(ta
 sourceDir, asks fn(path) for every regular file, symlink and directory (False leaves it out; None keeps all),
 writes members "./<relative path>" owned by root through gzip into tarname, and raises on the first error.
 tarCreate writes ".gz" only: the reference's ".xz" branch shells out to an external tool.  Unpack reads
-data.tar.gz, UnpackBz2 data.tar.bz2.  Test/bench harness, like
+data.tar.gz, UnpackBz2 data.tar.bz2; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203).  Test/bench harness, like
 helpers.py and hashes.py: the product is the C ABI.
 """
 from .helpers import default_context
@@ -31,3 +31,49 @@ def UnpackBz2(dataTarBz2, targetDir, hashesYaml=None, ctx=None):
     -> None, or (kind, name) of the first mismatch against hashesYaml."""
     mismatch, _ = (ctx or default_context()).tar_unpack_bz2(dataTarBz2, targetDir, hashesYaml)
     return mismatch
+
+
+class ClickDeb:
+    """The reference's ClickDeb on a .snap file (clickdeb/deb.go:108-203): the ar container read once, control.tar.* and
+    data.tar.* decoded at most once each however many calls follow.  ClickDeb.open(path) as the Go Open; a context manager."""
+
+    def __init__(self, snap):
+        self._snap = snap
+
+    @classmethod
+    def open(cls, path, ctx=None):
+        return cls((ctx or default_context()).snap_open(path))
+
+    def close(self):
+        self._snap.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def members(self):
+        """-> [(name, offset, size)] of the ar members."""
+        return self._snap.members()
+
+    def control_member(self, name):
+        """ClickDeb.ControlMember: the content of `name` in control.tar.* (None when absent)."""
+        return self._snap.control_member(name)
+
+    def meta_member(self, name):
+        """ClickDeb.MetaMember: the content of meta/<name> in data.tar.* (None when absent)."""
+        return self._snap.meta_member(name)
+
+    def unpack(self, targetDir, verify=True):
+        """ClickDeb.Unpack into targetDir, with the install-time Verify against the package's own hashes.yaml.
+        -> None, or (kind, name) of the first mismatch."""
+        return self._snap.unpack(targetDir, verify)[0]
+
+    def audit(self):
+        """Every check the package carries (CRCs, archive-sha512, every record of hashes.yaml), nothing written.
+        -> None, or (kind, name) of the first mismatch."""
+        return self._snap.audit()[0]
+
+    def stats(self):
+        return self._snap.stats()

@@ -8,6 +8,7 @@
 
 #include "bzip2_host.h"
 #include "bzip2_kernels.h"
+#include "crc_kernels.h"
 #include "deflate_kernels.h"
 #include "devbuf.h"
 #include "inflate_core.h"
@@ -205,6 +206,26 @@ struct Bzip2Bufs {
     {
         f(d_in); f(d_cand); f(h_cand); f(d_count); f(h_count); f(d_slots); f(d_tt); f(d_chunks); f(d_res); f(h_res); f(d_blk); f(h_blk);
     }
+};
+
+// CRC-32 of ranges in HBM (crc_kernels.hip): the ranges and the prefix of their tile counts, built in pinned memory, and
+// their HBM twins; a remainder per tile; the finished CRCs and their way back
+struct CrcBufs {
+    Twin<uint64_t> offs, lens;
+    Twin<uint32_t> tile0; // n + 1
+    DevBuf<uint32_t> d_partial;
+    Twin<uint32_t> crcs;
+    hipError_t ensure(size_t n, size_t tiles)
+    {
+        hipError_t e = offs.ensure(n);
+        if (!e) e = lens.ensure(n);
+        if (!e) e = tile0.ensure(n + 1);
+        if (!e) e = d_partial.reserve(std::max<size_t>(tiles, 1));
+        if (!e) e = crcs.ensure(n);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { offs.each(f); lens.each(f); tile0.each(f); f(d_partial); crcs.each(f); }
 };
 
 } // namespace snaphash

@@ -1,0 +1,302 @@
+// snap.inc -- the .snap itself, textually part of snaphash_api.cpp (after unpack.inc and unbz2.inc, whose decoders, tar
+// reader, member writer and Verify tail it drives).
+//
+// The reference opens a package with ClickDeb.Open (clickdeb/deb.go:108-127) and reads it through an `ar` reader:
+// ControlMember / MetaMember (deb.go:141-183) decode a whole tar to fetch one file, Unpack (deb.go:188-203) decodes
+// data.tar.* again.  Here a session reads the file once, parses the container (snap_core.h), and decodes each of the two
+// tars at most once: the decoded stream and its member list stay in the session, the data.tar stream in c->inf.d_out too
+// for the in-pass Verify and the audit.  Another decode on the ctx may take that buffer (control.tar.* after a
+// MetaMember call does): the engine counts the decodes that wrote it (DevCtx::fout_gen), and a session whose stream is no
+// longer there copies it up again from host memory -- it is never decoded twice.
+
+struct snaphash_snap {
+    snaphash_ctx* x = nullptr;
+    std::string path;
+    std::vector<uint8_t> file;
+    std::vector<ArMember> mem;
+    struct Tar {
+        bool tried = false;
+        int rc = 0;            // of the decode and tar_read
+        std::string err;
+        size_t member = 0;     // index into mem
+        std::vector<uint8_t> tar;
+        std::vector<TarEntry> ents;
+        snaphash_unpack_stats st{};
+        uint8_t adig[64] = {0}; // SHA-512 of the member's bytes
+        uint64_t gen = 0;       // DevCtx::fout_gen when the stream was left in c->inf.d_out
+    } control, data;
+    snaphash_snap_stats stats{};
+    CrcTally tally;
+};
+
+namespace {
+
+// The tar behind `prefix`, decoded once: t.rc / t.err keep what came of it for every later call.
+int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool keep_dev)
+{
+    snaphash_ctx* x = s->x;
+    DevCtx* c = x->d0();
+    if (t.tried) return t.rc ? fail(x, t.rc, t.err) : 0;
+    t.tried = true;
+    int codec = 0;
+    std::string why;
+    t.rc = ar_pick(s->mem, prefix, &t.member, &codec, why);
+    if (t.rc) { t.err = why; return fail(x, t.rc, t.err); }
+    const uint8_t* z = s->file.data() + s->mem[t.member].off;
+    const size_t zn = (size_t)s->mem[t.member].size;
+    t.st = snaphash_unpack_stats{};
+    t.st.struct_size = sizeof t.st;
+    t.st.gz_bytes = zn;
+    const double t0 = now_ms();
+    {
+        std::thread dig_th([&] {
+            HostSha h;
+            host_sha512_init(h);
+            host_sha512_update(h, z, zn);
+            host_sha512_final(h, t.adig);
+        });
+        struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{dig_th};
+        // under SNAPHASH_FLAG_GPU_ONLY the stream reaches HBM before host memory: the CRCs are taken there
+        const CrcAt at = x->gpu_only ? CrcAt::Device : CrcAt::Host;
+        t.rc = codec == kSnapGz ? gunzip_engine(x, c, z, zn, t.tar, keep_dev, t.st, at, &s->tally)
+                                : bunzip2_engine(x, c, z, zn, t.tar, keep_dev, t.st, at, &s->tally);
+        c->ev_used = 0;
+    }
+    (&t == &s->data ? s->stats.data_decodes : s->stats.control_decodes)++;
+    s->stats.device_crc_ranges = s->tally.device_ranges;
+    s->stats.host_crc_ranges = s->tally.host_ranges;
+    s->stats.device_crc_ms = s->tally.device_ms;
+    t.gen = c->fout_gen;
+    t.st.tar_bytes = t.tar.size();
+    if (t.rc) { t.err = c->last_error; return lift(x, c, t.rc); }
+    t.rc = tar_read(t.tar.data(), t.tar.size(), t.ents, why);
+    t.st.members = t.ents.size();
+    t.st.wall_ms = now_ms() - t0;
+    if (t.rc) { t.err = why; return fail(x, t.rc, t.err); }
+    return 0;
+}
+
+// member(): the content of the LAST tar member whose cleaned name is `want` (deb.go:167-176)
+int snap_member(snaphash_snap* s, snaphash_snap::Tar& t, const std::string& want, void** content, size_t* len)
+{
+    *content = nullptr;
+    *len = 0;
+    const TarEntry* hit = nullptr;
+    for (const TarEntry& e : t.ents)
+        if (e.name == want) hit = &e;
+    if (!hit) return SNAPHASH_OK;
+    void* p = malloc(hit->size ? (size_t)hit->size : 1);
+    if (!p) return fail(s->x, SNAPHASH_ENOMEM, "malloc");
+    if (hit->size) memcpy(p, t.tar.data() + hit->data_off, (size_t)hit->size);
+    *content = p;
+    *len = (size_t)hit->size;
+    return SNAPHASH_OK;
+}
+
+// the package's own hashes.yaml out of control.tar.*; *yaml stays null when there is none
+int snap_yaml(snaphash_snap* s, const uint8_t** yaml, size_t* yaml_len)
+{
+    *yaml = nullptr;
+    int rc = snap_tar(s, s->control, "control.tar", false);
+    if (rc) return rc;
+    for (const TarEntry& e : s->control.ents)
+        if (e.name == "hashes.yaml" && e.type == '0') { *yaml = s->control.tar.data() + e.data_off; *yaml_len = (size_t)e.size; }
+    return 0;
+}
+
+// the data.tar stream in c->inf.d_out again if another decode has written there since
+int snap_data_on_device(snaphash_snap* s)
+{
+    DevCtx* c = s->x->d0();
+    if (s->data.gen == c->fout_gen && c->inf.d_out.size() >= s->data.tar.size()) return 0;
+    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    int rc = ensure_fout(c, std::max<size_t>(s->data.tar.size(), 1), 0);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->inf.d_out.data(), s->data.tar.data(), s->data.tar.size(), hipMemcpyHostToDevice, c->f_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->f_stream));
+    s->data.gen = ++c->fout_gen;
+    return 0;
+}
+
+#define SNAP_ENTER(s)                                                            \
+    if (!(s) || !(s)->x) return SNAPHASH_EINVAL;                                 \
+    snaphash_ctx* x = (s)->x;                                                    \
+    TOP_ENTER(x);                                                                \
+    DevCtx* c = x->d0();                                                         \
+    HIP_TRY(c, hipSetDevice(c->device))
+
+} // namespace
+
+extern "C" {
+
+int snaphash_crc32_device(snaphash_ctx* x, int kind, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                          uint32_t* crcs)
+try {
+    if (!x || (n && (!d_base || !offsets || !lens || !crcs)) || (kind != kCrcGzip && kind != kCrcBzip2)) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
+    HIP_TRY(c, hipSetDevice(c->device));
+    double ms = 0;
+    const int rc = crc_ranges_dev(c, kind, (const uint8_t*)d_base, offsets, lens, n, crcs, c->stream, &ms);
+    c->ev_used = 0;
+    x->stats.kernel_ms = ms;
+    x->stats.launches = n ? 2 : 0;
+    end_top(x, t_top0_);
+    return lift(x, c, rc);
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_snap_open(snaphash_ctx* x, const char* snap_path, snaphash_snap** out)
+try {
+    if (!x || !snap_path || !out) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *out = nullptr;
+    std::unique_ptr<snaphash_snap> s(new snaphash_snap);
+    s->x = x;
+    s->path = snap_path;
+    s->stats.struct_size = sizeof s->stats;
+    int rc = read_whole(x, snap_path, s->file);
+    if (rc) return rc;
+    std::string why;
+    rc = ar_parse(s->file.data(), s->file.size(), s->mem, why);
+    if (rc) return fail(x, rc, std::string(snap_path) + ": " + why);
+    *out = s.release();
+    return SNAPHASH_OK;
+} catch (...) {
+    return SNAPHASH_ENOMEM;
+}
+
+void snaphash_snap_close(snaphash_snap* s) { delete s; }
+
+size_t snaphash_snap_members(const snaphash_snap* s) { return s ? s->mem.size() : 0; }
+
+int snaphash_snap_member_info(const snaphash_snap* s, size_t i, const char** name, uint64_t* offset, uint64_t* size)
+{
+    if (!s || i >= s->mem.size()) return SNAPHASH_EINVAL;
+    if (name) *name = s->mem[i].name.c_str();
+    if (offset) *offset = s->mem[i].off;
+    if (size) *size = s->mem[i].size;
+    return SNAPHASH_OK;
+}
+
+int snaphash_snap_control_member(snaphash_snap* s, const char* name, void** content, size_t* len)
+try {
+    if (!s || !name || !content || !len) return SNAPHASH_EINVAL;
+    SNAP_ENTER(s);
+    (void)t_top0_;
+    const int rc = snap_tar(s, s->control, "control.tar", false);
+    if (rc) return rc;
+    return snap_member(s, s->control, name, content, len);
+} catch (...) {
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_snap_meta_member(snaphash_snap* s, const char* name, void** content, size_t* len)
+try {
+    if (!s || !name || !content || !len) return SNAPHASH_EINVAL;
+    SNAP_ENTER(s);
+    (void)t_top0_;
+    const int rc = snap_tar(s, s->data, "data.tar", true);
+    if (rc) return rc;
+    return snap_member(s, s->data, go_clean(std::string("meta/") + name), content, len); // filepath.Join cleans
+} catch (...) {
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_snap_unpack(snaphash_snap* s, const char* target_dir, int verify, snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!s || !target_dir) return SNAPHASH_EINVAL;
+    SNAP_ENTER(s);
+    const uint8_t* yaml = nullptr;
+    size_t yaml_len = 0;
+    int rc = 0;
+    if (verify) {
+        rc = snap_yaml(s, &yaml, &yaml_len);
+        if (rc) return rc;
+        if (!yaml) return mismatch(x, first, 1, "hashes.yaml");
+    }
+    rc = snap_tar(s, s->data, "data.tar", true);
+    snaphash_unpack_stats st = s->data.st;
+    if (archive_digest && s->data.tried && s->data.member < s->mem.size()) memcpy(archive_digest, s->data.adig, 64);
+    if (!rc) rc = lift(x, c, unpack_members(c, s->data.ents, s->data.tar.data(), target_dir));
+    if (!rc && verify) {
+        rc = snap_data_on_device(s);
+        const std::vector<size_t> reg = last_regular_members(s->data.ents);
+        std::vector<uint8_t> dig;
+        if (!rc) rc = hash_members(x, c, s->data.tar, s->data.ents, reg, dig);
+        if (!rc) {
+            std::unordered_map<std::string, size_t> dig_of;
+            for (size_t q = 0; q < reg.size(); ++q) dig_of[s->data.ents[reg[q]].name] = q;
+            rc = verify_impl(x, target_dir, s->path.c_str(), s->data.adig, (const char*)yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
+                const auto it = dig_of.find(r.name);
+                if (it == dig_of.end() || (int64_t)s->data.ents[reg[it->second]].size != r.size) return false;
+                memcpy(d, dig.data() + 64 * it->second, 64);
+                return true;
+            });
+        }
+    }
+    st.wall_ms = now_ms() - t_top0_;
+    x->unpack = st;
+    end_top(x, t_top0_);
+    return rc;
+} catch (...) {
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_snap_audit(snaphash_snap* s, snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!s) return SNAPHASH_EINVAL;
+    SNAP_ENTER(s);
+    const uint8_t* yaml = nullptr;
+    size_t yaml_len = 0;
+    int rc = snap_yaml(s, &yaml, &yaml_len);
+    if (rc) return rc;
+    if (!yaml) return mismatch(x, first, 1, "hashes.yaml");
+    rc = snap_tar(s, s->data, "data.tar", true);
+    if (s->data.tried && s->data.member < s->mem.size() && archive_digest) memcpy(archive_digest, s->data.adig, 64);
+    if (rc) return rc;
+    x->unpack = s->data.st;
+    ParsedHashes ph;
+    rc = parse_yaml((const char*)yaml, yaml_len, ph);
+    if (rc) return fail(x, rc, "hashes.yaml: parse error");
+    if (!ph.has_archive || !digest_matches_hex(s->data.adig, ph.archive_hex)) return mismatch(x, first, 6, "archive-sha512");
+    rc = snap_data_on_device(s);
+    if (rc) return lift(x, c, rc);
+    const std::vector<TarEntry>& ents = s->data.ents;
+    const std::vector<size_t> reg = last_regular_members(ents);
+    std::vector<uint8_t> dig;
+    rc = hash_members(x, c, s->data.tar, ents, reg, dig);
+    if (rc) return rc;
+    std::vector<AuditMember> mem(ents.size());
+    for (size_t k = 0; k < ents.size(); ++k) {
+        mem[k].name = ents[k].name;
+        mem[k].type = ents[k].type;
+        mem[k].mode = ents[k].mode;
+        mem[k].size = ents[k].size;
+    }
+    for (size_t q = 0; q < reg.size(); ++q) mem[reg[q]].digest = dig.data() + 64 * q;
+    std::vector<AuditRecord> recs(ph.files.size());
+    for (size_t i = 0; i < recs.size(); ++i) {
+        recs[i].name = ph.files[i].name;
+        recs[i].st_mode = ph.files[i].st_mode;
+        recs[i].has_size = ph.files[i].has_size;
+        recs[i].size = ph.files[i].size;
+        recs[i].sha512_hex = ph.files[i].sha512_hex;
+    }
+    std::string name;
+    const int kind = snap_audit_compare(recs, mem, &name);
+    end_top(x, t_top0_);
+    return kind ? mismatch(x, first, kind, name) : SNAPHASH_OK;
+} catch (...) {
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_snap_get_stats(const snaphash_snap* s, snaphash_snap_stats* out)
+{
+    if (!s || !out || out->struct_size < sizeof(snaphash_snap_stats)) return SNAPHASH_EINVAL;
+    *out = s->stats;
+    out->struct_size = sizeof(snaphash_snap_stats);
+    return SNAPHASH_OK;
+}
+
+} // extern "C"

@@ -47,6 +47,7 @@
 #include "planner.h"
 #include "sha512_core.h"
 #include "sha512_kernels.h"
+#include "snap_core.h"
 #include "tarpack.h"
 #include "walk.h"
 
@@ -94,7 +95,9 @@ struct DevCtx {
     std::vector<hipEvent_t> z_part_ev;       // "part k of the pass's first slot is in HBM" (targz.inc)
     InflateBufs inf;
     Bzip2Bufs bz;
+    CrcBufs crc;
     hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
+    uint64_t fout_gen = 0;          // counts the decodes that wrote inf.d_out: a .snap session knows by it whether its stream is still there
 
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;
@@ -128,6 +131,7 @@ struct DevCtx {
         z.each(f);
         inf.each(f);
         bz.each(f);
+        crc.each(f);
     }
 };
 
@@ -2292,6 +2296,7 @@ void snaphash_batch_abort(snaphash_batch* b)
 #include "targz.inc"
 #include "unpack.inc"
 #include "unbz2.inc"
+#include "snap.inc"
 
 // ---- helpers.FilesAreEqual / DirUpdated (row f4) ----------------------------------------------
 

@@ -27,8 +27,10 @@ int ensure_bzip2(DevCtx* c, uint64_t piece, uint32_t slots)
 // the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->inf.d_out (after the decoded
 // stream so far when keep_dev), the bytes back to out, and every block's CRC checked on host threads, one block each
 // (bz_crc_block runs at about 0.4 GB/s a core: the host threads keep pace with the kernels; DESIGN.md sec. 15).
+// crc_at = CrcAt::Device: the blocks' CRCs by the CRC kernels instead, a range a block at the offsets the RLE1 stage wrote
+// them to, before the bytes travel back.
 int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uint32_t>& crcs, std::vector<uint8_t>& out, bool keep_dev,
-                  snaphash_unpack_stats& st, float& kms)
+                  snaphash_unpack_stats& st, float& kms, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
 {
     auto timed = [&](EventPair* ev) {
         float ms = 0;
@@ -65,6 +67,21 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
     BZ_TRY(hipMemcpyAsync(out.data() + o0, c->inf.d_out.data() + base, total, hipMemcpyDeviceToHost, c->f_stream));
     BZ_TRY(hipStreamSynchronize(c->f_stream));
     timed(ev);
+    if (crc_at == CrcAt::Device) {
+        std::vector<uint64_t> offs(nb), lens(nb);
+        for (uint32_t i = 0; i < nb; ++i) { offs[i] = c->bz.h_blk[i].out_off; lens[i] = c->bz.h_blk[i].out_len; }
+        std::vector<uint32_t> got(nb);
+        double ms = 0;
+        rc = crc_ranges_dev(c, kCrcBzip2, c->inf.d_out.data(), offs.data(), lens.data(), nb, got.data(), c->f_stream, &ms);
+        if (rc) return rc;
+        if (tally) { tally->device_ranges += nb; tally->device_ms += ms; }
+        if (got != crcs) return fail(c, SNAPHASH_EFORMAT, "bzip2: block CRC mismatch");
+        st.segments += nb;
+        st.gpu_segments += nb;
+        c->ev_used = 0;
+        return SNAPHASH_OK;
+    }
+    if (tally) tally->host_ranges += nb;
     std::atomic<uint32_t> next{0}, bad{0};
     auto work = [&]() {
         for (;;) {
@@ -91,9 +108,10 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
 // Decodes every stream of bz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
 // c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
 int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
-                   snaphash_unpack_stats& st)
+                   snaphash_unpack_stats& st, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: empty stream");
+    c->fout_gen++;
     const unsigned cpus = std::max(1u, x->cpus_call ? x->cpus_call : x->cpus);
     const size_t o_start = out.size();
     auto to_dev = [&](size_t from) -> int { // host-decoded bytes out[from..) into c->inf.d_out.data() at the same offset
@@ -116,6 +134,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
         }
         st.segments += blocks;
         st.host_bytes += out.size() - o_start;
+        if (tally) tally->host_ranges += blocks;
         return to_dev(o_start);
     }
     BzCursor cur;
@@ -139,6 +158,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
         bz_cursor_take(cur, r.end_bit, r.crc);
         st.segments++;
         st.host_bytes += out.size() - o0;
+        if (tally) tally->host_ranges++; // (the host decoder checks its block's CRC itself)
         return to_dev(o0);
     };
     bool chain_order = false; // more candidates than the cap: one block a launch, in chain order
@@ -225,7 +245,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
                     bz_cursor_take(cur, r.end_bit + pb * 8, r.crc);
                 }
                 if (nb) {
-                    rc = bunzip2_batch(x, c, nb, crcs, out, keep_dev, st, kms);
+                    rc = bunzip2_batch(x, c, nb, crcs, out, keep_dev, st, kms, crc_at, tally);
                     if (rc) return rc;
                 }
                 if (!host_next) break;

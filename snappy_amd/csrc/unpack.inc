@@ -38,6 +38,54 @@ int ensure_fout(DevCtx* c, uint64_t need, uint64_t keep)
 
 #define INF_TRY(expr) HIP_TRY(c, (expr))
 
+// Where a decoder takes the CRCs it checks.  Host: on host threads, out of the decoded bytes in host memory (every entry
+// point before the .snap session, and the session in the default configuration).  Device: by crc_kernels.hip out of the
+// decoded stream in c->inf.d_out -- the session's choice under SNAPHASH_FLAG_GPU_ONLY (snap.inc).
+enum class CrcAt { Host, Device };
+struct CrcTally { // what a session's decodes did about their CRCs
+    uint64_t device_ranges = 0, host_ranges = 0;
+    double device_ms = 0; // the CRC kernels, HIP events
+};
+
+// The CRC-32s (kind: kCrcGzip / kCrcBzip2) of n ranges of d_base on stream s, back on the host when the call returns.
+int crc_ranges_dev(DevCtx* c, int kind, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint32_t* crcs,
+                   hipStream_t s, double* ms)
+{
+    if (n == 0) return SNAPHASH_OK;
+    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (lens[i] > ~0ull - offs[i]) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
+        tiles += crc_tiles_of(lens[i]);
+    }
+    if (tiles >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "ranges of 256 TiB or more in one call");
+    HIP_TRY(c, c->crc.ensure(n, (size_t)tiles));
+    uint32_t t = 0;
+    for (size_t i = 0; i < n; ++i) {
+        c->crc.offs.h[i] = offs[i];
+        c->crc.lens.h[i] = lens[i];
+        c->crc.tile0.h[i] = t;
+        t += (uint32_t)crc_tiles_of(lens[i]);
+    }
+    c->crc.tile0.h[n] = t;
+    HIP_TRY(c, hipMemcpyAsync(c->crc.offs.d.data(), c->crc.offs.h.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crc.lens.d.data(), c->crc.lens.h.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crc.tile0.d.data(), c->crc.tile0.h.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+    EventPair* ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    HIP_TRY(c, hipEventRecord(ev->a, s));
+    HIP_TRY(c, launch_crc_ranges(kind, d_base, c->crc.offs.d.data(), c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, t,
+                                 c->crc.d_partial.data(), s));
+    HIP_TRY(c, launch_crc_fold(kind, c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, c->crc.d_partial.data(), c->crc.crcs.d.data(), s));
+    HIP_TRY(c, hipEventRecord(ev->b, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crc.crcs.h.data(), c->crc.crcs.d.data(), n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    float f = 0;
+    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
+    memcpy(crcs, c->crc.crcs.h.data(), n * 4);
+    return SNAPHASH_OK;
+}
+
 // ---- block mode (SNAPHASH_FLAG_SPLIT_BLOCKS, DESIGN.md sec. 14) ----------------------------------------------------------
 
 // A member that starts with less than this left of the stream takes the serial route.  A member's length is not known
@@ -302,10 +350,17 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
 // Decodes every gzip member of gz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
 // c->inf.d_out[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
 // member's last 32 KiB of output travel to the next as its window.
+// crc_at = CrcAt::Device (honoured with keep_dev, where the whole stream is in HBM): every member's CRC-32 is taken by the CRC
+// kernels when the last member is decoded, a range a member, instead of by crc_parallel member by member; tally (may be
+// null) counts what was taken where.
 int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
-                  snaphash_unpack_stats& st)
+                  snaphash_unpack_stats& st, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "gzip: empty stream");
+    c->fout_gen++;
+    const bool dev_crc = crc_at == CrcAt::Device && keep_dev;
+    std::vector<uint64_t> m_off, m_len; // dev_crc: the members' ranges of the decoded stream and their stored CRC-32s
+    std::vector<uint32_t> m_crc;
     x->block_scan = snaphash_block_scan_stats{};
     x->block_scan.struct_size = sizeof(snaphash_block_scan_stats);
     const bool split = (x->flags & SNAPHASH_FLAG_SPLIT_BLOCKS) != 0;
@@ -524,10 +579,31 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             c->ev_used = 0;
         }
         c->ev_used = 0;
-        const uint32_t crc = crc_parallel(out.data() + m0, out.size() - m0);
+        uint32_t crc;
+        const size_t tr = (size_t)((final_bit + 7) >> 3);
+        if (dev_crc && tr + 8 <= zn) { // the stored value now (the trailer's place and ISIZE are still checked here), the bytes' own below
+            crc = z[tr] | (uint32_t)z[tr + 1] << 8 | (uint32_t)z[tr + 2] << 16 | (uint32_t)z[tr + 3] << 24;
+            m_off.push_back(m0);
+            m_len.push_back(out.size() - m0);
+            m_crc.push_back(crc);
+        } else {
+            crc = crc_parallel(out.data() + m0, out.size() - m0);
+            if (tally) tally->host_ranges++;
+        }
         size_t next = 0;
         if (gzip_trailer(z, zn, final_bit, crc, out.size() - m0, &next)) return fail(c, SNAPHASH_EFORMAT, "gzip: CRC-32 or ISIZE mismatch");
         at += h + next;
+    }
+    if (!m_off.empty()) {
+        rc = ensure_fout(c, 1, 0); // (every member empty: nothing was written there yet, but the kernel takes a base)
+        if (rc) return rc;
+        std::vector<uint32_t> got(m_off.size());
+        double ms = 0;
+        rc = crc_ranges_dev(c, kCrcGzip, c->inf.d_out.data(), m_off.data(), m_len.data(), m_off.size(), got.data(), c->f_stream, &ms);
+        c->ev_used = 0;
+        if (rc) return rc;
+        if (tally) { tally->device_ranges += m_off.size(); tally->device_ms += ms; }
+        if (got != m_crc) return fail(c, SNAPHASH_EFORMAT, "gzip: CRC-32 or ISIZE mismatch");
     }
     st.inflate_ms += kms;
     return SNAPHASH_OK;
@@ -726,6 +802,87 @@ int unpack_members(DevCtx* c, const std::vector<TarEntry>& ents, const uint8_t* 
 // tar_read, unpack_members, the members' digests (host / GPU split) and verify_impl.
 using UnpackDecode = std::function<int(const uint8_t*, size_t, std::vector<uint8_t>&, bool, snaphash_unpack_stats&)>;
 
+// a whole file into memory, in one pass
+int read_whole(snaphash_ctx* x, const char* path, std::vector<uint8_t>& gz)
+{
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(path) + ": " + strerror(errno));
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { const int er = errno; close(fd); return fail(x, SNAPHASH_EIO, strerror(er)); }
+    gz.resize((size_t)sb.st_size);
+    size_t got = 0;
+    while (got < gz.size()) {
+        const ssize_t r = pread(fd, gz.data() + got, gz.size() - got, (off_t)got);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) { const int er = r < 0 ? errno : EIO; close(fd); return fail(x, SNAPHASH_EIO, std::string(path) + ": " + strerror(er)); }
+        got += (size_t)r;
+    }
+    close(fd);
+    return SNAPHASH_OK;
+}
+
+// The digests of the regular members reg (indices into ents, ascending) out of the decoded stream, 64 bytes each into
+// dig: long members on host threads out of tar, as the producer plans them (targz.inc), the others by the SHA-512 kernels
+// out of c->inf.d_out, which holds the same stream; SNAPHASH_FLAG_GPU_ONLY: all on the kernels.
+int hash_members(snaphash_ctx* x, DevCtx* c, const std::vector<uint8_t>& tar, const std::vector<TarEntry>& ents, const std::vector<size_t>& reg,
+                 std::vector<uint8_t>& dig)
+{
+    int rc = 0;
+    dig.assign(reg.size() * 64 + 64, 0);
+    std::vector<uint8_t> on_host(reg.size(), 0);
+    MemberHashers mh;
+    std::vector<size_t> hosted;
+    if (!x->gpu_only && !reg.empty()) {
+        const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
+        const double pass_s = std::max(0.008, (double)tar.size() / 4.5e9);
+        const uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s);
+        std::vector<uint64_t> sizes;
+        for (size_t q = 0; q < reg.size(); ++q)
+            if (long_from == 0 || ents[reg[q]].size > long_from) { on_host[q] = 1; hosted.push_back(q); sizes.push_back(ents[reg[q]].size); }
+        if (!hosted.empty()) {
+            mh.start(sizes, std::max(1u, std::min(6u, cpus / 3u)));
+            std::vector<MemberHashers::Task> ts;
+            for (size_t h = 0; h < hosted.size(); ++h) {
+                const TarEntry& e = ents[reg[hosted[h]]];
+                ts.push_back(MemberHashers::Task{(uint32_t)h, tar.data() + e.data_off, e.size, true, true, 0});
+            }
+            mh.give_all(ts);
+        }
+    }
+    std::vector<uint64_t> offs, lens;
+    std::vector<size_t> dev_q;
+    for (size_t q = 0; q < reg.size(); ++q)
+        if (!on_host[q]) { offs.push_back(ents[reg[q]].data_off); lens.push_back(ents[reg[q]].size); dev_q.push_back(q); }
+    if (!dev_q.empty()) {
+        DevBuf<uint8_t> d_dig;
+        HIP_TRY(c, d_dig.reserve(dev_q.size() * 64));
+        rc = snaphash_sha512_device(x, c->inf.d_out.data(), offs.data(), lens.data(), dev_q.size(), d_dig.data());
+        if (!rc) rc = snaphash_sync(x);
+        std::vector<uint8_t> hd(dev_q.size() * 64);
+        if (!rc && hipMemcpy(hd.data(), d_dig.data(), hd.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(x, SNAPHASH_EDEVICE, "D2H of digests failed");
+        if (rc) return rc;
+        for (size_t k = 0; k < dev_q.size(); ++k) memcpy(dig.data() + 64 * dev_q[k], hd.data() + 64 * k, 64);
+    }
+    if (!hosted.empty()) {
+        mh.wait_all();
+        mh.stop();
+        for (size_t h = 0; h < hosted.size(); ++h) memcpy(dig.data() + 64 * hosted[h], mh.digests.data() + 64 * h, 64);
+    }
+    return SNAPHASH_OK;
+}
+
+// the last member of every name that is a regular file (the content an unpack leaves on disk), ascending
+std::vector<size_t> last_regular_members(const std::vector<TarEntry>& ents)
+{
+    std::unordered_map<std::string, size_t> last;
+    for (size_t k = 0; k < ents.size(); ++k) last[ents[k].name] = k;
+    std::vector<size_t> reg;
+    for (const auto& kv : last)
+        if (ents[kv.second].type == '0') reg.push_back(kv.second);
+    std::sort(reg.begin(), reg.end());
+    return reg;
+}
+
 int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* archive, const char* target_dir, const char* yaml,
                       size_t yaml_len, snaphash_mismatch* first, uint8_t* archive_digest, const UnpackDecode& decode)
 {
@@ -733,21 +890,8 @@ int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* ar
     st.struct_size = sizeof st;
     // the archive, read once
     std::vector<uint8_t> gz; // (the compressed archive)
-    {
-        const int fd = open(archive, O_RDONLY | O_CLOEXEC);
-        if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(archive) + ": " + strerror(errno));
-        struct stat sb;
-        if (fstat(fd, &sb) != 0) { const int er = errno; close(fd); return fail(x, SNAPHASH_EIO, strerror(er)); }
-        gz.resize((size_t)sb.st_size);
-        size_t got = 0;
-        while (got < gz.size()) {
-            const ssize_t r = pread(fd, gz.data() + got, gz.size() - got, (off_t)got);
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) { const int er = r < 0 ? errno : EIO; close(fd); return fail(x, SNAPHASH_EIO, std::string(archive) + ": " + strerror(er)); }
-            got += (size_t)r;
-        }
-        close(fd);
-    }
+    int rd = read_whole(x, archive, gz);
+    if (rd) return rd;
     st.gz_bytes = gz.size();
     // the archive digest over the compressed bytes, on a host core beside the decode
     uint8_t adig[64];
@@ -781,53 +925,10 @@ int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* ar
     }
     if (want_verify) {
         // the regular members' digests out of the decoded stream: the last member of a name is what is on disk
-        std::unordered_map<std::string, size_t> last;
-        for (size_t k = 0; k < ents.size(); ++k) last[ents[k].name] = k;
-        std::vector<size_t> reg; // members hashed
-        for (const auto& kv : last)
-            if (ents[kv.second].type == '0') reg.push_back(kv.second);
-        std::sort(reg.begin(), reg.end());
-        std::vector<uint8_t> dig(reg.size() * 64 + 64);
-        std::vector<uint8_t> on_host(reg.size(), 0);
-        // long members on host threads, as the producer plans them (targz.inc); SNAPHASH_FLAG_GPU_ONLY: all on the kernels
-        MemberHashers mh;
-        std::vector<size_t> hosted;
-        if (!x->gpu_only && !reg.empty()) {
-            const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
-            const double pass_s = std::max(0.008, (double)tar.size() / 4.5e9);
-            const uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s);
-            std::vector<uint64_t> sizes;
-            for (size_t q = 0; q < reg.size(); ++q)
-                if (long_from == 0 || ents[reg[q]].size > long_from) { on_host[q] = 1; hosted.push_back(q); sizes.push_back(ents[reg[q]].size); }
-            if (!hosted.empty()) {
-                mh.start(sizes, std::max(1u, std::min(6u, cpus / 3u)));
-                std::vector<MemberHashers::Task> ts;
-                for (size_t h = 0; h < hosted.size(); ++h) {
-                    const TarEntry& e = ents[reg[hosted[h]]];
-                    ts.push_back(MemberHashers::Task{(uint32_t)h, tar.data() + e.data_off, e.size, true, true, 0});
-                }
-                mh.give_all(ts);
-            }
-        }
-        std::vector<uint64_t> offs, lens;
-        std::vector<size_t> dev_q;
-        for (size_t q = 0; q < reg.size(); ++q)
-            if (!on_host[q]) { offs.push_back(ents[reg[q]].data_off); lens.push_back(ents[reg[q]].size); dev_q.push_back(q); }
-        if (!dev_q.empty()) {
-            DevBuf<uint8_t> d_dig;
-            HIP_TRY(c, d_dig.reserve(dev_q.size() * 64));
-            rc = snaphash_sha512_device(x, c->inf.d_out.data(), offs.data(), lens.data(), dev_q.size(), d_dig.data());
-            if (!rc) rc = snaphash_sync(x);
-            std::vector<uint8_t> hd(dev_q.size() * 64);
-            if (!rc && hipMemcpy(hd.data(), d_dig.data(), hd.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(x, SNAPHASH_EDEVICE, "D2H of digests failed");
-            if (rc) return rc;
-            for (size_t k = 0; k < dev_q.size(); ++k) memcpy(dig.data() + 64 * dev_q[k], hd.data() + 64 * k, 64);
-        }
-        if (!hosted.empty()) {
-            mh.wait_all();
-            mh.stop();
-            for (size_t h = 0; h < hosted.size(); ++h) memcpy(dig.data() + 64 * hosted[h], mh.digests.data() + 64 * h, 64);
-        }
+        const std::vector<size_t> reg = last_regular_members(ents); // members hashed
+        std::vector<uint8_t> dig;
+        rc = hash_members(x, c, tar, ents, reg, dig);
+        if (rc) return rc;
         std::unordered_map<std::string, size_t> dig_of;
         for (size_t q = 0; q < reg.size(); ++q) dig_of[ents[reg[q]].name] = q;
         // Verify's own comparison on the unpacked tree (its walk is Lstat only: the modes as they are on disk); a record
