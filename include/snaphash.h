@@ -323,7 +323,10 @@ void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out
 
 typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack, or of the
                                         * bzip2 calls (snaphash_bunzip2_buffer / snaphash_tar_unpack_bz2), where the fields
-                                        * mean what the comment after each one's semicolon says */
+                                        * mean what the comment after each one's semicolon says, or of the xz calls
+                                        * (snaphash_unxz_buffer / snaphash_tar_unpack_xz: segments = Blocks, gpu_segments =
+                                        * Blocks the kernel decoded, host_bytes = output of the Blocks decoded on the
+                                        * host, inflate_ms = the decode and Check kernels) */
     uint32_t struct_size;   /* in: sizeof(snaphash_unpack_stats) */
     uint32_t reserved;
     uint64_t gz_bytes;      /* compressed input (bzip2: the same) */
@@ -404,6 +407,38 @@ int snaphash_bunzip2_buffer(snaphash_ctx *ctx, const void *bz, size_t n, void **
 int snaphash_tar_unpack_bz2(snaphash_ctx *ctx, const char *data_tar_bz2, const char *target_dir, const char *yaml,
                             size_t yaml_len, snaphash_mismatch *first, uint8_t *archive_digest);
 
+/* ---- the install side for data.tar.xz (skipToArMember's ".xz" branch, clickdeb/deb.go:408-441) ------------------- */
+
+/* Every Stream of xz[0..n) (the .xz file format: Stream Padding and concatenated Streams read as the xz tool reads them;
+ * a Stream without Blocks decodes to nothing), every header, Index and footer CRC-32 and every Block's Check verified
+ * (none, CRC-32, CRC-64, SHA-256).  *out is malloc'd (snaphash_free).  The Index gives every Block's place in the file and
+ * in the result before a byte is decoded, and a Block needs nothing from another: they are decoded side by side, each
+ * straight to its final offset -- a Block a host thread in the default configuration, a Block a workgroup of
+ * lzma2_blocks_kernel under SNAPHASH_FLAG_GPU_ONLY, with the CRC-32 and CRC-64 Checks taken in HBM.  Inside one Block LZMA
+ * is a serial chain: a file of one Block (what `xz` writes without -T or --block-size) decodes on one thread.  A Block of
+ * more than 4 MiB of output, and any Block the kernel gives up on, is decoded by a host thread in either configuration.
+ * In the unpack statistics segments = Blocks, gpu_segments = Blocks the kernel decoded, host_bytes = output of the
+ * Blocks decoded on the host, inflate_ms = the decode and Check kernels.
+ * SNAPHASH_EFORMAT: whatever liblzma refuses -- a wrong magic or CRC, an Index that disagrees with its Blocks, malformed
+ * LZMA2, a Check mismatch, bytes behind the last Stream that are neither padding nor a Stream, n == 0.
+ * SNAPHASH_EINVAL: a well-formed file this decoder does not take -- a filter chain other than one LZMA2 ("xz:
+ * unsupported filter 0xNN": the BCJ filters, delta) or a Check id other than 0, 1, 4, 10; the caller decodes it itself. */
+int snaphash_unxz_buffer(snaphash_ctx *ctx, const void *xz, size_t n, void **out, size_t *out_len);
+/* snaphash_tar_unpack for a data.tar.xz: the same UnpackTar rules, errors and in-pass Verify, from the xz-decoded
+ * stream; archive_digest (may be NULL): the 64 raw bytes of SHA-512(data_tar_xz). */
+int snaphash_tar_unpack_xz(snaphash_ctx *ctx, const char *data_tar_xz, const char *target_dir, const char *yaml,
+                           size_t yaml_len, snaphash_mismatch *first, uint8_t *archive_digest);
+/* One Block of a .xz file by lzma2_blocks_kernel alone, into the caller's HBM: Block `block` (counted over all Streams of
+ * xz[0..n), in order) decoded to d_dst[0..dst_len), where dst_len must be the Block's uncompressed size (at most 4 MiB).
+ * The container is checked as in snaphash_unxz_buffer; the Block's Check is NOT (snaphash_crc32_device /
+ * snaphash_crc64_device take it from d_dst).  No byte outside d_dst[0..dst_len) is written.  SNAPHASH_EFORMAT: the
+ * kernel refuses the Block's LZMA2 data (no host decoder stands behind this call).  Synchronous. */
+int snaphash_unxz_block_device(snaphash_ctx *ctx, const void *xz, size_t n, size_t block, void *d_dst, size_t dst_len);
+/* CRC-64/XZ (ECMA-182 reflected, the .xz Check id 4) of byte ranges resident in HBM: the twin of snaphash_crc32_device
+ * below, the same rules (a range of length 0 has CRC 0). */
+int snaphash_crc64_device(snaphash_ctx *ctx, const void *d_base, const uint64_t *offsets, const uint64_t *lens, size_t n,
+                          uint64_t *crcs);
+
 /* ---- the .snap itself: the ar container, its two tars, audit and unpack (clickdeb/deb.go:108-203, 408-441) ------------ */
 
 /* CRC-32 of byte ranges resident in HBM (the CRC kernels, crc_kernels.hip; for callers who hold decoded bytes there).
@@ -420,7 +455,8 @@ int snaphash_crc32_device(snaphash_ctx *ctx, int kind, const void *d_base, const
  * supported.  SNAPHASH_EFORMAT: a wrong magic or fmag, a size field that is not digits then spaces, a header or a member
  * the end of the file cuts off.
  * Member lookup is skipToArMember's (deb.go:408-441): the FIRST member whose name starts with "control.tar" /
- * "data.tar"; ".gz" takes the gzip engine, ".bz2" the bzip2 engine, ".xz" and anything else SNAPHASH_EINVAL with the
+ * "data.tar"; ".gz" takes the gzip engine, ".bz2" the bzip2 engine, ".xz" (which the session does not route to
+ * snaphash_tar_unpack_xz's engine yet) and anything else SNAPHASH_EINVAL with the
  * reference's text "Can not handle NAME" (as snaphash_tar_create answers a name that is not ".gz"); no such member is
  * SNAPHASH_EFORMAT with the prefix in the message.
  * open reads the file once and decodes nothing.  Each of the two tars is decoded at most once per session, by the

@@ -42,6 +42,8 @@ EXPORTS = [
     "snaphash_gunzip_buffer", "snaphash_tar_unpack", "snaphash_get_unpack_stats", "snaphash_get_block_scan_stats",
     # data.tar.bz2
     "snaphash_bunzip2_buffer", "snaphash_tar_unpack_bz2",
+    # data.tar.xz
+    "snaphash_unxz_buffer", "snaphash_tar_unpack_xz", "snaphash_unxz_block_device", "snaphash_crc64_device",
     # the .snap itself: CRCs in HBM, the ar container, audit and unpack
     "snaphash_crc32_device", "snaphash_snap_open", "snaphash_snap_close", "snaphash_snap_members", "snaphash_snap_member_info",
     "snaphash_snap_control_member", "snaphash_snap_meta_member", "snaphash_snap_unpack", "snaphash_snap_audit",
@@ -219,6 +221,10 @@ def lib():
     L.snaphash_bunzip2_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_crc32_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, sz, vp]
+    L.snaphash_unxz_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_unpack_xz.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_crc64_device.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.snaphash_unxz_block_device.argtypes = [vp, vp, sz, sz, vp, sz]
     L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.snaphash_snap_close.argtypes = [vp]
     L.snaphash_snap_close.restype = None
@@ -489,6 +495,43 @@ class Context:
         n = len(offsets)
         out = np.zeros(max(n, 1), dtype=np.uint32)
         self._check(lib().snaphash_crc32_device(self._h, kind, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
+    def unxz_buffer(self, xz):
+        """Every Stream of `xz` (.xz) decoded, Blocks side by side (host threads, or the GPU kernel with FLAG_GPU_ONLY)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        xz = bytes(xz)
+        self._check(lib().snaphash_unxz_buffer(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz),
+                                               ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def tar_unpack_xz(self, data_tar_xz, target_dir, yaml_bytes=None):
+        """tar_unpack for a data.tar.xz.  -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
+        m = Mismatch()
+        dig = ctypes.create_string_buffer(64)
+        rc = lib().snaphash_tar_unpack_xz(self._h, os.fsencode(data_tar_xz), os.fsencode(target_dir), yaml_bytes,
+                                          len(yaml_bytes) if yaml_bytes is not None else 0, ctypes.byref(m), dig)
+        if rc == EMISMATCH:
+            return (m.kind, m.name.decode(errors="replace")), dig.raw
+        self._check(rc)
+        return None, dig.raw
+
+    def unxz_block_device(self, xz, block, d_dst, dst_len):
+        """Block `block` of the .xz file `xz` decoded by the GPU kernel to the device address d_dst (int), dst_len bytes:
+        the Block's uncompressed size.  Its Check is not taken."""
+        xz = bytes(xz)
+        self._check(lib().snaphash_unxz_block_device(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz), block, d_dst, dst_len))
+
+    def crc64_device(self, d_base, offsets, lens):
+        """CRC-64/XZ of byte ranges resident in HBM.  d_base: device address (int); offsets / lens: contiguous numpy
+        uint64 arrays, any alignment.  -> numpy uint64 array."""
+        import numpy as np
+        n = len(offsets)
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(lib().snaphash_crc64_device(self._h, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
         return out[:n]
 
     def snap_open(self, snap_path):

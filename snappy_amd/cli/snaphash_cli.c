@@ -12,6 +12,8 @@
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
  *   snaphash [options] unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML]
+ *   snaphash [options] unxz IN.xz OUT            every .xz Stream decoded (Blocks side by side)
+ *   snaphash [options] unpack-xz DATA_TAR_XZ DIR [HASHES_YAML]
  *                                      ClickDeb.Unpack (clickdeb/deb.go:188-203) into DIR; with HASHES_YAML also the
  *                                      install-time Verify from the decoded bytes; exit 1 on mismatch
  *   snaphash [options] snap ls FILE.snap         the ar members of the package: size, offset, name
@@ -47,7 +49,8 @@ static int usage(void)
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
-                    "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
+                    "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
+                    "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
                     "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
@@ -208,13 +211,14 @@ int main(int argc, char **argv)
         }
         snaphash_free(z);
         free(in);
-    } else if ((!strcmp(argv[1], "gunzip") || !strcmp(argv[1], "bunzip2")) && argc == 4) {
-        const int bz = !strcmp(argv[1], "bunzip2");
+    } else if ((!strcmp(argv[1], "gunzip") || !strcmp(argv[1], "bunzip2") || !strcmp(argv[1], "unxz")) && argc == 4) {
+        const int xz = !strcmp(argv[1], "unxz");
+        const int bz = xz || !strcmp(argv[1], "bunzip2");
         size_t len = 0, ol = 0;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *o = NULL;
-        rc = bz ? snaphash_bunzip2_buffer(c, in, len, &o, &ol) : snaphash_gunzip_buffer(c, in, len, &o, &ol);
+        rc = xz ? snaphash_unxz_buffer(c, in, len, &o, &ol) : bz ? snaphash_bunzip2_buffer(c, in, len, &o, &ol) : snaphash_gunzip_buffer(c, in, len, &o, &ol);
         if (rc) ret = die(c, rc, argv[1]);
         else {
             FILE *f = fopen(argv[3], "wb");
@@ -223,14 +227,17 @@ int main(int argc, char **argv)
         if (show_stats && !bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         snaphash_free(o);
         free(in);
-    } else if ((!strcmp(argv[1], "unpack") || !strcmp(argv[1], "unpack-bz2")) && (argc == 4 || argc == 5)) {
-        const int bz = !strcmp(argv[1], "unpack-bz2");
+    } else if ((!strcmp(argv[1], "unpack") || !strcmp(argv[1], "unpack-bz2") || !strcmp(argv[1], "unpack-xz")) && (argc == 4 || argc == 5)) {
+        const int xz = !strcmp(argv[1], "unpack-xz");
+        const int bz = xz || !strcmp(argv[1], "unpack-bz2");
         size_t len = 0;
         char *y = NULL;
         if (argc == 5 && !(y = slurp(argv[4], &len))) { snaphash_destroy(c); return 2; }
         snaphash_mismatch m;
         uint8_t dig[64];
-        rc = bz ? snaphash_tar_unpack_bz2(c, argv[2], argv[3], y, len, &m, dig) : snaphash_tar_unpack(c, argv[2], argv[3], y, len, &m, dig);
+        rc = xz   ? snaphash_tar_unpack_xz(c, argv[2], argv[3], y, len, &m, dig)
+             : bz ? snaphash_tar_unpack_bz2(c, argv[2], argv[3], y, len, &m, dig)
+                  : snaphash_tar_unpack(c, argv[2], argv[3], y, len, &m, dig);
         if (rc) ret = die(c, rc, argv[1]);
         else printf("OK\n");
         if (show_stats) {
@@ -239,9 +246,9 @@ int main(int argc, char **argv)
             if (!snaphash_get_unpack_stats(c, &us))
                 fprintf(stderr, "%s: %llu %s bytes -> %llu tar bytes, %llu members, %llu %s (%llu on the GPU), %llu bytes decoded on "
                                 "the host, %s kernels %.2f ms, wall %.2f ms\n",
-                        argv[1], (unsigned long long)us.gz_bytes, bz ? "bz2" : "gz", (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
+                        argv[1], (unsigned long long)us.gz_bytes, xz ? "xz" : bz ? "bz2" : "gz", (unsigned long long)us.tar_bytes, (unsigned long long)us.members,
                         (unsigned long long)us.segments, bz ? "blocks" : "segments", (unsigned long long)us.gpu_segments,
-                        (unsigned long long)us.host_bytes, bz ? "bzip2" : "inflate", us.inflate_ms, us.wall_ms);
+                        (unsigned long long)us.host_bytes, xz ? "lzma2" : bz ? "bzip2" : "inflate", us.inflate_ms, us.wall_ms);
             if (!bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         }
         free(y);

@@ -4,7 +4,7 @@ Same name, argument meaning and error behaviour as the Go function: tarCreate(ta
 sourceDir, asks fn(path) for every regular file, symlink and directory (False leaves it out; None keeps all),
 writes members "./<relative path>" owned by root through gzip into tarname, and raises on the first error.
 tarCreate writes ".gz" only: the reference's ".xz" branch shells out to an external tool.  Unpack reads
-data.tar.gz, UnpackBz2 data.tar.bz2; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203).  Test/bench harness, like
+data.tar.gz, UnpackBz2 data.tar.bz2, UnpackXz data.tar.xz; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203).  Test/bench harness, like
 helpers.py and hashes.py: the product is the C ABI.
 """
 from .helpers import default_context
@@ -30,6 +30,15 @@ def UnpackBz2(dataTarBz2, targetDir, hashesYaml=None, ctx=None):
     408-441): the same rules, errors and Verify as Unpack, from the bzip2-decoded stream.
     -> None, or (kind, name) of the first mismatch against hashesYaml."""
     mismatch, _ = (ctx or default_context()).tar_unpack_bz2(dataTarBz2, targetDir, hashesYaml)
+    return mismatch
+
+
+def UnpackXz(dataTarXz, targetDir, hashesYaml=None, ctx=None):
+    """ClickDeb.Unpack of a package whose data member is data.tar.xz (skipToArMember's ".xz" branch, clickdeb/deb.go:
+    408-441): the same rules, errors and Verify as Unpack, from the xz-decoded stream.  A filter chain or Check the
+    decoder does not take raises SnaphashError with code EINVAL.
+    -> None, or (kind, name) of the first mismatch against hashesYaml."""
+    mismatch, _ = (ctx or default_context()).tar_unpack_xz(dataTarXz, targetDir, hashesYaml)
     return mismatch
 
 

@@ -187,4 +187,93 @@ template <int KIND> CRC_HD uint32_t crc_tile_shift(const CrcPowTable& t, uint64_
     return crc_xpow8<KIND>(t, k, kCrcTileLog);
 }
 
+// ---- CRC-64/XZ (the .xz container's Check id 4) -------------------------------------------------------------------------
+//
+// ECMA-182 reflected: polynomial 0xC96C5795D7870F42, init and final xor ~0.  The same arithmetic as kCrcGzip on 64-bit
+// remainders (bit 63 is the coefficient of x^0), the same cut of a range (crc_lane_slice, crc_tiles_of); a product is 64
+// shift-and-xor steps.
+
+constexpr uint64_t kCrc64Poly = 0xC96C5795D7870F42ull;
+constexpr uint64_t kCrc64One = 1ull << 63; // x^0
+constexpr uint64_t kCrc64X8 = 1ull << 55;  // x^8
+
+CRC_HD uint64_t crc64_mul(uint64_t a, uint64_t b)
+{
+    uint64_t p = 0;
+    for (int i = 63; i >= 0; --i) {
+        p ^= (a >> i & 1) ? b : 0;
+        b = (b >> 1) ^ ((b & 1) ? kCrc64Poly : 0);
+    }
+    return p;
+}
+struct Crc64PowTable {
+    uint64_t pw[64]; // x^(8 * 2^j) mod P
+};
+CRC_HD void crc64_pow_table(Crc64PowTable& t)
+{
+    uint64_t v = kCrc64X8;
+    for (int j = 0; j < 64; ++j) {
+        t.pw[j] = v;
+        v = crc64_mul(v, v);
+    }
+}
+// x^(8 * n * 2^shift) mod P
+CRC_HD uint64_t crc64_xpow8(const Crc64PowTable& t, uint64_t n, uint32_t shift = 0)
+{
+    uint64_t r = kCrc64One;
+    for (uint32_t j = shift; n; ++j, n >>= 1)
+        if (n & 1) r = crc64_mul(r, t.pw[j & 63]);
+    return r;
+}
+CRC_HD uint64_t crc64_combine(const Crc64PowTable& t, uint64_t crc_a, uint64_t crc_b, uint64_t len_b)
+{
+    return crc64_mul(crc_a, crc64_xpow8(t, len_b)) ^ crc_b;
+}
+CRC_HD uint64_t crc64_finish(const Crc64PowTable& t, uint64_t raw, uint64_t len)
+{
+    return raw ^ crc64_mul(~0ull, crc64_xpow8(t, len)) ^ ~0ull;
+}
+CRC_HD uint64_t crc64_table0(uint32_t b)
+{
+    uint64_t c = b;
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? kCrc64Poly : 0);
+    return c;
+}
+CRC_HD uint64_t crc64_table_next(const uint64_t* t0, uint64_t prev) { return (prev >> 8) ^ t0[prev & 0xff]; }
+CRC_HD void crc64_tables(uint64_t (*tab)[256])
+{
+    for (uint32_t b = 0; b < 256; ++b) tab[0][b] = crc64_table0(b);
+    for (int k = 1; k < 8; ++k)
+        for (uint32_t b = 0; b < 256; ++b) tab[k][b] = crc64_table_next(tab[0], tab[k - 1][b]);
+}
+CRC_HD uint64_t crc64_byte(const uint64_t (*tab)[256], uint64_t c, uint8_t b) { return (c >> 8) ^ tab[0][(c ^ b) & 0xff]; }
+// eight bytes as one little-endian word
+CRC_HD uint64_t crc64_word8(const uint64_t (*tab)[256], uint64_t c, uint64_t w)
+{
+    c ^= w;
+    return tab[7][c & 0xff] ^ tab[6][c >> 8 & 0xff] ^ tab[5][c >> 16 & 0xff] ^ tab[4][c >> 24 & 0xff] ^ tab[3][c >> 32 & 0xff] ^
+           tab[2][c >> 40 & 0xff] ^ tab[1][c >> 48 & 0xff] ^ tab[0][c >> 56];
+}
+// as crc_raw_update: nothing outside p[0..n) is read
+CRC_HD uint64_t crc64_raw_update(const uint64_t (*tab)[256], uint64_t c, const uint8_t* p, uint64_t n)
+{
+    while (n && ((uintptr_t)p & 15)) { c = crc64_byte(tab, c, *p++); --n; }
+    for (; n >= 16; p += 16, n -= 16) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 v = *(const uint4*)p;
+        const uint64_t w0 = (uint64_t)v.y << 32 | v.x, w1 = (uint64_t)v.w << 32 | v.z;
+#else
+        uint64_t w[2];
+        __builtin_memcpy(w, p, 16);
+        const uint64_t w0 = w[0], w1 = w[1];
+#endif
+        c = crc64_word8(tab, c, w0);
+        c = crc64_word8(tab, c, w1);
+    }
+    while (n) { c = crc64_byte(tab, c, *p++); --n; }
+    return c;
+}
+CRC_HD uint64_t crc64_lane_shift(const Crc64PowTable& t, uint32_t lane) { return crc64_xpow8(t, kCrcLanes - 1 - lane, kCrcSliceLog); }
+CRC_HD uint64_t crc64_tile_shift(const Crc64PowTable& t, uint64_t k) { return crc64_xpow8(t, k, kCrcTileLog); }
+
 } // namespace snaphash

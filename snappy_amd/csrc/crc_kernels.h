@@ -16,4 +16,10 @@ hipError_t launch_crc_ranges(int kind, const uint8_t* d_base, const uint64_t* d_
 hipError_t launch_crc_fold(int kind, const uint64_t* d_lens, const uint32_t* d_tile0, uint32_t n, const uint32_t* d_partial,
                            uint32_t* d_crcs, hipStream_t s);
 
+// The same for CRC-64/XZ (the .xz container's Check id 4): 64-bit remainders in d_partial and d_crcs.
+hipError_t launch_crc64_ranges(const uint8_t* d_base, const uint64_t* d_offs, const uint64_t* d_lens, const uint32_t* d_tile0, uint32_t n,
+                               uint32_t tile_total, uint64_t* d_partial, hipStream_t s);
+hipError_t launch_crc64_fold(const uint64_t* d_lens, const uint32_t* d_tile0, uint32_t n, const uint64_t* d_partial, uint64_t* d_crcs,
+                             hipStream_t s);
+
 } // namespace snaphash

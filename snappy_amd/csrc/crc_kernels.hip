@@ -1,4 +1,4 @@
-// crc_kernels.hip -- CRC-32 (gzip's and bzip2's) of byte ranges resident in HBM, for gfx950.
+// crc_kernels.hip -- CRC-32 (gzip's and bzip2's) and CRC-64/XZ of byte ranges resident in HBM, for gfx950.
 //
 // The decoded stream of a package sits in HBM (c->inf.d_out) before a single CRC of it can be compared; under
 // SNAPHASH_FLAG_GPU_ONLY these kernels take the gzip members' CRC-32s and the bzip2 blocks' CRCs there instead of on
@@ -110,6 +110,78 @@ template <int KIND> const CrcPowTable& pow_table()
     return t;
 }
 
+// ---- CRC-64/XZ: the same two kernels on 64-bit remainders (tables of 16 KiB in LDS) -------------------------------------
+
+__device__ inline uint64_t block_xor64(uint64_t v, uint32_t* red)
+{
+    const uint32_t lo = block_xor((uint32_t)v, red), hi = block_xor((uint32_t)(v >> 32), red);
+    return (uint64_t)hi << 32 | lo;
+}
+
+__global__ __launch_bounds__(kCrcLanes) void crc64_ranges_kernel(const uint8_t* base, const uint64_t* offs, const uint64_t* lens,
+                                                                const uint32_t* tile0, uint32_t n, uint32_t tile_total,
+                                                                uint64_t* partial, Crc64PowTable pw)
+{
+    __shared__ uint64_t tab[8][256];
+    __shared__ uint32_t red[4];
+    const uint32_t t = threadIdx.x;
+    tab[0][t] = crc64_table0(t);
+    __syncthreads();
+    uint64_t e = tab[0][t];
+    for (int k = 1; k < 8; ++k) {
+        e = crc64_table_next(tab[0], e);
+        tab[k][t] = e;
+    }
+    __syncthreads();
+    const uint64_t shift = crc64_lane_shift(pw, t);
+    for (uint32_t pair = blockIdx.x; pair < tile_total; pair += gridDim.x) {
+        uint32_t lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (tile0[mid] <= pair) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t r = lo;
+        const uint64_t len = lens[r];
+        const uint64_t k = (uint64_t)(tile0[r + 1] - 1 - pair); // counted from the range's end
+        uint64_t a, b;
+        crc_lane_slice(len, k, t, &a, &b);
+        uint64_t c = 0;
+        if (b > a) c = crc64_mul(crc64_raw_update(tab, 0, base + offs[r] + a, b - a), shift);
+        c = block_xor64(c, red);
+        if (t == 0) partial[pair] = c;
+    }
+}
+
+__global__ __launch_bounds__(kCrcLanes) void crc64_fold_kernel(const uint64_t* lens, const uint32_t* tile0, uint32_t n,
+                                                              const uint64_t* partial, uint64_t* crcs, Crc64PowTable pw)
+{
+    __shared__ uint32_t red[4];
+    const uint32_t t = threadIdx.x;
+    const uint64_t step = pw.pw[kCrcTileLog + 8]; // x^(8 * kCrcTile * 256): from a lane's tile to its next
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
+        const uint32_t first = tile0[r], nt = tile0[r + 1] - first;
+        uint64_t acc = 0;
+        uint64_t m = crc64_tile_shift(pw, t);
+        for (uint32_t k = t; k < nt; k += kCrcLanes) {
+            acc ^= crc64_mul(partial[first + nt - 1 - k], m);
+            m = crc64_mul(m, step);
+        }
+        acc = block_xor64(acc, red);
+        if (t == 0) crcs[r] = crc64_finish(pw, acc, lens[r]);
+    }
+}
+
+const Crc64PowTable& pow_table64()
+{
+    static const Crc64PowTable t = [] {
+        Crc64PowTable x;
+        crc64_pow_table(x);
+        return x;
+    }();
+    return t;
+}
+
 } // namespace
 
 hipError_t launch_crc_ranges(int kind, const uint8_t* d_base, const uint64_t* d_offs, const uint64_t* d_lens, const uint32_t* d_tile0,
@@ -137,6 +209,25 @@ hipError_t launch_crc_fold(int kind, const uint64_t* d_lens, const uint32_t* d_t
     else
         hipLaunchKernelGGL(crc_fold_kernel<kCrcBzip2>, dim3(grid), dim3(kCrcLanes), 0, s, d_lens, d_tile0, n, d_partial, d_crcs,
                            pow_table<kCrcBzip2>());
+    return hipGetLastError();
+}
+
+hipError_t launch_crc64_ranges(const uint8_t* d_base, const uint64_t* d_offs, const uint64_t* d_lens, const uint32_t* d_tile0, uint32_t n,
+                               uint32_t tile_total, uint64_t* d_partial, hipStream_t s)
+{
+    if (n == 0 || tile_total == 0) return hipSuccess;
+    const uint32_t grid = tile_total < 4096 ? tile_total : 4096;
+    hipLaunchKernelGGL(crc64_ranges_kernel, dim3(grid), dim3(kCrcLanes), 0, s, d_base, d_offs, d_lens, d_tile0, n, tile_total, d_partial,
+                       pow_table64());
+    return hipGetLastError();
+}
+
+hipError_t launch_crc64_fold(const uint64_t* d_lens, const uint32_t* d_tile0, uint32_t n, const uint64_t* d_partial, uint64_t* d_crcs,
+                             hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = n < 2048 ? n : 2048;
+    hipLaunchKernelGGL(crc64_fold_kernel, dim3(grid), dim3(kCrcLanes), 0, s, d_lens, d_tile0, n, d_partial, d_crcs, pow_table64());
     return hipGetLastError();
 }
 

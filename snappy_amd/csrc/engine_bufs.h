@@ -14,6 +14,8 @@
 #include "inflate_core.h"
 #include "inflate_kernels.h"
 #include "sha512_kernels.h"
+#include "xz_host.h"
+#include "xz_kernels.h"
 
 namespace snaphash {
 
@@ -215,6 +217,8 @@ struct CrcBufs {
     Twin<uint32_t> tile0; // n + 1
     DevBuf<uint32_t> d_partial;
     Twin<uint32_t> crcs;
+    DevBuf<uint64_t> d_partial64; // CRC-64/XZ: its remainders and results
+    Twin<uint64_t> crcs64;
     hipError_t ensure(size_t n, size_t tiles)
     {
         hipError_t e = offs.ensure(n);
@@ -225,7 +229,31 @@ struct CrcBufs {
         if (e) each(Release());
         return e;
     }
-    template <class F> void each(F&& f) { offs.each(f); lens.each(f); tile0.each(f); f(d_partial); crcs.each(f); }
+    hipError_t ensure64(size_t n, size_t tiles)
+    {
+        hipError_t e = offs.ensure(n);
+        if (!e) e = lens.ensure(n);
+        if (!e) e = tile0.ensure(n + 1);
+        if (!e) e = d_partial64.reserve(std::max<size_t>(tiles, 1));
+        if (!e) e = crcs64.ensure(n);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { offs.each(f); lens.each(f); tile0.each(f); f(d_partial); crcs.each(f); f(d_partial64); crcs64.each(f); }
+};
+
+// GPU LZMA2 (unxz.inc): the whole .xz file and the Blocks the kernel takes
+struct XzBufs {
+    DevBuf<uint8_t> d_in;
+    Twin<XzGpuBlock> blk;
+    hipError_t ensure(uint64_t bytes, size_t nb)
+    {
+        hipError_t e = d_in.reserve(bytes + 16);
+        if (!e) e = blk.ensure(std::max<size_t>(nb, 1));
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { f(d_in); blk.each(f); }
 };
 
 } // namespace snaphash

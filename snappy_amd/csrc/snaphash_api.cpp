@@ -96,6 +96,7 @@ struct DevCtx {
     InflateBufs inf;
     Bzip2Bufs bz;
     CrcBufs crc;
+    XzBufs xz;
     hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
     uint64_t fout_gen = 0;          // counts the decodes that wrote inf.d_out: a .snap session knows by it whether its stream is still there
 
@@ -132,6 +133,7 @@ struct DevCtx {
         inf.each(f);
         bz.each(f);
         crc.each(f);
+        xz.each(f);
     }
 };
 
@@ -2296,6 +2298,7 @@ void snaphash_batch_abort(snaphash_batch* b)
 #include "targz.inc"
 #include "unpack.inc"
 #include "unbz2.inc"
+#include "unxz.inc"
 #include "snap.inc"
 
 // ---- helpers.FilesAreEqual / DirUpdated (row f4) ----------------------------------------------
