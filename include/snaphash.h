@@ -318,6 +318,16 @@ int snaphash_tar_create_fn(snaphash_ctx *ctx, const char *tarname, const char *s
 /* The compressor alone: one gzip member (RFC 1952) of a host buffer; *gz_out is malloc'd (snaphash_free). */
 int snaphash_gzip_buffer(snaphash_ctx *ctx, const void *data, size_t n, void **gz_out, size_t *gz_len);
 void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out);
+/* The compressor's Huffman code construction alone, by the routines the chunk kernel runs (a wave per table): for callers
+ * who want to check them, as the tests do.  d_freq: n_tables tables of n_syms uint32 symbol counts each, resident in HBM.
+ * Per table, to the caller's HBM: d_lens, n_syms bytes -- the code lengths (0 for a count of 0, 1 for a lone used symbol,
+ * otherwise a complete prefix code of at most max_bits); d_codes, n_syms uint32 -- the canonical code of every symbol,
+ * bit-reversed for the LSB-first stream, << 8 | its length (0 for no code); d_rounds, one uint32 -- the trees built:
+ * 1 when the first fitted max_bits, one more for every halving of the counts (a count is never halved to 0, and counts
+ * above 65535 weigh 65535).  No byte outside the three arrays is written.  SNAPHASH_EINVAL unless 1 <= n_syms <= 320,
+ * 1 <= max_bits <= 15 and n_syms <= 2^max_bits.  Synchronous. */
+int snaphash_deflate_codes_device(snaphash_ctx *ctx, const void *d_freq, size_t n_tables, uint32_t n_syms, uint32_t max_bits,
+                                  void *d_lens, void *d_codes, void *d_rounds);
 
 /* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
 

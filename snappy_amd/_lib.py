@@ -48,6 +48,8 @@ EXPORTS = [
     "snaphash_crc32_device", "snaphash_snap_open", "snaphash_snap_close", "snaphash_snap_members", "snaphash_snap_member_info",
     "snaphash_snap_control_member", "snaphash_snap_meta_member", "snaphash_snap_unpack", "snaphash_snap_audit",
     "snaphash_snap_get_stats",
+    # the compressor's code construction alone
+    "snaphash_deflate_codes_device",
 ]
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
@@ -213,6 +215,7 @@ def lib():
                                       ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_gzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_get_targz_stats.argtypes = [vp, ctypes.POINTER(TargzStats)]
+    L.snaphash_deflate_codes_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.snaphash_get_targz_stats.restype = None
     L.snaphash_gunzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
@@ -496,6 +499,12 @@ class Context:
         out = np.zeros(max(n, 1), dtype=np.uint32)
         self._check(lib().snaphash_crc32_device(self._h, kind, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
         return out[:n]
+
+    def deflate_codes_device(self, d_freq, n_tables, n_syms, max_bits, d_lens, d_codes, d_rounds):
+        """The DEFLATE kernel's code construction alone, a wave per table.  Device addresses (int): d_freq -- n_tables x
+        n_syms uint32 counts; d_lens -- as many bytes; d_codes -- as many uint32 (code << 8 | length); d_rounds -- n_tables
+        uint32 (trees built before one fitted max_bits)."""
+        self._check(lib().snaphash_deflate_codes_device(self._h, d_freq, n_tables, n_syms, max_bits, d_lens, d_codes, d_rounds))
 
     def unxz_buffer(self, xz):
         """Every Stream of `xz` (.xz) decoded, Blocks side by side (host threads, or the GPU kernel with FLAG_GPU_ONLY)."""

@@ -22,4 +22,12 @@ hipError_t launch_deflate_chunks(const uint8_t* d_in, uint64_t n_in, uint8_t* d_
 hipError_t launch_deflate_compact(const uint8_t* d_slots, const uint32_t* d_sizes, const uint64_t* d_prefix, uint8_t* d_out,
                                   uint32_t chunk0, uint32_t count, hipStream_t s);
 
+// The kernel's code construction alone (tests): n_tables tables of n_syms counts each in d_freq -> per table the code
+// lengths (d_lens, n_syms bytes), the codes as the emission uses them (d_codes: bit-reversed code << 8 | length) and the
+// number of trees built before one fitted max_bits (d_rounds).  The caller checks kDfCodesMaxSyms and
+// n_syms <= 2^max_bits, max_bits <= kMaxBits: halving cannot flatten a tree of more leaves than that.
+constexpr uint32_t kDfCodesMaxSyms = 320; // five symbols a lane
+hipError_t launch_deflate_codes(const uint32_t* d_freq, uint32_t n_tables, uint32_t n_syms, uint32_t max_bits, uint8_t* d_lens, uint32_t* d_codes,
+                                uint32_t* d_rounds, hipStream_t s);
+
 } // namespace snaphash

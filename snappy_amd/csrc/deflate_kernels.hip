@@ -1488,6 +1488,60 @@ __global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t* __r
     for (uint32_t i = (nw << 2) + threadIdx.x; i < n; i += 256u) dst[i] = src[i];
 }
 
+// The code construction alone, for the tests: a wave (one workgroup of 64) per frequency table runs huff_lengths_wave and
+// huff_codes_wave exactly as the chunk kernel does -- out of LDS, five symbols a lane -- and writes what they leave.
+// The routine does not say how many trees it built, so the wave finds that out with the routine itself: the weights of
+// round r (the counts shifted by r, never to 0, at most 0xffff) under a limit no tree reaches give that round's
+// unlimited tree; the first round whose deepest leaf fits max_bits is the one the limited build stops at.
+struct CodesLds {
+    uint32_t freq[kDfCodesMaxSyms];
+    uint32_t halved[kDfCodesMaxSyms];
+    uint32_t w[2 * kDfCodesMaxSyms];
+    uint16_t parent[2 * kDfCodesMaxSyms];
+    uint16_t order[kDfCodesMaxSyms + 2];
+    uint32_t code[kDfCodesMaxSyms];
+    uint8_t len[kDfCodesMaxSyms];
+};
+__global__ __launch_bounds__(64) void deflate_codes_kernel(const uint32_t* __restrict__ freq, uint32_t n_tables, uint32_t n, uint32_t max_bits,
+                                                           uint8_t* __restrict__ lens, uint32_t* __restrict__ codes, uint32_t* __restrict__ rounds)
+{
+    __shared__ CodesLds T;
+    const uint32_t t = blockIdx.x, lane = threadIdx.x;
+    if (t >= n_tables || n > kDfCodesMaxSyms) return;
+    const uint64_t at = (uint64_t)t * n;
+    for (uint32_t i = lane; i < n; i += 64u) T.freq[i] = freq[at + i];
+    wave_lds_sync();
+    uint32_t built = 0;
+    for (uint32_t r = 0; r < 32u && built == 0u; ++r) { // (at r = 31 every weight is 1: ceil(log2 n) deep, which the caller's max_bits holds)
+        for (uint32_t i = lane; i < n; i += 64u) {
+            const uint32_t f = T.freq[i] >> r;
+            T.halved[i] = (f == 0u && T.freq[i] != 0u) ? 1u : (f > 0xffffu ? 0xffffu : f);
+        }
+        wave_lds_sync();
+        huff_lengths_wave(T.halved, n, 0xffffu, T.len, T.w, T.parent, T.order, lane);
+        wave_lds_sync();
+        uint32_t deepest = 0;
+        for (uint32_t i = lane; i < n; i += 64u) deepest = T.len[i] > deepest ? T.len[i] : deepest;
+        deepest = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_max_incl(deepest), 63);
+        if (deepest <= max_bits) built = r + 1u;
+        wave_lds_sync();
+    }
+    huff_lengths_wave(T.freq, n, max_bits, T.len, T.w, T.parent, T.order, lane);
+    wave_lds_sync();
+    huff_codes_wave(T.len, n, T.code, lane);
+    wave_lds_sync();
+    for (uint32_t i = lane; i < n; i += 64u) { lens[at + i] = T.len[i]; codes[at + i] = T.code[i]; }
+    if (lane == 0u) rounds[t] = built;
+}
+
+hipError_t launch_deflate_codes(const uint32_t* d_freq, uint32_t n_tables, uint32_t n_syms, uint32_t max_bits, uint8_t* d_lens, uint32_t* d_codes,
+                                uint32_t* d_rounds, hipStream_t s)
+{
+    if (n_tables == 0) return hipSuccess;
+    hipLaunchKernelGGL(deflate_codes_kernel, dim3(n_tables), dim3(64), 0, s, d_freq, n_tables, n_syms, max_bits, d_lens, d_codes, d_rounds);
+    return hipGetLastError();
+}
+
 hipError_t launch_deflate_chunks(const uint8_t* d_in, uint64_t n_in, uint8_t* d_slots, uint32_t* d_sizes, uint32_t* d_toks,
                                  uint32_t chunk0, uint32_t count, uint32_t nchunks, uint32_t n_xcd, uint32_t depth, hipStream_t s)
 {

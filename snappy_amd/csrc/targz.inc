@@ -417,6 +417,25 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+int snaphash_deflate_codes_device(snaphash_ctx* x, const void* d_freq, size_t n_tables, uint32_t n_syms, uint32_t max_bits, void* d_lens,
+                                  void* d_codes, void* d_rounds)
+try {
+    if (!x || (n_tables && (!d_freq || !d_lens || !d_codes || !d_rounds)) || n_tables > 0x7fffffffu || n_syms == 0 || n_syms > kDfCodesMaxSyms ||
+        max_bits == 0 || max_bits > (uint32_t)kMaxBits || n_syms > (1u << max_bits))
+        return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_deflate_codes((const uint32_t*)d_freq, (uint32_t)n_tables, n_syms, max_bits, (uint8_t*)d_lens, (uint32_t*)d_codes,
+                                    (uint32_t*)d_rounds, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    x->stats.launches = n_tables ? 1 : 0;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
 static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
                            snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 {

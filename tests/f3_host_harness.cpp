@@ -38,6 +38,40 @@ typedef dfmodel::Tok Tok; // len == 0: literal
 // framing below run the kernel's own routines (deflate_core.h).
 static uint32_t g_model_depth = 0; // 0 = kDfDepth; f3_model_gzip3 sets it (the product: snaphash_config.deflate_depth)
 
+// Trees huff_lengths builds for freq before one fits max_bits, found without touching it: round r's weights (the counts
+// shifted by r, never to 0, at most 0xffff) under a limit no tree reaches give that round's unlimited tree.  *first_depth:
+// the deepest leaf of round 0's.  n <= kHuffMaxSyms.
+constexpr int kHuffMaxSyms = 320;
+uint32_t huff_rounds(const uint32_t* freq, int n, uint32_t max_bits, uint32_t* first_depth)
+{
+    uint32_t g[kHuffMaxSyms], w[2 * kHuffMaxSyms], cnt[257];
+    uint16_t parent[2 * kHuffMaxSyms], order[kHuffMaxSyms];
+    uint8_t len[kHuffMaxSyms];
+    for (uint32_t r = 0; r < 32; ++r) {
+        for (int i = 0; i < n; ++i) {
+            const uint32_t f = freq[i] >> r;
+            g[i] = (f == 0 && freq[i] != 0) ? 1u : (f > 0xffffu ? 0xffffu : f);
+        }
+        huff_lengths(g, n, 0xffffu, len, w, parent, order, cnt);
+        uint32_t deepest = 0;
+        for (int i = 0; i < n; ++i) deepest = std::max<uint32_t>(deepest, len[i]);
+        if (r == 0 && first_depth) *first_depth = deepest;
+        if (deepest <= max_bits) return r + 1;
+    }
+    return 0; // n > 2^max_bits: no halving flattens it
+}
+
+// what the model's last gzip call did (f3_model_counters): test-side bookkeeping, nothing below depends on it
+struct ModelCounters {
+    uint32_t chunks, stored, fixed, dynamic;       // chunks, and how each went out
+    uint32_t matches, longest_match, farthest_dist; // over the tokens of every chunk, whatever block kind carried them
+    uint32_t window_matches;                        // matches whose source begins in front of their chunk
+    uint32_t dist0_chunks, dist1_chunks;            // chunks with no / exactly one distinct distance symbol (before the two are completed)
+    uint32_t ll_rounds, d_rounds, cl_rounds;        // most trees built for one chunk's literal/length, distance and code length code
+    uint32_t ll_depth, d_depth, cl_depth;           // deepest unlimited first tree of each
+};
+static ModelCounters g_counters;
+
 void deflate_chunk(const uint8_t* piece, size_t n_piece, size_t c0, size_t c1, std::vector<uint8_t>& out)
 {
     const uint8_t* src = piece + c0;
@@ -49,8 +83,15 @@ void deflate_chunk(const uint8_t* piece, size_t n_piece, size_t c0, size_t c1, s
     // symbol counts and the cost of both block kinds
     uint32_t llf[kNumLL] = {0}, df[kNumD] = {0};
     uint64_t extra_bits = 0, fixed_bits = 3 + 7;
+    ModelCounters& K = g_counters;
+    uint32_t at = 0; // position in the chunk
     for (const Tok& t : toks) {
-        if (t.len == 0) { llf[t.lit]++; fixed_bits += fixed_ll_bits(t.lit); continue; }
+        if (t.len == 0) { llf[t.lit]++; fixed_bits += fixed_ll_bits(t.lit); ++at; continue; }
+        K.matches++;
+        K.longest_match = std::max(K.longest_match, t.len);
+        K.farthest_dist = std::max(K.farthest_dist, t.dist);
+        K.window_matches += t.dist > at ? 1u : 0u;
+        at += t.len;
         uint32_t ls, le, lv, ds, de, dv;
         len_symbol(t.len, ls, le, lv);
         dist_symbol(t.dist, ds, de, dv);
@@ -59,6 +100,12 @@ void deflate_chunk(const uint8_t* piece, size_t n_piece, size_t c0, size_t c1, s
         fixed_bits += fixed_ll_bits(ls) + 5;
     }
     llf[256]++;
+    {
+        uint32_t used = 0;
+        for (int i = 0; i < kNumD; ++i) used += df[i] != 0;
+        K.dist0_chunks += used == 0;
+        K.dist1_chunks += used == 1;
+    }
     if (df[0] == 0) df[0] = 1; // at least two distance codes, as zlib sends (old inflaters want a complete code)
     if (df[1] == 0) df[1] = 1;
     fixed_bits += extra_bits;
@@ -71,6 +118,12 @@ void deflate_chunk(const uint8_t* piece, size_t n_piece, size_t c0, size_t c1, s
     build_dyn_header(lll, dl, rle.data(), clf.data(), cll, clc.data(), w.data(), parent.data(), order.data(), cnt.data(), hdr);
     huff_codes(lll, kNumLL, llc.data(), cnt.data());
     huff_codes(dl, kNumD, dc.data(), cnt.data());
+    {
+        uint32_t d0 = 0;
+        K.ll_rounds = std::max(K.ll_rounds, huff_rounds(llf, kNumLL, (uint32_t)kMaxBits, &d0)); K.ll_depth = std::max(K.ll_depth, d0);
+        K.d_rounds = std::max(K.d_rounds, huff_rounds(df, kNumD, (uint32_t)kMaxBits, &d0)); K.d_depth = std::max(K.d_depth, d0);
+        K.cl_rounds = std::max(K.cl_rounds, huff_rounds(clf.data(), kNumCL, (uint32_t)kMaxCLBits, &d0)); K.cl_depth = std::max(K.cl_depth, d0);
+    }
     uint64_t dyn_bits = hdr.bits + extra_bits;
     for (int i = 0; i < kNumLL; ++i) dyn_bits += (uint64_t)llf[i] * lll[i];
     for (int i = 0; i < kNumD; ++i) dyn_bits += (uint64_t)df[i] * dl[i];
@@ -100,6 +153,8 @@ void deflate_chunk(const uint8_t* piece, size_t n_piece, size_t c0, size_t c1, s
     bw.put(0, 3);  // empty stored block
     bw.align();
     z.push_back(0); z.push_back(0); z.push_back(0xff); z.push_back(0xff);
+    K.chunks++;
+    if (z.size() >= deflate_stored_size(len)) K.stored++; else if (dynamic) K.dynamic++; else K.fixed++;
     if (z.size() >= deflate_stored_size(len)) { // stored: LEN is 16 bits, a full 64 KiB chunk goes out as two blocks of 32 KiB
         const uint32_t first = len > 65535u ? 32768u : len;
         for (uint32_t at = 0, n = first; at < len || at == 0; at += n, n = len - at) {
@@ -122,6 +177,7 @@ extern "C" {
 uint8_t* f3_model_gzip2(const uint8_t* in, size_t n, size_t piece, size_t* out_len)
 {
     std::vector<uint8_t> out(kGzipHeader, kGzipHeader + 10);
+    g_counters = ModelCounters{};
     if (piece == 0) piece = n ? n : 1;
     for (size_t p0 = 0; p0 < n; p0 += piece) { // the window in front of a chunk never reaches into the previous piece
         const size_t pn = std::min(piece, n - p0);
@@ -144,6 +200,28 @@ uint8_t* f3_model_gzip3(const uint8_t* in, size_t n, size_t piece, uint32_t dept
     uint8_t* p = f3_model_gzip2(in, n, piece, out_len);
     g_model_depth = 0;
     return p;
+}
+
+// what the last f3_model_gzip* call did: sixteen uint32 in ModelCounters' order
+void f3_model_counters(uint32_t* out16) { memcpy(out16, &g_counters, sizeof g_counters); }
+static_assert(sizeof(ModelCounters) == 16 * sizeof(uint32_t), "f3_model_counters hands out sixteen words");
+
+// The serial code construction on n_tables tables of n (<= 320) counts each: huff_lengths and huff_codes of deflate_core.h
+// as the model calls them -> len (n bytes a table), codes (n words a table: bit-reversed code << 8 | length), rounds
+// (trees built before one fitted max_bits) and depth0 (deepest leaf of the first, unlimited tree), a word a table each.
+// -1: n or max_bits out of range (n <= 2^max_bits, or halving never ends).
+int f3_huff_tables(const uint32_t* freq, size_t n_tables, int n, uint32_t max_bits, uint8_t* len, uint32_t* codes, uint32_t* rounds, uint32_t* depth0)
+{
+    if (n < 1 || n > kHuffMaxSyms || max_bits < 1 || max_bits > (uint32_t)kMaxBits || (uint32_t)n > (1u << max_bits)) return -1;
+    uint32_t f[kHuffMaxSyms], w[2 * kHuffMaxSyms], cnt[257];
+    uint16_t parent[2 * kHuffMaxSyms], order[kHuffMaxSyms];
+    for (size_t t = 0; t < n_tables; ++t) {
+        memcpy(f, freq + t * (size_t)n, (size_t)n * sizeof(uint32_t));
+        huff_lengths(f, n, max_bits, len + t * (size_t)n, w, parent, order, cnt);
+        huff_codes(len + t * (size_t)n, n, codes + t * (size_t)n, cnt);
+        rounds[t] = huff_rounds(f, n, max_bits, depth0 + t);
+    }
+    return 0;
 }
 
 uint32_t f3_crc32(uint32_t crc, const uint8_t* p, size_t n) { return crc32_update(crc, p, n); }

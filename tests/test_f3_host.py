@@ -35,10 +35,17 @@ def f3(tmp_path_factory):
     L.f3_crc32_combine.restype = ctypes.c_uint32
     L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
     L.f3_free.argtypes = [ctypes.c_void_p]
+    L.f3_model_counters.argtypes = [ctypes.c_void_p]
+    L.f3_model_counters.restype = None
+    L.f3_huff_tables.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32] + [ctypes.c_void_p] * 4
     return L
 
 
 def sample_inputs():
+    """The samples of the compressor's tests.  "segment-1" / "segment+1" keep the names they were given when a pipeline
+    step took 4096 positions: 4095 and 4097 bytes are no edge of today's geometry (kDfSeg = 1920 positions, 30 tiles; a
+    window of 28800 = 15 segments) -- the sizes around THAT follow them ("1920-1" ...), and tests/deflate_edge_inputs.py
+    has the rest."""
     rng = np.random.default_rng(7)
     text = (b"The quick brown fox jumps over the lazy dog. " * 3000)
     words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 9)), dtype=np.uint8)) for _ in range(500)]
@@ -55,6 +62,10 @@ def sample_inputs():
         "segment-1": prose[:4095], "segment+1": prose[:4097], "tile+1": prose[:65], "window": (prose[:30000] + b"@" + prose[:30000] + b"#") * 3,
         "long run then noise": bytes(300) + rng.integers(0, 256, size=20000, dtype=np.uint8).tobytes() + bytes(5000),
         "high bytes": bytes(rng.integers(144, 256, size=40000, dtype=np.uint8)),
+        # today's segment (1920), its tile count's edges, the window (28800) and a chunk whose last segment is one byte / one tile
+        "1920-1": prose[:1919], "1920": prose[:1920], "1920+1": prose[:1921], "two segments+1": prose[:3841],
+        "window-1": prose[:28799], "window bytes": prose[:28800], "window+1": prose[:28801], "34 segments+1": prose[:65281],
+        "chunk+tile": prose[:65536 + 64], "chunk+segment+1": prose[:65536 + 1921],
     }
 
 
@@ -82,6 +93,44 @@ def test_model_of_the_deflate_kernel_is_valid_gzip(f3):
             assert len(gz) < len(zlib.compress(data, 6)), (name, len(gz), len(zlib.compress(data, 6)))
         if name in ("random", "random 64K", "random 200000", "high bytes"):
             assert len(gz) <= len(data) + 10 * (len(data) // 65536 + 1) + 20, (name, len(gz))
+
+
+def model_with_counters(f3, data, piece, depth=0):
+    """-> (the model's gzip member, its counters by name)."""
+    import deflate_edge_inputs as E
+    n = ctypes.c_size_t()
+    p = f3.f3_model_gzip3(data, len(data), piece, depth, ctypes.byref(n))
+    gz = ctypes.string_at(p, n.value)
+    f3.f3_free(p)
+    k = (ctypes.c_uint32 * len(E.COUNTERS))()
+    f3.f3_model_counters(k)
+    return gz, dict(zip(E.COUNTERS, list(k)))
+
+
+def test_edge_inputs_show_the_shapes_they_are_named_for(f3):
+    """tests/deflate_edge_inputs.py through the model: every input inflates to itself, and the model's counters show what the
+    input was built for -- the chunk count and block kinds of each size around the segment, the window and the chunk; the
+    planted repeat found at distance 28800 and not at 28801, inside a chunk and from the previous one, and not at all when
+    the chunk is the first of its staging piece or four links are walked (what a depth of 1 is raised to); matches of 257 and 258 bytes, 259 cut to 258; a
+    chunk with one distance symbol and one with none; and the code length code's 7-bit limiter building a second tree
+    (no input is known that takes the 15-bit limiter there: the tables of test_deflate_codes_host.py do)."""
+    import deflate_edge_inputs as E
+    fired = 0
+    for name, c in E.edge_inputs().items():
+        gz, k = model_with_counters(f3, c.data, c.piece, E.effective_depth(c.depth))
+        assert gzip.decompress(gz) == c.data, name
+        assert k["stored"] + k["fixed"] + k["dynamic"] == k["chunks"] and k["chunks"] <= 3, (name, k)
+        assert k["longest_match"] <= 258 and k["farthest_dist"] <= 28800, (name, k)
+        assert k["ll_rounds"] >= 1 and (k["ll_rounds"] > 1) == (k["ll_depth"] > 15) and (k["d_rounds"] > 1) == (k["d_depth"] > 15), (name, k)
+        assert (k["cl_rounds"] > 1) == (k["cl_depth"] > 7), (name, k)
+        E.check_shape(name, c.want, k)
+        fired += k["cl_rounds"] > 1
+    assert fired >= len(E.LIMITER_SEEDS)
+    # the counters themselves, on inputs whose shape needs no model to know
+    _, k = model_with_counters(f3, b"", 0)
+    assert k["chunks"] == 0 and k["matches"] == 0
+    _, k = model_with_counters(f3, b"abcabcabcabcabcabcabcabcabcabcabcabcabcabc", 0)
+    assert (k["chunks"], k["stored"], k["matches"], k["farthest_dist"], k["dist1_chunks"]) == (1, 0, 1, 3, 1), k
 
 
 def test_price_arithmetic_of_the_parse(f3):
@@ -266,6 +315,15 @@ int main(int argc, char** argv) {
     snaphash::host_sha512_final(hs, dig);
     for (size_t len : {size_t(0), size_t(1), size_t(16383), size_t(16384), size_t(16385), size_t(70000)}) {
         size_t m = 0; uint8_t* g2 = f3_model_gzip(out, len < n ? len : n, &m); f3_free(g2);
+    }
+    {   // the code construction alone, at its limits: ladders that are rebuilt, 320 symbols, weights beyond 16 bits
+        static uint32_t freq[3 * 320], codes[3 * 320], rounds[3], depth0[3]; static uint8_t len[3 * 320];
+        uint32_t a = 1, b = 1;
+        for (int i = 0; i < 320; ++i) { freq[i] = i < 40 ? a : 0; freq[320 + i] = 0xffffffffu - (uint32_t)i; freq[640 + i] = i == 319; const uint32_t c = a + b; a = b; b = c; }
+        if (f3_huff_tables(freq, 3, 320, 15, len, codes, rounds, depth0) != 0 || rounds[0] < 3 || rounds[1] != 1 || len[640 + 319] != 1) return 5;
+        if (f3_huff_tables(freq, 1, 19, 7, len, codes, rounds, depth0) != 0 || rounds[0] < 2 || depth0[0] != 18) return 6;
+        uint32_t k[16]; f3_model_counters(k);
+        if (k[0] == 0) return 7;
     }
     f3_free(gz); f3_free(out);
     printf("asan f3 ok %%02x\n", dig[0]);
