@@ -272,7 +272,10 @@ void snaphash_batch_abort(snaphash_batch *b);
 
 /* ---- the data.tar.gz producer (fused with the hash pass: row f2) ---- */
 
-typedef struct snaphash_targz_stats { /* of the most recent snaphash_tar_create / snaphash_gzip_buffer */
+typedef struct snaphash_targz_stats { /* of the most recent snaphash_tar_create / snaphash_gzip_buffer; after
+                                       * snaphash_tar_create_xz / snaphash_xz_buffer: gz_bytes = bytes written, chunks = LZMA2
+                                       * chunks of 65 536 bytes, stored_chunks = those written uncompressed, deflate_ms = the
+                                       * chain, chunk, concatenation and CRC-64 kernels */
     uint64_t tar_bytes;     /* uncompressed stream */
     uint64_t gz_bytes;      /* bytes written */
     uint64_t members;       /* tar members */
@@ -288,7 +291,7 @@ typedef struct snaphash_targz_stats { /* of the most recent snaphash_tar_create 
  * passes <source_dir>/DEBIAN, deb.go:361-363), names members "./<relative path>", owner root/root (ustar
  * headers; a name or link target they cannot hold travels in a PAX extended header, as archive/tar falls
  * back to; the size of a member of 8 GiB or more in the base-256 form), and writes the tar stream through a gzip member into tarname (must end in ".gz": the reference's ".xz"
- * branch is an external tool).  The DEFLATE stream is produced on the GPU, block-parallel: it is
+ * branch is snaphash_tar_create_xz below).  The DEFLATE stream is produced on the GPU, block-parallel: it is
  * format-compatible with, not byte-identical to, compress/gzip level 9 (archive-sha512 is defined over
  * whatever bytes are produced, build.go:222).
  * yaml_out != NULL fuses writeHashes into the same pass (row f2: every file is read ONCE): the SHA-512
@@ -317,6 +320,24 @@ int snaphash_tar_create_fn(snaphash_ctx *ctx, const char *tarname, const char *s
 
 /* The compressor alone: one gzip member (RFC 1952) of a host buffer; *gz_out is malloc'd (snaphash_free). */
 int snaphash_gzip_buffer(snaphash_ctx *ctx, const void *data, size_t n, void **gz_out, size_t *gz_len);
+
+/* ---- the data.tar.xz producer (tarCreate's ".xz" branch, clickdeb/deb.go:272-273) ---- */
+
+/* The .xz compressor alone, the twin of snaphash_gzip_buffer: one Stream (Check CRC-64) of a host buffer, a Block per
+ * block_size bytes -- a multiple of 64 KiB from 64 KiB to 4 MiB, 0 for the default of 1 MiB, anything else
+ * SNAPHASH_EINVAL -- each Block header stating both sizes, as `xz -T` writes them; n == 0 gives a Stream without Blocks
+ * (32 bytes).  Where the reference's `xz --compress --stdout` writes ONE Block, which any decoder reads on one thread,
+ * every Block written here is one snaphash_unxz_buffer / snaphash_tar_unpack_xz decode side by side (also under
+ * SNAPHASH_FLAG_GPU_ONLY: no Block is larger than the kernel takes).  Inside a Block the LZMA2 chunks (65 536 bytes
+ * each) reset the coder state and keep the dictionary, so the GPU codes them side by side (lc=3 lp=0 pb=2; a hash-chain
+ * match finder and a greedy parse: a little above `xz -0`'s size, well above `xz -6`'s).  The bytes are a function of
+ * (data, block_size) alone.  *xz_out is malloc'd (snaphash_free).  The engine's staging size must hold a Block. */
+int snaphash_xz_buffer(snaphash_ctx *ctx, const void *data, size_t n, uint64_t block_size, void **xz_out, size_t *xz_len);
+/* snaphash_tar_create for a data.tar.xz: the same walk, tar layout, single read, fused hashes.yaml, late truncation and
+ * unlink-on-failure; tarname must end in ".xz" (anything else: SNAPHASH_EINVAL, "unknown compression extension").
+ * Blocks of 1 MiB; a Block never spans two staging slots.  snaphash_get_targz_stats reports the pass. */
+int snaphash_tar_create_xz(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
+                           char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
 void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out);
 /* The compressor's Huffman code construction alone, by the routines the chunk kernel runs (a wave per table): for callers
  * who want to check them, as the tests do.  d_freq: n_tables tables of n_syms uint32 symbol counts each, resident in HBM.

@@ -30,6 +30,7 @@ EXPORTS = [
     "snaphash_get_stats_ex", "snaphash_get_device_stats", "snaphash_tree_ex",
     "snaphash_batch_begin", "snaphash_batch_append", "snaphash_batch_end", "snaphash_batch_finish", "snaphash_batch_abort",
     "snaphash_tar_create", "snaphash_tar_create_fn", "snaphash_gzip_buffer", "snaphash_get_targz_stats",
+    "snaphash_xz_buffer", "snaphash_tar_create_xz",
     "snaphash_get_engine_info", "snaphash_numa_probe",
     "snaphash_get_engine_cpus", "snaphash_numa_slice", "snaphash_plan_streams", "snaphash_usable_cpus", "snaphash_cgroup_cpu_quota",
     "snaphash_shard_plan", "snaphash_shard_rows", "snaphash_shard_count", "snaphash_shard_streams", "snaphash_shard_bytes",
@@ -214,6 +215,9 @@ def lib():
     L.snaphash_tar_create.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp),
                                       ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_gzip_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_xz_buffer.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_create_xz.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp),
+                                         ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_get_targz_stats.argtypes = [vp, ctypes.POINTER(TargzStats)]
     L.snaphash_deflate_codes_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.snaphash_get_targz_stats.restype = None
@@ -414,12 +418,27 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
+    def xz_buffer(self, data, block_size=0):
+        """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
+        self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
+        """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.
+        -> (yaml bytes or None, archive digest (64 bytes))."""
+        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
+
+    def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create"):
         """tarCreate (clickdeb/deb.go:261-344).  with_hashes: also hashes.yaml from the same read.
         -> (yaml bytes or None, archive digest (64 bytes))."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         dig = ctypes.create_string_buffer(64)
-        self._check(lib().snaphash_tar_create(self._h, os.fsencode(tarname), os.fsencode(source_dir),
+        self._check(getattr(lib(), _entry)(self._h, os.fsencode(tarname), os.fsencode(source_dir),
                                               os.fsencode(exclude_prefix) if exclude_prefix else None,
                                               ctypes.byref(p) if with_hashes else None, ctypes.byref(n), dig))
         try:

@@ -7,7 +7,10 @@
  *                                      Build's data step fused (clickdeb/deb.go:261-344 + snappy/build.go:517-520):
  *                                      data.tar.gz of BUILD_DIR without DEBIAN/, every file read once, then
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
+ *   snaphash [options] build-xz BUILD_DIR OUT.tar.xz
+ *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB, LZMA2 on the GPU
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
+ *   snaphash [options] xz IN OUT.xz [-B KiB]     the .xz compressor alone, a Block per KiB of input (default 1024)
  *   snaphash [options] gunzip IN.gz OUT          the inverse: every member decoded (GPU inflate)
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
@@ -47,7 +50,8 @@ static int die(snaphash_ctx *c, int rc, const char *what)
 static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
-                    "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
+                    "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | build-xz DIR OUT.tar.xz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
                     "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
@@ -175,7 +179,8 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, "verify");
         else printf("OK\n");
         free(y);
-    } else if (!strcmp(argv[1], "build") && argc == 4) {
+    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz")) && argc == 4) {
+        const int xz = !strcmp(argv[1], "build-xz");
         /* the exclude rule is writeHashes' own: every path that starts with <dir>/DEBIAN (build.go:229) */
         size_t dl = strlen(argv[2]);
         while (dl > 1 && argv[2][dl - 1] == '/') dl--;
@@ -187,8 +192,8 @@ int main(int argc, char **argv)
         char *y = NULL;
         size_t len = 0;
         uint8_t dig[64];
-        rc = snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
-        if (rc) ret = die(c, rc, "build");
+        rc = xz ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig) : snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
+        if (rc) ret = die(c, rc, argv[1]);
         else {
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
             FILE *f = fopen(ypath, "wb");
@@ -205,6 +210,20 @@ int main(int argc, char **argv)
         void *z = NULL;
         rc = snaphash_gzip_buffer(c, in, len, &z, &zl);
         if (rc) ret = die(c, rc, "gzip");
+        else {
+            FILE *f = fopen(argv[3], "wb");
+            if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[3]); ret = 2; }
+        }
+        snaphash_free(z);
+        free(in);
+    } else if (!strcmp(argv[1], "xz") && (argc == 4 || (argc == 6 && !strcmp(argv[4], "-B")))) {
+        size_t len = 0, zl = 0;
+        const uint64_t block = argc == 6 ? (uint64_t)strtoull(argv[5], NULL, 10) * 1024u : 0;
+        char *in = slurp(argv[2], &len);
+        if (!in) { snaphash_destroy(c); return 2; }
+        void *z = NULL;
+        rc = (argc == 6 && block == 0) ? SNAPHASH_EINVAL : snaphash_xz_buffer(c, in, len, block, &z, &zl);
+        if (rc) ret = die(c, rc, "xz");
         else {
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[3]); ret = 2; }
@@ -334,7 +353,7 @@ int main(int argc, char **argv)
                 (unsigned long long)st.bytes_hashed, (unsigned long long)st.streams, st.kernel_ms, st.h2d_ms,
                 (unsigned long long)ex.host_bytes);
         if (tz.tar_bytes)
-            fprintf(stderr, "snaphash: tar %llu B -> gz %llu B, %llu members, %llu chunks (%llu stored), deflate %.2f ms, wall %.1f ms\n",
+            fprintf(stderr, "snaphash: tar %llu B -> %llu B written, %llu members, %llu chunks (%llu stored), compressor kernels %.2f ms, wall %.1f ms\n",
                     (unsigned long long)tz.tar_bytes, (unsigned long long)tz.gz_bytes, (unsigned long long)tz.members,
                     (unsigned long long)tz.chunks, (unsigned long long)tz.stored_chunks, tz.deflate_ms, tz.wall_ms);
     }

@@ -3,7 +3,8 @@
 Same name, argument meaning and error behaviour as the Go function: tarCreate(tarname, sourceDir, fn) walks
 sourceDir, asks fn(path) for every regular file, symlink and directory (False leaves it out; None keeps all),
 writes members "./<relative path>" owned by root through gzip into tarname, and raises on the first error.
-tarCreate writes ".gz" only: the reference's ".xz" branch shells out to an external tool.  Unpack reads
+tarCreate dispatches on the suffix as deb.go:269-276 does: ".gz" to the gzip producer, ".xz" (which the reference pipes
+through the xz tool) to the library's own .xz producer; anything else is "unknown compression extension".  Unpack reads
 data.tar.gz, UnpackBz2 data.tar.bz2, UnpackXz data.tar.xz; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203).  Test/bench harness, like
 helpers.py and hashes.py: the product is the C ABI.
 """
@@ -12,7 +13,12 @@ from .helpers import default_context
 
 def tarCreate(tarname, sourceDir, fn=None, ctx=None):
     """-> the 64-byte SHA-512 of the archive written (the Go function returns only the error)."""
-    _, digest = (ctx or default_context()).tar_create_fn(tarname, sourceDir, fn)
+    c = ctx or default_context()
+    if str(tarname).endswith(".xz"):
+        if fn is not None:
+            raise ValueError("tarCreate: the .xz producer takes no exclude function (snaphash_tar_create_xz)")
+        return c.tar_create_xz(tarname, sourceDir)[1]
+    _, digest = c.tar_create_fn(tarname, sourceDir, fn)  # (any suffix but ".gz": SnaphashError, "unknown compression extension")
     return digest
 
 

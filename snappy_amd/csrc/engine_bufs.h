@@ -15,6 +15,7 @@
 #include "inflate_kernels.h"
 #include "sha512_kernels.h"
 #include "xz_host.h"
+#include "xz_enc_kernels.h"
 #include "xz_kernels.h"
 
 namespace snaphash {
@@ -254,6 +255,35 @@ struct XzBufs {
         return e;
     }
     template <class F> void each(F&& f) { f(d_in); blk.each(f); }
+};
+
+// GPU LZMA2 encoder (xzpack.inc), for a staging slot of slot_bytes: the chains and the candidates (a word per staged byte
+// each: 8x the slot), the chunks' coder output, their results and final offsets, the assembled piece and its way back
+struct XzEncBufs {
+    DevBuf<uint32_t> d_prev, d_cand;
+    DevBuf<uint8_t> d_slots, d_out;
+    Twin<uint32_t> res;
+    Twin<uint64_t> dst;
+    HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
+    // what a slot's output takes at most: every chunk stored (3 bytes of header), a Block a chunk (header, end byte,
+    // padding, Check)
+    static uint64_t out_cap(uint64_t slot_bytes) { return slot_bytes + ((slot_bytes + kXzEncChunk - 1) / kXzEncChunk) * 64 + 64; }
+    uint64_t cap() const { return h_out[0].size(); }
+    hipError_t ensure(uint64_t slot_bytes, int node)
+    {
+        const size_t nch = (size_t)((slot_bytes + kXzEncChunk - 1) / kXzEncChunk);
+        hipError_t e = d_prev.reserve(slot_bytes);
+        if (!e) e = d_cand.reserve(slot_bytes);
+        if (!e) e = d_slots.reserve(nch * kXzEncSlot);
+        if (!e) e = d_out.reserve(out_cap(slot_bytes));
+        if (!e) e = res.ensure(std::max<size_t>(nch, 1));
+        if (!e) e = dst.ensure(std::max<size_t>(nch, 1));
+        for (HostBuf<uint8_t>& b : h_out)
+            if (!e) e = b.reserve(out_cap(slot_bytes), node);
+        if (e) each(Release()); // (none of it is left behind)
+        return e;
+    }
+    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); }
 };
 
 } // namespace snaphash

@@ -97,6 +97,7 @@ struct DevCtx {
     Bzip2Bufs bz;
     CrcBufs crc;
     XzBufs xz;
+    XzEncBufs xe; // the .xz producer's (xzpack.inc)
     hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
     uint64_t fout_gen = 0;          // counts the decodes that wrote inf.d_out: a .snap session knows by it whether its stream is still there
 
@@ -134,6 +135,7 @@ struct DevCtx {
         bz.each(f);
         crc.each(f);
         xz.each(f);
+        xe.each(f);
     }
 };
 
@@ -2296,6 +2298,7 @@ void snaphash_batch_abort(snaphash_batch* b)
 } // extern "C"
 
 #include "targz.inc"
+#include "xzpack.inc"
 #include "unpack.inc"
 #include "unbz2.inc"
 #include "unxz.inc"

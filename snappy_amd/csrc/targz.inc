@@ -56,6 +56,9 @@ struct GzPipe {
     uint32_t z_nch = 0, z_launched = 0;
     EventPair z_evpair{};
     snaphash_targz_stats st{};
+    // the .xz producer (xzpack.inc): the Block size and the Index records of the Blocks written so far
+    uint64_t xz_block_size = kXzEncBlockDefault;
+    std::vector<XzEncRecord> xz_recs;
     // Whatever way the producer leaves (an exception on its way to the C boundary's catch included), the consumers are
     // told to finish and are joined: a joinable std::thread that is destroyed takes the process down.
     ~GzPipe()
@@ -436,13 +439,33 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
-static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
+namespace {
+
+// What tar_create_impl asks of a compressor (tarCreate's switch on the suffix, deb.go:269-276): the gzip producer below,
+// the .xz producer in xzpack.inc.  Both hand their bytes to the pass's consumers through gz_emit.
+struct TarCodec {
+    const char* suffix;
+    bool in_parts; // the pass's first slot may be compressed while it is still being filled (gz_slot_begin / _launch / _consume)
+    uint64_t (*slot_bytes)(const DevCtx* c, uint64_t job_bytes); // what the pass stages at a time (a multiple of 512)
+    int (*ensure)(DevCtx* c, uint64_t slot_bytes);
+    void (*begin)(GzPipe& g);                                    // what the file begins with
+    int (*slot)(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last);
+    int (*finish)(GzPipe& g, uint8_t archive_digest[64]);        // what it ends with; -> errno of the first failed write, or 0
+};
+
+void gz_header(GzPipe& g) { gz_emit(g, kGzipHeader, sizeof kGzipHeader, -1); }
+
+const TarCodec kGzipCodec = {".gz", true, producer_slot_bytes, ensure_deflate, gz_header, gz_process_slot, gz_finish};
+
+} // namespace
+
+static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* tarname, const char* source_dir, const char* exclude_prefix,
                            snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 {
     if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
     if (yaml_out) *yaml_out = nullptr;
     const size_t tl = strlen(tarname);
-    if (tl < 3 || strcmp(tarname + tl - 3, ".gz") != 0) // deb.go:270-276: .gz here; .xz is an external tool upstream
+    if (tl < 3 || strcmp(tarname + tl - 3, codec.suffix) != 0) // deb.go:270-276: the entry's own suffix (.xz: snaphash_tar_create_xz)
         return fail(x, SNAPHASH_EINVAL, std::string("unknown compression extension ") + tarname);
     TOP_ENTER(x);
     DevCtx* c = x->d0(); // several engines: the first one (the pass is bound by the serial archive digest, snaphash.h)
@@ -491,7 +514,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
         const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
         // what the pass takes whatever its members are: ~5 GiB/s of tree, and a floor
         const double pass_s = std::max(0.008, (double)plan.total / 4.5e9);
-        const uint64_t slot_bytes = producer_slot_bytes(c, plan.total);
+        const uint64_t slot_bytes = codec.slot_bytes(c, plan.total);
         const uint64_t nslots = std::max<uint64_t>(1, (plan.total + slot_bytes - 1) / slot_bytes);
         uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s / (double)nslots);
         if (const char* e = getenv("SNAPHASH_LONG_FROM")) long_from = strtoull(e, nullptr, 10); // lab: members longer than this on host threads
@@ -504,9 +527,10 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
         if (const char* e = getenv("SNAPHASH_MEMBER_HASHERS")) workers = (unsigned)std::min<unsigned long>(std::max<unsigned long>(strtoul(e, nullptr, 10), 1), 64); // lab
         if (!hosted_sizes.empty()) mh.start(hosted_sizes, workers);
     }
-    const uint64_t S = producer_slot_bytes(c, plan.total); // a multiple of 512 and of the deflate chunk
+    const uint64_t S = codec.slot_bytes(c, plan.total); // a multiple of 512 and of the compressor's chunk
+    if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "the engine's staging size is smaller than what the compressor takes at a time");
     rc = ensure_slots(c, 2, S);
-    if (!rc) rc = ensure_deflate(c, S);
+    if (!rc) rc = codec.ensure(c, S);
     if (rc) return lift(x, c, rc);
     if (nstreams) HIP_TRY(x, c->hash.ensure(nstreams, true));
 
@@ -529,7 +553,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
     g.fd = fd;
     g.want_sha = fused || archive_digest != nullptr;
     gz_begin(g);
-    gz_emit(g, kGzipHeader, sizeof kGzipHeader, -1);
+    codec.begin(g);
 
     // The pass, slot by slot (S bytes of the tar stream each), as a pipeline over the two staging slots:
     //   host threads   fill slot k+1 (headers, parallel pread at the tar offsets, job list)      | while
@@ -649,7 +673,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
     // they cost in hashing launches, each as long as its longest file whatever the slot holds.)
     EventPair* ev_next = (!rc && plan.total) ? next_events(c, 1) : nullptr;
     if (!rc && plan.total && !ev_next) rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const bool first_in_parts = std::min<uint64_t>(S, plan.total) > kPart;
+    const bool first_in_parts = codec.in_parts && std::min<uint64_t>(S, plan.total) > kPart;
     if (!rc && plan.total && !first_in_parts)
         next = std::async(std::launch::async, fill, std::ref(c->slot[0]), (uint64_t)0, std::min<uint64_t>(S, plan.total), *ev_next, false);
     unsigned k = 0;
@@ -679,7 +703,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
             if (!ev_next) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
             next = std::async(std::launch::async, fill, std::ref(c->slot[(k + 1) & 1u]), s0 + n, std::min<uint64_t>(S, plan.total - s0 - n), *ev_next, false);
         }
-        rc = parts ? gz_slot_consume(g, sl, n, (int)(k & 1u)) : gz_process_slot(g, sl, n, sl.copied, (int)(k & 1u), s0 == 0, s0 + n >= plan.total);
+        rc = parts ? gz_slot_consume(g, sl, n, (int)(k & 1u)) : codec.slot(g, sl, n, sl.copied, (int)(k & 1u), s0 == 0, s0 + n >= plan.total);
     }
     } catch (const std::exception& ex) {
         rc = fail(c, SNAPHASH_ENOMEM, std::string("the pipeline could not run: ") + ex.what());
@@ -696,7 +720,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
     uint8_t arch[64];
     const double t_produced = now_ms();
     if (!rc) {
-        const int werr = gz_finish(g, arch);
+        const int werr = codec.finish(g, arch);
         if (werr) rc = fail(c, SNAPHASH_EIO, std::string(tarname) + ": " + strerror(werr));
         else if (ftruncate(fd, (off_t)g.out_bytes) != 0 && errno != EINVAL) // (EINVAL: not a regular file -- a pipe, /dev/null -- nothing to cut)
             rc = fail(c, SNAPHASH_EIO, std::string(tarname) + ": " + strerror(errno));
@@ -752,7 +776,7 @@ static int tar_create_impl(snaphash_ctx* x, const char* tarname, const char* sou
 int snaphash_tar_create(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
                         char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    return tar_create_impl(x, kGzipCodec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -760,7 +784,7 @@ try {
 int snaphash_tar_create_fn(snaphash_ctx* x, const char* tarname, const char* source_dir, snaphash_keep_fn keep, void* user,
                            char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, tarname, source_dir, nullptr, keep, user, yaml_out, yaml_len, archive_digest);
+    return tar_create_impl(x, kGzipCodec, tarname, source_dir, nullptr, keep, user, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }

@@ -1,0 +1,598 @@
+// xz_enc_core.h -- the .xz writer: container assembly and the LZMA2 / LZMA encoder, shared by the GPU kernels
+// (xz_enc_kernels.hip), the library's host side (xzpack.inc) and a host model in tests/, the way xz_core.h serves the
+// decoders.  The container assembly is host-only, the encoder is host + device (XZ_HD).
+//
+// What is written: one Stream, Check CRC-64, a Block per block_size bytes of input (the last one
+// shorter), every Block header stating both sizes, one LZMA2 filter with lc=3 lp=0 pb=2 and the smallest dictionary that
+// holds a Block.  Inside a Block an LZMA2 chunk holds kXzEncChunk (65 536) uncompressed bytes, the one size at which both
+// of LZMA2's limits hold without a second split.  Every chunk resets the coder state and sends the properties again (the
+// first of a Block 0xE0 / 0x01, the later ones 0xC0 / 0x02) but keeps the dictionary: a chunk's output depends on the
+// Block's bytes in front of it and on nothing another chunk's coder did, so the chunks of a Block are coded side by side
+// and still match into each other's bytes.  A chunk is written as LZMA iff 6 + csize < 3 + usize and csize <= 65 536,
+// as an uncompressed chunk otherwise; no end marker is written; the Block ends with the 0x00 byte.
+//
+// The match rules are those the head of xz_core.h lists as settled against liblzma: lengths 2..273, no match past its
+// chunk's end, a distance at most the bytes since the Block's start, no rep or short rep before the first byte.
+//
+// The bytes are a function of (input, block_size) alone.  The three steps below are pure functions of the Block:
+//   xzenc_chains_host / lzma_chains_kernel   prev[p] = the nearest earlier position of the Block with the same 4-byte hash
+//   xzenc_find                               the best (length, distance) at p: the chain in order, kXzEncDepth links, the
+//                                            longest kept, the nearest among equals, every compare cut at the chunk's end
+//   xzenc_chunk                              the parse (greedy, one step of lazy evaluation, rep0-3 first, short reps),
+//                                            the symbol coder and the adaptive range encoder, one serial pass
+#pragma once
+#include <algorithm>
+
+#include "xz_core.h"
+
+// (inlined by force on the device: the coder's registers then never take the detour through a stack frame)
+#if defined(__HIPCC__)
+#define XZE_HD __host__ __device__ __forceinline__
+#else
+#define XZE_HD inline
+#endif
+
+namespace snaphash {
+
+constexpr uint32_t kXzEncChunk = 65536;              // uncompressed bytes of an LZMA2 chunk
+constexpr uint32_t kXzEncSlot = kXzEncChunk + 64;    // room for a chunk's coder output (what does not fit is counted, not stored)
+constexpr uint64_t kXzEncBlockDefault = 1ull << 20;
+constexpr uint64_t kXzEncBlockMax = 4ull << 20;      // what the install side's kernel takes (kXzGpuBlockMax)
+constexpr uint32_t kXzEncHashBits = 15;
+constexpr uint32_t kXzEncDepth = 8;                  // chain links examined per position
+constexpr uint32_t kXzEncNone = 0xffffffffu;         // prev[]: no earlier position
+constexpr uint32_t kXzEncStored = 0x80000000u;       // a chunk's result: written uncompressed (otherwise: its csize)
+constexpr uint32_t kXzEncProbs = kLzmaLitBase + (0x300u << 3); // lc=3 lp=0: 7 990 probabilities, 15 980 bytes
+constexpr uint32_t kXzEncProps = (2 * 5 + 0) * 9 + 3;          // pb=2 lp=0 lc=3: 0x5D
+
+// ---- the match model ----------------------------------------------------------------------------------------------------
+
+XZE_HD uint32_t xzenc_ld32(const uint8_t* p)
+{
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+XZE_HD uint32_t xzenc_hash(uint32_t four) { return (four * 2654435761u) >> (32 - kXzEncHashBits); }
+
+// the bytes a[0..) and b[0..) have in common, at most maxlen (a < b may overlap b: only bytes below b + maxlen are read)
+XZE_HD uint32_t xzenc_common(const uint8_t* a, const uint8_t* b, uint32_t maxlen)
+{
+    uint32_t l = 0;
+    while (l + 4 <= maxlen) {
+        const uint32_t x = xzenc_ld32(a + l) ^ xzenc_ld32(b + l);
+        if (x) return l + ((uint32_t)__builtin_ctz(x) >> 3);
+        l += 4;
+    }
+    while (l < maxlen && a[l] == b[l]) ++l;
+    return l;
+}
+
+// a candidate: length << 22 | distance - 1 (a Block is at most 4 MiB), 0 for none
+XZE_HD uint32_t xzenc_cand_len(uint32_t c) { return c >> 22; }
+XZE_HD uint32_t xzenc_cand_dist1(uint32_t c) { return c & 0x3fffffu; }
+
+// The best match at position p of the Block blk, p in the chunk that ends at ce.  prev: the Block's chains.
+XZE_HD uint32_t xzenc_find(const uint8_t* blk, const uint32_t* prev, uint32_t p, uint32_t ce)
+{
+    const uint32_t maxlen = ce - p < kLzmaMatchMax ? ce - p : kLzmaMatchMax;
+    if (maxlen < 2) return 0;
+    uint32_t best_len = 1, best_dist = 0;
+    uint32_t c = prev[p];
+    for (uint32_t d = 0; d < kXzEncDepth && c < p; ++d) { // (kXzEncNone fails c < p)
+        const uint32_t l = xzenc_common(blk + c, blk + p, maxlen);
+        if (l > best_len) {
+            best_len = l;
+            best_dist = p - c;
+            if (l == maxlen) break;
+        }
+        c = prev[c];
+    }
+    // a short match far away costs more than its literals
+    if (best_len < 2 || (best_len == 2 && best_dist > 128) || (best_len == 3 && best_dist > (1u << 14))) return 0;
+    return best_len << 22 | (best_dist - 1);
+}
+
+// ---- the range encoder ---------------------------------------------------------------------------------------------------
+
+// low is 64 bits wide: bit 32 is a carry into the bytes already shifted out, of which the last (cache) and a run of
+// 0xFF bytes behind it (cache_size counts both) are held back until it is known.  Bytes past cap are counted, not stored.
+struct XzRcEnc {
+    uint64_t low;
+    uint32_t range, cache_size, cache;
+    uint8_t* out;
+    uint32_t n, cap;
+};
+
+XZE_HD void xzrc_init(XzRcEnc& r, uint8_t* out, uint32_t cap)
+{
+    r.low = 0;
+    r.range = 0xffffffffu;
+    r.cache_size = 1; // the chunk's first byte: the zero the decoder asks for
+    r.cache = 0;
+    r.out = out;
+    r.n = 0;
+    r.cap = cap;
+}
+XZE_HD void xzrc_shift_low(XzRcEnc& r)
+{
+    if ((uint32_t)r.low < 0xff000000u || (r.low >> 32) != 0) {
+        const uint32_t carry = (uint32_t)(r.low >> 32);
+        do {
+            if (r.n < r.cap) r.out[r.n] = (uint8_t)(r.cache + carry);
+            ++r.n;
+            r.cache = 0xff;
+        } while (--r.cache_size);
+        r.cache = (uint32_t)(r.low >> 24) & 0xff;
+    }
+    ++r.cache_size;
+    r.low = (r.low & 0x00ffffffu) << 8;
+}
+XZE_HD void xzrc_bit(XzRcEnc& r, uint16_t* p, uint32_t bit)
+{
+    const uint32_t v = *p;
+    const uint32_t bound = (r.range >> 11) * v;
+    if (!bit) {
+        r.range = bound;
+        *p = (uint16_t)(v + ((2048 - v) >> 5));
+    } else {
+        r.low += bound;
+        r.range -= bound;
+        *p = (uint16_t)(v - (v >> 5));
+    }
+    while (r.range < (1u << 24)) {
+        r.range <<= 8;
+        xzrc_shift_low(r);
+    }
+}
+XZE_HD void xzrc_direct(XzRcEnc& r, uint32_t value, uint32_t bits)
+{
+    for (uint32_t i = bits; i-- > 0;) {
+        r.range >>= 1;
+        if ((value >> i) & 1) r.low += r.range;
+        while (r.range < (1u << 24)) {
+            r.range <<= 8;
+            xzrc_shift_low(r);
+        }
+    }
+}
+XZE_HD void xzrc_tree(XzRcEnc& r, uint16_t* p, uint32_t bits, uint32_t value)
+{
+    uint32_t m = 1;
+    for (uint32_t i = bits; i-- > 0;) {
+        const uint32_t b = (value >> i) & 1;
+        xzrc_bit(r, p + m, b);
+        m = (m << 1) | b;
+    }
+}
+XZE_HD void xzrc_tree_rev(XzRcEnc& r, uint16_t* p, uint32_t bits, uint32_t value)
+{
+    uint32_t m = 1;
+    for (uint32_t i = 0; i < bits; ++i) {
+        const uint32_t b = (value >> i) & 1;
+        xzrc_bit(r, p + m, b);
+        m = (m << 1) | b;
+    }
+}
+// the five-byte flush: the decoder's code is zero after its last normalisation; returns the bytes produced
+XZE_HD uint32_t xzrc_finish(XzRcEnc& r)
+{
+    for (int i = 0; i < 5; ++i) xzrc_shift_low(r);
+    return r.n;
+}
+
+// ---- the symbol coder ----------------------------------------------------------------------------------------------------
+
+struct LzmaEnc {
+    XzRcEnc rc;
+    uint32_t state;
+    uint32_t rep0, rep1, rep2, rep3; // distances - 1 (four names, not an array: they stay in registers on the device)
+};
+
+XZE_HD void lzmaenc_len(LzmaEnc& e, uint16_t* p, uint32_t len, uint32_t pos_state)
+{
+    const uint32_t l = len - 2;
+    if (l < 8) {
+        xzrc_bit(e.rc, p + kLenChoice, 0);
+        xzrc_tree(e.rc, p + kLenLow + (pos_state << 3), 3, l);
+    } else if (l < 16) {
+        xzrc_bit(e.rc, p + kLenChoice, 1);
+        xzrc_bit(e.rc, p + kLenChoice2, 0);
+        xzrc_tree(e.rc, p + kLenMid + (pos_state << 3), 3, l - 8);
+    } else {
+        xzrc_bit(e.rc, p + kLenChoice, 1);
+        xzrc_bit(e.rc, p + kLenChoice2, 1);
+        xzrc_tree(e.rc, p + kLenHigh, 8, l - 16);
+    }
+}
+
+// byte b at Block position pos (prev: the byte in front of it, 0 at the Block's start)
+XZE_HD void lzmaenc_literal(LzmaEnc& e, uint16_t* probs, const uint8_t* blk, uint32_t pos, uint32_t prev)
+{
+    const uint32_t b = blk[pos];
+    xzrc_bit(e.rc, probs + kPIsMatch + (e.state << 4) + (pos & 3), 0);
+    uint16_t* p = probs + kLzmaLitBase + 0x300u * (prev >> 5);
+    if (e.state < 7) {
+        xzrc_tree(e.rc, p, 8, b);
+    } else { // after a match: the byte the match would have continued with steers the tree while it agrees
+        uint32_t mb = blk[pos - e.rep0 - 1], offs = 0x100, sym = 1;
+        for (uint32_t i = 8; i-- > 0;) {
+            mb <<= 1;
+            const uint32_t mbit = mb & offs;
+            const uint32_t bit = (b >> i) & 1;
+            xzrc_bit(e.rc, p + offs + mbit + sym, bit);
+            sym = (sym << 1) | bit;
+            offs &= bit ? mbit : ~mbit;
+        }
+    }
+    e.state = e.state < 4 ? 0 : e.state < 10 ? e.state - 3 : e.state - 6;
+}
+
+XZE_HD uint32_t lzmaenc_dist_slot(uint32_t d)
+{
+    if (d < 4) return d;
+    const uint32_t nb = 31 - (uint32_t)__builtin_clz(d);
+    return 2 * nb + ((d >> (nb - 1)) & 1);
+}
+
+// a new match of distance dist1 + 1
+XZE_HD void lzmaenc_match(LzmaEnc& e, uint16_t* probs, uint32_t pos, uint32_t dist1, uint32_t len)
+{
+    const uint32_t ps = pos & 3;
+    xzrc_bit(e.rc, probs + kPIsMatch + (e.state << 4) + ps, 1);
+    xzrc_bit(e.rc, probs + kPIsRep + e.state, 0);
+    lzmaenc_len(e, probs + kPLen, len, ps);
+    e.state = e.state < 7 ? 7 : 10;
+    const uint32_t slot = lzmaenc_dist_slot(dist1);
+    xzrc_tree(e.rc, probs + kPPosSlot + ((len < 6 ? len - 2 : 3) << 6), 6, slot);
+    if (slot >= 4) {
+        const uint32_t nb = (slot >> 1) - 1;
+        const uint32_t base = (2 | (slot & 1)) << nb;
+        const uint32_t rest = dist1 - base;
+        if (slot < 14) {
+            xzrc_tree_rev(e.rc, probs + kPSpecPos + base - slot - 1, nb, rest);
+        } else {
+            xzrc_direct(e.rc, rest >> 4, nb - 4);
+            xzrc_tree_rev(e.rc, probs + kPAlign, 4, rest & 15);
+        }
+    }
+    e.rep3 = e.rep2;
+    e.rep2 = e.rep1;
+    e.rep1 = e.rep0;
+    e.rep0 = dist1;
+}
+
+// a match of rep distance k
+XZE_HD void lzmaenc_rep(LzmaEnc& e, uint16_t* probs, uint32_t pos, uint32_t k, uint32_t len)
+{
+    const uint32_t ps = pos & 3;
+    xzrc_bit(e.rc, probs + kPIsMatch + (e.state << 4) + ps, 1);
+    xzrc_bit(e.rc, probs + kPIsRep + e.state, 1);
+    if (k == 0) {
+        xzrc_bit(e.rc, probs + kPIsRepG0 + e.state, 0);
+        xzrc_bit(e.rc, probs + kPIsRep0Long + (e.state << 4) + ps, 1);
+    } else {
+        xzrc_bit(e.rc, probs + kPIsRepG0 + e.state, 1);
+        if (k == 1) { // (a branch a distance, no select among the four: they stay in registers on the device)
+            xzrc_bit(e.rc, probs + kPIsRepG1 + e.state, 0);
+            const uint32_t dist = e.rep1;
+            e.rep1 = e.rep0;
+            e.rep0 = dist;
+        } else if (k == 2) {
+            xzrc_bit(e.rc, probs + kPIsRepG1 + e.state, 1);
+            xzrc_bit(e.rc, probs + kPIsRepG2 + e.state, 0);
+            const uint32_t dist = e.rep2;
+            e.rep2 = e.rep1;
+            e.rep1 = e.rep0;
+            e.rep0 = dist;
+        } else {
+            xzrc_bit(e.rc, probs + kPIsRepG1 + e.state, 1);
+            xzrc_bit(e.rc, probs + kPIsRepG2 + e.state, 1);
+            const uint32_t dist = e.rep3;
+            e.rep3 = e.rep2;
+            e.rep2 = e.rep1;
+            e.rep1 = e.rep0;
+            e.rep0 = dist;
+        }
+    }
+    lzmaenc_len(e, probs + kPRepLen, len, ps);
+    e.state = e.state < 7 ? 8 : 11;
+}
+
+XZE_HD void lzmaenc_short_rep(LzmaEnc& e, uint16_t* probs, uint32_t pos)
+{
+    const uint32_t ps = pos & 3;
+    xzrc_bit(e.rc, probs + kPIsMatch + (e.state << 4) + ps, 1);
+    xzrc_bit(e.rc, probs + kPIsRep + e.state, 1);
+    xzrc_bit(e.rc, probs + kPIsRepG0 + e.state, 0);
+    xzrc_bit(e.rc, probs + kPIsRep0Long + (e.state << 4) + ps, 0);
+    e.state = e.state < 7 ? 9 : 11;
+}
+
+// ---- a chunk ---------------------------------------------------------------------------------------------------------------
+
+// What the encoder tells about the operations it chose (the host harness counts them; the kernel passes NoEncOps).
+struct NoEncOps {
+    XZE_HD void lit(uint32_t) {}
+    XZE_HD void short_rep(uint32_t) {}
+    XZE_HD void match(uint32_t, uint32_t, uint32_t) {} // position, distance, length
+    XZE_HD void rep(uint32_t, uint32_t, uint32_t) {}   // position, k, length
+};
+
+XZE_HD bool xzenc_is_lzma(uint32_t csize, uint32_t usize) { return 6 + (uint64_t)csize < 3 + (uint64_t)usize && csize <= 65536; }
+
+// Codes the chunk [cs, ce) of the Block blk into out[0 .. cap): the chunk's result, its csize or kXzEncStored.  cand: the
+// Block's candidates (xzenc_find), indexed by Block position; probs: kXzEncProbs entries, all kLzmaProbInit.  The coder
+// gives up as soon as its output can no longer be smaller than the bytes themselves.
+template <class OPS>
+XZE_HD uint32_t xzenc_chunk(const uint8_t* blk, uint32_t cs, uint32_t ce, const uint32_t* cand, uint16_t* probs, uint8_t* out, uint32_t cap,
+                           OPS& ops)
+{
+    const uint32_t usize = ce - cs;
+    LzmaEnc e;
+    xzrc_init(e.rc, out, cap);
+    e.state = 0;
+    e.rep0 = e.rep1 = e.rep2 = e.rep3 = 0;
+    uint32_t pos = cs;
+    while (pos < ce) {
+        if (e.rc.n + e.rc.cache_size >= usize) return kXzEncStored; // (the flush adds four bytes at least)
+        const uint32_t maxlen = ce - pos < kLzmaMatchMax ? ce - pos : kLzmaMatchMax;
+        // the rep distances first; none before the Block's first byte
+        uint32_t rep_len = 0, rep_k = 0;
+        bool rep0_byte = false;
+        if (pos > 0) {
+            const uint32_t d0 = e.rep0 + 1, d1 = e.rep1 + 1, d2 = e.rep2 + 1, d3 = e.rep3 + 1;
+            if (d0 <= pos) {
+                rep0_byte = blk[pos - d0] == blk[pos];
+                rep_len = xzenc_common(blk + pos - d0, blk + pos, maxlen);
+            }
+            const uint32_t l1 = d1 <= pos ? xzenc_common(blk + pos - d1, blk + pos, maxlen) : 0;
+            if (l1 > rep_len) { rep_len = l1; rep_k = 1; }
+            const uint32_t l2 = d2 <= pos ? xzenc_common(blk + pos - d2, blk + pos, maxlen) : 0;
+            if (l2 > rep_len) { rep_len = l2; rep_k = 2; }
+            const uint32_t l3 = d3 <= pos ? xzenc_common(blk + pos - d3, blk + pos, maxlen) : 0;
+            if (l3 > rep_len) { rep_len = l3; rep_k = 3; }
+        }
+        const uint32_t m = cand[pos];
+        const uint32_t mlen = xzenc_cand_len(m);
+        if (rep_len >= 2 && rep_len + 1 >= mlen) { // a rep beats a new match at most one byte longer
+            ops.rep(pos, rep_k, rep_len);
+            lzmaenc_rep(e, probs, pos, rep_k, rep_len);
+            pos += rep_len;
+            continue;
+        }
+        // one step of lazy evaluation: a longer match at the next position is worth a literal here
+        if (mlen >= 2 && !(pos + 1 < ce && xzenc_cand_len(cand[pos + 1]) > mlen)) {
+            ops.match(pos, xzenc_cand_dist1(m) + 1, mlen);
+            lzmaenc_match(e, probs, pos, xzenc_cand_dist1(m), mlen);
+            pos += mlen;
+            continue;
+        }
+        if (rep0_byte) {
+            ops.short_rep(pos);
+            lzmaenc_short_rep(e, probs, pos);
+        } else {
+            ops.lit(e.state >= 7);
+            lzmaenc_literal(e, probs, blk, pos, pos ? blk[pos - 1] : 0);
+        }
+        ++pos;
+    }
+    const uint32_t csize = xzrc_finish(e.rc);
+    return xzenc_is_lzma(csize, usize) ? csize : kXzEncStored;
+}
+
+// A chunk's header into p: 6 bytes for LZMA (res = csize), 3 for an uncompressed chunk (res = kXzEncStored).  first: the
+// Block's first chunk resets the dictionary; every chunk resets the state and sends the properties.
+XZE_HD uint32_t xzenc_chunk_header(uint8_t* p, bool first, uint32_t usize, uint32_t res)
+{
+    if (res == kXzEncStored) {
+        p[0] = first ? 0x01 : 0x02;
+        p[1] = (uint8_t)((usize - 1) >> 8);
+        p[2] = (uint8_t)(usize - 1);
+        return 3;
+    }
+    p[0] = (uint8_t)((first ? 0xE0 : 0xC0) | ((usize - 1) >> 16));
+    p[1] = (uint8_t)((usize - 1) >> 8);
+    p[2] = (uint8_t)(usize - 1);
+    p[3] = (uint8_t)((res - 1) >> 8);
+    p[4] = (uint8_t)(res - 1);
+    p[5] = (uint8_t)kXzEncProps;
+    return 6;
+}
+// what a chunk takes in its Block's data: header and body
+XZE_HD uint32_t xzenc_chunk_bytes(uint32_t usize, uint32_t res) { return res == kXzEncStored ? 3 + usize : 6 + res; }
+// a result the kernel may report for a chunk of usize bytes
+XZE_HD bool xzenc_res_valid(uint32_t usize, uint32_t res) { return res == kXzEncStored || (res >= 5 && xzenc_is_lzma(res, usize)); }
+
+// ---- the container (host only) -------------------------------------------------------------------------------------------
+
+// 0 = the default; a multiple of 64 KiB from 64 KiB to kXzEncBlockMax
+inline bool xzenc_block_size(uint64_t* block_size)
+{
+    if (*block_size == 0) *block_size = kXzEncBlockDefault;
+    return *block_size >= kXzEncChunk && *block_size <= kXzEncBlockMax && *block_size % kXzEncChunk == 0;
+}
+// the smallest encodable dictionary that holds a Block: xz_dict_size run backwards
+inline uint32_t xzenc_dict_byte(uint64_t block_size)
+{
+    uint32_t b = 0;
+    while (b < 40 && xz_dict_size(b) < block_size) ++b;
+    return b;
+}
+inline uint32_t xzenc_vli(uint8_t* p, uint64_t v)
+{
+    uint32_t n = 0;
+    while (v >= 0x80) {
+        p[n++] = (uint8_t)(v | 0x80);
+        v >>= 7;
+    }
+    p[n++] = (uint8_t)v;
+    return n;
+}
+inline void xzenc_le32(uint8_t* p, uint32_t v)
+{
+    for (int k = 0; k < 4; ++k) p[k] = (uint8_t)(v >> (8 * k));
+}
+inline void xzenc_le64(uint8_t* p, uint64_t v)
+{
+    for (int k = 0; k < 8; ++k) p[k] = (uint8_t)(v >> (8 * k));
+}
+constexpr uint32_t kXzEncStreamHeader = 12, kXzEncBlockHeaderMax = 32, kXzEncCheck = 8;
+
+inline void xzenc_stream_header(uint8_t* p)
+{
+    static const uint8_t magic[6] = {0xFD, '7', 'z', 'X', 'Z', 0};
+    memcpy(p, magic, 6);
+    p[6] = 0;
+    p[7] = (uint8_t)kXzCheckCrc64;
+    xzenc_le32(p + 8, xz_crc32(p + 6, 2));
+}
+// a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size
+inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, uint32_t dict_byte)
+{
+    uint32_t n = 2;
+    p[1] = 0xC0; // one filter; compressed and uncompressed size present
+    n += xzenc_vli(p + n, csize);
+    n += xzenc_vli(p + n, usize);
+    p[n++] = 0x21;
+    p[n++] = 0x01;
+    p[n++] = (uint8_t)dict_byte;
+    while (n & 3) p[n++] = 0;
+    p[0] = (uint8_t)((n + 4) / 4 - 1);
+    xzenc_le32(p + n, xz_crc32(p, n));
+    return n + 4;
+}
+inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize)
+{
+    uint8_t t[kXzEncBlockHeaderMax];
+    return xzenc_block_header(t, csize, usize, 0);
+}
+struct XzEncRecord { uint64_t unpadded, usize; };
+// the Index and the Stream footer behind the last Block
+inline void xzenc_index_footer(const std::vector<XzEncRecord>& recs, std::vector<uint8_t>& out)
+{
+    const size_t i0 = out.size();
+    uint8_t t[10];
+    out.push_back(0);
+    out.insert(out.end(), t, t + xzenc_vli(t, recs.size()));
+    for (const XzEncRecord& r : recs) {
+        out.insert(out.end(), t, t + xzenc_vli(t, r.unpadded));
+        out.insert(out.end(), t, t + xzenc_vli(t, r.usize));
+    }
+    while ((out.size() - i0) & 3) out.push_back(0);
+    xzenc_le32(t, xz_crc32(out.data() + i0, out.size() - i0));
+    out.insert(out.end(), t, t + 4);
+    const uint64_t isize = out.size() - i0;
+    uint8_t f[12];
+    xzenc_le32(f + 4, (uint32_t)(isize / 4 - 1));
+    f[8] = 0;
+    f[9] = (uint8_t)kXzCheckCrc64;
+    xzenc_le32(f, xz_crc32(f + 4, 6));
+    f[10] = 'Y';
+    f[11] = 'Z';
+    out.insert(out.end(), f, f + 12);
+}
+
+// Where a Block's parts lie, from its chunks' results: dst[k] = chunk k's header, relative to the Block's first byte.
+struct XzEncBlockLayout {
+    uint32_t hdr = 0;       // the Block header's size
+    uint64_t data = 0;      // the LZMA2 data with its end byte
+    uint64_t check_at = 0;  // behind the Block Padding
+    uint64_t total = 0;     // header, data, padding, Check
+    uint64_t unpadded = 0;  // the Index record's
+};
+inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst)
+{
+    XzEncBlockLayout L;
+    uint64_t data = 0;
+    for (uint32_t k = 0; k < nch; ++k) {
+        const uint32_t usize = (uint32_t)std::min<uint64_t>(kXzEncChunk, blen - (uint64_t)k * kXzEncChunk);
+        dst[k] = data;
+        data += xzenc_chunk_bytes(usize, res[k]);
+    }
+    L.data = data + 1;
+    L.hdr = xzenc_block_header_size(L.data, blen);
+    for (uint32_t k = 0; k < nch; ++k) dst[k] += L.hdr;
+    L.unpadded = L.hdr + L.data + kXzEncCheck;
+    L.check_at = (L.hdr + L.data + 3) & ~3ull;
+    L.total = L.check_at + kXzEncCheck;
+    return L;
+}
+
+// ---- the host model --------------------------------------------------------------------------------------------------------
+
+// prev[p] for every position of the Block blk[0 .. blen); head: 1 << kXzEncHashBits entries of scratch
+inline void xzenc_chains_host(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* head)
+{
+    for (uint32_t i = 0; i < (1u << kXzEncHashBits); ++i) head[i] = kXzEncNone;
+    for (uint32_t p = 0; p < blen; ++p) {
+        if (p + 4 > blen) {
+            prev[p] = kXzEncNone;
+            continue;
+        }
+        const uint32_t h = xzenc_hash(xzenc_ld32(blk + p));
+        prev[p] = head[h];
+        head[h] = p;
+    }
+}
+
+struct XzEncInfo {
+    uint64_t chunks = 0, stored = 0;
+    std::vector<uint32_t> res; // every chunk's result, in order
+};
+
+// The whole file on this thread, through the routines the kernels run.  crc64: the Check of a Block's bytes.  false: the
+// block size is not one the format decisions allow.
+template <class OPS, class CRC>
+inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std::vector<uint8_t>& out, OPS& ops, CRC crc64,
+                       XzEncInfo* info = nullptr)
+{
+    if (!xzenc_block_size(&block_size)) return false;
+    const uint32_t dict_byte = xzenc_dict_byte(block_size);
+    out.resize(kXzEncStreamHeader);
+    xzenc_stream_header(out.data());
+    std::vector<XzEncRecord> recs;
+    std::vector<uint32_t> prev, cand, head(1u << kXzEncHashBits), res;
+    std::vector<uint64_t> dst;
+    std::vector<uint16_t> probs(kXzEncProbs);
+    std::vector<std::vector<uint8_t>> body;
+    for (uint64_t b0 = 0; b0 < n; b0 += block_size) {
+        const uint8_t* blk = data + b0;
+        const uint32_t blen = (uint32_t)std::min<uint64_t>(block_size, n - b0);
+        const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
+        prev.resize(blen);
+        cand.resize(blen);
+        res.resize(nch);
+        dst.resize(nch);
+        body.resize(nch);
+        xzenc_chains_host(blk, blen, prev.data(), head.data());
+        for (uint32_t k = 0; k < nch; ++k) {
+            const uint32_t cs = k * kXzEncChunk, ce = std::min(blen, cs + kXzEncChunk);
+            for (uint32_t p = cs; p < ce; ++p) cand[p] = xzenc_find(blk, prev.data(), p, ce);
+            for (uint16_t& p : probs) p = (uint16_t)kLzmaProbInit;
+            body[k].resize(kXzEncSlot);
+            res[k] = xzenc_chunk(blk, cs, ce, cand.data(), probs.data(), body[k].data(), kXzEncSlot, ops);
+            if (info) {
+                info->chunks++;
+                info->stored += res[k] == kXzEncStored;
+                info->res.push_back(res[k]);
+            }
+        }
+        const XzEncBlockLayout L = xzenc_block_layout(res.data(), nch, blen, dst.data());
+        const size_t o = out.size();
+        out.resize(o + L.total, 0);
+        uint8_t* q = out.data() + o;
+        xzenc_block_header(q, L.data, blen, dict_byte);
+        for (uint32_t k = 0; k < nch; ++k) {
+            const uint32_t cs = k * kXzEncChunk, usize = std::min(blen, cs + kXzEncChunk) - cs;
+            const uint32_t h = xzenc_chunk_header(q + dst[k], k == 0, usize, res[k]);
+            memcpy(q + dst[k] + h, res[k] == kXzEncStored ? blk + cs : body[k].data(), res[k] == kXzEncStored ? usize : res[k]);
+        }
+        xzenc_le64(q + L.check_at, crc64(blk, (uint64_t)blen));
+        recs.push_back(XzEncRecord{L.unpadded, blen});
+    }
+    xzenc_index_footer(recs, out);
+    return true;
+}
+
+} // namespace snaphash

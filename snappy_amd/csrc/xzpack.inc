@@ -1,0 +1,224 @@
+// xzpack.inc -- the data.tar.xz producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers and
+// staging it shares: tar_create_impl takes the compressor as a parameter).
+//
+// tarCreate's ".xz" branch (reference clickdeb/deb.go:272-273) pipes the tar stream through `xz --compress --stdout`,
+// which writes ONE Block: one serial LZMA chain, for the encoder and for every decoder after it.  Here the staged tar
+// stream is cut into Blocks of block_size bytes (1 MiB unless the caller says otherwise) and every Block into LZMA2 chunks
+// of 65 536 bytes that reset the coder state but keep the Block's dictionary (xz_enc_core.h): lzma_chains_kernel links
+// every Block's hash chains, lzma2_chunks_kernel codes every chunk of the slot side by side, lzma2_concat_kernel puts
+// headers and bodies in their final places, and the Blocks' CRC-64 Checks come from the kernels the install side uses
+// (crc_kernels.hip), over the staged bytes in HBM.  The host writes what is left: Block headers, padding, Checks, the
+// Index and the footer.  A Block never spans two staging slots; a slot's last Block may be short.  The file is one the
+// library's own install side (unxz.inc) decodes a Block a thread or a Block a workgroup.
+
+namespace {
+
+int crc64_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint64_t* crcs, hipStream_t s,
+                     double* ms); // unxz.inc
+
+static_assert(kXzEncBlockMax == kXzGpuBlockMax, "every Block this side writes is one the install side's kernel takes");
+
+// the producer's slot size, cut down to whole Blocks
+uint64_t xz_slot_bytes_for(const DevCtx* c, uint64_t job_bytes, uint64_t block_size)
+{
+    const uint64_t s = producer_slot_bytes(c, job_bytes);
+    return std::max<uint64_t>(s - s % block_size, block_size);
+}
+uint64_t xz_slot_bytes(const DevCtx* c, uint64_t job_bytes) { return xz_slot_bytes_for(c, job_bytes, kXzEncBlockDefault); }
+
+int ensure_xzenc(DevCtx* c, uint64_t slot_bytes)
+{
+    if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority (ensure_deflate)
+        int least = 0, greatest = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
+    }
+    if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking));
+    HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
+    return SNAPHASH_OK;
+}
+
+void xz_header(GzPipe& g)
+{
+    uint8_t h[kXzEncStreamHeader];
+    xzenc_stream_header(h);
+    g.xz_recs.clear();
+    gz_emit(g, h, sizeof h, -1);
+}
+
+// The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream)
+// as whole Blocks into c->xe.h_out[zbuf] and on to the consumers.
+int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
+{
+    if (n == 0) return SNAPHASH_OK;
+    DevCtx* c = g.c;
+    XzEncBufs& b = c->xe;
+    hipStream_t zs = c->z_stream;
+    const uint64_t bs = g.xz_block_size;
+    const uint32_t nch = (uint32_t)((n + kXzEncChunk - 1) / kXzEncChunk), cpb = (uint32_t)(bs / kXzEncChunk);
+    const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
+    if (n > sl.cap() || b.d_prev.size() < n || b.res.size() < nch || b.cap() < XzEncBufs::out_cap(n))
+        return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
+    if (ready) HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0));
+    EventPair* evp = next_events(c, 2);
+    if (!evp) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const EventPair ev = *evp; // (by value: the pool may grow)
+    HIP_TRY(c, hipEventRecord(ev.a, zs));
+    HIP_TRY(c, launch_lzma_chains(sl.d_buf.data(), n, (uint32_t)bs, b.d_prev.data(), zs));
+    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    // a launch codes what is resident at once, no more: a longer slot goes in several launches (each with its own pair of
+    // events: the longest single launch is what DESIGN.md sec. 18 holds against sec. 17's one-second bound)
+    std::vector<EventPair> evl;
+    for (uint32_t c0 = 0; c0 < nch; c0 += kXzEncLaunchChunks) {
+        EventPair* e = next_events(c, 2);
+        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        evl.push_back(*e);
+        HIP_TRY(c, hipEventRecord(evl.back().a, zs));
+        HIP_TRY(c, launch_lzma2_chunks(sl.d_buf.data(), n, (uint32_t)bs, b.d_prev.data(), b.d_cand.data(), b.d_slots.data(), b.res.d.data(), c0,
+                                       std::min(kXzEncLaunchChunks, nch - c0), zs));
+        HIP_TRY(c, hipEventRecord(evl.back().b, zs));
+    }
+    HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nch * 4, hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    // where everything goes: a Block after the other, a chunk after the other
+    std::vector<XzEncBlockLayout> lay(nblk);
+    std::vector<uint64_t> at(nblk), offs(nblk), lens(nblk), crcs(nblk);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < nblk; ++k) {
+        const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
+        const uint32_t ch0 = k * cpb, cn = (uint32_t)((blen + kXzEncChunk - 1) / kXzEncChunk);
+        for (uint32_t i = 0; i < cn; ++i) {
+            const uint32_t usize = (uint32_t)std::min<uint64_t>(kXzEncChunk, blen - (uint64_t)i * kXzEncChunk);
+            if (!xzenc_res_valid(usize, b.res.h[ch0 + i])) return fail(c, SNAPHASH_EDEVICE, "xz: the chunk kernel reported an impossible size");
+            g.st.stored_chunks += b.res.h[ch0 + i] == kXzEncStored;
+        }
+        lay[k] = xzenc_block_layout(b.res.h.data() + ch0, cn, blen, b.dst.h.data() + ch0);
+        for (uint32_t i = 0; i < cn; ++i) b.dst.h[ch0 + i] += total;
+        at[k] = total;
+        offs[k] = b0;
+        lens[k] = blen;
+        total += lay[k].total;
+    }
+    if (total > b.cap()) return fail(c, SNAPHASH_EDEVICE, "xz: a slot's output outgrew its buffer");
+    gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
+    uint8_t* h = b.h_out[zbuf].data();
+    HIP_TRY(c, hipMemcpyAsync(b.dst.d.data(), b.dst.h.data(), (size_t)nch * 8, hipMemcpyHostToDevice, zs));
+    EventPair* evp2 = next_events(c, 2);
+    if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const EventPair ev2 = *evp2;
+    HIP_TRY(c, hipEventRecord(ev2.a, zs));
+    HIP_TRY(c, launch_lzma2_concat(sl.d_buf.data(), n, (uint32_t)bs, b.d_slots.data(), b.res.d.data(), b.dst.d.data(), b.d_out.data(), nch, zs));
+    HIP_TRY(c, hipEventRecord(ev2.b, zs));
+    HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), total, hipMemcpyDeviceToHost, zs));
+    // the Blocks' Checks, from the staged bytes in HBM (it waits for the stream: the piece is back when it returns)
+    double crc_ms = 0;
+    const int rc = crc64_ranges_dev(c, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+    if (rc) return rc;
+    if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
+        float chains = 0, concat = 0, sum = 0, longest = 0;
+        (void)hipEventElapsedTime(&chains, ev.a, ev.b);
+        (void)hipEventElapsedTime(&concat, ev2.a, ev2.b);
+        for (const EventPair& e : evl) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, e.a, e.b);
+            sum += ms;
+            longest = std::max(longest, ms);
+        }
+        fprintf(stderr, "snaphash xz: slot of %llu bytes, %u blocks, %u chunks: chains %.3f ms, chunks %.3f ms in %zu launch(es) (longest %.3f), "
+                        "concat %.3f ms, crc64 %.3f ms\n", (unsigned long long)n, nblk, nch, chains, sum, evl.size(), longest, concat, crc_ms);
+    }
+    const uint32_t dict_byte = xzenc_dict_byte(bs);
+    for (uint32_t k = 0; k < nblk; ++k) {
+        uint8_t* q = h + at[k];
+        xzenc_block_header(q, lay[k].data, lens[k], dict_byte);
+        for (uint64_t z = lay[k].hdr + lay[k].data; z < lay[k].check_at; ++z) q[z] = 0; // the Block Padding
+        xzenc_le64(q + lay[k].check_at, crcs[k]);
+        g.xz_recs.push_back(XzEncRecord{lay[k].unpadded, lens[k]});
+    }
+    gz_emit(g, h, total, zbuf);
+    g.isize += n;
+    g.st.chunks += nch;
+    return SNAPHASH_OK;
+}
+
+// the Index and the footer; -> errno of the first failed write, or 0
+int xz_finish(GzPipe& g, uint8_t archive_digest[64])
+{
+    std::vector<uint8_t> tail;
+    xzenc_index_footer(g.xz_recs, tail);
+    gz_emit(g, tail.data(), tail.size(), -1);
+    gz_join(g);
+    if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
+    return g.write_err;
+}
+
+const TarCodec kXzCodec = {".xz", false, xz_slot_bytes, ensure_xzenc, xz_header, xz_process_slot, xz_finish};
+
+} // namespace
+
+extern "C" {
+
+int snaphash_xz_buffer(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, void** xz_out, size_t* xz_len)
+try {
+    if (!x || (!data && n) || !xz_out || !xz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *xz_out = nullptr;
+    *xz_len = 0;
+    if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t S = xz_slot_bytes_for(c, n, block_size);
+    if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "xz: the block size is larger than the engine's staging size");
+    int rc = ensure_slots(c, 2, S);
+    if (!rc) rc = ensure_xzenc(c, S);
+    if (rc) return lift(x, c, rc);
+    std::string out;
+    GzPipe g;
+    g.c = c;
+    g.mem = &out;
+    gz_begin(g);
+    g.xz_block_size = block_size;
+    xz_header(g);
+    Slot& sl = c->slot[0];
+    const double t0 = now_ms();
+    for (uint64_t off = 0; off < n && !rc; off += S) {
+        const uint64_t take = std::min<uint64_t>(S, n - off);
+        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
+        EventPair* ev = next_events(c, 1);
+        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
+        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
+            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
+            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
+        rc = xz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
+    }
+    if (!rc && xz_finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
+    if (rc) gz_abort(g);
+    (void)hipStreamSynchronize(c->z_stream);
+    (void)hipStreamSynchronize(c->z2_stream);
+    collect_targz_events(c, g);
+    g.st.tar_bytes = n;
+    g.st.gz_bytes = out.size();
+    g.st.wall_ms = now_ms() - t0;
+    x->targz = g.st;
+    merge_stats(x);
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(out.size() ? out.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    memcpy(p, out.data(), out.size());
+    *xz_out = p;
+    *xz_len = out.size();
+    return SNAPHASH_OK;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_create_xz(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix, char** yaml_out,
+                           size_t* yaml_len, uint8_t* archive_digest)
+try {
+    return tar_create_impl(x, kXzCodec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+} // extern "C"
