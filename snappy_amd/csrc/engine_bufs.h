@@ -118,7 +118,7 @@ struct DeflateBufs {
 
 // GPU inflate (row f5, unpack.inc): the compressed piece (+16 bytes the bit reader may read past it) and its candidates,
 // the speculative segments' slots and results, the linked chain, the hole counters, the window in front of the piece,
-// and the decoded bytes (grown by ensure_fout; the bzip2 decode writes there too)
+// and the decoded bytes (grown by DecodedStream, unpack.inc; the bzip2 decode writes there too)
 struct InflateBufs {
     DevBuf<uint8_t> d_in;
     DevBuf<uint32_t> d_cand; // the count, the candidates, the piece start
@@ -211,7 +211,7 @@ struct Bzip2Bufs {
     }
 };
 
-// CRC-32 of ranges in HBM (crc_kernels.hip): the ranges and the prefix of their tile counts, built in pinned memory, and
+// CRC-32 and CRC-64/XZ of ranges in HBM (crc_kernels.hip): the ranges and the prefix of their tile counts, built in pinned memory, and
 // their HBM twins; a remainder per tile; the finished CRCs and their way back
 struct CrcBufs {
     Twin<uint64_t> offs, lens;
@@ -220,23 +220,23 @@ struct CrcBufs {
     Twin<uint32_t> crcs;
     DevBuf<uint64_t> d_partial64; // CRC-64/XZ: its remainders and results
     Twin<uint64_t> crcs64;
-    hipError_t ensure(size_t n, size_t tiles)
+    template <class Crc> DevBuf<Crc>& partial()
     {
-        hipError_t e = offs.ensure(n);
-        if (!e) e = lens.ensure(n);
-        if (!e) e = tile0.ensure(n + 1);
-        if (!e) e = d_partial.reserve(std::max<size_t>(tiles, 1));
-        if (!e) e = crcs.ensure(n);
-        if (e) each(Release());
-        return e;
+        if constexpr (sizeof(Crc) == 8) return d_partial64;
+        else return d_partial;
     }
-    hipError_t ensure64(size_t n, size_t tiles)
+    template <class Crc> Twin<Crc>& result()
+    {
+        if constexpr (sizeof(Crc) == 8) return crcs64;
+        else return crcs;
+    }
+    hipError_t ensure(size_t n, size_t tiles, size_t width) // width: the bytes of a CRC, 4 or 8
     {
         hipError_t e = offs.ensure(n);
         if (!e) e = lens.ensure(n);
         if (!e) e = tile0.ensure(n + 1);
-        if (!e) e = d_partial64.reserve(std::max<size_t>(tiles, 1));
-        if (!e) e = crcs64.ensure(n);
+        if (!e) e = width == 8 ? d_partial64.reserve(std::max<size_t>(tiles, 1)) : d_partial.reserve(std::max<size_t>(tiles, 1));
+        if (!e) e = width == 8 ? crcs64.ensure(n) : crcs.ensure(n);
         if (e) each(Release());
         return e;
     }

@@ -1,5 +1,5 @@
-// snap.inc -- the .snap itself, textually part of snaphash_api.cpp (after unpack.inc and unbz2.inc, whose decoders, tar
-// reader, member writer and Verify tail it drives).
+// snap.inc -- the .snap itself, textually part of snaphash_api.cpp (after unpack.inc, unbz2.inc and unxz.inc: it owns the
+// session and drives their codecs, tar reader, member writer and Verify tail; DecodedStream owns what is in c->inf.d_out).
 //
 // The reference opens a package with ClickDeb.Open (clickdeb/deb.go:108-127) and reads it through an `ar` reader:
 // ControlMember / MetaMember (deb.go:141-183) decode a whole tar to fetch one file, Unpack (deb.go:188-203) decodes
@@ -31,6 +31,9 @@ struct snaphash_snap {
 
 namespace {
 
+const UnpackCodec* const kSnapCodecs[] = {&kGunzipCodec, &kBunzip2Codec}; // by ar_pick's codec (snap_core.h)
+static_assert(kSnapGz == 0 && kSnapBz2 == 1, "kSnapCodecs is indexed by ar_pick's codec");
+
 // The tar behind `prefix`, decoded once: t.rc / t.err keep what came of it for every later call.
 int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool keep_dev)
 {
@@ -49,17 +52,10 @@ int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool k
     t.st.gz_bytes = zn;
     const double t0 = now_ms();
     {
-        std::thread dig_th([&] {
-            HostSha h;
-            host_sha512_init(h);
-            host_sha512_update(h, z, zn);
-            host_sha512_final(h, t.adig);
-        });
-        struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{dig_th};
+        DigestThread dig_th(z, zn, t.adig);
+        DecodedStream ds(c, t.tar, keep_dev);
         // under SNAPHASH_FLAG_GPU_ONLY the stream reaches HBM before host memory: the CRCs are taken there
-        const CrcAt at = x->gpu_only ? CrcAt::Device : CrcAt::Host;
-        t.rc = codec == kSnapGz ? gunzip_engine(x, c, z, zn, t.tar, keep_dev, t.st, at, &s->tally)
-                                : bunzip2_engine(x, c, z, zn, t.tar, keep_dev, t.st, at, &s->tally);
+        t.rc = kSnapCodecs[codec]->decode(x, c, z, zn, ds, t.st, x->gpu_only ? CrcAt::Device : CrcAt::Host, &s->tally);
         c->ev_used = 0;
     }
     (&t == &s->data ? s->stats.data_decodes : s->stats.control_decodes)++;
@@ -109,11 +105,8 @@ int snap_data_on_device(snaphash_snap* s)
 {
     DevCtx* c = s->x->d0();
     if (s->data.gen == c->fout_gen && c->inf.d_out.size() >= s->data.tar.size()) return 0;
-    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
-    int rc = ensure_fout(c, std::max<size_t>(s->data.tar.size(), 1), 0);
+    const int rc = DecodedStream::upload(c, s->data.tar);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->inf.d_out.data(), s->data.tar.data(), s->data.tar.size(), hipMemcpyHostToDevice, c->f_stream));
-    HIP_TRY(c, hipStreamSynchronize(c->f_stream));
     s->data.gen = ++c->fout_gen;
     return 0;
 }
@@ -128,24 +121,6 @@ int snap_data_on_device(snaphash_snap* s)
 } // namespace
 
 extern "C" {
-
-int snaphash_crc32_device(snaphash_ctx* x, int kind, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n,
-                          uint32_t* crcs)
-try {
-    if (!x || (n && (!d_base || !offsets || !lens || !crcs)) || (kind != kCrcGzip && kind != kCrcBzip2)) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
-    HIP_TRY(c, hipSetDevice(c->device));
-    double ms = 0;
-    const int rc = crc_ranges_dev(c, kind, (const uint8_t*)d_base, offsets, lens, n, crcs, c->stream, &ms);
-    c->ev_used = 0;
-    x->stats.kernel_ms = ms;
-    x->stats.launches = n ? 2 : 0;
-    end_top(x, t_top0_);
-    return lift(x, c, rc);
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
-}
 
 int snaphash_snap_open(snaphash_ctx* x, const char* snap_path, snaphash_snap** out)
 try {
@@ -221,19 +196,7 @@ try {
     if (!rc) rc = lift(x, c, unpack_members(c, s->data.ents, s->data.tar.data(), target_dir));
     if (!rc && verify) {
         rc = snap_data_on_device(s);
-        const std::vector<size_t> reg = last_regular_members(s->data.ents);
-        std::vector<uint8_t> dig;
-        if (!rc) rc = hash_members(x, c, s->data.tar, s->data.ents, reg, dig);
-        if (!rc) {
-            std::unordered_map<std::string, size_t> dig_of;
-            for (size_t q = 0; q < reg.size(); ++q) dig_of[s->data.ents[reg[q]].name] = q;
-            rc = verify_impl(x, target_dir, s->path.c_str(), s->data.adig, (const char*)yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
-                const auto it = dig_of.find(r.name);
-                if (it == dig_of.end() || (int64_t)s->data.ents[reg[it->second]].size != r.size) return false;
-                memcpy(d, dig.data() + 64 * it->second, 64);
-                return true;
-            });
-        }
+        if (!rc) rc = verify_unpacked(x, c, s->data.tar, s->data.ents, target_dir, s->path.c_str(), s->data.adig, (const char*)yaml, yaml_len, first);
     }
     st.wall_ms = now_ms() - t_top0_;
     x->unpack = st;

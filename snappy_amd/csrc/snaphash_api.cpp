@@ -198,6 +198,8 @@ int lift(snaphash_ctx* x, DevCtx* c, int rc)
     if (rc && x && c) x->last_error = c->last_error;
     return rc;
 }
+// the cores this call may plan with (snaphash_ctx::cpus_call)
+unsigned call_cpus(const snaphash_ctx* x) { return std::max(1u, x->cpus_call ? x->cpus_call : x->cpus); }
 #define HIP_TRY(c, expr)                                                                             \
     do {                                                                                             \
         hipError_t e_ = (expr);                                                                      \
@@ -779,7 +781,7 @@ PlanModel plan_model_of(const snaphash_ctx* x, bool from_files)
 {
     PlanModel m;
     m.n_devices = (unsigned)x->dev.size();
-    m.cpus = x->cpus_call ? x->cpus_call : x->cpus;
+    m.cpus = call_cpus(x);
     m.fill_threads = std::min(x->d0()->fill_cap, from_files ? 12u : 6u); // what run_reads uses per engine
     if (x->cpus_call) m.fill_threads = std::max(1u, std::min(m.fill_threads, x->cpus_call > 2u ? x->cpus_call - 1u : 1u));
     if (host_sha512_x8_available()) m.host_lane_gain = from_files ? 2.4 : 3.2; // (measured on the box per pool thread: 3.1 GB/s of files, 4.5 GB/s of memory against 1.26 / 1.4 one stream at a time)
@@ -898,7 +900,7 @@ int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests
     std::atomic<int64_t> herr_src{-1};
     unsigned nh = hidx.empty() ? 0u : std::max(1u, std::min<unsigned>(plan_threads, (unsigned)hidx.size()));
     const bool gpu_part = !gidx.empty();
-    const bool spare_cores = 2u * nh <= (x->cpus_call ? x->cpus_call : x->cpus); // a long file stream may take a reader thread beside its hasher (hostsha.h)
+    const bool spare_cores = 2u * nh <= call_cpus(x); // a long file stream may take a reader thread beside its hasher (hostsha.h)
     std::vector<double> hbusy(std::max(1u, nh), 0.0);
     std::stable_sort(hidx.begin(), hidx.end(), [&](uint32_t a, uint32_t b) { return src[a].len > src[b].len; });
     // A thread takes streams off the queue (longest first) and runs up to eight of them side by side, a stream per 64-bit
@@ -2293,6 +2295,97 @@ void snaphash_batch_abort(snaphash_batch* b)
     b->c->slot[0].busy = b->c->slot[1].busy = false;
     b->x->open_batch = nullptr;
     delete b;
+}
+
+} // extern "C"
+
+// ---- CRCs of ranges resident in HBM (crc_kernels.hip): what the install side checks and the .xz producer writes ------
+
+namespace {
+
+// The CRCs of n ranges of d_base on stream s, back on the host when the call returns.  Crc = uint32_t: CRC-32 of `kind`
+// (kCrcGzip / kCrcBzip2); Crc = uint64_t: CRC-64/XZ, kind is not read.
+template <class Crc>
+int crc_ranges_dev(DevCtx* c, int kind, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, Crc* crcs, hipStream_t s,
+                   double* ms)
+{
+    if (n == 0) return SNAPHASH_OK;
+    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (lens[i] > ~0ull - offs[i]) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
+        tiles += crc_tiles_of(lens[i]);
+    }
+    if (tiles >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "ranges of 256 TiB or more in one call");
+    HIP_TRY(c, c->crc.ensure(n, (size_t)tiles, sizeof(Crc)));
+    uint32_t t = 0;
+    for (size_t i = 0; i < n; ++i) {
+        c->crc.offs.h[i] = offs[i];
+        c->crc.lens.h[i] = lens[i];
+        c->crc.tile0.h[i] = t;
+        t += (uint32_t)crc_tiles_of(lens[i]);
+    }
+    c->crc.tile0.h[n] = t;
+    HIP_TRY(c, hipMemcpyAsync(c->crc.offs.d.data(), c->crc.offs.h.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crc.lens.d.data(), c->crc.lens.h.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crc.tile0.d.data(), c->crc.tile0.h.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+    EventPair* ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const uint64_t* d_offs = c->crc.offs.d.data();
+    const uint64_t* d_lens = c->crc.lens.d.data();
+    const uint32_t* d_tile0 = c->crc.tile0.d.data();
+    Twin<Crc>& res = c->crc.template result<Crc>();
+    Crc* d_partial = c->crc.template partial<Crc>().data();
+    HIP_TRY(c, hipEventRecord(ev->a, s));
+    if constexpr (sizeof(Crc) == 8) {
+        HIP_TRY(c, launch_crc64_ranges(d_base, d_offs, d_lens, d_tile0, (uint32_t)n, t, d_partial, s));
+        HIP_TRY(c, launch_crc64_fold(d_lens, d_tile0, (uint32_t)n, d_partial, res.d.data(), s));
+    } else {
+        HIP_TRY(c, launch_crc_ranges(kind, d_base, d_offs, d_lens, d_tile0, (uint32_t)n, t, d_partial, s));
+        HIP_TRY(c, launch_crc_fold(kind, d_lens, d_tile0, (uint32_t)n, d_partial, res.d.data(), s));
+    }
+    HIP_TRY(c, hipEventRecord(ev->b, s));
+    HIP_TRY(c, hipMemcpyAsync(res.h.data(), res.d.data(), n * sizeof(Crc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    float f = 0;
+    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
+    memcpy(crcs, res.h.data(), n * sizeof(Crc));
+    return SNAPHASH_OK;
+}
+
+// the body of snaphash_crc32_device / snaphash_crc64_device
+template <class Crc>
+int crc_device_entry(snaphash_ctx* x, int kind, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n, Crc* crcs)
+try {
+    if (!x || (n && (!d_base || !offsets || !lens || !crcs)) || (sizeof(Crc) == 4 && kind != kCrcGzip && kind != kCrcBzip2))
+        return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
+    HIP_TRY(c, hipSetDevice(c->device));
+    double ms = 0;
+    const int rc = crc_ranges_dev(c, kind, (const uint8_t*)d_base, offsets, lens, n, crcs, c->stream, &ms);
+    c->ev_used = 0;
+    x->stats.kernel_ms = ms;
+    x->stats.launches = n ? 2 : 0;
+    end_top(x, t_top0_);
+    return lift(x, c, rc);
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+} // namespace
+
+extern "C" {
+
+int snaphash_crc32_device(snaphash_ctx* x, int kind, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                          uint32_t* crcs)
+{
+    return crc_device_entry(x, kind, d_base, offsets, lens, n, crcs);
+}
+
+int snaphash_crc64_device(snaphash_ctx* x, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n, uint64_t* crcs)
+{
+    return crc_device_entry(x, 0, d_base, offsets, lens, n, crcs);
 }
 
 } // extern "C"

@@ -511,7 +511,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     std::vector<uint64_t> hosted_sizes;
     MemberHashers mh;
     if (fused && !x->gpu_only) {
-        const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
+        const unsigned cpus = call_cpus(x);
         // what the pass takes whatever its members are: ~5 GiB/s of tree, and a floor
         const double pass_s = std::max(0.008, (double)plan.total / 4.5e9);
         const uint64_t slot_bytes = codec.slot_bytes(c, plan.total);

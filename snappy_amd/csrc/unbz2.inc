@@ -1,5 +1,5 @@
-// unbz2.inc -- the data.tar.bz2 side of the install path, textually part of snaphash_api.cpp (after unpack.inc, whose
-// tar reader, member writer and Verify tail it shares).
+// unbz2.inc -- the data.tar.bz2 side of the install path, textually part of snaphash_api.cpp (after unpack.inc, which
+// owns DecodedStream and everything behind the decoder; this file owns the bzip2 decoder and its codec entry, kBunzip2Codec).
 //
 // The reference's ClickDeb.Unpack takes data.tar.{gz,bz2,xz} (clickdeb/deb.go:185); skipToArMember (deb.go:408-441)
 // reads the .bz2 member with Go's compress/bzip2, in-process on one core.  Here a bzip2 stream is decoded block by block
@@ -16,38 +16,38 @@ constexpr uint32_t kBzLaunchSlots = 256;
 // the scratch of a job, sized for it; on any allocation failure none is left behind
 int ensure_bzip2(DevCtx* c, uint64_t piece, uint32_t slots)
 {
-    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    const int rc = DecodedStream::stream(c);
+    if (rc) return rc;
     HIP_TRY(c, c->bz.ensure(piece, slots, c->numa_node));
     return SNAPHASH_OK;
 }
 
-#define BZ_TRY(expr) HIP_TRY(c, (expr))
-
 // The later stages of the nb linked blocks in c->bz.h_blk (their stored CRCs in crcs): the inverse BWT and the RLE1 count,
-// the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->inf.d_out (after the decoded
-// stream so far when keep_dev), the bytes back to out, and every block's CRC checked on host threads, one block each
+// the blocks' output offsets by a prefix sum here, the RLE1 write at those offsets in c->inf.d_out (where ds says the
+// run begins), the bytes back to ds.out, and every block's CRC checked on host threads, one block each
 // (bz_crc_block runs at about 0.4 GB/s a core: the host threads keep pace with the kernels; DESIGN.md sec. 15).
 // crc_at = CrcAt::Device: the blocks' CRCs by the CRC kernels instead, a range a block at the offsets the RLE1 stage wrote
 // them to, before the bytes travel back.
-int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uint32_t>& crcs, std::vector<uint8_t>& out, bool keep_dev,
-                  snaphash_unpack_stats& st, float& kms, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
+int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uint32_t>& crcs, DecodedStream& ds, snaphash_unpack_stats& st,
+                  float& kms, CrcAt crc_at, CrcTally* tally)
 {
+    std::vector<uint8_t>& out = ds.out;
     auto timed = [&](EventPair* ev) {
         float ms = 0;
         if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
     };
-    BZ_TRY(hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
     EventPair* ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-    BZ_TRY(launch_bz_ibwt(c->bz.d_slots.data(), c->bz.d_tt.data(), c->bz.d_blk.data(), nb, c->f_stream));
-    BZ_TRY(launch_bz_rle1_count(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->f_stream));
-    BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-    BZ_TRY(hipMemcpyAsync(c->bz.h_blk.data(), c->bz.d_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
-    BZ_TRY(hipStreamSynchronize(c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    HIP_TRY(c, launch_bz_ibwt(c->bz.d_slots.data(), c->bz.d_tt.data(), c->bz.d_blk.data(), nb, c->f_stream));
+    HIP_TRY(c, launch_bz_rle1_count(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->bz.h_blk.data(), c->bz.d_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->f_stream));
     timed(ev);
     const size_t o0 = out.size();
-    const uint64_t base = keep_dev ? o0 : 0;
+    const uint64_t base = ds.dev_base(o0);
     uint64_t total = 0;
     for (uint32_t i = 0; i < nb; ++i) {
         // (a broken inverse BWT walk; a corrupt block that walks leaves it to the block CRC, as libbz2 and Go do)
@@ -55,17 +55,18 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         c->bz.h_blk[i].out_off = base + total;
         total += c->bz.h_blk[i].out_len;
     }
-    int rc = ensure_fout(c, base + total, keep_dev ? o0 : 0);
+    int rc = ds.reserve_dev(c, base + total, base);
     if (rc) return rc;
-    BZ_TRY(hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
     ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-    BZ_TRY(launch_bz_rle1_write(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->inf.d_out.data(), c->f_stream));
-    BZ_TRY(hipEventRecord(ev->b, c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    HIP_TRY(c, launch_bz_rle1_write(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->inf.d_out.data(), c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
     out.resize(o0 + total);
-    BZ_TRY(hipMemcpyAsync(out.data() + o0, c->inf.d_out.data() + base, total, hipMemcpyDeviceToHost, c->f_stream));
-    BZ_TRY(hipStreamSynchronize(c->f_stream));
+    rc = ds.fetch(o0, o0, o0 + total);
+    if (!rc) rc = ds.sync();
+    if (rc) return rc;
     timed(ev);
     if (crc_at == CrcAt::Device) {
         std::vector<uint64_t> offs(nb), lens(nb);
@@ -92,7 +93,7 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         }
     };
     {
-        const unsigned T = (unsigned)std::min<uint64_t>(nb, std::max(1u, x->cpus_call ? x->cpus_call : x->cpus));
+        const unsigned T = (unsigned)std::min<uint64_t>(nb, call_cpus(x));
         ThreadJoiner th;
         for (unsigned k = 1; k < T; ++k) th.spawn(work);
         work();
@@ -105,37 +106,28 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
     return SNAPHASH_OK;
 }
 
-// Decodes every stream of bz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
+// Decodes every stream of bz[0..n) and appends the bytes to ds.out; keep_dev: the whole decoded stream also stays in
 // c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
-int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
-                   snaphash_unpack_stats& st, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
+int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, DecodedStream& ds, snaphash_unpack_stats& st, CrcAt crc_at,
+                   CrcTally* tally)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "bzip2: empty stream");
+    std::vector<uint8_t>& out = ds.out;
     c->fout_gen++;
-    const unsigned cpus = std::max(1u, x->cpus_call ? x->cpus_call : x->cpus);
-    const size_t o_start = out.size();
-    auto to_dev = [&](size_t from) -> int { // host-decoded bytes out[from..) into c->inf.d_out.data() at the same offset
-        if (!keep_dev || out.size() <= from) return SNAPHASH_OK;
-        if (!c->f_stream) BZ_TRY(hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
-        int e = ensure_fout(c, out.size(), from);
-        if (e) return e;
-        BZ_TRY(hipMemcpyAsync(c->inf.d_out.data() + from, out.data() + from, out.size() - from, hipMemcpyHostToDevice, c->f_stream));
-        BZ_TRY(hipStreamSynchronize(c->f_stream));
-        return SNAPHASH_OK;
-    };
+    const unsigned cpus = call_cpus(x);
     if (!x->gpu_only && cpus >= 2) {
         // the default configuration: the blocks on host threads wherever two cores are there to take them (measured
         // 7.5-11x one core of libbz2 with 16 cores, the kernels 2.6-5.7x: DESIGN.md sec. 15); on one core the kernels,
         // which beat it; SNAPHASH_FLAG_GPU_ONLY sends every linked block through the kernels
         uint64_t blocks = 0;
         if (bzip2_host_threads(bz, n, out, cpus, &blocks)) {
-            out.resize(o_start);
+            ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "bzip2: corrupt stream");
         }
         st.segments += blocks;
-        st.host_bytes += out.size() - o_start;
+        st.host_bytes += out.size() - ds.o_start;
         if (tally) tally->host_ranges += blocks;
-        return to_dev(o_start);
+        return ds.mirror(ds.o_start, out.size());
     }
     BzCursor cur;
     cur.in = bz;
@@ -159,7 +151,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
         st.segments++;
         st.host_bytes += out.size() - o0;
         if (tally) tally->host_ranges++; // (the host decoder checks its block's CRC itself)
-        return to_dev(o0);
+        return ds.mirror(o0, out.size());
     };
     bool chain_order = false; // more candidates than the cap: one block a launch, in chain order
     for (;;) {
@@ -169,23 +161,23 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
         // a piece: the compressed bytes from the byte that holds the next block's first bit
         const uint64_t pb = cur.bit >> 3;
         const uint64_t pn = std::min<uint64_t>(chain_order ? std::min<uint64_t>(P, 4u << 20) : P, n - pb);
-        BZ_TRY(hipMemcpyAsync(c->bz.d_in.data(), bz + pb, pn, hipMemcpyHostToDevice, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->bz.d_in.data(), bz + pb, pn, hipMemcpyHostToDevice, c->f_stream));
         std::vector<uint64_t> cand;
         if (!chain_order) {
-            BZ_TRY(hipMemsetAsync(c->bz.d_count.data(), 0, 4, c->f_stream));
+            HIP_TRY(c, hipMemsetAsync(c->bz.d_count.data(), 0, 4, c->f_stream));
             EventPair* ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-            BZ_TRY(launch_bz_scan(c->bz.d_in.data(), pn, c->bz.d_cand.data(), c->bz.d_count.data(), (uint32_t)c->bz.cand_cap(), c->f_stream));
-            BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-            BZ_TRY(hipMemcpyAsync(c->bz.h_count.data(), c->bz.d_count.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
-            BZ_TRY(hipStreamSynchronize(c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            HIP_TRY(c, launch_bz_scan(c->bz.d_in.data(), pn, c->bz.d_cand.data(), c->bz.d_count.data(), (uint32_t)c->bz.cand_cap(), c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            HIP_TRY(c, hipMemcpyAsync(c->bz.h_count.data(), c->bz.d_count.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+            HIP_TRY(c, hipStreamSynchronize(c->f_stream));
             timed(ev);
             if (c->bz.h_count[0] > c->bz.cand_cap()) {
                 chain_order = true;
             } else if (c->bz.h_count[0]) {
-                BZ_TRY(hipMemcpyAsync(c->bz.h_cand.data(), c->bz.d_cand.data(), (size_t)c->bz.h_count[0] * 8, hipMemcpyDeviceToHost, c->f_stream));
-                BZ_TRY(hipStreamSynchronize(c->f_stream));
+                HIP_TRY(c, hipMemcpyAsync(c->bz.h_cand.data(), c->bz.d_cand.data(), (size_t)c->bz.h_count[0] * 8, hipMemcpyDeviceToHost, c->f_stream));
+                HIP_TRY(c, hipStreamSynchronize(c->f_stream));
                 cand.assign(c->bz.h_cand.data(), c->bz.h_cand.data() + c->bz.h_count[0]);
                 std::sort(cand.begin(), cand.end());
             }
@@ -205,14 +197,14 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
             rc = ensure_bzip2(c, std::min<uint64_t>(P, n), std::max<uint32_t>(K, 8));
             if (rc) return rc;
             memcpy(c->bz.h_cand.data(), cand.data() + idx, (size_t)K * 8);
-            BZ_TRY(hipMemcpyAsync(c->bz.d_cand.data(), c->bz.h_cand.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
+            HIP_TRY(c, hipMemcpyAsync(c->bz.d_cand.data(), c->bz.h_cand.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
             EventPair* ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            BZ_TRY(hipEventRecord(ev->a, c->f_stream));
-            BZ_TRY(launch_bz_symbols(c->bz.d_in.data(), pn, c->bz.d_cand.data(), K, c->bz.d_slots.data(), c->bz.d_res.data(), c->f_stream));
-            BZ_TRY(hipEventRecord(ev->b, c->f_stream));
-            BZ_TRY(hipMemcpyAsync(c->bz.h_res.data(), c->bz.d_res.data(), (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
-            BZ_TRY(hipStreamSynchronize(c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            HIP_TRY(c, launch_bz_symbols(c->bz.d_in.data(), pn, c->bz.d_cand.data(), K, c->bz.d_slots.data(), c->bz.d_res.data(), c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            HIP_TRY(c, hipMemcpyAsync(c->bz.h_res.data(), c->bz.d_res.data(), (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
+            HIP_TRY(c, hipStreamSynchronize(c->f_stream));
             timed(ev);
             const uint64_t* lc = cand.data() + idx;
             for (;;) { // link what this launch decoded, then run the linked blocks through the later stages
@@ -245,7 +237,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
                     bz_cursor_take(cur, r.end_bit + pb * 8, r.crc);
                 }
                 if (nb) {
-                    rc = bunzip2_batch(x, c, nb, crcs, out, keep_dev, st, kms, crc_at, tally);
+                    rc = bunzip2_batch(x, c, nb, crcs, ds, st, kms, crc_at, tally);
                     if (rc) return rc;
                 }
                 if (!host_next) break;
@@ -261,52 +253,21 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, std:
     return SNAPHASH_OK;
 }
 
+const UnpackCodec kBunzip2Codec = {"bzip2", bunzip2_engine};
+
 } // namespace
 
 extern "C" {
 
 int snaphash_bunzip2_buffer(snaphash_ctx* x, const void* bz, size_t n, void** out, size_t* out_len)
-try {
-    if (!x || (!bz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    *out = nullptr;
-    *out_len = 0;
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    snaphash_unpack_stats st{};
-    st.struct_size = sizeof st;
-    st.gz_bytes = n;
-    std::vector<uint8_t> o;
-    const int rc = bunzip2_engine(x, c, (const uint8_t*)bz, n, o, false, st);
-    c->ev_used = 0;
-    st.tar_bytes = o.size();
-    st.wall_ms = now_ms() - t_top0_;
-    x->unpack = st;
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(o.size() ? o.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    if (!o.empty()) memcpy(p, o.data(), o.size());
-    *out = p;
-    *out_len = o.size();
-    return SNAPHASH_OK;
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
+{
+    return decode_to_malloc(x, kBunzip2Codec, bz, n, out, out_len);
 }
 
 int snaphash_tar_unpack_bz2(snaphash_ctx* x, const char* data_tar_bz2, const char* target_dir, const char* yaml, size_t yaml_len,
                             snaphash_mismatch* first, uint8_t* archive_digest)
-try {
-    if (!x || !data_tar_bz2 || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    return tar_unpack_common(x, c, t_top0_, data_tar_bz2, target_dir, yaml, yaml_len, first, archive_digest,
-                             [&](const uint8_t* bz, size_t n, std::vector<uint8_t>& tar, bool keep_dev, snaphash_unpack_stats& st) {
-                                 return bunzip2_engine(x, c, bz, n, tar, keep_dev, st);
-                             });
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
+{
+    return tar_unpack_entry(x, kBunzip2Codec, data_tar_bz2, target_dir, yaml, yaml_len, first, archive_digest);
 }
 
 } // extern "C"

@@ -1,5 +1,8 @@
 // unpack.inc -- the install side (SURVEY sec. 8 row f5), textually part of snaphash_api.cpp (it uses the engine's
-// streams, events, the hashing kernels and Verify's comparison).
+// streams, events, the hashing kernels and Verify's comparison).  It owns what every data-member format shares --
+// DecodedStream (where decoded bytes live, on the host and in HBM), the codec table's type, the tar reader, the member
+// writer, the members' digests and the Verify tail -- and the gzip decoder; unbz2.inc and unxz.inc add a decoder each,
+// snap.inc the .snap session that drives them.
 //
 // The reference unpacks a package with ClickDeb.Unpack (clickdeb/deb.go:188-203): gzip.NewReader (deb.go:427) -- one Go
 // inflate on one core -- into helpers.UnpackTar (helpers/helpers.go:74-147) with clickVerifyContentFn (deb.go:96-103);
@@ -9,34 +12,90 @@
 
 namespace {
 
+// Where a decoder's bytes live.  Every decoder appends to `out`; with keep_dev the same bytes also sit in c->inf.d_out
+// at the same offset (Verify's SHA-512 kernels and the CRC kernels read them there).  Without keep_dev d_out is scratch:
+// a run of bytes the kernels decode starts at its offset 0 and nothing a host thread decoded goes there.  Every copy and
+// kernel of the install side runs on c->f_stream.
+struct DecodedStream {
+    DevCtx* c;
+    std::vector<uint8_t>& out;
+    const bool keep_dev;
+    const size_t o_start; // out.size() when the decode began
+    DecodedStream(DevCtx* c_, std::vector<uint8_t>& out_, bool keep_dev_) : c(c_), out(out_), keep_dev(keep_dev_), o_start(out_.size()) {}
+
+    static int stream(DevCtx* c)
+    {
+        if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+        return SNAPHASH_OK;
+    }
+    // d_out of `end` bytes or more; `keep` bytes of what is there are kept when it grows
+    static int reserve_dev(DevCtx* c, uint64_t end, uint64_t keep)
+    {
+        DevBuf<uint8_t>& d = c->inf.d_out;
+        if (d.size() >= end) return SNAPHASH_OK;
+        uint64_t cap = std::max<uint64_t>(end, d.size() + d.size() / 2);
+        cap = (cap + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1);
+        DevBuf<uint8_t> p;
+        HIP_TRY(c, p.reserve(cap));
+        if (keep && d.data()) {
+            const hipError_t e = hipMemcpyAsync(p.data(), d.data(), keep, hipMemcpyDeviceToDevice, c->f_stream);
+            if (e == hipSuccess) (void)hipStreamSynchronize(c->f_stream);
+            HIP_TRY(c, e);
+        }
+        d = std::move(p);
+        return SNAPHASH_OK;
+    }
+    // a whole decoded stream into d_out from offset 0 (a session whose stream another decode has overwritten)
+    static int upload(DevCtx* c, const std::vector<uint8_t>& bytes)
+    {
+        int rc = stream(c);
+        if (!rc) rc = reserve_dev(c, std::max<size_t>(bytes.size(), 1), 0);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->inf.d_out.data(), bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->f_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
+        return SNAPHASH_OK;
+    }
+
+    // the offset in d_out of out[run0], where a run of bytes the kernels decode begins
+    uint64_t dev_base(size_t run0) const { return keep_dev ? run0 : 0; }
+    // host-decoded out[from..to) into HBM at the same offset: nothing without keep_dev
+    int mirror_async(size_t from, size_t to)
+    {
+        if (!keep_dev || to <= from) return SNAPHASH_OK;
+        int rc = stream(c);
+        if (!rc) rc = reserve_dev(c, to, from);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->inf.d_out.data() + from, out.data() + from, to - from, hipMemcpyHostToDevice, c->f_stream));
+        return SNAPHASH_OK;
+    }
+    int mirror(size_t from, size_t to)
+    {
+        const int rc = mirror_async(from, to);
+        return rc || !keep_dev || to <= from ? rc : sync();
+    }
+    // kernel-decoded out[from..to) of the run that began at out[run0], back from HBM; the caller syncs
+    int fetch(size_t run0, size_t from, size_t to)
+    {
+        if (to > from) HIP_TRY(c, hipMemcpyAsync(out.data() + from, c->inf.d_out.data() + dev_base(run0) + (from - run0), to - from, hipMemcpyDeviceToHost, c->f_stream));
+        return SNAPHASH_OK;
+    }
+    int sync()
+    {
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
+        return SNAPHASH_OK;
+    }
+    void rollback() { out.resize(o_start); } // a corrupt stream leaves nothing behind
+};
+
 // the compressed piece (and its candidates) and the segments a launch decodes
 int ensure_inflate(DevCtx* c, uint64_t piece, uint32_t slots, uint32_t slot_syms = kInflateSlotSyms, uint64_t bcand = 0,
                    uint32_t host_bslots = 0)
 {
-    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    const int rc = DecodedStream::stream(c);
+    if (rc) return rc;
     HIP_TRY(c, c->inf.ensure(piece, slots, c->numa_node, slot_syms, bcand, host_bslots));
     return SNAPHASH_OK;
 }
-
-// the decoded bytes in HBM: `keep` bytes of what is there are kept when it grows
-int ensure_fout(DevCtx* c, uint64_t need, uint64_t keep)
-{
-    DevBuf<uint8_t>& out = c->inf.d_out;
-    if (out.size() >= need) return SNAPHASH_OK;
-    uint64_t cap = std::max<uint64_t>(need, out.size() + out.size() / 2);
-    cap = (cap + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1);
-    DevBuf<uint8_t> p;
-    HIP_TRY(c, p.reserve(cap));
-    if (keep && out.data()) {
-        const hipError_t e = hipMemcpyAsync(p.data(), out.data(), keep, hipMemcpyDeviceToDevice, c->f_stream);
-        if (e == hipSuccess) (void)hipStreamSynchronize(c->f_stream);
-        HIP_TRY(c, e);
-    }
-    out = std::move(p);
-    return SNAPHASH_OK;
-}
-
-#define INF_TRY(expr) HIP_TRY(c, (expr))
 
 // Where a decoder takes the CRCs it checks.  Host: on host threads, out of the decoded bytes in host memory (every entry
 // point before the .snap session, and the session in the default configuration).  Device: by crc_kernels.hip out of the
@@ -47,44 +106,12 @@ struct CrcTally { // what a session's decodes did about their CRCs
     double device_ms = 0; // the CRC kernels, HIP events
 };
 
-// The CRC-32s (kind: kCrcGzip / kCrcBzip2) of n ranges of d_base on stream s, back on the host when the call returns.
-int crc_ranges_dev(DevCtx* c, int kind, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint32_t* crcs,
-                   hipStream_t s, double* ms)
-{
-    if (n == 0) return SNAPHASH_OK;
-    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (lens[i] > ~0ull - offs[i]) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
-        tiles += crc_tiles_of(lens[i]);
-    }
-    if (tiles >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "ranges of 256 TiB or more in one call");
-    HIP_TRY(c, c->crc.ensure(n, (size_t)tiles));
-    uint32_t t = 0;
-    for (size_t i = 0; i < n; ++i) {
-        c->crc.offs.h[i] = offs[i];
-        c->crc.lens.h[i] = lens[i];
-        c->crc.tile0.h[i] = t;
-        t += (uint32_t)crc_tiles_of(lens[i]);
-    }
-    c->crc.tile0.h[n] = t;
-    HIP_TRY(c, hipMemcpyAsync(c->crc.offs.d.data(), c->crc.offs.h.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.lens.d.data(), c->crc.lens.h.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.tile0.d.data(), c->crc.tile0.h.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, s));
-    HIP_TRY(c, launch_crc_ranges(kind, d_base, c->crc.offs.d.data(), c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, t,
-                                 c->crc.d_partial.data(), s));
-    HIP_TRY(c, launch_crc_fold(kind, c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, c->crc.d_partial.data(), c->crc.crcs.d.data(), s));
-    HIP_TRY(c, hipEventRecord(ev->b, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.crcs.h.data(), c->crc.crcs.d.data(), n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    float f = 0;
-    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
-    memcpy(crcs, c->crc.crcs.h.data(), n * 4);
-    return SNAPHASH_OK;
-}
+// A data-member format of the install side (ClickDeb.Unpack's data.tar.{gz,bz2,xz}, deb.go:185): its decoder appends the
+// decoded stream to ds.  kGunzipCodec below, kBunzip2Codec in unbz2.inc, kUnxzCodec in unxz.inc.
+struct UnpackCodec {
+    const char* name;
+    int (*decode)(snaphash_ctx*, DevCtx*, const uint8_t*, size_t, DecodedStream&, snaphash_unpack_stats&, CrcAt, CrcTally*);
+};
 
 // ---- block mode (SNAPHASH_FLAG_SPLIT_BLOCKS, DESIGN.md sec. 14) ----------------------------------------------------------
 
@@ -99,59 +126,61 @@ constexpr uint32_t kHostBlockSlots = 256;             // candidates a piece of t
 constexpr uint64_t kBlockPiecePerSlot = 16u << 10;    // compressed bytes a slot stands for: zlib's blocks took 12-31 KB
 
 // The linked segments' holes filled on the GPU (one pass over all, then -- if holes are left -- the segments that hold them
-// in order) and their symbols laid end to end into the decoded bytes: out[o0 .. o0 + total) and, with keep_dev, HBM.
+// in order) and their symbols laid end to end into the decoded bytes: appended to ds.out and, with keep_dev, left in HBM.
 // 1: holes are left (cannot happen after the ordered sweep: the caller falls back to the host decoder).
-int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, std::vector<uint8_t>& out, size_t m0, bool keep_dev,
-                    bool trace, const std::function<void(EventPair*)>& timed)
+int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, DecodedStream& ds, size_t m0, bool trace,
+                    const std::function<void(EventPair*)>& timed)
 {
+    std::vector<uint8_t>& out = ds.out;
     const size_t o0 = out.size();
     const uint32_t wlen = (uint32_t)std::min<size_t>(kInfWindow, o0 - m0);
-    if (wlen) INF_TRY(hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
-    INF_TRY(hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
+    if (wlen) HIP_TRY(c, hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
     bool filled = false;
     EventPair* ev = nullptr;
     for (int pass = 0; pass < 2 && !filled; ++pass) {
-        INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
+        HIP_TRY(c, hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
         ev = next_events(c, 2);
         if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        INF_TRY(hipEventRecord(ev->a, c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
         if (pass == 1)
             for (uint32_t j = 0; j < nl; ++j)
-                if (c->inf.h_links[j].hole_end) INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
-        if (pass == 1) INF_TRY(hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
-        INF_TRY(launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
-        INF_TRY(hipEventRecord(ev->b, c->f_stream));
-        INF_TRY(hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
-        INF_TRY(hipStreamSynchronize(c->f_stream));
+                if (c->inf.h_links[j].hole_end) HIP_TRY(c, launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
+        if (pass == 1) HIP_TRY(c, hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
+        HIP_TRY(c, launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
         timed(ev);
         if (c->inf.h_flags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
         filled = c->inf.h_flags[0] == 0;
         if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->inf.h_flags[0]);
     }
     if (!filled) return 1;
-    int rc = ensure_fout(c, keep_dev ? o0 + total : total, keep_dev ? o0 : 0);
+    int rc = ds.reserve_dev(c, ds.dev_base(o0) + total, ds.dev_base(o0));
     if (rc) return rc;
-    uint8_t* dst = c->inf.d_out.data() + (keep_dev ? o0 : 0);
     ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    INF_TRY(hipEventRecord(ev->a, c->f_stream));
-    INF_TRY(launch_inflate_concat(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), nl, dst, c->f_stream));
-    INF_TRY(hipEventRecord(ev->b, c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    HIP_TRY(c, launch_inflate_concat(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), nl, c->inf.d_out.data() + ds.dev_base(o0), c->f_stream));
+    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
     out.resize(o0 + total);
-    INF_TRY(hipMemcpyAsync(out.data() + o0, dst, total, hipMemcpyDeviceToHost, c->f_stream));
-    INF_TRY(hipStreamSynchronize(c->f_stream));
+    rc = ds.fetch(o0, o0, o0 + total);
+    if (!rc) rc = ds.sync();
+    if (rc) return rc;
     timed(ev);
     return 0;
 }
 
-// One member's raw DEFLATE stream z[0..zn) in block mode, appended to out (the member's output starts at m0).  Pieces
+// One member's raw DEFLATE stream z[0..zn) in block mode, appended to ds.out (the member's output starts at m0).  Pieces
 // start at any bit: the block scan and the stored-block scan on the GPU give the candidates, every candidate is decoded
 // into a slot (the inflate kernel under SNAPHASH_FLAG_GPU_ONLY, host threads otherwise), the chain is linked from the
 // piece's start bit and filled in order.  Where it breaks at the piece's start the host decoder takes the stretch to the
 // next block the scan can find.  *final_bit: where the final block ended.
-int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std::vector<uint8_t>& out, size_t m0, bool keep_dev,
-                  snaphash_unpack_stats& st, float& kms, uint64_t* final_bit)
+int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, DecodedStream& ds, size_t m0, snaphash_unpack_stats& st,
+                  float& kms, uint64_t* final_bit)
 {
+    std::vector<uint8_t>& out = ds.out;
     snaphash_block_scan_stats& bs = x->block_scan;
     const bool host_mode = !x->gpu_only;
     static const bool trace = getenv("SNAPHASH_TRACE_INFLATE") != nullptr;
@@ -181,30 +210,30 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
         const uint64_t b0 = cur >> 3, sb = cur & 7, pn = std::min<uint64_t>(piece, zn - b0);
         piece = P;
         // the scans: block headers at every bit, stored-block ends at every byte
-        INF_TRY(hipMemcpyAsync(c->inf.d_in.data(), z + b0, pn, hipMemcpyHostToDevice, c->f_stream));
-        INF_TRY(hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
-        INF_TRY(hipMemsetAsync(c->inf.d_bcand.data(), 0, 4, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->inf.d_in.data(), z + b0, pn, hipMemcpyHostToDevice, c->f_stream));
+        HIP_TRY(c, hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
+        HIP_TRY(c, hipMemsetAsync(c->inf.d_bcand.data(), 0, 4, c->f_stream));
         // (both pairs taken before either is used: taking one may grow the pool and move the other)
         if (!next_events(c, 2) || !next_events(c, 2)) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
         EventPair* ev = &c->ev_pool[c->ev_used - 2];
         EventPair* evb = &c->ev_pool[c->ev_used - 1];
-        INF_TRY(hipEventRecord(ev->a, c->f_stream));
-        INF_TRY(launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
-        INF_TRY(hipEventRecord(evb->a, c->f_stream));
-        INF_TRY(launch_inflate_block_scan(c->inf.d_in.data(), pn, c->inf.d_bcand.data() + 1, c->inf.d_bcand.data(), (uint32_t)c->inf.bcand_cap(), c->f_stream));
-        INF_TRY(hipEventRecord(evb->b, c->f_stream));
-        INF_TRY(hipEventRecord(ev->b, c->f_stream));
-        INF_TRY(hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
-        INF_TRY(hipMemcpyAsync(c->inf.h_bcand.data(), c->inf.d_bcand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
-        INF_TRY(hipStreamSynchronize(c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+        HIP_TRY(c, launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
+        HIP_TRY(c, hipEventRecord(evb->a, c->f_stream));
+        HIP_TRY(c, launch_inflate_block_scan(c->inf.d_in.data(), pn, c->inf.d_bcand.data() + 1, c->inf.d_bcand.data(), (uint32_t)c->inf.bcand_cap(), c->f_stream));
+        HIP_TRY(c, hipEventRecord(evb->b, c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->inf.h_bcand.data(), c->inf.d_bcand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
         timed(ev);
         float sms = 0;
         if (hipEventElapsedTime(&sms, evb->a, evb->b) == hipSuccess) bs.scan_ms += sms;
         const uint64_t ns = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
         const uint64_t nb = std::min<uint64_t>(c->inf.h_bcand[0], c->inf.bcand_cap());
-        if (ns) INF_TRY(hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ns * 4, hipMemcpyDeviceToHost, c->f_stream));
-        if (nb) INF_TRY(hipMemcpyAsync(c->inf.h_bcand.data() + 1, c->inf.d_bcand.data() + 1, nb * 4, hipMemcpyDeviceToHost, c->f_stream));
-        INF_TRY(hipStreamSynchronize(c->f_stream));
+        if (ns) HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ns * 4, hipMemcpyDeviceToHost, c->f_stream));
+        if (nb) HIP_TRY(c, hipMemcpyAsync(c->inf.h_bcand.data() + 1, c->inf.d_bcand.data() + 1, nb * 4, hipMemcpyDeviceToHost, c->f_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
         bs.bits_scanned += pn * 8;
         bs.candidates += c->inf.h_bcand[0];
         // the candidates in order from the piece's start bit: block starts, stored-block ends, the start itself
@@ -248,7 +277,7 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
                     done[i].store(1, std::memory_order_release);
                 }
             };
-            const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, x->cpus_call ? x->cpus_call : x->cpus) - 1);
+            const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, call_cpus(x)) - 1);
             ThreadJoiner th;
             for (unsigned k = 0; k < T; ++k) th.spawn(work);
             const size_t o0 = out.size();
@@ -273,22 +302,18 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
             next.store(K); // (what is left of the piece is scanned and decoded again as the next piece)
             th.join_all();
             if (bad) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
-            if (nl && keep_dev && out.size() > o0) {
-                rc = ensure_fout(c, out.size(), o0);
-                if (rc) return rc;
-                INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
-                INF_TRY(hipStreamSynchronize(c->f_stream));
-            }
+            rc = ds.mirror(o0, out.size());
+            if (rc) return rc;
         } else {
             memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
-            INF_TRY(hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
+            HIP_TRY(c, hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
             ev = next_events(c, 2);
             if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            INF_TRY(hipEventRecord(ev->a, c->f_stream));
-            INF_TRY(launch_inflate_decode_blocks(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
-            INF_TRY(hipEventRecord(ev->b, c->f_stream));
-            INF_TRY(hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
-            INF_TRY(hipStreamSynchronize(c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            HIP_TRY(c, launch_inflate_decode_blocks(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
+            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            HIP_TRY(c, hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
+            HIP_TRY(c, hipStreamSynchronize(c->f_stream));
             timed(ev);
             uint64_t off = 0;
             for (;;) {
@@ -310,7 +335,7 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
                 if (pos >= pn * 8) break;
             }
             if (nl) {
-                rc = gpu_fill_concat(c, nl, off, kInflateBlockSlotSyms, out, m0, keep_dev, trace, timed_f);
+                rc = gpu_fill_concat(c, nl, off, kInflateBlockSlotSyms, ds, m0, trace, timed_f);
                 if (rc < 0) return rc;
                 if (rc) { nl = 0; fin = false; } // (holes left: the host decoder takes over from the piece's start)
                 else st.gpu_segments += nl;
@@ -336,29 +361,26 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, std
         st.segments++;
         st.host_bytes += out.size() - o0;
         bs.host_blocks++;
-        if (keep_dev && out.size() > o0) {
-            rc = ensure_fout(c, out.size(), o0);
-            if (rc) return rc;
-            INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
-            INF_TRY(hipStreamSynchronize(c->f_stream));
-        }
+        rc = ds.mirror(o0, out.size());
+        if (rc) return rc;
         if (r.status == kInfFinal) { *final_bit = r.end_bit; return 0; }
         cur = r.end_bit;
     }
 }
 
-// Decodes every gzip member of gz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
+// Decodes every gzip member of gz[0..n) and appends the bytes to ds.out; keep_dev: the whole decoded stream also stays in
 // c->inf.d_out[0..out.size()).  Pieces of at most c->staging compressed bytes; each ends on a segment boundary and the
 // member's last 32 KiB of output travel to the next as its window.
 // crc_at = CrcAt::Device (honoured with keep_dev, where the whole stream is in HBM): every member's CRC-32 is taken by the CRC
 // kernels when the last member is decoded, a range a member, instead of by crc_parallel member by member; tally (may be
 // null) counts what was taken where.
-int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::vector<uint8_t>& out, bool keep_dev,
-                  snaphash_unpack_stats& st, CrcAt crc_at = CrcAt::Host, CrcTally* tally = nullptr)
+int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, DecodedStream& ds, snaphash_unpack_stats& st, CrcAt crc_at,
+                  CrcTally* tally)
 {
     if (n == 0) return fail(c, SNAPHASH_EFORMAT, "gzip: empty stream");
+    std::vector<uint8_t>& out = ds.out;
     c->fout_gen++;
-    const bool dev_crc = crc_at == CrcAt::Device && keep_dev;
+    const bool dev_crc = crc_at == CrcAt::Device && ds.keep_dev;
     std::vector<uint64_t> m_off, m_len; // dev_crc: the members' ranges of the decoded stream and their stored CRC-32s
     std::vector<uint32_t> m_crc;
     x->block_scan = snaphash_block_scan_stats{};
@@ -401,18 +423,13 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             if (r.status != kInfFinal && r.status != kInfFlush) return fail(c, SNAPHASH_EFORMAT, "gzip: corrupt DEFLATE stream");
             st.segments++;
             st.host_bytes += out.size() - o0;
-            if (keep_dev && out.size() > o0) {
-                int e = ensure_fout(c, out.size(), o0);
-                if (e) return e;
-                INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
-                INF_TRY(hipStreamSynchronize(c->f_stream));
-            }
+            if (int e = ds.mirror(o0, out.size())) return e;
             if (r.status == kInfFinal) { ended = true; final_bit = r.end_bit; }
             else cur = r.end_bit >> 3;
             return 0;
         };
         if (split && zn >= kSplitMinBytes) { // block mode: the whole member
-            rc = gunzip_blocks(x, c, z, zn, out, m0, keep_dev, st, kms, &final_bit);
+            rc = gunzip_blocks(x, c, z, zn, ds, m0, st, kms, &final_bit);
             if (rc) return rc;
             ended = true;
         }
@@ -424,20 +441,20 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
             if (host_mode) {
                 for (uint64_t v : flush_candidates(z + cur, pn)) cand.push_back((uint32_t)v);
             } else {
-                INF_TRY(hipMemcpyAsync(c->inf.d_in.data(), z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
-                INF_TRY(hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
+                HIP_TRY(c, hipMemcpyAsync(c->inf.d_in.data(), z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
+                HIP_TRY(c, hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
                 EventPair* ev = next_events(c, 2);
                 if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-                INF_TRY(hipEventRecord(ev->a, c->f_stream));
-                INF_TRY(launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
-                INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
-                INF_TRY(hipStreamSynchronize(c->f_stream));
+                HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+                HIP_TRY(c, launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
+                HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+                HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
+                HIP_TRY(c, hipStreamSynchronize(c->f_stream));
                 timed(ev);
                 const uint64_t ncand = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
                 if (ncand) {
-                    INF_TRY(hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
-                    INF_TRY(hipStreamSynchronize(c->f_stream));
+                    HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
+                    HIP_TRY(c, hipStreamSynchronize(c->f_stream));
                 }
                 cand.assign(c->inf.h_cand.data() + 1, c->inf.h_cand.data() + 1 + ncand);
             }
@@ -480,7 +497,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                         done[i].store(1, std::memory_order_release);
                     }
                 };
-                const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, x->cpus_call ? x->cpus_call : x->cpus) - 1);
+                const unsigned T = (unsigned)std::min<uint64_t>(K, std::max(2u, call_cpus(x)) - 1);
                 ThreadJoiner th;
                 for (unsigned k = 0; k < T; ++k) th.spawn(work);
                 const size_t o0 = out.size();
@@ -511,26 +528,22 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                     if (rc) return rc;
                     continue;
                 }
-                if (keep_dev && out.size() > o0) {
-                    rc = ensure_fout(c, out.size(), o0);
-                    if (rc) return rc;
-                    INF_TRY(hipMemcpyAsync(c->inf.d_out.data() + o0, out.data() + o0, out.size() - o0, hipMemcpyHostToDevice, c->f_stream));
-                    INF_TRY(hipStreamSynchronize(c->f_stream));
-                }
+                rc = ds.mirror(o0, out.size());
+                if (rc) return rc;
                 st.segments += nl;
                 if (fin) ended = true;
                 else cur += pos;
                 continue;
             } else {
                 memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
-                INF_TRY(hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
+                HIP_TRY(c, hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
                 EventPair* ev = next_events(c, 2);
                 if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-                INF_TRY(hipEventRecord(ev->a, c->f_stream));
-                INF_TRY(launch_inflate_decode(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
-                INF_TRY(hipEventRecord(ev->b, c->f_stream));
-                INF_TRY(hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
-                INF_TRY(hipStreamSynchronize(c->f_stream));
+                HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+                HIP_TRY(c, launch_inflate_decode(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
+                HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+                HIP_TRY(c, hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
+                HIP_TRY(c, hipStreamSynchronize(c->f_stream));
                 timed(ev);
             }
             // link: from the piece's start, each segment where the one before ended
@@ -565,7 +578,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
                 if (rc) return rc;
                 continue;
             }
-            rc = gpu_fill_concat(c, nl, off, kInflateSlotSyms, out, m0, keep_dev, trace, timed_f);
+            rc = gpu_fill_concat(c, nl, off, kInflateSlotSyms, ds, m0, trace, timed_f);
             if (rc < 0) return rc;
             if (rc) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
                 rc = host_run();
@@ -595,7 +608,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
         at += h + next;
     }
     if (!m_off.empty()) {
-        rc = ensure_fout(c, 1, 0); // (every member empty: nothing was written there yet, but the kernel takes a base)
+        rc = ds.reserve_dev(c, 1, 0); // (every member empty: nothing was written there yet, but the kernel takes a base)
         if (rc) return rc;
         std::vector<uint32_t> got(m_off.size());
         double ms = 0;
@@ -608,6 +621,8 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, std::
     st.inflate_ms += kms;
     return SNAPHASH_OK;
 }
+
+const UnpackCodec kGunzipCodec = {"gzip", gunzip_engine};
 
 // ---- the tar side: archive/tar's reader as UnpackTar drives it ---------------------------------------------------------
 
@@ -797,11 +812,6 @@ int unpack_members(DevCtx* c, const std::vector<TarEntry>& ents, const uint8_t* 
     return SNAPHASH_OK;
 }
 
-// ClickDeb.Unpack after the choice of decoder, for both data-member formats: the archive read once, its digest on a host
-// core beside the decode, `decode` into the tar stream (kept in c->inf.d_out.data() too when hashes.yaml asks for Verify), then
-// tar_read, unpack_members, the members' digests (host / GPU split) and verify_impl.
-using UnpackDecode = std::function<int(const uint8_t*, size_t, std::vector<uint8_t>&, bool, snaphash_unpack_stats&)>;
-
 // a whole file into memory, in one pass
 int read_whole(snaphash_ctx* x, const char* path, std::vector<uint8_t>& gz)
 {
@@ -833,7 +843,7 @@ int hash_members(snaphash_ctx* x, DevCtx* c, const std::vector<uint8_t>& tar, co
     MemberHashers mh;
     std::vector<size_t> hosted;
     if (!x->gpu_only && !reg.empty()) {
-        const unsigned cpus = x->cpus_call ? x->cpus_call : x->cpus;
+        const unsigned cpus = call_cpus(x);
         const double pass_s = std::max(0.008, (double)tar.size() / 4.5e9);
         const uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s);
         std::vector<uint64_t> sizes;
@@ -883,9 +893,52 @@ std::vector<size_t> last_regular_members(const std::vector<TarEntry>& ents)
     return reg;
 }
 
-int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* archive, const char* target_dir, const char* yaml,
-                      size_t yaml_len, snaphash_mismatch* first, uint8_t* archive_digest, const UnpackDecode& decode)
+// the SHA-512 of p[0..n) on a host core of its own, beside what its scope does; joined where the scope ends at the latest
+struct DigestThread {
+    std::thread th;
+    DigestThread(const uint8_t* p, size_t n, uint8_t* dig)
+        : th([=] {
+              HostSha s;
+              host_sha512_init(s);
+              host_sha512_update(s, p, n);
+              host_sha512_final(s, dig);
+          })
+    {
+    }
+    void join() { if (th.joinable()) th.join(); }
+    ~DigestThread() { join(); }
+};
+
+// Verify after the members were written: the regular members' digests out of the decoded stream tar (which c->inf.d_out
+// holds too), then Verify's own comparison on the unpacked tree (its walk is Lstat only: the modes as they are on disk); a
+// record whose bytes came from the archive takes their digest, anything else there was before is hashed from disk.
+int verify_unpacked(snaphash_ctx* x, DevCtx* c, const std::vector<uint8_t>& tar, const std::vector<TarEntry>& ents, const char* target_dir,
+                    const char* archive, const uint8_t* adig, const char* yaml, size_t yaml_len, snaphash_mismatch* first)
 {
+    const std::vector<size_t> reg = last_regular_members(ents); // members hashed: the last member of a name is what is on disk
+    std::vector<uint8_t> dig;
+    const int rc = hash_members(x, c, tar, ents, reg, dig);
+    if (rc) return rc;
+    std::unordered_map<std::string, size_t> dig_of;
+    for (size_t q = 0; q < reg.size(); ++q) dig_of[ents[reg[q]].name] = q;
+    return verify_impl(x, target_dir, archive, adig, yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
+        const auto it = dig_of.find(r.name);
+        if (it == dig_of.end() || (int64_t)ents[reg[it->second]].size != r.size) return false;
+        memcpy(d, dig.data() + 64 * it->second, 64);
+        return true;
+    });
+}
+
+// ClickDeb.Unpack after the choice of decoder, for every data-member format: the archive read once, its digest on a host
+// core beside the decode, the codec's decoder into the tar stream (kept in c->inf.d_out too when hashes.yaml asks for
+// Verify), then tar_read, unpack_members and verify_unpacked.  The body of the snaphash_tar_unpack* entry points.
+int tar_unpack_entry(snaphash_ctx* x, const UnpackCodec& codec, const char* archive, const char* target_dir, const char* yaml, size_t yaml_len,
+                     snaphash_mismatch* first, uint8_t* archive_digest)
+try {
+    if (!x || !archive || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
     snaphash_unpack_stats st{};
     st.struct_size = sizeof st;
     // the archive, read once
@@ -895,16 +948,11 @@ int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* ar
     st.gz_bytes = gz.size();
     // the archive digest over the compressed bytes, on a host core beside the decode
     uint8_t adig[64];
-    std::thread dig_th([&] {
-        HostSha s;
-        host_sha512_init(s);
-        host_sha512_update(s, gz.data(), gz.size());
-        host_sha512_final(s, adig);
-    });
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{dig_th};
+    DigestThread dig_th(gz.data(), gz.size(), adig);
     std::vector<uint8_t> tar;
     const bool want_verify = yaml != nullptr;
-    int rc = decode(gz.data(), gz.size(), tar, want_verify, st);
+    DecodedStream ds(c, tar, want_verify);
+    int rc = codec.decode(x, c, gz.data(), gz.size(), ds, st, CrcAt::Host, nullptr);
     c->ev_used = 0;
     st.tar_bytes = tar.size();
     std::vector<TarEntry> ents;
@@ -917,42 +965,20 @@ int tar_unpack_common(snaphash_ctx* x, DevCtx* c, double t_top0_, const char* ar
     if (!rc) rc = unpack_members(c, ents, tar.data(), target_dir);
     dig_th.join();
     if (archive_digest) memcpy(archive_digest, adig, 64);
-    if (rc) {
-        st.wall_ms = now_ms() - t_top0_;
-        x->unpack = st;
-        end_top(x, t_top0_);
-        return lift(x, c, rc);
-    }
-    if (want_verify) {
-        // the regular members' digests out of the decoded stream: the last member of a name is what is on disk
-        const std::vector<size_t> reg = last_regular_members(ents); // members hashed
-        std::vector<uint8_t> dig;
-        rc = hash_members(x, c, tar, ents, reg, dig);
-        if (rc) return rc;
-        std::unordered_map<std::string, size_t> dig_of;
-        for (size_t q = 0; q < reg.size(); ++q) dig_of[ents[reg[q]].name] = q;
-        // Verify's own comparison on the unpacked tree (its walk is Lstat only: the modes as they are on disk); a record
-        // whose bytes came from the archive takes their digest, anything else there was before is hashed from disk
-        rc = verify_impl(x, target_dir, archive, adig, yaml, yaml_len, first, [&](const Record& r, uint8_t* d) {
-            const auto it = dig_of.find(r.name);
-            if (it == dig_of.end() || (int64_t)ents[reg[it->second]].size != r.size) return false;
-            memcpy(d, dig.data() + 64 * it->second, 64);
-            return true;
-        });
-    }
+    if (rc) rc = lift(x, c, rc);
+    else if (want_verify) rc = verify_unpacked(x, c, tar, ents, target_dir, archive, adig, yaml, yaml_len, first);
     st.wall_ms = now_ms() - t_top0_;
     x->unpack = st;
     end_top(x, t_top0_);
     return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
 }
 
-} // namespace
-
-extern "C" {
-
-int snaphash_gunzip_buffer(snaphash_ctx* x, const void* gz, size_t n, void** out, size_t* out_len)
+// A whole compressed buffer decoded into memory the caller frees: the body of the snaphash_*_buffer entry points.
+int decode_to_malloc(snaphash_ctx* x, const UnpackCodec& codec, const void* in, size_t n, void** out, size_t* out_len)
 try {
-    if (!x || (!gz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (!x || (!in && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
     *out = nullptr;
     *out_len = 0;
     TOP_ENTER(x);
@@ -962,7 +988,8 @@ try {
     st.struct_size = sizeof st;
     st.gz_bytes = n;
     std::vector<uint8_t> o;
-    const int rc = gunzip_engine(x, c, (const uint8_t*)gz, n, o, false, st);
+    DecodedStream ds(c, o, false);
+    const int rc = codec.decode(x, c, (const uint8_t*)in, n, ds, st, CrcAt::Host, nullptr);
     c->ev_used = 0;
     st.tar_bytes = o.size();
     st.wall_ms = now_ms() - t_top0_;
@@ -979,19 +1006,19 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+} // namespace
+
+extern "C" {
+
+int snaphash_gunzip_buffer(snaphash_ctx* x, const void* gz, size_t n, void** out, size_t* out_len)
+{
+    return decode_to_malloc(x, kGunzipCodec, gz, n, out, out_len);
+}
+
 int snaphash_tar_unpack(snaphash_ctx* x, const char* data_tar_gz, const char* target_dir, const char* yaml, size_t yaml_len,
                         snaphash_mismatch* first, uint8_t* archive_digest)
-try {
-    if (!x || !data_tar_gz || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    return tar_unpack_common(x, c, t_top0_, data_tar_gz, target_dir, yaml, yaml_len, first, archive_digest,
-                             [&](const uint8_t* gz, size_t n, std::vector<uint8_t>& tar, bool keep_dev, snaphash_unpack_stats& st) {
-                                 return gunzip_engine(x, c, gz, n, tar, keep_dev, st);
-                             });
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
+{
+    return tar_unpack_entry(x, kGunzipCodec, data_tar_gz, target_dir, yaml, yaml_len, first, archive_digest);
 }
 
 int snaphash_get_unpack_stats(const snaphash_ctx* x, snaphash_unpack_stats* out)

@@ -1,5 +1,5 @@
-// unxz.inc -- the data.tar.xz side of the install path, textually part of snaphash_api.cpp (after unpack.inc and
-// unbz2.inc, whose tar reader, member writer and Verify tail it shares).
+// unxz.inc -- the data.tar.xz side of the install path, textually part of snaphash_api.cpp (after unpack.inc, which
+// owns DecodedStream and everything behind the decoder; this file owns the .xz decoder and its codec entry, kUnxzCodec).
 //
 // The reference's ClickDeb.Unpack takes data.tar.{gz,bz2,xz} (clickdeb/deb.go:185); skipToArMember (deb.go:408-441)
 // pipes the .xz member through the xz program.  Here the file's Index says where every Block begins and where its bytes
@@ -10,108 +10,58 @@
 
 namespace {
 
-// The CRC-64/XZ of n ranges of d_base on stream s, back on the host when the call returns (the twin of crc_ranges_dev).
-int crc64_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint64_t* crcs, hipStream_t s,
-                     double* ms)
+// Decodes every Stream of xz[0..n) and appends the bytes to ds.out; keep_dev: the whole decoded stream also stays in
+// c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.  The two CRC arguments of a codec's
+// decoder are not read: under SNAPHASH_FLAG_GPU_ONLY the Checks are taken in HBM whoever calls, on host threads otherwise.
+int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, DecodedStream& ds, snaphash_unpack_stats& st, CrcAt, CrcTally*)
 {
-    if (n == 0) return SNAPHASH_OK;
-    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (lens[i] > ~0ull - offs[i]) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
-        tiles += crc_tiles_of(lens[i]);
-    }
-    if (tiles >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "ranges of 256 TiB or more in one call");
-    HIP_TRY(c, c->crc.ensure64(n, (size_t)tiles));
-    uint32_t t = 0;
-    for (size_t i = 0; i < n; ++i) {
-        c->crc.offs.h[i] = offs[i];
-        c->crc.lens.h[i] = lens[i];
-        c->crc.tile0.h[i] = t;
-        t += (uint32_t)crc_tiles_of(lens[i]);
-    }
-    c->crc.tile0.h[n] = t;
-    HIP_TRY(c, hipMemcpyAsync(c->crc.offs.d.data(), c->crc.offs.h.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.lens.d.data(), c->crc.lens.h.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.tile0.d.data(), c->crc.tile0.h.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, s));
-    HIP_TRY(c, launch_crc64_ranges(d_base, c->crc.offs.d.data(), c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, t,
-                                   c->crc.d_partial64.data(), s));
-    HIP_TRY(c, launch_crc64_fold(c->crc.lens.d.data(), c->crc.tile0.d.data(), (uint32_t)n, c->crc.d_partial64.data(), c->crc.crcs64.d.data(), s));
-    HIP_TRY(c, hipEventRecord(ev->b, s));
-    HIP_TRY(c, hipMemcpyAsync(c->crc.crcs64.h.data(), c->crc.crcs64.d.data(), n * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    float f = 0;
-    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
-    memcpy(crcs, c->crc.crcs64.h.data(), n * 8);
-    return SNAPHASH_OK;
-}
-
-#define XZ_TRY(expr) HIP_TRY(c, (expr))
-
-// Decodes every Stream of xz[0..n) and appends the bytes to out; keep_dev: the whole decoded stream also stays in
-// c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.
-int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, std::vector<uint8_t>& out, bool keep_dev, snaphash_unpack_stats& st)
-{
+    std::vector<uint8_t>& out = ds.out;
     std::vector<XzBlock> blocks;
     uint64_t total = 0;
     std::string why;
     const int pe = xz_plan(xz, n, blocks, &total, why);
     if (pe) return fail(c, pe == kXzPlanUnsupported ? SNAPHASH_EINVAL : SNAPHASH_EFORMAT, why);
     c->fout_gen++;
-    const unsigned cpus = std::max(1u, x->cpus_call ? x->cpus_call : x->cpus);
+    const unsigned cpus = call_cpus(x);
     const size_t o0 = out.size();
     out.resize(o0 + total);
     uint8_t* dst = out.data() + o0;
-    const uint64_t base = keep_dev ? o0 : 0; // where the result begins in c->inf.d_out
-    auto to_dev = [&](uint64_t off, uint64_t len) -> int { // host-decoded bytes of the result into c->inf.d_out
-        if (!len) return SNAPHASH_OK;
-        XZ_TRY(hipMemcpyAsync(c->inf.d_out.data() + base + off, dst + off, len, hipMemcpyHostToDevice, c->f_stream));
-        return SNAPHASH_OK;
-    };
-    if (!c->f_stream) XZ_TRY(hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    const uint64_t base = ds.dev_base(o0); // where the result begins in c->inf.d_out
+    int rc = DecodedStream::stream(c);
+    if (rc) return rc;
     st.segments += blocks.size();
     if (!x->gpu_only) {
         // the default configuration: a Block a host thread (DESIGN.md sec. 17)
         if (xz_blocks_host(xz, blocks, nullptr, dst, cpus)) {
-            out.resize(o0);
+            ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "xz: corrupt block");
         }
         st.host_bytes += total;
-        if (keep_dev && total) {
-            int e = ensure_fout(c, base + total, base);
-            if (e) return e;
-            e = to_dev(0, total);
-            if (e) return e;
-            XZ_TRY(hipStreamSynchronize(c->f_stream));
-        }
-        return SNAPHASH_OK;
+        return ds.mirror(o0, o0 + total);
     }
     // SNAPHASH_FLAG_GPU_ONLY: every Block up to kXzGpuBlockMax through the kernel, the rest (and what the kernel refuses) on
     // host threads
     std::vector<uint32_t> gpu, host;
     for (uint32_t i = 0; i < blocks.size(); ++i) (blocks[i].out_len <= kXzGpuBlockMax ? gpu : host).push_back(i);
-    int rc = ensure_fout(c, std::max<uint64_t>(base + total, 1), base);
+    rc = ds.reserve_dev(c, std::max<uint64_t>(base + total, 1), base);
     if (rc) return rc;
     if (!gpu.empty()) {
         float kms = 0;
         double cms = 0;
-        XZ_TRY(c->xz.ensure(n, gpu.size()));
-        XZ_TRY(hipMemcpyAsync(c->xz.d_in.data(), xz, n, hipMemcpyHostToDevice, c->f_stream));
+        HIP_TRY(c, c->xz.ensure(n, gpu.size()));
+        HIP_TRY(c, hipMemcpyAsync(c->xz.d_in.data(), xz, n, hipMemcpyHostToDevice, c->f_stream));
         for (size_t k = 0; k < gpu.size(); ++k) {
             const XzBlock& b = blocks[gpu[k]];
             c->xz.blk.h[k] = XzGpuBlock{b.in_off, b.in_len, base + b.out_off, b.out_len, b.dict_size, (uint32_t)kXzBad};
         }
-        XZ_TRY(hipMemcpyAsync(c->xz.blk.d.data(), c->xz.blk.h.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->xz.blk.d.data(), c->xz.blk.h.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
         EventPair* ev = next_events(c, 2);
         if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        XZ_TRY(hipEventRecord(ev->a, c->f_stream));
-        XZ_TRY(launch_lzma2_blocks(c->xz.d_in.data(), c->inf.d_out.data(), c->xz.blk.d.data(), (uint32_t)gpu.size(), c->f_stream));
-        XZ_TRY(hipEventRecord(ev->b, c->f_stream));
-        XZ_TRY(hipMemcpyAsync(c->xz.blk.h.data(), c->xz.blk.d.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
-        XZ_TRY(hipStreamSynchronize(c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+        HIP_TRY(c, launch_lzma2_blocks(c->xz.d_in.data(), c->inf.d_out.data(), c->xz.blk.d.data(), (uint32_t)gpu.size(), c->f_stream));
+        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        HIP_TRY(c, hipMemcpyAsync(c->xz.blk.h.data(), c->xz.blk.d.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream));
         (void)hipEventElapsedTime(&kms, ev->a, ev->b);
         st.inflate_ms += kms;
         c->ev_used = 0;
@@ -129,7 +79,8 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, std::ve
             const uint64_t from = blocks[ok[k]].out_off;
             uint64_t to = from + blocks[ok[k]].out_len;
             for (++k; k < ok.size() && blocks[ok[k]].out_off == to; ++k) to += blocks[ok[k]].out_len;
-            if (to > from) XZ_TRY(hipMemcpyAsync(dst + from, c->inf.d_out.data() + base + from, to - from, hipMemcpyDeviceToHost, c->f_stream));
+            rc = ds.fetch(o0, o0 + from, o0 + to);
+            if (rc) return rc;
         }
         std::vector<uint64_t> offs, lens;
         auto ranges = [&](const std::vector<uint32_t>& v) {
@@ -149,7 +100,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, std::ve
         if (!k64.empty()) {
             ranges(k64);
             std::vector<uint64_t> got(k64.size());
-            rc = crc64_ranges_dev(c, c->inf.d_out.data(), offs.data(), lens.data(), k64.size(), got.data(), c->f_stream, &cms);
+            rc = crc_ranges_dev(c, 0, c->inf.d_out.data(), offs.data(), lens.data(), k64.size(), got.data(), c->f_stream, &cms);
             c->ev_used = 0;
             if (rc) return rc;
             for (size_t k = 0; k < k64.size(); ++k) {
@@ -157,79 +108,47 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, std::ve
                 bad |= got[k] != ((uint64_t)xz_le32(f + 4) << 32 | xz_le32(f));
             }
         }
-        XZ_TRY(hipStreamSynchronize(c->f_stream)); // (the bytes are back: the CRC calls waited on the same stream, but there may be none)
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the CRC calls waited on the same stream, but there may be none)
         st.inflate_ms += cms;
         for (uint32_t i : ok)
             if (blocks[i].check == kXzCheckSha256) bad |= !xz_check_block(xz, blocks[i], dst + blocks[i].out_off);
         if (bad) {
-            out.resize(o0);
+            ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "xz: block check mismatch");
         }
         st.gpu_segments += ok.size();
     }
     if (!host.empty()) {
         if (xz_blocks_host(xz, blocks, &host, dst, cpus)) {
-            out.resize(o0);
+            ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "xz: corrupt block");
         }
         for (uint32_t i : host) {
             st.host_bytes += blocks[i].out_len;
-            if (keep_dev) {
-                rc = to_dev(blocks[i].out_off, blocks[i].out_len);
-                if (rc) return rc;
-            }
+            rc = ds.mirror_async(o0 + blocks[i].out_off, o0 + blocks[i].out_off + blocks[i].out_len);
+            if (rc) return rc;
         }
-        XZ_TRY(hipStreamSynchronize(c->f_stream));
+        rc = ds.sync();
+        if (rc) return rc;
     }
     return SNAPHASH_OK;
 }
+
+const UnpackCodec kUnxzCodec = {"xz", unxz_engine};
 
 } // namespace
 
 extern "C" {
 
 int snaphash_unxz_buffer(snaphash_ctx* x, const void* xz, size_t n, void** out, size_t* out_len)
-try {
-    if (!x || (!xz && n) || !out || !out_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    *out = nullptr;
-    *out_len = 0;
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    snaphash_unpack_stats st{};
-    st.struct_size = sizeof st;
-    st.gz_bytes = n;
-    std::vector<uint8_t> o;
-    const int rc = unxz_engine(x, c, (const uint8_t*)xz, n, o, false, st);
-    c->ev_used = 0;
-    st.tar_bytes = o.size();
-    st.wall_ms = now_ms() - t_top0_;
-    x->unpack = st;
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(o.size() ? o.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    if (!o.empty()) memcpy(p, o.data(), o.size());
-    *out = p;
-    *out_len = o.size();
-    return SNAPHASH_OK;
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
+{
+    return decode_to_malloc(x, kUnxzCodec, xz, n, out, out_len);
 }
 
 int snaphash_tar_unpack_xz(snaphash_ctx* x, const char* data_tar_xz, const char* target_dir, const char* yaml, size_t yaml_len,
                            snaphash_mismatch* first, uint8_t* archive_digest)
-try {
-    if (!x || !data_tar_xz || !target_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    return tar_unpack_common(x, c, t_top0_, data_tar_xz, target_dir, yaml, yaml_len, first, archive_digest,
-                             [&](const uint8_t* z, size_t n, std::vector<uint8_t>& tar, bool keep_dev, snaphash_unpack_stats& st) {
-                                 return unxz_engine(x, c, z, n, tar, keep_dev, st);
-                             });
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
+{
+    return tar_unpack_entry(x, kUnxzCodec, data_tar_xz, target_dir, yaml, yaml_len, first, archive_digest);
 }
 
 int snaphash_unxz_block_device(snaphash_ctx* x, const void* xz, size_t n, size_t block, void* d_dst, size_t dst_len)
@@ -246,7 +165,7 @@ try {
     if (block >= blocks.size() || blocks[block].out_len != dst_len) return fail(x, SNAPHASH_EINVAL, "xz: no such Block, or dst_len is not its uncompressed size");
     const XzBlock& b = blocks[block];
     if (b.out_len > kXzGpuBlockMax) return fail(x, SNAPHASH_EINVAL, "xz: the Block is larger than the kernel takes");
-    if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+    if (int rc = DecodedStream::stream(c)) return lift(x, c, rc);
     HIP_TRY(c, c->xz.ensure(b.in_len, 1));
     HIP_TRY(c, hipMemcpyAsync(c->xz.d_in.data(), (const uint8_t*)xz + b.in_off, b.in_len, hipMemcpyHostToDevice, c->f_stream));
     c->xz.blk.h[0] = XzGpuBlock{0, b.in_len, 0, b.out_len, b.dict_size, (uint32_t)kXzBad};
@@ -258,23 +177,6 @@ try {
     if (c->xz.blk.h[0].status != kXzOk) return fail(x, SNAPHASH_EFORMAT, "xz: corrupt block");
     return SNAPHASH_OK;
 } catch (...) { // allocation failure: no C++ exception crosses the C boundary
-    return SNAPHASH_ENOMEM;
-}
-
-int snaphash_crc64_device(snaphash_ctx* x, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n, uint64_t* crcs)
-try {
-    if (!x || (n && (!d_base || !offsets || !lens || !crcs))) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
-    HIP_TRY(c, hipSetDevice(c->device));
-    double ms = 0;
-    const int rc = crc64_ranges_dev(c, (const uint8_t*)d_base, offsets, lens, n, crcs, c->stream, &ms);
-    c->ev_used = 0;
-    x->stats.kernel_ms = ms;
-    x->stats.launches = n ? 2 : 0;
-    end_top(x, t_top0_);
-    return lift(x, c, rc);
-} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
 

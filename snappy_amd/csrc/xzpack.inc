@@ -13,9 +13,6 @@
 
 namespace {
 
-int crc64_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint64_t* crcs, hipStream_t s,
-                     double* ms); // unxz.inc
-
 static_assert(kXzEncBlockMax == kXzGpuBlockMax, "every Block this side writes is one the install side's kernel takes");
 
 // the producer's slot size, cut down to whole Blocks
@@ -112,7 +109,7 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), total, hipMemcpyDeviceToHost, zs));
     // the Blocks' Checks, from the staged bytes in HBM (it waits for the stream: the piece is back when it returns)
     double crc_ms = 0;
-    const int rc = crc64_ranges_dev(c, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+    const int rc = crc_ranges_dev(c, 0, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
     if (rc) return rc;
     if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
         float chains = 0, concat = 0, sum = 0, longest = 0;

@@ -10,7 +10,7 @@ import tarfile
 
 import pytest
 
-from snappy_amd import Context, _lib, clickdeb
+from snappy_amd import Context, _lib, clickdeb, getHashes
 from test_gpu_unpack import corpus, make_tree, tree_view
 
 pytestmark = pytest.mark.gpu
@@ -172,6 +172,44 @@ def test_unpack_bz2_verify_matches_the_gz_path(snaphash_mode, tmp_path, umask_02
         mb, _ = c.tar_unpack_bz2(arc_bz, str(tmp_path / "ba"), y_gz)
         assert mg is not None and mb == mg
         assert clickdeb.UnpackBz2(arc_bz, str(tmp_path / "cd"), y_bz, ctx=c) is None
+
+
+def flip_digest(yaml, name):
+    """hashes.yaml with the last hex digit of `name`'s sha512 changed."""
+    lines = yaml.split(b"\n")
+    k = next(j for j in range(lines.index(b"- name: " + name.encode()), len(lines)) if lines[j].startswith(b"  sha512: "))
+    lines[k] = lines[k][:-1] + (b"0" if lines[k][-1:] != b"0" else b"1")
+    return b"\n".join(lines)
+
+
+def test_verify_reads_the_stream_two_pieces_left_in_hbm(snaphash_mode, tmp_path, umask_022):
+    """The decoded stream's copy in HBM across pieces: more than 4 MiB of compressed bytes with the staging size of
+    test_small_staging_forces_pieces take two pieces, so under FLAG_GPU_ONLY the second piece's blocks are written behind
+    the first's while Verify's copy is kept (bunzip2_batch with a base that is not 0).  Level 1: a block is 100 000
+    bytes, and runs in random bytes are too rare for RLE1 to change that.  Two pieces: a piece is never under 4 MiB
+    (unbz2.inc, P in bunzip2_engine: max(staging, 4 MiB)), which the bounds on len(z) below rely on.  The copy in HBM is
+    read back under FLAG_GPU_ONLY, where every member is hashed by the kernels; the default configuration hashes the
+    members on host threads wherever 8 or more cores are usable, and checks the same digests from host memory."""
+    from test_gpu_inflate_edges import tar_of
+    files = {"r%d" % k: corpus("random", 1 << 20, seed=20 + k) for k in range(5)}
+    files["notes"] = corpus("text", 3000, seed=30)
+    raw = tar_of(files)
+    z = bz2.compress(raw, 1)
+    assert bz2.decompress(z) == raw and 4 << 20 < len(z) <= 8 << 20
+    arc = str(tmp_path / "data.tar.bz2")
+    with open(arc, "wb") as f:
+        f.write(z)
+    with Context(device=0, staging_bytes=1 << 20) as c:
+        assert c.tar_unpack_bz2(arc, str(tmp_path / "plain"))[0] is None
+        assert {k: (tmp_path / "plain" / k).read_bytes() for k in files} == files
+        yaml = getHashes(str(tmp_path / "plain"), arc, c)
+        assert c.tar_unpack_bz2(arc, str(tmp_path / "verified"), yaml)[0] is None
+        st = check_stats(c, snaphash_mode, raw, z)
+        assert st["members"] == len(files) and st["segments"] >= len(raw) // 100000, st
+        if snaphash_mode == "gpu_only":
+            assert st["gpu_segments"] == st["segments"] and st["host_bytes"] == 0, st
+        mis, _ = c.tar_unpack_bz2(arc, str(tmp_path / "tampered"), flip_digest(yaml, "notes"))
+        assert mis is not None and mis[1] == "notes", mis
 
 
 def test_dotdot_member_is_econtent_and_stays_inside(snaphash_mode, tmp_path):

@@ -221,7 +221,7 @@ def tar_of(files):
 
 
 def test_edge_streams_through_tar_unpack_with_verify(snaphash_mode, tmp_path, umask_022):
-    """gpu_fill_concat with keep_dev and ensure_fout: the decoded bytes stay in HBM for Verify while d_out grows and is
+    """gpu_fill_concat with keep_dev and DecodedStream::reserve_dev: the decoded bytes stay in HBM for Verify while d_out grows and is
     copied, piece after piece with the window carried along (pieces of 64 KiB); the archives have the shapes of items
     5 (segments at and over the slot capacity) and 6 (stored blocks no piece holds) and plain short segments."""
     files = {"text": E.text(2500000, 50), "blob": E.noise(300000, 51), "zeros": bytes(100000), "empty": b"", "x/y": b"deep\n"}

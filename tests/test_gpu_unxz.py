@@ -14,8 +14,9 @@ import tarfile
 import pytest
 
 import xz_cases as X
-from snappy_amd import Context, _lib, clickdeb
-from test_gpu_bunzip2 import _yaml_for, tar_bytes, umask_022  # noqa: F401 (umask_022 is a fixture)
+from snappy_amd import Context, _lib, clickdeb, getHashes
+from test_gpu_bunzip2 import _yaml_for, flip_digest, tar_bytes, umask_022  # noqa: F401 (umask_022 is a fixture)
+from test_gpu_inflate_edges import tar_of
 from test_gpu_unpack import corpus, make_tree, tree_view
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +138,36 @@ def test_unpack_xz_verify_matches_the_gz_path(snaphash_mode, tmp_path, umask_022
         mx, _ = c.tar_unpack_xz(arc_xz, str(tmp_path / "xa"), y_gz)
         assert mg is not None and mx == mg
         assert clickdeb.UnpackXz(arc_xz, str(tmp_path / "cd"), y_xz, ctx=c) is None
+
+
+def test_verify_reads_a_host_block_between_kernel_blocks(snaphash_mode, tmp_path, umask_022):
+    """The decoded stream's copy in HBM where its bytes come from both sides: three Blocks, the middle one over the
+    kernel's cap (a host thread decodes it and its bytes are copied up between the two the kernel wrote in place), and
+    members `a` and `big` that each lie across a Block boundary.  Verify hashes the members out of HBM under
+    FLAG_GPU_ONLY; the default configuration decodes every Block on host threads and, wherever 8 or more cores are
+    usable, hashes the members there too: it checks the same digests from host memory."""
+    files = {"a": corpus("text", 100000, 11), "big": bytes(GPU_BLOCK_MAX + 4096), "c": corpus("text", 100000, 12)}
+    raw = tar_of(files)
+    cuts = [0, 65536, 65536 + GPU_BLOCK_MAX + 512, len(raw)]
+    a0, big0 = 512, 512 + 100352 + 512  # where the members' bytes begin in the tar stream
+    assert raw[a0:a0 + 100000] == files["a"] and a0 < cuts[1] < a0 + 100000
+    assert raw[big0:big0 + 8] == bytes(8) and big0 < cuts[2] < big0 + len(files["big"]) and cuts[2] < len(raw) <= cuts[2] + GPU_BLOCK_MAX
+    z = X.xz_file([X.raw_lzma2(raw[cuts[k]:cuts[k + 1]], dict_size=1 << 16) for k in range(3)], X.CHECK_CRC64)
+    assert lzma.decompress(z) == raw
+    arc = str(tmp_path / "data.tar.xz")
+    with open(arc, "wb") as f:
+        f.write(z)
+    with Context(device=0) as c:
+        assert c.tar_unpack_xz(arc, str(tmp_path / "plain"))[0] is None
+        assert {k: (tmp_path / "plain" / k).read_bytes() for k in files} == files
+        yaml = getHashes(str(tmp_path / "plain"), arc, c)
+        assert c.tar_unpack_xz(arc, str(tmp_path / "verified"), yaml)[0] is None
+        st = check_stats(c, snaphash_mode, raw, z, 3, host_bytes=cuts[2] - cuts[1])
+        if snaphash_mode == "gpu_only":
+            assert st["gpu_segments"] == 2, st
+        for name in ("a", "big"):
+            mis, _ = c.tar_unpack_xz(arc, str(tmp_path / ("tampered_" + name)), flip_digest(yaml, name))
+            assert mis is not None and mis[1] == name, (name, mis)
 
 
 def test_dotdot_member_is_econtent_and_stays_inside(snaphash_mode, tmp_path):
