@@ -350,6 +350,27 @@ void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out
 int snaphash_deflate_codes_device(snaphash_ctx *ctx, const void *d_freq, size_t n_tables, uint32_t n_syms, uint32_t max_bits,
                                   void *d_lens, void *d_codes, void *d_rounds);
 
+/* The .xz encoder's three kernels alone, on the caller's HBM: what snaphash_xz_buffer / snaphash_tar_create_xz run for one
+ * staged piece d_in[0..n) (the same steps in the same order, in a routine of this entry's own), cut
+ * into Blocks of block_size bytes (as in snaphash_xz_buffer; the last Block may be short) -- lzma_chains_kernel,
+ * lzma2_chunks_kernel in launches of launch_chunks chunks (0: the producer's 2048, the most allowed), the results back to
+ * the host, every Block's layout, the chunks' places up to the device, lzma2_concat_kernel.  With nch = ceil(n / 65536):
+ *   d_prev, d_cand   n uint32 each: the hash chains (Block-relative, 0xffffffff for none) and the candidates
+ *                    (length << 22 | distance - 1, 0 for none)
+ *   d_slots          nch * 65600 bytes: every chunk's coder output from its slot's first byte (what does not fit is
+ *                    counted, not stored)
+ *   d_res            nch uint32: a chunk's compressed size, or 0x80000000 for one written uncompressed
+ *   d_dst            nch uint64: where a chunk's header goes in d_out
+ *   d_out            out_cap >= n + nch * 64 + 64 bytes: the Blocks one after another, chunk headers, bodies and each
+ *                    Block's end byte in place.  Block headers, Block Padding and Checks are NOT written: those bytes
+ *                    stay what the caller put there.
+ * block_total (host, may be NULL): a uint64 a Block, its bytes in d_out (header, data, padding, Check).  No byte outside
+ * the six arrays is written.  SNAPHASH_EINVAL: a refused block size, launch_chunks > 2048, out_cap too small, a null
+ * pointer with n > 0.  n == 0 does nothing.  Synchronous. */
+int snaphash_xzenc_stages_device(snaphash_ctx *ctx, const void *d_in, size_t n, uint64_t block_size, uint32_t launch_chunks,
+                                 void *d_prev, void *d_cand, void *d_slots, void *d_res, void *d_dst, void *d_out, size_t out_cap,
+                                 uint64_t *block_total);
+
 /* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
 
 typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack, or of the

@@ -51,6 +51,8 @@ EXPORTS = [
     "snaphash_snap_get_stats",
     # the compressor's code construction alone
     "snaphash_deflate_codes_device",
+    # the .xz encoder's kernels alone
+    "snaphash_xzenc_stages_device",
 ]
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
@@ -232,6 +234,7 @@ def lib():
     L.snaphash_tar_unpack_xz.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_crc64_device.argtypes = [vp, vp, vp, vp, sz, vp]
     L.snaphash_unxz_block_device.argtypes = [vp, vp, sz, sz, vp, sz]
+    L.snaphash_xzenc_stages_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, sz, u64p]
     L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.snaphash_snap_close.argtypes = [vp]
     L.snaphash_snap_close.restype = None
@@ -552,6 +555,16 @@ class Context:
         the Block's uncompressed size.  Its Check is not taken."""
         xz = bytes(xz)
         self._check(lib().snaphash_unxz_block_device(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz), block, d_dst, dst_len))
+
+    def xzenc_stages_device(self, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst, d_out, out_cap):
+        """The .xz encoder's chain, chunk and concatenation kernels over d_in[0..n) in the caller's HBM (device addresses
+        as ints; sizes as snaphash.h states them), the chunks in launches of launch_chunks (0: the producer's).  Block
+        headers, padding and Checks are not written.  -> every Block's total bytes in d_out."""
+        bs = block_size or 1 << 20
+        tot = (ctypes.c_uint64 * max((n + bs - 1) // bs, 1))()
+        self._check(lib().snaphash_xzenc_stages_device(self._h, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst,
+                                                       d_out, out_cap, tot))
+        return list(tot[:(n + bs - 1) // bs])
 
     def crc64_device(self, d_base, offsets, lens):
         """CRC-64/XZ of byte ranges resident in HBM.  d_base: device address (int); offsets / lens: contiguous numpy

@@ -541,6 +541,43 @@ struct XzEncInfo {
     std::vector<uint32_t> res; // every chunk's result, in order
 };
 
+// One Block through the three steps, as the kernels leave their arrays: prev and cand (blen words each, Block-relative),
+// res and dst (a word a chunk; dst relative to the Block's first byte) and slots (kXzEncSlot bytes a chunk: the coder's
+// output, nothing else written).  head: 1 << kXzEncHashBits entries of scratch; probs: kXzEncProbs.
+template <class OPS>
+inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* cand, uint32_t* head, uint16_t* probs,
+                                           uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops)
+{
+    const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
+    xzenc_chains_host(blk, blen, prev, head);
+    for (uint32_t k = 0; k < nch; ++k) {
+        const uint32_t cs = k * kXzEncChunk, ce = std::min(blen, cs + kXzEncChunk);
+        for (uint32_t p = cs; p < ce; ++p) cand[p] = xzenc_find(blk, prev, p, ce);
+        for (uint32_t i = 0; i < kXzEncProbs; ++i) probs[i] = (uint16_t)kLzmaProbInit;
+        res[k] = xzenc_chunk(blk, cs, ce, cand, probs, slots + (size_t)k * kXzEncSlot, kXzEncSlot, ops);
+    }
+    return xzenc_block_layout(res, nch, blen, dst);
+}
+// what lzma2_concat_kernel writes of a Block that begins at q: chunk headers, bodies and the end byte
+inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t* res, const uint64_t* dst, const uint8_t* slots, uint8_t* q)
+{
+    const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
+    for (uint32_t k = 0; k < nch; ++k) {
+        const uint32_t cs = k * kXzEncChunk, usize = std::min(blen, cs + kXzEncChunk) - cs;
+        const bool stored = res[k] == kXzEncStored;
+        const uint32_t h = xzenc_chunk_header(q + dst[k], k == 0, usize, res[k]), len = stored ? usize : res[k];
+        memcpy(q + dst[k] + h, stored ? blk + cs : slots + (size_t)k * kXzEncSlot, len);
+        if (k + 1 == nch) q[dst[k] + h + len] = 0;
+    }
+}
+// what the host writes of a Block that begins at q: header, Block Padding, Check
+inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, uint64_t crc)
+{
+    xzenc_block_header(q, L.data, blen, dict_byte);
+    for (uint64_t z = L.hdr + L.data; z < L.check_at; ++z) q[z] = 0;
+    xzenc_le64(q + L.check_at, crc);
+}
+
 // The whole file on this thread, through the routines the kernels run.  crc64: the Check of a Block's bytes.  false: the
 // block size is not one the format decisions allow.
 template <class OPS, class CRC>
@@ -555,7 +592,7 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std
     std::vector<uint32_t> prev, cand, head(1u << kXzEncHashBits), res;
     std::vector<uint64_t> dst;
     std::vector<uint16_t> probs(kXzEncProbs);
-    std::vector<std::vector<uint8_t>> body;
+    std::vector<uint8_t> slots;
     for (uint64_t b0 = 0; b0 < n; b0 += block_size) {
         const uint8_t* blk = data + b0;
         const uint32_t blen = (uint32_t)std::min<uint64_t>(block_size, n - b0);
@@ -564,31 +601,19 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std
         cand.resize(blen);
         res.resize(nch);
         dst.resize(nch);
-        body.resize(nch);
-        xzenc_chains_host(blk, blen, prev.data(), head.data());
-        for (uint32_t k = 0; k < nch; ++k) {
-            const uint32_t cs = k * kXzEncChunk, ce = std::min(blen, cs + kXzEncChunk);
-            for (uint32_t p = cs; p < ce; ++p) cand[p] = xzenc_find(blk, prev.data(), p, ce);
-            for (uint16_t& p : probs) p = (uint16_t)kLzmaProbInit;
-            body[k].resize(kXzEncSlot);
-            res[k] = xzenc_chunk(blk, cs, ce, cand.data(), probs.data(), body[k].data(), kXzEncSlot, ops);
-            if (info) {
+        slots.resize((size_t)nch * kXzEncSlot);
+        const XzEncBlockLayout L = xzenc_block_stages(blk, blen, prev.data(), cand.data(), head.data(), probs.data(), res.data(), dst.data(),
+                                                      slots.data(), ops);
+        if (info)
+            for (uint32_t k = 0; k < nch; ++k) {
                 info->chunks++;
                 info->stored += res[k] == kXzEncStored;
                 info->res.push_back(res[k]);
             }
-        }
-        const XzEncBlockLayout L = xzenc_block_layout(res.data(), nch, blen, dst.data());
         const size_t o = out.size();
         out.resize(o + L.total, 0);
-        uint8_t* q = out.data() + o;
-        xzenc_block_header(q, L.data, blen, dict_byte);
-        for (uint32_t k = 0; k < nch; ++k) {
-            const uint32_t cs = k * kXzEncChunk, usize = std::min(blen, cs + kXzEncChunk) - cs;
-            const uint32_t h = xzenc_chunk_header(q + dst[k], k == 0, usize, res[k]);
-            memcpy(q + dst[k] + h, res[k] == kXzEncStored ? blk + cs : body[k].data(), res[k] == kXzEncStored ? usize : res[k]);
-        }
-        xzenc_le64(q + L.check_at, crc64(blk, (uint64_t)blen));
+        xzenc_block_frame(out.data() + o, L, blen, dict_byte, crc64(blk, (uint64_t)blen));
+        xzenc_block_place(blk, blen, res.data(), dst.data(), slots.data(), out.data() + o);
         recs.push_back(XzEncRecord{L.unpadded, blen});
     }
     xzenc_index_footer(recs, out);

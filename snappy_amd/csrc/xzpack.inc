@@ -149,6 +149,49 @@ int xz_finish(GzPipe& g, uint8_t archive_digest[64])
     return g.write_err;
 }
 
+// The producer's kernel sequence once more, for snaphash_xzenc_stages_device: xz_process_slot's steps in its order on a
+// caller's buffers, without its events and its trace line.  (A copy, not a shared routine: with the sequence shared, the
+// producer's call measured above the spread of its parent's on one of three corpora -- DESIGN.md sec. 18 -- so its loop
+// stays as it was.)  h_res / h_dst: a word a chunk of host memory.  launch_chunks: 0 for kXzEncLaunchChunks.  The concat
+// kernel is queued on zs, not waited for.
+struct XzEncStageBufs {
+    uint32_t *d_prev, *d_cand;
+    uint8_t* d_slots;
+    uint32_t *d_res, *h_res;
+    uint64_t *d_dst, *h_dst;
+    uint8_t* d_out;
+    uint64_t out_cap;
+};
+int xz_encode_stages(DevCtx* c, const uint8_t* d_in, uint64_t n, uint64_t bs, uint32_t launch_chunks, const XzEncStageBufs& b, hipStream_t zs,
+                     std::vector<XzEncBlockLayout>& lay)
+{
+    if (launch_chunks == 0) launch_chunks = kXzEncLaunchChunks;
+    const uint32_t nch = (uint32_t)((n + kXzEncChunk - 1) / kXzEncChunk), cpb = (uint32_t)(bs / kXzEncChunk);
+    const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
+    HIP_TRY(c, launch_lzma_chains(d_in, n, (uint32_t)bs, b.d_prev, zs));
+    for (uint32_t c0 = 0; c0 < nch; c0 += launch_chunks)
+        HIP_TRY(c, launch_lzma2_chunks(d_in, n, (uint32_t)bs, b.d_prev, b.d_cand, b.d_slots, b.d_res, c0, std::min(launch_chunks, nch - c0), zs));
+    HIP_TRY(c, hipMemcpyAsync(b.h_res, b.d_res, (size_t)nch * 4, hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    lay.resize(nblk);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < nblk; ++k) {
+        const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
+        const uint32_t ch0 = k * cpb, cn = (uint32_t)((blen + kXzEncChunk - 1) / kXzEncChunk);
+        for (uint32_t i = 0; i < cn; ++i) {
+            const uint32_t usize = (uint32_t)std::min<uint64_t>(kXzEncChunk, blen - (uint64_t)i * kXzEncChunk);
+            if (!xzenc_res_valid(usize, b.h_res[ch0 + i])) return fail(c, SNAPHASH_EDEVICE, "xz: the chunk kernel reported an impossible size");
+        }
+        lay[k] = xzenc_block_layout(b.h_res + ch0, cn, blen, b.h_dst + ch0);
+        for (uint32_t i = 0; i < cn; ++i) b.h_dst[ch0 + i] += total;
+        total += lay[k].total;
+    }
+    if (total > b.out_cap) return fail(c, SNAPHASH_EDEVICE, "xz: a slot's output outgrew its buffer");
+    HIP_TRY(c, hipMemcpyAsync(b.d_dst, b.h_dst, (size_t)nch * 8, hipMemcpyHostToDevice, zs));
+    HIP_TRY(c, launch_lzma2_concat(d_in, n, (uint32_t)bs, b.d_slots, b.d_res, b.d_dst, b.d_out, nch, zs));
+    return SNAPHASH_OK;
+}
+
 const TarCodec kXzCodec = {".xz", false, xz_slot_bytes, ensure_xzenc, xz_header, xz_process_slot, xz_finish};
 
 } // namespace
@@ -207,6 +250,36 @@ try {
     *xz_len = out.size();
     return SNAPHASH_OK;
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_xzenc_stages_device(snaphash_ctx* x, const void* d_in, size_t n, uint64_t block_size, uint32_t launch_chunks, void* d_prev,
+                                 void* d_cand, void* d_slots, void* d_res, void* d_dst, void* d_out, size_t out_cap, uint64_t* block_total)
+try {
+    if (!x || (n && (!d_in || !d_prev || !d_cand || !d_slots || !d_res || !d_dst || !d_out))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
+    if (launch_chunks > kXzEncLaunchChunks) return fail(x, SNAPHASH_EINVAL, "xz: a launch holds at most 2048 chunks");
+    if (n > ((uint64_t)0x7fffffffu - 1) * kXzEncChunk) return fail(x, SNAPHASH_EINVAL, "xz: the piece is too long");
+    if (n == 0) return SNAPHASH_OK;
+    if (out_cap < XzEncBufs::out_cap(n)) return fail(x, SNAPHASH_EINVAL, "xz: out_cap is smaller than a piece of n bytes may need");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nch = (size_t)((n + kXzEncChunk - 1) / kXzEncChunk);
+    std::vector<uint32_t> h_res(nch);
+    std::vector<uint64_t> h_dst(nch);
+    const XzEncStageBufs sb = {(uint32_t*)d_prev, (uint32_t*)d_cand, (uint8_t*)d_slots, (uint32_t*)d_res, h_res.data(),
+                               (uint64_t*)d_dst, h_dst.data(), (uint8_t*)d_out, out_cap};
+    std::vector<XzEncBlockLayout> lay;
+    const int rc = xz_encode_stages(c, (const uint8_t*)d_in, n, block_size, launch_chunks, sb, c->stream, lay);
+    const hipError_t e = hipStreamSynchronize(c->stream); // (h_dst is read by a copy still in flight)
+    if (rc) return lift(x, c, rc);
+    HIP_TRY(c, e);
+    if (block_total)
+        for (size_t k = 0; k < lay.size(); ++k) block_total[k] = lay[k].total;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
 

@@ -4,7 +4,10 @@ compiled for the host by tests/xzenc_host_harness.cpp) over every input of tests
 tests/xz_host_harness.cpp, whose histogram shows that each shape -- matches, every rep, short reps, matched literals,
 every control byte -- really occurred; the range encoder is held against xz_cases.py's Python one; xz_plan and the xz
 tool judge the container; and a stand-alone program runs the model under ASan/UBSan.  The kernels that run the same
-header are checked in tests/test_gpu_xzenc.py."""
+header are checked in tests/test_gpu_xzenc.py, and stage by stage -- against the arrays of stages() below -- in
+tests/test_gpu_xzenc_edges.py; the tests from test_the_models_stages_make_the_models_file on show that the inputs made for
+that (last Blocks of a few bytes, tiles of many hash groups, two values of one hash, distances up to a 4 MiB Block's
+end, chunks on the stored / LZMA line at both places that decide it) are what their names say."""
 import ctypes
 import lzma
 import os
@@ -12,6 +15,7 @@ import random
 import struct
 import subprocess
 
+import numpy as np
 import pytest
 
 import xz_cases as X
@@ -23,9 +27,11 @@ DEC_HARNESS = os.path.join(ROOT, "tests", "xz_host_harness.cpp")
 # the decoder harness's histogram (xz_host_harness.cpp, test_xz_host.py)
 H_LIT, H_MATCHED_LIT, H_MATCH, H_REP, H_SHORT_REP, H_COPY, H_CTL, H_N = 0, 1, 2, 3, 7, 10, 26, 300
 # the encoder harness's statistics (xzenc_host_harness.cpp)
-S_LIT, S_MATCHED_LIT, S_MATCH, S_REP, S_SHORT_REP, S_ENDS, S_CROSSES, S_CHUNKS, S_STORED, S_WATCH, S_WATCH_BYTES, S_REP0_273, S_MAX_DIST, S_N = (
-    0, 1, 2, 3, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)
+S_LIT, S_MATCHED_LIT, S_MATCH, S_REP, S_SHORT_REP, S_ENDS, S_CROSSES, S_CHUNKS, S_STORED, S_WATCH, S_WATCH_BYTES, S_REP0_273, S_MAX_DIST, S_MAX_SLOT, S_CODED, S_N = (
+    0, 1, 2, 3, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18)
 STORED = 0x80000000
+SLOT = E.CHUNK + 64  # kXzEncSlot
+FILL = 0xA5          # what stages() puts where the encoder writes nothing
 P = ctypes.POINTER
 
 
@@ -44,7 +50,46 @@ def load_enc(so_dir):
     L.xe_plan.restype = ctypes.c_int64
     L.xe_dict_byte.argtypes = [ctypes.c_uint64]
     L.xe_dict_byte.restype = ctypes.c_uint32
+    vp = ctypes.c_void_p
+    L.xe_stages.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.xe_stages.restype = ctypes.c_int64
+    L.xe_finish.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, vp, vp, ctypes.c_size_t, P(ctypes.c_size_t)]
+    L.xe_finish.restype = ctypes.c_void_p
+    L.xe_hash.argtypes = [ctypes.c_uint32]
+    L.xe_hash.restype = ctypes.c_uint32
     return L
+
+
+def out_cap(n):
+    """XzEncBufs::out_cap: what the Blocks of a piece of n bytes take at most."""
+    return n + (n + E.CHUNK - 1) // E.CHUNK * 64 + 64
+
+
+def stages(L, data, block_size):
+    """The model stage by stage, as the kernels leave their arrays: prev, cand (uint32 a byte, Block-relative), res (uint32
+    a chunk), dst (uint64 a chunk), slots and out (bytes, FILL where nothing is written), total (bytes of out a Block)."""
+    n, bs = len(data), block_size or 1 << 20
+    nch, nblk = (n + E.CHUNK - 1) // E.CHUNK, (n + bs - 1) // bs
+    a = {"prev": np.full(n, 0xA5A5A5A5, np.uint32), "cand": np.full(n, 0xA5A5A5A5, np.uint32), "res": np.full(nch, 0xA5A5A5A5, np.uint32),
+         "dst": np.full(nch, 0xA5A5A5A5A5A5A5A5, np.uint64), "slots": np.full(nch * SLOT, FILL, np.uint8), "out": np.full(out_cap(n), FILL, np.uint8),
+         "total": np.zeros(max(nblk, 1), np.uint64)}
+    used = L.xe_stages(data, n, block_size, *(a[k].ctypes.data for k in ("prev", "cand", "res", "slots", "dst", "out")), out_cap(n),
+                       a["total"].ctypes.data)
+    assert 0 <= used <= out_cap(n)
+    a["total"] = a["total"][:nblk]
+    a["used"] = used
+    return a
+
+
+def finish(L, data, block_size, res, out, used):
+    """The file from the kernels' (or the model's) out: the host's part -- headers, padding, Checks, Index -- added."""
+    res, out = np.ascontiguousarray(res, np.uint32), np.ascontiguousarray(out, np.uint8)
+    n = ctypes.c_size_t()
+    p = L.xe_finish(data, len(data), block_size, res.ctypes.data, out.ctypes.data, used, ctypes.byref(n))
+    assert p
+    z = ctypes.string_at(p, n.value)
+    L.xe_free(p)
+    return z
 
 
 def encode(L, data, block_size):
@@ -330,3 +375,139 @@ def test_xzenc_host_model_under_asan_and_ubsan(tmp_path):
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
     assert out.stdout.split() == ["ok"] * len(E.cases())
+
+
+# ---- the model stage by stage, and the inputs made for the kernels' own edges ---------------------------------------------
+
+
+def test_the_models_stages_make_the_models_file(files, xe):
+    """xe_stages (what test_gpu_xzenc_edges.py holds the kernels' arrays against) is the model of xzenc_host and no
+    other: its out, with the host's part added, is the file; out differs from the file's Blocks only where the host
+    writes (there it is still FILL), nothing lies behind the last Block, and an LZMA chunk's slot ends with its csize."""
+    for name, (z, data, bs) in files.items():
+        if name == "block_default":
+            continue  # (1 MiB and 100 bytes: nothing the others do not show)
+        a = stages(xe, data, bs)
+        assert a["used"] == int(a["total"].sum()) == len(z) - 12 - (len(z) - plan(xe, z)[-1][3] - 8 if len(data) else 20), name
+        assert finish(xe, data, bs, a["res"], a["out"], a["used"]) == z, name
+        body = np.frombuffer(z, np.uint8)[12:12 + a["used"]]
+        differs = a["out"][:a["used"]] != body
+        assert (a["out"][:a["used"]][differs] == FILL).all() and (a["out"][a["used"]:] == FILL).all(), name
+        for ci, r in enumerate(a["res"]):
+            if r != STORED:
+                assert (a["slots"][ci * SLOT + int(r):(ci + 1) * SLOT] == FILL).all(), (name, ci)
+        if len(data):
+            assert (a["prev"] != 0xA5A5A5A5).all() and (a["cand"] != 0xA5A5A5A5).all(), name  # every position has both
+
+
+def test_tails_are_blocks_of_their_own_and_their_last_positions_do_not_hash(files, xe):
+    for k in E.TAILS:
+        z, data, bs = files["tails_%d" % k]
+        assert [b[2] for b in plan(xe, z)] == [E.CHUNK, k]
+        prev = stages(xe, data, bs)["prev"][E.CHUNK:]
+        assert len(prev) == k and (prev[max(k - 3, 0):] == E.NONE).all(), k  # p + 4 <= blen fails
+        if k > 4:  # the last position that does hash has company: a kernel that dropped it would show
+            assert prev[k - 4] != E.NONE and data[E.CHUNK + int(prev[k - 4]):][:4] == data[-4:], (k, prev[k - 4])
+        else:
+            assert (prev == E.NONE).all()
+    assert (64 - 4) // E.TILE == 0 and (65 - 4) // E.TILE == 0 and 64 // E.TILE == 1  # 65: a second tile, none of it hashes
+
+
+def _tile_hashes(xe, data, t0):
+    """The hashes of the positions of tile t0 that have four bytes."""
+    return [xe.xe_hash(int.from_bytes(data[p:p + 4], "little")) for p in range(t0, min(t0 + E.TILE, len(data) - 3))]
+
+
+def test_tile_groups_has_tiles_of_3_to_33_hashes_at_every_alignment(files, xe):
+    _, data, bs = files["tile_groups"]
+    _, starts = E.tile_groups()
+    prev = stages(xe, data, bs)["prev"]
+    assert sorted(s % E.TILE for s in starts) == sorted(set(s % E.TILE for s in starts))
+    shared_seen = set()
+    for p, start in zip(E.GROUP_PERIODS, starts):
+        t0 = (start + E.TILE - 1) // E.TILE * E.TILE  # the first tile wholly inside the run
+        assert t0 + E.TILE + 3 <= start + E.GROUP_RUN
+        hs = _tile_hashes(xe, data, t0)
+        shared = sum(1 for h in set(hs) if hs.count(h) > 1)
+        assert len(set(hs)) == p and shared == (p if 2 * p <= E.TILE else E.TILE - p), (p, len(set(hs)), shared)
+        shared_seen.add(shared)
+        for q in range(max(t0, start + p), t0 + E.TILE):  # the nearest earlier position of the same hash: a period back, in or out of the tile
+            assert prev[q] == q - p, (p, q)
+    assert shared_seen == {3, 4, 5, 7, 16, 31, 32}  # (33 hashes in a tile: 31 of them twice)
+    for t0 in range(0, len(data), E.TILE):  # and the tiles where a run begins or ends: a filler's hashes beside a period's
+        hs = _tile_hashes(xe, data, t0)
+        shared_seen.add(sum(1 for h in set(hs) if hs.count(h) > 1))
+    assert len(shared_seen) > 7
+
+
+def test_hash_twins_link_and_do_not_match(files, xe):
+    _, data, bs = files["hash_twins"]
+    a, b = E.twin_values()
+    ia, ib = int.from_bytes(a, "little"), int.from_bytes(b, "little")
+    assert a != b and a[0] != b[0] and xe.xe_hash(ia) == xe.xe_hash(ib) == E.hash32(ia) == E.hash32(ib)
+    r = random.Random(3)
+    for _ in range(200):
+        v = r.getrandbits(32)
+        assert xe.xe_hash(v) == E.hash32(v)
+    st = stages(xe, data, bs)
+    a1, b1, a2, b2 = E.TWIN_AT
+    assert data[a1:a1 + 4] == data[a2:a2 + 4] == a and data[b1:b1 + 4] == data[b2:b2 + 4] == b
+    assert a1 // E.TILE == b1 // E.TILE and b1 - a1 == 8 and a2 // E.TILE + 1 == b2 // E.TILE and b2 - a2 == 8
+    for ta, tb in ((a1, b1), (a2, b2)):
+        assert st["prev"][tb] == ta  # the link is there, and followed ...
+        c = int(st["cand"][tb])
+        assert c == 0 or tb - ((c & 0x3FFFFF) + 1) != ta, (tb, c)  # ... and is no match: none, or one from elsewhere
+    assert st["prev"][a2] == b1 and int(st["cand"][a2]) == (4 << 22 | (a2 - a1 - 1))  # through the twin to the value itself
+
+
+def test_far_dists_reach_the_last_distance_slots_and_the_packing_limit(files, xe):
+    z, data, bs = files["far_dists"]
+    assert len(data) == bs == 4 << 20 and lzma.decompress(z) == data
+    _, where = E.far_dists()
+    assert [d for _, d in where] == list(E.FAR_DISTS) and len(E.FAR_DISTS) == 15
+    for at, d in where:
+        assert data[at:at + 64] == data[at + d:at + d + 64] and 0 not in data[at:at + 64]
+        s, _ = stats(xe, data, bs, watch=d)
+        assert s[S_WATCH] >= 1, d
+    s, res = stats(xe, data, bs, watch=E.FAR_MAX)
+    assert s[S_WATCH] == 1 and s[S_WATCH_BYTES] == 273 and s[S_MAX_DIST] == E.FAR_MAX == 4194031
+    assert s[S_MAX_SLOT] == 43 and len(res) == 64 and STORED not in res  # 2^21 + 2^20 <= 4 194 030 < 2^22: the format's slot 43
+    st = stages(xe, data, bs)
+    assert int(st["cand"][E.FAR_MAX]) == (273 << 22 | (E.FAR_MAX - 1)) and E.FAR_MAX - 1 < 1 << 22
+    assert max(stats(xe, d2, b2)[0][S_MAX_SLOT] for n2, (_, d2, b2) in files.items() if n2 != "far_dists") < 40  # (block_default: 39)
+
+
+def test_margin_cases_sit_on_the_stored_lzma_line(files, xe):
+    """The decision 6 + csize < 3 + usize is made in two places, and S_CODED (the bytes the operations cover) tells which
+    one stored a chunk: all 65 536 for the verdict after the flush, fewer for the give-up inside the loop.  margin_lzma
+    is the last k written as LZMA, margin_stored the first stored one (by the verdict), margin_giveup the first one the
+    loop gives up on, five bytes before its end.  (No k gives csize 65 532, the last LZMA size: the model goes from
+    65 531 to stored.)"""
+    assert E.MARGIN_STORED_K == E.MARGIN_LZMA_K + 1 < E.MARGIN_GIVEUP_K
+    z, data, bs = files["margin_lzma"]
+    s, res = stats(xe, data, bs)
+    assert len(res) == 1 and res[0] != STORED and 65533 - 64 <= res[0] <= 65532, res  # 6 + csize < 3 + 65536
+    assert s[S_CODED] == E.CHUNK and controls(block_payloads(xe, z)[0]) == [0xE0, 0x00]
+    z, data, bs = files["margin_stored"]
+    s, res = stats(xe, data, bs)
+    assert res == [STORED] and s[S_CODED] == E.CHUNK and controls(block_payloads(xe, z)[0]) == [0x01, 0x00]  # the verdict
+    z, data, bs = files["margin_giveup"]
+    s, res = stats(xe, data, bs)
+    assert res == [STORED] and E.CHUNK - 64 <= s[S_CODED] < E.CHUNK, s[S_CODED]  # the give-up, as late as it comes
+    assert controls(block_payloads(xe, z)[0]) == [0x01, 0x00]
+    for k in range(E.MARGIN_STORED_K, E.MARGIN_GIVEUP_K + 8):  # the line is crossed once, and so is the one between the places
+        s, res = stats(xe, E.margin(k), bs)
+        assert res == [STORED] and (s[S_CODED] == E.CHUNK) == (k < E.MARGIN_GIVEUP_K), (k, s[S_CODED])
+
+
+def test_the_smallest_tail_chunk_written_as_lzma(files, xe):
+    z, data, bs = files["tail_min"]
+    _, res = stats(xe, data, bs)
+    assert len(data) == E.CHUNK + E.TAIL_MIN_T and res[1] != STORED and 5 <= res[1] and 6 + res[1] < 3 + E.TAIL_MIN_T, res
+    assert controls(block_payloads(xe, z)[0]) == [0xE0, 0xC0, 0x00]
+    z, data, bs = files["tail_min_less"]
+    _, res = stats(xe, data, bs)
+    assert len(data) == E.CHUNK + E.TAIL_MIN_T - 1 and res[1] == STORED and res[0] != STORED
+    assert controls(block_payloads(xe, z)[0]) == [0xE0, 0x02, 0x00]
+    for t in range(1, E.TAIL_MIN_T):  # TAIL_MIN_T is the smallest
+        assert stats(xe, E.tail_min(t), bs)[1][1] == STORED, t
