@@ -269,10 +269,10 @@ __device__ __forceinline__ void index_segment_across(ChunkLds& L, uint64_t n_in,
 
 // How many bytes at cand equal those at p (at most maxl).  The first eight alone -- most candidates of prose end there --
 // then THIRTY-TWO a step: the four 8-byte compares of a step are independent, so a step costs one LDS round trip where
-// round 3's eight-bytes-a-step loop cost four, and the walk is bound by exactly those round trips (a wave issues an
+// a loop of eight bytes a step costs four, and the walk is bound by exactly those round trips (a wave issues an
 // instruction every ~6 cycles with four waves per SIMD: it waits).  Reads run up to 31 bytes past the match's end: inside
 // the data ring (the look-ahead covers 258 + 8; what lies beyond only ever raises a length that is cut to maxl).
-#if !defined(SNAPHASH_DF_NARROW_EXTEND)
+
 // index of the lowest set bit, 0xFFFFFFFF for 0 (v_ffbl_b32 as the hardware has it: __builtin_ctz of 0 is undefined)
 __device__ __forceinline__ uint32_t ffbl_or_ones(uint32_t x)
 {
@@ -308,20 +308,13 @@ __device__ __forceinline__ uint32_t extend_match(const ChunkLds& L, uint32_t p, 
     }
     return l < maxl ? l : maxl;
 }
-#else // round 3's form, for A/B (make narrow)
-__device__ __forceinline__ uint32_t extend_match(const ChunkLds& L, uint32_t p, uint32_t cand, uint32_t maxl)
-{
-    uint32_t l = 0;
-    while (l < maxl) { // eight bytes a step
-        const uint64_t x = d64(L, p + l) ^ d64(L, cand + l);
-        if (x) { l += (uint32_t)__builtin_ctzll(x) >> 3; break; }
-        l += 8u;
-    }
-    return l < maxl ? l : maxl;
-}
-#endif
 
 // ---- searcher: the best match of one position ------------------------------------------------------------------
+// One form of the search is built.  Tried, measured and removed (the text was last in f65c6d1, each behind a -D of its own):
+// an extension of eight bytes a step (sources 17.0 against 12.1 ms, profiles/r04_deflate_corpora.txt); the walk's decisions
+// as branches (2-3 % slower); the walk before it was pipelined, and one shared extension a batch (6-11 %
+// slower), and two tiles a wave (14-17 % slower) (profiles/r05_deflate_experiments.txt); lanes that stream through a segment's
+// positions instead of a tile a wave (10-20 % slower, profiles/r04_deflate_stream_search.txt).
 __device__ __forceinline__ uint32_t search_position(const ChunkLds& L, const uint8_t* __restrict__ in, uint64_t n_in, uint64_t p64, uint64_t c1, uint32_t depth)
 {
     if (p64 >= c1) return 0u;
@@ -335,75 +328,6 @@ __device__ __forceinline__ uint32_t search_position(const ChunkLds& L, const uin
     // check only ever spares work.
     uint32_t best = kDfMinMatch - 1u, bdist = 0u, left = depth;
     uint32_t cur = p;
-    bool more = true;
-#if defined(SNAPHASH_DF_SHARED_EXTEND) && !defined(SNAPHASH_DF_BRANCHY_WALK)
-    // Round 5 experiment (make sharedext; MEASURED SLOWER, profiles/r05_deflate_experiments.txt): ONE copy of the extension
-    // per batch, shared by the lanes' survivors.  The shipped walk writes "check, extend, update" four times a batch (a
-    // copy per candidate), and a wave runs a copy whenever ANY of its lanes has a candidate that passes its check, which on
-    // prose is nearly always; 3.35 G vector instructions a launch at four cycles each are half of all SIMD cycles
-    // (profiles/r04_targz_text_pmc.json), so fewer copies looked like the lever.  Here a batch is: the four links, the four
-    // check words, the four checks (against the best the batch STARTED with: a check only ever spares work, so an older
-    // best means at most an extension that did not have to be -- the result is the serial walk's), and then a loop in
-    // which every lane extends its next survivor, in order: as many rounds as the lane with the most survivors has.  The
-    // budget is counted as the serial walk counts it: a candidate visited costs one link whether it passed its check or
-    // not, and a cut (good / nice) ends the visit of the rest.  Byte-identical output -- and 6-11 % slower on all three
-    // corpora at every depth (text 9.9 against 9.3 ms per 64 MiB at depth 32, 15.5 against 14.8 at 96): a batch's first
-    // candidates mostly pass (there is no best to check against yet), so the rounds are four anyway, each with its ballot,
-    // its bit scan and its selects on top.
-    while (more && left) {
-        uint32_t c0_ = 0, c1_ = 0, c2_ = 0, c3_ = 0, ncand = 0;
-#define SNAPHASH_DF_LINK(dst)                                                       \
-        {                                                                           \
-            const bool want_ = more && ncand < left;                                \
-            const uint32_t d_ = L.ix.ring[cur & kRingMask];                         \
-            const bool ok_ = want_ && d_ != 0u && p - (cur - d_) <= kDfMaxDist;     \
-            more = want_ ? ok_ : more;                                              \
-            cur = ok_ ? cur - d_ : cur;                                             \
-            dst = ok_ ? cur : 0u;                                                   \
-            ncand += ok_ ? 1u : 0u;                                                 \
-        }
-        SNAPHASH_DF_LINK(c0_) SNAPHASH_DF_LINK(c1_) SNAPHASH_DF_LINK(c2_) SNAPHASH_DF_LINK(c3_)
-#undef SNAPHASH_DF_LINK
-        const uint32_t off = best >= 3u ? best - 3u : 0u;
-        const uint32_t mine = d32(L, p + off);
-        const uint8_t* gb = in + (p64 - p); // the check words come through L1/L2, beside the LDS pipe (round 3)
-        const uint32_t k0 = *reinterpret_cast<const u32_unaligned*>(gb + c0_ + off), k1 = *reinterpret_cast<const u32_unaligned*>(gb + c1_ + off),
-                       k2 = *reinterpret_cast<const u32_unaligned*>(gb + c2_ + off), k3 = *reinterpret_cast<const u32_unaligned*>(gb + c3_ + off);
-        // who passes (bit k: candidate k); without a best of three bytes or more there is nothing to check yet
-        const bool chk = best >= 3u;
-        uint32_t gomask = ((!chk || k0 == mine) ? 1u : 0u) | ((!chk || k1 == mine) ? 2u : 0u) | ((!chk || k2 == mine) ? 4u : 0u) | ((!chk || k3 == mine) ? 8u : 0u);
-        gomask &= (1u << ncand) - 1u;
-        uint32_t kpos = 0; // candidates of the batch this lane has visited
-        bool open = ncand != 0u && left != 0u;
-        while (__builtin_amdgcn_ballot_w64(open) != 0ull) { // (uniform: a round of the shared extension)
-            uint32_t cand = 0, l = 0;
-            bool ext = false;
-            if (open) {
-                const uint32_t rest = gomask >> kpos;
-                const uint32_t skip = rest ? (uint32_t)__builtin_ctz(rest) : ncand - kpos; // candidates that failed their check, up to the next survivor
-                if (rest == 0u || left <= skip) { // no survivor left in the batch, or the budget ends in front of it
-                    left -= left < skip ? left : skip;
-                    open = false;
-                } else {
-                    const uint32_t sidx = kpos + skip;
-                    left -= skip + 1u;
-                    kpos = sidx + 1u;
-                    cand = sidx == 0u ? c0_ : (sidx == 1u ? c1_ : (sidx == 2u ? c2_ : c3_));
-                    ext = true;
-                }
-            }
-            if (ext) {
-                l = extend_match(L, p, cand, maxl);
-                const bool better = l > best;
-                const uint32_t cut = (l >= kDfNice || l >= maxl) ? 0u : ((l >= kDfGood && left > depth / 4u) ? depth / 4u : left);
-                bdist = better ? p - cand : bdist;
-                left = better ? cut : left;
-                best = better ? l : best;
-                open = kpos < ncand && left != 0u;
-            }
-        }
-    }
-#elif !defined(SNAPHASH_DF_BRANCHY_WALK) && !defined(SNAPHASH_DF_UNPIPELINED) // the shipped walk
     // Round 5, the walk as a two-stage pipeline.  A batch is four links -- four DEPENDENT reads of the ring -- then four
     // check words from L2, then the survivors' extensions.  The links of the NEXT batch do not need the candidates of this
     // one (only the budget does, and a link walked in vain costs nothing but itself), so they are walked while this
@@ -426,7 +350,6 @@ __device__ __forceinline__ uint32_t search_position(const ChunkLds& L, const uin
     //   * every candidate of a batch is checked against the best the batch STARTED with (a check only ever spares work, so
     //     an older best means at most an extension that did not have to be).
     // Exactly the serial walk's result.
-    (void)more;
     uint32_t room = kDfMaxDist;
     bool last_dead; // ... of the batch in work: the chain ends inside it
     {
@@ -495,295 +418,9 @@ __device__ __forceinline__ uint32_t search_position(const ChunkLds& L, const uin
     }
 #undef SNAPHASH_DF_LINK
 #undef SNAPHASH_DF_UPDATE
-#elif !defined(SNAPHASH_DF_BRANCHY_WALK) // round 5's walk before the pipeline (make unpipelined, for A/B): check, extend, update written out per candidate
-    // (The inner decisions are selects, not branches: every `if` of a divergent wave costs scalar instructions for the
-    // exec mask -- the kernel issued as many of those as vector instructions -- and only the ones that skip real work
-    // (a candidate that fails its check word, the extension) are worth them.)
-    // (Round 5: the links' bookkeeping in lane masks.  A link is a candidate when the one before it was, the budget wants
-    // it (link k of a batch: k < left) and it leads to a position inside the window -- `ok` of link k implies `ok` of link
-    // k - 1, so "candidate k exists" is ok_k itself and the chain goes on iff the LAST wanted link was there.  The earlier
-    // form carried `more` and a candidate count through every link as vector registers -- a 0/1 select, its conversion
-    // back into a mask, an add and a compare a link: sixteen vector instructions a link where this takes ten.)
-#if defined(SNAPHASH_DF_FRESH_CHECKS)
-    const bool first_alone = false;
-#else
-    bool first_alone = true; // the first batch is ONE link: it finds a best to check the others against (below)
-#endif
-    while (more && left) {
-        const uint32_t lim = first_alone ? 1u : left; // links this batch may take (the first `lim` of its four)
-        uint32_t c0_, c1_, c2_, c3_;
-        bool ok0, ok1, ok2, ok3;
-#define SNAPHASH_DF_LINK(k, dst, okv, prev)                                         \
-        {                                                                           \
-            const uint32_t d_ = L.ix.ring[cur & kRingMask];                         \
-            const uint32_t nxt_ = cur - d_;                                         \
-            okv = (prev) && (k) < lim && p - nxt_ <= kDfMaxDist; /* (kNoLink fails it) */ \
-            cur = nxt_; /* (behind a link that was not taken nothing of this lane's walk is used again: the chain has ended, or the \
-                           budget has -- lim = left, and every candidate visited costs one -- and the ring's index is masked; the \
-                           one-link first batch puts its `cur` back below) */ \
-            dst = okv ? nxt_ : 0u; /* (the check word is loaded whatever ok says: a safe address) */ \
-        }
-        SNAPHASH_DF_LINK(0u, c0_, ok0, true)
-        const uint32_t cur_after0 = cur;
-        SNAPHASH_DF_LINK(1u, c1_, ok1, ok0) SNAPHASH_DF_LINK(2u, c2_, ok2, ok1) SNAPHASH_DF_LINK(3u, c3_, ok3, ok2)
-#undef SNAPHASH_DF_LINK
-        cur = first_alone ? cur_after0 : cur;
-        more = ok3 || (lim == 3u && ok2) || (lim == 2u && ok1) || (lim == 1u && ok0); // (ok3 implies lim >= 4)
-        const uint32_t off = best >= 3u ? best - 3u : 0u;
-        const uint32_t mine = d32(L, p + off);
-        // the candidates' check words come through L1/L2 (the texture path), not from the data ring: the ring's LDS
-        // pipe is what bounds the walk (links, this position's words, the extensions), and the two paths run side by
-        // side (12.6 instead of 14.5 ms per 64 MiB of text)
-        // (round 5: a scalar base and ONE 32-bit offset a load -- the tile's positions share the upper half of their 64-bit
-        // position, a tile never straddles 4 GiB -- where `gb + c + off` was two 64-bit vector additions a candidate)
-        const uint8_t* gb = in + ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((p64 - p) >> 32)) << 32);
-        const uint32_t k0 = *reinterpret_cast<const u32_unaligned*>(gb + (uint32_t)(c0_ + off)), k1 = *reinterpret_cast<const u32_unaligned*>(gb + (uint32_t)(c1_ + off)),
-                       k2 = *reinterpret_cast<const u32_unaligned*>(gb + (uint32_t)(c2_ + off)), k3 = *reinterpret_cast<const u32_unaligned*>(gb + (uint32_t)(c3_ + off));
-        // Round 5: every candidate of a batch is checked against the best the batch STARTED with -- a check only ever spares
-        // work, so an older best means at most an extension that did not have to be -- where a candidate behind one that
-        // raised the best used to fetch two fresh check words from LDS, under three nested branches.  The batch that would
-        // pay for that is the first (no best yet: all four extended), so the first batch is one link.
-#if defined(SNAPHASH_DF_FRESH_CHECKS)
-#define SNAPHASH_DF_GO(cand, chk) (best < 3u || ((off == best - 3u) ? (chk == mine) : (d32(L, cand + best - 3u) == d32(L, p + best - 3u))))
-#else
-        const bool nochk = best < 3u;
-        first_alone = false;
-#define SNAPHASH_DF_GO(cand, chk) (nochk || chk == mine)
-#endif
-#define SNAPHASH_DF_EVAL(okv, cand, chk)                                                                        \
-        if (okv && left) {                                                                                      \
-            --left;                                                                                             \
-            const bool go = SNAPHASH_DF_GO(cand, chk);                                                          \
-            if (go) {                                                                                           \
-                const uint32_t l = extend_match(L, p, cand, maxl);                                              \
-                if (l > best) { /* (a branch: most extensions end short of the best, and the update is a dozen instructions) */ \
-                    best = l;                                                                                   \
-                    bdist = p - cand;                                                                           \
-                    left = (l >= kDfNice || l >= maxl) ? 0u : ((l >= kDfGood && left > depth / 4u) ? depth / 4u : left); \
-                }                                                                                               \
-            }                                                                                                   \
-        }
-        SNAPHASH_DF_EVAL(ok0, c0_, k0) SNAPHASH_DF_EVAL(ok1, c1_, k1) SNAPHASH_DF_EVAL(ok2, c2_, k2) SNAPHASH_DF_EVAL(ok3, c3_, k3)
-#undef SNAPHASH_DF_EVAL
-#undef SNAPHASH_DF_GO
-    }
-#else // round 3's branches (make branchy, for A/B)
-    while (more && left) {
-        uint32_t c0_ = 0, c1_ = 0, c2_ = 0, c3_ = 0, ncand = 0;
-#define SNAPHASH_DF_LINK(dst)                                                       \
-        if (more && ncand < left) {                                                 \
-            const uint32_t d_ = L.ix.ring[cur & kRingMask];                         \
-            if (d_ == 0u || p - (cur - d_) > kDfMaxDist) more = false;              \
-            else { cur -= d_; dst = cur; ++ncand; }                                 \
-        }
-        SNAPHASH_DF_LINK(c0_) SNAPHASH_DF_LINK(c1_) SNAPHASH_DF_LINK(c2_) SNAPHASH_DF_LINK(c3_)
-#undef SNAPHASH_DF_LINK
-        const uint32_t off = best >= 3u ? best - 3u : 0u;
-        const uint32_t mine = d32(L, p + off);
-        // the candidates' check words come through L1/L2 (the texture path), not from the data ring: the ring's LDS
-        // pipe is what bounds the walk (links, this position's words, the extensions), and the two paths run side by
-        // side (12.6 instead of 14.5 ms per 64 MiB of text)
-        const uint8_t* gb = in + (p64 - p);
-        const uint32_t k0 = *reinterpret_cast<const u32_unaligned*>(gb + c0_ + off), k1 = *reinterpret_cast<const u32_unaligned*>(gb + c1_ + off),
-                       k2 = *reinterpret_cast<const u32_unaligned*>(gb + c2_ + off), k3 = *reinterpret_cast<const u32_unaligned*>(gb + c3_ + off);
-#define SNAPHASH_DF_EVAL(k, cand, chk)                                                                         \
-        if (k < ncand && left) {                                                                                \
-            --left;                                                                                             \
-            bool go = true;                                                                                     \
-            if (best >= 3u) go = (off == best - 3u) ? (chk == mine) : (d32(L, cand + best - 3u) == d32(L, p + best - 3u)); \
-            if (go) {                                                                                           \
-                const uint32_t l = extend_match(L, p, cand, maxl);                                              \
-                if (l > best) {                                                                                 \
-                    best = l;                                                                                   \
-                    bdist = p - cand;                                                                           \
-                    if (l >= kDfNice || l >= maxl) left = 0u;                                                   \
-                    else if (l >= kDfGood && left > depth / 4u) left = depth / 4u;                              \
-                }                                                                                               \
-            }                                                                                                   \
-        }
-        SNAPHASH_DF_EVAL(0u, c0_, k0) SNAPHASH_DF_EVAL(1u, c1_, k1) SNAPHASH_DF_EVAL(2u, c2_, k2) SNAPHASH_DF_EVAL(3u, c3_, k3)
-#undef SNAPHASH_DF_EVAL
-    }
-#endif
     if (best == 3u && bdist > kDfTooFar) best = 0u;
     return best >= kDfMinMatch ? res_pack(best, bdist, byte) : res_pack(0u, 0u, byte);
 }
-
-// ---- searcher, round 5 experiment (make pairtiles): TWO tiles per wave at a time, a lane walking the chains of two
-// positions (p and p + 64) side by side.  The walk of a position is unchanged -- same links, same candidates, same
-// result -- but its dependent LDS reads (a link, the next link, ...) now have an independent twin in flight: the kernel
-// is latency-bound (a SIMD issues one instruction in ~7 cycles with its four waves: LDS holds one workgroup per CU), so
-// memory-level parallelism inside a wave is what is left to add.
-#if defined(SNAPHASH_DF_PAIR_TILES)
-__device__ __forceinline__ void search_pair(const ChunkLds& L, const uint8_t* __restrict__ in, uint64_t n_in, uint64_t pa64, uint64_t pb64, uint64_t c1,
-                                            uint32_t depth, uint32_t& ra, uint32_t& rb)
-{
-    const uint64_t p64[2] = {pa64, pb64};
-    uint32_t p[2], byte[2], maxl[2], best[2], bdist[2], left[2], cur[2], res[2];
-    bool more[2], live[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        p[u] = (uint32_t)p64[u];
-        const bool inside = p64[u] < c1;
-        byte[u] = inside ? L.data[p[u] & kDataMask] : 0u;
-        maxl[u] = inside ? ((c1 - p64[u] < 258u) ? (uint32_t)(c1 - p64[u]) : 258u) : 0u;
-        live[u] = inside && maxl[u] >= kDfMinMatch && p64[u] + 3u <= n_in;
-        res[u] = inside ? res_pack(0u, 0u, byte[u]) : 0u;
-        best[u] = kDfMinMatch - 1u; bdist[u] = 0u; left[u] = live[u] ? depth : 0u; cur[u] = p[u]; more[u] = live[u];
-    }
-    const uint8_t* gb = in + (p64[0] - p[0]); // (both positions lie in one staged piece: the same base)
-    while ((more[0] && left[0]) || (more[1] && left[1])) {
-        uint32_t c[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, ncand[2] = {0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const bool want = more[u] && ncand[u] < left[u];
-                const uint32_t d = L.ix.ring[cur[u] & kRingMask];
-                const bool ok = want && d != 0u && p[u] - (cur[u] - d) <= kDfMaxDist;
-                more[u] = want ? ok : more[u];
-                cur[u] = ok ? cur[u] - d : cur[u];
-                c[u][k] = ok ? cur[u] : 0u;
-                ncand[u] += ok ? 1u : 0u;
-            }
-        }
-        uint32_t off[2], mine[2], kw[2][4];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            off[u] = best[u] >= 3u ? best[u] - 3u : 0u;
-            mine[u] = d32(L, p[u] + off[u]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) kw[u][k] = *reinterpret_cast<const u32_unaligned*>(gb + c[u][k] + off[u]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if ((uint32_t)k < ncand[u] && left[u]) {
-                    --left[u];
-                    bool go = true;
-                    if (best[u] >= 3u) go = (off[u] == best[u] - 3u) ? (kw[u][k] == mine[u]) : (d32(L, c[u][k] + best[u] - 3u) == d32(L, p[u] + best[u] - 3u));
-                    if (go) {
-                        const uint32_t l = extend_match(L, p[u], c[u][k], maxl[u]);
-                        const bool better = l > best[u];
-                        const uint32_t cut = (l >= kDfNice || l >= maxl[u]) ? 0u : ((l >= kDfGood && left[u] > depth / 4u) ? depth / 4u : left[u]);
-                        bdist[u] = better ? p[u] - c[u][k] : bdist[u];
-                        left[u] = better ? cut : left[u];
-                        best[u] = better ? l : best[u];
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        if (live[u]) {
-            if (best[u] == 3u && bdist[u] > kDfTooFar) best[u] = 0u;
-            res[u] = best[u] >= kDfMinMatch ? res_pack(best[u], bdist[u], byte[u]) : res_pack(0u, 0u, byte[u]);
-        }
-    }
-    ra = res[0];
-    rb = res[1];
-}
-#endif // SNAPHASH_DF_PAIR_TILES
-
-// ---- searcher, round 4 experiment (make stream; MEASURED SLOWER, profiles/r04_deflate_stream_search.txt): the lanes of a
-// wave STREAM through positions.  search_position above gives a wave one tile and the tile costs what its slowest lane
-// costs: on content with long matches a few lanes walk 8 batches while most are done after one or two (sources: 17 ms per
-// 64 MiB against 10 for text).  Here a lane that is done with its position takes the next one of the
-// wave's pool (a tile from the step's queue, as before) at the top of the next batch: the wave stays full until the queue
-// is empty, and a step costs the lanes' average instead of a maximum per tile.  The walk of a position is unchanged and the
-// output is byte for byte the same -- and the kernel is 10-20 % SLOWER on all three corpora (12.1 / 18.9 / 12.3 ms against
-// 10.0 / 16.8 / 11.4): in a tile adjacent lanes hold adjacent positions, whose chains visit adjacent candidates (one
-// cache line of check words, neighbouring LDS banks), and a wave of unrelated positions gives that up for its fuller lanes.
-#if defined(SNAPHASH_DF_STREAM_SEARCH)
-__device__ __forceinline__ void search_segment_stream(ChunkLds& L, const uint8_t* __restrict__ in, uint64_t n_in, uint64_t seg64, uint64_t c1,
-                                                      uint32_t* __restrict__ res, uint32_t lane, uint32_t depth)
-{
-    uint32_t pool = 0, pool_end = 0; // the wave's pool: positions [pool, pool_end) of the segment (uniform)
-    bool tiles_left = true;
-    bool active = false;             // this lane is in the middle of a position's walk
-    uint32_t rel = 0, p = 0, byte = 0, maxl = 0, best = 0, bdist = 0, left = 0, cur = 0;
-    bool more = false;
-    const uint8_t* gb = in;
-    for (;;) {
-        uint64_t idle = __ballot(!active);
-        while (idle) { // every idle lane takes the next position of the pool; an empty pool takes the next tile of the queue
-            if (pool == pool_end) {
-                if (!tiles_left) break;
-                uint32_t item = 0;
-                if (lane == 0u) item = atomicAdd(&L.queue[1], 1u);
-                item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
-                if (item >= kSegTiles) { tiles_left = false; break; }
-                while (__hip_atomic_load(&L.across_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= item) __builtin_amdgcn_s_sleep(1);
-                pool = item * 64u;
-                pool_end = pool + 64u;
-            }
-            const uint32_t navail = pool_end - pool;
-            const uint32_t rank = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
-            if (!active && rank < navail) {
-                rel = pool + rank;
-                const uint64_t p64 = seg64 + rel;
-                p = (uint32_t)p64;
-                gb = in + (p64 - p);
-                if (p64 >= c1) {
-                    res[rel] = 0u;
-                } else {
-                    byte = L.data[p & kDataMask];
-                    maxl = (c1 - p64 < 258u) ? (uint32_t)(c1 - p64) : 258u;
-                    if (maxl < kDfMinMatch || p64 + 3u > n_in) {
-                        res[rel] = res_pack(0u, 0u, byte);
-                    } else {
-                        best = kDfMinMatch - 1u; bdist = 0u; left = depth; cur = p; more = true;
-                        active = true;
-                    }
-                }
-            }
-            const uint32_t nidle = (uint32_t)__builtin_popcountll(idle);
-            pool += nidle < navail ? nidle : navail;
-            idle = __ballot(!active); // (a position that needs no walk leaves its lane idle: it takes another)
-        }
-        if (__ballot(active) == 0ull) break;
-        if (active) { // one batch of the walk: search_position's loop body
-            uint32_t c0_ = 0, c1_ = 0, c2_ = 0, c3_ = 0, ncand = 0;
-#define SNAPHASH_DF_LINK(dst)                                                       \
-            if (more && ncand < left) {                                             \
-                const uint32_t d_ = L.ix.ring[cur & kRingMask];                     \
-                if (d_ == 0u || p - (cur - d_) > kDfMaxDist) more = false;          \
-                else { cur -= d_; dst = cur; ++ncand; }                             \
-            }
-            SNAPHASH_DF_LINK(c0_) SNAPHASH_DF_LINK(c1_) SNAPHASH_DF_LINK(c2_) SNAPHASH_DF_LINK(c3_)
-#undef SNAPHASH_DF_LINK
-            const uint32_t off = best >= 3u ? best - 3u : 0u;
-            const uint32_t mine = d32(L, p + off);
-            const uint32_t k0 = *reinterpret_cast<const u32_unaligned*>(gb + c0_ + off), k1 = *reinterpret_cast<const u32_unaligned*>(gb + c1_ + off),
-                           k2 = *reinterpret_cast<const u32_unaligned*>(gb + c2_ + off), k3 = *reinterpret_cast<const u32_unaligned*>(gb + c3_ + off);
-#define SNAPHASH_DF_EVAL(k, cand, chk)                                                                              \
-            if (k < ncand && left) {                                                                                \
-                --left;                                                                                             \
-                bool go = true;                                                                                     \
-                if (best >= 3u) go = (off == best - 3u) ? (chk == mine) : (d32(L, cand + best - 3u) == d32(L, p + best - 3u)); \
-                if (go) {                                                                                           \
-                    const uint32_t l = extend_match(L, p, cand, maxl);                                              \
-                    if (l > best) {                                                                                 \
-                        best = l;                                                                                   \
-                        bdist = p - cand;                                                                           \
-                        if (l >= kDfNice || l >= maxl) left = 0u;                                                   \
-                        else if (l >= kDfGood && left > depth / 4u) left = depth / 4u;                              \
-                    }                                                                                               \
-                }                                                                                                   \
-            }
-            SNAPHASH_DF_EVAL(0u, c0_, k0) SNAPHASH_DF_EVAL(1u, c1_, k1) SNAPHASH_DF_EVAL(2u, c2_, k2) SNAPHASH_DF_EVAL(3u, c3_, k3)
-#undef SNAPHASH_DF_EVAL
-            if (!(more && left)) { // the walk is over: the position's result
-                if (best == 3u && bdist > kDfTooFar) best = 0u;
-                res[rel] = best >= kDfMinMatch ? res_pack(best, bdist, byte) : res_pack(0u, 0u, byte);
-                active = false;
-            }
-        }
-    }
-}
-#endif // SNAPHASH_DF_STREAM_SEARCH
 
 // ---- parser (waves 1-4): the price parse of one window of a segment (deflate_core.h; tests/deflate_model.h is its
 // serial form).  In: the search results of the segment.  Out: startbits / matchbits / per-tile match counts of its
@@ -1269,21 +906,7 @@ __global__ __launch_bounds__(1024) void deflate_chunks_kernel(const uint8_t* __r
             __builtin_amdgcn_s_setprio(0);
         }
         if (chunk_step && j < nseg) {
-#if defined(SNAPHASH_DF_PAIR_TILES) // round 5 experiment: two tiles per wave at a time (search_pair)
-            static_assert(kSegTiles % 2u == 0u, "whole pairs of tiles");
-            for (;;) {
-                uint32_t item = 0;
-                if (lane == 0u) item = atomicAdd(&L.queue[1], 1u);
-                item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
-                if (item >= kSegTiles / 2u) break;
-                STAMP(t_wait, while (__hip_atomic_load(&L.across_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= 2u * item + 1u) __builtin_amdgcn_s_sleep(1));
-                uint32_t ra, rb;
-                const uint64_t pa = c0 + (uint64_t)j * kDfSeg + item * 128u + lane;
-                STAMP(t_sea, search_pair(L, in, n_in, pa, pa + 64u, c1, depth, ra, rb));
-                L.res[j % 3u][item * 128u + lane] = ra;
-                L.res[j % 3u][item * 128u + 64u + lane] = rb;
-            }
-#elif !defined(SNAPHASH_DF_STREAM_SEARCH) // a tile per wave at a time: a tile costs its slowest lane, and adjacent positions walk adjacent candidates
+            // a tile per wave at a time: a tile costs its slowest lane, and adjacent positions walk adjacent candidates
             for (;;) {
                 uint32_t item = 0;
                 if (lane == 0u) item = atomicAdd(&L.queue[1], 1u);
@@ -1292,9 +915,6 @@ __global__ __launch_bounds__(1024) void deflate_chunks_kernel(const uint8_t* __r
                 STAMP(t_wait, while (__hip_atomic_load(&L.across_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= item) __builtin_amdgcn_s_sleep(1));
                 STAMP(t_sea, L.res[j % 3u][item * 64u + lane] = search_position(L, in, n_in, c0 + (uint64_t)j * kDfSeg + item * 64u + lane, c1, depth));
             }
-#else
-            STAMP(t_sea, search_segment_stream(L, in, n_in, c0 + (uint64_t)j * kDfSeg, c1, L.res[j % 3u], lane, depth));
-#endif
         }
         SYNC_STAMPED(3);
         if (threadIdx.x == 0u) { L.queue[0] = 0u; L.queue[1] = 0u; } // handed out again only behind the next step's barriers

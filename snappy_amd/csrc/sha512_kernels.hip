@@ -21,7 +21,6 @@
 // One block is prefetched into registers while the previous one is hashed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "pair_rounds.inc"
 #if defined(SNAPHASH_WITH_QUAD) // the measured-negative four-lane variant: `make QUAD=1`
@@ -77,12 +76,7 @@ __device__ __forceinline__ void store_digest_be(uint8_t* out, const uint64_t H[8
 // chip: every VALU instruction advances 64 streams; saturates the VALUs at
 // ~1.05 TB/s from 65 536 streams on (profiles/r01_regime_sweep.txt).
 // ---------------------------------------------------------------------------
-#if defined(SNAPHASH_WIDE_WAVES) // experiment: ask the register allocator for that many waves per SIMD
-#define SNAPHASH_WIDE_ATTR __attribute__((amdgpu_waves_per_eu(SNAPHASH_WIDE_WAVES, SNAPHASH_WIDE_WAVES)))
-#else
-#define SNAPHASH_WIDE_ATTR
-#endif
-__global__ __launch_bounds__(64) SNAPHASH_WIDE_ATTR void sha512_wide_kernel(const Job* __restrict__ jobs, uint32_t njobs,
+__global__ __launch_bounds__(64) void sha512_wide_kernel(const Job* __restrict__ jobs, uint32_t njobs,
                                                          uint64_t* __restrict__ state,
                                                          uint8_t* __restrict__ digests)
 {
@@ -171,69 +165,6 @@ __global__ __launch_bounds__(64) SNAPHASH_WIDE_ATTR void sha512_wide_kernel(cons
     }
 }
 
-#if defined(SNAPHASH_EXPERIMENT_WIDE_DIRECT)
-// ---------------------------------------------------------------------------
-// WIDE, direct form: as above without the LDS tile.  Every lane fetches ITS OWN 128-byte block with eight
-// global_load_dwordx4 (one cache line per lane, all of it used by the eight loads back to back: the HBM traffic
-// stays 1x, the address unit sees 64 lines per instruction -- ~0.5 k cycles of it per 16 k-cycle block).  No tile,
-// no cooperative pointers, no register prefetch: 56 VGPRs less, no LDS, so 5 waves per SIMD instead of 3 and the
-// other waves hide the load latency.  EXPERIMENT (make WIDE_DIRECT=1, then SNAPHASH_WIDE_FORM=1|2|3 at run time):
-// bit-exact and no faster at 5, 6 or 8 waves per SIMD -- the saturated regime is bound by the vector unit's rate for
-// this instruction mix, not by latency (profiles/r03_wide_saturated_explained.txt).
-// ---------------------------------------------------------------------------
-template <int WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void sha512_wide_direct_kernel(
-    const Job* __restrict__ jobs, uint32_t njobs, uint64_t* __restrict__ state, uint8_t* __restrict__ digests)
-{
-    const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
-    const bool have = slot < njobs;
-    Job jb;
-    if (have) {
-        jb = jobs[slot];
-    } else {
-        jb.data = 0; jb.nbytes = 0; jb.total_prev = 0; jb.idx = 0; jb.flags = 0;
-    }
-    const uint64_t nbytes = jb.nbytes;
-    const uint32_t nfull = (uint32_t)(nbytes >> 7);
-    const uint32_t rem = (uint32_t)(nbytes & 127);
-    const bool fin = (jb.flags & kJobFinal) != 0;
-    const uint32_t nblk = have ? padded_blocks(nbytes, fin) : 0u;
-    const uint64_t total = jb.total_prev + nbytes;
-    const uint32_t npieces = (uint32_t)((nbytes + 15u) >> 4); // 16-byte pieces the stream holds (the last may be partial: the slack behind a stream is readable)
-    const uint8_t* p = reinterpret_cast<const uint8_t*>(jb.data);
-
-    uint64_t H[8];
-    if (jb.flags & kJobFirst) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) H[k] = IV512[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) H[k] = have ? state[(uint64_t)jb.idx * 8 + k] : 0;
-    }
-    for (uint32_t b = 0; __any(b < nblk); ++b) {
-        uint64_t w[16];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            uint4 q = make_uint4(0, 0, 0, 0);
-            if (b * 8u + (uint32_t)k < npieces) q = load_u4(p + (uint64_t)b * 128u + 16u * k);
-            w[2 * k] = be64(q.x, q.y);
-            w[2 * k + 1] = be64(q.z, q.w);
-        }
-        if (__any(b >= nfull && b < nblk)) apply_padding(w, b >= nfull, b - nfull, rem, total);
-        compress_block(H, w, b < nblk, d_K512);
-    }
-    if (have) {
-        if (fin) {
-            store_digest_be(digests + (uint64_t)jb.idx * 64, H);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) state[(uint64_t)jb.idx * 8 + k] = H[k];
-        }
-    }
-}
-
-#endif // SNAPHASH_EXPERIMENT_WIDE_DIRECT
-
 // ---------------------------------------------------------------------------
 // SPLIT kernel: for the stream-starved regime (fewer streams than the chip has
 // SIMDs x 64 lanes -- BASELINE config 2 has 10 001).  There a wave sits alone on
@@ -293,11 +224,7 @@ __device__ __forceinline__ void schedule_span(uint64_t w[16], uint64_t* __restri
 #pragma unroll
     for (int t = T0; t < T1; ++t) {
         if (t >= 16) w[t & 15] += small_sigma1(w[(t + 14) & 15]) + w[(t + 9) & 15] + small_sigma0(w[(t + 1) & 15]);
-#if defined(SNAPHASH_EXPERIMENT_NO_KW_STORE) // timing experiment only (wrong digests): the schedule is computed, never stored
-        { uint64_t v_ = w[t & 15] + K512[t]; asm volatile("" ::"v"(v_)); (void)row; }
-#else
         row[t] = w[t & 15] + K512[t];
-#endif
     }
 }
 
@@ -381,11 +308,6 @@ __device__ __forceinline__ void split_helper_wave(SplitShared& sh, uint32_t hk, 
     const uint32_t nfull = (uint32_t)(nbytes >> 7);
     const uint32_t rem = (uint32_t)(nbytes & 127);
     const uint64_t total = jb.total_prev + nbytes;
-#if defined(SNAPHASH_EXPERIMENT_IDLE_HELPERS) // timing experiment only (wrong digests): what do the round waves cost alone?
-    for (uint32_t tau = 0; tau < steps; ++tau) __syncthreads();
-    (void)nfull; (void)rem; (void)total; (void)hk; (void)lane;
-    return;
-#endif
     uint4* __restrict__ tile = sh.tile[hk];
     const uint32_t piece = lane & 7u;
     const uint8_t* tptr[8];
@@ -419,11 +341,9 @@ __device__ __forceinline__ void split_helper_wave(SplitShared& sh, uint32_t hk, 
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                [[maybe_unused]] const uint32_t p = (b + 2u) * 8u + piece;
+                const uint32_t p = (b + 2u) * 8u + piece;
                 pre[i] = make_uint4(0, 0, 0, 0);
-#if !defined(SNAPHASH_EXPERIMENT_NO_FETCH) // timing experiment only (wrong digests): no global loads in the helpers
                 if (p < tnp[i]) pre[i] = load_u4(tptr[i] + (uint64_t)(b + 2u) * 128u);
-#endif
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -738,12 +658,6 @@ hipError_t launch_wide(const Job* d_jobs, uint32_t njobs, uint64_t* d_state, uin
 {
     if (njobs == 0) return hipSuccess;
     const uint32_t grid = (njobs + 63u) / 64u;
-#if defined(SNAPHASH_EXPERIMENT_WIDE_DIRECT)
-    static const int form = [] { const char* e = getenv("SNAPHASH_WIDE_FORM"); return e ? atoi(e) : 0; }();
-    if (form == 1) { hipLaunchKernelGGL(sha512_wide_direct_kernel<5>, dim3(grid), dim3(64), 0, s, d_jobs, njobs, d_state, d_digests); return hipGetLastError(); }
-    if (form == 2) { hipLaunchKernelGGL(sha512_wide_direct_kernel<6>, dim3(grid), dim3(64), 0, s, d_jobs, njobs, d_state, d_digests); return hipGetLastError(); }
-    if (form == 3) { hipLaunchKernelGGL(sha512_wide_direct_kernel<8>, dim3(grid), dim3(64), 0, s, d_jobs, njobs, d_state, d_digests); return hipGetLastError(); }
-#endif
     hipLaunchKernelGGL(sha512_wide_kernel, dim3(grid), dim3(64), 0, s, d_jobs, njobs, d_state, d_digests);
     return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """64 MiB of this repository's sources (the corpus of tools/deflate_corpora.py) through snaphash_gzip_buffer a few times: the
-workload for rocprofv3 counter passes on deflate_chunks_kernel (SNAPHASH_LIB picks the build: make narrow for A/B)."""
+workload for rocprofv3 counter passes on deflate_chunks_kernel (SNAPHASH_LIB picks another build of the same ABI)."""
 import importlib.util, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
