@@ -323,7 +323,8 @@ int snaphash_gzip_buffer(snaphash_ctx *ctx, const void *data, size_t n, void **g
 
 /* ---- the data.tar.xz producer (tarCreate's ".xz" branch, clickdeb/deb.go:272-273) ---- */
 
-/* The .xz compressor alone, the twin of snaphash_gzip_buffer: one Stream (Check CRC-64) of a host buffer, a Block per
+/* The .xz compressor alone, the twin of snaphash_gzip_buffer: one Stream of a host buffer (Check CRC-64, taken in HBM from
+ * the staged bytes; the entry point below it takes the Check of the caller's choice), a Block per
  * block_size bytes -- a multiple of 64 KiB from 64 KiB to 4 MiB, 0 for the default of 1 MiB, anything else
  * SNAPHASH_EINVAL -- each Block header stating both sizes, as `xz -T` writes them; n == 0 gives a Stream without Blocks
  * (32 bytes).  Where the reference's `xz --compress --stdout` writes ONE Block, which any decoder reads on one thread,
@@ -333,6 +334,11 @@ int snaphash_gzip_buffer(snaphash_ctx *ctx, const void *data, size_t n, void **g
  * match finder and a greedy parse: a little above `xz -0`'s size, well above `xz -6`'s).  The bytes are a function of
  * (data, block_size) alone.  *xz_out is malloc'd (snaphash_free).  The engine's staging size must hold a Block. */
 int snaphash_xz_buffer(snaphash_ctx *ctx, const void *data, size_t n, uint64_t block_size, void **xz_out, size_t *xz_len);
+/* The same with the Check of the caller's choice, each taken in HBM by its kernel: 0 none, 1 CRC-32, 4 CRC-64 (then byte
+ * for byte the output of the call above), 10 SHA-256 (what `xz -C sha256` writes: the one cryptographic Check of the
+ * format); anything else SNAPHASH_EINVAL.  The Stream flags of header and footer carry the id; the Index follows its size. */
+int snaphash_xz_buffer_check(snaphash_ctx *ctx, const void *data, size_t n, uint64_t block_size, uint32_t check,
+                             void **xz_out, size_t *xz_len);
 /* snaphash_tar_create for a data.tar.xz: the same walk, tar layout, single read, fused hashes.yaml, late truncation and
  * unlink-on-failure; tarname must end in ".xz" (anything else: SNAPHASH_EINVAL, "unknown compression extension").
  * Blocks of 1 MiB; a Block never spans two staging slots.  snaphash_get_targz_stats reports the pass. */
@@ -466,9 +472,10 @@ int snaphash_tar_unpack_bz2(snaphash_ctx *ctx, const char *data_tar_bz2, const c
  * (none, CRC-32, CRC-64, SHA-256).  *out is malloc'd (snaphash_free).  The Index gives every Block's place in the file and
  * in the result before a byte is decoded, and a Block needs nothing from another: they are decoded side by side, each
  * straight to its final offset -- a Block a host thread in the default configuration, a Block a workgroup of
- * lzma2_blocks_kernel under SNAPHASH_FLAG_GPU_ONLY, with the CRC-32 and CRC-64 Checks taken in HBM.  Inside one Block LZMA
- * is a serial chain: a file of one Block (what `xz` writes without -T or --block-size) decodes on one thread.  A Block of
- * more than 4 MiB of output, and any Block the kernel gives up on, is decoded by a host thread in either configuration.
+ * lzma2_blocks_kernel under SNAPHASH_FLAG_GPU_ONLY, with the CRC-32, CRC-64 and SHA-256 Checks of those Blocks taken in HBM
+ * (a range a Block: the CRC kernels, sha256_ranges_kernel).  Inside one Block LZMA is a serial chain: a file of one Block
+ * (what `xz` writes without -T or --block-size) decodes on one thread.  A Block of more than 4 MiB of output, and any
+ * Block the kernel gives up on, is decoded and checked by a host thread in either configuration.
  * In the unpack statistics segments = Blocks, gpu_segments = Blocks the kernel decoded, host_bytes = output of the
  * Blocks decoded on the host, inflate_ms = the decode and Check kernels.
  * SNAPHASH_EFORMAT: whatever liblzma refuses -- a wrong magic or CRC, an Index that disagrees with its Blocks, malformed
@@ -483,13 +490,29 @@ int snaphash_tar_unpack_xz(snaphash_ctx *ctx, const char *data_tar_xz, const cha
 /* One Block of a .xz file by lzma2_blocks_kernel alone, into the caller's HBM: Block `block` (counted over all Streams of
  * xz[0..n), in order) decoded to d_dst[0..dst_len), where dst_len must be the Block's uncompressed size (at most 4 MiB).
  * The container is checked as in snaphash_unxz_buffer; the Block's Check is NOT (snaphash_crc32_device /
- * snaphash_crc64_device take it from d_dst).  No byte outside d_dst[0..dst_len) is written.  SNAPHASH_EFORMAT: the
+ * snaphash_crc64_device / snaphash_sha256_device take it from d_dst).  No byte outside d_dst[0..dst_len) is written.  SNAPHASH_EFORMAT: the
  * kernel refuses the Block's LZMA2 data (no host decoder stands behind this call).  Synchronous. */
 int snaphash_unxz_block_device(snaphash_ctx *ctx, const void *xz, size_t n, size_t block, void *d_dst, size_t dst_len);
 /* CRC-64/XZ (ECMA-182 reflected, the .xz Check id 4) of byte ranges resident in HBM: the twin of snaphash_crc32_device
  * below, the same rules (a range of length 0 has CRC 0). */
 int snaphash_crc64_device(snaphash_ctx *ctx, const void *d_base, const uint64_t *offsets, const uint64_t *lens, size_t n,
                           uint64_t *crcs);
+/* SHA-256 (the .xz Check id 10) of byte ranges resident in HBM, by sha256_ranges_kernel: the twin of the call above (any
+ * alignment, any length below 32 GiB, ranges may overlap, a range of length 0 has the digest of the empty message);
+ * digests: host, n * 32 bytes, each range's at its own index.  A range is one chain on one lane, so many ranges are fast
+ * and one long range is not.  Synchronous. */
+int snaphash_sha256_device(snaphash_ctx *ctx, const void *d_base, const uint64_t *offsets, const uint64_t *lens, size_t n,
+                           uint8_t *digests);
+
+/* Who took the Blocks' Checks in the most recent .xz decode (buffer or tar unpack) of this ctx. */
+typedef struct snaphash_xz_check_stats {
+    uint32_t struct_size;
+    uint32_t reserved;
+    uint64_t device_crc32, device_crc64, device_sha256; /* Blocks whose Check a kernel took */
+    uint64_t host_checks;                               /* Blocks whose Check a host thread took (Check none: counted nowhere) */
+    double device_check_ms;                             /* the Check kernels, HIP events */
+} snaphash_xz_check_stats;
+int snaphash_get_xz_check_stats(const snaphash_ctx *ctx, snaphash_xz_check_stats *out);
 
 /* ---- the .snap itself: the ar container, its two tars, audit and unpack (clickdeb/deb.go:108-203, 408-441) ------------ */
 

@@ -30,7 +30,7 @@ EXPORTS = [
     "snaphash_get_stats_ex", "snaphash_get_device_stats", "snaphash_tree_ex",
     "snaphash_batch_begin", "snaphash_batch_append", "snaphash_batch_end", "snaphash_batch_finish", "snaphash_batch_abort",
     "snaphash_tar_create", "snaphash_tar_create_fn", "snaphash_gzip_buffer", "snaphash_get_targz_stats",
-    "snaphash_xz_buffer", "snaphash_tar_create_xz",
+    "snaphash_xz_buffer", "snaphash_xz_buffer_check", "snaphash_tar_create_xz",
     "snaphash_get_engine_info", "snaphash_numa_probe",
     "snaphash_get_engine_cpus", "snaphash_numa_slice", "snaphash_plan_streams", "snaphash_usable_cpus", "snaphash_cgroup_cpu_quota",
     "snaphash_shard_plan", "snaphash_shard_rows", "snaphash_shard_count", "snaphash_shard_streams", "snaphash_shard_bytes",
@@ -45,6 +45,7 @@ EXPORTS = [
     "snaphash_bunzip2_buffer", "snaphash_tar_unpack_bz2",
     # data.tar.xz
     "snaphash_unxz_buffer", "snaphash_tar_unpack_xz", "snaphash_unxz_block_device", "snaphash_crc64_device",
+    "snaphash_sha256_device", "snaphash_get_xz_check_stats",
     # the .snap itself: CRCs in HBM, the ar container, audit and unpack
     "snaphash_crc32_device", "snaphash_snap_open", "snaphash_snap_close", "snaphash_snap_members", "snaphash_snap_member_info",
     "snaphash_snap_control_member", "snaphash_snap_meta_member", "snaphash_snap_unpack", "snaphash_snap_audit",
@@ -111,6 +112,12 @@ class TargzStats(ctypes.Structure):
     _fields_ = [("tar_bytes", ctypes.c_uint64), ("gz_bytes", ctypes.c_uint64), ("members", ctypes.c_uint64),
                 ("chunks", ctypes.c_uint64), ("stored_chunks", ctypes.c_uint64), ("deflate_ms", ctypes.c_double),
                 ("fill_ms", ctypes.c_double), ("wall_ms", ctypes.c_double)]
+
+
+class XzCheckStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("device_crc32", ctypes.c_uint64),
+                ("device_crc64", ctypes.c_uint64), ("device_sha256", ctypes.c_uint64), ("host_checks", ctypes.c_uint64),
+                ("device_check_ms", ctypes.c_double)]
 
 
 class UnpackStats(ctypes.Structure):
@@ -233,6 +240,9 @@ def lib():
     L.snaphash_unxz_buffer.argtypes = [vp, vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_unpack_xz.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_crc64_device.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.snaphash_sha256_device.argtypes = [vp, vp, vp, vp, sz, vp]
+    L.snaphash_get_xz_check_stats.argtypes = [vp, ctypes.POINTER(XzCheckStats)]
+    L.snaphash_xz_buffer_check.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_unxz_block_device.argtypes = [vp, vp, sz, sz, vp, sz]
     L.snaphash_xzenc_stages_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, sz, u64p]
     L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -421,11 +431,17 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def xz_buffer(self, data, block_size=0):
-        """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU."""
+    def xz_buffer(self, data, block_size=0, check=None):
+        """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU.  check: the Blocks'
+        Check id -- 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256, each taken in HBM; None: CRC-64 through the entry point that
+        takes no Check."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
+        if check is None:
+            self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
+        else:
+            self._check(lib().snaphash_xz_buffer_check(self._h, ctypes.addressof(buf), len(data), block_size, check, ctypes.byref(p),
+                                                       ctypes.byref(n)))
         try:
             return ctypes.string_at(p.value, n.value)
         finally:
@@ -574,6 +590,23 @@ class Context:
         out = np.zeros(max(n, 1), dtype=np.uint64)
         self._check(lib().snaphash_crc64_device(self._h, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
         return out[:n]
+
+    def sha256_device(self, d_base, offsets, lens):
+        """SHA-256 of byte ranges resident in HBM.  d_base: device address (int); offsets / lens: contiguous numpy
+        uint64 arrays, any alignment.  -> numpy uint8 array of shape (n, 32), a range's digest at its own index."""
+        import numpy as np
+        n = len(offsets)
+        out = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        self._check(lib().snaphash_sha256_device(self._h, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
+    def xz_check_stats(self):
+        """Who took the Blocks' Checks in the last unxz_buffer / tar_unpack_xz: Blocks per Check kernel, Blocks on host
+        threads, the Check kernels' milliseconds."""
+        s = XzCheckStats()
+        s.struct_size = ctypes.sizeof(XzCheckStats)
+        self._check(lib().snaphash_get_xz_check_stats(self._h, ctypes.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in XzCheckStats._fields_ if f[0] not in ("struct_size", "reserved")}
 
     def snap_open(self, snap_path):
         """A session on a .snap file (ClickDeb.Open): see Snap."""

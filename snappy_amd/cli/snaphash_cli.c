@@ -10,7 +10,9 @@
  *   snaphash [options] build-xz BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB, LZMA2 on the GPU
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
- *   snaphash [options] xz IN OUT.xz [-B KiB]     the .xz compressor alone, a Block per KiB of input (default 1024)
+ *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256]
+ *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
+ *                                                Blocks' Check as named (default crc64), taken on the GPU
  *   snaphash [options] gunzip IN.gz OUT          the inverse: every member decoded (GPU inflate)
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
@@ -51,7 +53,7 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | build-xz DIR OUT.tar.xz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
-                    "       xz IN OUT.xz [-B BLOCK_KiB] |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
                     "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
@@ -216,13 +218,26 @@ int main(int argc, char **argv)
         }
         snaphash_free(z);
         free(in);
-    } else if (!strcmp(argv[1], "xz") && (argc == 4 || (argc == 6 && !strcmp(argv[4], "-B")))) {
+    } else if (!strcmp(argv[1], "xz") && argc >= 4 && argc % 2 == 0) {
         size_t len = 0, zl = 0;
-        const uint64_t block = argc == 6 ? (uint64_t)strtoull(argv[5], NULL, 10) * 1024u : 0;
+        uint64_t block = 0;
+        int have_block = 0, check = -1; /* -1: no -C, the entry point that takes no Check */
+        for (int i = 4; i < argc; i += 2) {
+            if (!strcmp(argv[i], "-B")) {
+                block = (uint64_t)strtoull(argv[i + 1], NULL, 10) * 1024u;
+                have_block = 1;
+            } else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "none")) check = 0;
+            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "crc32")) check = 1;
+            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "crc64")) check = 4;
+            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "sha256")) check = 10;
+            else { snaphash_destroy(c); return usage(); }
+        }
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *z = NULL;
-        rc = (argc == 6 && block == 0) ? SNAPHASH_EINVAL : snaphash_xz_buffer(c, in, len, block, &z, &zl);
+        rc = (have_block && block == 0) ? SNAPHASH_EINVAL
+             : check < 0                ? snaphash_xz_buffer(c, in, len, block, &z, &zl)
+                                        : snaphash_xz_buffer_check(c, in, len, block, (uint32_t)check, &z, &zl);
         if (rc) ret = die(c, rc, "xz");
         else {
             FILE *f = fopen(argv[3], "wb");

@@ -13,6 +13,7 @@
 #include "devbuf.h"
 #include "inflate_core.h"
 #include "inflate_kernels.h"
+#include "sha256_kernels.h"
 #include "sha512_kernels.h"
 #include "xz_host.h"
 #include "xz_enc_kernels.h"
@@ -243,6 +244,21 @@ struct CrcBufs {
     template <class F> void each(F&& f) { offs.each(f); lens.each(f); tile0.each(f); f(d_partial); crcs.each(f); f(d_partial64); crcs64.each(f); }
 };
 
+// SHA-256 of ranges in HBM (sha256_kernels.hip): the ranges in the order the waves take them, built in pinned memory, and their
+// HBM twin; the digests (32 bytes a range, in the caller's order) and their way back
+struct Sha256Bufs {
+    Twin<Sha256Range> ranges;
+    Twin<uint8_t> digests;
+    hipError_t ensure(size_t n)
+    {
+        hipError_t e = ranges.ensure(n);
+        if (!e) e = digests.ensure(n * kSha256Digest);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { ranges.each(f); digests.each(f); }
+};
+
 // GPU LZMA2 (unxz.inc): the whole .xz file and the Blocks the kernel takes
 struct XzBufs {
     DevBuf<uint8_t> d_in;
@@ -265,8 +281,8 @@ struct XzEncBufs {
     Twin<uint32_t> res;
     Twin<uint64_t> dst;
     HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
-    // what a slot's output takes at most: every chunk stored (3 bytes of header), a Block a chunk (header, end byte,
-    // padding, Check)
+    // what a slot's output takes at most: every chunk stored (3 bytes of header), a Block a chunk (a header of 20 bytes
+    // for sizes that take four bytes each, the end byte, 3 of padding and the longest Check, SHA-256's 32: 59 in all)
     static uint64_t out_cap(uint64_t slot_bytes) { return slot_bytes + ((slot_bytes + kXzEncChunk - 1) / kXzEncChunk) * 64 + 64; }
     uint64_t cap() const { return h_out[0].size(); }
     hipError_t ensure(uint64_t slot_bytes, int node)

@@ -96,6 +96,7 @@ struct DevCtx {
     InflateBufs inf;
     Bzip2Bufs bz;
     CrcBufs crc;
+    Sha256Bufs sha256;
     XzBufs xz;
     XzEncBufs xe; // the .xz producer's (xzpack.inc)
     hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
@@ -134,6 +135,7 @@ struct DevCtx {
         inf.each(f);
         bz.each(f);
         crc.each(f);
+        sha256.each(f);
         xz.each(f);
         xe.each(f);
     }
@@ -174,6 +176,7 @@ struct snaphash_ctx {
     snaphash_stats_ex ex{};
     snaphash_targz_stats targz{};
     snaphash_unpack_stats unpack{};
+    snaphash_xz_check_stats xz_check{}; // of the most recent .xz decode (unxz.inc)
     snaphash_block_scan_stats block_scan{};
     std::string last_error;
     snaphash_batch* open_batch = nullptr;
@@ -2373,9 +2376,57 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+// The SHA-256 digests of n ranges of d_base on stream s, 32 bytes each in the caller's order, back on the host when the
+// call returns: crc_ranges_dev's contract.  A wave runs until the longest of its 64 ranges ends, so the ranges go to the
+// waves sorted by block count, the longest first (the launch then ends with its short waves); the kernel writes every
+// digest at its range's own index.
+int sha256_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, const uint64_t* lens, size_t n, uint8_t* digests, hipStream_t s,
+                      double* ms)
+{
+    if (n == 0) return SNAPHASH_OK;
+    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
+    for (size_t i = 0; i < n; ++i) {
+        if (lens[i] > ~0ull - offs[i]) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
+        if (lens[i] >= kSha256RangeMax) return fail(c, SNAPHASH_EINVAL, "a range of 32 GiB or more");
+    }
+    HIP_TRY(c, c->sha256.ensure(n));
+    Sha256Range* r = c->sha256.ranges.h.data();
+    for (size_t i = 0; i < n; ++i) r[i] = Sha256Range{offs[i], lens[i], (uint32_t)i, 0};
+    std::stable_sort(r, r + n, [](const Sha256Range& a, const Sha256Range& b) { return sha256_blocks(a.len) > sha256_blocks(b.len); });
+    HIP_TRY(c, hipMemcpyAsync(c->sha256.ranges.d.data(), r, n * sizeof(Sha256Range), hipMemcpyHostToDevice, s));
+    EventPair* ev = next_events(c, 2);
+    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    HIP_TRY(c, hipEventRecord(ev->a, s));
+    HIP_TRY(c, launch_sha256_ranges(d_base, c->sha256.ranges.d.data(), (uint32_t)n, c->sha256.digests.d.data(), s));
+    HIP_TRY(c, hipEventRecord(ev->b, s));
+    HIP_TRY(c, hipMemcpyAsync(c->sha256.digests.h.data(), c->sha256.digests.d.data(), n * kSha256Digest, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    float f = 0;
+    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
+    memcpy(digests, c->sha256.digests.h.data(), n * kSha256Digest);
+    return SNAPHASH_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int snaphash_sha256_device(snaphash_ctx* x, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n, uint8_t* digests)
+try {
+    if (!x || (n && (!d_base || !offsets || !lens || !digests))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
+    HIP_TRY(c, hipSetDevice(c->device));
+    double ms = 0;
+    const int rc = sha256_ranges_dev(c, (const uint8_t*)d_base, offsets, lens, n, digests, c->stream, &ms);
+    c->ev_used = 0;
+    x->stats.kernel_ms = ms;
+    x->stats.launches = n ? 1 : 0;
+    end_top(x, t_top0_);
+    return lift(x, c, rc);
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
 
 int snaphash_crc32_device(snaphash_ctx* x, int kind, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n,
                           uint32_t* crcs)

@@ -58,6 +58,7 @@ struct GzPipe {
     snaphash_targz_stats st{};
     // the .xz producer (xzpack.inc): the Block size and the Index records of the Blocks written so far
     uint64_t xz_block_size = kXzEncBlockDefault;
+    uint32_t xz_check = kXzCheckCrc64; // the Blocks' Check (snaphash_xz_buffer_check names another)
     std::vector<XzEncRecord> xz_recs;
     // Whatever way the producer leaves (an exception on its way to the C boundary's catch included), the consumers are
     // told to finish and are joined: a joinable std::thread that is destroyed takes the process down.

@@ -5,8 +5,8 @@
 // pipes the .xz member through the xz program.  Here the file's Index says where every Block begins and where its bytes
 // go (xz_core.h xz_plan), so the Blocks are decoded side by side, each straight to its final offset -- on host threads
 // in the default configuration (xz_host.cpp), by lzma2_blocks_kernel (xz_kernels.hip) under SNAPHASH_FLAG_GPU_ONLY, where
-// the CRC-32 and CRC-64 Checks are taken in HBM right after the decode (crc_kernels.hip) -- and the decoded stream goes
-// through the same unpack and in-pass Verify as data.tar.gz.
+// the CRC-32, CRC-64 and SHA-256 Checks are taken in HBM right after the decode (crc_kernels.hip, sha256_kernels.hip) -- and
+// the decoded stream goes through the same unpack and in-pass Verify as data.tar.gz.
 
 namespace {
 
@@ -22,6 +22,13 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
     const int pe = xz_plan(xz, n, blocks, &total, why);
     if (pe) return fail(c, pe == kXzPlanUnsupported ? SNAPHASH_EINVAL : SNAPHASH_EFORMAT, why);
     c->fout_gen++;
+    snaphash_xz_check_stats& ck = x->xz_check; // who took the Checks of this decode
+    ck = snaphash_xz_check_stats{};
+    ck.struct_size = sizeof ck;
+    auto host_checked = [&](const std::vector<uint32_t>* which) {
+        const size_t K = which ? which->size() : blocks.size();
+        for (size_t k = 0; k < K; ++k) ck.host_checks += blocks[which ? (*which)[k] : k].check != kXzCheckNone;
+    };
     const unsigned cpus = call_cpus(x);
     const size_t o0 = out.size();
     out.resize(o0 + total);
@@ -37,6 +44,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             return fail(c, SNAPHASH_EFORMAT, "xz: corrupt block");
         }
         st.host_bytes += total;
+        host_checked(nullptr);
         return ds.mirror(o0, o0 + total);
     }
     // SNAPHASH_FLAG_GPU_ONLY: every Block up to kXzGpuBlockMax through the kernel, the rest (and what the kernel refuses) on
@@ -65,13 +73,14 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
         (void)hipEventElapsedTime(&kms, ev->a, ev->b);
         st.inflate_ms += kms;
         c->ev_used = 0;
-        // the Checks of what the kernel decoded: CRC-32 and CRC-64 in HBM, a range a Block; SHA-256 on the host
-        std::vector<uint32_t> ok, k32, k64;
+        // the Checks of what the kernel decoded, in HBM, a range a Block
+        std::vector<uint32_t> ok, k32, k64, k256;
         for (size_t k = 0; k < gpu.size(); ++k) {
             if (c->xz.blk.h[k].status != kXzOk) { host.push_back(gpu[k]); continue; } // the host decoder says what is wrong
             ok.push_back(gpu[k]);
             if (blocks[gpu[k]].check == kXzCheckCrc32) k32.push_back(gpu[k]);
             if (blocks[gpu[k]].check == kXzCheckCrc64) k64.push_back(gpu[k]);
+            if (blocks[gpu[k]].check == kXzCheckSha256) k256.push_back(gpu[k]);
         }
         // the bytes of the Blocks the kernel decoded on their way back (neighbours in one copy), beside the Check kernels;
         // what a host thread will decode is not moved
@@ -108,10 +117,20 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
                 bad |= got[k] != ((uint64_t)xz_le32(f + 4) << 32 | xz_le32(f));
             }
         }
-        HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the CRC calls waited on the same stream, but there may be none)
+        if (!k256.empty()) {
+            ranges(k256);
+            std::vector<uint8_t> got(k256.size() * kSha256Digest);
+            rc = sha256_ranges_dev(c, c->inf.d_out.data(), offs.data(), lens.data(), k256.size(), got.data(), c->f_stream, &cms);
+            c->ev_used = 0;
+            if (rc) return rc;
+            for (size_t k = 0; k < k256.size(); ++k) bad |= memcmp(got.data() + k * kSha256Digest, xz + blocks[k256[k]].check_off, kSha256Digest) != 0;
+        }
+        HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the Check calls waited on the same stream, but there may be none)
         st.inflate_ms += cms;
-        for (uint32_t i : ok)
-            if (blocks[i].check == kXzCheckSha256) bad |= !xz_check_block(xz, blocks[i], dst + blocks[i].out_off);
+        ck.device_crc32 = k32.size();
+        ck.device_crc64 = k64.size();
+        ck.device_sha256 = k256.size();
+        ck.device_check_ms = cms;
         if (bad) {
             ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "xz: block check mismatch");
@@ -123,6 +142,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             ds.rollback();
             return fail(c, SNAPHASH_EFORMAT, "xz: corrupt block");
         }
+        host_checked(&host);
         for (uint32_t i : host) {
             st.host_bytes += blocks[i].out_len;
             rc = ds.mirror_async(o0 + blocks[i].out_off, o0 + blocks[i].out_off + blocks[i].out_len);
@@ -149,6 +169,14 @@ int snaphash_tar_unpack_xz(snaphash_ctx* x, const char* data_tar_xz, const char*
                            snaphash_mismatch* first, uint8_t* archive_digest)
 {
     return tar_unpack_entry(x, kUnxzCodec, data_tar_xz, target_dir, yaml, yaml_len, first, archive_digest);
+}
+
+int snaphash_get_xz_check_stats(const snaphash_ctx* x, snaphash_xz_check_stats* out)
+{
+    if (!x || !out) return SNAPHASH_EINVAL;
+    *out = x->xz_check;
+    out->struct_size = sizeof *out;
+    return SNAPHASH_OK;
 }
 
 int snaphash_unxz_block_device(snaphash_ctx* x, const void* xz, size_t n, size_t block, void* d_dst, size_t dst_len)

@@ -2,7 +2,9 @@
 // (xz_enc_kernels.hip), the library's host side (xzpack.inc) and a host model in tests/, the way xz_core.h serves the
 // decoders.  The container assembly is host-only, the encoder is host + device (XZ_HD).
 //
-// What is written: one Stream, Check CRC-64, a Block per block_size bytes of input (the last one
+// What is written: one Stream, Check CRC-64 unless the caller names another of the four this project
+// reads (none, CRC-32, CRC-64, SHA-256: the container's routines take the id, CRC-64 where it is left out), a Block per
+// block_size bytes of input (the last one
 // shorter), every Block header stating both sizes, one LZMA2 filter with lc=3 lp=0 pb=2 and the smallest dictionary that
 // holds a Block.  Inside a Block an LZMA2 chunk holds kXzEncChunk (65 536) uncompressed bytes, the one size at which both
 // of LZMA2's limits hold without a second split.  Every chunk resets the coder state and sends the properties again (the
@@ -14,7 +16,7 @@
 // The match rules are those the head of xz_core.h lists as settled against liblzma: lengths 2..273, no match past its
 // chunk's end, a distance at most the bytes since the Block's start, no rep or short rep before the first byte.
 //
-// The bytes are a function of (input, block_size) alone.  The three steps below are pure functions of the Block:
+// The bytes are a function of (input, block_size, Check) alone.  The three steps below are pure functions of the Block:
 //   xzenc_chains_host / lzma_chains_kernel   prev[p] = the nearest earlier position of the Block with the same 4-byte hash
 //   xzenc_find                               the best (length, distance) at p: the chain in order, kXzEncDepth links, the
 //                                            longest kept, the nearest among equals, every compare cut at the chunk's end
@@ -437,14 +439,23 @@ inline void xzenc_le64(uint8_t* p, uint64_t v)
 {
     for (int k = 0; k < 8; ++k) p[k] = (uint8_t)(v >> (8 * k));
 }
-constexpr uint32_t kXzEncStreamHeader = 12, kXzEncBlockHeaderMax = 32, kXzEncCheck = 8;
+constexpr uint32_t kXzEncStreamHeader = 12, kXzEncBlockHeaderMax = 32, kXzEncCheck = 8; // (CRC-64's size: the default Check)
+constexpr uint32_t kXzEncCheckMax = 32;
 
-inline void xzenc_stream_header(uint8_t* p)
+// the Checks this side writes: what the install side reads
+inline bool xzenc_check_valid(uint32_t check)
+{
+    return check == kXzCheckNone || check == kXzCheckCrc32 || check == kXzCheckCrc64 || check == kXzCheckSha256;
+}
+// the bytes of a Block's Check field
+inline uint32_t xzenc_check_size(uint32_t check) { return check == kXzCheckNone ? 0 : check == kXzCheckCrc32 ? 4 : check == kXzCheckCrc64 ? 8 : 32; }
+
+inline void xzenc_stream_header(uint8_t* p, uint32_t check = kXzCheckCrc64)
 {
     static const uint8_t magic[6] = {0xFD, '7', 'z', 'X', 'Z', 0};
     memcpy(p, magic, 6);
     p[6] = 0;
-    p[7] = (uint8_t)kXzCheckCrc64;
+    p[7] = (uint8_t)check;
     xzenc_le32(p + 8, xz_crc32(p + 6, 2));
 }
 // a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size
@@ -469,7 +480,7 @@ inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize)
 }
 struct XzEncRecord { uint64_t unpadded, usize; };
 // the Index and the Stream footer behind the last Block
-inline void xzenc_index_footer(const std::vector<XzEncRecord>& recs, std::vector<uint8_t>& out)
+inline void xzenc_index_footer(const std::vector<XzEncRecord>& recs, std::vector<uint8_t>& out, uint32_t check = kXzCheckCrc64)
 {
     const size_t i0 = out.size();
     uint8_t t[10];
@@ -486,7 +497,7 @@ inline void xzenc_index_footer(const std::vector<XzEncRecord>& recs, std::vector
     uint8_t f[12];
     xzenc_le32(f + 4, (uint32_t)(isize / 4 - 1));
     f[8] = 0;
-    f[9] = (uint8_t)kXzCheckCrc64;
+    f[9] = (uint8_t)check;
     xzenc_le32(f, xz_crc32(f + 4, 6));
     f[10] = 'Y';
     f[11] = 'Z';
@@ -501,8 +512,9 @@ struct XzEncBlockLayout {
     uint64_t total = 0;     // header, data, padding, Check
     uint64_t unpadded = 0;  // the Index record's
 };
-inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst)
+inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst, uint32_t check = kXzCheckCrc64)
 {
+    const uint32_t check_size = xzenc_check_size(check);
     XzEncBlockLayout L;
     uint64_t data = 0;
     for (uint32_t k = 0; k < nch; ++k) {
@@ -513,9 +525,9 @@ inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, ui
     L.data = data + 1;
     L.hdr = xzenc_block_header_size(L.data, blen);
     for (uint32_t k = 0; k < nch; ++k) dst[k] += L.hdr;
-    L.unpadded = L.hdr + L.data + kXzEncCheck;
+    L.unpadded = L.hdr + L.data + check_size;
     L.check_at = (L.hdr + L.data + 3) & ~3ull;
-    L.total = L.check_at + kXzEncCheck;
+    L.total = L.check_at + check_size;
     return L;
 }
 
@@ -546,7 +558,7 @@ struct XzEncInfo {
 // output, nothing else written).  head: 1 << kXzEncHashBits entries of scratch; probs: kXzEncProbs.
 template <class OPS>
 inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* cand, uint32_t* head, uint16_t* probs,
-                                           uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops)
+                                           uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops, uint32_t check = kXzCheckCrc64)
 {
     const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
     xzenc_chains_host(blk, blen, prev, head);
@@ -556,7 +568,7 @@ inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, ui
         for (uint32_t i = 0; i < kXzEncProbs; ++i) probs[i] = (uint16_t)kLzmaProbInit;
         res[k] = xzenc_chunk(blk, cs, ce, cand, probs, slots + (size_t)k * kXzEncSlot, kXzEncSlot, ops);
     }
-    return xzenc_block_layout(res, nch, blen, dst);
+    return xzenc_block_layout(res, nch, blen, dst, check);
 }
 // what lzma2_concat_kernel writes of a Block that begins at q: chunk headers, bodies and the end byte
 inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t* res, const uint64_t* dst, const uint8_t* slots, uint8_t* q)
@@ -570,24 +582,31 @@ inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t*
         if (k + 1 == nch) q[dst[k] + h + len] = 0;
     }
 }
-// what the host writes of a Block that begins at q: header, Block Padding, Check
-inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, uint64_t crc)
+// what the host writes of a Block that begins at q: header, Block Padding, Check (CRC-64, or any Check's field as bytes)
+inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, const uint8_t* field, uint32_t check_size)
 {
     xzenc_block_header(q, L.data, blen, dict_byte);
     for (uint64_t z = L.hdr + L.data; z < L.check_at; ++z) q[z] = 0;
-    xzenc_le64(q + L.check_at, crc);
+    if (check_size) memcpy(q + L.check_at, field, check_size);
+}
+inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, uint64_t crc)
+{
+    uint8_t field[8];
+    xzenc_le64(field, crc);
+    xzenc_block_frame(q, L, blen, dict_byte, field, 8);
 }
 
-// The whole file on this thread, through the routines the kernels run.  crc64: the Check of a Block's bytes.  false: the
-// block size is not one the format decisions allow.
-template <class OPS, class CRC>
-inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std::vector<uint8_t>& out, OPS& ops, CRC crc64,
+// The whole file on this thread, through the routines the kernels run, with Check `check` (xzenc_check_valid).
+// field(p, len, out): the Check of a Block's bytes, xzenc_check_size(check) bytes as the file holds them.  false: the
+// block size or the Check is not one the format decisions allow.
+template <class OPS, class FIELD>
+inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uint32_t check, std::vector<uint8_t>& out, OPS& ops, FIELD field,
                        XzEncInfo* info = nullptr)
 {
-    if (!xzenc_block_size(&block_size)) return false;
-    const uint32_t dict_byte = xzenc_dict_byte(block_size);
+    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check)) return false;
+    const uint32_t dict_byte = xzenc_dict_byte(block_size), check_size = xzenc_check_size(check);
     out.resize(kXzEncStreamHeader);
-    xzenc_stream_header(out.data());
+    xzenc_stream_header(out.data(), check);
     std::vector<XzEncRecord> recs;
     std::vector<uint32_t> prev, cand, head(1u << kXzEncHashBits), res;
     std::vector<uint64_t> dst;
@@ -603,7 +622,7 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std
         dst.resize(nch);
         slots.resize((size_t)nch * kXzEncSlot);
         const XzEncBlockLayout L = xzenc_block_stages(blk, blen, prev.data(), cand.data(), head.data(), probs.data(), res.data(), dst.data(),
-                                                      slots.data(), ops);
+                                                      slots.data(), ops, check);
         if (info)
             for (uint32_t k = 0; k < nch; ++k) {
                 info->chunks++;
@@ -612,12 +631,22 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std
             }
         const size_t o = out.size();
         out.resize(o + L.total, 0);
-        xzenc_block_frame(out.data() + o, L, blen, dict_byte, crc64(blk, (uint64_t)blen));
+        uint8_t f[kXzEncCheckMax] = {0};
+        field(blk, (uint64_t)blen, f);
+        xzenc_block_frame(out.data() + o, L, blen, dict_byte, f, check_size);
         xzenc_block_place(blk, blen, res.data(), dst.data(), slots.data(), out.data() + o);
         recs.push_back(XzEncRecord{L.unpadded, blen});
     }
-    xzenc_index_footer(recs, out);
+    xzenc_index_footer(recs, out, check);
     return true;
+}
+// The same with the default Check.  crc64: the CRC-64 of a Block's bytes, as a number.
+template <class OPS, class CRC>
+inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, std::vector<uint8_t>& out, OPS& ops, CRC crc64,
+                       XzEncInfo* info = nullptr)
+{
+    return xzenc_host(data, n, block_size, (uint32_t)kXzCheckCrc64, out, ops, [&](const uint8_t* p, uint64_t len, uint8_t* f) { xzenc_le64(f, crc64(p, len)); },
+                      info);
 }
 
 } // namespace snaphash

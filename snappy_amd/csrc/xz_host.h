@@ -1,6 +1,6 @@
 // xz_host.h -- the host half of the data.tar.xz side: the Blocks of a planned .xz buffer (xz_core.h) decoded on host
 // threads, a Block a thread, each straight to its final offset with its Check taken by the thread that decoded it; the
-// host's CRC-64/XZ (slice-by-8) and a small SHA-256 for Check id 10.  Internal; the public entry points are
+// host's CRC-64/XZ (slice-by-8) and the SHA-256 of sha256_core.h for Check id 10.  Internal; the public entry points are
 // snaphash_unxz_buffer / snaphash_tar_unpack_xz (include/snaphash.h).
 #pragma once
 #include <stddef.h>

@@ -6,10 +6,11 @@
 // stream is cut into Blocks of block_size bytes (1 MiB unless the caller says otherwise) and every Block into LZMA2 chunks
 // of 65 536 bytes that reset the coder state but keep the Block's dictionary (xz_enc_core.h): lzma_chains_kernel links
 // every Block's hash chains, lzma2_chunks_kernel codes every chunk of the slot side by side, lzma2_concat_kernel puts
-// headers and bodies in their final places, and the Blocks' CRC-64 Checks come from the kernels the install side uses
-// (crc_kernels.hip), over the staged bytes in HBM.  The host writes what is left: Block headers, padding, Checks, the
-// Index and the footer.  A Block never spans two staging slots; a slot's last Block may be short.  The file is one the
-// library's own install side (unxz.inc) decodes a Block a thread or a Block a workgroup.
+// headers and bodies in their final places, and the Blocks' Checks -- CRC-64 unless the caller names CRC-32, SHA-256 or
+// none -- come from the kernels the install side uses (crc_kernels.hip, sha256_kernels.hip), over the staged bytes in HBM.
+// The host writes what is left: Block headers, padding, Checks, the Index and the footer.  A Block never spans two staging
+// slots; a slot's last Block may be short.  The file is one the library's own install side (unxz.inc) decodes a Block a
+// thread or a Block a workgroup.
 
 namespace {
 
@@ -38,7 +39,7 @@ int ensure_xzenc(DevCtx* c, uint64_t slot_bytes)
 void xz_header(GzPipe& g)
 {
     uint8_t h[kXzEncStreamHeader];
-    xzenc_stream_header(h);
+    xzenc_stream_header(h, g.xz_check);
     g.xz_recs.clear();
     gz_emit(g, h, sizeof h, -1);
 }
@@ -79,7 +80,9 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     HIP_TRY(c, hipStreamSynchronize(zs));
     // where everything goes: a Block after the other, a chunk after the other
     std::vector<XzEncBlockLayout> lay(nblk);
-    std::vector<uint64_t> at(nblk), offs(nblk), lens(nblk), crcs(nblk);
+    const uint32_t check = g.xz_check, check_size = xzenc_check_size(check);
+    std::vector<uint64_t> at(nblk), offs(nblk), lens(nblk);
+    std::vector<uint8_t> fields((size_t)nblk * kXzEncCheckMax); // a Block's Check field as the file holds it
     uint64_t total = 0;
     for (uint32_t k = 0; k < nblk; ++k) {
         const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
@@ -89,7 +92,7 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
             if (!xzenc_res_valid(usize, b.res.h[ch0 + i])) return fail(c, SNAPHASH_EDEVICE, "xz: the chunk kernel reported an impossible size");
             g.st.stored_chunks += b.res.h[ch0 + i] == kXzEncStored;
         }
-        lay[k] = xzenc_block_layout(b.res.h.data() + ch0, cn, blen, b.dst.h.data() + ch0);
+        lay[k] = xzenc_block_layout(b.res.h.data() + ch0, cn, blen, b.dst.h.data() + ch0, check);
         for (uint32_t i = 0; i < cn; ++i) b.dst.h[ch0 + i] += total;
         at[k] = total;
         offs[k] = b0;
@@ -107,9 +110,25 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     HIP_TRY(c, launch_lzma2_concat(sl.d_buf.data(), n, (uint32_t)bs, b.d_slots.data(), b.res.d.data(), b.dst.d.data(), b.d_out.data(), nch, zs));
     HIP_TRY(c, hipEventRecord(ev2.b, zs));
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), total, hipMemcpyDeviceToHost, zs));
-    // the Blocks' Checks, from the staged bytes in HBM (it waits for the stream: the piece is back when it returns)
+    // the Blocks' Checks, from the staged bytes in HBM by the Check's kernel (each waits for the stream: the piece is back
+    // when it returns; with no Check the stream is waited for here)
     double crc_ms = 0;
-    const int rc = crc_ranges_dev(c, 0, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+    int rc = SNAPHASH_OK;
+    if (check == kXzCheckCrc64) {
+        std::vector<uint64_t> crcs(nblk);
+        rc = crc_ranges_dev(c, 0, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+        for (uint32_t k = 0; k < nblk && !rc; ++k) xzenc_le64(fields.data() + (size_t)k * kXzEncCheckMax, crcs[k]);
+    } else if (check == kXzCheckCrc32) {
+        std::vector<uint32_t> crcs(nblk);
+        rc = crc_ranges_dev(c, kCrcGzip, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+        for (uint32_t k = 0; k < nblk && !rc; ++k) xzenc_le32(fields.data() + (size_t)k * kXzEncCheckMax, crcs[k]);
+    } else if (check == kXzCheckSha256) {
+        std::vector<uint8_t> dig((size_t)nblk * kSha256Digest);
+        rc = sha256_ranges_dev(c, sl.d_buf.data(), offs.data(), lens.data(), nblk, dig.data(), zs, &crc_ms);
+        for (uint32_t k = 0; k < nblk && !rc; ++k) memcpy(fields.data() + (size_t)k * kXzEncCheckMax, dig.data() + (size_t)k * kSha256Digest, kSha256Digest);
+    } else {
+        HIP_TRY(c, hipStreamSynchronize(zs));
+    }
     if (rc) return rc;
     if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
         float chains = 0, concat = 0, sum = 0, longest = 0;
@@ -122,14 +141,12 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
             longest = std::max(longest, ms);
         }
         fprintf(stderr, "snaphash xz: slot of %llu bytes, %u blocks, %u chunks: chains %.3f ms, chunks %.3f ms in %zu launch(es) (longest %.3f), "
-                        "concat %.3f ms, crc64 %.3f ms\n", (unsigned long long)n, nblk, nch, chains, sum, evl.size(), longest, concat, crc_ms);
+                        "concat %.3f ms, %s %.3f ms\n", (unsigned long long)n, nblk, nch, chains, sum, evl.size(), longest, concat,
+                check == kXzCheckSha256 ? "sha256" : check == kXzCheckCrc32 ? "crc32" : check == kXzCheckNone ? "no check" : "crc64", crc_ms);
     }
     const uint32_t dict_byte = xzenc_dict_byte(bs);
     for (uint32_t k = 0; k < nblk; ++k) {
-        uint8_t* q = h + at[k];
-        xzenc_block_header(q, lay[k].data, lens[k], dict_byte);
-        for (uint64_t z = lay[k].hdr + lay[k].data; z < lay[k].check_at; ++z) q[z] = 0; // the Block Padding
-        xzenc_le64(q + lay[k].check_at, crcs[k]);
+        xzenc_block_frame(h + at[k], lay[k], lens[k], dict_byte, fields.data() + (size_t)k * kXzEncCheckMax, check_size);
         g.xz_recs.push_back(XzEncRecord{lay[k].unpadded, lens[k]});
     }
     gz_emit(g, h, total, zbuf);
@@ -142,7 +159,7 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
 int xz_finish(GzPipe& g, uint8_t archive_digest[64])
 {
     std::vector<uint8_t> tail;
-    xzenc_index_footer(g.xz_recs, tail);
+    xzenc_index_footer(g.xz_recs, tail, g.xz_check);
     gz_emit(g, tail.data(), tail.size(), -1);
     gz_join(g);
     if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
@@ -194,15 +211,13 @@ int xz_encode_stages(DevCtx* c, const uint8_t* d_in, uint64_t n, uint64_t bs, ui
 
 const TarCodec kXzCodec = {".xz", false, xz_slot_bytes, ensure_xzenc, xz_header, xz_process_slot, xz_finish};
 
-} // namespace
-
-extern "C" {
-
-int snaphash_xz_buffer(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, void** xz_out, size_t* xz_len)
+// the body of snaphash_xz_buffer / snaphash_xz_buffer_check
+int xz_buffer_entry(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, uint32_t check, void** xz_out, size_t* xz_len)
 try {
     if (!x || (!data && n) || !xz_out || !xz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
     *xz_out = nullptr;
     *xz_len = 0;
+    if (!xzenc_check_valid(check)) return fail(x, SNAPHASH_EINVAL, "xz: the Check is 0 (none), 1 (CRC-32), 4 (CRC-64) or 10 (SHA-256)");
     if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
     TOP_ENTER(x);
     DevCtx* c = x->d0();
@@ -218,6 +233,7 @@ try {
     g.mem = &out;
     gz_begin(g);
     g.xz_block_size = block_size;
+    g.xz_check = check;
     xz_header(g);
     Slot& sl = c->slot[0];
     const double t0 = now_ms();
@@ -251,6 +267,20 @@ try {
     return SNAPHASH_OK;
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
+}
+
+} // namespace
+
+extern "C" {
+
+int snaphash_xz_buffer(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, void** xz_out, size_t* xz_len)
+{
+    return xz_buffer_entry(x, data, n, block_size, kXzCheckCrc64, xz_out, xz_len);
+}
+
+int snaphash_xz_buffer_check(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, uint32_t check, void** xz_out, size_t* xz_len)
+{
+    return xz_buffer_entry(x, data, n, block_size, check, xz_out, xz_len);
 }
 
 int snaphash_xzenc_stages_device(snaphash_ctx* x, const void* d_in, size_t n, uint64_t block_size, uint32_t launch_chunks, void* d_prev,
