@@ -210,6 +210,32 @@ int snaphash_sha512_device(snaphash_ctx *ctx, const void *d_base, const uint64_t
                            const uint64_t *lens, size_t n, void *d_digests);
 int snaphash_sync(snaphash_ctx *ctx);
 
+/* One SHA-512 kernel alone over a job table of the caller's, on the caller's HBM: a test instrument, as
+ * snaphash_xzenc_stages_device is one.  A job is one segment of one stream, what the library's own planners hand the
+ * kernels (its internal Job, field for field). */
+typedef struct snaphash_sha512_job {
+    uint64_t data;       /* device address of the segment's first byte, 16-byte aligned */
+    uint64_t nbytes;     /* bytes in this segment, < 32 GiB; a multiple of 128 unless the job is final */
+    uint64_t total_prev; /* bytes of this stream hashed by earlier segments (the padding's length is total_prev + nbytes,
+                          * a 64-bit byte count) */
+    uint32_t idx;        /* the stream's row in d_state and d_digests */
+    uint32_t flags;      /* SNAPHASH_JOB_FIRST | SNAPHASH_JOB_FINAL */
+} snaphash_sha512_job;
+#define SNAPHASH_JOB_FIRST 1u /* start from the initial hash value; otherwise from d_state[idx] */
+#define SNAPHASH_JOB_FINAL 2u /* pad and write the digest to d_digests[idx]; otherwise the chaining value to d_state[idx] */
+/* jobs[0..n) (host) go up in the caller's order -- NOT sorted longest first, as every other entry sorts them -- and
+ * exactly one kernel runs over the whole table: kernel is SNAPHASH_KERNEL_WIDE, _SPLIT or _PAIR (_QUAD in a build that has
+ * it); staged != 0 launches PAIR under its second name, sha512_pair_staged_kernel (other kernels have one name).
+ * d_state: n_rows * 8 uint64 (a row's chaining value in host byte order), 8-byte aligned; d_digests: n_rows * 64 bytes,
+ * 16-byte aligned.  A final job reads (unless first) its state row and writes its digest row; any other job writes its
+ * state row; no other row and no byte outside the two arrays is written.  The kernels fetch 16 bytes at a time:
+ * [data, data + round_up(nbytes, 16)) must be readable.  SNAPHASH_EINVAL: SNAPHASH_KERNEL_AUTO or an unknown kernel, an
+ * address not 16-byte aligned, nbytes >= 2^35, a job that is not final whose nbytes is not a multiple of 128 or which is
+ * first and empty (no planner builds one: there is nothing to carry yet), unknown flag bits, idx >= n_rows, two jobs with
+ * one idx, a misaligned array, a streaming batch open on the ctx.  n == 0 does nothing.  Synchronous. */
+int snaphash_sha512_jobs_device(snaphash_ctx *ctx, uint32_t kernel, int staged, const snaphash_sha512_job *jobs, size_t n,
+                                size_t n_rows, void *d_state, void *d_digests);
+
 /* ---- the pass: writeHashes / getHashes / Verify ----------------------------- */
 
 /* writeHashes (build.go:216-270) minus the file write (north_star "getHashes"):

@@ -54,7 +54,10 @@ EXPORTS = [
     "snaphash_deflate_codes_device",
     # the .xz encoder's kernels alone
     "snaphash_xzenc_stages_device",
+    # a SHA-512 kernel alone, over a caller's job table
+    "snaphash_sha512_jobs_device",
 ]
+JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
 FLAG_SPLIT_BLOCKS = 64  # gunzip_buffer / tar_unpack: cut streams without flush points at their DEFLATE blocks too
@@ -112,6 +115,11 @@ class TargzStats(ctypes.Structure):
     _fields_ = [("tar_bytes", ctypes.c_uint64), ("gz_bytes", ctypes.c_uint64), ("members", ctypes.c_uint64),
                 ("chunks", ctypes.c_uint64), ("stored_chunks", ctypes.c_uint64), ("deflate_ms", ctypes.c_double),
                 ("fill_ms", ctypes.c_double), ("wall_ms", ctypes.c_double)]
+
+
+class Sha512Job(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_uint64), ("nbytes", ctypes.c_uint64), ("total_prev", ctypes.c_uint64), ("idx", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
 
 
 class XzCheckStats(ctypes.Structure):
@@ -245,6 +253,7 @@ def lib():
     L.snaphash_xz_buffer_check.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_unxz_block_device.argtypes = [vp, vp, sz, sz, vp, sz]
     L.snaphash_xzenc_stages_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, sz, u64p]
+    L.snaphash_sha512_jobs_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(Sha512Job), sz, sz, vp, vp]
     L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.snaphash_snap_close.argtypes = [vp]
     L.snaphash_snap_close.restype = None
@@ -581,6 +590,13 @@ class Context:
         self._check(lib().snaphash_xzenc_stages_device(self._h, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst,
                                                        d_out, out_cap, tot))
         return list(tot[:(n + bs - 1) // bs])
+
+    def sha512_jobs_device(self, kernel, jobs, n_rows, d_state, d_digests, staged=False):
+        """One SHA-512 kernel (KERNEL_WIDE / _SPLIT / _PAIR; staged: PAIR under its second name) alone over a job table in
+        the caller's order.  jobs: (device address, nbytes, total_prev, idx, flags) tuples, flags JOB_FIRST | JOB_FINAL;
+        d_state / d_digests: device addresses (ints) of n_rows rows of 8 uint64 / 64 bytes.  Synchronous."""
+        tab = (Sha512Job * max(len(jobs), 1))(*[Sha512Job(*j) for j in jobs])
+        self._check(lib().snaphash_sha512_jobs_device(self._h, kernel, 1 if staged else 0, tab, len(jobs), n_rows, d_state, d_digests))
 
     def crc64_device(self, d_base, offsets, lens):
         """CRC-64/XZ of byte ranges resident in HBM.  d_base: device address (int); offsets / lens: contiguous numpy

@@ -1445,6 +1445,66 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+// Test instrument (tests/test_gpu_sha512_edges.py): one kernel over the caller's job table as it stands.  launch_jobs, the
+// product's path, sorts every table longest first and picks the kernel; this entry does neither, so that a test can put
+// any stream on any lane.
+static_assert(sizeof(snaphash_sha512_job) == sizeof(Job), "the public job is the kernels' Job");
+static_assert(SNAPHASH_JOB_FIRST == kJobFirst && SNAPHASH_JOB_FINAL == kJobFinal, "the public flags are the kernels'");
+
+int snaphash_sha512_jobs_device(snaphash_ctx* x, uint32_t kernel, int staged, const snaphash_sha512_job* jobs, size_t n, size_t n_rows,
+                                void* d_state, void* d_digests)
+try {
+    if (!x || (n && (!jobs || !d_state || !d_digests))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (x->open_batch) return fail(x, SNAPHASH_EINVAL, "a streaming batch is open on this ctx");
+    if (kernel != SNAPHASH_KERNEL_WIDE && kernel != SNAPHASH_KERNEL_SPLIT && kernel != SNAPHASH_KERNEL_PAIR &&
+        !(kernel == SNAPHASH_KERNEL_QUAD && have_quad_kernel()))
+        return fail(x, SNAPHASH_EINVAL, "sha512 jobs: the kernel is WIDE, SPLIT or PAIR (QUAD in a build that has it)");
+    if (n > 0xffffffffull || n_rows > 0xffffffffull) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: too many jobs or rows");
+    if (((uintptr_t)d_state & 7) != 0 || ((uintptr_t)d_digests & 15) != 0) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: d_state must be 8-byte, d_digests 16-byte aligned");
+    std::vector<bool> named(n_rows, false);
+    for (size_t i = 0; i < n; ++i) {
+        const snaphash_sha512_job& j = jobs[i];
+        const bool fin = (j.flags & SNAPHASH_JOB_FINAL) != 0;
+        if (j.flags & ~(SNAPHASH_JOB_FIRST | SNAPHASH_JOB_FINAL)) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: unknown flag bits");
+        if (j.data & 15) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: a segment's address must be 16-byte aligned");
+        if (j.nbytes >> 35) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: a segment is limited to 32 GiB (32-bit block counters)");
+        if (!fin && (j.nbytes & 127)) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: a segment that is not final is a whole number of blocks");
+        if (!fin && (j.flags & SNAPHASH_JOB_FIRST) && j.nbytes == 0) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: a first segment that is not final holds a block at least");
+        if (j.idx >= n_rows) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: idx is not a row");
+        if (named[j.idx]) return fail(x, SNAPHASH_EINVAL, "sha512 jobs: two jobs name one row");
+        named[j.idx] = true;
+    }
+    if (n == 0) return SNAPHASH_OK;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    auto run = [&]() -> int {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, c->hash.jobs.ensure(n));
+        Job* h = c->hash.jobs.h.data();
+        for (size_t i = 0; i < n; ++i) h[i] = Job{jobs[i].data, jobs[i].nbytes, jobs[i].total_prev, jobs[i].idx, jobs[i].flags};
+        HIP_TRY(c, hipMemcpyAsync(c->hash.jobs.d.data(), h, n * sizeof(Job), hipMemcpyHostToDevice, c->stream));
+        const Job* d = c->hash.jobs.d.data();
+        hipError_t e;
+        if (kernel == SNAPHASH_KERNEL_QUAD) e = launch_quad(d, (uint32_t)n, (uint64_t*)d_state, (uint8_t*)d_digests, c->stream);
+        else if (kernel == SNAPHASH_KERNEL_PAIR) e = launch_pair(d, (uint32_t)n, (uint64_t*)d_state, (uint8_t*)d_digests, c->stream, staged != 0);
+        else if (kernel == SNAPHASH_KERNEL_SPLIT) e = launch_split(d, (uint32_t)n, (uint64_t*)d_state, (uint8_t*)d_digests, c->stream);
+        else e = launch_wide(d, (uint32_t)n, (uint64_t*)d_state, (uint8_t*)d_digests, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream); // (the pinned table is read by a copy still in flight)
+        if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+        HIP_TRY(c, es);
+        return SNAPHASH_OK;
+    };
+    const int rc = run();
+    if (rc) return lift(x, c, rc);
+    x->stats.launches = 1;
+    x->stats.kernel_used = kernel;
+    x->stats.streams = n;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
 int snaphash_sync(snaphash_ctx* x)
 try {
     if (!x) return SNAPHASH_EINVAL;

@@ -50,8 +50,24 @@ extern "C" void core_sha512(const uint8_t* data, uint64_t len, uint64_t split, u
         for (int b = 0; b < 8; ++b) out[8 * i + b] = (uint8_t)(H[i] >> (56 - 8 * b));
 }
 
+// one segment as a kernel lane walks it, from the caller's chaining value and byte count: what a Job describes
+extern "C" void core_segment(uint64_t H[8], const uint8_t* data, uint64_t nbytes, uint64_t total_prev, int fin)
+{
+    run_segment(H, data, nbytes, total_prev, fin != 0);
+}
+
 // ---- the library's host SHA-512 (hostsha.cpp: hybrid scheduling only) -----------------------
 #include "../snappy_amd/csrc/hostsha.cpp"
+
+// a stream taken over after total_prev bytes with the chaining value H, its last n bytes hashed here (in two updates)
+extern "C" void hostsha_resume_final(const uint64_t H[8], uint64_t total_prev, const uint8_t* data, uint64_t n, uint8_t* out)
+{
+    HostSha s;
+    host_sha512_resume(s, H, total_prev);
+    host_sha512_update(s, data, n / 3);
+    host_sha512_update(s, data + n / 3, n - n / 3);
+    host_sha512_final(s, out);
+}
 
 // one-shot, optionally resumed at `split` (a multiple of 128) from the state after the prefix
 extern "C" void hostsha_buffer(const uint8_t* data, uint64_t n, uint64_t split, uint8_t* out)

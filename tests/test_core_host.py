@@ -55,6 +55,62 @@ def test_round_constants_from_first_principles():
     assert [int(x, 16) for x in re.findall(r"0x([0-9a-f]{16})ULL", iv[:iv.index("};")])] == IV
 
 
+def test_plain_python_reference_vs_hashlib():
+    """tests/sha512_ref.py, which the tests below and tests/test_gpu_sha512_edges.py compare with, against hashlib.sha512:
+    every length 0..300, and a 753-byte message cut at every block boundary, the chaining value carried over the cut."""
+    import hashlib
+    import sha512_ref as ref
+    rnd = os.urandom(753)
+    for n in range(301):
+        assert ref.digest(ref.segment(ref.IV, rnd[:n], 0, True)) == hashlib.sha512(rnd[:n]).digest(), n
+    for cut in range(0, 753, 128):
+        H = ref.segment(ref.IV, rnd[:cut], 0, False)
+        assert ref.digest(ref.segment(H, rnd[cut:], cut, True)) == hashlib.sha512(rnd).digest(), cut
+    for cut in range(128, 753, 128):  # and at two of them
+        H = ref.segment(ref.segment(ref.IV, rnd[:128], 0, False), rnd[128:cut], 128, False)
+        assert ref.digest(ref.segment(H, rnd[cut:], cut, True)) == hashlib.sha512(rnd).digest(), cut
+
+
+# byte counts a stream has behind it when a segment starts: none, a block, around the 2^32 bits and the 2^32 bytes of a
+# 32-bit counter, 5 GiB, the longest resident segment, around 2^61 (where the bit length enters its high word) and the end
+# of the 64-bit counter -- the last four no caller reaches, Job.total_prev holds them all the same
+TOTAL_PREV = [0, 128, (1 << 29) - 128, 1 << 29, (1 << 32) - 128, 1 << 32, (1 << 32) + 128, 5 << 30, (1 << 35) - 128,
+              (1 << 61) - 128, 1 << 61, (1 << 61) + (1 << 32), (1 << 64) - 256]
+TAIL_BYTES = [0, 5, 111, 112, 127, 128, 300]
+
+
+def test_segment_from_any_state_and_byte_count(tmp_path):
+    """run_segment (sha512_core.h as a kernel lane walks it) and host_sha512_resume + update + final, each from a random
+    chaining value and every byte count of TOTAL_PREV, over every tail of TAIL_BYTES, final: the plain-Python reference's
+    digest.  The two length words of the padding are what this is about."""
+    import random
+    import sha512_ref as ref
+    so = str(tmp_path / "libcorehost.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "core_host_harness.cpp"), "-pthread"])
+    L = ctypes.CDLL(so)
+    H8 = ctypes.c_uint64 * 8
+    L.core_segment.argtypes = [H8, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    L.core_segment.restype = None
+    L.hostsha_resume_final.argtypes = [H8, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+    L.hostsha_resume_final.restype = None
+    rng = random.Random(512)
+    out = ctypes.create_string_buffer(64)
+    for total_prev in TOTAL_PREV:
+        for n in TAIL_BYTES:
+            H0 = [rng.getrandbits(64) for _ in range(8)]
+            data = rng.randbytes(n)
+            want = ref.digest(ref.segment(H0, data, total_prev, True))
+            H = H8(*H0)
+            L.core_segment(H, data, n, total_prev, 1)
+            assert ref.digest(list(H)) == want, ("run_segment", total_prev, n)
+            L.hostsha_resume_final(H8(*H0), total_prev, data, n, out)
+            assert out.raw == want, ("host_sha512_resume", total_prev, n)
+            if n % 128 == 0:  # not final: the byte count plays no part
+                H = H8(*H0)
+                L.core_segment(H, data, n, total_prev, 0)
+                assert list(H) == ref.segment(H0, data, total_prev, False), ("run_segment, not final", total_prev, n)
+
+
 def test_host_sha512_of_the_hybrid_scheduler(core, tmp_path_factory):
     """snappy_amd/csrc/hostsha.cpp (the library's own host SHA-512, used only when host_threads > 0):
     every tail length, resumed mid-stream from a chaining value, and the file reader's size check."""
