@@ -9,6 +9,8 @@
 // MetaMember call does): the engine counts the decodes that wrote it (DevCtx::fout_gen), and a session whose stream is no
 // longer there copies it up again from host memory -- it is never decoded twice.
 
+#include "tar_core.h"
+
 struct snaphash_snap {
     snaphash_ctx* x = nullptr;
     std::string path;
@@ -81,6 +83,7 @@ int snap_member(snaphash_snap* s, snaphash_snap::Tar& t, const std::string& want
     for (const TarEntry& e : t.ents)
         if (e.name == want) hit = &e;
     if (!hit) return SNAPHASH_OK;
+    if (hit->data_off > t.tar.size() || hit->size > t.tar.size() - hit->data_off) return fail(s->x, SNAPHASH_EFORMAT, "tar: member outside the stream");
     void* p = malloc(hit->size ? (size_t)hit->size : 1);
     if (!p) return fail(s->x, SNAPHASH_ENOMEM, "malloc");
     if (hit->size) memcpy(p, t.tar.data() + hit->data_off, (size_t)hit->size);

@@ -1,7 +1,7 @@
 // unpack.inc -- the install side (SURVEY sec. 8 row f5), textually part of snaphash_api.cpp (it uses the engine's
 // streams, events, the hashing kernels and Verify's comparison).  It owns what every data-member format shares --
-// DecodedStream (where decoded bytes live, on the host and in HBM), the codec table's type, the tar reader, the member
-// writer, the members' digests and the Verify tail -- and the gzip decoder; unbz2.inc and unxz.inc add a decoder each,
+// DecodedStream (where decoded bytes live, on the host and in HBM), the codec table's type, the member writer (the tar
+// reader it trusts is tar_core.h, host-only), the members' digests and the Verify tail -- and the gzip decoder; unbz2.inc and unxz.inc add a decoder each,
 // snap.inc the .snap session that drives them.
 //
 // The reference unpacks a package with ClickDeb.Unpack (clickdeb/deb.go:188-203): gzip.NewReader (deb.go:427) -- one Go
@@ -9,6 +9,8 @@
 // the Verify hook (snappy/click.go:955-970) then reads every file of the unpacked tree again.  Here the archive is
 // decoded by the GPU inflate (inflate_kernels.hip) into HBM, written out from there, and -- with hashes.yaml -- every
 // regular member is hashed out of the decoded stream that is already in HBM: nothing is read back from disk.
+
+#include "tar_core.h"
 
 namespace {
 
@@ -626,146 +628,8 @@ const UnpackCodec kGunzipCodec = {"gzip", gunzip_engine};
 
 // ---- the tar side: archive/tar's reader as UnpackTar drives it ---------------------------------------------------------
 
-struct TarEntry {
-    std::string name;     // after clickVerifyContentFn (filepath.Clean)
-    std::string linkname;
-    char type = '0';
-    uint32_t mode = 0;    // permission and set-id bits
-    uint64_t size = 0;
-    uint64_t data_off = 0;
-};
-
-// Go's filepath.Clean (path/filepath, Unix)
-std::string go_clean(const std::string& p)
-{
-    if (p.empty()) return ".";
-    const bool rooted = p[0] == '/';
-    std::vector<std::string> parts;
-    size_t i = 0;
-    while (i < p.size()) {
-        size_t j = p.find('/', i);
-        if (j == std::string::npos) j = p.size();
-        const std::string e = p.substr(i, j - i);
-        i = j + 1;
-        if (e.empty() || e == ".") continue;
-        if (e == "..") {
-            if (!parts.empty() && parts.back() != "..") parts.pop_back();
-            else if (!rooted) parts.push_back("..");
-            continue;
-        }
-        parts.push_back(e);
-    }
-    std::string r = rooted ? "/" : "";
-    for (size_t k = 0; k < parts.size(); ++k) r += (k ? "/" : "") + parts[k];
-    return r.empty() ? "." : r;
-}
-
-bool tar_octal(const uint8_t* f, size_t w, uint64_t* v)
-{
-    if (f[0] & 0x80) { // base-256 (archive/tar's parseNumeric)
-        uint64_t x = f[0] & 0x7f;
-        for (size_t i = 1; i < w; ++i) { if (x >> 55) return false; x = x << 8 | f[i]; }
-        *v = x;
-        return true;
-    }
-    size_t i = 0;
-    while (i < w && (f[i] == ' ' || f[i] == 0)) ++i;
-    uint64_t x = 0;
-    for (; i < w && f[i] >= '0' && f[i] <= '7'; ++i) { if (x >> 60) return false; x = x * 8 + (f[i] - '0'); }
-    for (; i < w; ++i) if (f[i] != ' ' && f[i] != 0) return false;
-    *v = x;
-    return true;
-}
-
-std::string tar_str(const uint8_t* f, size_t w)
-{
-    size_t k = 0;
-    while (k < w && f[k]) ++k;
-    return std::string((const char*)f, k);
-}
-
-// the members of the tar stream t[0..n); SNAPHASH_EFORMAT for a stream archive/tar refuses, SNAPHASH_ECONTENT for a
-// name with ".." or a member type UnpackTar does not create
-int tar_read(const uint8_t* t, uint64_t n, std::vector<TarEntry>& ents, std::string& why)
-{
-    uint64_t at = 0;
-    std::string pax_path, pax_link, gnu_name, gnu_link;
-    bool pax_size = false;
-    uint64_t pax_sz = 0;
-    static const uint8_t zero[512] = {0};
-    for (;;) {
-        if (at == n) return 0; // (io.EOF at a record boundary)
-        if (at + 512 > n) { why = "tar: truncated header"; return SNAPHASH_EFORMAT; }
-        const uint8_t* hd = t + at;
-        if (!memcmp(hd, zero, 512)) {
-            if (at + 1024 <= n && memcmp(hd + 512, zero, 512)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
-            return 0;
-        }
-        uint64_t chk = 0;
-        if (!tar_octal(hd + 148, 8, &chk)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
-        int64_t su = 0, ss = 0;
-        for (int i = 0; i < 512; ++i) {
-            const uint8_t b = (i >= 148 && i < 156) ? ' ' : hd[i];
-            su += b;
-            ss += (int8_t)b;
-        }
-        if ((int64_t)chk != su && (int64_t)chk != ss) { why = "tar: header checksum"; return SNAPHASH_EFORMAT; }
-        uint64_t size = 0, mode = 0;
-        if (!tar_octal(hd + 124, 12, &size) || !tar_octal(hd + 100, 8, &mode)) { why = "tar: invalid header"; return SNAPHASH_EFORMAT; }
-        const char type = (char)hd[156];
-        if (pax_size) size = pax_sz;
-        const uint64_t data = at + 512;
-        const bool has_data = type == '0' || type == 0 || type == '7' || type == 'x' || type == 'L' || type == 'K' || type == 'g';
-        const uint64_t padded = has_data ? (size + 511) & ~(uint64_t)511 : 0; // (links, devices, directories: no content)
-        if (data + padded > n) { why = "tar: truncated member"; return SNAPHASH_EFORMAT; }
-        if (type == 'x' || type == 'L' || type == 'K') {
-            const std::string body((const char*)t + data, (size_t)size);
-            if (type == 'L') gnu_name = tar_str((const uint8_t*)body.data(), body.size());
-            else if (type == 'K') gnu_link = tar_str((const uint8_t*)body.data(), body.size());
-            else { // records "<len> <key>=<value>\n" (archive/tar parsePAX)
-                size_t p = 0;
-                while (p < body.size()) {
-                    size_t sp = body.find(' ', p);
-                    if (sp == std::string::npos) { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
-                    const uint64_t len = strtoull(body.substr(p, sp - p).c_str(), nullptr, 10);
-                    if (len < sp - p + 3 || p + len > body.size() || body[p + len - 1] != '\n') { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
-                    const std::string kv = body.substr(sp + 1, p + len - 1 - (sp + 1));
-                    const size_t eq = kv.find('=');
-                    if (eq == std::string::npos) { why = "tar: invalid PAX record"; return SNAPHASH_EFORMAT; }
-                    const std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
-                    if (k == "path") pax_path = v;
-                    else if (k == "linkpath") pax_link = v;
-                    else if (k == "size") { pax_size = true; pax_sz = strtoull(v.c_str(), nullptr, 10); }
-                    p += len;
-                }
-            }
-            at = data + padded;
-            continue;
-        }
-        TarEntry e;
-        std::string name = tar_str(hd, 100);
-        if (!memcmp(hd + 257, "ustar", 5)) {
-            const std::string prefix = tar_str(hd + 345, 155);
-            if (!prefix.empty()) name = prefix + "/" + name;
-        }
-        if (!gnu_name.empty()) name = gnu_name;
-        if (!pax_path.empty()) name = pax_path;
-        e.linkname = tar_str(hd + 157, 100);
-        if (!gnu_link.empty()) e.linkname = gnu_link;
-        if (!pax_link.empty()) e.linkname = pax_link;
-        pax_path.clear(); pax_link.clear(); gnu_name.clear(); gnu_link.clear();
-        pax_size = false;
-        e.name = go_clean(name);
-        if (e.name.find("..") != std::string::npos) { why = "tar: " + name + ": invalid content"; return SNAPHASH_ECONTENT; }
-        e.type = type == 0 || type == '7' ? '0' : type;
-        if (e.type != '0' && e.type != '2' && e.type != '5') { why = "tar: " + name + ": unsupported member type"; return SNAPHASH_ECONTENT; }
-        e.mode = (uint32_t)(mode & 07777);
-        e.size = e.type == '0' ? size : 0;
-        e.data_off = data;
-        ents.push_back(e);
-        at = data + padded;
-    }
-}
+// (TarEntry, go_clean, tar_read and last_regular_members: tar_core.h)
+static_assert(kTarEFormat == SNAPHASH_EFORMAT && kTarEContent == SNAPHASH_ECONTENT, "tar_core.h restates the two codes");
 
 int mkdir_all(const std::string& dir)
 {
@@ -838,6 +702,8 @@ int hash_members(snaphash_ctx* x, DevCtx* c, const std::vector<uint8_t>& tar, co
                  std::vector<uint8_t>& dig)
 {
     int rc = 0;
+    for (const size_t k : reg) // tar_read's promise (tar_core.h), held again here: the kernels read d_out with no check of their own
+        if (ents[k].data_off > tar.size() || ents[k].size > tar.size() - ents[k].data_off) return fail(x, SNAPHASH_EFORMAT, "tar: member outside the stream");
     dig.assign(reg.size() * 64 + 64, 0);
     std::vector<uint8_t> on_host(reg.size(), 0);
     MemberHashers mh;
@@ -879,18 +745,6 @@ int hash_members(snaphash_ctx* x, DevCtx* c, const std::vector<uint8_t>& tar, co
         for (size_t h = 0; h < hosted.size(); ++h) memcpy(dig.data() + 64 * hosted[h], mh.digests.data() + 64 * h, 64);
     }
     return SNAPHASH_OK;
-}
-
-// the last member of every name that is a regular file (the content an unpack leaves on disk), ascending
-std::vector<size_t> last_regular_members(const std::vector<TarEntry>& ents)
-{
-    std::unordered_map<std::string, size_t> last;
-    for (size_t k = 0; k < ents.size(); ++k) last[ents[k].name] = k;
-    std::vector<size_t> reg;
-    for (const auto& kv : last)
-        if (ents[kv.second].type == '0') reg.push_back(kv.second);
-    std::sort(reg.begin(), reg.end());
-    return reg;
 }
 
 // the SHA-512 of p[0..n) on a host core of its own, beside what its scope does; joined where the scope ends at the latest
