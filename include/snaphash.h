@@ -301,7 +301,10 @@ void snaphash_batch_abort(snaphash_batch *b);
 typedef struct snaphash_targz_stats { /* of the most recent snaphash_tar_create / snaphash_gzip_buffer; after
                                        * snaphash_tar_create_xz / snaphash_xz_buffer: gz_bytes = bytes written, chunks = LZMA2
                                        * chunks of 65 536 bytes, stored_chunks = those written uncompressed, deflate_ms = the
-                                       * chain, chunk, concatenation and CRC-64 kernels */
+                                       * chain, chunk, concatenation and CRC-64 kernels; after
+                                       * snaphash_tar_create_bz2 / snaphash_bzip2_buffer: gz_bytes = bytes written, chunks =
+                                       * bzip2 blocks, stored_chunks = 0 (bzip2 has no stored form), deflate_ms = all encoder
+                                       * kernels (CRC, RLE1, BWT, MTF, coding, concatenation) */
     uint64_t tar_bytes;     /* uncompressed stream */
     uint64_t gz_bytes;      /* bytes written */
     uint64_t members;       /* tar members */
@@ -402,6 +405,31 @@ int snaphash_deflate_codes_device(snaphash_ctx *ctx, const void *d_freq, size_t 
 int snaphash_xzenc_stages_device(snaphash_ctx *ctx, const void *d_in, size_t n, uint64_t block_size, uint32_t launch_chunks,
                                  void *d_prev, void *d_cand, void *d_slots, void *d_res, void *d_dst, void *d_out, size_t out_cap,
                                  uint64_t *block_total);
+
+/* ---- the data.tar.bz2 producer (the one format ClickDeb.Unpack reads, deb.go:185, and tarCreate refuses to write) ---- */
+
+/* One bzip2 stream of a host buffer; level 1..9 (0 = 9), anything else SNAPHASH_EINVAL; n == 0 gives the 14-byte stream
+ * without blocks; *bz_out is malloc'd (snaphash_free).  The input is cut into blocks by INPUT size -- 719 872 bytes at
+ * level 9, 79 872 at level 1: floor((100 000 level - 19) * 4/5 / 512) * 512, what RLE1 can never expand past libbz2's own
+ * block size -- so every block is coded side by side on the GPU: RLE1, the Burrows-Wheeler transform by prefix doubling
+ * with radix passes, move-to-front, libbz2's Huffman scheme (2-6 tables, four refinement rounds, codes of up to 17 bits).
+ * Any bzip2 decoder reads the file, block-parallel ones side by side.  The bytes are a function of (data, level) alone.
+ * The engine's staging size must hold a block's input. */
+int snaphash_bzip2_buffer(snaphash_ctx *ctx, const void *data, size_t n, uint32_t level, void **bz_out, size_t *bz_len);
+
+/* snaphash_tar_create for a data.tar.bz2 (level 9): same walk, tar layout, single read, fused hashes.yaml, host-thread
+ * member digests, late truncation, unlink on failure; tarname must end in ".bz2", else SNAPHASH_EINVAL with
+ * "unknown compression extension".  A block never spans two staging slots.  snaphash_get_targz_stats reports the pass. */
+int snaphash_tar_create_bz2(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
+                            char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
+
+/* Test instrument, like snaphash_deflate_codes_device: the BWT stage alone over n_blocks ranges of a caller's HBM buffer
+ * (offsets / lens: host arrays; each range 1..900 000 bytes, taken as it is: no RLE1), by the kernel the encoder runs.
+ * d_last receives each range's last column of its sorted cyclic rotations at the range's own offset, d_orig_ptr one uint32
+ * per range: the number of rotations that sort before rotation 0 (equal rotations by start index).  No byte outside those
+ * is written, d_in is only read.  Ranges that overlap give undefined last columns.  Synchronous. */
+int snaphash_bwt_device(snaphash_ctx *ctx, const void *d_in, const uint64_t *offsets, const uint64_t *lens, size_t n_blocks,
+                        void *d_last, void *d_orig_ptr);
 
 /* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
 

@@ -56,6 +56,8 @@ EXPORTS = [
     "snaphash_xzenc_stages_device",
     # a SHA-512 kernel alone, over a caller's job table
     "snaphash_sha512_jobs_device",
+    # the data.tar.bz2 producer, and its BWT stage alone
+    "snaphash_bzip2_buffer", "snaphash_tar_create_bz2", "snaphash_bwt_device",
 ]
 JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
@@ -235,6 +237,10 @@ def lib():
     L.snaphash_xz_buffer.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_create_xz.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp),
                                          ctypes.POINTER(sz), ctypes.c_char_p]
+    L.snaphash_bzip2_buffer.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_create_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp),
+                                          ctypes.POINTER(sz), ctypes.c_char_p]
+    L.snaphash_bwt_device.argtypes = [vp, vp, vp, vp, sz, vp, vp]
     L.snaphash_get_targz_stats.argtypes = [vp, ctypes.POINTER(TargzStats)]
     L.snaphash_deflate_codes_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.snaphash_get_targz_stats.restype = None
@@ -455,6 +461,28 @@ class Context:
             return ctypes.string_at(p.value, n.value)
         finally:
             lib().snaphash_free(p)
+
+    def bzip2_buffer(self, data, level=0):
+        """One bzip2 stream of `data` at `level` (1..9; 0: 9), every block coded on the GPU; a block per 719 872 bytes of
+        input at level 9 (79 872 at level 1).  The bytes are a function of (data, level) alone."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
+        self._check(lib().snaphash_bzip2_buffer(self._h, ctypes.addressof(buf), len(data), level, ctypes.byref(p), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(p.value, n.value)
+        finally:
+            lib().snaphash_free(p)
+
+    def tar_create_bz2(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
+        """tar_create with the .bz2 producer (level 9): the format the install side reads and tarCreate refuses to write.
+        -> (yaml bytes or None, archive digest (64 bytes))."""
+        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_bz2")
+
+    def bwt_device(self, d_in, offsets, lens, d_last, d_orig_ptr):
+        """The bzip2 encoder's BWT kernel alone over ranges resident in HBM.  d_in / d_last / d_orig_ptr: device addresses
+        (int); offsets / lens: contiguous numpy uint64 arrays (each range 1..900 000 bytes).  d_last receives each range's
+        last column at the range's offset, d_orig_ptr a uint32 per range."""
+        self._check(lib().snaphash_bwt_device(self._h, d_in, offsets.ctypes.data, lens.ctypes.data, len(offsets), d_last, d_orig_ptr))
 
     def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
         """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.

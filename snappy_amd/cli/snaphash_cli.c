@@ -9,7 +9,10 @@
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
  *   snaphash [options] build-xz BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB, LZMA2 on the GPU
+ *   snaphash [options] build-bz2 BUILD_DIR OUT.tar.bz2
+ *                                      the same with data.tar.bz2 (level 9): every bzip2 block coded on the GPU
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
+ *   snaphash [options] bzip2 [-L LEVEL] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9)
  *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
  *                                                Blocks' Check as named (default crc64), taken on the GPU
@@ -53,6 +56,7 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | build-xz DIR OUT.tar.xz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
+                    "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
                     "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
@@ -181,8 +185,8 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, "verify");
         else printf("OK\n");
         free(y);
-    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz")) && argc == 4) {
-        const int xz = !strcmp(argv[1], "build-xz");
+    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz") || !strcmp(argv[1], "build-bz2")) && argc == 4) {
+        const int xz = !strcmp(argv[1], "build-xz"), bz2 = !strcmp(argv[1], "build-bz2");
         /* the exclude rule is writeHashes' own: every path that starts with <dir>/DEBIAN (build.go:229) */
         size_t dl = strlen(argv[2]);
         while (dl > 1 && argv[2][dl - 1] == '/') dl--;
@@ -194,7 +198,9 @@ int main(int argc, char **argv)
         char *y = NULL;
         size_t len = 0;
         uint8_t dig[64];
-        rc = xz ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig) : snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
+        rc = xz    ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig)
+             : bz2 ? snaphash_tar_create_bz2(c, argv[3], dir, excl, &y, &len, dig)
+                   : snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
         if (rc) ret = die(c, rc, argv[1]);
         else {
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
@@ -215,6 +221,23 @@ int main(int argc, char **argv)
         else {
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[3]); ret = 2; }
+        }
+        snaphash_free(z);
+        free(in);
+    } else if (!strcmp(argv[1], "bzip2") && (argc == 4 || (argc == 6 && !strcmp(argv[2], "-L")))) {
+        size_t len = 0, zl = 0;
+        const int at = argc == 6 ? 4 : 2;
+        char *end = NULL;
+        const unsigned long level = argc == 6 ? strtoul(argv[3], &end, 10) : 9;
+        if (argc == 6 && (*end || !*argv[3] || level < 1 || level > 9)) { snaphash_destroy(c); return usage(); }
+        char *in = slurp(argv[at], &len);
+        if (!in) { snaphash_destroy(c); return 2; }
+        void *z = NULL;
+        rc = snaphash_bzip2_buffer(c, in, len, (uint32_t)level, &z, &zl);
+        if (rc) ret = die(c, rc, "bzip2");
+        else {
+            FILE *f = fopen(argv[at + 1], "wb");
+            if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[at + 1]); ret = 2; }
         }
         snaphash_free(z);
         free(in);

@@ -1,0 +1,243 @@
+// bzpack.inc -- the data.tar.bz2 producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers and
+// staging it shares, and xzpack.inc, whose shape it has).
+//
+// The reference's tarCreate refuses a ".bz2" name (clickdeb/deb.go:274-275) and snaphash_tar_create keeps doing so; this
+// is the writer of the one format the install side reads (ClickDeb.Unpack, deb.go:185) and the library could not write.
+// The staged tar stream is cut into pieces of bzenc_piece(level) bytes, a bzip2 block each (bzip2_enc_core.h), and a
+// staging slot is a whole number of pieces, no more than one launch codes: the blocks' CRCs come from crc_kernels.hip over
+// the staged bytes, bzip2_enc_kernels.hip runs RLE1, the BWT, MTF and the Huffman coding of every block of the slot side by
+// side and shifts their bits together.  The host adds the four bytes in front and the footer, folds the combined CRC, and
+// holds the stream's last partial byte back until the next slot (or the footer) completes it.
+
+namespace {
+
+// blocks of one launch: their BWT scratch together stays under kBzEncLaunchBytes x kBzEncScratchPerByte (0.8 GB)
+uint32_t bz_launch_blocks(uint32_t level) { return (uint32_t)std::min<uint64_t>(kBzEncLaunchBlocksMax, kBzEncLaunchBytes / bzenc_rle_cap(level)); }
+
+// the producer's slot: whole pieces, as many as the job has, the staging size holds and one launch takes (at least one)
+uint64_t bz_slot_bytes_for(const DevCtx* c, uint64_t job_bytes, uint32_t level)
+{
+    const uint64_t P = bzenc_piece(level);
+    const uint64_t want = std::max<uint64_t>(1, (job_bytes + P - 1) / P);
+    return std::max<uint64_t>(1, std::min({want, c->staging / P, (uint64_t)bz_launch_blocks(level)})) * P;
+}
+uint64_t bz_slot_bytes(const DevCtx* c, uint64_t job_bytes) { return bz_slot_bytes_for(c, job_bytes, 9); }
+
+int ensure_bzenc_for(DevCtx* c, uint32_t blocks, uint32_t cap, bool with_output)
+{
+    if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority (ensure_deflate)
+        int least = 0, greatest = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
+    }
+    if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking));
+    HIP_TRY(c, c->be.ensure(blocks, cap, with_output, c->numa_node)); // (a failure leaves none of it)
+    return SNAPHASH_OK;
+}
+int ensure_bzenc(DevCtx* c, uint64_t slot_bytes) { return ensure_bzenc_for(c, (uint32_t)(slot_bytes / bzenc_piece(9)), bzenc_rle_cap(9), true); }
+
+void bz_header(GzPipe& g)
+{
+    const uint8_t h[kBzEncStreamHead] = {'B', 'Z', 'h', (uint8_t)('0' + g.bz_level)};
+    g.bz_crc = g.bz_carry = g.bz_carry_bits = 0;
+    gz_emit(g, h, sizeof h, -1);
+}
+
+// The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream) as
+// blocks into c->be.h_out[zbuf] and on to the consumers.
+int bz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
+{
+    if (n == 0) return SNAPHASH_OK;
+    DevCtx* c = g.c;
+    BzEncBufs& b = c->be;
+    hipStream_t zs = c->z_stream;
+    const uint64_t P = bzenc_piece(g.bz_level);
+    const uint32_t nblk = (uint32_t)((n + P - 1) / P);
+    if (n > sl.cap() || nblk > b.made_blocks || bzenc_rle_cap(g.bz_level) > b.made_cap || !b.h_out[0].size())
+        return fail(c, SNAPHASH_EDEVICE, "bzip2: the encoder's buffers are smaller than the slot");
+    if (ready) HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0));
+    // the blocks' CRCs: over the pieces as they are, before RLE1
+    std::vector<uint64_t> offs(nblk), lens(nblk);
+    std::vector<uint32_t> crcs(nblk);
+    for (uint32_t k = 0; k < nblk; ++k) {
+        offs[k] = (uint64_t)k * P;
+        lens[k] = std::min<uint64_t>(P, n - offs[k]);
+    }
+    double crc_ms = 0;
+    int rc = crc_ranges_dev(c, kCrcBzip2, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
+    if (rc) return rc;
+    for (uint32_t k = 0; k < nblk; ++k) b.jobs.h[k] = BzEncJob{offs[k], (uint32_t)lens[k], crcs[k]};
+    const BzEncScratch s = b.scratch();
+    HIP_TRY(c, hipMemcpyAsync(b.jobs.d.data(), b.jobs.h.data(), (size_t)nblk * sizeof(BzEncJob), hipMemcpyHostToDevice, zs));
+    const bool trace = getenv("SNAPHASH_TRACE_BZ2") != nullptr; // the stages one by one (tools/bzip2_enc_bench.py reads the line)
+    hipEvent_t stage_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{stage_ev};
+    if (trace)
+        for (hipEvent_t& e : stage_ev) HIP_TRY(c, hipEventCreate(&e));
+    EventPair* evp = next_events(c, 2);
+    if (!evp) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const EventPair ev = *evp; // (by value: the pool may grow)
+    HIP_TRY(c, hipEventRecord(ev.a, zs));
+    HIP_TRY(c, launch_bzenc_blocks(sl.d_buf.data(), b.jobs.d.data(), s, nblk, zs, trace ? stage_ev : nullptr));
+    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nblk * sizeof(BzEncRes), hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    // where every block goes: behind the bits the last slot left
+    uint64_t at = g.bz_carry_bits;
+    for (uint32_t k = 0; k < nblk; ++k) {
+        const BzEncRes& r = b.res.h[k];
+        if (r.over || r.bits == 0 || r.bits > (uint64_t)s.slot_words * 32 || r.rle_n == 0 || r.orig_ptr >= r.rle_n)
+            return fail(c, SNAPHASH_EDEVICE, "bzip2: a block's stages reported an impossible result");
+        b.dst.h[k] = at;
+        at += r.bits;
+        g.bz_crc = bz_crc_combine(g.bz_crc, crcs[k]);
+    }
+    const uint64_t out_words = (at + 31) / 32, whole = at / 8;
+    if (out_words > b.d_out.size() || out_words * 4 > b.h_out[zbuf].size()) return fail(c, SNAPHASH_EDEVICE, "bzip2: a slot's output outgrew its buffer");
+    gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
+    uint8_t* h = b.h_out[zbuf].data();
+    HIP_TRY(c, hipMemcpyAsync(b.dst.d.data(), b.dst.h.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, zs));
+    EventPair* evp2 = next_events(c, 2);
+    if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const EventPair ev2 = *evp2;
+    HIP_TRY(c, hipEventRecord(ev2.a, zs));
+    HIP_TRY(c, launch_bzenc_concat(s, b.dst.d.data(), nblk, b.d_out.data(), out_words, g.bz_carry, zs));
+    HIP_TRY(c, hipEventRecord(ev2.b, zs));
+    HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), (size_t)out_words * 4, hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    if (trace) {
+        float ms[4] = {0, 0, 0, 0}, cat = 0;
+        for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], stage_ev[i], stage_ev[i + 1]);
+        (void)hipEventElapsedTime(&cat, ev2.a, ev2.b);
+        fprintf(stderr, "snaphash bz2: slot of %llu bytes, %u blocks: crc %.3f ms, rle1 %.3f ms, bwt %.3f ms, mtf %.3f ms, code %.3f ms, concat %.3f ms\n",
+                (unsigned long long)n, nblk, crc_ms, ms[0], ms[1], ms[2], ms[3], cat);
+    }
+    g.bz_carry_bits = (uint32_t)(at & 7);
+    g.bz_carry = g.bz_carry_bits ? h[whole] : 0u;
+    gz_emit(g, h, whole, zbuf);
+    g.isize += n;
+    g.st.chunks += nblk;
+    return SNAPHASH_OK;
+}
+
+// the end-of-stream magic and the combined CRC behind the held-back bits; -> errno of the first failed write, or 0
+int bz_finish(GzPipe& g, uint8_t archive_digest[64])
+{
+    uint32_t tail[4] = {g.bz_carry & 0xffu, 0, 0, 0}; // (memory in stream order: the held-back byte is byte 0)
+    BzW w;
+    bzw_start(w, tail, 4, g.bz_carry_bits);
+    bzw_put(w, (uint32_t)(kBzEosMagic >> 24), 24);
+    bzw_put(w, (uint32_t)(kBzEosMagic & 0xffffffu), 24);
+    bzw_put(w, g.bz_crc, 32);
+    const uint64_t bytes = (bzw_pos(w) + 7) / 8;
+    bzw_flush(w);
+    gz_emit(g, (const uint8_t*)tail, (size_t)bytes, -1);
+    gz_join(g);
+    if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
+    return g.write_err;
+}
+
+const TarCodec kBz2Codec = {".bz2", false, bz_slot_bytes, ensure_bzenc, bz_header, bz_process_slot, bz_finish};
+
+} // namespace
+
+extern "C" {
+
+int snaphash_bzip2_buffer(snaphash_ctx* x, const void* data, size_t n, uint32_t level, void** bz_out, size_t* bz_len)
+try {
+    if (!x || (!data && n) || !bz_out || !bz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *bz_out = nullptr;
+    *bz_len = 0;
+    level = bzenc_level(level);
+    if (!level) return fail(x, SNAPHASH_EINVAL, "bzip2: the level is 1 to 9, or 0 for 9");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t S = bz_slot_bytes_for(c, n, level);
+    if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "bzip2: a block's input is larger than the engine's staging size");
+    int rc = ensure_slots(c, 2, S);
+    if (!rc) rc = ensure_bzenc_for(c, (uint32_t)(S / bzenc_piece(level)), bzenc_rle_cap(level), true);
+    if (rc) return lift(x, c, rc);
+    std::string out;
+    GzPipe g;
+    g.c = c;
+    g.mem = &out;
+    gz_begin(g);
+    g.bz_level = level;
+    bz_header(g);
+    Slot& sl = c->slot[0];
+    const double t0 = now_ms();
+    for (uint64_t off = 0; off < n && !rc; off += S) {
+        const uint64_t take = std::min<uint64_t>(S, n - off);
+        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
+        EventPair* ev = next_events(c, 1);
+        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
+        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
+            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
+            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
+        rc = bz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
+    }
+    if (!rc && bz_finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
+    if (rc) gz_abort(g);
+    (void)hipStreamSynchronize(c->z_stream);
+    (void)hipStreamSynchronize(c->z2_stream);
+    collect_targz_events(c, g);
+    g.st.tar_bytes = n;
+    g.st.gz_bytes = out.size();
+    g.st.wall_ms = now_ms() - t0;
+    x->targz = g.st;
+    merge_stats(x);
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(out.size() ? out.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    memcpy(p, out.data(), out.size());
+    *bz_out = p;
+    *bz_len = out.size();
+    return SNAPHASH_OK;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_bwt_device(snaphash_ctx* x, const void* d_in, const uint64_t* offsets, const uint64_t* lens, size_t n_blocks, void* d_last,
+                        void* d_orig_ptr)
+try {
+    if (!x || (n_blocks && (!d_in || !offsets || !lens || !d_last || !d_orig_ptr))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    uint32_t cap = 0;
+    for (size_t i = 0; i < n_blocks; ++i) {
+        if (lens[i] < 1 || lens[i] > kBzMaxBlock) return fail(x, SNAPHASH_EINVAL, "bwt: a range is 1 to 900 000 bytes");
+        if (lens[i] > ~0ull - offsets[i]) return fail(x, SNAPHASH_EINVAL, "a range wraps around the address space");
+        cap = std::max(cap, (uint32_t)lens[i]);
+    }
+    if (n_blocks == 0) return SNAPHASH_OK;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    cap = (cap + 63) & ~63u;
+    const uint32_t per = (uint32_t)std::min<uint64_t>({(uint64_t)n_blocks, (uint64_t)kBzEncLaunchBlocksMax, std::max<uint64_t>(1, kBzEncLaunchBytes / cap)});
+    int rc = ensure_bzenc_for(c, per, cap, false);
+    if (rc) return lift(x, c, rc);
+    BzEncBufs& b = c->be;
+    const BzEncScratch s = b.scratch();
+    for (size_t k0 = 0; k0 < n_blocks; k0 += per) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(per, n_blocks - k0);
+        for (uint32_t k = 0; k < nb; ++k) b.bwt_jobs.h[k] = BzBwtJob{offsets[k0 + k], offsets[k0 + k], (uint32_t)lens[k0 + k], 0};
+        HIP_TRY(c, hipMemcpyAsync(b.bwt_jobs.d.data(), b.bwt_jobs.h.data(), (size_t)nb * sizeof(BzBwtJob), hipMemcpyHostToDevice, c->z_stream));
+        HIP_TRY(c, launch_bzenc_bwt((const uint8_t*)d_in, b.bwt_jobs.d.data(), (uint8_t*)d_last, (uint32_t*)d_orig_ptr + k0, s, nb, c->z_stream));
+        HIP_TRY(c, hipStreamSynchronize(c->z_stream)); // (the job table is written again for the next launch)
+    }
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_create_bz2(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix, char** yaml_out,
+                            size_t* yaml_len, uint8_t* archive_digest)
+try {
+    return tar_create_impl(x, kBz2Codec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+} // extern "C"

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "bzip2_host.h"
+#include "bzip2_enc_kernels.h"
 #include "bzip2_kernels.h"
 #include "crc_kernels.h"
 #include "deflate_kernels.h"
@@ -300,6 +301,83 @@ struct XzEncBufs {
         return e;
     }
     template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); }
+};
+
+// GPU bzip2 encoder (bzpack.inc), for `blocks` blocks a launch of up to `cap` bytes each after RLE1: the sort's scratch
+// (kBzEncScratchPerByte bytes a byte), the stages' arrays, the blocks' output slots, the assembled piece and its way back.
+// The dimensions the buffers were made for are kept: a call that fits them allocates nothing, any other frees all of it
+// and allocates for its own (blocks x cap never exceeds kBzEncLaunchBytes: bzpack.inc), and a failure leaves none of it.
+struct BzEncBufs {
+    DevBuf<uint8_t> d_rle, d_last, d_sel;
+    DevBuf<uint64_t> d_key_a, d_key_b;
+    DevBuf<uint32_t> d_idx_a, d_idx_b, d_rank, d_slots, d_out;
+    DevBuf<uint16_t> d_syms;
+    DevBuf<BzEncMap> d_maps;
+    Twin<BzEncJob> jobs;
+    Twin<BzBwtJob> bwt_jobs;
+    Twin<BzEncRes> res;
+    Twin<uint64_t> dst;
+    HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
+    uint32_t made_blocks = 0, made_cap = 0;
+    uint64_t out_words() const { return (uint64_t)made_blocks * bzenc_slot_words(made_cap) + 2; }
+    hipError_t ensure(uint32_t blocks, uint32_t cap, bool with_output, int node)
+    {
+        cap = (cap + 63) & ~63u;
+        if (blocks <= made_blocks && cap <= made_cap) {
+            if (!with_output || h_out[0].size()) return hipSuccess;
+            blocks = made_blocks; // (made for snaphash_bwt_device, which takes no output buffers: they are added)
+            cap = made_cap;
+        } else {
+            each(Release());
+        }
+        const size_t nb = blocks, el = (size_t)blocks * cap, room = (size_t)blocks * (cap + 64);
+        hipError_t e = d_rle.reserve(room);
+        if (!e) e = d_last.reserve(room);
+        if (!e) e = d_syms.reserve(room);
+        if (!e) e = d_key_a.reserve(el);
+        if (!e) e = d_key_b.reserve(el);
+        if (!e) e = d_idx_a.reserve(el);
+        if (!e) e = d_idx_b.reserve(el);
+        if (!e) e = d_rank.reserve(el);
+        if (!e) e = d_maps.reserve(nb);
+        if (!e) e = d_sel.reserve(nb * kBzEncSelStride);
+        if (!e) e = jobs.ensure(nb);
+        if (!e) e = bwt_jobs.ensure(nb);
+        if (!e) e = res.ensure(nb);
+        if (!e) e = dst.ensure(nb);
+        const size_t words = nb * bzenc_slot_words(cap) + 2;
+        if (!e && with_output) {
+            e = d_slots.reserve(words);
+            if (!e) e = d_out.reserve(words);
+            for (HostBuf<uint8_t>& b : h_out)
+                if (!e) e = b.reserve(words * 4, node);
+        }
+        if (e) {
+            each(Release()); // (none of it is left behind)
+            made_blocks = made_cap = 0;
+            return e;
+        }
+        made_blocks = blocks;
+        made_cap = cap;
+        return hipSuccess;
+    }
+    BzEncScratch scratch() const
+    {
+        BzEncScratch s{};
+        s.cap = made_cap;
+        s.slot_words = bzenc_slot_words(made_cap);
+        s.rle = d_rle.data(); s.last = d_last.data();
+        s.key_a = d_key_a.data(); s.key_b = d_key_b.data();
+        s.idx_a = d_idx_a.data(); s.idx_b = d_idx_b.data(); s.rank = d_rank.data();
+        s.syms = d_syms.data(); s.maps = d_maps.data(); s.sel = d_sel.data();
+        s.slots = d_slots.data(); s.bwt_jobs = bwt_jobs.d.data(); s.res = res.d.data();
+        return s;
+    }
+    template <class F> void each(F&& f)
+    {
+        f(d_rle); f(d_last); f(d_sel); f(d_key_a); f(d_key_b); f(d_idx_a); f(d_idx_b); f(d_rank); f(d_slots); f(d_out); f(d_syms); f(d_maps);
+        jobs.each(f); bwt_jobs.each(f); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]);
+    }
 };
 
 } // namespace snaphash

@@ -99,6 +99,7 @@ struct DevCtx {
     Sha256Bufs sha256;
     XzBufs xz;
     XzEncBufs xe; // the .xz producer's (xzpack.inc)
+    BzEncBufs be; // the .bz2 producer's (bzpack.inc)
     hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
     uint64_t fout_gen = 0;          // counts the decodes that wrote inf.d_out: a .snap session knows by it whether its stream is still there
 
@@ -138,6 +139,7 @@ struct DevCtx {
         sha256.each(f);
         xz.each(f);
         xe.each(f);
+        be.each(f);
     }
 };
 
@@ -2503,6 +2505,7 @@ int snaphash_crc64_device(snaphash_ctx* x, const void* d_base, const uint64_t* o
 
 #include "targz.inc"
 #include "xzpack.inc"
+#include "bzpack.inc"
 #include "unpack.inc"
 #include "unbz2.inc"
 #include "unxz.inc"

@@ -60,6 +60,9 @@ struct GzPipe {
     uint64_t xz_block_size = kXzEncBlockDefault;
     uint32_t xz_check = kXzCheckCrc64; // the Blocks' Check (snaphash_xz_buffer_check names another)
     std::vector<XzEncRecord> xz_recs;
+    // the .bz2 producer (bzpack.inc): the level, the combined CRC so far, and the stream's last, partial byte -- held back
+    // until the next slot's blocks (or the footer) complete it
+    uint32_t bz_level = 9, bz_crc = 0, bz_carry = 0, bz_carry_bits = 0;
     // Whatever way the producer leaves (an exception on its way to the C boundary's catch included), the consumers are
     // told to finish and are joined: a joinable std::thread that is destroyed takes the process down.
     ~GzPipe()
@@ -443,7 +446,7 @@ try {
 namespace {
 
 // What tar_create_impl asks of a compressor (tarCreate's switch on the suffix, deb.go:269-276): the gzip producer below,
-// the .xz producer in xzpack.inc.  Both hand their bytes to the pass's consumers through gz_emit.
+// the .xz producer in xzpack.inc, the .bz2 producer in bzpack.inc.  All hand their bytes to the pass's consumers through gz_emit.
 struct TarCodec {
     const char* suffix;
     bool in_parts; // the pass's first slot may be compressed while it is still being filled (gz_slot_begin / _launch / _consume)
@@ -466,7 +469,8 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
     if (yaml_out) *yaml_out = nullptr;
     const size_t tl = strlen(tarname);
-    if (tl < 3 || strcmp(tarname + tl - 3, codec.suffix) != 0) // deb.go:270-276: the entry's own suffix (.xz: snaphash_tar_create_xz)
+    const size_t sfx = strlen(codec.suffix);
+    if (tl < sfx || strcmp(tarname + tl - sfx, codec.suffix) != 0) // deb.go:270-276: the entry's own suffix (.xz: snaphash_tar_create_xz, .bz2: _bz2)
         return fail(x, SNAPHASH_EINVAL, std::string("unknown compression extension ") + tarname);
     TOP_ENTER(x);
     DevCtx* c = x->d0(); // several engines: the first one (the pass is bound by the serial archive digest, snaphash.h)
