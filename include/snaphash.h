@@ -633,6 +633,83 @@ typedef struct snaphash_snap_stats { /* of the session so far */
 } snaphash_snap_stats;
 int snaphash_snap_get_stats(const snaphash_snap *s, snaphash_snap_stats *out);
 
+/* ---- writing the .snap: ClickDeb.Build (clickdeb/deb.go:346-406) with snappy.Build's callback (snappy/build.go:269) ---- */
+
+enum { /* snaphash_snap_build_options.flags */
+    SNAPHASH_BUILD_NO_HASHES = 1, /* the reference's nil dataTarFinishedCallback: DEBIAN/hashes.yaml is neither computed nor
+                                     written (the data member is still hashed for archive_digest) */
+    SNAPHASH_BUILD_CHECK = 2      /* the self-check: every 64 KiB chunk of both tars' DEFLATE streams is decoded again in HBM
+                                     by deflate_check_kernel and compared with the staged bytes it was made from, before the
+                                     bytes travel to the host; a chunk that does not is SNAPHASH_EDEVICE, last_error naming
+                                     the member, the chunk and the offset in the tar stream.  It covers the DEFLATE blocks
+                                     of every chunk -- not the gzip header and trailer (CRC-32, ISIZE, the final empty block,
+                                     written by the host), not the copy back to the host, not the write to disk.  The bytes
+                                     written are the same with and without it. */
+};
+
+typedef struct snaphash_snap_build_options {
+    uint32_t struct_size; /* sizeof(snaphash_snap_build_options) */
+    uint32_t flags;       /* SNAPHASH_BUILD_* */
+    int64_t mtime;        /* of the four ar members, seconds since the epoch; negative = now */
+} snaphash_snap_build_options;
+
+typedef struct snaphash_snap_build_stats {
+    uint32_t struct_size;   /* in: sizeof(snaphash_snap_build_stats) */
+    uint32_t reserved;
+    uint64_t snap_bytes;    /* the file written */
+    uint64_t data_bytes;    /* its data.tar.gz member */
+    uint64_t control_bytes; /* its control.tar.gz member */
+    uint64_t tar_bytes;     /* the data member's uncompressed tar stream */
+    uint64_t members;       /* tar members of the data member */
+    uint64_t check_chunks;  /* SNAPHASH_BUILD_CHECK: chunks the check kernel walked (both tars), all accepted */
+    double check_ms;        /* ... and the kernel's own time, HIP events */
+    double data_ms;         /* the fused pass over source_dir (tar, DEFLATE, hashes.yaml, archive digest) */
+    double control_ms;      /* the pass over source_dir/DEBIAN */
+    double ar_ms;           /* writing the container and hashing it */
+    double wall_ms;
+} snaphash_snap_build_stats;
+
+/* ClickDeb.Build to the letter, from ONE read of every source file:
+ *   data.tar.gz     tarCreate of source_dir without what starts with <source_dir>/DEBIAN (deb.go:361-363), by the fused pass
+ *                   of snaphash_tar_create: the member is byte for byte what that call writes for the same tree on the same
+ *                   ctx, and the same pass yields hashes.yaml and archive_digest (the SHA-512 of the member);
+ *   hashes.yaml     written to <source_dir>/DEBIAN/hashes.yaml, mode 0644, as writeHashes does (snappy/build.go:269) -- the
+ *                   dataTarFinishedCallback of snappy.Build; SNAPHASH_BUILD_NO_HASHES writes nothing;
+ *   control.tar.gz  tarCreate of <source_dir>/DEBIAN with no exclude rule, through the same producer (no DEBIAN: the walk's
+ *                   error, SNAPHASH_EIO);
+ *   the container   "!<arch>\n", then debian-binary ("2.0\n"), _click-binary ("0.4\n"), control.tar.gz, data.tar.gz.  The
+ *                   reference's ar writer is not part of its tree, so what is written is defined HERE: per member a 60-byte
+ *                   header -- the name left-justified in 16 bytes (a longer name: SNAPHASH_EINVAL), the mtime in decimal in
+ *                   12, uid "0" and gid "0" in 6 each, the mode in octal in 8 ("100644"), the size in decimal in 10, every
+ *                   field padded with spaces, then "`\n" -- the data, and one "\n" after data of odd size (the last
+ *                   member's included).  snaphash_snap_open reads back exactly these members.
+ * control.tar.gz precedes data.tar.gz and carries the data member's digest, so the data member is written first, to a
+ * temporary file beside the target (<snap_path>.data.tar.gz; control likewise), and copied into the container once the control member
+ * is known; both temporaries are removed on every way out.  snap_digest (may be NULL): the SHA-512 of the file written, the
+ * store's download_sha512, taken while the container is written.  archive_digest (may be NULL): of the data member.
+ * opt may be NULL (no flags, mtime now); stats may be NULL.  On failure snap_path is unlinked. */
+int snaphash_snap_build(snaphash_ctx *ctx, const char *source_dir, const char *snap_path, const snaphash_snap_build_options *opt,
+                        uint8_t *archive_digest, uint8_t *snap_digest, snaphash_snap_build_stats *stats);
+
+typedef struct snaphash_deflate_verdict {
+    uint32_t status; /* 0 accepted; 1 a literal or stored byte differs; 2 a match's copy differs; 3 a distance beyond
+                        min(32768, bytes in front); 4 not RFC 1951 (or BFINAL before the last chunk); 5 the blocks produce more
+                        than the chunk; 6 they end at the stretch's end with fewer; 7 they do not end at the stretch's end;
+                        8 the chunk's table entry lies outside the compressed bytes */
+    uint32_t offset; /* within the chunk: the first byte that differs, else how far the walk had come */
+} snaphash_deflate_verdict;
+/* The self-check kernel alone, on tables the caller wrote (tests): d_in[0..n_in) is the staged stream in HBM, cut into
+ * nchunks chunks of 65 536 bytes (nchunks * 65 536 >= n_in; a chunk past the end is empty); d_z holds z_off[nchunks] compressed
+ * bytes, chunk c's stretch being [z_off[c], z_off[c + 1]) (host array of nchunks + 1 ascending offsets).  A chunk is accepted
+ * when its stretch is a sequence of RFC 1951 blocks -- any valid one -- that produces exactly the chunk's bytes, matches
+ * reaching at most min(32768, bytes of d_in in front of them) back, and ends exactly at the stretch's end: without BFINAL
+ * on a byte boundary (after an empty stored block, or a stored chunk), or -- last_is_final != 0, last chunk only -- with
+ * the byte after the final block.  verdicts: nchunks entries (host).  Nothing is written to HBM but the verdicts, in a
+ * buffer of the library's own.  SNAPHASH_EINVAL: a null pointer, nchunks == 0 or too few for n_in, offsets that descend.
+ * Synchronous. */
+int snaphash_deflate_check_device(snaphash_ctx *ctx, const void *d_in, size_t n_in, const void *d_z, const uint64_t *z_off,
+                                  size_t nchunks, int last_is_final, snaphash_deflate_verdict *verdicts);
+
 /* ---- neighbouring scan: helpers.FilesAreEqual / DirUpdated -------- */
 
 /* helpers.FilesAreEqual (helpers/cmp.go:31-60), batched: equal[i] = 1 iff a[i] and b[i] both

@@ -58,7 +58,10 @@ EXPORTS = [
     "snaphash_sha512_jobs_device",
     # the data.tar.bz2 producer, and its BWT stage alone
     "snaphash_bzip2_buffer", "snaphash_tar_create_bz2", "snaphash_bwt_device",
+    # writing the .snap (ClickDeb.Build), and its self-check kernel alone
+    "snaphash_snap_build", "snaphash_deflate_check_device",
 ]
+BUILD_NO_HASHES, BUILD_CHECK = 1, 2
 JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
@@ -147,6 +150,17 @@ class SnapStats(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("data_decodes", ctypes.c_uint64),
                 ("control_decodes", ctypes.c_uint64), ("device_crc_ranges", ctypes.c_uint64), ("host_crc_ranges", ctypes.c_uint64),
                 ("device_crc_ms", ctypes.c_double)]
+
+
+class SnapBuildOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("mtime", ctypes.c_int64)]
+
+
+class SnapBuildStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("snap_bytes", ctypes.c_uint64),
+                ("data_bytes", ctypes.c_uint64), ("control_bytes", ctypes.c_uint64), ("tar_bytes", ctypes.c_uint64),
+                ("members", ctypes.c_uint64), ("check_chunks", ctypes.c_uint64), ("check_ms", ctypes.c_double),
+                ("data_ms", ctypes.c_double), ("control_ms", ctypes.c_double), ("ar_ms", ctypes.c_double), ("wall_ms", ctypes.c_double)]
 
 
 class Mismatch(ctypes.Structure):
@@ -271,6 +285,9 @@ def lib():
     L.snaphash_snap_unpack.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_snap_audit.argtypes = [vp, ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_snap_get_stats.argtypes = [vp, ctypes.POINTER(SnapStats)]
+    L.snaphash_snap_build.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(SnapBuildOptions), ctypes.c_char_p, ctypes.c_char_p,
+                                      ctypes.POINTER(SnapBuildStats)]
+    L.snaphash_deflate_check_device.argtypes = [vp, vp, sz, vp, u64p, sz, ctypes.c_int, vp]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -651,6 +668,29 @@ class Context:
         s.struct_size = ctypes.sizeof(XzCheckStats)
         self._check(lib().snaphash_get_xz_check_stats(self._h, ctypes.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in XzCheckStats._fields_ if f[0] not in ("struct_size", "reserved")}
+
+    def snap_build(self, source_dir, snap_path, hashes=True, check=False, mtime=-1):
+        """ClickDeb.Build with snappy.Build's callback: source_dir (with its DEBIAN/) -> the .snap at snap_path, every
+        source file read once.  hashes=False is the reference's nil callback (no DEBIAN/hashes.yaml); check=True runs
+        the self-check kernel over both tars' DEFLATE streams; mtime < 0: now.
+        -> (archive digest, digest of the .snap written, stats dict)."""
+        opt = SnapBuildOptions(ctypes.sizeof(SnapBuildOptions), (0 if hashes else BUILD_NO_HASHES) | (BUILD_CHECK if check else 0), int(mtime))
+        st = SnapBuildStats()
+        st.struct_size = ctypes.sizeof(SnapBuildStats)
+        adig, sdig = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+        self._check(lib().snaphash_snap_build(self._h, os.fsencode(source_dir), os.fsencode(snap_path), ctypes.byref(opt), adig, sdig,
+                                              ctypes.byref(st)))
+        return adig.raw, sdig.raw, {f[0]: getattr(st, f[0]) for f in SnapBuildStats._fields_ if f[0] not in ("struct_size", "reserved")}
+
+    def deflate_check_device(self, d_in, n_in, d_z, z_off, last_is_final=False):
+        """deflate_check_kernel alone: d_in / d_z device addresses (ints) of the staged stream (n_in bytes) and the
+        compressed bytes; z_off: the len(z_off) - 1 chunks' stretches.  -> [(status, offset)] a chunk.  Synchronous."""
+        nch = len(z_off) - 1
+        off = (ctypes.c_uint64 * (nch + 1))(*z_off)
+        v = (ctypes.c_uint32 * (2 * max(nch, 1)))()
+        self._check(lib().snaphash_deflate_check_device(self._h, d_in, n_in, d_z, off, nch, 1 if last_is_final else 0,
+                                                        ctypes.cast(v, ctypes.c_void_p)))
+        return [(v[2 * c], v[2 * c + 1]) for c in range(nch)]
 
     def snap_open(self, snap_path):
         """A session on a .snap file (ClickDeb.Open): see Snap."""

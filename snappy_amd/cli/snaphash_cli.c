@@ -30,6 +30,9 @@
  *   snaphash [options] snap audit FILE.snap      every check the package carries, nothing written; exit 1 on mismatch
  *   snaphash [options] snap unpack DIR FILE.snap ClickDeb.Unpack + Verify against the package's own hashes.yaml;
  *                                      exit 1 on mismatch; -s prints the unpack and session statistics
+ *   snaphash [options] snap build [-c] DIR OUT.snap   ClickDeb.Build with writeHashes fused in: DIR (with its DEBIAN/) -> the
+ *                                      package, DIR/DEBIAN/hashes.yaml written on the way; prints the SHA-512 of the file
+ *                                      (the store's download_sha512); -c: the DEFLATE self-check on the GPU
  *   snaphash [options] cmp A B [A B ...]         helpers.FilesAreEqual per pair; exit 1 if any pair differs
  *   snaphash [options] dirupdated DIR_A DIR_B [PREFIX]   helpers.DirUpdated
  * options: -d DEV[,DEV...]  engines (default: the current device; -1 = all visible)
@@ -61,7 +64,7 @@ static int usage(void)
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
                     "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
-                    "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap |\n"
+                    "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap | snap build [-c] DIR OUT.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
                     "       -b: gunzip / unpack also split streams without flush points at their blocks (SNAPHASH_FLAG_SPLIT_BLOCKS)\n"
@@ -309,6 +312,26 @@ int main(int argc, char **argv)
             if (!bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
         }
         free(y);
+    } else if (!strcmp(argv[1], "snap") && argc >= 4 && !strcmp(argv[2], "build")) {
+        const int check = argc == 6 && !strcmp(argv[3], "-c");
+        if (argc != (check ? 6 : 5)) ret = usage();
+        else {
+            snaphash_snap_build_options opt = {sizeof opt, check ? SNAPHASH_BUILD_CHECK : 0, -1};
+            snaphash_snap_build_stats bs;
+            uint8_t adig[64], sdig[64];
+            bs.struct_size = sizeof bs;
+            rc = snaphash_snap_build(c, argv[argc - 2], argv[argc - 1], &opt, adig, sdig, &bs);
+            if (rc) ret = die(c, rc, "snap build");
+            else {
+                for (int i = 0; i < 64; i++) printf("%02x", sdig[i]);
+                printf("  %s\n", argv[argc - 1]);
+                if (show_stats)
+                    fprintf(stderr, "snap build: %llu bytes (data.tar.gz %llu of %llu tar bytes, %llu members; control.tar.gz %llu); data %.1f ms, control %.1f ms, "
+                                    "container %.1f ms, wall %.1f ms; self-check: %llu chunks, %.3f ms\n",
+                            (unsigned long long)bs.snap_bytes, (unsigned long long)bs.data_bytes, (unsigned long long)bs.tar_bytes, (unsigned long long)bs.members,
+                            (unsigned long long)bs.control_bytes, bs.data_ms, bs.control_ms, bs.ar_ms, bs.wall_ms, (unsigned long long)bs.check_chunks, bs.check_ms);
+            }
+        }
     } else if (!strcmp(argv[1], "snap") && argc >= 4) {
         const char *verb = argv[2], *file = argv[argc - 1];
         const int takes_arg = !strcmp(verb, "cat-control") || !strcmp(verb, "cat-meta") || !strcmp(verb, "unpack");

@@ -5,7 +5,8 @@ sourceDir, asks fn(path) for every regular file, symlink and directory (False le
 writes members "./<relative path>" owned by root through gzip into tarname, and raises on the first error.
 tarCreate dispatches on the suffix as deb.go:269-276 does: ".gz" to the gzip producer, ".xz" (which the reference pipes
 through the xz tool) to the library's own .xz producer; anything else is "unknown compression extension".  Unpack reads
-data.tar.gz, UnpackBz2 data.tar.bz2, UnpackXz data.tar.xz; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203).  Test/bench harness, like
+data.tar.gz, UnpackBz2 data.tar.bz2, UnpackXz data.tar.xz; ClickDeb opens the .snap itself (clickdeb/deb.go:108-203)
+and ClickDeb.create(path).build(dir) writes one (deb.go:346-406).  Test/bench harness, like
 helpers.py and hashes.py: the product is the C ABI.
 """
 from .helpers import default_context
@@ -59,6 +60,11 @@ class ClickDeb:
     def open(cls, path, ctx=None):
         return cls((ctx or default_context()).snap_open(path))
 
+    @classmethod
+    def create(cls, path, ctx=None):
+        """clickdeb.Create(path): the package to be written by build().  (The file appears when build() runs.)"""
+        return ClickDebWriter(path, ctx or default_context())
+
     def close(self):
         self._snap.close()
 
@@ -92,3 +98,30 @@ class ClickDeb:
 
     def stats(self):
         return self._snap.stats()
+
+
+class ClickDebWriter:
+    """What ClickDeb.create returns: Build (clickdeb/deb.go:346-406) with snappy.Build's writeHashes callback fused in."""
+
+    def __init__(self, path, ctx):
+        self.path = path
+        self._ctx = ctx
+        self.archive_digest = self.snap_digest = self.build_stats = None
+
+    def build(self, sourceDir, hashes=True, check=False, mtime=-1):
+        """ClickDeb.Build(sourceDir, callback): data.tar.gz from one read of the tree, DEBIAN/hashes.yaml from the same
+        pass (hashes=False: the nil callback), control.tar.gz, the ar container.  check=True: every DEFLATE chunk is
+        decoded again in HBM and compared with what it was made from before it is written.  Raises SnaphashError and
+        leaves no file on failure.  -> self; archive_digest, snap_digest (the store's download_sha512) and build_stats
+        are set."""
+        self.archive_digest, self.snap_digest, self.build_stats = self._ctx.snap_build(sourceDir, self.path, hashes, check, mtime)
+        return self
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

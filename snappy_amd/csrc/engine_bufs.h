@@ -10,6 +10,7 @@
 #include "bzip2_enc_kernels.h"
 #include "bzip2_kernels.h"
 #include "crc_kernels.h"
+#include "deflate_check_kernels.h"
 #include "deflate_kernels.h"
 #include "devbuf.h"
 #include "inflate_core.h"
@@ -100,6 +101,7 @@ struct DeflateBufs {
     HostBuf<uint32_t> h_sizes;
     HostBuf<uint64_t> h_prefix;
     HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next D2H fills the other
+    Twin<DfCheckVerdict> chk;  // the self-check's verdicts, a chunk each: sized by the call that asks for the check (targz.inc), empty otherwise
     size_t chunks() const { return d_sizes.size(); }
     hipError_t ensure(size_t nch, int node)
     {
@@ -115,7 +117,7 @@ struct DeflateBufs {
         if (e) each(Release());
         return e;
     }
-    template <class F> void each(F&& f) { f(d_slots); f(d_out); f(d_toks); f(d_sizes); f(d_prefix); f(h_sizes); f(h_prefix); f(h_out[0]); f(h_out[1]); }
+    template <class F> void each(F&& f) { f(d_slots); f(d_out); f(d_toks); f(d_sizes); f(d_prefix); f(h_sizes); f(h_prefix); f(h_out[0]); f(h_out[1]); chk.each(f); }
 };
 
 // GPU inflate (row f5, unpack.inc): the compressed piece (+16 bytes the bit reader may read past it) and its candidates,

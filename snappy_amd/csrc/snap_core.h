@@ -1,4 +1,5 @@
-// snap_core.h -- the parts of the .snap session that need neither a device nor the engine: the `ar` container, the choice
+// snap_core.h -- the parts of the .snap session that need neither a device nor the engine: the `ar` container (read, and
+// written for snaphash_snap_build), the choice
 // of the member a call reads (skipToArMember, clickdeb/deb.go:408-441) and the audit's comparison of hashes.yaml with the
 // tar headers.  Host-only and self-contained, so that snap.inc and a host harness in tests/ run the same code.
 //
@@ -53,6 +54,59 @@ inline int ar_parse(const uint8_t* p, uint64_t n, std::vector<ArMember>& out, st
         if (size > n - m.off) { why = "ar: member " + m.name + " runs past the end of the file"; return SNAPHASH_EFORMAT; }
         out.push_back(m);
         at = m.off + size + (size & 1);
+    }
+    return 0;
+}
+
+// ---- the writer (snapbuild.inc: ClickDeb.Build, deb.go:381-403) --------------------------------------------------------------
+// The reference's ar writer is not in its tree either, so what is written is defined here, field for field what ar_parse
+// above (and ar(1), dpkg-deb) reads: the name left-justified in 16 bytes, the mtime in decimal in 12, uid "0" and gid "0" in
+// 6 each, the mode in octal in 8, the size in decimal in 10 -- every field padded with spaces -- and "`\n".
+
+constexpr char kArMagic[] = "!<arch>\n"; // 8 bytes
+constexpr size_t kArHeader = 60;
+
+// One member's header into out[60].  SNAPHASH_EINVAL: an empty name, one longer than 16 bytes or ending in a space (the
+// reader would not give it back), a negative mtime, a number its field cannot hold.
+inline int ar_header(const std::string& name, int64_t mtime, uint32_t mode, uint64_t size, uint8_t out[kArHeader])
+{
+    if (name.empty() || name.size() > 16 || name.back() == ' ') return SNAPHASH_EINVAL;
+    if (mtime < 0 || mtime > 999999999999ll || mode > 077777777u || size > 9999999999ull) return SNAPHASH_EINVAL;
+    memset(out, ' ', kArHeader);
+    memcpy(out, name.data(), name.size());
+    auto field = [&](size_t at, size_t width, uint64_t v, unsigned base) {
+        char digits[24];
+        size_t nd = 0;
+        do { digits[nd++] = (char)('0' + v % base); v /= base; } while (v);
+        for (size_t i = 0; i < nd && i < width; ++i) out[at + i] = (uint8_t)digits[nd - 1 - i];
+    };
+    field(16, 12, (uint64_t)mtime, 10);
+    field(28, 6, 0, 10);
+    field(34, 6, 0, 10);
+    field(40, 8, mode, 8);
+    field(48, 10, size, 10);
+    out[58] = '`';
+    out[59] = '\n';
+    return 0;
+}
+
+struct ArInput {
+    std::string name;
+    const uint8_t* data = nullptr;
+    uint64_t size = 0;
+};
+
+// A whole container in memory: the global magic, then header, data and the padding byte of every member.
+inline int ar_write(const std::vector<ArInput>& mem, int64_t mtime, uint32_t mode, std::vector<uint8_t>& out)
+{
+    out.assign((const uint8_t*)kArMagic, (const uint8_t*)kArMagic + 8);
+    for (const ArInput& m : mem) {
+        uint8_t h[kArHeader];
+        const int rc = ar_header(m.name, mtime, mode, m.size, h);
+        if (rc) { out.clear(); return rc; }
+        out.insert(out.end(), h, h + kArHeader);
+        if (m.size) out.insert(out.end(), m.data, m.data + m.size);
+        if (m.size & 1) out.push_back('\n');
     }
     return 0;
 }

@@ -17,6 +17,7 @@
 #include <string.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
+#include <time.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -2510,6 +2511,7 @@ int snaphash_crc64_device(snaphash_ctx* x, const void* d_base, const uint64_t* o
 #include "unbz2.inc"
 #include "unxz.inc"
 #include "snap.inc"
+#include "snapbuild.inc"
 
 // ---- helpers.FilesAreEqual / DirUpdated (row f4) ----------------------------------------------
 

@@ -31,6 +31,14 @@ struct GzItem {
     std::shared_ptr<std::vector<uint8_t>> own;
 };
 
+// The gzip producer's self-check, asked for by snaphash_snap_build alone: every piece's compacted bytes are walked against
+// the staged stream by deflate_check_kernel before they leave HBM (deflate_check_core.h).
+struct GzCheck {
+    const char* member = ""; // for last_error
+    uint64_t chunks = 0;     // chunks checked (all accepted, or the call failed)
+    double ms = 0;           // the check kernel's own time, HIP events
+};
+
 struct GzPipe {
     DevCtx* c = nullptr;
     int fd = -1;                 // output file, or -1: collect into `mem`
@@ -63,6 +71,8 @@ struct GzPipe {
     // the .bz2 producer (bzpack.inc): the level, the combined CRC so far, and the stream's last, partial byte -- held back
     // until the next slot's blocks (or the footer) complete it
     uint32_t bz_level = 9, bz_crc = 0, bz_carry = 0, bz_carry_bits = 0;
+    // the self-check (snapbuild.inc, SNAPHASH_BUILD_CHECK): null = off, the producer's path as it always was
+    GzCheck* check = nullptr;
     // Whatever way the producer leaves (an exception on its way to the C boundary's catch included), the consumers are
     // told to finish and are joined: a joinable std::thread that is destroyed takes the process down.
     ~GzPipe()
@@ -308,8 +318,28 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
         const hipError_t e = launch_deflate_compact(c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_prefix.data(), c->z.d_out.data(), c0, cnt, z2);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("compact launch: ") + hipGetErrorString(e));
         HIP_TRY(c, hipEventRecord(ev2->b, z2));
+        if (g.check) { // behind the compaction: the piece's stretches of d_out against the slot's staged bytes
+            EventPair* ev3 = next_events(c, 3);
+            if (!ev3) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            HIP_TRY(c, hipEventRecord(ev3->a, z2));
+            const hipError_t ec = launch_deflate_check(sl.d_buf.data(), n, c->z.d_out.data(), total, c->z.d_prefix.data(), c->z.d_sizes.data(), c0, cnt,
+                                                       g.z_nch, false, c->z.chk.d.data(), z2);
+            if (ec != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("check launch: ") + hipGetErrorString(ec));
+            HIP_TRY(c, hipEventRecord(ev3->b, z2));
+            HIP_TRY(c, hipMemcpyAsync(c->z.chk.h.data() + c0, c->z.chk.d.data() + c0, (size_t)cnt * sizeof(DfCheckVerdict), hipMemcpyDeviceToHost, z2));
+        }
         HIP_TRY(c, hipMemcpyAsync(c->z.h_out[zbuf].data() + base, c->z.d_out.data() + base, total - base, hipMemcpyDeviceToHost, z2));
         HIP_TRY(c, hipStreamSynchronize(z2));
+        if (g.check) {
+            for (uint32_t i = c0; i < c0 + cnt; ++i) {
+                const DfCheckVerdict v = c->z.chk.h[i];
+                if (v.status == kDfCheckOk) continue;
+                const uint64_t chunk = g.st.chunks + i; // of the member: the slots before this one, then this slot's
+                return fail(c, SNAPHASH_EDEVICE, std::string("self-check: ") + g.check->member + ": chunk " + std::to_string(chunk) + " does not decode to the bytes it was made from (status " +
+                                                     std::to_string(v.status) + ") at offset " + std::to_string(chunk * kDeflateChunk + v.offset) + " of the tar stream");
+            }
+            g.check->chunks += cnt;
+        }
         gz_emit(g, c->z.h_out[zbuf].data() + base, total - base, zbuf);
     }
     HIP_TRY(c, hipStreamSynchronize(zs));
@@ -363,6 +393,7 @@ void collect_targz_events(DevCtx* c, GzPipe& g)
         if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) != hipSuccess) continue;
         if (c->ev_pool[i].kind == 0) c->stats.kernel_ms += ms;
         else if (c->ev_pool[i].kind == 1) c->stats.h2d_ms += ms;
+        else if (c->ev_pool[i].kind == 3) { if (g.check) g.check->ms += ms; }
         else g.st.deflate_ms += ms;
     }
     c->ev_used = 0;
@@ -464,7 +495,8 @@ const TarCodec kGzipCodec = {".gz", true, producer_slot_bytes, ensure_deflate, g
 } // namespace
 
 static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* tarname, const char* source_dir, const char* exclude_prefix,
-                           snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
+                           snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest,
+                           GzCheck* check = nullptr /* the gzip producer's self-check: snaphash_snap_build alone asks for it */)
 {
     if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
     if (yaml_out) *yaml_out = nullptr;
@@ -537,6 +569,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     rc = ensure_slots(c, 2, S);
     if (!rc) rc = codec.ensure(c, S);
     if (rc) return lift(x, c, rc);
+    if (check) HIP_TRY(x, c->z.chk.ensure((size_t)((S + kDeflateChunk - 1) / kDeflateChunk)));
     if (nstreams) HIP_TRY(x, c->hash.ensure(nstreams, true));
 
     std::vector<Source> srcs(plan.members.size());
@@ -557,6 +590,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     g.c = c;
     g.fd = fd;
     g.want_sha = fused || archive_digest != nullptr;
+    g.check = check;
     gz_begin(g);
     codec.begin(g);
 
