@@ -1,5 +1,5 @@
-// bzpack.inc -- the data.tar.bz2 producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers and
-// staging it shares, and xzpack.inc, whose shape it has).
+// bzpack.inc -- the data.tar.bz2 producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers,
+// staging and buffer driver it shares: BzEncoder is one of targz.inc's Encoders, as xzpack.inc's XzEncoder is).
 //
 // The reference's tarCreate refuses a ".bz2" name (clickdeb/deb.go:274-275) and snaphash_tar_create keeps doing so; this
 // is the writer of the one format the install side reads (ClickDeb.Unpack, deb.go:185) and the library could not write.
@@ -15,45 +15,61 @@ namespace {
 uint32_t bz_launch_blocks(uint32_t level) { return (uint32_t)std::min<uint64_t>(kBzEncLaunchBlocksMax, kBzEncLaunchBytes / bzenc_rle_cap(level)); }
 
 // the producer's slot: whole pieces, as many as the job has, the staging size holds and one launch takes (at least one)
-uint64_t bz_slot_bytes_for(const DevCtx* c, uint64_t job_bytes, uint32_t level)
+uint64_t bz_slot_bytes(const DevCtx* c, uint64_t job_bytes, uint32_t level)
 {
     const uint64_t P = bzenc_piece(level);
     const uint64_t want = std::max<uint64_t>(1, (job_bytes + P - 1) / P);
     return std::max<uint64_t>(1, std::min({want, c->staging / P, (uint64_t)bz_launch_blocks(level)})) * P;
 }
-uint64_t bz_slot_bytes(const DevCtx* c, uint64_t job_bytes) { return bz_slot_bytes_for(c, job_bytes, 9); }
 
-int ensure_bzenc_for(DevCtx* c, uint32_t blocks, uint32_t cap, bool with_output)
+// with_output: the producer's; without: the scratch of the stages alone (snaphash_bwt_device)
+int ensure_bzenc(DevCtx* c, uint32_t blocks, uint32_t cap, bool with_output)
 {
-    if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority (ensure_deflate)
-        int least = 0, greatest = 0;
-        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
-    }
-    if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking));
+    const int rc = ensure_producer_streams(c);
+    if (rc) return rc;
     HIP_TRY(c, c->be.ensure(blocks, cap, with_output, c->numa_node)); // (a failure leaves none of it)
     return SNAPHASH_OK;
 }
-int ensure_bzenc(DevCtx* c, uint64_t slot_bytes) { return ensure_bzenc_for(c, (uint32_t)(slot_bytes / bzenc_piece(9)), bzenc_rle_cap(9), true); }
 
-void bz_header(GzPipe& g)
-{
-    const uint8_t h[kBzEncStreamHead] = {'B', 'Z', 'h', (uint8_t)('0' + g.bz_level)};
-    g.bz_crc = g.bz_carry = g.bz_carry_bits = 0;
-    gz_emit(g, h, sizeof h, -1);
-}
+// The .bz2 encoder of one call: the level it was asked for (1 to 9), the combined CRC so far, and the stream's last, partial
+// byte -- held back until the next slot's blocks (or the footer) complete it.
+struct BzEncoder final : Encoder {
+    const uint32_t level;
+    uint32_t crc = 0, carry = 0, carry_bits = 0;
+    explicit BzEncoder(uint32_t lvl = 9) : Encoder(".bz2", "bzip2: a block's input is larger than the engine's staging size"), level(lvl) {}
+    uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const override { return bz_slot_bytes(c, job_bytes, level); }
+    int ensure(DevCtx* c, uint64_t slot_bytes) override { return ensure_bzenc(c, (uint32_t)(slot_bytes / bzenc_piece(level)), bzenc_rle_cap(level), true); }
+    void begin(OutPipe& g) override
+    {
+        const uint8_t h[kBzEncStreamHead] = {'B', 'Z', 'h', (uint8_t)('0' + level)};
+        gz_emit(g, h, sizeof h, -1);
+    }
+    int slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last) override;
+    int finish(OutPipe& g, uint8_t archive_digest[64]) override // the end-of-stream magic and the combined CRC behind the held-back bits
+    {
+        uint32_t tail[4] = {carry & 0xffu, 0, 0, 0}; // (memory in stream order: the held-back byte is byte 0)
+        BzW w;
+        bzw_start(w, tail, 4, carry_bits);
+        bzw_put(w, (uint32_t)(kBzEosMagic >> 24), 24);
+        bzw_put(w, (uint32_t)(kBzEosMagic & 0xffffffu), 24);
+        bzw_put(w, crc, 32);
+        const uint64_t bytes = (bzw_pos(w) + 7) / 8;
+        bzw_flush(w);
+        return pipe_finish(g, (const uint8_t*)tail, (size_t)bytes, archive_digest);
+    }
+};
 
 // The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream) as
 // blocks into c->be.h_out[zbuf] and on to the consumers.
-int bz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
+int bz_process_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
 {
     if (n == 0) return SNAPHASH_OK;
     DevCtx* c = g.c;
     BzEncBufs& b = c->be;
     hipStream_t zs = c->z_stream;
-    const uint64_t P = bzenc_piece(g.bz_level);
+    const uint64_t P = bzenc_piece(z.level);
     const uint32_t nblk = (uint32_t)((n + P - 1) / P);
-    if (n > sl.cap() || nblk > b.made_blocks || bzenc_rle_cap(g.bz_level) > b.made_cap || !b.h_out[0].size())
+    if (n > sl.cap() || nblk > b.made_blocks || bzenc_rle_cap(z.level) > b.made_cap || !b.h_out[0].size())
         return fail(c, SNAPHASH_EDEVICE, "bzip2: the encoder's buffers are smaller than the slot");
     if (ready) HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0));
     // the blocks' CRCs: over the pieces as they are, before RLE1
@@ -83,14 +99,14 @@ int bz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nblk * sizeof(BzEncRes), hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
     // where every block goes: behind the bits the last slot left
-    uint64_t at = g.bz_carry_bits;
+    uint64_t at = z.carry_bits;
     for (uint32_t k = 0; k < nblk; ++k) {
         const BzEncRes& r = b.res.h[k];
         if (r.over || r.bits == 0 || r.bits > (uint64_t)s.slot_words * 32 || r.rle_n == 0 || r.orig_ptr >= r.rle_n)
             return fail(c, SNAPHASH_EDEVICE, "bzip2: a block's stages reported an impossible result");
         b.dst.h[k] = at;
         at += r.bits;
-        g.bz_crc = bz_crc_combine(g.bz_crc, crcs[k]);
+        z.crc = bz_crc_combine(z.crc, crcs[k]);
     }
     const uint64_t out_words = (at + 31) / 32, whole = at / 8;
     if (out_words > b.d_out.size() || out_words * 4 > b.h_out[zbuf].size()) return fail(c, SNAPHASH_EDEVICE, "bzip2: a slot's output outgrew its buffer");
@@ -101,7 +117,7 @@ int bz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     const EventPair ev2 = *evp2;
     HIP_TRY(c, hipEventRecord(ev2.a, zs));
-    HIP_TRY(c, launch_bzenc_concat(s, b.dst.d.data(), nblk, b.d_out.data(), out_words, g.bz_carry, zs));
+    HIP_TRY(c, launch_bzenc_concat(s, b.dst.d.data(), nblk, b.d_out.data(), out_words, z.carry, zs));
     HIP_TRY(c, hipEventRecord(ev2.b, zs));
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), (size_t)out_words * 4, hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
@@ -112,32 +128,17 @@ int bz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
         fprintf(stderr, "snaphash bz2: slot of %llu bytes, %u blocks: crc %.3f ms, rle1 %.3f ms, bwt %.3f ms, mtf %.3f ms, code %.3f ms, concat %.3f ms\n",
                 (unsigned long long)n, nblk, crc_ms, ms[0], ms[1], ms[2], ms[3], cat);
     }
-    g.bz_carry_bits = (uint32_t)(at & 7);
-    g.bz_carry = g.bz_carry_bits ? h[whole] : 0u;
+    z.carry_bits = (uint32_t)(at & 7);
+    z.carry = z.carry_bits ? h[whole] : 0u;
     gz_emit(g, h, whole, zbuf);
-    g.isize += n;
     g.st.chunks += nblk;
     return SNAPHASH_OK;
 }
 
-// the end-of-stream magic and the combined CRC behind the held-back bits; -> errno of the first failed write, or 0
-int bz_finish(GzPipe& g, uint8_t archive_digest[64])
+int BzEncoder::slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last)
 {
-    uint32_t tail[4] = {g.bz_carry & 0xffu, 0, 0, 0}; // (memory in stream order: the held-back byte is byte 0)
-    BzW w;
-    bzw_start(w, tail, 4, g.bz_carry_bits);
-    bzw_put(w, (uint32_t)(kBzEosMagic >> 24), 24);
-    bzw_put(w, (uint32_t)(kBzEosMagic & 0xffffffu), 24);
-    bzw_put(w, g.bz_crc, 32);
-    const uint64_t bytes = (bzw_pos(w) + 7) / 8;
-    bzw_flush(w);
-    gz_emit(g, (const uint8_t*)tail, (size_t)bytes, -1);
-    gz_join(g);
-    if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
-    return g.write_err;
+    return bz_process_slot(g, *this, sl, n, ready, zbuf, is_first, is_last);
 }
-
-const TarCodec kBz2Codec = {".bz2", false, bz_slot_bytes, ensure_bzenc, bz_header, bz_process_slot, bz_finish};
 
 } // namespace
 
@@ -150,51 +151,8 @@ try {
     *bz_len = 0;
     level = bzenc_level(level);
     if (!level) return fail(x, SNAPHASH_EINVAL, "bzip2: the level is 1 to 9, or 0 for 9");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t S = bz_slot_bytes_for(c, n, level);
-    if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "bzip2: a block's input is larger than the engine's staging size");
-    int rc = ensure_slots(c, 2, S);
-    if (!rc) rc = ensure_bzenc_for(c, (uint32_t)(S / bzenc_piece(level)), bzenc_rle_cap(level), true);
-    if (rc) return lift(x, c, rc);
-    std::string out;
-    GzPipe g;
-    g.c = c;
-    g.mem = &out;
-    gz_begin(g);
-    g.bz_level = level;
-    bz_header(g);
-    Slot& sl = c->slot[0];
-    const double t0 = now_ms();
-    for (uint64_t off = 0; off < n && !rc; off += S) {
-        const uint64_t take = std::min<uint64_t>(S, n - off);
-        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
-        EventPair* ev = next_events(c, 1);
-        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
-            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
-            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
-        rc = bz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
-    }
-    if (!rc && bz_finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
-    if (rc) gz_abort(g);
-    (void)hipStreamSynchronize(c->z_stream);
-    (void)hipStreamSynchronize(c->z2_stream);
-    collect_targz_events(c, g);
-    g.st.tar_bytes = n;
-    g.st.gz_bytes = out.size();
-    g.st.wall_ms = now_ms() - t0;
-    x->targz = g.st;
-    merge_stats(x);
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(out.size() ? out.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    memcpy(p, out.data(), out.size());
-    *bz_out = p;
-    *bz_len = out.size();
-    return SNAPHASH_OK;
+    BzEncoder enc(level);
+    return encode_to_malloc(x, enc, data, n, bz_out, bz_len);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -215,7 +173,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     cap = (cap + 63) & ~63u;
     const uint32_t per = (uint32_t)std::min<uint64_t>({(uint64_t)n_blocks, (uint64_t)kBzEncLaunchBlocksMax, std::max<uint64_t>(1, kBzEncLaunchBytes / cap)});
-    int rc = ensure_bzenc_for(c, per, cap, false);
+    int rc = ensure_bzenc(c, per, cap, false);
     if (rc) return lift(x, c, rc);
     BzEncBufs& b = c->be;
     const BzEncScratch s = b.scratch();
@@ -235,7 +193,8 @@ try {
 int snaphash_tar_create_bz2(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix, char** yaml_out,
                             size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, kBz2Codec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    BzEncoder enc;
+    return tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }

@@ -96,8 +96,8 @@ int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_pa
     char* yaml = nullptr;
     size_t yaml_len = 0;
     struct Free { char*& p; ~Free() { free(p); } } free_yaml{yaml};
-    int rc = tar_create_impl(x, kGzipCodec, tmp.data.c_str(), source_dir, debian.c_str(), nullptr, nullptr, hashes ? &yaml : nullptr, &yaml_len, adig,
-                             check ? &chk_data : nullptr);
+    GzipEncoder enc_data(check ? &chk_data : nullptr), enc_control(check ? &chk_control : nullptr);
+    int rc = tar_create_impl(x, enc_data, tmp.data.c_str(), source_dir, debian.c_str(), nullptr, nullptr, hashes ? &yaml : nullptr, &yaml_len, adig);
     if (rc) return rc;
     st.data_ms = x->targz.wall_ms;
     st.tar_bytes = x->targz.tar_bytes;
@@ -107,7 +107,7 @@ int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_pa
         rc = write_yaml_file(x, source_dir, std::string(yaml, yaml_len));
         if (rc) return rc;
     }
-    rc = tar_create_impl(x, kGzipCodec, tmp.control.c_str(), debian.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, check ? &chk_control : nullptr);
+    rc = tar_create_impl(x, enc_control, tmp.control.c_str(), debian.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
     st.control_ms = x->targz.wall_ms;
     st.control_bytes = x->targz.gz_bytes;

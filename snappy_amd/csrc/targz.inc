@@ -10,6 +10,11 @@
 // content starts on a 512-byte boundary).  The compressed bytes come back, are appended to the
 // .gz and feed the archive digest -- one sequential stream, hashed on a host core by the
 // library's own SHA-512 (a lone stream is 10x faster there than on the GPU).
+//
+// The file also holds what the three build-side formats share: OutPipe (the consumers), Encoder (a format's parameters and
+// running state, made for one call: GzipEncoder here, XzEncoder in xzpack.inc, BzEncoder in bzpack.inc), tar_create_impl (the
+// pass, which takes an Encoder) and encode_to_malloc (the body of the *_buffer entries).  Where a slot's headers, padding
+// and members' bytes lie is tarpack.cpp's tar_fill_slot, host code with a CPU suite of its own (tests/test_f3_host.py).
 
 namespace {
 
@@ -39,12 +44,11 @@ struct GzCheck {
     double ms = 0;           // the check kernel's own time, HIP events
 };
 
-struct GzPipe {
+// What every compressor hands its bytes to (gz_emit): the pass's two consumers, or a string in memory.
+struct OutPipe {
     DevCtx* c = nullptr;
     int fd = -1;                 // output file, or -1: collect into `mem`
     std::string* mem = nullptr;
-    uint32_t crc = 0;            // of the uncompressed stream
-    uint64_t isize = 0;
     uint64_t out_bytes = 0;
     // Two consumers take the compressed bytes in order, off the producer's thread: one appends them to the file,
     // one absorbs them into the archive digest (the stream that cannot be parallel: it bounds the whole pass).
@@ -54,34 +58,60 @@ struct GzPipe {
     std::mutex mu;
     std::condition_variable cv;
     std::queue<GzItem> q_sha, q_wr;
-    int inflight[2] = {0, 0};    // consumers still reading z.h_out[b]
+    int inflight[2] = {0, 0};    // consumers still reading the encoder's pinned output buffer b
     int write_err = 0;
     bool closing = false;
     double busy_ms[2] = {0, 0}, wait_ms[2] = {0, 0}; // per consumer (digest, writer): working / waiting for the producer
     double t_first_piece = 0, t_last_piece = 0;      // when the compressor's first / last piece went to the consumers (trace)
-    // the slot in the compressor (gz_slot_begin / _launch / _consume)
-    std::vector<std::pair<uint32_t, uint32_t>> z_pieces; // (first chunk, count)
-    uint32_t z_nch = 0, z_launched = 0;
-    EventPair z_evpair{};
     snaphash_targz_stats st{};
-    // the .xz producer (xzpack.inc): the Block size and the Index records of the Blocks written so far
-    uint64_t xz_block_size = kXzEncBlockDefault;
-    uint32_t xz_check = kXzCheckCrc64; // the Blocks' Check (snaphash_xz_buffer_check names another)
-    std::vector<XzEncRecord> xz_recs;
-    // the .bz2 producer (bzpack.inc): the level, the combined CRC so far, and the stream's last, partial byte -- held back
-    // until the next slot's blocks (or the footer) complete it
-    uint32_t bz_level = 9, bz_crc = 0, bz_carry = 0, bz_carry_bits = 0;
-    // the self-check (snapbuild.inc, SNAPHASH_BUILD_CHECK): null = off, the producer's path as it always was
-    GzCheck* check = nullptr;
     // Whatever way the producer leaves (an exception on its way to the C boundary's catch included), the consumers are
     // told to finish and are joined: a joinable std::thread that is destroyed takes the process down.
-    ~GzPipe()
+    ~OutPipe()
     {
         { std::lock_guard<std::mutex> lk(mu); closing = true; }
         cv.notify_all();
         if (sha_thread.joinable()) sha_thread.join();
         if (wr_thread.joinable()) wr_thread.join();
     }
+};
+
+// What tar_create_impl and encode_to_malloc ask of a compressor (tarCreate's switch on the suffix, deb.go:269-276): the gzip
+// encoder below, the .xz encoder in xzpack.inc, the .bz2 encoder in bzpack.inc.  An encoder is made for one call, with the
+// call's parameters, and holds the stream's running state; all hand their bytes to the consumers through gz_emit.
+struct GzipEncoder;
+struct Encoder {
+    const char* const suffix;
+    const char* const staging_refusal;  // encode_to_malloc's words when a slot outgrows the engine's staging size; null: none does
+    GzipEncoder* parts = nullptr;       // set: the pass's first slot may be compressed while it is still being filled (gz_slot_begin / _launch / _consume)
+    double* check_ms = nullptr;         // where the time of the call's events of kind 3 goes (the gzip self-check's kernel); null: there are none
+    Encoder(const char* sfx, const char* refusal) : suffix(sfx), staging_refusal(refusal) {}
+    virtual ~Encoder() = default;
+    virtual uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const = 0; // what the pass stages at a time (a multiple of 512)
+    virtual int ensure(DevCtx* c, uint64_t slot_bytes) = 0;
+    virtual void begin(OutPipe& g) = 0;                                         // what the file begins with
+    virtual int slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last) = 0;
+    virtual int finish(OutPipe& g, uint8_t archive_digest[64]) = 0;             // what it ends with; -> errno of the first failed write, or 0
+};
+
+struct GzipEncoder final : Encoder {
+    uint32_t crc = 0;            // of the uncompressed stream
+    uint64_t isize = 0;
+    // the slot in the compressor (gz_slot_begin / _launch / _consume)
+    std::vector<std::pair<uint32_t, uint32_t>> z_pieces; // (first chunk, count)
+    uint32_t z_nch = 0, z_launched = 0;
+    EventPair z_evpair{};
+    // the self-check (snapbuild.inc, SNAPHASH_BUILD_CHECK): null = off, the compressor's path without it
+    GzCheck* const check;
+    explicit GzipEncoder(GzCheck* chk = nullptr) : Encoder(".gz", nullptr), check(chk)
+    {
+        parts = this;
+        if (chk) check_ms = &chk->ms;
+    }
+    uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const override;
+    int ensure(DevCtx* c, uint64_t slot_bytes) override;
+    void begin(OutPipe& g) override;
+    int slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last) override;
+    int finish(OutPipe& g, uint8_t archive_digest[64]) override;
 };
 
 // What a call of the producer stages at a time: the engine's staging size, or -- for a job smaller than that -- the next
@@ -99,22 +129,33 @@ uint64_t producer_slot_bytes(const DevCtx* c, uint64_t job_bytes)
     return std::max<uint64_t>(want & ~(uint64_t)(kDeflateChunk - 1), kDeflateChunk);
 }
 
-int ensure_deflate(DevCtx* c, uint64_t slot_bytes)
+// the two streams every encoder works on
+int ensure_producer_streams(DevCtx* c)
 {
-    const size_t nch = (size_t)((slot_bytes + kDeflateChunk - 1) / kDeflateChunk);
     if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority: they are the longer chain
         int least = 0, greatest = 0;
         HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
     }
     if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking)); // concatenation + the way back
+    return SNAPHASH_OK;
+}
+
+uint64_t GzipEncoder::slot_bytes(const DevCtx* c, uint64_t job_bytes) const { return producer_slot_bytes(c, job_bytes); }
+
+int GzipEncoder::ensure(DevCtx* c, uint64_t slot_bytes)
+{
+    const size_t nch = (size_t)((slot_bytes + kDeflateChunk - 1) / kDeflateChunk);
+    const int rc = ensure_producer_streams(c);
+    if (rc) return rc;
     // (grown: what a smaller job left behind goes first; a failure leaves none of it, and the next call allocates it all)
     HIP_TRY(c, c->z.ensure(nch, c->numa_node));
+    if (check) HIP_TRY(c, c->z.chk.ensure(nch));
     return SNAPHASH_OK;
 }
 
 // buf >= 0: p points into z.h_out[buf] (stays valid until gz_wait_buf(buf) returns); buf < 0: p is copied.
-void gz_emit(GzPipe& g, const uint8_t* p, size_t n, int buf)
+void gz_emit(OutPipe& g, const uint8_t* p, size_t n, int buf)
 {
     if (n == 0) return;
     if (g.mem) g.mem->append((const char*)p, n);
@@ -136,13 +177,13 @@ void gz_emit(GzPipe& g, const uint8_t* p, size_t n, int buf)
     g.cv.notify_all();
 }
 
-void gz_wait_buf(GzPipe& g, int buf)
+void gz_wait_buf(OutPipe& g, int buf)
 {
     std::unique_lock<std::mutex> lk(g.mu);
     g.cv.wait(lk, [&] { return g.inflight[buf] == 0; });
 }
 
-void gz_consumer(GzPipe* g, bool is_writer)
+void gz_consumer(OutPipe* g, bool is_writer)
 {
     std::queue<GzItem>& q = is_writer ? g->q_wr : g->q_sha;
     for (;;) {
@@ -178,7 +219,7 @@ void gz_consumer(GzPipe* g, bool is_writer)
     }
 }
 
-void gz_begin(GzPipe& g)
+void gz_begin(OutPipe& g)
 {
     if (g.want_sha) {
         host_sha512_init(g.sha);
@@ -249,50 +290,50 @@ struct ZPieces {
 // One slot on its way through the compressor, in three steps so that the pass's first slot can be compressed while it
 // is still being filled: begin (cut into pieces), launch (the pieces whose bytes are in HBM), consume (sizes -> prefix
 // -> concatenation -> pinned z.h_out -> the consumers).
-int gz_slot_begin(GzPipe& g, uint64_t n, bool is_first, bool is_last)
+int gz_slot_begin(OutPipe& g, GzipEncoder& z, uint64_t n, bool is_first, bool is_last)
 {
     DevCtx* c = g.c;
     static const ZPieces zp;
-    g.z_nch = (uint32_t)((n + kDeflateChunk - 1) / kDeflateChunk);
-    zp.cut(g.z_nch, is_first, is_last, g.z_pieces);
-    g.z_launched = 0;
-    while (c->z_ev.size() < g.z_pieces.size()) {
+    z.z_nch = (uint32_t)((n + kDeflateChunk - 1) / kDeflateChunk);
+    zp.cut(z.z_nch, is_first, is_last, z.z_pieces);
+    z.z_launched = 0;
+    while (c->z_ev.size() < z.z_pieces.size()) {
         hipEvent_t e = nullptr;
         HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->z_ev.push_back(e);
     }
     EventPair* ev = next_events(c, 2);
     if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    g.z_evpair = *ev;
-    HIP_TRY(c, hipEventRecord(g.z_evpair.a, c->z_stream));
+    z.z_evpair = *ev;
+    HIP_TRY(c, hipEventRecord(z.z_evpair.a, c->z_stream));
     return SNAPHASH_OK;
 }
 
 // launches, in order, every piece that ends at or before bytes_ready (bytes_ready >= n: all that are left); `ready`
 // (may be NULL) is waited for first: the copy that brought those bytes
-int gz_slot_launch(GzPipe& g, Slot& sl, uint64_t n, uint64_t bytes_ready, hipEvent_t ready)
+int gz_slot_launch(OutPipe& g, GzipEncoder& z, Slot& sl, uint64_t n, uint64_t bytes_ready, hipEvent_t ready)
 {
     DevCtx* c = g.c;
     hipStream_t zs = c->z_stream;
     bool waited = false;
-    while (g.z_launched < g.z_pieces.size()) {
-        const uint32_t c0 = g.z_pieces[g.z_launched].first, cnt = g.z_pieces[g.z_launched].second;
+    while (z.z_launched < z.z_pieces.size()) {
+        const uint32_t c0 = z.z_pieces[z.z_launched].first, cnt = z.z_pieces[z.z_launched].second;
         if (bytes_ready < n && (uint64_t)(c0 + cnt) * kDeflateChunk > bytes_ready) break;
         if (ready && !waited) { HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0)); waited = true; }
-        const hipError_t e = launch_deflate_chunks(sl.d_buf.data(), n, c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_toks.data(), c0, cnt, g.z_nch, c->n_xcd, c->deflate_depth, zs);
+        const hipError_t e = launch_deflate_chunks(sl.d_buf.data(), n, c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_toks.data(), c0, cnt, z.z_nch, c->n_xcd, c->deflate_depth, zs);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("deflate launch: ") + hipGetErrorString(e));
         HIP_TRY(c, hipMemcpyAsync(c->z.h_sizes.data() + c0, c->z.d_sizes.data() + c0, (size_t)cnt * 4, hipMemcpyDeviceToHost, zs));
-        HIP_TRY(c, hipEventRecord(c->z_ev[g.z_launched], zs));
-        if (++g.z_launched == g.z_pieces.size()) HIP_TRY(c, hipEventRecord(g.z_evpair.b, zs));
+        HIP_TRY(c, hipEventRecord(c->z_ev[z.z_launched], zs));
+        if (++z.z_launched == z.z_pieces.size()) HIP_TRY(c, hipEventRecord(z.z_evpair.b, zs));
     }
     return SNAPHASH_OK;
 }
 
-int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
+int gz_slot_consume(OutPipe& g, GzipEncoder& z, Slot& sl, uint64_t n, int zbuf)
 {
     DevCtx* c = g.c;
     hipStream_t zs = c->z_stream, z2 = c->z2_stream;
-    if (g.z_launched != g.z_pieces.size()) return fail(c, SNAPHASH_EDEVICE, "a piece of the slot was never launched");
+    if (z.z_launched != z.z_pieces.size()) return fail(c, SNAPHASH_EDEVICE, "a piece of the slot was never launched");
     // while the kernels run: CRC of the uncompressed bytes on a few host threads of their own -- NOT on this thread, which
     // has the pieces to hand on
     struct CrcJob { // joined on every way out
@@ -301,8 +342,8 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
     } crc_job{std::async(std::launch::async, crc_parallel, (const uint8_t*)sl.h_buf.data(), (size_t)n)};
     gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
     uint64_t total = 0;
-    for (uint32_t k = 0; k < g.z_pieces.size(); ++k) {
-        const uint32_t c0 = g.z_pieces[k].first, cnt = g.z_pieces[k].second;
+    for (uint32_t k = 0; k < z.z_pieces.size(); ++k) {
+        const uint32_t c0 = z.z_pieces[k].first, cnt = z.z_pieces[k].second;
         HIP_TRY(c, hipEventSynchronize(c->z_ev[k]));
         const uint64_t base = total;
         for (uint32_t i = c0; i < c0 + cnt; ++i) {
@@ -318,50 +359,50 @@ int gz_slot_consume(GzPipe& g, Slot& sl, uint64_t n, int zbuf)
         const hipError_t e = launch_deflate_compact(c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_prefix.data(), c->z.d_out.data(), c0, cnt, z2);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("compact launch: ") + hipGetErrorString(e));
         HIP_TRY(c, hipEventRecord(ev2->b, z2));
-        if (g.check) { // behind the compaction: the piece's stretches of d_out against the slot's staged bytes
+        if (z.check) { // behind the compaction: the piece's stretches of d_out against the slot's staged bytes
             EventPair* ev3 = next_events(c, 3);
             if (!ev3) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             HIP_TRY(c, hipEventRecord(ev3->a, z2));
             const hipError_t ec = launch_deflate_check(sl.d_buf.data(), n, c->z.d_out.data(), total, c->z.d_prefix.data(), c->z.d_sizes.data(), c0, cnt,
-                                                       g.z_nch, false, c->z.chk.d.data(), z2);
+                                                       z.z_nch, false, c->z.chk.d.data(), z2);
             if (ec != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("check launch: ") + hipGetErrorString(ec));
             HIP_TRY(c, hipEventRecord(ev3->b, z2));
             HIP_TRY(c, hipMemcpyAsync(c->z.chk.h.data() + c0, c->z.chk.d.data() + c0, (size_t)cnt * sizeof(DfCheckVerdict), hipMemcpyDeviceToHost, z2));
         }
         HIP_TRY(c, hipMemcpyAsync(c->z.h_out[zbuf].data() + base, c->z.d_out.data() + base, total - base, hipMemcpyDeviceToHost, z2));
         HIP_TRY(c, hipStreamSynchronize(z2));
-        if (g.check) {
+        if (z.check) {
             for (uint32_t i = c0; i < c0 + cnt; ++i) {
                 const DfCheckVerdict v = c->z.chk.h[i];
                 if (v.status == kDfCheckOk) continue;
                 const uint64_t chunk = g.st.chunks + i; // of the member: the slots before this one, then this slot's
-                return fail(c, SNAPHASH_EDEVICE, std::string("self-check: ") + g.check->member + ": chunk " + std::to_string(chunk) + " does not decode to the bytes it was made from (status " +
+                return fail(c, SNAPHASH_EDEVICE, std::string("self-check: ") + z.check->member + ": chunk " + std::to_string(chunk) + " does not decode to the bytes it was made from (status " +
                                                      std::to_string(v.status) + ") at offset " + std::to_string(chunk * kDeflateChunk + v.offset) + " of the tar stream");
             }
-            g.check->chunks += cnt;
+            z.check->chunks += cnt;
         }
         gz_emit(g, c->z.h_out[zbuf].data() + base, total - base, zbuf);
     }
     HIP_TRY(c, hipStreamSynchronize(zs));
     const uint32_t crc = crc_job.f.get();
-    g.crc = g.isize ? crc32_combine(g.crc, crc, n) : crc;
-    g.isize += n;
-    g.st.chunks += g.z_nch;
+    z.crc = z.isize ? crc32_combine(z.crc, crc, n) : crc;
+    z.isize += n;
+    g.st.chunks += z.z_nch;
     return SNAPHASH_OK;
 }
 
 // The slot's first n bytes (in sl.h_buf.data(), and in sl.d_buf.data() once `ready` has fired; ready == nullptr: already ordered on the
 // compressor's stream), all three steps.
-int gz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first = false, bool is_last = false)
+int gz_process_slot(OutPipe& g, GzipEncoder& z, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first = false, bool is_last = false)
 {
     if (n == 0) return SNAPHASH_OK;
-    int rc = gz_slot_begin(g, n, is_first, is_last);
-    if (!rc) rc = gz_slot_launch(g, sl, n, n, ready);
-    if (!rc) rc = gz_slot_consume(g, sl, n, zbuf);
+    int rc = gz_slot_begin(g, z, n, is_first, is_last);
+    if (!rc) rc = gz_slot_launch(g, z, sl, n, n, ready);
+    if (!rc) rc = gz_slot_consume(g, z, sl, n, zbuf);
     return rc;
 }
 
-void gz_join(GzPipe& g)
+void gz_join(OutPipe& g)
 {
     { std::lock_guard<std::mutex> lk(g.mu); g.closing = true; }
     g.cv.notify_all();
@@ -369,34 +410,98 @@ void gz_join(GzPipe& g)
     if (g.wr_thread.joinable()) g.wr_thread.join();
 }
 
+// What every encoder's finish ends with: the stream's last bytes, the consumers joined, the archive digest.
 // -> errno of the first failed write, or 0
-int gz_finish(GzPipe& g, uint8_t archive_digest[64])
+int pipe_finish(OutPipe& g, const uint8_t* tail, size_t n, uint8_t archive_digest[64])
 {
-    uint8_t tail[10] = {0x03, 0x00}; // final empty fixed-Huffman block (BFINAL=1, BTYPE=01, end-of-block)
-    for (int k = 0; k < 4; ++k) tail[2 + k] = (uint8_t)(g.crc >> (8 * k));
-    for (int k = 0; k < 4; ++k) tail[6 + k] = (uint8_t)((uint32_t)g.isize >> (8 * k));
-    gz_emit(g, tail, sizeof tail, -1);
+    gz_emit(g, tail, n, -1);
     gz_join(g);
     if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
-    if (getenv("SNAPHASH_TRACE_TARGZ"))
-        fprintf(stderr, "snaphash targz: digest thread busy %.0f ms, starved %.0f ms; writer busy %.0f ms, starved %.0f ms\n", g.busy_ms[0],
-                g.wait_ms[0], g.busy_ms[1], g.wait_ms[1]);
     return g.write_err;
 }
 
-void gz_abort(GzPipe& g) { gz_join(g); }
+void GzipEncoder::begin(OutPipe& g) { gz_emit(g, kGzipHeader, sizeof kGzipHeader, -1); }
 
-void collect_targz_events(DevCtx* c, GzPipe& g)
+int GzipEncoder::slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last)
+{
+    return gz_process_slot(g, *this, sl, n, ready, zbuf, is_first, is_last);
+}
+
+int GzipEncoder::finish(OutPipe& g, uint8_t archive_digest[64])
+{
+    uint8_t tail[10] = {0x03, 0x00}; // final empty fixed-Huffman block (BFINAL=1, BTYPE=01, end-of-block)
+    for (int k = 0; k < 4; ++k) tail[2 + k] = (uint8_t)(crc >> (8 * k));
+    for (int k = 0; k < 4; ++k) tail[6 + k] = (uint8_t)((uint32_t)isize >> (8 * k));
+    const int werr = pipe_finish(g, tail, sizeof tail, archive_digest);
+    if (getenv("SNAPHASH_TRACE_TARGZ"))
+        fprintf(stderr, "snaphash targz: digest thread busy %.0f ms, starved %.0f ms; writer busy %.0f ms, starved %.0f ms\n", g.busy_ms[0],
+                g.wait_ms[0], g.busy_ms[1], g.wait_ms[1]);
+    return werr;
+}
+
+void gz_abort(OutPipe& g) { gz_join(g); }
+
+void collect_targz_events(DevCtx* c, snaphash_targz_stats& st, double* check_ms)
 {
     for (size_t i = 0; i < c->ev_used; ++i) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) != hipSuccess) continue;
         if (c->ev_pool[i].kind == 0) c->stats.kernel_ms += ms;
         else if (c->ev_pool[i].kind == 1) c->stats.h2d_ms += ms;
-        else if (c->ev_pool[i].kind == 3) { if (g.check) g.check->ms += ms; }
-        else g.st.deflate_ms += ms;
+        else if (c->ev_pool[i].kind == 3) { if (check_ms) *check_ms += ms; }
+        else st.deflate_ms += ms;
     }
     c->ev_used = 0;
+}
+
+// A whole buffer through an encoder into memory the caller frees: the body of the snaphash_*_buffer entry points of the
+// build side, behind their own argument checks (decode_to_malloc is the install side's).
+int encode_to_malloc(snaphash_ctx* x, Encoder& enc, const void* data, size_t n, void** out_p, size_t* out_len)
+{
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t S = enc.slot_bytes(c, n);
+    if (enc.staging_refusal && S > c->staging) return fail(x, SNAPHASH_EINVAL, enc.staging_refusal);
+    int rc = ensure_slots(c, 2, S);
+    if (!rc) rc = enc.ensure(c, S);
+    if (rc) return lift(x, c, rc);
+    std::string out;
+    OutPipe g;
+    g.c = c;
+    g.mem = &out;
+    gz_begin(g);
+    enc.begin(g);
+    Slot& sl = c->slot[0];
+    const double t0 = now_ms();
+    for (uint64_t off = 0; off < n && !rc; off += S) {
+        const uint64_t take = std::min<uint64_t>(S, n - off);
+        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
+        EventPair* ev = next_events(c, 1);
+        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
+        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
+            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
+            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
+        rc = enc.slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
+    }
+    if (!rc && enc.finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
+    if (rc) gz_abort(g);
+    (void)hipStreamSynchronize(c->z_stream);
+    (void)hipStreamSynchronize(c->z2_stream);
+    collect_targz_events(c, g.st, enc.check_ms);
+    g.st.tar_bytes = n;
+    g.st.gz_bytes = out.size();
+    g.st.wall_ms = now_ms() - t0;
+    x->targz = g.st;
+    merge_stats(x);
+    end_top(x, t_top0_);
+    if (rc) return lift(x, c, rc);
+    void* p = malloc(out.size() ? out.size() : 1);
+    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
+    memcpy(p, out.data(), out.size());
+    *out_p = p;
+    *out_len = out.size();
+    return SNAPHASH_OK;
 }
 
 } // namespace
@@ -408,49 +513,8 @@ try {
     if (!x || (!data && n) || !gz_out || !gz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
     *gz_out = nullptr;
     *gz_len = 0;
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t S = producer_slot_bytes(c, n);
-    int rc = ensure_slots(c, 2, S);
-    if (!rc) rc = ensure_deflate(c, S);
-    if (rc) return lift(x, c, rc);
-    std::string out;
-    GzPipe g;
-    g.c = c;
-    g.mem = &out;
-    gz_begin(g);
-    gz_emit(g, kGzipHeader, sizeof kGzipHeader, -1);
-    Slot& sl = c->slot[0];
-    const double t0 = now_ms();
-    for (uint64_t off = 0; off < n && !rc; off += S) {
-        const uint64_t take = std::min<uint64_t>(S, n - off);
-        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
-        EventPair* ev = next_events(c, 1);
-        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
-            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
-            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
-        rc = gz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
-    }
-    if (!rc && gz_finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
-    if (rc) gz_abort(g);
-    (void)hipStreamSynchronize(c->z_stream);
-    (void)hipStreamSynchronize(c->z2_stream);
-    collect_targz_events(c, g);
-    g.st.tar_bytes = n;
-    g.st.gz_bytes = out.size();
-    g.st.wall_ms = now_ms() - t0;
-    x->targz = g.st;
-    merge_stats(x);
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(out.size() ? out.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    memcpy(p, out.data(), out.size());
-    *gz_out = p;
-    *gz_len = out.size();
-    return SNAPHASH_OK;
+    GzipEncoder enc;
+    return encode_to_malloc(x, enc, data, n, gz_out, gz_len);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -474,35 +538,14 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
-namespace {
-
-// What tar_create_impl asks of a compressor (tarCreate's switch on the suffix, deb.go:269-276): the gzip producer below,
-// the .xz producer in xzpack.inc, the .bz2 producer in bzpack.inc.  All hand their bytes to the pass's consumers through gz_emit.
-struct TarCodec {
-    const char* suffix;
-    bool in_parts; // the pass's first slot may be compressed while it is still being filled (gz_slot_begin / _launch / _consume)
-    uint64_t (*slot_bytes)(const DevCtx* c, uint64_t job_bytes); // what the pass stages at a time (a multiple of 512)
-    int (*ensure)(DevCtx* c, uint64_t slot_bytes);
-    void (*begin)(GzPipe& g);                                    // what the file begins with
-    int (*slot)(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last);
-    int (*finish)(GzPipe& g, uint8_t archive_digest[64]);        // what it ends with; -> errno of the first failed write, or 0
-};
-
-void gz_header(GzPipe& g) { gz_emit(g, kGzipHeader, sizeof kGzipHeader, -1); }
-
-const TarCodec kGzipCodec = {".gz", true, producer_slot_bytes, ensure_deflate, gz_header, gz_process_slot, gz_finish};
-
-} // namespace
-
-static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* tarname, const char* source_dir, const char* exclude_prefix,
-                           snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest,
-                           GzCheck* check = nullptr /* the gzip producer's self-check: snaphash_snap_build alone asks for it */)
+static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, const char* source_dir, const char* exclude_prefix,
+                           snaphash_keep_fn keep, void* keep_user, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 {
     if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
     if (yaml_out) *yaml_out = nullptr;
     const size_t tl = strlen(tarname);
-    const size_t sfx = strlen(codec.suffix);
-    if (tl < sfx || strcmp(tarname + tl - sfx, codec.suffix) != 0) // deb.go:270-276: the entry's own suffix (.xz: snaphash_tar_create_xz, .bz2: _bz2)
+    const size_t sfx = strlen(enc.suffix);
+    if (tl < sfx || strcmp(tarname + tl - sfx, enc.suffix) != 0) // deb.go:270-276: the entry's own suffix (.xz: snaphash_tar_create_xz, .bz2: _bz2)
         return fail(x, SNAPHASH_EINVAL, std::string("unknown compression extension ") + tarname);
     TOP_ENTER(x);
     DevCtx* c = x->d0(); // several engines: the first one (the pass is bound by the serial archive digest, snaphash.h)
@@ -551,7 +594,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
         const unsigned cpus = call_cpus(x);
         // what the pass takes whatever its members are: ~5 GiB/s of tree, and a floor
         const double pass_s = std::max(0.008, (double)plan.total / 4.5e9);
-        const uint64_t slot_bytes = codec.slot_bytes(c, plan.total);
+        const uint64_t slot_bytes = enc.slot_bytes(c, plan.total);
         const uint64_t nslots = std::max<uint64_t>(1, (plan.total + slot_bytes - 1) / slot_bytes);
         uint64_t long_from = cpus >= 8 ? 0 : (uint64_t)(44e6 * pass_s / (double)nslots);
         if (const char* e = getenv("SNAPHASH_LONG_FROM")) long_from = strtoull(e, nullptr, 10); // lab: members longer than this on host threads
@@ -564,12 +607,11 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
         if (const char* e = getenv("SNAPHASH_MEMBER_HASHERS")) workers = (unsigned)std::min<unsigned long>(std::max<unsigned long>(strtoul(e, nullptr, 10), 1), 64); // lab
         if (!hosted_sizes.empty()) mh.start(hosted_sizes, workers);
     }
-    const uint64_t S = codec.slot_bytes(c, plan.total); // a multiple of 512 and of the compressor's chunk
+    const uint64_t S = enc.slot_bytes(c, plan.total); // a multiple of 512 and of the compressor's chunk
     if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "the engine's staging size is smaller than what the compressor takes at a time");
     rc = ensure_slots(c, 2, S);
-    if (!rc) rc = codec.ensure(c, S);
+    if (!rc) rc = enc.ensure(c, S);
     if (rc) return lift(x, c, rc);
-    if (check) HIP_TRY(x, c->z.chk.ensure((size_t)((S + kDeflateChunk - 1) / kDeflateChunk)));
     if (nstreams) HIP_TRY(x, c->hash.ensure(nstreams, true));
 
     std::vector<Source> srcs(plan.members.size());
@@ -586,13 +628,12 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     if (fd < 0) return fail(x, SNAPHASH_EIO, std::string(tarname) + ": " + strerror(errno));
     const double t_opened = now_ms();
     double t_first_fill = 0;
-    GzPipe g; // declared after the guard: its consumers are joined before the descriptor closes
+    OutPipe g; // declared after the guard: its consumers are joined before the descriptor closes
     g.c = c;
     g.fd = fd;
     g.want_sha = fused || archive_digest != nullptr;
-    g.check = check;
     gz_begin(g);
-    codec.begin(g);
+    enc.begin(g);
 
     // The pass, slot by slot (S bytes of the tar stream each), as a pipeline over the two staging slots:
     //   host threads   fill slot k+1 (headers, parallel pread at the tar offsets, job list)      | while
@@ -618,56 +659,31 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
         const int slot_no = (int)(&sl - &c->slot[0]);
         std::vector<MemberHashers::Task> host_tasks; // given out when the slot's bytes are there
         if (!hosted_sizes.empty()) mh.wait_slot(slot_no); // (host threads may still be hashing what this buffer held two slots ago)
-        while (mi < plan.members.size()) {
-            const TarMember& m = plan.members[mi];
-            const uint64_t end = m.data_off + (((uint64_t)m.size + 511) & ~(uint64_t)511);
-            if (m.first_off() >= s0 + n) break;
-            if (!m.pax.empty() && m.hdr_off > s0) { // the PAX extended header in front of the member: record, data, padding
-                if (m.pax_off >= s0) tar_pax_header(m, sl.h_buf.data() + (m.pax_off - s0));
-                const uint64_t x0 = m.pax_off + 512, x1 = x0 + m.pax.size(), xe = m.hdr_off; // data [x0, x1), zeros [x1, xe)
-                const uint64_t c0 = std::max(x0, s0), c1 = std::min(x1, s0 + n);
-                if (c1 > c0) memcpy(sl.h_buf.data() + (c0 - s0), m.pax.data() + (c0 - x0), c1 - c0);
-                const uint64_t z0 = std::max(x1, s0), z1 = std::min(xe, s0 + n);
-                if (z1 > z0) memset(sl.h_buf.data() + (z0 - s0), 0, z1 - z0);
-                if (m.hdr_off >= s0 + n) break; // the member's own header starts in the next slot
-            }
-            if (m.hdr_off >= s0) { // header record (never straddles: offsets and S are multiples of 512)
-                f.rc = tar_header(m, sl.h_buf.data() + (m.hdr_off - s0));
-                if (f.rc) {
-                    f.err = "member does not fit a tar header: " + m.name;
-                    return f;
-                }
-            }
-            const uint64_t d0 = std::max<uint64_t>(m.data_off, s0), d1 = std::min<uint64_t>(m.data_off + (uint64_t)m.size, s0 + n);
-            if (m.typeflag == '0' && d1 > d0)
-                ops.push_back(ReadOp{(uint32_t)mi, d0 - m.data_off, d1 - d0, sl.h_buf.data() + (d0 - s0), d1 == m.data_off + (uint64_t)m.size});
-            const uint64_t p0 = std::max<uint64_t>(m.data_off + (uint64_t)m.size, s0), p1 = std::min<uint64_t>(end, s0 + n);
-            if (p1 > p0) memset(sl.h_buf.data() + (p0 - s0), 0, p1 - p0); // padding to the 512-byte record
-            if (fused && hosted_of[mi] != 0xffffffffu) {
-                if (d1 > d0 || (m.size == 0 && m.hdr_off >= s0)) // (an empty member: one task of no bytes, where its header lies)
-                    host_tasks.push_back(MemberHashers::Task{hosted_of[mi], sl.h_buf.data() + (d1 > d0 ? d0 - s0 : 0), d1 > d0 ? d1 - d0 : 0, d0 == m.data_off || m.size == 0,
-                                                             d1 == m.data_off + (uint64_t)m.size || m.size == 0, slot_no});
-            } else if (fused && stream_of[mi] != 0xffffffffu && (d1 > d0 || (m.size == 0 && m.hdr_off >= s0))) {
+        std::vector<TarSegment> segs; // where the regular members' bytes go: the layout itself is tarpack.cpp's
+        f.rc = tar_fill_slot(plan, mi, s0, n, sl.h_buf.data(), segs);
+        if (f.rc) {
+            f.err = "member does not fit a tar header: " + plan.members[mi].name;
+            return f;
+        }
+        for (const TarSegment& sg : segs) {
+            if (sg.n) ops.push_back(ReadOp{sg.member, sg.file_off, sg.n, sl.h_buf.data() + sg.slot_off, sg.fin});
+            if (fused && hosted_of[sg.member] != 0xffffffffu) {
+                host_tasks.push_back(MemberHashers::Task{hosted_of[sg.member], sl.h_buf.data() + (sg.n ? sg.slot_off : 0), sg.n, sg.first, sg.fin, slot_no});
+            } else if (fused && stream_of[sg.member] != 0xffffffffu) {
                 Job j; // the file's bytes where they lie in the staged tar stream
-                j.data = (uint64_t)(uintptr_t)(sl.d_buf.data() + (d0 - s0));
-                j.nbytes = d1 > d0 ? d1 - d0 : 0;
-                j.total_prev = d0 - m.data_off;
-                j.idx = stream_of[mi];
-                j.flags = (d0 == m.data_off ? kJobFirst : 0u) | (d1 == m.data_off + (uint64_t)m.size ? kJobFinal : 0u);
+                j.data = (uint64_t)(uintptr_t)(sl.d_buf.data() + sg.slot_off);
+                j.nbytes = sg.n;
+                j.total_prev = sg.file_off;
+                j.idx = stream_of[sg.member];
+                j.flags = (sg.first ? kJobFirst : 0u) | (sg.fin ? kJobFinal : 0u);
                 sl.jobs.h[f.nj++] = j;
                 f.blocks += padded_blocks(j.nbytes, (j.flags & kJobFinal) != 0);
                 f.bytes += j.nbytes;
             }
-            if (end > s0 + n) break; // continues in the next slot
-            ++mi;
-        }
-        if (s0 + n > plan.total - 1024) { // tar.Writer.Close: two zero records
-            const uint64_t z0 = std::max<uint64_t>(plan.total - 1024, s0);
-            memset(sl.h_buf.data() + (z0 - s0), 0, s0 + n - z0);
         }
         if (in_parts) {
             if (hipSetDevice(c->device) != hipSuccess || hipEventRecord(ev.a, c->copy_stream) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "H2D failed"; return f; }
-            f.rc = gz_slot_begin(g, n, true, s0 + n >= plan.total);
+            f.rc = gz_slot_begin(g, *enc.parts, n, true, s0 + n >= plan.total);
             if (f.rc) { f.err = c->last_error; return f; }
             size_t o = 0;
             unsigned k = 0;
@@ -685,7 +701,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
                 }
                 if (hipMemcpyAsync(sl.d_buf.data() + b, sl.h_buf.data() + b, e - b, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
                     hipEventRecord(c->z_part_ev[k], c->copy_stream) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "H2D failed"; return f; }
-                f.rc = gz_slot_launch(g, sl, n, e, c->z_part_ev[k]);
+                f.rc = gz_slot_launch(g, *enc.parts, sl, n, e, c->z_part_ev[k]);
                 if (f.rc) { f.err = c->last_error; return f; }
             }
             f.ms = now_ms() - tf0;
@@ -712,7 +728,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     // they cost in hashing launches, each as long as its longest file whatever the slot holds.)
     EventPair* ev_next = (!rc && plan.total) ? next_events(c, 1) : nullptr;
     if (!rc && plan.total && !ev_next) rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const bool first_in_parts = codec.in_parts && std::min<uint64_t>(S, plan.total) > kPart;
+    const bool first_in_parts = enc.parts && std::min<uint64_t>(S, plan.total) > kPart;
     if (!rc && plan.total && !first_in_parts)
         next = std::async(std::launch::async, fill, std::ref(c->slot[0]), (uint64_t)0, std::min<uint64_t>(S, plan.total), *ev_next, false);
     unsigned k = 0;
@@ -742,7 +758,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
             if (!ev_next) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
             next = std::async(std::launch::async, fill, std::ref(c->slot[(k + 1) & 1u]), s0 + n, std::min<uint64_t>(S, plan.total - s0 - n), *ev_next, false);
         }
-        rc = parts ? gz_slot_consume(g, sl, n, (int)(k & 1u)) : codec.slot(g, sl, n, sl.copied, (int)(k & 1u), s0 == 0, s0 + n >= plan.total);
+        rc = parts ? gz_slot_consume(g, *enc.parts, sl, n, (int)(k & 1u)) : enc.slot(g, sl, n, sl.copied, (int)(k & 1u), s0 == 0, s0 + n >= plan.total);
     }
     } catch (const std::exception& ex) {
         rc = fail(c, SNAPHASH_ENOMEM, std::string("the pipeline could not run: ") + ex.what());
@@ -759,7 +775,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     uint8_t arch[64];
     const double t_produced = now_ms();
     if (!rc) {
-        const int werr = codec.finish(g, arch);
+        const int werr = enc.finish(g, arch);
         if (werr) rc = fail(c, SNAPHASH_EIO, std::string(tarname) + ": " + strerror(werr));
         else if (ftruncate(fd, (off_t)g.out_bytes) != 0 && errno != EINVAL) // (EINVAL: not a regular file -- a pipe, /dev/null -- nothing to cut)
             rc = fail(c, SNAPHASH_EIO, std::string(tarname) + ": " + strerror(errno));
@@ -773,7 +789,7 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
     (void)hipStreamSynchronize(c->z_stream);
     (void)hipStreamSynchronize(c->z2_stream);
     (void)hipStreamSynchronize(c->stream);
-    collect_targz_events(c, g);
+    collect_targz_events(c, g.st, enc.check_ms);
     c->pending = false;
     std::vector<uint8_t> dig(nstreams * 64 + 64);
     if (!rc && nstreams && hipMemcpy(dig.data(), c->hash.d_digests.data(), nstreams * 64, hipMemcpyDeviceToHost) != hipSuccess)
@@ -815,7 +831,8 @@ static int tar_create_impl(snaphash_ctx* x, const TarCodec& codec, const char* t
 int snaphash_tar_create(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
                         char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, kGzipCodec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    GzipEncoder enc;
+    return tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -823,7 +840,8 @@ try {
 int snaphash_tar_create_fn(snaphash_ctx* x, const char* tarname, const char* source_dir, snaphash_keep_fn keep, void* user,
                            char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, kGzipCodec, tarname, source_dir, nullptr, keep, user, yaml_out, yaml_len, archive_digest);
+    GzipEncoder enc;
+    return tar_create_impl(x, enc, tarname, source_dir, nullptr, keep, user, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }

@@ -178,6 +178,42 @@ void tar_pax_header(const TarMember& m, uint8_t h[512])
     h[155] = ' ';
 }
 
+// ---- the stream, a slot at a time -------------------------------------------------------------
+
+int tar_fill_slot(const TarPlan& plan, size_t& mi, uint64_t s0, uint64_t n, uint8_t* buf, std::vector<TarSegment>& segs)
+{
+    while (mi < plan.members.size()) {
+        const TarMember& m = plan.members[mi];
+        const uint64_t end = m.data_off + (((uint64_t)m.size + 511) & ~(uint64_t)511);
+        if (m.first_off() >= s0 + n) break;
+        if (!m.pax.empty() && m.hdr_off > s0) { // the PAX extended header in front of the member: record, data, padding
+            if (m.pax_off >= s0) tar_pax_header(m, buf + (m.pax_off - s0));
+            const uint64_t x0 = m.pax_off + 512, x1 = x0 + m.pax.size(), xe = m.hdr_off; // data [x0, x1), zeros [x1, xe)
+            const uint64_t c0 = std::max(x0, s0), c1 = std::min(x1, s0 + n);
+            if (c1 > c0) memcpy(buf + (c0 - s0), m.pax.data() + (c0 - x0), c1 - c0);
+            const uint64_t z0 = std::max(x1, s0), z1 = std::min(xe, s0 + n);
+            if (z1 > z0) memset(buf + (z0 - s0), 0, z1 - z0);
+            if (m.hdr_off >= s0 + n) break; // the member's own header starts in the next slot
+        }
+        if (m.hdr_off >= s0) { // header record (never straddles: offsets and slots are multiples of 512)
+            const int rc = tar_header(m, buf + (m.hdr_off - s0));
+            if (rc) return rc;
+        }
+        const uint64_t d0 = std::max<uint64_t>(m.data_off, s0), d1 = std::min<uint64_t>(m.data_off + (uint64_t)m.size, s0 + n);
+        if (m.typeflag == '0' && (d1 > d0 || (m.size == 0 && m.hdr_off >= s0))) // (an empty member: one segment of no bytes, where its header lies)
+            segs.push_back(TarSegment{(uint32_t)mi, d0 - s0, d0 - m.data_off, d1 > d0 ? d1 - d0 : 0, d0 == m.data_off, d1 == m.data_off + (uint64_t)m.size});
+        const uint64_t p0 = std::max<uint64_t>(m.data_off + (uint64_t)m.size, s0), p1 = std::min<uint64_t>(end, s0 + n);
+        if (p1 > p0) memset(buf + (p0 - s0), 0, p1 - p0); // padding to the 512-byte record
+        if (end > s0 + n) break; // continues in the next slot
+        ++mi;
+    }
+    if (s0 + n > plan.total - 1024) { // tar.Writer.Close: two zero records
+        const uint64_t z0 = std::max<uint64_t>(plan.total - 1024, s0);
+        memset(buf + (z0 - s0), 0, s0 + n - z0);
+    }
+    return SNAPHASH_OK;
+}
+
 // ---- CRC-32 -----------------------------------------------------------------------------------
 
 static uint32_t g_crc[8][256];

@@ -57,6 +57,20 @@ int tar_header(const TarMember& m, uint8_t out[512]);
 // The header record of m's PAX extended header (typeflag 'x', size = m.pax.size()).
 void tar_pax_header(const TarMember& m, uint8_t out[512]);
 
+// The stream a slot at a time, as the producer stages it: [s0, s0 + n) of plan's stream (both multiples of 512, but for
+// the stream's end) into buf -- PAX header records, PAX data and padding, ustar headers, member padding and the two closing
+// zero records, and none of a regular member's content.  For that, every regular member with content in the slot gets a
+// segment: n bytes from file_off of the member's file belong at buf + slot_off; first / fin: the stretch holds the file's
+// first / last byte.  An empty regular member gets one segment of no bytes where its header lies, with both set.
+// mi: the first member that may still touch the slot, advanced to the next slot's.  Returns 0, or tar_header's code with
+// mi at the member whose header does not fit.
+struct TarSegment {
+    uint32_t member;
+    uint64_t slot_off, file_off, n;
+    bool first, fin;
+};
+int tar_fill_slot(const TarPlan& plan, size_t& mi, uint64_t s0, uint64_t n, uint8_t* buf, std::vector<TarSegment>& segs);
+
 // CRC-32 (IEEE 802.3, the gzip trailer's), slice-by-8, and the combination of the CRCs of two
 // adjacent ranges (the second of len2 bytes).
 uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n);

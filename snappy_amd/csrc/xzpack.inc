@@ -1,5 +1,5 @@
-// xzpack.inc -- the data.tar.xz producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers and
-// staging it shares: tar_create_impl takes the compressor as a parameter).
+// xzpack.inc -- the data.tar.xz producer, textually part of snaphash_api.cpp (behind targz.inc, whose pass, consumers,
+// staging and buffer driver it shares: XzEncoder is one of targz.inc's Encoders, made for a call with the call's parameters).
 //
 // tarCreate's ".xz" branch (reference clickdeb/deb.go:272-273) pipes the tar stream through `xz --compress --stdout`,
 // which writes ONE Block: one serial LZMA chain, for the encoder and for every decoder after it.  Here the staged tar
@@ -16,43 +16,50 @@ namespace {
 
 static_assert(kXzEncBlockMax == kXzGpuBlockMax, "every Block this side writes is one the install side's kernel takes");
 
-// the producer's slot size, cut down to whole Blocks
-uint64_t xz_slot_bytes_for(const DevCtx* c, uint64_t job_bytes, uint64_t block_size)
-{
-    const uint64_t s = producer_slot_bytes(c, job_bytes);
-    return std::max<uint64_t>(s - s % block_size, block_size);
-}
-uint64_t xz_slot_bytes(const DevCtx* c, uint64_t job_bytes) { return xz_slot_bytes_for(c, job_bytes, kXzEncBlockDefault); }
-
-int ensure_xzenc(DevCtx* c, uint64_t slot_bytes)
-{
-    if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority (ensure_deflate)
-        int least = 0, greatest = 0;
-        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
+// The .xz encoder of one call: the Block size and the Blocks' Check it was asked for (the entries have validated them), and
+// the Index records of the Blocks written so far.
+struct XzEncoder final : Encoder {
+    const uint64_t block_size;
+    const uint32_t check;
+    std::vector<XzEncRecord> recs;
+    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64)
+        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk) {}
+    uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const override // the producer's slot size, cut down to whole Blocks
+    {
+        const uint64_t s = producer_slot_bytes(c, job_bytes);
+        return std::max<uint64_t>(s - s % block_size, block_size);
     }
-    if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking));
-    HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
-    return SNAPHASH_OK;
-}
-
-void xz_header(GzPipe& g)
-{
-    uint8_t h[kXzEncStreamHeader];
-    xzenc_stream_header(h, g.xz_check);
-    g.xz_recs.clear();
-    gz_emit(g, h, sizeof h, -1);
-}
+    int ensure(DevCtx* c, uint64_t slot_bytes) override
+    {
+        const int rc = ensure_producer_streams(c);
+        if (rc) return rc;
+        HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
+        return SNAPHASH_OK;
+    }
+    void begin(OutPipe& g) override
+    {
+        uint8_t h[kXzEncStreamHeader];
+        xzenc_stream_header(h, check);
+        gz_emit(g, h, sizeof h, -1);
+    }
+    int slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last) override;
+    int finish(OutPipe& g, uint8_t archive_digest[64]) override // the Index and the footer
+    {
+        std::vector<uint8_t> tail;
+        xzenc_index_footer(recs, tail, check);
+        return pipe_finish(g, tail.data(), tail.size(), archive_digest);
+    }
+};
 
 // The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream)
 // as whole Blocks into c->xe.h_out[zbuf] and on to the consumers.
-int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
+int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool, bool)
 {
     if (n == 0) return SNAPHASH_OK;
     DevCtx* c = g.c;
     XzEncBufs& b = c->xe;
     hipStream_t zs = c->z_stream;
-    const uint64_t bs = g.xz_block_size;
+    const uint64_t bs = z.block_size;
     const uint32_t nch = (uint32_t)((n + kXzEncChunk - 1) / kXzEncChunk), cpb = (uint32_t)(bs / kXzEncChunk);
     const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
     if (n > sl.cap() || b.d_prev.size() < n || b.res.size() < nch || b.cap() < XzEncBufs::out_cap(n))
@@ -80,7 +87,7 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     HIP_TRY(c, hipStreamSynchronize(zs));
     // where everything goes: a Block after the other, a chunk after the other
     std::vector<XzEncBlockLayout> lay(nblk);
-    const uint32_t check = g.xz_check, check_size = xzenc_check_size(check);
+    const uint32_t check = z.check, check_size = xzenc_check_size(check);
     std::vector<uint64_t> at(nblk), offs(nblk), lens(nblk);
     std::vector<uint8_t> fields((size_t)nblk * kXzEncCheckMax); // a Block's Check field as the file holds it
     uint64_t total = 0;
@@ -147,23 +154,16 @@ int xz_process_slot(GzPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf,
     const uint32_t dict_byte = xzenc_dict_byte(bs);
     for (uint32_t k = 0; k < nblk; ++k) {
         xzenc_block_frame(h + at[k], lay[k], lens[k], dict_byte, fields.data() + (size_t)k * kXzEncCheckMax, check_size);
-        g.xz_recs.push_back(XzEncRecord{lay[k].unpadded, lens[k]});
+        z.recs.push_back(XzEncRecord{lay[k].unpadded, lens[k]});
     }
     gz_emit(g, h, total, zbuf);
-    g.isize += n;
     g.st.chunks += nch;
     return SNAPHASH_OK;
 }
 
-// the Index and the footer; -> errno of the first failed write, or 0
-int xz_finish(GzPipe& g, uint8_t archive_digest[64])
+int XzEncoder::slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf, bool is_first, bool is_last)
 {
-    std::vector<uint8_t> tail;
-    xzenc_index_footer(g.xz_recs, tail, g.xz_check);
-    gz_emit(g, tail.data(), tail.size(), -1);
-    gz_join(g);
-    if (g.want_sha && archive_digest) host_sha512_final(g.sha, archive_digest);
-    return g.write_err;
+    return xz_process_slot(g, *this, sl, n, ready, zbuf, is_first, is_last);
 }
 
 // The producer's kernel sequence once more, for snaphash_xzenc_stages_device: xz_process_slot's steps in its order on a
@@ -209,8 +209,6 @@ int xz_encode_stages(DevCtx* c, const uint8_t* d_in, uint64_t n, uint64_t bs, ui
     return SNAPHASH_OK;
 }
 
-const TarCodec kXzCodec = {".xz", false, xz_slot_bytes, ensure_xzenc, xz_header, xz_process_slot, xz_finish};
-
 // the body of snaphash_xz_buffer / snaphash_xz_buffer_check
 int xz_buffer_entry(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, uint32_t check, void** xz_out, size_t* xz_len)
 try {
@@ -219,52 +217,8 @@ try {
     *xz_len = 0;
     if (!xzenc_check_valid(check)) return fail(x, SNAPHASH_EINVAL, "xz: the Check is 0 (none), 1 (CRC-32), 4 (CRC-64) or 10 (SHA-256)");
     if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
-    TOP_ENTER(x);
-    DevCtx* c = x->d0();
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t S = xz_slot_bytes_for(c, n, block_size);
-    if (S > c->staging) return fail(x, SNAPHASH_EINVAL, "xz: the block size is larger than the engine's staging size");
-    int rc = ensure_slots(c, 2, S);
-    if (!rc) rc = ensure_xzenc(c, S);
-    if (rc) return lift(x, c, rc);
-    std::string out;
-    GzPipe g;
-    g.c = c;
-    g.mem = &out;
-    gz_begin(g);
-    g.xz_block_size = block_size;
-    g.xz_check = check;
-    xz_header(g);
-    Slot& sl = c->slot[0];
-    const double t0 = now_ms();
-    for (uint64_t off = 0; off < n && !rc; off += S) {
-        const uint64_t take = std::min<uint64_t>(S, n - off);
-        memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
-        EventPair* ev = next_events(c, 1);
-        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
-            hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
-            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
-        rc = xz_process_slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
-    }
-    if (!rc && xz_finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
-    if (rc) gz_abort(g);
-    (void)hipStreamSynchronize(c->z_stream);
-    (void)hipStreamSynchronize(c->z2_stream);
-    collect_targz_events(c, g);
-    g.st.tar_bytes = n;
-    g.st.gz_bytes = out.size();
-    g.st.wall_ms = now_ms() - t0;
-    x->targz = g.st;
-    merge_stats(x);
-    end_top(x, t_top0_);
-    if (rc) return lift(x, c, rc);
-    void* p = malloc(out.size() ? out.size() : 1);
-    if (!p) return fail(x, SNAPHASH_ENOMEM, "malloc");
-    memcpy(p, out.data(), out.size());
-    *xz_out = p;
-    *xz_len = out.size();
-    return SNAPHASH_OK;
+    XzEncoder enc(block_size, check);
+    return encode_to_malloc(x, enc, data, n, xz_out, xz_len);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }
@@ -316,7 +270,8 @@ try {
 int snaphash_tar_create_xz(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix, char** yaml_out,
                            size_t* yaml_len, uint8_t* archive_digest)
 try {
-    return tar_create_impl(x, kXzCodec, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    XzEncoder enc;
+    return tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
 }

@@ -160,7 +160,7 @@ void case_groups()
     printf("groups ok\n");
 }
 
-// The review's sequence (targz.inc ensure_deflate): a small job's ensure fails after its first buffer,
+// The review's sequence (targz.inc GzipEncoder::ensure): a small job's ensure fails after its first buffer,
 // then a larger job's ensure succeeds on the same group.  Every buffer must hold the larger job.
 void case_review()
 {

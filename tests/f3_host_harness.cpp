@@ -1,7 +1,7 @@
 // Test-only (CPU): (1) a serial model of deflate_chunks_kernel -- same chunking, hash chains, lazy parse
 // (tests/deflate_model.h), token encoder (snappy_amd/csrc/deflate_core.h) and framing -- so that the code tables and the
 // byte-aligned chunk framing are checked against zlib before the kernel runs on a GPU; (2) the host
-// half of the tar producer (tarpack.cpp): plan + ustar headers + CRC-32.  Not part of the product.
+// half of the tar producer (tarpack.cpp): plan + ustar headers + the slot layout + CRC-32.  Not part of the product.
 #include <fcntl.h>
 #include <stdlib.h>
 #include <string.h>
@@ -252,6 +252,74 @@ int f3_tar_stream(const char* dir, const char* exclude_prefix, uint8_t** out, si
     *out = buf;
     *out_len = plan.total;
     return 0;
+}
+// The same stream as the producer stages it: tar_fill_slot, slot after slot of slot_bytes (a multiple of 512; 0: the whole
+// stream in one) into a buffer pre-filled with 0xA5, so that a position no branch writes shows; every segment's bytes are
+// then read to their place.  *segs_out: seven uint64 a segment -- member, s0, slot_off, file_off, n, first, fin.
+int f3_tar_stream_slots(const char* dir, const char* exclude_prefix, uint64_t slot_bytes, uint8_t** out, size_t* out_len, uint64_t** segs_out,
+                        size_t* nsegs_out)
+{
+    TarPlan plan;
+    int en = 0;
+    std::string what;
+    int rc = tar_plan(dir, exclude_prefix ? exclude_prefix : "", plan, &en, &what);
+    if (rc) return rc;
+    if (slot_bytes == 0) slot_bytes = plan.total;
+    if (slot_bytes % 512) return -2;
+    uint8_t* buf = (uint8_t*)malloc(plan.total);
+    memset(buf, 0xA5, plan.total);
+    std::vector<uint64_t> flat;
+    std::vector<TarSegment> segs;
+    size_t mi = 0;
+    for (uint64_t s0 = 0; s0 < plan.total; s0 += slot_bytes) {
+        const uint64_t n = std::min<uint64_t>(slot_bytes, plan.total - s0);
+        segs.clear();
+        rc = tar_fill_slot(plan, mi, s0, n, buf + s0, segs);
+        if (rc) { free(buf); return rc; }
+        for (const TarSegment& sg : segs) {
+            if (sg.member >= plan.members.size() || sg.slot_off > n || sg.n > n - sg.slot_off) { free(buf); return -4; } // before anything is read there
+            if (sg.n) {
+                const int fd = open(plan.members[sg.member].path.c_str(), O_RDONLY);
+                if (fd < 0 || pread(fd, buf + s0 + sg.slot_off, (size_t)sg.n, (off_t)sg.file_off) != (ssize_t)sg.n) { if (fd >= 0) close(fd); free(buf); return -3; }
+                close(fd);
+            }
+            for (uint64_t v : {(uint64_t)sg.member, s0, sg.slot_off, sg.file_off, sg.n, (uint64_t)sg.first, (uint64_t)sg.fin}) flat.push_back(v);
+        }
+    }
+    if (mi != plan.members.size()) { free(buf); return -5; }
+    uint64_t* fs = (uint64_t*)malloc(flat.size() * sizeof(uint64_t) + 1);
+    memcpy(fs, flat.data(), flat.size() * sizeof(uint64_t));
+    *out = buf;
+    *out_len = plan.total;
+    *segs_out = fs;
+    *nsegs_out = flat.size() / 7;
+    return 0;
+}
+// tar_fill_slot over a hand-made plan of three members whose second has a name no ustar field holds and no PAX record (what
+// tar_plan never leaves: it adds the record): -> tar_fill_slot's code; *mi_out: where it left mi
+int f3_tar_fill_slot_unfit(uint64_t slot_bytes, size_t* mi_out)
+{
+    TarPlan plan;
+    uint64_t off = 0;
+    for (const std::string& name : {std::string("./a"), "./" + std::string(120, 'n'), std::string("./z")}) {
+        TarMember m;
+        m.name = name;
+        m.size = 700;
+        m.st_mode = 0100644;
+        m.mtime = 1;
+        m.hdr_off = off;
+        m.data_off = off + 512;
+        off += 512 + 1024;
+        plan.members.push_back(m);
+    }
+    plan.total = off + 1024;
+    std::vector<uint8_t> buf(plan.total, 0xA5);
+    std::vector<TarSegment> segs;
+    size_t mi = 0;
+    int rc = 0;
+    for (uint64_t s0 = 0; s0 < plan.total && !rc; s0 += slot_bytes) rc = tar_fill_slot(plan, mi, s0, std::min<uint64_t>(slot_bytes, plan.total - s0), buf.data() + s0, segs);
+    *mi_out = mi;
+    return rc;
 }
 // the header record of a regular member of the given size (tests: the fields beyond what a real tree can afford)
 int f3_tar_header_of(const char* name, int64_t size, uint8_t* out512)

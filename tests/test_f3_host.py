@@ -293,6 +293,122 @@ def test_tar_size_field_beyond_8_gib(f3):
         assert ti.size == size and ti.name == "./big" and ti.isreg(), size
 
 
+SLOT_SIZES = (512, 1024, 1536, 4096, 65536, 0)  # 512: every record on a slot boundary; 0: the whole stream in one
+
+
+def _make_slot_tree(root):
+    """Every shape tar_fill_slot has a branch for: regular files around the record size and one of many records, two empty
+    files next to each other, an empty file as the stream's last member, a symlink, directories, PAX members whose records
+    fit one 512-byte record and PAX members whose records take two.  -> {relative path: content} of the regular files."""
+    rng = np.random.default_rng(11)
+    files = {"sizes/f%05d" % n: rng.integers(0, 256, size=n, dtype=np.uint8).tobytes() for n in (0, 1, 511, 512, 513, 1023, 1024, 1025, 70001)}
+    files.update({"empties/e0": b"", "empties/e1": b"", "empties/e2-not": b"x", "zzz-last-and-empty": b""})
+    files["x" * 101] = b"short PAX record: no slash to split at"
+    files[os.path.join("d" * 90, "e" * 90, "f" * 90, "leaf")] = b"deep " * 300
+    wide = "w" * 250
+    files[os.path.join(wide, "r" * 240)] = b"r" * 513                                  # a path record of ~505 bytes: one record
+    files[os.path.join(wide, "q" * 250, "p" * 240)] = b"two records of PAX data" * 50  # ~755 bytes: two
+    files[os.path.join(wide, "q" * 250, "empty-behind-pax" + "o" * 200)] = b""
+    for rel, data in files.items():
+        os.makedirs(os.path.dirname(os.path.join(root, rel)), exist_ok=True)
+        with open(os.path.join(root, rel), "wb") as f:
+            f.write(data)
+    os.makedirs(os.path.join(root, "empty-dir"))
+    os.symlink("sizes/f00513", os.path.join(root, "link"))
+    os.symlink("t" * 150, os.path.join(root, "long-link"))                             # linkpath alone: under 512
+    os.symlink("t" * 400, os.path.join(root, wide, "s" * 240))                         # path + linkpath: over 512
+    return files
+
+
+@pytest.fixture(scope="module")
+def slot_tree(f3, tmp_path_factory):
+    """The tree, its stream as f3_tar_stream lays it out whole (the independent reference) and tarfile's view of that."""
+    root = str(tmp_path_factory.mktemp("slots") / "src")
+    os.makedirs(root)
+    files = _make_slot_tree(root)
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    assert f3.f3_tar_stream(root.encode(), None, ctypes.byref(out), ctypes.byref(n)) == 0
+    ref = ctypes.string_at(out.value, n.value)
+    f3.f3_free(out)
+    members = tarfile.open(fileobj=io.BytesIO(ref), mode="r:").getmembers()
+    # the tree holds what it is meant to: the last member empty, two empty neighbours, PAX data of one record and of two
+    assert members[-1].isreg() and members[-1].size == 0 and ref[-1536:] != bytes(1536) and ref[-1024:] == bytes(1024)
+    assert any(a.isreg() and b.isreg() and a.size == 0 and b.size == 0 for a, b in zip(members, members[1:]))
+    pax_sizes = [int(ref[o + 124:o + 135], 8) for o in range(0, len(ref) - 1024, 512) if ref[o + 156:o + 157] == b"x" and ref[o + 257:o + 262] == b"ustar"]
+    assert any(s < 512 for s in pax_sizes) and any(s > 512 for s in pax_sizes), pax_sizes
+    return root, files, ref, members
+
+
+def _stream_in_slots(f3, root, slot_bytes):
+    """-> (the stream assembled by tar_fill_slot, its segments as dicts)."""
+    f3.f3_tar_stream_slots.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    out, n, segs, nsegs = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p(), ctypes.c_size_t()
+    assert f3.f3_tar_stream_slots(root.encode(), None, slot_bytes, ctypes.byref(out), ctypes.byref(n), ctypes.byref(segs), ctypes.byref(nsegs)) == 0
+    stream = ctypes.string_at(out.value, n.value)
+    flat = np.frombuffer(ctypes.string_at(segs.value, nsegs.value * 56), dtype=np.uint64).reshape(-1, 7).tolist()
+    f3.f3_free(out)
+    f3.f3_free(segs)
+    return stream, [dict(zip(("member", "s0", "slot_off", "file_off", "n", "first", "fin"), row)) for row in flat]
+
+
+@pytest.mark.parametrize("slot_bytes", SLOT_SIZES)
+def test_tar_fill_slot_lays_out_the_stream_slot_by_slot(f3, slot_tree, slot_bytes):
+    """tarpack.cpp's tar_fill_slot, the layout the producer stages from, at slot sizes no GPU run reaches: the stream put
+    together slot by slot (into a buffer of 0xA5, the segments' bytes read to their places) is f3_tar_stream's byte for byte,
+    and tarfile reads every name, link target and content back from it.  The segments: none for a directory or a symlink;
+    per regular member they run through the file from 0 without gap or overlap and sum to its size, lie where the member's
+    content lies in the stream, the first alone has `first` and the last alone `fin`; an empty member has exactly one, of no
+    bytes, with both."""
+    root, files, ref, members = slot_tree
+    stream, segs = _stream_in_slots(f3, root, slot_bytes)
+    assert len(stream) == len(ref)
+    if stream != ref:
+        at = next(i for i in range(len(ref)) if stream[i] != ref[i])
+        pytest.fail("slot size %d: first difference at offset %d (record %d + %d): %r, reference %r" % (slot_bytes, at, at // 512, at % 512, stream[at:at + 16], ref[at:at + 16]))
+    tf = tarfile.open(fileobj=io.BytesIO(stream), mode="r:")
+    got = tf.getmembers()
+    assert [m.name for m in got] == [m.name for m in members] and len(got) == len(files) + sum(1 for m in members if not m.isreg())
+    for m in got:
+        p = os.path.join(root, m.name[2:])
+        if m.isreg():
+            assert tf.extractfile(m).read() == files[m.name[2:]], m.name
+        elif m.issym():
+            assert m.linkname == os.readlink(p), m.name
+        else:
+            assert m.isdir() and os.path.isdir(p), m.name
+    by_member = {}
+    for s in segs:
+        assert members[s["member"]].isreg(), (slot_bytes, s, members[s["member"]].name)
+        assert s["s0"] % (slot_bytes or len(ref)) == 0 and s["slot_off"] + s["n"] <= (slot_bytes or len(ref)), (slot_bytes, s)
+        by_member.setdefault(s["member"], []).append(s)
+    assert sorted(by_member) == [i for i, m in enumerate(members) if m.isreg()]
+    for i, ss in by_member.items():
+        m = members[i]
+        at = 0
+        for k, s in enumerate(ss):
+            assert s["file_off"] == at and s["s0"] + s["slot_off"] == m.offset_data + at, (slot_bytes, m.name, s)
+            assert (s["first"], s["fin"]) == (int(k == 0), int(k == len(ss) - 1)), (slot_bytes, m.name, ss)
+            assert s["n"] > 0 or m.size == 0, (slot_bytes, m.name, ss)
+            at += s["n"]
+        assert at == m.size, (slot_bytes, m.name, ss)
+        if m.size == 0:
+            assert len(ss) == 1 and ss[0]["n"] == 0 and ss[0]["first"] == 1 and ss[0]["fin"] == 1, (slot_bytes, m.name, ss)
+        if slot_bytes == 512:  # a slot a record: a segment a record of content
+            assert len(ss) == max(1, (m.size + 511) // 512), (m.name, len(ss))
+
+
+def test_tar_fill_slot_returns_the_header_that_does_not_fit(f3):
+    """A name that neither the ustar fields nor a PAX record carry (a plan made by hand: tar_plan would add the record):
+    tar_header's SNAPHASH_ENAME comes back with mi at that member, whatever the slot size."""
+    from snappy_amd import _lib
+    f3.f3_tar_fill_slot_unfit.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
+    for slot_bytes in (512, 1024, 1536, 4096, 65536):
+        mi = ctypes.c_size_t(99)
+        assert f3.f3_tar_fill_slot_unfit(slot_bytes, ctypes.byref(mi)) == _lib.ENAME, slot_bytes
+        assert mi.value == 1, slot_bytes
+
+
 def test_f3_host_code_under_asan_and_ubsan(tmp_path):
     """tarpack.cpp (walk, ustar headers, CRC-32), hostsha.cpp and the serial model of the DEFLATE kernel under
     AddressSanitizer + UBSan (CPU build; GPU sanitizers are not available on the pool): a tree with every member
@@ -306,6 +422,13 @@ def test_f3_host_code_under_asan_and_ubsan(tmp_path):
 int main(int argc, char** argv) {
     uint8_t* out = nullptr; size_t n = 0;
     if (f3_tar_stream(argv[1], argv[2], &out, &n) != 0 || n %% 512) return 3;
+    {   // the same stream from tar_fill_slot, a record a slot: every header, PAX record and padding on a slot boundary
+        uint8_t* out2 = nullptr; size_t n2 = 0, nsegs = 0; uint64_t* segs = nullptr;
+        if (f3_tar_stream_slots(argv[1], argv[2], 512, &out2, &n2, &segs, &nsegs) != 0 || n2 != n || memcmp(out, out2, n) != 0 || nsegs == 0) return 8;
+        size_t mi = 0;
+        if (f3_tar_fill_slot_unfit(512, &mi) == 0 || mi != 1) return 9;
+        f3_free(out2); f3_free(segs);
+    }
     size_t gz_len = 0;
     uint8_t* gz = f3_model_gzip(out, n, &gz_len);            // the tar stream through the kernel's CPU model
     if (!gz || gz_len < 18) return 4;
@@ -340,5 +463,7 @@ int main(int argc, char** argv) {
     open(os.path.join(deep, "f" * 60), "w").write("prefix split")
     open(os.path.join(deep, "g" * 200), "w").write("PAX path record")          # beyond any ustar split
     os.symlink("t" * 300, os.path.join(deep, "pax-link"))                      # PAX linkpath record
+    os.makedirs(os.path.join(root, "zz-slots"))
+    _make_slot_tree(os.path.join(root, "zz-slots"))                            # sizes around the record, PAX data of two records, an empty last member
     r = subprocess.run([exe, root, root + "/DEBIAN"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0 and b"asan f3 ok" in r.stdout, r.stderr.decode()[-2000:]

@@ -3,13 +3,17 @@ the CRC-64 kernels) and snaphash_tar_create_xz, in both configurations (conftest
 tests/xzenc_cases.py.  liblzma's verdict (Python's lzma) carries the tests; the bytes are also held against the host
 model of the same header (tests/xzenc_host_harness.cpp) -- a self-comparison that shows no lane, workgroup, slot or launch
 leaks into the output -- and the library's own install side reads every file back, a Block a workgroup."""
+import bz2
+import ctypes
 import hashlib
 import io
 import lzma
 import os
 import subprocess
 import tarfile
+import zlib
 
+import numpy as np
 import pytest
 
 import trees
@@ -17,6 +21,7 @@ import xz_cases as X
 import xzenc_cases as E
 from conftest import ROOT
 from snappy_amd import Context, _lib, clickdeb
+from test_f3_host import f3  # noqa: F401  (f3_tar_stream: the tar stream laid out whole)
 from test_xzenc_host import encode, load_enc, plan
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +91,84 @@ def test_the_bytes_do_not_depend_on_slots_or_launches(snaphash_mode, xe):
         with pytest.raises(_lib.SnaphashError) as e:  # a Block must fit the engine's staging
             c.xz_buffer(data, 128 * 1024)
         assert e.value.code == _lib.EINVAL
+
+
+def _encoder_calls(data):
+    """The build side's buffer calls, one format after the other and each format twice with other parameters:
+    (what to call on a Context, Python's decoder, what the stream's header must say)."""
+    return [
+        (lambda c: c.xz_buffer(data, 65536, 1), lzma.decompress, lambda z: z[:6] == b"\xfd7zXZ\x00" and z[6:8] == b"\x00\x01"),
+        (lambda c: c.bzip2_buffer(data, 1), bz2.decompress, lambda z: z[:4] == b"BZh1"),
+        (lambda c: c.gzip_buffer(data), lambda z: zlib.decompress(z, 31), lambda z: z[:3] == b"\x1f\x8b\x08"),
+        (lambda c: c.xz_buffer(data), lzma.decompress, lambda z: z[:6] == b"\xfd7zXZ\x00" and z[6:8] == b"\x00\x04"),
+        (lambda c: c.bzip2_buffer(data, 9), bz2.decompress, lambda z: z[:4] == b"BZh9"),
+        (lambda c: c.gzip_buffer(data), lambda z: zlib.decompress(z, 31), lambda z: z[:3] == b"\x1f\x8b\x08"),
+    ]
+
+
+@pytest.mark.kernels_only("the encoders hold the same state in both configurations: no call here hashes a member")
+def test_encoder_state_is_the_calls_own(snaphash_mode, tmp_path, f3):
+    """An encoder's parameters and running state belong to one call: six buffer calls in one Context -- .xz with a 64 KiB
+    Block and CRC-32, .bz2 at level 1, gzip, .xz with the default Block and Check, .bz2 at level 9, gzip again -- each decode
+    (lzma, bz2, zlib) to the input, say in their header what was asked (the Check id, the level), and are byte for byte what
+    the same call gives as the first of a fresh Context of the same staging size; then a .tar.bz2 and a .tar.xz of a small
+    tree in that Context carry f3_tar_stream's stream at level 9 and with CRC-64.
+
+    The staging size is 1 MiB: the smallest that admits every call of the list (a Block of the default 1 MiB and a level 9
+    block's 719 872 bytes of input must fit the staging; an engine of 128 KiB refuses both, as the test above and
+    test_gpu_bz2enc.py pin for smaller engines).  The 128 KiB engine follows with the calls it admits, which then take two
+    and three slots each -- the Index records, the carried bits and the CRC go from slot to slot -- and with its refusals,
+    after which it still gives the same bytes."""
+    rng = np.random.default_rng(90)
+    n = 3 * 65536 + 1
+    data = X.text(n // 2, 91) + rng.integers(0, 256, size=n - n // 2, dtype=np.uint8).tobytes()
+    calls = _encoder_calls(data)
+
+    def fresh(staging, k):
+        with Context(device=0, staging_bytes=staging) as c:
+            return calls[k][0](c)
+
+    root = str(tmp_path / "src")
+    os.makedirs(os.path.join(root, "d"))
+    for rel, content in (("a", b"a" * 1000), ("d/b", data[:70001]), ("d/empty", b"")):
+        with open(os.path.join(root, rel), "wb") as fh:
+            fh.write(content)
+    p, ln = ctypes.c_void_p(), ctypes.c_size_t()
+    assert f3.f3_tar_stream(root.encode(), None, ctypes.byref(p), ctypes.byref(ln)) == 0
+    tar = ctypes.string_at(p.value, ln.value)
+    f3.f3_free(p)
+
+    with Context(device=0, staging_bytes=1 << 20) as c:
+        outs = []
+        for k, (call, decode, header_ok) in enumerate(calls):
+            z = call(c)
+            assert decode(z) == data, k
+            assert header_ok(z), (k, z[:8])
+            assert z == fresh(1 << 20, k), k
+            outs.append(z)
+        assert outs[2] == outs[5] and outs[0] != outs[3] and outs[1] != outs[4]
+        out_bz, out_xz = str(tmp_path / "t.tar.bz2"), str(tmp_path / "t.tar.xz")
+        c.tar_create_bz2(out_bz, root)
+        raw = open(out_bz, "rb").read()
+        assert bz2.decompress(raw) == tar and raw[:4] == b"BZh9"
+        c.tar_create_xz(out_xz, root)
+        raw = open(out_xz, "rb").read()
+        assert lzma.decompress(raw) == tar and raw[6:8] == b"\x00\x04"
+
+    with Context(device=0, staging_bytes=128 * 1024) as c:
+        for k in (0, 1, 2, 3, 4, 5, 0, 1):
+            call, decode, header_ok = calls[k]
+            if k in (3, 4):  # a Block, a block's input, larger than the engine's staging: refused, and the engine goes on
+                with pytest.raises(_lib.SnaphashError) as e:
+                    call(c)
+                assert e.value.code == _lib.EINVAL and "larger than the engine's staging size" in str(e.value), k
+                continue
+            z = call(c)
+            assert decode(z) == data and header_ok(z), k
+            assert c.targz_stats()["tar_bytes"] == n, k
+            assert z == fresh(128 * 1024, k), k
+            if k != 2 and k != 5:  # (.xz and .bz2 depend on no slot size; a gzip chunk's window ends at its slot's start)
+                assert z == outs[k], k
 
 
 def test_round_trip_through_the_librarys_own_install_side(snaphash_mode, model):
