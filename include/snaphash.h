@@ -373,6 +373,60 @@ int snaphash_xz_buffer_check(snaphash_ctx *ctx, const void *data, size_t n, uint
  * Blocks of 1 MiB; a Block never spans two staging slots.  snaphash_get_targz_stats reports the pass. */
 int snaphash_tar_create_xz(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
                            char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
+
+/* The two producers above with the caller's Block size and Check, and with the producer's self-check. */
+enum { SNAPHASH_XZ_SELF_CHECK = 1 }; /* every LZMA2 chunk is walked against the staged bytes it was made from, in HBM, before
+                                      * it leaves the GPU: a chunk that would not decode back fails the call (SNAPHASH_EDEVICE;
+                                      * snaphash_last_error names the Block, the chunk, the status -- snaphash_lzma2_verdict's --
+                                      * and the offset in the uncompressed stream; a file being written is unlinked).  The bytes
+                                      * written are the same with and without it.  Not covered: Block headers, padding,
+                                      * Check fields, Index and footer (written on the host), the copy back and the write;
+                                      * decoding the file covers those. */
+typedef struct snaphash_xz_options {
+    uint32_t struct_size; /* sizeof(snaphash_xz_options) */
+    uint32_t flags;       /* SNAPHASH_XZ_*; an unknown bit is SNAPHASH_EINVAL */
+    uint64_t block_size;  /* as in snaphash_xz_buffer: 0 = 1 MiB */
+    uint32_t check;       /* as in snaphash_xz_buffer_check: 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256 */
+    uint32_t reserved;    /* 0 */
+} snaphash_xz_options;
+typedef struct snaphash_xz_selfcheck_stats {
+    uint32_t struct_size; /* set by the caller */
+    uint32_t reserved;
+    uint64_t chunks;      /* LZMA2 chunks walked (all accepted, or the call failed); 0 without SNAPHASH_XZ_SELF_CHECK */
+    double ms;            /* the check kernel's own time, HIP events */
+} snaphash_xz_selfcheck_stats;
+/* opt == NULL, or a struct that is all zero (struct_size included): byte for byte what snaphash_xz_buffer /
+ * snaphash_tar_create_xz write (1 MiB Blocks, CRC-64, no self-check).  Otherwise struct_size says the struct's size and
+ * every field means what it says.  SNAPHASH_EINVAL: an unknown flag, a refused Block size, an unknown Check id. */
+int snaphash_xz_buffer_ex(snaphash_ctx *ctx, const void *data, size_t n, const snaphash_xz_options *opt, void **xz_out,
+                          size_t *xz_len);
+int snaphash_tar_create_xz_ex(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
+                              const snaphash_xz_options *opt, char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
+/* of the most recent of the two _ex calls above */
+int snaphash_get_xz_selfcheck_stats(const snaphash_ctx *ctx, snaphash_xz_selfcheck_stats *out);
+
+typedef struct snaphash_lzma2_verdict {
+    uint32_t status; /* 0 accepted; 1 a literal or stored byte differs; 2 a match's or short rep's copy differs; 3 a distance
+                        beyond the bytes in front of the position in its Block (or block_size); 4 not the producer's LZMA2
+                        (control byte, properties, dictionary reset inside a Block, first range coder byte not zero, end
+                        marker, input overrun); 5 a match longer than what is left of the chunk; 6 the header's uncompressed
+                        size is not the chunk's; 7 sizes or the coder's end do not meet the stretch's end (a missing, non-zero
+                        or misplaced end byte too); 8 the table entry lies outside the compressed bytes, or z_end < z_beg */
+    uint32_t offset; /* within the chunk: the first byte that differs, else how far the walk had come */
+} snaphash_lzma2_verdict;
+/* The self-check kernel alone, on tables the caller wrote (tests): d_in[0..n_in) is the staged stream in HBM, cut into Blocks
+ * of block_size bytes (as in snaphash_xz_buffer) and nchunks == ceil(n_in / 65536) chunks; d_z[0..n_z) holds the compressed
+ * bytes, chunk c's stretch being [z_beg[c], z_end[c]) (host arrays).  A chunk is accepted when its stretch is ONE LZMA2 chunk
+ * of the producer's form -- a Block's first 0xE0|.. with properties 0x5D or 0x01, a later one 0xC0|.. with 0x5D or 0x02 --
+ * whose uncompressed size is the chunk's, that ends exactly at the stretch's end (behind the 0x00 end byte for a Block's last
+ * chunk, which no other stretch may include), whose coder consumes every compressed byte and ends with code == 0, and whose
+ * every byte and every match, taken from the staged stream, equals the staged bytes.  One launch takes launch_chunks chunks
+ * (0: 2048, the most allowed).  verdicts: nchunks entries (host).  Nothing is written to the caller's HBM.
+ * SNAPHASH_EINVAL: a null pointer, n_in == 0, a refused block size, nchunks other than ceil(n_in / 65536), launch_chunks >
+ * 2048.  Synchronous. */
+int snaphash_lzma2_check_device(snaphash_ctx *ctx, const void *d_in, size_t n_in, uint64_t block_size, const void *d_z, size_t n_z,
+                                const uint64_t *z_beg, const uint64_t *z_end, size_t nchunks, uint32_t launch_chunks,
+                                snaphash_lzma2_verdict *verdicts);
 void snaphash_get_targz_stats(const snaphash_ctx *ctx, snaphash_targz_stats *out);
 /* The compressor's Huffman code construction alone, by the routines the chunk kernel runs (a wave per table): for callers
  * who want to check them, as the tests do.  d_freq: n_tables tables of n_syms uint32 symbol counts each, resident in HBM.

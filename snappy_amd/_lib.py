@@ -60,8 +60,11 @@ EXPORTS = [
     "snaphash_bzip2_buffer", "snaphash_tar_create_bz2", "snaphash_bwt_device",
     # writing the .snap (ClickDeb.Build), and its self-check kernel alone
     "snaphash_snap_build", "snaphash_deflate_check_device",
+    # the .xz producer with options and its self-check, and that check's kernel alone
+    "snaphash_xz_buffer_ex", "snaphash_tar_create_xz_ex", "snaphash_get_xz_selfcheck_stats", "snaphash_lzma2_check_device",
 ]
 BUILD_NO_HASHES, BUILD_CHECK = 1, 2
+XZ_SELF_CHECK = 1
 JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
@@ -131,6 +134,15 @@ class XzCheckStats(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("device_crc32", ctypes.c_uint64),
                 ("device_crc64", ctypes.c_uint64), ("device_sha256", ctypes.c_uint64), ("host_checks", ctypes.c_uint64),
                 ("device_check_ms", ctypes.c_double)]
+
+
+class XzOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("block_size", ctypes.c_uint64),
+                ("check", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class XzSelfCheckStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("chunks", ctypes.c_uint64), ("ms", ctypes.c_double)]
 
 
 class UnpackStats(ctypes.Structure):
@@ -288,6 +300,11 @@ def lib():
     L.snaphash_snap_build.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(SnapBuildOptions), ctypes.c_char_p, ctypes.c_char_p,
                                       ctypes.POINTER(SnapBuildStats)]
     L.snaphash_deflate_check_device.argtypes = [vp, vp, sz, vp, u64p, sz, ctypes.c_int, vp]
+    L.snaphash_xz_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(XzOptions), ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_create_xz_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(XzOptions), ctypes.POINTER(vp),
+                                            ctypes.POINTER(sz), ctypes.c_char_p]
+    L.snaphash_get_xz_selfcheck_stats.argtypes = [vp, ctypes.POINTER(XzSelfCheckStats)]
+    L.snaphash_lzma2_check_device.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, sz, u64p, u64p, sz, ctypes.c_uint32, vp]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -463,13 +480,18 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def xz_buffer(self, data, block_size=0, check=None):
+    def xz_buffer(self, data, block_size=0, check=None, self_check=False):
         """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU.  check: the Blocks'
         Check id -- 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256, each taken in HBM; None: CRC-64 through the entry point that
-        takes no Check."""
+        takes no Check.  self_check: every LZMA2 chunk is walked against the bytes it was made from before it leaves HBM
+        (snaphash_xz_buffer_ex with SNAPHASH_XZ_SELF_CHECK; xz_selfcheck_stats() tells what was walked); the bytes are
+        the same."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        if check is None:
+        if self_check:
+            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK, block_size, 4 if check is None else check, 0)
+            self._check(lib().snaphash_xz_buffer_ex(self._h, ctypes.addressof(buf), len(data), ctypes.byref(opt), ctypes.byref(p), ctypes.byref(n)))
+        elif check is None:
             self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
         else:
             self._check(lib().snaphash_xz_buffer_check(self._h, ctypes.addressof(buf), len(data), block_size, check, ctypes.byref(p),
@@ -501,18 +523,24 @@ class Context:
         last column at the range's offset, d_orig_ptr a uint32 per range."""
         self._check(lib().snaphash_bwt_device(self._h, d_in, offsets.ctypes.data, lens.ctypes.data, len(offsets), d_last, d_orig_ptr))
 
-    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
-        """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.
+    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False):
+        """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.  With the defaults:
+        snaphash_tar_create_xz (1 MiB Blocks, CRC-64).  Anything else goes through snaphash_tar_create_xz_ex: block_size
+        and check as in xz_buffer, self_check as there.
         -> (yaml bytes or None, archive digest (64 bytes))."""
-        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
+        if block_size == 0 and check == 4 and not self_check:
+            return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
+        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, 0)
+        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz_ex", _opt=opt)
 
-    def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create"):
+    def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create", _opt=None):
         """tarCreate (clickdeb/deb.go:261-344).  with_hashes: also hashes.yaml from the same read.
         -> (yaml bytes or None, archive digest (64 bytes))."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         dig = ctypes.create_string_buffer(64)
+        extra = () if _opt is None else (ctypes.byref(_opt),)  # (the _ex entry's options)
         self._check(getattr(lib(), _entry)(self._h, os.fsencode(tarname), os.fsencode(source_dir),
-                                              os.fsencode(exclude_prefix) if exclude_prefix else None,
+                                              os.fsencode(exclude_prefix) if exclude_prefix else None, *extra,
                                               ctypes.byref(p) if with_hashes else None, ctypes.byref(n), dig))
         try:
             return (ctypes.string_at(p.value, n.value) if with_hashes else None), dig.raw
@@ -691,6 +719,27 @@ class Context:
         self._check(lib().snaphash_deflate_check_device(self._h, d_in, n_in, d_z, off, nch, 1 if last_is_final else 0,
                                                         ctypes.cast(v, ctypes.c_void_p)))
         return [(v[2 * c], v[2 * c + 1]) for c in range(nch)]
+
+    def lzma2_check_device(self, d_in, n_in, block_size, d_z, n_z, z_beg, z_end, launch_chunks=0):
+        """lzma2_check_kernel alone: d_in / d_z device addresses (ints) of the staged stream (n_in bytes, Blocks of
+        block_size) and the compressed bytes (n_z); chunk c's stretch is [z_beg[c], z_end[c]).  -> [(status, offset)] a
+        chunk.  Synchronous."""
+        nch = len(z_beg)
+        assert len(z_end) == nch
+        beg = (ctypes.c_uint64 * max(nch, 1))(*z_beg)
+        end = (ctypes.c_uint64 * max(nch, 1))(*z_end)
+        v = (ctypes.c_uint32 * (2 * max(nch, 1)))()
+        self._check(lib().snaphash_lzma2_check_device(self._h, d_in, n_in, block_size, d_z, n_z, beg, end, nch, launch_chunks,
+                                                      ctypes.cast(v, ctypes.c_void_p)))
+        return [(v[2 * c], v[2 * c + 1]) for c in range(nch)]
+
+    def xz_selfcheck_stats(self):
+        """The self-check of the last xz_buffer / tar_create_xz that went through an _ex entry: chunks walked, the check
+        kernel's milliseconds."""
+        s = XzSelfCheckStats()
+        s.struct_size = ctypes.sizeof(XzSelfCheckStats)
+        self._check(lib().snaphash_get_xz_selfcheck_stats(self._h, ctypes.byref(s)))
+        return {"chunks": s.chunks, "ms": s.ms}
 
     def snap_open(self, snap_path):
         """A session on a .snap file (ClickDeb.Open): see Snap."""

@@ -7,15 +7,17 @@
  *                                      Build's data step fused (clickdeb/deb.go:261-344 + snappy/build.go:517-520):
  *                                      data.tar.gz of BUILD_DIR without DEBIAN/, every file read once, then
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
- *   snaphash [options] build-xz BUILD_DIR OUT.tar.xz
- *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB, LZMA2 on the GPU
+ *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] BUILD_DIR OUT.tar.xz
+ *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB (or -B), Check
+ *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU
  *   snaphash [options] build-bz2 BUILD_DIR OUT.tar.bz2
  *                                      the same with data.tar.bz2 (level 9): every bzip2 block coded on the GPU
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
  *   snaphash [options] bzip2 [-L LEVEL] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9)
- *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256]
+ *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
- *                                                Blocks' Check as named (default crc64), taken on the GPU
+ *                                                Blocks' Check as named (default crc64), taken on the GPU; -c: the LZMA2
+ *                                                self-check on the GPU (-s prints what it walked)
  *   snaphash [options] gunzip IN.gz OUT          the inverse: every member decoded (GPU inflate)
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
@@ -58,9 +60,10 @@ static int die(snaphash_ctx *c, int rc, const char *what)
 static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
-                    "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | build-xz DIR OUT.tar.xz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
+                    "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
+                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] DIR OUT.tar.xz |\n"
                     "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
-                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
                     "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
@@ -82,6 +85,21 @@ static void print_block_stats(snaphash_ctx *c, const char *what)
                         "%llu host stretches, scan %.2f ms\n",
                 what, (unsigned long long)b.bits_scanned, (unsigned long long)b.candidates, (unsigned long long)b.linked,
                 (unsigned long long)b.unreached, (unsigned long long)b.host_blocks, b.scan_ms);
+}
+
+/* -C's word -> the Check id, or -1 */
+static int xz_check_id(const char *w)
+{
+    return !strcmp(w, "none") ? 0 : !strcmp(w, "crc32") ? 1 : !strcmp(w, "crc64") ? 4 : !strcmp(w, "sha256") ? 10 : -1;
+}
+
+/* -s after an .xz producer call with -c: what the self-check walked */
+static void print_xz_selfcheck(snaphash_ctx *c, const char *what)
+{
+    snaphash_xz_selfcheck_stats s;
+    s.struct_size = sizeof s;
+    if (!snaphash_get_xz_selfcheck_stats(c, &s))
+        fprintf(stderr, "%s: self-check: %llu chunks, %.3f ms\n", what, (unsigned long long)s.chunks, s.ms);
 }
 
 static char *slurp(const char *path, size_t *len)
@@ -188,8 +206,29 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, "verify");
         else printf("OK\n");
         free(y);
-    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz") || !strcmp(argv[1], "build-bz2")) && argc == 4) {
+    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-bz2")) && argc != 4) {
+        ret = usage();
+    } else if (!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz") || !strcmp(argv[1], "build-bz2")) {
         const int xz = !strcmp(argv[1], "build-xz"), bz2 = !strcmp(argv[1], "build-bz2");
+        /* build-xz's own options, in front of its two names: any of them goes through snaphash_tar_create_xz_ex */
+        snaphash_xz_options xo;
+        memset(&xo, 0, sizeof xo);
+        xo.struct_size = sizeof xo;
+        xo.check = 4;
+        int xz_ex = 0, bad = 0;
+        const char *cmd = argv[1];
+        while (xz && argc > 4 && !bad) {
+            int id = -1;
+            if (!strcmp(argv[2], "-c")) { xo.flags |= SNAPHASH_XZ_SELF_CHECK; argv++; argc--; }
+            else if (!strcmp(argv[2], "-B") && argc > 5) {
+                xo.block_size = (uint64_t)strtoull(argv[3], NULL, 10) * 1024u;
+                if (xo.block_size == 0) bad = 1;
+                argv += 2; argc -= 2;
+            } else if (!strcmp(argv[2], "-C") && argc > 5 && (id = xz_check_id(argv[3])) >= 0) { xo.check = (uint32_t)id; argv += 2; argc -= 2; }
+            else bad = 1;
+            xz_ex = 1;
+        }
+        if (bad || argc != 4) { snaphash_destroy(c); return usage(); }
         /* the exclude rule is writeHashes' own: every path that starts with <dir>/DEBIAN (build.go:229) */
         size_t dl = strlen(argv[2]);
         while (dl > 1 && argv[2][dl - 1] == '/') dl--;
@@ -201,11 +240,13 @@ int main(int argc, char **argv)
         char *y = NULL;
         size_t len = 0;
         uint8_t dig[64];
-        rc = xz    ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig)
+        rc = xz_ex ? snaphash_tar_create_xz_ex(c, argv[3], dir, excl, &xo, &y, &len, dig)
+             : xz  ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig)
              : bz2 ? snaphash_tar_create_bz2(c, argv[3], dir, excl, &y, &len, dig)
                    : snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
-        if (rc) ret = die(c, rc, argv[1]);
+        if (rc) ret = die(c, rc, cmd);
         else {
+            if (show_stats && (xo.flags & SNAPHASH_XZ_SELF_CHECK)) print_xz_selfcheck(c, cmd);
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
             FILE *f = fopen(ypath, "wb");
             if (!f || fwrite(y, 1, len, f) != len || fclose(f)) { perror(ypath); ret = 2; }
@@ -244,28 +285,36 @@ int main(int argc, char **argv)
         }
         snaphash_free(z);
         free(in);
-    } else if (!strcmp(argv[1], "xz") && argc >= 4 && argc % 2 == 0) {
+    } else if (!strcmp(argv[1], "xz") && argc >= 4) {
         size_t len = 0, zl = 0;
         uint64_t block = 0;
-        int have_block = 0, check = -1; /* -1: no -C, the entry point that takes no Check */
-        for (int i = 4; i < argc; i += 2) {
+        int have_block = 0, check = -1, self = 0; /* -1: no -C, the entry point that takes no Check */
+        for (int i = 4; i < argc;) {
+            if (!strcmp(argv[i], "-c")) { self = 1; i += 1; continue; }
+            if (i + 1 >= argc) { snaphash_destroy(c); return usage(); }
             if (!strcmp(argv[i], "-B")) {
                 block = (uint64_t)strtoull(argv[i + 1], NULL, 10) * 1024u;
                 have_block = 1;
-            } else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "none")) check = 0;
-            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "crc32")) check = 1;
-            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "crc64")) check = 4;
-            else if (!strcmp(argv[i], "-C") && !strcmp(argv[i + 1], "sha256")) check = 10;
+            } else if (!strcmp(argv[i], "-C") && xz_check_id(argv[i + 1]) >= 0) check = xz_check_id(argv[i + 1]);
             else { snaphash_destroy(c); return usage(); }
+            i += 2;
         }
+        snaphash_xz_options xo;
+        memset(&xo, 0, sizeof xo);
+        xo.struct_size = sizeof xo;
+        xo.flags = SNAPHASH_XZ_SELF_CHECK;
+        xo.block_size = block;
+        xo.check = check < 0 ? 4u : (uint32_t)check;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *z = NULL;
         rc = (have_block && block == 0) ? SNAPHASH_EINVAL
+             : self                     ? snaphash_xz_buffer_ex(c, in, len, &xo, &z, &zl)
              : check < 0                ? snaphash_xz_buffer(c, in, len, block, &z, &zl)
                                         : snaphash_xz_buffer_check(c, in, len, block, (uint32_t)check, &z, &zl);
         if (rc) ret = die(c, rc, "xz");
         else {
+            if (show_stats && self) print_xz_selfcheck(c, "xz");
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[3]); ret = 2; }
         }

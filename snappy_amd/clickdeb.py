@@ -12,13 +12,16 @@ helpers.py and hashes.py: the product is the C ABI.
 from .helpers import default_context
 
 
-def tarCreate(tarname, sourceDir, fn=None, ctx=None):
-    """-> the 64-byte SHA-512 of the archive written (the Go function returns only the error)."""
+def tarCreate(tarname, sourceDir, fn=None, ctx=None, self_check=False):
+    """-> the 64-byte SHA-512 of the archive written (the Go function returns only the error).  self_check (".xz" names
+    only): the producer walks every LZMA2 chunk against the bytes it was made from before it leaves the GPU."""
     c = ctx or default_context()
     if str(tarname).endswith(".xz"):
         if fn is not None:
             raise ValueError("tarCreate: the .xz producer takes no exclude function (snaphash_tar_create_xz)")
-        return c.tar_create_xz(tarname, sourceDir)[1]
+        return c.tar_create_xz(tarname, sourceDir, self_check=self_check)[1]
+    if self_check:
+        raise ValueError("tarCreate: self_check is the .xz producer's (ClickDeb.build(check=True) is the .gz producer's)")
     _, digest = c.tar_create_fn(tarname, sourceDir, fn)  # (any suffix but ".gz": SnaphashError, "unknown compression extension")
     return digest
 

@@ -15,6 +15,7 @@
 #include "devbuf.h"
 #include "inflate_core.h"
 #include "inflate_kernels.h"
+#include "lzma2_check_kernels.h"
 #include "sha256_kernels.h"
 #include "sha512_kernels.h"
 #include "xz_host.h"
@@ -284,6 +285,15 @@ struct XzEncBufs {
     Twin<uint32_t> res;
     Twin<uint64_t> dst;
     HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
+    Twin<uint64_t> zend;       // the self-check's: where every chunk's stretch ends, and the verdicts, a chunk each: sized by
+    Twin<Lzma2Verdict> chk;    // the call that asks for the check (xzpack.inc), empty otherwise
+    hipError_t ensure_check(uint64_t slot_bytes)
+    {
+        const size_t nch = std::max<size_t>((size_t)((slot_bytes + kXzEncChunk - 1) / kXzEncChunk), 1);
+        hipError_t e = zend.ensure(nch);
+        if (!e) e = chk.ensure(nch);
+        return e;
+    }
     // what a slot's output takes at most: every chunk stored (3 bytes of header), a Block a chunk (a header of 20 bytes
     // for sizes that take four bytes each, the end byte, 3 of padding and the longest Check, SHA-256's 32: 59 in all)
     static uint64_t out_cap(uint64_t slot_bytes) { return slot_bytes + ((slot_bytes + kXzEncChunk - 1) / kXzEncChunk) * 64 + 64; }
@@ -302,7 +312,7 @@ struct XzEncBufs {
         if (e) each(Release()); // (none of it is left behind)
         return e;
     }
-    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); }
+    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); zend.each(f); chk.each(f); }
 };
 
 // GPU bzip2 encoder (bzpack.inc), for `blocks` blocks a launch of up to `cap` bytes each after RLE1: the sort's scratch

@@ -16,14 +16,27 @@ namespace {
 
 static_assert(kXzEncBlockMax == kXzGpuBlockMax, "every Block this side writes is one the install side's kernel takes");
 
+// The .xz producer's self-check (DESIGN.md sec. 23), asked for by the _ex entries' SNAPHASH_XZ_SELF_CHECK alone: every slot's
+// LZMA2 chunks are walked against the staged stream by lzma2_check_kernel before they leave HBM (lzma2_check_core.h).
+struct XzSelfCheck {
+    const char* member = ""; // for last_error
+    uint64_t chunks = 0;     // chunks checked (all accepted, or the call failed)
+    double ms = 0;           // the check kernel's own time, HIP events
+    uint64_t bytes = 0;      // of the tar stream, in the slots checked so far
+};
+
 // The .xz encoder of one call: the Block size and the Blocks' Check it was asked for (the entries have validated them), and
 // the Index records of the Blocks written so far.
 struct XzEncoder final : Encoder {
     const uint64_t block_size;
     const uint32_t check;
     std::vector<XzEncRecord> recs;
-    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64)
-        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk) {}
+    XzSelfCheck* const self_check; // null = off, the producer's path without it
+    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr)
+        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc)
+    {
+        if (sc) check_ms = &sc->ms;
+    }
     uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const override // the producer's slot size, cut down to whole Blocks
     {
         const uint64_t s = producer_slot_bytes(c, job_bytes);
@@ -34,6 +47,7 @@ struct XzEncoder final : Encoder {
         const int rc = ensure_producer_streams(c);
         if (rc) return rc;
         HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
+        if (self_check) HIP_TRY(c, c->xe.ensure_check(slot_bytes));
         return SNAPHASH_OK;
     }
     void begin(OutPipe& g) override
@@ -50,6 +64,52 @@ struct XzEncoder final : Encoder {
         return pipe_finish(g, tail.data(), tail.size(), archive_digest);
     }
 };
+
+// The self-check of a slot, behind lzma2_concat_kernel on the compressor's stream: the chunks' stretches of b.d_out[0 .. total)
+// against the slot's staged bytes.  A stretch begins where the host placed the chunk (b.dst) and ends where the host's
+// Block layouts say -- the next chunk's place, or the end of the Block's LZMA2 data -- not where the chunk's own header says.
+// at[k]: where Block k begins in b.d_out.  Waits for the verdicts; a refused chunk fails the call.
+int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, const std::vector<XzEncBlockLayout>& lay, const std::vector<uint64_t>& at,
+                       uint64_t total)
+{
+    DevCtx* c = g.c;
+    XzEncBufs& b = c->xe;
+    hipStream_t zs = c->z_stream;
+    XzSelfCheck& sc = *z.self_check;
+    const uint64_t bs = z.block_size;
+    const uint32_t nch = (uint32_t)((n + kXzEncChunk - 1) / kXzEncChunk), cpb = (uint32_t)(bs / kXzEncChunk);
+    if (b.zend.size() < nch || b.chk.size() < nch) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
+    for (uint32_t k = 0; k < lay.size(); ++k) {
+        const uint64_t blen = std::min<uint64_t>(bs, n - (uint64_t)k * bs);
+        const uint32_t ch0 = k * cpb, cn = (uint32_t)((blen + kXzEncChunk - 1) / kXzEncChunk);
+        for (uint32_t i = 0; i < cn; ++i) b.zend.h[ch0 + i] = lzma2_check_stretch_end(b.dst.h.data() + ch0, i, cn, at[k] + lay[k].hdr + lay[k].data);
+    }
+    HIP_TRY(c, hipMemcpyAsync(b.zend.d.data(), b.zend.h.data(), (size_t)nch * 8, hipMemcpyHostToDevice, zs));
+    HIP_TRY(c, hipMemsetAsync(b.chk.d.data(), 0xff, (size_t)nch * sizeof(Lzma2Verdict), zs)); // (a verdict that is not written is a refusal)
+    for (uint32_t c0 = 0; c0 < nch; c0 += kLzCheckLaunchChunks) {
+        EventPair* e = next_events(c, 3);
+        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        const EventPair ev = *e;
+        HIP_TRY(c, hipEventRecord(ev.a, zs));
+        HIP_TRY(c, launch_lzma2_check(sl.d_buf.data(), n, bs, b.d_out.data(), total, b.dst.d.data(), b.zend.d.data(), c0,
+                                      std::min(kLzCheckLaunchChunks, nch - c0), nch, b.chk.d.data(), zs));
+        HIP_TRY(c, hipEventRecord(ev.b, zs));
+    }
+    HIP_TRY(c, hipMemcpyAsync(b.chk.h.data(), b.chk.d.data(), (size_t)nch * sizeof(Lzma2Verdict), hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    for (uint32_t i = 0; i < nch; ++i) {
+        const Lzma2Verdict v = b.chk.h[i];
+        if (v.status == kLzCheckOk) continue;
+        // (the Block and the chunk count through the whole stream: xz_process_slot calls this BEFORE it adds the slot's
+        // Blocks to z.recs and its chunks to g.st.chunks, and sc.bytes grows below; moved behind either, the text would
+        // name the wrong Block or chunk)
+        return fail(c, SNAPHASH_EDEVICE, lzma2_check_error_text(sc.member, z.recs.size() + i / cpb, g.st.chunks + i, v.status,
+                                                               sc.bytes + (uint64_t)i * kXzEncChunk + v.offset));
+    }
+    sc.chunks += nch;
+    sc.bytes += n;
+    return SNAPHASH_OK;
+}
 
 // The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream)
 // as whole Blocks into c->xe.h_out[zbuf] and on to the consumers.
@@ -137,6 +197,7 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
         HIP_TRY(c, hipStreamSynchronize(zs));
     }
     if (rc) return rc;
+    if (z.self_check && (rc = xz_self_check_slot(g, z, sl, n, lay, at, total)) != SNAPHASH_OK) return rc;
     if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
         float chains = 0, concat = 0, sum = 0, longest = 0;
         (void)hipEventElapsedTime(&chains, ev.a, ev.b);
@@ -223,9 +284,125 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+// What the _ex entries were asked for.  opt == nullptr, or an all-zero struct: what the plain entries write (1 MiB, CRC-64, no
+// self-check); otherwise the struct says its size and every field means what it says (check 0 is "none").
+int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check)
+{
+    *block_size = kXzEncBlockDefault;
+    *check = kXzCheckCrc64;
+    *self_check = false;
+    if (opt && opt->struct_size == 0) {
+        if (opt->flags || opt->block_size || opt->check || opt->reserved) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+        return SNAPHASH_OK;
+    }
+    if (!opt) return SNAPHASH_OK;
+    if (opt->struct_size < sizeof(snaphash_xz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+    if (opt->flags & ~(uint32_t)SNAPHASH_XZ_SELF_CHECK) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
+    if (opt->reserved) return fail(x, SNAPHASH_EINVAL, "xz: snaphash_xz_options.reserved is not zero");
+    if (!xzenc_check_valid(opt->check)) return fail(x, SNAPHASH_EINVAL, "xz: the Check is 0 (none), 1 (CRC-32), 4 (CRC-64) or 10 (SHA-256)");
+    *block_size = opt->block_size;
+    if (!xzenc_block_size(block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
+    *check = opt->check;
+    *self_check = (opt->flags & SNAPHASH_XZ_SELF_CHECK) != 0;
+    return SNAPHASH_OK;
+}
+
+// what snaphash_get_xz_selfcheck_stats hands out: of this _ex call
+void xz_keep_selfcheck_stats(snaphash_ctx* x, const XzSelfCheck& sc)
+{
+    x->xz_selfcheck = snaphash_xz_selfcheck_stats{};
+    x->xz_selfcheck.struct_size = sizeof(snaphash_xz_selfcheck_stats);
+    x->xz_selfcheck.chunks = sc.chunks;
+    x->xz_selfcheck.ms = sc.ms;
+}
+
 } // namespace
 
 extern "C" {
+
+int snaphash_xz_buffer_ex(snaphash_ctx* x, const void* data, size_t n, const snaphash_xz_options* opt, void** xz_out, size_t* xz_len)
+try {
+    if (!x || (!data && n) || !xz_out || !xz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *xz_out = nullptr;
+    *xz_len = 0;
+    uint64_t bs;
+    uint32_t check;
+    bool self;
+    int rc = xz_read_options(x, opt, &bs, &check, &self);
+    if (rc) return rc;
+    XzSelfCheck sc;
+    sc.member = "the buffer";
+    XzEncoder enc(bs, check, self ? &sc : nullptr);
+    rc = encode_to_malloc(x, enc, data, n, xz_out, xz_len);
+    xz_keep_selfcheck_stats(x, sc);
+    return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_create_xz_ex(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
+                              const snaphash_xz_options* opt, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
+try {
+    if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    uint64_t bs;
+    uint32_t check;
+    bool self;
+    int rc = xz_read_options(x, opt, &bs, &check, &self);
+    if (rc) return rc;
+    XzSelfCheck sc;
+    const char* base = strrchr(tarname, '/');
+    sc.member = base ? base + 1 : tarname;
+    XzEncoder enc(bs, check, self ? &sc : nullptr);
+    rc = tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    xz_keep_selfcheck_stats(x, sc);
+    return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_get_xz_selfcheck_stats(const snaphash_ctx* x, snaphash_xz_selfcheck_stats* out)
+{
+    if (!x || !out || out->struct_size < sizeof(snaphash_xz_selfcheck_stats)) return SNAPHASH_EINVAL;
+    *out = x->xz_selfcheck;
+    out->struct_size = sizeof(snaphash_xz_selfcheck_stats);
+    return SNAPHASH_OK;
+}
+
+int snaphash_lzma2_check_device(snaphash_ctx* x, const void* d_in, size_t n_in, uint64_t block_size, const void* d_z, size_t n_z,
+                                const uint64_t* z_beg, const uint64_t* z_end, size_t nchunks, uint32_t launch_chunks,
+                                snaphash_lzma2_verdict* verdicts)
+try {
+    static_assert(sizeof(snaphash_lzma2_verdict) == sizeof(Lzma2Verdict), "the verdicts travel as they are");
+    static_assert(kLzCheckLaunchChunks == kXzEncLaunchChunks && kLzCheckChunk == kXzEncChunk && kLzCheckProbs == kXzEncProbs &&
+                      kLzCheckProps == kXzEncProps,
+                  "the check walks what the producer writes");
+    if (!x || !d_in || !z_beg || !z_end || !verdicts || n_in == 0 || (n_z && !d_z)) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
+    if (nchunks != (n_in + kLzCheckChunk - 1) / kLzCheckChunk || nchunks > 0x7fffffffu) return fail(x, SNAPHASH_EINVAL, "xz: nchunks is not ceil(n_in / 65536)");
+    if (launch_chunks > kLzCheckLaunchChunks) return fail(x, SNAPHASH_EINVAL, "xz: a launch holds at most 2048 chunks");
+    if (launch_chunks == 0) launch_chunks = kLzCheckLaunchChunks;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<uint64_t> d_tab; // z_beg, then z_end
+    DevBuf<Lzma2Verdict> d_v;
+    HIP_TRY(c, d_tab.reserve(2 * nchunks));
+    HIP_TRY(c, d_v.reserve(nchunks));
+    HIP_TRY(c, hipMemcpyAsync(d_tab.data(), z_beg, nchunks * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_tab.data() + nchunks, z_end, nchunks * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_v.data(), 0xff, nchunks * sizeof(Lzma2Verdict), c->stream));
+    uint64_t launches = 0;
+    for (size_t c0 = 0; c0 < nchunks; c0 += launch_chunks, ++launches)
+        HIP_TRY(c, launch_lzma2_check((const uint8_t*)d_in, n_in, block_size, (const uint8_t*)d_z, n_z, d_tab.data(), d_tab.data() + nchunks, (uint32_t)c0,
+                                      (uint32_t)std::min<size_t>(launch_chunks, nchunks - c0), (uint32_t)nchunks, d_v.data(), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(verdicts, d_v.data(), nchunks * sizeof(Lzma2Verdict), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    x->stats.launches = launches;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
 
 int snaphash_xz_buffer(snaphash_ctx* x, const void* data, size_t n, uint64_t block_size, void** xz_out, size_t* xz_len)
 {

@@ -12,7 +12,20 @@ GPU) on tools/deflate_corpora.py's text, sources and binaries, 64 MiB each (--qu
             Python's lzma otherwise, one core)
   install   snaphash_unxz_buffer (default configuration) of our own output against the same bytes as `xz -6`'s one Block
   build     `snaphash build-xz` of the 297-file package of tools/unxz_bench.py beside `snaphash build`
-usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--out FILE]   (JSON lines on stdout and in FILE)"""
+  --self-check   instead of the legs above: what SNAPHASH_XZ_SELF_CHECK costs.  On each corpus, after one
+            warm call, snaphash_xz_buffer and snaphash_xz_buffer_ex with the flag, alternating, five of each: best / median /
+            worst of the call, and the check kernel's own time from HIP events (snaphash_get_xz_selfcheck_stats); the bytes
+            must be the same.  Then `snaphash -s build-xz` and `snaphash -s build-xz -c` of the 297-file package
+            (tools/snap_build_bench.py's), alternating in the same way.
+  --no-flag-ab LABEL   instead of the legs above: one run of an A/B of snaphash_xz_buffer WITHOUT the flag between two
+            checkouts.  `--tree DIR` names the checkout whose snappy_amd (and libsnaphash.so) is loaded, `--corpora-root DIR`
+            the checkout whose files make the corpora: tools/deflate_corpora.py builds "sources" from a tree's own files and
+            "binaries" from its own libsnaphash.so, so two checkouts compress different bytes unless both runs name the same
+            DIR.  On each corpus (8 MiB) one warm call, then five: best / median / worst, as "build": LABEL.  Alternate the
+            two checkouts, three runs each:  xz_bench.py --no-flag-ab parent_run1 --tree P --corpora-root P;
+            xz_bench.py --no-flag-ab branch_run1 --corpora-root P; ... (profiles/r16_xz_buffer_parent_ab.jsonl)
+usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--out FILE]
+       tools/xz_bench.py --no-flag-ab LABEL [--tree DIR] [--corpora-root DIR] [--out FILE]   (JSON lines on stdout and in FILE; --out appends here)"""
 import argparse
 import lzma
 import os
@@ -26,7 +39,9 @@ import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# --tree DIR: the checkout whose library is measured (read here, before the library is imported); this one otherwise
+TREE = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]) if "--tree" in sys.argv[1:-1] else ROOT
+sys.path.insert(0, TREE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context, _lib  # noqa: E402
@@ -124,18 +139,98 @@ def build_leg(total, reps, fh, tmp):
     emit(rec, fh)
 
 
+def three(ms):
+    """best / median / worst, in ms"""
+    s = sorted(ms)
+    return [round(s[0], 2), round(s[len(s) // 2], 2), round(s[-1], 2)]
+
+
+CHECK_LINE = re.compile(r"self-check: (\d+) chunks, ([\d.]+) ms")
+
+
+def self_check_legs(g, size, total, fh, tmp, reps=5):
+    for name, data in corpora(size).items():
+        g.xz_buffer(data)  # one warm call: the scratch
+        off, on, kernel, chunks = [], [], [], 0
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            z0 = g.xz_buffer(data)
+            off.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            z1 = g.xz_buffer(data, self_check=True)
+            on.append((time.perf_counter() - t0) * 1e3)
+            st = g.xz_selfcheck_stats()
+            assert z0 == z1 and st["chunks"] == g.targz_stats()["chunks"]
+            kernel.append(st["ms"])
+            chunks = st["chunks"]
+        emit({"leg": "self_check", "corpus": name, "bytes": len(data), "chunks": chunks, "reps": reps, "off_ms_best_median_worst": three(off),
+              "on_ms_best_median_worst": three(on), "check_kernel_ms_best_median_worst": three(kernel),
+              "kernels_ms_on": round(g.targz_stats()["deflate_ms"], 2)}, fh)
+    build = package(tmp, total, 297, 5)
+    arc = os.path.join(tmp, "data.tar.xz")
+    subprocess.run([CLI, "build-xz", build, arc], stdout=subprocess.DEVNULL, check=True)  # one warm call: the page cache
+    off, on, kernel, chunks, sizes = [], [], [], 0, set()
+    for _ in range(reps):
+        for flag, ts in (([], off), (["-c"], on)):
+            t0 = time.perf_counter()
+            p = subprocess.run([CLI, "-s", "build-xz"] + flag + [build, arc], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, check=True)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            sizes.add(os.path.getsize(arc))
+            if flag:
+                m = CHECK_LINE.search(p.stderr)
+                chunks = int(m.group(1))
+                kernel.append(float(m.group(2)))
+    assert len(sizes) == 1
+    emit({"leg": "self_check_build", "files": 297, "bytes": total, "chunks": chunks, "reps": reps, "off_ms_best_median_worst": three(off),
+          "on_ms_best_median_worst": three(on), "check_kernel_ms_best_median_worst": three(kernel), "xz_bytes": sizes.pop()}, fh)
+
+
+def corpora_of(root, size):
+    """unpack_bench.corpora with the corpus builders of the checkout at `root`, over that checkout's files."""
+    origin = os.path.join(os.path.abspath(root), "tools", "deflate_corpora.py")
+    src = open(origin).read().split("depths = ")[0]  # the corpus builders, not the script's own run
+    g = {"__name__": "deflate_corpora_src", "__file__": origin}
+    exec(compile(src, origin, "exec"), g)
+    g["SIZE"] = size
+    return {"text": g["text"](), "sources": g["fill"](g["sources"]()), "binaries": g["fill"](g["binaries"]())}
+
+
+def no_flag_ab(g, label, corpora_root, fh, reps=5):
+    for name, data in corpora_of(corpora_root, 8 << 20).items():
+        g.xz_buffer(data)  # one warm call: the scratch
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            g.xz_buffer(data)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        emit({"leg": "xz_buffer_without_the_flag", "build": label, "corpus": name, "bytes": len(data), "call_ms_best_median_worst": three(ms),
+              "kernels_ms": round(g.targz_stats()["deflate_ms"], 2)}, fh)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--legs", default="size,time,install,build")
     ap.add_argument("--out")
+    ap.add_argument("--self-check", action="store_true")
+    ap.add_argument("--no-flag-ab", metavar="LABEL")
+    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--corpora-root", default=ROOT)
     a = ap.parse_args()
-    fh = open(a.out, "w") if a.out else None
+    fh = open(a.out, "a" if a.no_flag_ab else "w") if a.out else None
     legs = a.legs.split(",")
     size = (8 << 20) if a.quick else (64 << 20)
     tmp = tempfile.mkdtemp(prefix="xzenc")
     try:
+        if a.no_flag_ab:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
+                no_flag_ab(g, a.no_flag_ab, a.corpora_root, fh)
+            return
+        if a.self_check:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
+                self_check_legs(g, 8 << 20, (32 << 20) if a.quick else (256 << 20), fh, tmp)
+            return
         with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, Context(device=0, flags=0) as d:
             if set(legs) & {"size", "time", "install"}:
                 corpus_legs(g, d, size, a.reps, legs, fh, tmp)
