@@ -485,6 +485,57 @@ int snaphash_tar_create_bz2(snaphash_ctx *ctx, const char *tarname, const char *
 int snaphash_bwt_device(snaphash_ctx *ctx, const void *d_in, const uint64_t *offsets, const uint64_t *lens, size_t n_blocks,
                         void *d_last, void *d_orig_ptr);
 
+/* The two producers above with the caller's level, and with the producer's self-check. */
+enum { SNAPHASH_BZ2_SELF_CHECK = 1 }; /* every block is decoded again in HBM -- symbols, inverse BWT, RLE1 -- and compared with
+                                       * the staged piece it was made from before it leaves the GPU: a block that would not
+                                       * decode back fails the call (SNAPHASH_EDEVICE; snaphash_last_error names the member,
+                                       * the block, the status -- snaphash_bz2_verdict's -- and the offset in the uncompressed
+                                       * stream; a file being written is unlinked).  The bytes written are the same with and
+                                       * without it.  Not covered: "BZh" + level, the end-of-stream magic and the combined CRC
+                                       * (written on the host), the copy back and the write; decoding the file covers those.
+                                       * Adds the install side's decode scratch: 4.5 MB a block of a staging slot, 256 blocks
+                                       * at most. */
+typedef struct snaphash_bz2_options {
+    uint32_t struct_size; /* sizeof(snaphash_bz2_options) */
+    uint32_t flags;       /* SNAPHASH_BZ2_*; an unknown bit is SNAPHASH_EINVAL */
+    uint32_t level;       /* as in snaphash_bzip2_buffer: 1..9, 0 = 9 */
+} snaphash_bz2_options;
+typedef struct snaphash_bz2_selfcheck_stats {
+    uint32_t struct_size; /* set by the caller */
+    uint32_t reserved;
+    uint64_t blocks;      /* blocks decoded again (all accepted, or the call failed); 0 without SNAPHASH_BZ2_SELF_CHECK */
+    double ms;            /* the check's kernels' own time, HIP events */
+} snaphash_bz2_selfcheck_stats;
+/* opt == NULL, or a struct that is all zero (struct_size included): byte for byte what snaphash_bzip2_buffer(level 9) /
+ * snaphash_tar_create_bz2 write.  Otherwise struct_size says the struct's size and every field means what it says.
+ * SNAPHASH_EINVAL, and the ctx stays usable: an unknown flag, another struct_size, a level above 9.
+ * snaphash_tar_create_bz2_ex is the tar entry that gives .bz2 a level. */
+int snaphash_bzip2_buffer_ex(snaphash_ctx *ctx, const void *data, size_t n, const snaphash_bz2_options *opt, void **bz_out,
+                             size_t *bz_len);
+int snaphash_tar_create_bz2_ex(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
+                               const snaphash_bz2_options *opt, char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
+/* of the most recent of the two _ex calls above */
+int snaphash_get_bz2_selfcheck_stats(const snaphash_ctx *ctx, snaphash_bz2_selfcheck_stats *out);
+
+typedef struct snaphash_bz2_verdict {
+    uint32_t status; /* in order of precedence: 0 accepted; 8 the table entry lies outside the compressed bytes, or z_end < z_beg,
+                        or the piece lies outside the staged buffer (nothing was read); 3 no valid block at z_beg (magic,
+                        randomised bit, maps, selectors, tables, truncated, empty); 4 more symbols than 100 000 x level; 7 origPtr
+                        >= n, or the inverse BWT's walk breaks; 5 the block does not end at z_end; 6 the stored block CRC is not
+                        the piece's; 1 a byte differs; 2 all of min(decoded, in_len) bytes agree and the lengths differ */
+    uint32_t offset; /* 0: in_len; 8, 6: 0; 3: the block reader's own status (2 truncated, 4 bad); 4: the cap; 7: origPtr; 5: the
+                        low 32 bits of the block's end bit - z_beg; 1: the first differing byte within the piece; 2: the minimum */
+} snaphash_bz2_verdict;
+/* The self-check's four steps alone, on tables the caller wrote (tests): d_z[0..n_z) holds compressed bytes in HBM, block k's
+ * bits being [z_beg[k], z_end[k]) (bit offsets, MSB first; host arrays); d_in[0..n_in) is the staged stream in HBM, block k's
+ * piece being d_in[in_off[k] .. in_off[k] + in_len[k]) and crc[k] the bzip2 CRC the caller holds for it; level: the stream's,
+ * 1..9.  Any valid bzip2 block is taken, not only this library's.  verdicts: n_blocks entries (host).  Nothing is written to
+ * the caller's HBM; nothing outside d_z[0..n_z) and the blocks' pieces is read.  SNAPHASH_EINVAL: a null pointer, a level
+ * outside 1..9.  Synchronous. */
+int snaphash_bz2_check_device(snaphash_ctx *ctx, const void *d_z, size_t n_z, const uint64_t *z_beg, const uint64_t *z_end,
+                              const void *d_in, size_t n_in, const uint64_t *in_off, const uint64_t *in_len, const uint32_t *crc,
+                              uint32_t level, size_t n_blocks, snaphash_bz2_verdict *verdicts);
+
 /* ---- the install side: data.tar.gz unpacked and verified in one read ---------------------- */
 
 typedef struct snaphash_unpack_stats { /* of the most recent snaphash_gunzip_buffer / snaphash_tar_unpack, or of the

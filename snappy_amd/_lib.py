@@ -62,9 +62,12 @@ EXPORTS = [
     "snaphash_snap_build", "snaphash_deflate_check_device",
     # the .xz producer with options and its self-check, and that check's kernel alone
     "snaphash_xz_buffer_ex", "snaphash_tar_create_xz_ex", "snaphash_get_xz_selfcheck_stats", "snaphash_lzma2_check_device",
+    # the .bz2 producer with options and its self-check, and that check's kernels alone
+    "snaphash_bzip2_buffer_ex", "snaphash_tar_create_bz2_ex", "snaphash_get_bz2_selfcheck_stats", "snaphash_bz2_check_device",
 ]
 BUILD_NO_HASHES, BUILD_CHECK = 1, 2
 XZ_SELF_CHECK = 1
+BZ2_SELF_CHECK = 1
 JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
 FLAG_CHECK_GATHER, FLAG_NO_RCCL, FLAG_FORCE_GATHER, FLAG_GPU_ONLY, FLAG_NO_NUMA, FLAG_KEEP_RLIMIT = 1, 2, 4, 8, 16, 32
@@ -143,6 +146,14 @@ class XzOptions(ctypes.Structure):
 
 class XzSelfCheckStats(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("chunks", ctypes.c_uint64), ("ms", ctypes.c_double)]
+
+
+class Bz2Options(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("level", ctypes.c_uint32)]
+
+
+class Bz2SelfCheckStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("blocks", ctypes.c_uint64), ("ms", ctypes.c_double)]
 
 
 class UnpackStats(ctypes.Structure):
@@ -305,6 +316,11 @@ def lib():
                                             ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_get_xz_selfcheck_stats.argtypes = [vp, ctypes.POINTER(XzSelfCheckStats)]
     L.snaphash_lzma2_check_device.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, sz, u64p, u64p, sz, ctypes.c_uint32, vp]
+    L.snaphash_bzip2_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(Bz2Options), ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_create_bz2_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bz2Options), ctypes.POINTER(vp),
+                                             ctypes.POINTER(sz), ctypes.c_char_p]
+    L.snaphash_get_bz2_selfcheck_stats.argtypes = [vp, ctypes.POINTER(Bz2SelfCheckStats)]
+    L.snaphash_bz2_check_device.argtypes = [vp, vp, sz, u64p, u64p, vp, sz, u64p, u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, sz, vp]
     L.snaphash_get_engine_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(EngineInfo)]
     L.snaphash_numa_probe.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), vp, sz, ctypes.POINTER(sz)]
     L.snaphash_shard_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vp)]
@@ -501,21 +517,54 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def bzip2_buffer(self, data, level=0):
+    def bzip2_buffer(self, data, level=0, self_check=False, _ex=False):
         """One bzip2 stream of `data` at `level` (1..9; 0: 9), every block coded on the GPU; a block per 719 872 bytes of
-        input at level 9 (79 872 at level 1).  The bytes are a function of (data, level) alone."""
+        input at level 9 (79 872 at level 1).  The bytes are a function of (data, level) alone.  self_check: every block is
+        decoded again in HBM and compared with the piece it was made from before it leaves the GPU
+        (snaphash_bzip2_buffer_ex with SNAPHASH_BZ2_SELF_CHECK; bz2_selfcheck_stats() tells what was checked); the bytes
+        are the same.  _ex: through the _ex entry also without the flag."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        self._check(lib().snaphash_bzip2_buffer(self._h, ctypes.addressof(buf), len(data), level, ctypes.byref(p), ctypes.byref(n)))
+        if self_check or _ex:
+            opt = Bz2Options(ctypes.sizeof(Bz2Options), BZ2_SELF_CHECK if self_check else 0, level)
+            self._check(lib().snaphash_bzip2_buffer_ex(self._h, ctypes.addressof(buf), len(data), ctypes.byref(opt), ctypes.byref(p), ctypes.byref(n)))
+        else:
+            self._check(lib().snaphash_bzip2_buffer(self._h, ctypes.addressof(buf), len(data), level, ctypes.byref(p), ctypes.byref(n)))
         try:
             return ctypes.string_at(p.value, n.value)
         finally:
             lib().snaphash_free(p)
 
-    def tar_create_bz2(self, tarname, source_dir, exclude_prefix=None, with_hashes=False):
-        """tar_create with the .bz2 producer (level 9): the format the install side reads and tarCreate refuses to write.
+    def tar_create_bz2(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, level=0, self_check=False):
+        """tar_create with the .bz2 producer: the format the install side reads and tarCreate refuses to write.  With the
+        defaults: snaphash_tar_create_bz2 (level 9).  Anything else goes through snaphash_tar_create_bz2_ex: level and
+        self_check as in bzip2_buffer.
         -> (yaml bytes or None, archive digest (64 bytes))."""
-        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_bz2")
+        if level == 0 and not self_check:
+            return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_bz2")
+        opt = Bz2Options(ctypes.sizeof(Bz2Options), BZ2_SELF_CHECK if self_check else 0, level)
+        return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_bz2_ex", _opt=opt)
+
+    def bz2_check_device(self, d_z, n_z, z_beg, z_end, d_in, n_in, in_off, in_len, crc, level):
+        """The .bz2 self-check's four steps alone: d_z / d_in device addresses (ints) of the compressed bytes (n_z) and the
+        staged stream (n_in); block k's bits are [z_beg[k], z_end[k]), its piece d_in[in_off[k] .. in_off[k] + in_len[k]), its
+        CRC crc[k]; level: the stream's.  -> [(status, offset)] a block.  Synchronous."""
+        nb = len(z_beg)
+        assert len(z_end) == nb and len(in_off) == nb and len(in_len) == nb and len(crc) == nb
+        arr = lambda t, v: (t * max(nb, 1))(*v)
+        v = (ctypes.c_uint32 * (2 * max(nb, 1)))()
+        self._check(lib().snaphash_bz2_check_device(self._h, d_z, n_z, arr(ctypes.c_uint64, z_beg), arr(ctypes.c_uint64, z_end), d_in, n_in,
+                                                    arr(ctypes.c_uint64, in_off), arr(ctypes.c_uint64, in_len), arr(ctypes.c_uint32, crc), level, nb,
+                                                    ctypes.cast(v, ctypes.c_void_p)))
+        return [(v[2 * k], v[2 * k + 1]) for k in range(nb)]
+
+    def bz2_selfcheck_stats(self):
+        """The self-check of the last bzip2_buffer / tar_create_bz2 that went through an _ex entry: blocks decoded again,
+        the check's kernels' milliseconds."""
+        s = Bz2SelfCheckStats()
+        s.struct_size = ctypes.sizeof(Bz2SelfCheckStats)
+        self._check(lib().snaphash_get_bz2_selfcheck_stats(self._h, ctypes.byref(s)))
+        return {"blocks": s.blocks, "ms": s.ms}
 
     def bwt_device(self, d_in, offsets, lens, d_last, d_orig_ptr):
         """The bzip2 encoder's BWT kernel alone over ranges resident in HBM.  d_in / d_last / d_orig_ptr: device addresses

@@ -10,10 +10,12 @@
  *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB (or -B), Check
  *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU
- *   snaphash [options] build-bz2 BUILD_DIR OUT.tar.bz2
- *                                      the same with data.tar.bz2 (level 9): every bzip2 block coded on the GPU
+ *   snaphash [options] build-bz2 [-c] [-L LEVEL] BUILD_DIR OUT.tar.bz2
+ *                                      the same with data.tar.bz2 (level 9, or -L): every bzip2 block coded on the GPU; -c: every
+ *                                      block decoded again and compared on the GPU (the .bz2 self-check)
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
- *   snaphash [options] bzip2 [-L LEVEL] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9)
+ *   snaphash [options] bzip2 [-L LEVEL] [-c] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9); -c: the .bz2
+ *                                                self-check on the GPU (-s prints what it checked)
  *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
  *                                                Blocks' Check as named (default crc64), taken on the GPU; -c: the LZMA2
@@ -63,6 +65,7 @@ static int usage(void)
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
                     "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] DIR OUT.tar.xz |\n"
                     "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
+                    "       (in front of their names build-bz2 also takes [-c] [-L LEVEL] and bzip2 [-c]: -c is the .bz2 self-check)\n"
                     "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
@@ -100,6 +103,21 @@ static void print_xz_selfcheck(snaphash_ctx *c, const char *what)
     s.struct_size = sizeof s;
     if (!snaphash_get_xz_selfcheck_stats(c, &s))
         fprintf(stderr, "%s: self-check: %llu chunks, %.3f ms\n", what, (unsigned long long)s.chunks, s.ms);
+}
+
+/* -s after a .bz2 producer call with -c: what the self-check decoded again */
+static void print_bz2_selfcheck(snaphash_ctx *c, const char *what)
+{
+    snaphash_bz2_selfcheck_stats s;
+    s.struct_size = sizeof s;
+    if (!snaphash_get_bz2_selfcheck_stats(c, &s))
+        fprintf(stderr, "%s: self-check: %llu blocks, %.3f ms\n", what, (unsigned long long)s.blocks, s.ms);
+}
+
+/* -L's word -> the level 1..9, or 0 */
+static unsigned bz2_level(const char *w)
+{
+    return (w[0] >= '1' && w[0] <= '9' && !w[1]) ? (unsigned)(w[0] - '0') : 0;
 }
 
 static char *slurp(const char *path, size_t *len)
@@ -206,7 +224,7 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, "verify");
         else printf("OK\n");
         free(y);
-    } else if ((!strcmp(argv[1], "build") || !strcmp(argv[1], "build-bz2")) && argc != 4) {
+    } else if (!strcmp(argv[1], "build") && argc != 4) {
         ret = usage();
     } else if (!strcmp(argv[1], "build") || !strcmp(argv[1], "build-xz") || !strcmp(argv[1], "build-bz2")) {
         const int xz = !strcmp(argv[1], "build-xz"), bz2 = !strcmp(argv[1], "build-bz2");
@@ -228,6 +246,17 @@ int main(int argc, char **argv)
             else bad = 1;
             xz_ex = 1;
         }
+        /* build-bz2's, the same way: any of them goes through snaphash_tar_create_bz2_ex */
+        snaphash_bz2_options bo;
+        memset(&bo, 0, sizeof bo);
+        bo.struct_size = sizeof bo;
+        int bz2_ex = 0;
+        while (bz2 && argc > 4 && !bad) {
+            if (!strcmp(argv[2], "-c")) { bo.flags |= SNAPHASH_BZ2_SELF_CHECK; argv++; argc--; }
+            else if (!strcmp(argv[2], "-L") && argc > 5 && (bo.level = bz2_level(argv[3])) != 0) { argv += 2; argc -= 2; }
+            else bad = 1;
+            bz2_ex = 1;
+        }
         if (bad || argc != 4) { snaphash_destroy(c); return usage(); }
         /* the exclude rule is writeHashes' own: every path that starts with <dir>/DEBIAN (build.go:229) */
         size_t dl = strlen(argv[2]);
@@ -242,11 +271,13 @@ int main(int argc, char **argv)
         uint8_t dig[64];
         rc = xz_ex ? snaphash_tar_create_xz_ex(c, argv[3], dir, excl, &xo, &y, &len, dig)
              : xz  ? snaphash_tar_create_xz(c, argv[3], dir, excl, &y, &len, dig)
+             : bz2_ex ? snaphash_tar_create_bz2_ex(c, argv[3], dir, excl, &bo, &y, &len, dig)
              : bz2 ? snaphash_tar_create_bz2(c, argv[3], dir, excl, &y, &len, dig)
                    : snaphash_tar_create(c, argv[3], dir, excl, &y, &len, dig);
         if (rc) ret = die(c, rc, cmd);
         else {
             if (show_stats && (xo.flags & SNAPHASH_XZ_SELF_CHECK)) print_xz_selfcheck(c, cmd);
+            if (show_stats && (bo.flags & SNAPHASH_BZ2_SELF_CHECK)) print_bz2_selfcheck(c, cmd);
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
             FILE *f = fopen(ypath, "wb");
             if (!f || fwrite(y, 1, len, f) != len || fclose(f)) { perror(ypath); ret = 2; }
@@ -268,18 +299,28 @@ int main(int argc, char **argv)
         }
         snaphash_free(z);
         free(in);
-    } else if (!strcmp(argv[1], "bzip2") && (argc == 4 || (argc == 6 && !strcmp(argv[2], "-L")))) {
+    } else if (!strcmp(argv[1], "bzip2") && argc >= 4) {
         size_t len = 0, zl = 0;
-        const int at = argc == 6 ? 4 : 2;
-        char *end = NULL;
-        const unsigned long level = argc == 6 ? strtoul(argv[3], &end, 10) : 9;
-        if (argc == 6 && (*end || !*argv[3] || level < 1 || level > 9)) { snaphash_destroy(c); return usage(); }
+        unsigned level = 9;
+        int self = 0, at = 2;
+        while (argc - at > 2) { /* the options, in front of the two names */
+            if (!strcmp(argv[at], "-c")) { self = 1; at += 1; }
+            else if (!strcmp(argv[at], "-L") && argc - at > 3 && (level = bz2_level(argv[at + 1])) != 0) at += 2;
+            else { snaphash_destroy(c); return usage(); }
+        }
+        if (argc - at != 2) { snaphash_destroy(c); return usage(); }
+        snaphash_bz2_options bo;
+        memset(&bo, 0, sizeof bo);
+        bo.struct_size = sizeof bo;
+        bo.flags = SNAPHASH_BZ2_SELF_CHECK;
+        bo.level = level;
         char *in = slurp(argv[at], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *z = NULL;
-        rc = snaphash_bzip2_buffer(c, in, len, (uint32_t)level, &z, &zl);
+        rc = self ? snaphash_bzip2_buffer_ex(c, in, len, &bo, &z, &zl) : snaphash_bzip2_buffer(c, in, len, (uint32_t)level, &z, &zl);
         if (rc) ret = die(c, rc, "bzip2");
         else {
+            if (show_stats && self) print_bz2_selfcheck(c, "bzip2");
             FILE *f = fopen(argv[at + 1], "wb");
             if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[at + 1]); ret = 2; }
         }

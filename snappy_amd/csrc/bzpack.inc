@@ -7,7 +7,9 @@
 // staging slot is a whole number of pieces, no more than one launch codes: the blocks' CRCs come from crc_kernels.hip over
 // the staged bytes, bzip2_enc_kernels.hip runs RLE1, the BWT, MTF and the Huffman coding of every block of the slot side by
 // side and shifts their bits together.  The host adds the four bytes in front and the footer, folds the combined CRC, and
-// holds the stream's last partial byte back until the next slot (or the footer) completes it.
+// holds the stream's last partial byte back until the next slot (or the footer) completes it.  Asked to
+// (SNAPHASH_BZ2_SELF_CHECK), it has every block of a slot decoded again in HBM by the install side's kernels and compared
+// with the staged piece before the bytes go on (bz2_check_core.h, bz2_check_kernels.hip; DESIGN.md sec. 24).
 
 namespace {
 
@@ -31,14 +33,79 @@ int ensure_bzenc(DevCtx* c, uint32_t blocks, uint32_t cap, bool with_output)
     return SNAPHASH_OK;
 }
 
+// The .bz2 producer's self-check (DESIGN.md sec. 24), asked for by the _ex entries' SNAPHASH_BZ2_SELF_CHECK alone: every slot's
+// blocks are decoded again in HBM and compared with the staged pieces before they leave it (bz2_check_core.h).
+struct BzSelfCheck {
+    const char* member = ""; // for last_error
+    uint64_t blocks = 0;     // blocks checked (all accepted, or the call failed)
+    double ms = 0;           // the check's kernels, HIP events
+    uint64_t bytes = 0;      // of the tar stream, in the slots checked so far
+};
+
+// The check's groups are the install side's batches (unbz2.inc's kBzLaunchSlots, which asserts the two agree): 256 slots of
+// Bzip2Bufs at most, 4.5 MB each.
+constexpr uint32_t kBz2CheckGroup = 256;
+
+// The four steps of the check over `count` blocks, enqueued on s and not waited for (but under stage_ms, which waits for every
+// group to time its steps): table entries d_jobs and verdicts d_verdicts in HBM, the compressed bytes d_z[0 .. n_z), the
+// staged stream d_in[0 .. n_in).  The scratch is the install side's, c->bz, through its own ensure, a group of at most
+// kBz2CheckGroup blocks at a time; c->inf.d_out is not touched.  stage_ms: symbols, link, inverse BWT + RLE1 count, compare.
+int bz2_check_run(DevCtx* c, const uint8_t* d_z, uint64_t n_z, const uint8_t* d_in, uint64_t n_in, const Bz2CheckJob* d_jobs, uint32_t count,
+                  uint32_t level, Bz2Verdict* d_verdicts, hipStream_t s, float* stage_ms)
+{
+    if (count == 0) return SNAPHASH_OK;
+    HIP_TRY(c, c->bz.ensure(0, std::min(count, kBz2CheckGroup), c->numa_node));
+    Bzip2Bufs& z = c->bz;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    if (stage_ms)
+        for (hipEvent_t& e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (uint32_t g0 = 0; g0 < count; g0 += kBz2CheckGroup) {
+        const uint32_t nb = std::min(kBz2CheckGroup, count - g0);
+        if (nb > z.nslots()) return fail(c, SNAPHASH_EDEVICE, "bzip2: the self-check's scratch is smaller than its group");
+        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[0], s));
+        HIP_TRY(c, launch_bz2_check_symbols(d_z, n_z, n_in, d_jobs + g0, level, nb, z.d_slots.data(), z.d_res.data(), s));
+        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[1], s));
+        HIP_TRY(c, launch_bz2_check_link(z.d_res.data(), d_jobs + g0, n_z, n_in, level, nb, z.d_blk.data(), d_verdicts + g0, s));
+        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[2], s));
+        HIP_TRY(c, launch_bz_ibwt(z.d_slots.data(), z.d_tt.data(), z.d_blk.data(), nb, s));
+        HIP_TRY(c, launch_bz_rle1_count(z.d_slots.data(), z.d_blk.data(), z.d_chunks.data(), nb, s));
+        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[3], s));
+        HIP_TRY(c, launch_bz2_check_compare(z.d_slots.data(), z.d_blk.data(), z.d_chunks.data(), d_in, d_jobs + g0, nb, d_verdicts + g0, s));
+        if (stage_ms) {
+            HIP_TRY(c, hipEventRecord(ev[4], s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            for (int i = 0; i < 4; ++i) {
+                float ms = 0;
+                (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+                stage_ms[i] += ms;
+            }
+        }
+    }
+    return SNAPHASH_OK;
+}
+
 // The .bz2 encoder of one call: the level it was asked for (1 to 9), the combined CRC so far, and the stream's last, partial
 // byte -- held back until the next slot's blocks (or the footer) complete it.
 struct BzEncoder final : Encoder {
     const uint32_t level;
     uint32_t crc = 0, carry = 0, carry_bits = 0;
-    explicit BzEncoder(uint32_t lvl = 9) : Encoder(".bz2", "bzip2: a block's input is larger than the engine's staging size"), level(lvl) {}
+    BzSelfCheck* const self_check; // null = off, the producer's path without it
+    explicit BzEncoder(uint32_t lvl = 9, BzSelfCheck* sc = nullptr)
+        : Encoder(".bz2", "bzip2: a block's input is larger than the engine's staging size"), level(lvl), self_check(sc)
+    {
+        if (sc) check_ms = &sc->ms;
+    }
     uint64_t slot_bytes(const DevCtx* c, uint64_t job_bytes) const override { return bz_slot_bytes(c, job_bytes, level); }
-    int ensure(DevCtx* c, uint64_t slot_bytes) override { return ensure_bzenc(c, (uint32_t)(slot_bytes / bzenc_piece(level)), bzenc_rle_cap(level), true); }
+    int ensure(DevCtx* c, uint64_t slot_bytes) override
+    {
+        const uint32_t blocks = (uint32_t)(slot_bytes / bzenc_piece(level));
+        const int rc = ensure_bzenc(c, blocks, bzenc_rle_cap(level), true);
+        if (rc || !self_check) return rc;
+        HIP_TRY(c, c->be.ensure_check(c->be.made_blocks));
+        HIP_TRY(c, c->bz.ensure(0, std::min(blocks, kBz2CheckGroup), c->numa_node));
+        return SNAPHASH_OK;
+    }
     void begin(OutPipe& g) override
     {
         const uint8_t h[kBzEncStreamHead] = {'B', 'Z', 'h', (uint8_t)('0' + level)};
@@ -58,6 +125,49 @@ struct BzEncoder final : Encoder {
         return pipe_finish(g, (const uint8_t*)tail, (size_t)bytes, archive_digest);
     }
 };
+
+// The self-check of a slot, behind bz_enc_concat_kernel on the compressor's stream: the nblk blocks' bit stretches of
+// b.d_out[0 .. out_words) against their pieces of the slot's staged bytes.  A stretch begins where the host placed the block
+// (b.dst; the first one at carry_bits: the held-back byte is in the buffer) and ends where the next one begins, or at the
+// slot's `at` -- not where the block's own end-of-block symbol says; pieces and CRCs are the host's own.  Waits for the
+// verdicts; a refused block fails the call.
+int bz_self_check_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, uint32_t nblk, uint64_t at, uint64_t out_words,
+                       const std::vector<uint64_t>& offs, const std::vector<uint64_t>& lens, const std::vector<uint32_t>& crcs, bool trace)
+{
+    DevCtx* c = g.c;
+    BzEncBufs& b = c->be;
+    hipStream_t zs = c->z_stream;
+    BzSelfCheck& sc = *z.self_check;
+    if (b.ckjobs.size() < nblk || b.chk.size() < nblk) return fail(c, SNAPHASH_EDEVICE, "bzip2: the self-check's tables are smaller than the slot");
+    for (uint32_t k = 0; k < nblk; ++k) b.ckjobs.h[k] = Bz2CheckJob{b.dst.h[k], k + 1 < nblk ? b.dst.h[k + 1] : at, offs[k], lens[k], crcs[k], 0};
+    HIP_TRY(c, hipMemcpyAsync(b.ckjobs.d.data(), b.ckjobs.h.data(), (size_t)nblk * sizeof(Bz2CheckJob), hipMemcpyHostToDevice, zs));
+    HIP_TRY(c, hipMemsetAsync(b.chk.d.data(), 0xff, (size_t)nblk * sizeof(Bz2Verdict), zs)); // (a verdict that is not written is a refusal)
+    EventPair* e = next_events(c, 3);
+    if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    const EventPair ev = *e;
+    float stage_ms[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipEventRecord(ev.a, zs));
+    const int rc = bz2_check_run(c, (const uint8_t*)b.d_out.data(), out_words * 4, sl.d_buf.data(), n, b.ckjobs.d.data(), nblk, z.level, b.chk.d.data(),
+                                 zs, trace ? stage_ms : nullptr);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    HIP_TRY(c, hipMemcpyAsync(b.chk.h.data(), b.chk.d.data(), (size_t)nblk * sizeof(Bz2Verdict), hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    if (trace)
+        fprintf(stderr, "snaphash bz2 self-check: %u blocks: symbols %.3f ms, link %.3f ms, ibwt+rle1 %.3f ms, compare %.3f ms\n", nblk, stage_ms[0],
+                stage_ms[1], stage_ms[2], stage_ms[3]);
+    for (uint32_t k = 0; k < nblk; ++k) {
+        const Bz2Verdict v = b.chk.h[k];
+        if (v.status == kBz2CheckOk) continue;
+        // (the block counts through the whole stream: bz_process_slot calls this BEFORE it adds the slot's blocks to
+        // g.st.chunks, and sc.bytes grows below; the offset is the differing byte for status 1 and 2, else the piece's first)
+        const uint64_t in_piece = v.status == kBz2CheckByte || v.status == kBz2CheckLength ? v.offset : 0;
+        return fail(c, SNAPHASH_EDEVICE, bz2_check_error_text(sc.member, g.st.chunks + k, v.status, sc.bytes + offs[k] + in_piece));
+    }
+    sc.blocks += nblk;
+    sc.bytes += n;
+    return SNAPHASH_OK;
+}
 
 // The slot's first n bytes (in sl.d_buf once `ready` has fired; nullptr: already ordered on the compressor's stream) as
 // blocks into c->be.h_out[zbuf] and on to the consumers.
@@ -121,6 +231,7 @@ int bz_process_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     HIP_TRY(c, hipEventRecord(ev2.b, zs));
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), (size_t)out_words * 4, hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
+    if (z.self_check && (rc = bz_self_check_slot(g, z, sl, n, nblk, at, out_words, offs, lens, crcs, trace)) != SNAPHASH_OK) return rc;
     if (trace) {
         float ms[4] = {0, 0, 0, 0}, cat = 0;
         for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], stage_ev[i], stage_ev[i + 1]);
@@ -140,9 +251,117 @@ int BzEncoder::slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf
     return bz_process_slot(g, *this, sl, n, ready, zbuf, is_first, is_last);
 }
 
+// What the _ex entries were asked for.  opt == nullptr, or an all-zero struct: what the plain entries write (level 9, no
+// self-check); otherwise the struct says its size and every field means what it says (level 0 is 9).
+int bz2_read_options(snaphash_ctx* x, const snaphash_bz2_options* opt, uint32_t* level, bool* self_check)
+{
+    *level = 9;
+    *self_check = false;
+    if (!opt) return SNAPHASH_OK;
+    if (opt->struct_size == 0) {
+        if (opt->flags || opt->level) return fail(x, SNAPHASH_EINVAL, "snaphash_bz2_options.struct_size");
+        return SNAPHASH_OK;
+    }
+    if (opt->struct_size != sizeof(snaphash_bz2_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_bz2_options.struct_size");
+    if (opt->flags & ~(uint32_t)SNAPHASH_BZ2_SELF_CHECK) return fail(x, SNAPHASH_EINVAL, "bzip2: unknown flag");
+    *level = bzenc_level(opt->level);
+    if (!*level) return fail(x, SNAPHASH_EINVAL, "bzip2: the level is 1 to 9, or 0 for 9");
+    *self_check = (opt->flags & SNAPHASH_BZ2_SELF_CHECK) != 0;
+    return SNAPHASH_OK;
+}
+
+// what snaphash_get_bz2_selfcheck_stats hands out: of this _ex call
+void bz2_keep_selfcheck_stats(snaphash_ctx* x, const BzSelfCheck& sc)
+{
+    x->bz2_selfcheck = snaphash_bz2_selfcheck_stats{};
+    x->bz2_selfcheck.struct_size = sizeof(snaphash_bz2_selfcheck_stats);
+    x->bz2_selfcheck.blocks = sc.blocks;
+    x->bz2_selfcheck.ms = sc.ms;
+}
+
 } // namespace
 
 extern "C" {
+
+int snaphash_bzip2_buffer_ex(snaphash_ctx* x, const void* data, size_t n, const snaphash_bz2_options* opt, void** bz_out, size_t* bz_len)
+try {
+    if (!x || (!data && n) || !bz_out || !bz_len) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *bz_out = nullptr;
+    *bz_len = 0;
+    uint32_t level;
+    bool self;
+    int rc = bz2_read_options(x, opt, &level, &self);
+    if (rc) return rc;
+    BzSelfCheck sc;
+    sc.member = "the buffer";
+    BzEncoder enc(level, self ? &sc : nullptr);
+    rc = encode_to_malloc(x, enc, data, n, bz_out, bz_len);
+    bz2_keep_selfcheck_stats(x, sc);
+    return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_tar_create_bz2_ex(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix,
+                               const snaphash_bz2_options* opt, char** yaml_out, size_t* yaml_len, uint8_t* archive_digest)
+try {
+    if (!x || !tarname || !source_dir) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    uint32_t level;
+    bool self;
+    int rc = bz2_read_options(x, opt, &level, &self);
+    if (rc) return rc;
+    BzSelfCheck sc;
+    const char* base = strrchr(tarname, '/');
+    sc.member = base ? base + 1 : tarname;
+    BzEncoder enc(level, self ? &sc : nullptr);
+    rc = tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
+    bz2_keep_selfcheck_stats(x, sc);
+    return rc;
+} catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_get_bz2_selfcheck_stats(const snaphash_ctx* x, snaphash_bz2_selfcheck_stats* out)
+{
+    if (!x || !out || out->struct_size < sizeof(snaphash_bz2_selfcheck_stats)) return SNAPHASH_EINVAL;
+    *out = x->bz2_selfcheck;
+    out->struct_size = sizeof(snaphash_bz2_selfcheck_stats);
+    return SNAPHASH_OK;
+}
+
+int snaphash_bz2_check_device(snaphash_ctx* x, const void* d_z, size_t n_z, const uint64_t* z_beg, const uint64_t* z_end, const void* d_in,
+                              size_t n_in, const uint64_t* in_off, const uint64_t* in_len, const uint32_t* crc, uint32_t level, size_t n_blocks,
+                              snaphash_bz2_verdict* verdicts)
+try {
+    static_assert(sizeof(snaphash_bz2_verdict) == sizeof(Bz2Verdict), "the verdicts travel as they are");
+    if (!x || (n_blocks && (!z_beg || !z_end || !in_off || !in_len || !crc || !verdicts)) || (n_z && !d_z) || (n_in && !d_in))
+        return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (level < 1 || level > 9) return fail(x, SNAPHASH_EINVAL, "bzip2: the stream's level is 1 to 9");
+    if (n_blocks > 0x7fffffffu) return fail(x, SNAPHASH_EINVAL, "bzip2: too many blocks");
+    if (n_blocks == 0) return SNAPHASH_OK;
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<Bz2CheckJob> jobs(n_blocks);
+    for (size_t k = 0; k < n_blocks; ++k) jobs[k] = Bz2CheckJob{z_beg[k], z_end[k], in_off[k], in_len[k], crc[k], 0};
+    DevBuf<Bz2CheckJob> d_jobs;
+    DevBuf<Bz2Verdict> d_v;
+    HIP_TRY(c, d_jobs.reserve(n_blocks));
+    HIP_TRY(c, d_v.reserve(n_blocks));
+    HIP_TRY(c, hipMemcpyAsync(d_jobs.data(), jobs.data(), n_blocks * sizeof(Bz2CheckJob), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_v.data(), 0xff, n_blocks * sizeof(Bz2Verdict), c->stream));
+    const int rc = bz2_check_run(c, (const uint8_t*)d_z, n_z, (const uint8_t*)d_in, n_in, d_jobs.data(), (uint32_t)n_blocks, level, d_v.data(), c->stream,
+                                 nullptr);
+    const hipError_t e = hipStreamSynchronize(c->stream); // (jobs is read by a copy that may still be in flight)
+    if (rc) return lift(x, c, rc);
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(verdicts, d_v.data(), n_blocks * sizeof(Bz2Verdict), hipMemcpyDeviceToHost));
+    x->stats.launches = 5 * ((n_blocks + kBz2CheckGroup - 1) / kBz2CheckGroup);
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
 
 int snaphash_bzip2_buffer(snaphash_ctx* x, const void* data, size_t n, uint32_t level, void** bz_out, size_t* bz_len)
 try {

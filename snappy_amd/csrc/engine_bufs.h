@@ -6,6 +6,7 @@
 #pragma once
 #include <algorithm>
 
+#include "bz2_check_kernels.h"
 #include "bzip2_host.h"
 #include "bzip2_enc_kernels.h"
 #include "bzip2_kernels.h"
@@ -330,6 +331,14 @@ struct BzEncBufs {
     Twin<BzEncRes> res;
     Twin<uint64_t> dst;
     HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
+    Twin<Bz2CheckJob> ckjobs;  // the self-check's: every block's table entry and verdict: sized by the call that asks for
+    Twin<Bz2Verdict> chk;      // the check (bzpack.inc, behind ensure, which may release them), empty otherwise
+    hipError_t ensure_check(uint32_t blocks)
+    {
+        hipError_t e = ckjobs.ensure(std::max<size_t>(blocks, 1));
+        if (!e) e = chk.ensure(std::max<size_t>(blocks, 1));
+        return e;
+    }
     uint32_t made_blocks = 0, made_cap = 0;
     uint64_t out_words() const { return (uint64_t)made_blocks * bzenc_slot_words(made_cap) + 2; }
     hipError_t ensure(uint32_t blocks, uint32_t cap, bool with_output, int node)
@@ -388,7 +397,7 @@ struct BzEncBufs {
     template <class F> void each(F&& f)
     {
         f(d_rle); f(d_last); f(d_sel); f(d_key_a); f(d_key_b); f(d_idx_a); f(d_idx_b); f(d_rank); f(d_slots); f(d_out); f(d_syms); f(d_maps);
-        jobs.each(f); bwt_jobs.each(f); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]);
+        jobs.each(f); bwt_jobs.each(f); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); ckjobs.each(f); chk.each(f);
     }
 };
 

@@ -181,6 +181,7 @@ struct snaphash_ctx {
     snaphash_unpack_stats unpack{};
     snaphash_xz_check_stats xz_check{}; // of the most recent .xz decode (unxz.inc)
     snaphash_xz_selfcheck_stats xz_selfcheck{}; // of the most recent snaphash_xz_buffer_ex / snaphash_tar_create_xz_ex (xzpack.inc)
+    snaphash_bz2_selfcheck_stats bz2_selfcheck{}; // of the most recent snaphash_bzip2_buffer_ex / snaphash_tar_create_bz2_ex (bzpack.inc)
     snaphash_block_scan_stats block_scan{};
     std::string last_error;
     snaphash_batch* open_batch = nullptr;

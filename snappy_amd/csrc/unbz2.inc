@@ -12,6 +12,7 @@ namespace {
 // block each: 4.5 MB.  kBzLaunchSlots of them (1.2 GB) bound the scratch whatever the input; a larger input takes more
 // launches.  The piece (compressed bytes a launch's candidates come from) is at most the staging size, 64 MiB.
 constexpr uint32_t kBzLaunchSlots = 256;
+static_assert(kBz2CheckGroup <= kBzLaunchSlots, "the producer's self-check (bzpack.inc) takes groups no larger than this side's batch");
 
 // the scratch of a job, sized for it; on any allocation failure none is left behind
 int ensure_bzip2(DevCtx* c, uint64_t piece, uint32_t slots)

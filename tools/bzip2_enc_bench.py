@@ -9,9 +9,21 @@ the GPU) on tools/deflate_corpora.py's text, sources and binaries, 64 MiB each (
   size      output bytes beside bz2.compress of the whole, bz2 over the same pieces, and zlib -9
   install   snaphash_bunzip2_buffer (default configuration) of this writer's file beside libbz2's file
   build     `snaphash build-bz2` of the 297-file package of tools/bunzip2_bench.py beside `build` and `build-xz`
+  --self-check   instead of the legs above: what SNAPHASH_BZ2_SELF_CHECK costs.  On each corpus (8 MiB,
+            level 9), after one warm call, snaphash_bzip2_buffer and snaphash_bzip2_buffer_ex with the flag, alternating, five
+            of each: best / median / worst of the call, the check's own time from HIP events (snaphash_get_bz2_selfcheck_stats)
+            and, from a `snaphash bzip2 -c` child under SNAPHASH_TRACE_BZ2=1, the check's time by stage beside the encoder's;
+            the bytes must be the same.  Then `snaphash -s build-bz2` and `snaphash -s build-bz2 -c` of the 297-file package,
+            alternating in the same way.
+  --no-flag-ab LABEL   instead of the legs above: one run of an A/B of snaphash_bzip2_buffer WITHOUT the flag between two
+            checkouts.  `--tree DIR` names the checkout whose snappy_amd (and libsnaphash.so) is loaded, `--corpora-root DIR`
+            the checkout whose files make the corpora (tools/xz_bench.py says why).  On each corpus (8 MiB) one warm call, then
+            five: best / median / worst, as "build": LABEL.  Alternate the two checkouts, three runs each
+            (profiles/r17_bzip2_buffer_parent_ab.jsonl).
 Every GPU step -- the timed calls, the traced run, each decode, each build -- is a child process under a time limit sized
 to it; host work (bz2, zlib) runs outside them; the first step that fails or runs out ends the run.
-usage: tools/bzip2_enc_bench.py [--quick] [--reps N] [--legs time,size,install,build] [--out FILE]   (JSON lines on stdout and in FILE)"""
+usage: tools/bzip2_enc_bench.py [--quick] [--reps N] [--legs time,size,install,build] [--self-check] [--out FILE]
+       tools/bzip2_enc_bench.py --no-flag-ab LABEL [--tree DIR] [--corpora-root DIR] [--out FILE]   (JSON lines on stdout and in FILE; --out appends here)"""
 import argparse
 import bz2
 import json
@@ -26,13 +38,16 @@ import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# --tree DIR: the checkout whose snappy_amd is loaded (the tools and tests stay this one's)
+TREE = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]) if "--tree" in sys.argv[:-1] else ROOT
+sys.path.insert(0, TREE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context, _lib  # noqa: E402
 from bunzip2_bench import package  # noqa: E402
 from unpack_bench import corpora, emit  # noqa: E402
 from unxz_bench import timed  # noqa: E402
+from xz_bench import corpora_of, three  # noqa: E402
 
 PIECE = (100000 * 9 - 19) * 4 // 5 // 512 * 512
 CLI = os.path.join(ROOT, "snappy_amd", "bin", "snaphash")
@@ -143,6 +158,78 @@ def build_leg(total, reps, fh, tmp):
     emit(rec, fh)
 
 
+CHECK_LINE = re.compile(r"self-check: (\d+) blocks, ([\d.]+) ms")
+CHECK_TRACE = re.compile(r"self-check: \d+ blocks: symbols ([\d.]+) ms, link ([\d.]+) ms, ibwt\+rle1 ([\d.]+) ms, compare ([\d.]+) ms")
+CHECK_STAGES = ("symbols", "link", "ibwt_rle1", "compare")
+
+
+def check_trace(data, tmp):
+    """The stages of one `snaphash bzip2 -c` call, summed over its slots: the encoder's and the check's."""
+    src, dst = os.path.join(tmp, "in"), os.path.join(tmp, "out.bz2")
+    with open(src, "wb") as f:
+        f.write(data)
+    p = subprocess.run([CLI, "-g", "bzip2", "-c", src, dst], env=dict(os.environ, SNAPHASH_TRACE_BZ2="1"), stderr=subprocess.PIPE, text=True, check=True,
+                       timeout=TRACE_LIMIT)
+    enc = [tuple(float(x) for x in m) for m in TRACE.findall(p.stderr)]
+    chk = [tuple(float(x) for x in m) for m in CHECK_TRACE.findall(p.stderr)]
+    assert enc and len(chk) == len(enc)
+    rec = {"encoder_" + s + "_ms": round(sum(r[i] for r in enc), 3) for i, s in enumerate(STAGES)}
+    rec.update({"check_" + s + "_ms": round(sum(r[i] for r in chk), 3) for i, s in enumerate(CHECK_STAGES)})
+    return rec
+
+
+def self_check_legs(g, size, total, fh, tmp, reps=5):
+    for name, data in corpora(size).items():
+        g.bzip2_buffer(data)  # one warm call: the scratch
+        g.bzip2_buffer(data, self_check=True)  # (and the check's)
+        off, on, kernel, blocks = [], [], [], 0
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            z0 = g.bzip2_buffer(data)
+            off.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            z1 = g.bzip2_buffer(data, self_check=True)
+            on.append((time.perf_counter() - t0) * 1e3)
+            st = g.bz2_selfcheck_stats()
+            assert z0 == z1 and st["blocks"] == g.targz_stats()["chunks"]
+            kernel.append(st["ms"])
+            blocks = st["blocks"]
+        rec = {"leg": "self_check", "corpus": name, "bytes": len(data), "level": 9, "blocks": blocks, "reps": reps, "off_ms_best_median_worst": three(off),
+               "on_ms_best_median_worst": three(on), "check_ms_best_median_worst": three(kernel)}
+        rec.update(check_trace(data, tmp))
+        emit(rec, fh)
+    build = package(tmp, total, 297, 5)
+    arc = os.path.join(tmp, "data.tar.bz2")
+    subprocess.run([CLI, "build-bz2", build, arc], stdout=subprocess.DEVNULL, check=True, timeout=BUILD_LIMIT)  # one warm call: the page cache
+    off, on, kernel, blocks, sizes = [], [], [], 0, set()
+    for _ in range(reps):
+        for flag, ts in (([], off), (["-c"], on)):
+            t0 = time.perf_counter()
+            p = subprocess.run([CLI, "-s", "build-bz2"] + flag + [build, arc], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, check=True,
+                               timeout=BUILD_LIMIT)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            sizes.add(os.path.getsize(arc))
+            if flag:
+                m = CHECK_LINE.search(p.stderr)
+                blocks = int(m.group(1))
+                kernel.append(float(m.group(2)))
+    assert len(sizes) == 1
+    emit({"leg": "self_check_build", "files": 297, "bytes": total, "blocks": blocks, "reps": reps, "off_ms_best_median_worst": three(off),
+          "on_ms_best_median_worst": three(on), "check_ms_best_median_worst": three(kernel), "bz2_bytes": sizes.pop()}, fh)
+
+
+def no_flag_ab(g, label, corpora_root, fh, reps=5):
+    for name, data in corpora_of(corpora_root, 8 << 20).items():
+        g.bzip2_buffer(data)  # one warm call: the scratch
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            g.bzip2_buffer(data)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        emit({"leg": "bzip2_buffer_without_the_flag", "build": label, "corpus": name, "bytes": len(data), "call_ms_best_median_worst": three(ms),
+              "kernels_ms": round(g.targz_stats()["deflate_ms"], 2)}, fh)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -150,15 +237,27 @@ def main():
     ap.add_argument("--legs", default="time,size,install,build")
     ap.add_argument("--out")
     ap.add_argument("--step", nargs="+", help=argparse.SUPPRESS)  # one GPU step, in a process of its own
+    ap.add_argument("--self-check", action="store_true")
+    ap.add_argument("--no-flag-ab", metavar="LABEL")
+    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--corpora-root", default=ROOT)
     a = ap.parse_args()
     if a.step:
         return step_call(a.step[1], a.step[2], int(a.step[3])) if a.step[0] == "call" else step_install(a.step[1], a.step[2], int(a.step[3]))
     legs = a.legs.split(",")
     reps = 1 if a.quick else a.reps
     size = (8 << 20) if a.quick else (64 << 20)
-    fh = open(a.out, "w") if a.out else None
+    fh = open(a.out, "a" if a.no_flag_ab else "w") if a.out else None
     tmp = tempfile.mkdtemp(prefix="bz2enc")
     try:
+        if a.no_flag_ab:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
+                no_flag_ab(g, a.no_flag_ab, a.corpora_root, fh)
+            return
+        if a.self_check:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
+                self_check_legs(g, 8 << 20, (32 << 20) if a.quick else (256 << 20), fh, tmp)
+            return
         if set(legs) & {"time", "size", "install"}:
             for name, data in corpora(size).items():
                 corpus_legs(name, data, reps, legs, fh, tmp)
