@@ -485,6 +485,39 @@ int snaphash_tar_create_bz2(snaphash_ctx *ctx, const char *tarname, const char *
 int snaphash_bwt_device(snaphash_ctx *ctx, const void *d_in, const uint64_t *offsets, const uint64_t *lens, size_t n_blocks,
                         void *d_last, void *d_orig_ptr);
 
+/* Test instrument, like snaphash_xzenc_stages_device: the .bz2 producer's sequence for one staged slot, step for step --
+ * the job table, the blocks' CRCs, RLE1 / BWT / MTF / coding in one launch each, the host's placement of the blocks with its
+ * check of what the stages reported, the concat kernel -- over n_blocks ranges of d_in taken as they are (offsets / lens:
+ * host arrays, as snaphash_bwt_device takes them; each range 1 byte to the level's piece, (100 000 x level - 19) x 4 / 5
+ * rounded down to 512), with every per-block array but the sort's scratch in the caller's HBM, block k at k strides:
+ *   d_rle, d_last   cap + 64 bytes          RLE1's output, the BWT's last column
+ *   d_syms          cap + 64 uint16         the MTF / RUNA / RUNB symbols, the end-of-block symbol last
+ *   d_maps          516 bytes               used[256], seq[256], nused (uint32)
+ *   d_sel           18 048 bytes            a selector a group of 50 symbols
+ *   d_slots         W(cap) uint32           the block's bits from bit 0, zero behind them; W(cap) = (159 521 + 17 x (cap + 1)
+ *                                           + 31) / 32 + 2: the header's worst case and 17 bits a symbol
+ *   d_res           6 uint32                rle_n, orig_ptr, nmtf, bits, over, 0
+ *   d_dst           uint64                  the bit of d_out the block starts at
+ *   d_out           out_words uint32 in all the blocks shifted together, zero behind the last bit
+ * level: 1 to 9.  cap: the longest RLE1 output a block may have, a multiple of 64 up to 899 840; 0: the producer's, the
+ * level's piece x 5 / 4 rounded up to 64.  carry / carry_bits: the carry_bits (< 8) bits that precede block 0 in byte 0 of
+ * d_out, left-aligned in a byte, the rest of it zero.  At most 1024 blocks, and n_blocks x cap <= 32 x 899 840.
+ * rle_n != NULL is the from_last mode: RLE1 and the BWT are not run; the caller has put block k's last column, rle_n[k]
+ * (1 to cap) bytes, into d_last, and orig_ptr[k] (< rle_n[k]) and crc[k] are what the header is to say; d_in, offsets,
+ * lens and d_rle are not looked at.  Otherwise rle_n, orig_ptr and crc are NULL.
+ * Returns SNAPHASH_OK and *total_bits, the bit behind the last block (carry_bits included).  SNAPHASH_EINVAL, before anything
+ * is launched: a range or a column outside its limits, orig_ptr >= rle_n, a bad level, cap or carry, a NULL array; and,
+ * once the blocks' lengths are known and before d_dst and d_out are written, out_words below (total bits + 31) / 32.  A
+ * block whose RLE1 output exceeds cap stores what fits into its cap + 64 bytes and reports rle_n 0 and over 1; then, and
+ * for any other result the producer refuses, the call fails as the producer does: SNAPHASH_EDEVICE, "bzip2: a block's stages
+ * reported an impossible result", d_dst and d_out untouched, the other arrays as the kernels left them.  No byte outside
+ * the arrays as sized above is written, d_in is only read.  Ranges may overlap.  Synchronous. */
+int snaphash_bzenc_stages_device(snaphash_ctx *ctx, const void *d_in, const uint64_t *offsets, const uint64_t *lens, size_t n_blocks,
+                                 uint32_t level, uint32_t cap, uint32_t carry, uint32_t carry_bits, const uint32_t *rle_n,
+                                 const uint32_t *orig_ptr, const uint32_t *crc, void *d_rle, void *d_last, void *d_syms, void *d_maps,
+                                 void *d_sel, void *d_slots, void *d_res, void *d_dst, void *d_out, size_t out_words,
+                                 uint64_t *total_bits);
+
 /* The two producers above with the caller's level, and with the producer's self-check. */
 enum { SNAPHASH_BZ2_SELF_CHECK = 1 }; /* every block is decoded again in HBM -- symbols, inverse BWT, RLE1 -- and compared with
                                        * the staged piece it was made from before it leaves the GPU: a block that would not

@@ -56,8 +56,8 @@ EXPORTS = [
     "snaphash_xzenc_stages_device",
     # a SHA-512 kernel alone, over a caller's job table
     "snaphash_sha512_jobs_device",
-    # the data.tar.bz2 producer, and its BWT stage alone
-    "snaphash_bzip2_buffer", "snaphash_tar_create_bz2", "snaphash_bwt_device",
+    # the data.tar.bz2 producer, its BWT stage alone, and its stages on a caller's arrays
+    "snaphash_bzip2_buffer", "snaphash_tar_create_bz2", "snaphash_bwt_device", "snaphash_bzenc_stages_device",
     # writing the .snap (ClickDeb.Build), and its self-check kernel alone
     "snaphash_snap_build", "snaphash_deflate_check_device",
     # the .xz producer with options and its self-check, and that check's kernel alone
@@ -278,6 +278,7 @@ def lib():
     L.snaphash_tar_create_bz2.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp),
                                           ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_bwt_device.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    L.snaphash_bzenc_stages_device.argtypes = [vp, vp, vp, vp, sz] + [ctypes.c_uint32] * 4 + [vp] * 12 + [sz, u64p]
     L.snaphash_get_targz_stats.argtypes = [vp, ctypes.POINTER(TargzStats)]
     L.snaphash_deflate_codes_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.snaphash_get_targz_stats.restype = None
@@ -571,6 +572,22 @@ class Context:
         (int); offsets / lens: contiguous numpy uint64 arrays (each range 1..900 000 bytes).  d_last receives each range's
         last column at the range's offset, d_orig_ptr a uint32 per range."""
         self._check(lib().snaphash_bwt_device(self._h, d_in, offsets.ctypes.data, lens.ctypes.data, len(offsets), d_last, d_orig_ptr))
+
+    def bzenc_stages_device(self, d_in, offsets, lens, level, cap, carry, carry_bits, arrays, out_words, from_last=None):
+        """The .bz2 producer's sequence for one slot (CRCs, RLE1, BWT, MTF, coding, placement, concat) over ranges of d_in,
+        every per-block array in the caller's HBM.  d_in: a device address (int); offsets / lens: contiguous numpy uint64
+        arrays; arrays: the device addresses (ints) of d_rle, d_last, d_syms, d_maps, d_sel, d_slots, d_res, d_dst, d_out in
+        that order, sized as snaphash.h states; from_last: None, or (rle_n, orig_ptr, crc), contiguous numpy uint32 arrays of
+        a value a block -- then RLE1 and the BWT are not run and d_in / offsets / lens are not looked at.  -> the bit behind
+        the last block in d_out."""
+        total = ctypes.c_uint64()
+        if from_last is None:
+            head, nb, tail = (d_in, offsets.ctypes.data, lens.ctypes.data), len(offsets), (None, None, None)
+        else:
+            head, nb, tail = (None, None, None), len(from_last[0]), tuple(a.ctypes.data for a in from_last)
+        self._check(lib().snaphash_bzenc_stages_device(self._h, *head, nb, level, cap, carry, carry_bits, *tail, *arrays, out_words,
+                                                       ctypes.byref(total)))
+        return total.value
 
     def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False):
         """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.  With the defaults:

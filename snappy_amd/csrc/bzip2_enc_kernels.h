@@ -47,6 +47,10 @@ struct BzEncScratch {
 // RLE1, BWT, MTF and coding of nblk pieces of d_in (jobs: nblk entries in HBM).  ev: null, or five events recorded before
 // and after each of the four stages.
 hipError_t launch_bzenc_blocks(const uint8_t* d_in, const BzEncJob* d_jobs, const BzEncScratch& s, uint32_t nblk, hipStream_t st, hipEvent_t* ev);
+// The same launch entered behind its second stage (snaphash_bzenc_stages_device's from_last mode): MTF and coding of nblk
+// last columns the caller has put into s.last, with s.res[k].rle_n (1 .. s.cap) and .orig_ptr set and the other fields of
+// s.res zero; of d_jobs only the CRCs are read.
+hipError_t launch_bzenc_from_last(const BzEncJob* d_jobs, const BzEncScratch& s, uint32_t nblk, hipStream_t st);
 // the BWT stage alone over nblk ranges (jobs in HBM, every n <= s.cap): last columns to d_out, origPtr to d_op[0..nblk)
 hipError_t launch_bzenc_bwt(const uint8_t* d_in, const BzBwtJob* d_jobs, uint8_t* d_out, uint32_t* d_op, const BzEncScratch& s, uint32_t nblk,
                             hipStream_t st);

@@ -404,6 +404,16 @@ hipError_t launch_bzenc_blocks(const uint8_t* d_in, const BzEncJob* d_jobs, cons
     return hipGetLastError();
 }
 
+hipError_t launch_bzenc_from_last(const BzEncJob* d_jobs, const BzEncScratch& s, uint32_t nblk, hipStream_t st)
+{
+    if (nblk == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(s.slots, 0, (size_t)nblk * s.slot_words * 4, st);
+    if (e) return e;
+    bz_enc_mtf_kernel<<<nblk, 64, 0, st>>>(s);
+    bz_enc_code_kernel<<<nblk, 1024, 0, st>>>(d_jobs, s);
+    return hipGetLastError();
+}
+
 hipError_t launch_bzenc_bwt(const uint8_t* d_in, const BzBwtJob* d_jobs, uint8_t* d_out, uint32_t* d_op, const BzEncScratch& s, uint32_t nblk,
                             hipStream_t st)
 {

@@ -409,6 +409,94 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+// bz_process_slot's sequence once more on a caller's arrays (a copy, as xz_encode_stages is one of xz_process_slot: the
+// producer's loop stays as it was): the job table, the CRCs, the four stages -- or, from_last, the last two -- the host's
+// placement with its check of the results, the concat kernel.  Only the sort's keys, indices and ranks are the ctx's.
+int snaphash_bzenc_stages_device(snaphash_ctx* x, const void* d_in, const uint64_t* offsets, const uint64_t* lens, size_t n_blocks, uint32_t level,
+                                 uint32_t cap, uint32_t carry, uint32_t carry_bits, const uint32_t* rle_n, const uint32_t* orig_ptr,
+                                 const uint32_t* crc, void* d_rle, void* d_last, void* d_syms, void* d_maps, void* d_sel, void* d_slots, void* d_res,
+                                 void* d_dst, void* d_out, size_t out_words, uint64_t* total_bits)
+try {
+    const bool from_last = rle_n != nullptr;
+    if (!x || !total_bits) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    *total_bits = 0;
+    if (level < 1 || level > 9) return fail(x, SNAPHASH_EINVAL, "bzip2: the level is 1 to 9");
+    if (cap == 0) cap = (bzenc_rle_cap(level) + 63) & ~63u;
+    if (cap % 64 || cap > ((bzenc_rle_cap(9) + 63) & ~63u)) return fail(x, SNAPHASH_EINVAL, "bzip2: cap is a multiple of 64, at most 899 840, or 0");
+    if (carry_bits > 7 || (carry & ~((0xff00u >> carry_bits) & 0xffu)) != 0) // (only the carry_bits highest bits of a byte)
+        return fail(x, SNAPHASH_EINVAL, "bzip2: carry is carry_bits < 8 bits, left-aligned in a byte");
+    if (n_blocks == 0) {
+        *total_bits = carry_bits;
+        return SNAPHASH_OK;
+    }
+    if (!d_last || !d_syms || !d_maps || !d_sel || !d_slots || !d_res || !d_dst || !d_out) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (from_last ? (!orig_ptr || !crc) : (!d_in || !offsets || !lens || !d_rle)) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (n_blocks > kBzEncLaunchBlocksMax || n_blocks * (uint64_t)cap > kBzEncLaunchBytes)
+        return fail(x, SNAPHASH_EINVAL, "bzip2: more blocks than one launch takes");
+    for (size_t k = 0; k < n_blocks; ++k) {
+        if (from_last) {
+            if (rle_n[k] < 1 || rle_n[k] > cap) return fail(x, SNAPHASH_EINVAL, "bzip2: a last column is 1 to cap bytes");
+            if (orig_ptr[k] >= rle_n[k]) return fail(x, SNAPHASH_EINVAL, "bzip2: origPtr is below the column's length");
+        } else {
+            if (lens[k] < 1 || lens[k] > bzenc_piece(level)) return fail(x, SNAPHASH_EINVAL, "bzip2: a range is 1 byte to the level's piece");
+            if (lens[k] > ~0ull - offsets[k]) return fail(x, SNAPHASH_EINVAL, "a range wraps around the address space");
+        }
+    }
+    TOP_ENTER(x);
+    DevCtx* c = x->d0();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t nblk = (uint32_t)n_blocks;
+    int rc = ensure_bzenc(c, nblk, cap, false);
+    if (rc) return lift(x, c, rc);
+    BzEncBufs& b = c->be;
+    hipStream_t zs = c->z_stream;
+    BzEncScratch s = b.scratch(); // (the sort's scratch: made for at least nblk blocks of cap, walked with this call's stride)
+    s.cap = cap;
+    s.slot_words = bzenc_slot_words(cap);
+    s.rle = (uint8_t*)d_rle; s.last = (uint8_t*)d_last; s.syms = (uint16_t*)d_syms; s.maps = (BzEncMap*)d_maps; s.sel = (uint8_t*)d_sel;
+    s.slots = (uint32_t*)d_slots; s.res = (BzEncRes*)d_res;
+    std::vector<BzEncRes> res(nblk, BzEncRes{});
+    std::vector<uint64_t> dst(nblk);
+    std::vector<uint32_t> crcs(nblk);
+    if (from_last) {
+        for (uint32_t k = 0; k < nblk; ++k) {
+            crcs[k] = crc[k];
+            res[k].rle_n = rle_n[k];
+            res[k].orig_ptr = orig_ptr[k];
+            b.jobs.h[k] = BzEncJob{0, 0, crcs[k]};
+        }
+        HIP_TRY(c, hipMemcpyAsync(b.jobs.d.data(), b.jobs.h.data(), (size_t)nblk * sizeof(BzEncJob), hipMemcpyHostToDevice, zs));
+        HIP_TRY(c, hipMemcpyAsync(d_res, res.data(), (size_t)nblk * sizeof(BzEncRes), hipMemcpyHostToDevice, zs));
+        HIP_TRY(c, launch_bzenc_from_last(b.jobs.d.data(), s, nblk, zs));
+    } else {
+        rc = crc_ranges_dev(c, kCrcBzip2, (const uint8_t*)d_in, offsets, lens, nblk, crcs.data(), zs, nullptr);
+        if (rc) return lift(x, c, rc);
+        for (uint32_t k = 0; k < nblk; ++k) b.jobs.h[k] = BzEncJob{offsets[k], (uint32_t)lens[k], crcs[k]};
+        HIP_TRY(c, hipMemcpyAsync(b.jobs.d.data(), b.jobs.h.data(), (size_t)nblk * sizeof(BzEncJob), hipMemcpyHostToDevice, zs));
+        HIP_TRY(c, launch_bzenc_blocks((const uint8_t*)d_in, b.jobs.d.data(), s, nblk, zs, nullptr));
+    }
+    HIP_TRY(c, hipMemcpyAsync(res.data(), d_res, (size_t)nblk * sizeof(BzEncRes), hipMemcpyDeviceToHost, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    uint64_t at = carry_bits;
+    for (uint32_t k = 0; k < nblk; ++k) {
+        const BzEncRes& r = res[k];
+        if (r.over || r.bits == 0 || r.bits > (uint64_t)s.slot_words * 32 || r.rle_n == 0 || r.orig_ptr >= r.rle_n)
+            return lift(x, c, fail(c, SNAPHASH_EDEVICE, "bzip2: a block's stages reported an impossible result"));
+        dst[k] = at;
+        at += r.bits;
+    }
+    if ((at + 31) / 32 > out_words) return lift(x, c, fail(c, SNAPHASH_EINVAL, "bzip2: out_words is smaller than the placed bits need"));
+    HIP_TRY(c, hipMemcpyAsync(d_dst, dst.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, zs));
+    HIP_TRY(c, launch_bzenc_concat(s, (const uint64_t*)d_dst, nblk, (uint32_t*)d_out, out_words, carry, zs));
+    HIP_TRY(c, hipStreamSynchronize(zs));
+    *total_bits = at;
+    x->stats.launches = (from_last ? 2 : 4) + 1;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
 int snaphash_tar_create_bz2(snaphash_ctx* x, const char* tarname, const char* source_dir, const char* exclude_prefix, char** yaml_out,
                             size_t* yaml_len, uint8_t* archive_digest)
 try {

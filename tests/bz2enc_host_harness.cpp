@@ -1,10 +1,12 @@
 // bz2enc_host_harness.cpp -- the .bz2 writer's host model (snappy_amd/csrc/bzip2_enc_core.h: the routines the GPU kernels
 // run, stage by stage) compiled for the host, for tests/test_bz2enc_host.py and as the expected bytes of
-// tests/test_gpu_bz2enc.py; and a reader of what it wrote, built on bzip2_core.h's bit reader and block decoder.
+// tests/test_gpu_bz2enc.py; a reader of what it wrote, built on bzip2_core.h's bit reader and block decoder; and every array
+// the kernels leave, stage by stage (bz2enc_stage_model.h), as the expected arrays of tests/test_gpu_bz2enc_edges.py.
 #include <stdlib.h>
 #include <string.h>
 
 #include "../snappy_amd/csrc/bzip2_enc_core.h"
+#include "bz2enc_stage_model.h"
 
 using namespace snaphash;
 
@@ -52,6 +54,34 @@ void be_code_lengths(const uint32_t* freq, uint32_t alpha, uint32_t max_bits, ui
 {
     BzEncHuffScratch s;
     bzenc_code_lengths(freq, alpha, max_bits, len, s);
+}
+
+uint32_t be_slot_words(uint32_t cap) { return bzenc_slot_words(cap); }
+uint32_t be_rle_cap(uint32_t level) { return (bzenc_rle_cap(level) + 63) & ~63u; } // what the producer gives a fresh ctx
+
+// What snaphash_bzenc_stages_device must leave in every array (bz2enc_stage_model.h): nblk ranges of data, cap a multiple of
+// 64.  The caller hands the arrays in as the device buffers start out (slots, res, out zero; the rest the fill).  Returns
+// the bit behind the last block; -1 when a block's RLE1 output exceeds cap (over[k] says which; dst and out as they were).
+int64_t be_stages(const uint8_t* data, const uint64_t* offs, const uint64_t* lens, uint32_t nblk, uint32_t cap, uint32_t carry, uint32_t carry_bits,
+                  uint8_t* rle, uint8_t* last, uint16_t* syms, uint8_t* maps, uint8_t* sel, uint32_t* slots, uint32_t* res, uint64_t* dst, uint32_t* out,
+                  uint64_t out_words, uint8_t* over)
+{
+    const BeArrays a = {rle, last, syms, maps, sel, slots, res, dst, out, out_words, over};
+    return be_stages_host(data, offs, lens, nblk, cap, carry, carry_bits, a);
+}
+// the same behind the BWT: block k's last column is last[k * (cap + 64) ..][0 .. rle_n[k])
+int64_t be_stages_from_last(const uint32_t* rle_n, const uint32_t* orig_ptr, const uint32_t* crc, uint32_t nblk, uint32_t cap, uint32_t carry,
+                            uint32_t carry_bits, uint8_t* last, uint16_t* syms, uint8_t* maps, uint8_t* sel, uint32_t* slots, uint32_t* res,
+                            uint64_t* dst, uint32_t* out, uint64_t out_words, uint8_t* over)
+{
+    const BeArrays a = {nullptr, last, syms, maps, sel, slots, res, dst, out, out_words, over};
+    return be_stages_from_last_host(rle_n, orig_ptr, crc, nblk, cap, carry, carry_bits, a);
+}
+// one slot's bits back to the last column, origPtr and CRC by the install side's decoder; returns its status (0: a whole block)
+int32_t be_read_slot(const uint32_t* slot, uint32_t slot_words, uint8_t* last, uint32_t cap_out, uint32_t* n, uint32_t* op, uint32_t* crc,
+                     uint64_t* end_bit)
+{
+    return be_read_slot_host(slot, slot_words, last, cap_out, n, op, crc, end_bit);
 }
 
 // Reads a stream this side wrote: per block (8 uint64): the bit it starts at, its CRC, origPtr, the table count, the
