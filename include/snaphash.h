@@ -387,7 +387,8 @@ typedef struct snaphash_xz_options {
     uint32_t flags;       /* SNAPHASH_XZ_*; an unknown bit is SNAPHASH_EINVAL */
     uint64_t block_size;  /* as in snaphash_xz_buffer: 0 = 1 MiB */
     uint32_t check;       /* as in snaphash_xz_buffer_check: 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256 */
-    uint32_t reserved;    /* 0 */
+    uint32_t filter;      /* a BCJ filter in front of LZMA2, by the format's id: 0 none, 4 x86, 7 ARM, 8 ARM-Thumb; anything
+                           * else is SNAPHASH_EINVAL.  (The field was `reserved`, 0, at this offset and size.)  See below. */
 } snaphash_xz_options;
 typedef struct snaphash_xz_selfcheck_stats {
     uint32_t struct_size; /* set by the caller */
@@ -404,6 +405,16 @@ int snaphash_tar_create_xz_ex(snaphash_ctx *ctx, const char *tarname, const char
                               const snaphash_xz_options *opt, char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
 /* of the most recent of the two _ex calls above */
 int snaphash_get_xz_selfcheck_stats(const snaphash_ctx *ctx, snaphash_xz_selfcheck_stats *out);
+/* snaphash_xz_options.filter.  A snap's data member is mostly machine code; a BCJ (branch-call-jump)
+ * filter rewrites the relative targets of calls and jumps as absolute ones, so that calls of one function become equal
+ * bytes for LZMA2.  With a filter every Block's chain is that filter (no properties: start_offset 0) followed by LZMA2,
+ * the chain `xz --x86 --lzma2` writes; liblzma and snaphash_unxz_buffer_ex with SNAPHASH_UNXZ_BCJ read it.  The slot's staged
+ * bytes are copied once more in HBM, the copy is filtered in place by the BCJ kernels (a Block a range, positions from the
+ * Block's first byte, so Blocks stay independent), and the LZMA2 kernels read the copy; the Blocks' Checks, the members'
+ * SHA-512 and hashes.yaml are taken from the unfiltered bytes, as the format asks.  filter == 0 writes byte for byte what
+ * the struct wrote before the field had a name.  SNAPHASH_XZ_SELF_CHECK with a filter walks the chunks against the filtered
+ * bytes, then undoes the filter in place and compares the result with the staged bytes in HBM: a difference is
+ * SNAPHASH_EDEVICE, snaphash_last_error naming the Block and the offset. */
 
 typedef struct snaphash_lzma2_verdict {
     uint32_t status; /* 0 accepted; 1 a literal or stored byte differs; 2 a match's or short rep's copy differs; 3 a distance
@@ -673,12 +684,53 @@ int snaphash_tar_unpack_bz2(snaphash_ctx *ctx, const char *data_tar_bz2, const c
  * SNAPHASH_EFORMAT: whatever liblzma refuses -- a wrong magic or CRC, an Index that disagrees with its Blocks, malformed
  * LZMA2, a Check mismatch, bytes behind the last Stream that are neither padding nor a Stream, n == 0.
  * SNAPHASH_EINVAL: a well-formed file this decoder does not take -- a filter chain other than one LZMA2 ("xz:
- * unsupported filter 0xNN": the BCJ filters, delta) or a Check id other than 0, 1, 4, 10; the caller decodes it itself. */
+ * unsupported filter 0xNN": the BCJ filters, delta; snaphash_unxz_buffer_ex below takes three of the former) or a Check id other than 0, 1, 4, 10; the caller decodes it itself. */
 int snaphash_unxz_buffer(snaphash_ctx *ctx, const void *xz, size_t n, void **out, size_t *out_len);
 /* snaphash_tar_unpack for a data.tar.xz: the same UnpackTar rules, errors and in-pass Verify, from the xz-decoded
  * stream; archive_digest (may be NULL): the 64 raw bytes of SHA-512(data_tar_xz). */
 int snaphash_tar_unpack_xz(snaphash_ctx *ctx, const char *data_tar_xz, const char *target_dir, const char *yaml,
                            size_t yaml_len, snaphash_mismatch *first, uint8_t *archive_digest);
+/* The two calls above for files whose Blocks carry a BCJ filter in front of LZMA2.  The plain entries answer SNAPHASH_EINVAL
+ * for such a file, and keep doing so; these take it when asked to. */
+enum { SNAPHASH_UNXZ_BCJ = 1 }; /* accept, Block by Block, the chain of one BCJ filter -- x86 (0x04), ARM (0x07), ARM-Thumb
+                                 * (0x08) -- followed by LZMA2, with filter properties of 0 bytes or 4 (the start_offset).
+                                 * Every other chain (Delta, PowerPC, IA64, SPARC, two filters in front of LZMA2, ids
+                                 * liblzma 5.2.5 does not know) stays SNAPHASH_EINVAL with the plain entries' text.
+                                 * SNAPHASH_EFORMAT: properties of any other size, or a start_offset liblzma refuses (not a
+                                 * multiple of 4 for ARM, of 2 for Thumb). */
+typedef struct snaphash_unxz_options {
+    uint32_t struct_size; /* sizeof(snaphash_unxz_options) */
+    uint32_t flags;       /* SNAPHASH_UNXZ_*; an unknown bit is SNAPHASH_EINVAL */
+} snaphash_unxz_options;
+/* opt == NULL, or a struct that is all zero: what snaphash_unxz_buffer / snaphash_tar_unpack_xz do, error text included.
+ * With SNAPHASH_UNXZ_BCJ a Block's filter is undone behind its LZMA2 decode and in front of its Check (the Check is over the
+ * unfiltered bytes): by the host thread that decoded the Block in the default configuration; under SNAPHASH_FLAG_GPU_ONLY
+ * by one launch of the BCJ kernels over the ranges of the Blocks lzma2_blocks_kernel decoded, in front of the Check
+ * kernels (Blocks that went to a host thread are filtered there).  snaphash_get_xz_filter_stats tells who did what. */
+int snaphash_unxz_buffer_ex(snaphash_ctx *ctx, const void *xz, size_t n, const snaphash_unxz_options *opt, void **out,
+                            size_t *out_len);
+int snaphash_tar_unpack_xz_ex(snaphash_ctx *ctx, const char *data_tar_xz, const char *target_dir, const char *yaml,
+                              size_t yaml_len, const snaphash_unxz_options *opt, snaphash_mismatch *first,
+                              uint8_t *archive_digest);
+/* The BCJ kernels alone, in place on byte ranges resident in HBM: the twin of snaphash_crc64_device and the tests'
+ * instrument.  Range i is d_base[offsets[i] .. + lens[i]) (any alignment, any length; ranges must not overlap) and is
+ * filtered as a Block of its own: positions count from its first byte plus start_offset, modulo 2^32.  filter: 4 x86, 7 ARM,
+ * 8 ARM-Thumb; encode: nonzero = the producer's direction, 0 = the decoder's.  A range's last 4 bytes (x86), incomplete word
+ * (ARM) or halfword pair (Thumb) are left as they are, as liblzma leaves them; the bytes are liblzma's.  SNAPHASH_EINVAL:
+ * another filter id, a start_offset that is not a multiple of the filter's alignment (1, 4, 2), more than 2^40 bytes in all.
+ * Synchronous; stats.kernel_ms = the kernels (HIP events), stats.launches = their number. */
+int snaphash_bcj_device(snaphash_ctx *ctx, uint32_t filter, int encode, void *d_base, const uint64_t *offsets,
+                        const uint64_t *lens, size_t n, uint32_t start_offset);
+/* What the BCJ filters did in the most recent call of this ctx among snaphash_xz_buffer_ex, snaphash_tar_create_xz_ex,
+ * snaphash_unxz_buffer(_ex) and snaphash_tar_unpack_xz(_ex). */
+typedef struct snaphash_xz_filter_stats {
+    uint32_t struct_size;   /* set by the caller */
+    uint32_t filter;        /* the producer's filter; on the install side the filter of the last filtered Block; 0: none */
+    uint64_t device_blocks; /* Blocks the BCJ kernels filtered */
+    uint64_t host_blocks;   /* Blocks a host thread filtered (install side) */
+    double device_ms;       /* the BCJ kernels, HIP events (with the producer's self-check: its undo included) */
+} snaphash_xz_filter_stats;
+int snaphash_get_xz_filter_stats(const snaphash_ctx *ctx, snaphash_xz_filter_stats *out);
 /* One Block of a .xz file by lzma2_blocks_kernel alone, into the caller's HBM: Block `block` (counted over all Streams of
  * xz[0..n), in order) decoded to d_dst[0..dst_len), where dst_len must be the Block's uncompressed size (at most 4 MiB).
  * The container is checked as in snaphash_unxz_buffer; the Block's Check is NOT (snaphash_crc32_device /

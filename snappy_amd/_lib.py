@@ -62,11 +62,24 @@ EXPORTS = [
     "snaphash_snap_build", "snaphash_deflate_check_device",
     # the .xz producer with options and its self-check, and that check's kernel alone
     "snaphash_xz_buffer_ex", "snaphash_tar_create_xz_ex", "snaphash_get_xz_selfcheck_stats", "snaphash_lzma2_check_device",
+    # .xz with a BCJ filter in front of LZMA2, both sides, and the filter kernels alone
+    "snaphash_unxz_buffer_ex", "snaphash_tar_unpack_xz_ex", "snaphash_bcj_device", "snaphash_get_xz_filter_stats",
     # the .bz2 producer with options and its self-check, and that check's kernels alone
     "snaphash_bzip2_buffer_ex", "snaphash_tar_create_bz2_ex", "snaphash_get_bz2_selfcheck_stats", "snaphash_bz2_check_device",
 ]
 BUILD_NO_HASHES, BUILD_CHECK = 1, 2
 XZ_SELF_CHECK = 1
+UNXZ_BCJ = 1
+BCJ_X86, BCJ_ARM, BCJ_ARMTHUMB = 4, 7, 8  # the .xz format's filter ids
+BCJ_NAMES = {"x86": BCJ_X86, "arm": BCJ_ARM, "armthumb": BCJ_ARMTHUMB}
+
+
+def bcj_filter(f):
+    """A filter as the entry points take it: None / 0, an id (4, 7, 8) or a name ("x86", "arm", "armthumb")."""
+    if not f:
+        return 0
+    return BCJ_NAMES[f] if isinstance(f, str) else int(f)
+
 BZ2_SELF_CHECK = 1
 JOB_FIRST, JOB_FINAL = 1, 2
 CRC_GZIP, CRC_BZIP2 = 0, 1
@@ -141,7 +154,16 @@ class XzCheckStats(ctypes.Structure):
 
 class XzOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("block_size", ctypes.c_uint64),
-                ("check", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("check", ctypes.c_uint32), ("filter", ctypes.c_uint32)]
+
+
+class UnxzOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class XzFilterStats(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("filter", ctypes.c_uint32), ("device_blocks", ctypes.c_uint64),
+                ("host_blocks", ctypes.c_uint64), ("device_ms", ctypes.c_double)]
 
 
 class XzSelfCheckStats(ctypes.Structure):
@@ -316,6 +338,11 @@ def lib():
     L.snaphash_tar_create_xz_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(XzOptions), ctypes.POINTER(vp),
                                             ctypes.POINTER(sz), ctypes.c_char_p]
     L.snaphash_get_xz_selfcheck_stats.argtypes = [vp, ctypes.POINTER(XzSelfCheckStats)]
+    L.snaphash_unxz_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(UnxzOptions), ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.snaphash_tar_unpack_xz_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(UnxzOptions),
+                                            ctypes.POINTER(Mismatch), ctypes.c_char_p]
+    L.snaphash_bcj_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, vp, vp, sz, ctypes.c_uint32]
+    L.snaphash_get_xz_filter_stats.argtypes = [vp, ctypes.POINTER(XzFilterStats)]
     L.snaphash_lzma2_check_device.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, sz, u64p, u64p, sz, ctypes.c_uint32, vp]
     L.snaphash_bzip2_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(Bz2Options), ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_create_bz2_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bz2Options), ctypes.POINTER(vp),
@@ -497,16 +524,18 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def xz_buffer(self, data, block_size=0, check=None, self_check=False):
+    def xz_buffer(self, data, block_size=0, check=None, self_check=False, filter=None):
         """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU.  check: the Blocks'
         Check id -- 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256, each taken in HBM; None: CRC-64 through the entry point that
         takes no Check.  self_check: every LZMA2 chunk is walked against the bytes it was made from before it leaves HBM
         (snaphash_xz_buffer_ex with SNAPHASH_XZ_SELF_CHECK; xz_selfcheck_stats() tells what was walked); the bytes are
-        the same."""
+        the same.  filter: a BCJ filter in front of LZMA2 in every Block -- "x86", "arm", "armthumb" or the format's id
+        (4, 7, 8), applied in HBM (snaphash_xz_buffer_ex; xz_filter_stats() tells what ran); None or 0: none."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
-        if self_check:
-            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK, block_size, 4 if check is None else check, 0)
+        filter = bcj_filter(filter)
+        if self_check or filter:
+            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, 4 if check is None else check, filter)
             self._check(lib().snaphash_xz_buffer_ex(self._h, ctypes.addressof(buf), len(data), ctypes.byref(opt), ctypes.byref(p), ctypes.byref(n)))
         elif check is None:
             self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
@@ -589,14 +618,15 @@ class Context:
                                                        ctypes.byref(total)))
         return total.value
 
-    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False):
+    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False, filter=None):
         """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.  With the defaults:
         snaphash_tar_create_xz (1 MiB Blocks, CRC-64).  Anything else goes through snaphash_tar_create_xz_ex: block_size
-        and check as in xz_buffer, self_check as there.
+        check, self_check and filter as in xz_buffer (hashes.yaml and the Blocks' Checks are of the unfiltered bytes).
         -> (yaml bytes or None, archive digest (64 bytes))."""
-        if block_size == 0 and check == 4 and not self_check:
+        filter = bcj_filter(filter)
+        if block_size == 0 and check == 4 and not self_check and not filter:
             return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
-        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, 0)
+        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, filter)
         return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz_ex", _opt=opt)
 
     def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create", _opt=None):
@@ -692,23 +722,36 @@ class Context:
         uint32 (trees built before one fitted max_bits)."""
         self._check(lib().snaphash_deflate_codes_device(self._h, d_freq, n_tables, n_syms, max_bits, d_lens, d_codes, d_rounds))
 
-    def unxz_buffer(self, xz):
-        """Every Stream of `xz` (.xz) decoded, Blocks side by side (host threads, or the GPU kernel with FLAG_GPU_ONLY)."""
+    def unxz_buffer(self, xz, bcj=False):
+        """Every Stream of `xz` (.xz) decoded, Blocks side by side (host threads, or the GPU kernel with FLAG_GPU_ONLY).
+        bcj: also take Blocks with an x86, ARM or ARM-Thumb filter in front of LZMA2 (snaphash_unxz_buffer_ex with
+        SNAPHASH_UNXZ_BCJ); without it such a file is SNAPHASH_EINVAL."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         xz = bytes(xz)
-        self._check(lib().snaphash_unxz_buffer(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz),
-                                               ctypes.byref(p), ctypes.byref(n)))
+        if bcj:
+            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), UNXZ_BCJ)
+            self._check(lib().snaphash_unxz_buffer_ex(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz), ctypes.byref(opt),
+                                                      ctypes.byref(p), ctypes.byref(n)))
+        else:
+            self._check(lib().snaphash_unxz_buffer(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz),
+                                                   ctypes.byref(p), ctypes.byref(n)))
         try:
             return ctypes.string_at(p.value, n.value)
         finally:
             lib().snaphash_free(p)
 
-    def tar_unpack_xz(self, data_tar_xz, target_dir, yaml_bytes=None):
-        """tar_unpack for a data.tar.xz.  -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
+    def tar_unpack_xz(self, data_tar_xz, target_dir, yaml_bytes=None, bcj=False):
+        """tar_unpack for a data.tar.xz; bcj as in unxz_buffer (snaphash_tar_unpack_xz_ex).
+        -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
         m = Mismatch()
         dig = ctypes.create_string_buffer(64)
-        rc = lib().snaphash_tar_unpack_xz(self._h, os.fsencode(data_tar_xz), os.fsencode(target_dir), yaml_bytes,
-                                          len(yaml_bytes) if yaml_bytes is not None else 0, ctypes.byref(m), dig)
+        ylen = len(yaml_bytes) if yaml_bytes is not None else 0
+        if bcj:
+            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), UNXZ_BCJ)
+            rc = lib().snaphash_tar_unpack_xz_ex(self._h, os.fsencode(data_tar_xz), os.fsencode(target_dir), yaml_bytes, ylen, ctypes.byref(opt),
+                                                 ctypes.byref(m), dig)
+        else:
+            rc = lib().snaphash_tar_unpack_xz(self._h, os.fsencode(data_tar_xz), os.fsencode(target_dir), yaml_bytes, ylen, ctypes.byref(m), dig)
         if rc == EMISMATCH:
             return (m.kind, m.name.decode(errors="replace")), dig.raw
         self._check(rc)
@@ -745,6 +788,23 @@ class Context:
         out = np.zeros(max(n, 1), dtype=np.uint64)
         self._check(lib().snaphash_crc64_device(self._h, d_base, offsets.ctypes.data, lens.ctypes.data, n, out.ctypes.data))
         return out[:n]
+
+    def bcj_device(self, filter, encode, d_base, offsets, lens, start_offset=0):
+        """A BCJ filter in place over byte ranges resident in HBM, each range a Block of its own (snaphash_bcj_device).
+        filter: "x86", "arm", "armthumb" or 4, 7, 8; encode: the producer's direction (False: the decoder's); d_base: device
+        address (int); offsets / lens: contiguous numpy uint64 arrays, any alignment, no overlap.  stats() tells the
+        kernels' milliseconds and their number."""
+        n = len(offsets)
+        self._check(lib().snaphash_bcj_device(self._h, bcj_filter(filter), 1 if encode else 0, d_base, offsets.ctypes.data if n else None,
+                                              lens.ctypes.data if n else None, n, start_offset))
+
+    def xz_filter_stats(self):
+        """What the BCJ filters did in the last .xz call of either side: the filter, Blocks filtered by the kernels and on
+        host threads, the kernels' milliseconds."""
+        s = XzFilterStats()
+        s.struct_size = ctypes.sizeof(XzFilterStats)
+        self._check(lib().snaphash_get_xz_filter_stats(self._h, ctypes.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in XzFilterStats._fields_ if f[0] != "struct_size"}
 
     def sha256_device(self, d_base, offsets, lens):
         """SHA-256 of byte ranges resident in HBM.  d_base: device address (int); offsets / lens: contiguous numpy

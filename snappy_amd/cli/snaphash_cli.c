@@ -7,25 +7,28 @@
  *                                      Build's data step fused (clickdeb/deb.go:261-344 + snappy/build.go:517-520):
  *                                      data.tar.gz of BUILD_DIR without DEBIAN/, every file read once, then
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
- *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] BUILD_DIR OUT.tar.xz
+ *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB (or -B), Check
- *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU
+ *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU; -F: a BCJ
+ *                                      filter in front of LZMA2, applied on the GPU (what xz writes when XZ_OPT names one)
  *   snaphash [options] build-bz2 [-c] [-L LEVEL] BUILD_DIR OUT.tar.bz2
  *                                      the same with data.tar.bz2 (level 9, or -L): every bzip2 block coded on the GPU; -c: every
  *                                      block decoded again and compared on the GPU (the .bz2 self-check)
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
  *   snaphash [options] bzip2 [-L LEVEL] [-c] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9); -c: the .bz2
  *                                                self-check on the GPU (-s prints what it checked)
- *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c]
+ *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
  *                                                Blocks' Check as named (default crc64), taken on the GPU; -c: the LZMA2
- *                                                self-check on the GPU (-s prints what it walked)
+ *                                                self-check on the GPU (-s prints what it walked); -F: a BCJ filter
+ *                                                in front of LZMA2 (-s prints what the filter kernels did)
  *   snaphash [options] gunzip IN.gz OUT          the inverse: every member decoded (GPU inflate)
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
  *   snaphash [options] unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML]
- *   snaphash [options] unxz IN.xz OUT            every .xz Stream decoded (Blocks side by side)
- *   snaphash [options] unpack-xz DATA_TAR_XZ DIR [HASHES_YAML]
+ *   snaphash [options] unxz [-F] IN.xz OUT       every .xz Stream decoded (Blocks side by side); -F: Blocks with an x86, ARM
+ *                                                or ARM-Thumb filter in front of LZMA2 are taken too (SNAPHASH_UNXZ_BCJ)
+ *   snaphash [options] unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML]
  *                                      ClickDeb.Unpack (clickdeb/deb.go:188-203) into DIR; with HASHES_YAML also the
  *                                      install-time Verify from the decoded bytes; exit 1 on mismatch
  *   snaphash [options] snap ls FILE.snap         the ar members of the package: size, offset, name
@@ -63,13 +66,14 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
-                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] DIR OUT.tar.xz |\n"
+                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] DIR OUT.tar.xz |\n"
                     "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
                     "       (in front of their names build-bz2 also takes [-c] [-L LEVEL] and bzip2 [-c]: -c is the .bz2 self-check)\n"
-                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
-                    "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz IN.xz OUT |\n"
-                    "       unpack-xz DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
+                    "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz [-F] IN.xz OUT |\n"
+                    "       unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
+                    "       (-F on the two .xz decoding commands: also take Blocks with a BCJ filter in front of LZMA2)\n"
                     "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap | snap build [-c] DIR OUT.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
@@ -94,6 +98,22 @@ static void print_block_stats(snaphash_ctx *c, const char *what)
 static int xz_check_id(const char *w)
 {
     return !strcmp(w, "none") ? 0 : !strcmp(w, "crc32") ? 1 : !strcmp(w, "crc64") ? 4 : !strcmp(w, "sha256") ? 10 : -1;
+}
+
+/* -F's word -> the filter id, or 0 */
+static uint32_t xz_filter_id(const char *w)
+{
+    return !strcmp(w, "x86") ? 4u : !strcmp(w, "arm") ? 7u : !strcmp(w, "armthumb") ? 8u : 0u;
+}
+
+/* -s after an .xz call with -F: what the BCJ filters did */
+static void print_xz_filter(snaphash_ctx *c, const char *what)
+{
+    snaphash_xz_filter_stats s;
+    s.struct_size = sizeof s;
+    if (!snaphash_get_xz_filter_stats(c, &s))
+        fprintf(stderr, "%s: filter 0x%02X: %llu blocks on the GPU (%.3f ms), %llu on host threads\n", what, s.filter,
+                (unsigned long long)s.device_blocks, s.device_ms, (unsigned long long)s.host_blocks);
 }
 
 /* -s after an .xz producer call with -c: what the self-check walked */
@@ -162,6 +182,16 @@ int main(int argc, char **argv)
     argc -= a - 1;
     argv += a - 1;
     if (argc < 3) return usage();
+    /* unxz / unpack-xz -F, in front of their names: the _ex entries with SNAPHASH_UNXZ_BCJ */
+    snaphash_unxz_options uo;
+    memset(&uo, 0, sizeof uo);
+    if ((!strcmp(argv[1], "unxz") || !strcmp(argv[1], "unpack-xz")) && !strcmp(argv[2], "-F")) {
+        uo.struct_size = sizeof uo;
+        uo.flags = SNAPHASH_UNXZ_BCJ;
+        for (int i = 2; i + 1 < argc; i++) argv[i] = argv[i + 1];
+        argc--;
+        if (argc < 3) return usage();
+    }
     if (!strcmp(argv[1], "plan")) { /* what the planner would do with these files: no device is touched */
         size_t n = (size_t)argc - 2;
         uint64_t *lens = malloc(n * sizeof *lens);
@@ -243,6 +273,7 @@ int main(int argc, char **argv)
                 if (xo.block_size == 0) bad = 1;
                 argv += 2; argc -= 2;
             } else if (!strcmp(argv[2], "-C") && argc > 5 && (id = xz_check_id(argv[3])) >= 0) { xo.check = (uint32_t)id; argv += 2; argc -= 2; }
+            else if (!strcmp(argv[2], "-F") && argc > 5 && (xo.filter = xz_filter_id(argv[3])) != 0) { argv += 2; argc -= 2; }
             else bad = 1;
             xz_ex = 1;
         }
@@ -277,6 +308,7 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, cmd);
         else {
             if (show_stats && (xo.flags & SNAPHASH_XZ_SELF_CHECK)) print_xz_selfcheck(c, cmd);
+            if (show_stats && xo.filter) print_xz_filter(c, cmd);
             if (show_stats && (bo.flags & SNAPHASH_BZ2_SELF_CHECK)) print_bz2_selfcheck(c, cmd);
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
             FILE *f = fopen(ypath, "wb");
@@ -330,6 +362,7 @@ int main(int argc, char **argv)
         size_t len = 0, zl = 0;
         uint64_t block = 0;
         int have_block = 0, check = -1, self = 0; /* -1: no -C, the entry point that takes no Check */
+        uint32_t filter = 0;
         for (int i = 4; i < argc;) {
             if (!strcmp(argv[i], "-c")) { self = 1; i += 1; continue; }
             if (i + 1 >= argc) { snaphash_destroy(c); return usage(); }
@@ -337,25 +370,28 @@ int main(int argc, char **argv)
                 block = (uint64_t)strtoull(argv[i + 1], NULL, 10) * 1024u;
                 have_block = 1;
             } else if (!strcmp(argv[i], "-C") && xz_check_id(argv[i + 1]) >= 0) check = xz_check_id(argv[i + 1]);
+            else if (!strcmp(argv[i], "-F") && xz_filter_id(argv[i + 1]) != 0) filter = xz_filter_id(argv[i + 1]);
             else { snaphash_destroy(c); return usage(); }
             i += 2;
         }
         snaphash_xz_options xo;
         memset(&xo, 0, sizeof xo);
         xo.struct_size = sizeof xo;
-        xo.flags = SNAPHASH_XZ_SELF_CHECK;
+        xo.flags = self ? SNAPHASH_XZ_SELF_CHECK : 0;
         xo.block_size = block;
         xo.check = check < 0 ? 4u : (uint32_t)check;
+        xo.filter = filter;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *z = NULL;
         rc = (have_block && block == 0) ? SNAPHASH_EINVAL
-             : self                     ? snaphash_xz_buffer_ex(c, in, len, &xo, &z, &zl)
+             : self || filter           ? snaphash_xz_buffer_ex(c, in, len, &xo, &z, &zl)
              : check < 0                ? snaphash_xz_buffer(c, in, len, block, &z, &zl)
                                         : snaphash_xz_buffer_check(c, in, len, block, (uint32_t)check, &z, &zl);
         if (rc) ret = die(c, rc, "xz");
         else {
             if (show_stats && self) print_xz_selfcheck(c, "xz");
+            if (show_stats && filter) print_xz_filter(c, "xz");
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(z, 1, zl, f) != zl || fclose(f)) { perror(argv[3]); ret = 2; }
         }
@@ -368,13 +404,14 @@ int main(int argc, char **argv)
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *o = NULL;
-        rc = xz ? snaphash_unxz_buffer(c, in, len, &o, &ol) : bz ? snaphash_bunzip2_buffer(c, in, len, &o, &ol) : snaphash_gunzip_buffer(c, in, len, &o, &ol);
+        rc = xz && uo.flags ? snaphash_unxz_buffer_ex(c, in, len, &uo, &o, &ol) : xz ? snaphash_unxz_buffer(c, in, len, &o, &ol) : bz ? snaphash_bunzip2_buffer(c, in, len, &o, &ol) : snaphash_gunzip_buffer(c, in, len, &o, &ol);
         if (rc) ret = die(c, rc, argv[1]);
         else {
             FILE *f = fopen(argv[3], "wb");
             if (!f || fwrite(o, 1, ol, f) != ol || fclose(f)) { perror(argv[3]); ret = 2; }
         }
         if (show_stats && !bz && (cfg.flags & SNAPHASH_FLAG_SPLIT_BLOCKS)) print_block_stats(c, argv[1]);
+        if (show_stats && xz && uo.flags && !rc) print_xz_filter(c, argv[1]);
         snaphash_free(o);
         free(in);
     } else if ((!strcmp(argv[1], "unpack") || !strcmp(argv[1], "unpack-bz2") || !strcmp(argv[1], "unpack-xz")) && (argc == 4 || argc == 5)) {
@@ -385,7 +422,8 @@ int main(int argc, char **argv)
         if (argc == 5 && !(y = slurp(argv[4], &len))) { snaphash_destroy(c); return 2; }
         snaphash_mismatch m;
         uint8_t dig[64];
-        rc = xz   ? snaphash_tar_unpack_xz(c, argv[2], argv[3], y, len, &m, dig)
+        rc = xz && uo.flags ? snaphash_tar_unpack_xz_ex(c, argv[2], argv[3], y, len, &uo, &m, dig)
+             : xz ? snaphash_tar_unpack_xz(c, argv[2], argv[3], y, len, &m, dig)
              : bz ? snaphash_tar_unpack_bz2(c, argv[2], argv[3], y, len, &m, dig)
                   : snaphash_tar_unpack(c, argv[2], argv[3], y, len, &m, dig);
         if (rc) ret = die(c, rc, argv[1]);

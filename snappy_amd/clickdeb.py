@@ -12,16 +12,20 @@ helpers.py and hashes.py: the product is the C ABI.
 from .helpers import default_context
 
 
-def tarCreate(tarname, sourceDir, fn=None, ctx=None, self_check=False):
+def tarCreate(tarname, sourceDir, fn=None, ctx=None, self_check=False, filter=None):
     """-> the 64-byte SHA-512 of the archive written (the Go function returns only the error).  self_check (".xz" names
-    only): the producer walks every LZMA2 chunk against the bytes it was made from before it leaves the GPU."""
+    only): the producer walks every LZMA2 chunk against the bytes it was made from before it leaves the GPU.  filter
+    (".xz" names only): a BCJ filter in front of LZMA2 -- "x86", "arm" or "armthumb", what the reference's xz writes when
+    XZ_OPT names one; UnpackXz(..., bcj=True) reads the file back."""
     c = ctx or default_context()
     if str(tarname).endswith(".xz"):
         if fn is not None:
             raise ValueError("tarCreate: the .xz producer takes no exclude function (snaphash_tar_create_xz)")
-        return c.tar_create_xz(tarname, sourceDir, self_check=self_check)[1]
+        return c.tar_create_xz(tarname, sourceDir, self_check=self_check, filter=filter)[1]
     if self_check:
         raise ValueError("tarCreate: self_check is the .xz producer's (ClickDeb.build(check=True) is the .gz producer's)")
+    if filter:
+        raise ValueError("tarCreate: filter is the .xz producer's")
     _, digest = c.tar_create_fn(tarname, sourceDir, fn)  # (any suffix but ".gz": SnaphashError, "unknown compression extension")
     return digest
 
@@ -43,12 +47,13 @@ def UnpackBz2(dataTarBz2, targetDir, hashesYaml=None, ctx=None):
     return mismatch
 
 
-def UnpackXz(dataTarXz, targetDir, hashesYaml=None, ctx=None):
+def UnpackXz(dataTarXz, targetDir, hashesYaml=None, ctx=None, bcj=False):
     """ClickDeb.Unpack of a package whose data member is data.tar.xz (skipToArMember's ".xz" branch, clickdeb/deb.go:
     408-441): the same rules, errors and Verify as Unpack, from the xz-decoded stream.  A filter chain or Check the
-    decoder does not take raises SnaphashError with code EINVAL.
+    decoder does not take raises SnaphashError with code EINVAL.  bcj: Blocks with an x86, ARM or ARM-Thumb filter in front
+    of LZMA2 are taken too (what tarCreate(..., filter=) writes).
     -> None, or (kind, name) of the first mismatch against hashesYaml."""
-    mismatch, _ = (ctx or default_context()).tar_unpack_xz(dataTarXz, targetDir, hashesYaml)
+    mismatch, _ = (ctx or default_context()).tar_unpack_xz(dataTarXz, targetDir, hashesYaml, bcj=bcj)
     return mismatch
 
 

@@ -6,6 +6,7 @@
 #pragma once
 #include <algorithm>
 
+#include "bcj_kernels.h"
 #include "bz2_check_kernels.h"
 #include "bzip2_host.h"
 #include "bzip2_enc_kernels.h"
@@ -264,6 +265,21 @@ struct Sha256Bufs {
     template <class F> void each(F&& f) { ranges.each(f); digests.each(f); }
 };
 
+// The BCJ filters over ranges in HBM (bcj_kernels.hip): the range table (n + 1 entries) built in pinned memory and its HBM twin,
+// and a word a stretch for the x86 restart points
+struct BcjBufs {
+    Twin<BcjRange> ranges;
+    DevBuf<uint32_t> d_points;
+    hipError_t ensure(size_t n, size_t units)
+    {
+        hipError_t e = ranges.ensure(n + 1);
+        if (!e) e = d_points.reserve(std::max<size_t>(units, 1));
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { ranges.each(f); f(d_points); }
+};
+
 // GPU LZMA2 (unxz.inc): the whole .xz file and the Blocks the kernel takes
 struct XzBufs {
     DevBuf<uint8_t> d_in;
@@ -288,6 +304,17 @@ struct XzEncBufs {
     HostBuf<uint8_t> h_out[2]; // double-buffered: the consumers read one while the next slot fills the other
     Twin<uint64_t> zend;       // the self-check's: where every chunk's stretch ends, and the verdicts, a chunk each: sized by
     Twin<Lzma2Verdict> chk;    // the call that asks for the check (xzpack.inc), empty otherwise
+    DevBuf<uint8_t> d_filt;    // a BCJ filter's: the slot's bytes filtered, a byte per staged byte: allocated by the call that
+    Twin<CmpChunk> fcmp;       // asks for a filter; with the self-check too, the range-compare kernel's table and its verdicts,
+    Twin<uint8_t> feq;         // a byte a Block
+    hipError_t ensure_filter(uint64_t slot_bytes) { return d_filt.reserve(slot_bytes + 16); } // (the compare kernel loads 16 bytes at a time)
+    hipError_t ensure_filter_check(uint64_t slot_bytes)
+    {
+        const size_t nblk = (size_t)(slot_bytes / kXzEncChunk + 1); // (a Block is a chunk at least)
+        hipError_t e = fcmp.ensure((size_t)(slot_bytes / kCmpChunk) + nblk);
+        if (!e) e = feq.ensure(nblk);
+        return e;
+    }
     hipError_t ensure_check(uint64_t slot_bytes)
     {
         const size_t nch = std::max<size_t>((size_t)((slot_bytes + kXzEncChunk - 1) / kXzEncChunk), 1);
@@ -313,7 +340,7 @@ struct XzEncBufs {
         if (e) each(Release()); // (none of it is left behind)
         return e;
     }
-    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); zend.each(f); chk.each(f); }
+    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); zend.each(f); chk.each(f); f(d_filt); fcmp.each(f); feq.each(f); }
 };
 
 // GPU bzip2 encoder (bzpack.inc), for `blocks` blocks a launch of up to `cap` bytes each after RLE1: the sort's scratch

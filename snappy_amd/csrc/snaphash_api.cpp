@@ -98,6 +98,9 @@ struct DevCtx {
     Bzip2Bufs bz;
     CrcBufs crc;
     Sha256Bufs sha256;
+    BcjBufs bcj; // the BCJ filter kernels' (both sides of .xz)
+    EventPair bcj_ev;               // around the install side's filter launch (unxz.inc; the pool's pairs are reused by the Check calls behind it)
+    hipStream_t bcj_busy = nullptr; // the stream that last read bcj's pinned table (bcj_ranges_dev waits for it before a rewrite)
     XzBufs xz;
     XzEncBufs xe; // the .xz producer's (xzpack.inc)
     BzEncBufs be; // the .bz2 producer's (bzpack.inc)
@@ -138,6 +141,7 @@ struct DevCtx {
         bz.each(f);
         crc.each(f);
         sha256.each(f);
+        bcj.each(f);
         xz.each(f);
         xe.each(f);
         be.each(f);
@@ -181,6 +185,8 @@ struct snaphash_ctx {
     snaphash_unpack_stats unpack{};
     snaphash_xz_check_stats xz_check{}; // of the most recent .xz decode (unxz.inc)
     snaphash_xz_selfcheck_stats xz_selfcheck{}; // of the most recent snaphash_xz_buffer_ex / snaphash_tar_create_xz_ex (xzpack.inc)
+    snaphash_xz_filter_stats xz_filter{}; // of the most recent .xz call of either side that knows filters (xzpack.inc, unxz.inc)
+    bool unxz_bcj = false; // SNAPHASH_UNXZ_BCJ of the _ex decode in progress (unxz.inc)
     snaphash_bz2_selfcheck_stats bz2_selfcheck{}; // of the most recent snaphash_bzip2_buffer_ex / snaphash_tar_create_bz2_ex (bzpack.inc)
     snaphash_block_scan_stats block_scan{};
     std::string last_error;
@@ -1164,6 +1170,8 @@ static void destroy_dev(DevCtx* c)
     for (hipEvent_t e : c->z_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->z_part_ev) (void)hipEventDestroy(e);
     for (EventPair& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
+    if (c->bcj_ev.a) (void)hipEventDestroy(c->bcj_ev.a);
+    if (c->bcj_ev.b) (void)hipEventDestroy(c->bcj_ev.b);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
@@ -2472,9 +2480,75 @@ int sha256_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, co
     return SNAPHASH_OK;
 }
 
+// A BCJ filter over n ranges of d_base, each a Block of its own, in place, queued on stream s and NOT waited for: r[i]'s off,
+// len, filter, start and encode as the caller set them (unit0 is filled in here).  *ev: the pair of events around the
+// kernels, for the caller to read once it has waited for s.  The table lies in c->bcj until the stream has passed it: a
+// second call before that waits for s first.
+int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStream_t s, EventPair* ev)
+{
+    const size_t n = r.size();
+    if (n == 0) return SNAPHASH_OK;
+    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
+    uint64_t units = 0;
+    bool any_x86 = false;
+    for (size_t i = 0; i < n; ++i) {
+        if (r[i].len > ~0ull - r[i].off) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
+        if (!bcj_filter_valid(r[i].filter) || (r[i].start & (bcj_alignment(r[i].filter) - 1))) return fail(c, SNAPHASH_EINVAL, "bcj: the filter is 4 (x86), 7 (ARM) or 8 (ARM-Thumb), its start_offset a multiple of 1, 4 or 2");
+        r[i].unit0 = (uint32_t)units;
+        units += (r[i].len + kBcjStretch - 1) / kBcjStretch;
+        if (units > (1ull << 32) - 1) return fail(c, SNAPHASH_EINVAL, "bcj: more than 2^40 bytes in one call");
+        any_x86 |= r[i].filter == kBcjX86;
+    }
+    if (c->bcj_busy) HIP_TRY(c, hipStreamSynchronize(c->bcj_busy));
+    HIP_TRY(c, c->bcj.ensure(n, (size_t)units));
+    BcjRange* h = c->bcj.ranges.h.data();
+    memcpy(h, r.data(), n * sizeof(BcjRange));
+    h[n] = BcjRange{0, 0, (uint32_t)units, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(c->bcj.ranges.d.data(), h, (n + 1) * sizeof(BcjRange), hipMemcpyHostToDevice, s));
+    c->bcj_busy = s;
+    if (ev) HIP_TRY(c, hipEventRecord(ev->a, s));
+    HIP_TRY(c, launch_bcj_ranges(d_base, c->bcj.ranges.d.data(), (uint32_t)n, (uint32_t)units, c->bcj.d_points.data(), any_x86, s));
+    if (ev) HIP_TRY(c, hipEventRecord(ev->b, s));
+    return SNAPHASH_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int snaphash_bcj_device(snaphash_ctx* x, uint32_t filter, int encode, void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                        uint32_t start_offset)
+try {
+    if (!x || (n && (!d_base || !offsets || !lens))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (!bcj_filter_valid(filter) || (start_offset & (bcj_alignment(filter) - 1)))
+        return fail(x, SNAPHASH_EINVAL, "bcj: the filter is 4 (x86), 7 (ARM) or 8 (ARM-Thumb), its start_offset a multiple of 1, 4 or 2");
+    TOP_ENTER(x);
+    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<BcjRange> r(n);
+    bool any_x86 = false;
+    for (size_t i = 0; i < n; ++i) {
+        r[i] = BcjRange{offsets[i], lens[i], 0, filter, start_offset, encode ? 1u : 0u};
+        any_x86 |= lens[i] != 0 && filter == kBcjX86;
+    }
+    EventPair* ev = next_events(c, 2);
+    if (!ev) return fail(x, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    int rc = bcj_ranges_dev(c, (uint8_t*)d_base, r, c->stream, ev);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    c->ev_used = 0;
+    if (rc) return lift(x, c, rc);
+    HIP_TRY(c, e);
+    float ms = 0;
+    bool ran = false;
+    for (size_t i = 0; i < n; ++i) ran |= lens[i] != 0;
+    if (ran) (void)hipEventElapsedTime(&ms, ev->a, ev->b);
+    x->stats.kernel_ms = ms;
+    x->stats.launches = ran ? (any_x86 ? 2 : 1) : 0;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
 
 int snaphash_sha256_device(snaphash_ctx* x, const void* d_base, const uint64_t* offsets, const uint64_t* lens, size_t n, uint8_t* digests)
 try {

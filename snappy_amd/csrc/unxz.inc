@@ -6,7 +6,9 @@
 // go (xz_core.h xz_plan), so the Blocks are decoded side by side, each straight to its final offset -- on host threads
 // in the default configuration (xz_host.cpp), by lzma2_blocks_kernel (xz_kernels.hip) under SNAPHASH_FLAG_GPU_ONLY, where
 // the CRC-32, CRC-64 and SHA-256 Checks are taken in HBM right after the decode (crc_kernels.hip, sha256_kernels.hip) -- and
-// the decoded stream goes through the same unpack and in-pass Verify as data.tar.gz.
+// the decoded stream goes through the same unpack and in-pass Verify as data.tar.gz.  The _ex entries' SNAPHASH_UNXZ_BCJ
+// also takes Blocks with an x86, ARM or ARM-Thumb filter in front of LZMA2 (DESIGN.md sec. 25): the filter is undone behind
+// the Block's decode and in front of its Check, by the Block's host thread or by bcj_kernels.hip over what the kernel decoded.
 
 namespace {
 
@@ -19,9 +21,18 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
     std::vector<XzBlock> blocks;
     uint64_t total = 0;
     std::string why;
-    const int pe = xz_plan(xz, n, blocks, &total, why);
+    x->xz_filter = snaphash_xz_filter_stats{};
+    const int pe = xz_plan(xz, n, blocks, &total, why, x->unxz_bcj); // (the _ex entries' SNAPHASH_UNXZ_BCJ: a BCJ filter a Block)
     if (pe) return fail(c, pe == kXzPlanUnsupported ? SNAPHASH_EINVAL : SNAPHASH_EFORMAT, why);
     c->fout_gen++;
+    snaphash_xz_filter_stats& fs = x->xz_filter; // who undid the Blocks' filters
+    auto host_filtered = [&](const std::vector<uint32_t>* which) {
+        const size_t K = which ? which->size() : blocks.size();
+        for (size_t k = 0; k < K; ++k) {
+            const XzBlock& b = blocks[which ? (*which)[k] : k];
+            if (b.bcj) { fs.host_blocks++; fs.filter = b.bcj; }
+        }
+    };
     snaphash_xz_check_stats& ck = x->xz_check; // who took the Checks of this decode
     ck = snaphash_xz_check_stats{};
     ck.struct_size = sizeof ck;
@@ -45,6 +56,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
         }
         st.host_bytes += total;
         host_checked(nullptr);
+        host_filtered(nullptr);
         return ds.mirror(o0, o0 + total);
     }
     // SNAPHASH_FLAG_GPU_ONLY: every Block up to kXzGpuBlockMax through the kernel, the rest (and what the kernel refuses) on
@@ -81,6 +93,23 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             if (blocks[gpu[k]].check == kXzCheckCrc32) k32.push_back(gpu[k]);
             if (blocks[gpu[k]].check == kXzCheckCrc64) k64.push_back(gpu[k]);
             if (blocks[gpu[k]].check == kXzCheckSha256) k256.push_back(gpu[k]);
+        }
+        // the filters of what the kernel decoded, undone in HBM in one launch of the BCJ kernels, a range a Block: in front of
+        // the Checks, which are over the unfiltered bytes, and of the copies back
+        std::vector<BcjRange> fr;
+        for (uint32_t i : ok)
+            if (blocks[i].bcj) {
+                fr.push_back(BcjRange{base + blocks[i].out_off, blocks[i].out_len, 0, blocks[i].bcj, blocks[i].bcj_start, 0});
+                fs.filter = blocks[i].bcj;
+            }
+        EventPair fev{};
+        if (!fr.empty()) {
+            if ((!c->bcj_ev.a && hipEventCreate(&c->bcj_ev.a) != hipSuccess) || (!c->bcj_ev.b && hipEventCreate(&c->bcj_ev.b) != hipSuccess))
+                return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            fev = c->bcj_ev;
+            rc = bcj_ranges_dev(c, c->inf.d_out.data(), fr, c->f_stream, &fev);
+            if (rc) return rc;
+            fs.device_blocks = fr.size();
         }
         // the bytes of the Blocks the kernel decoded on their way back (neighbours in one copy), beside the Check kernels;
         // what a host thread will decode is not moved
@@ -127,6 +156,12 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
         }
         HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the Check calls waited on the same stream, but there may be none)
         st.inflate_ms += cms;
+        if (!fr.empty()) {
+            float fms = 0;
+            (void)hipEventElapsedTime(&fms, fev.a, fev.b);
+            fs.device_ms = fms;
+            st.inflate_ms += fms;
+        }
         ck.device_crc32 = k32.size();
         ck.device_crc64 = k64.size();
         ck.device_sha256 = k256.size();
@@ -143,6 +178,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             return fail(c, SNAPHASH_EFORMAT, "xz: corrupt block");
         }
         host_checked(&host);
+        host_filtered(&host);
         for (uint32_t i : host) {
             st.host_bytes += blocks[i].out_len;
             rc = ds.mirror_async(o0 + blocks[i].out_off, o0 + blocks[i].out_off + blocks[i].out_len);
@@ -155,6 +191,22 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
 }
 
 const UnpackCodec kUnxzCodec = {"xz", unxz_engine};
+
+// What an _ex entry was asked for, for the length of its call: unxz_engine reads x->unxz_bcj (a codec's decoder takes no
+// options of its own).  opt == nullptr or all zero: the plain entries' behaviour.
+struct UnxzCall {
+    snaphash_ctx* const x;
+    explicit UnxzCall(snaphash_ctx* x_) : x(x_) {}
+    ~UnxzCall() { x->unxz_bcj = false; }
+    int read(const snaphash_unxz_options* opt)
+    {
+        if (!opt || (opt->struct_size == 0 && opt->flags == 0)) return SNAPHASH_OK;
+        if (opt->struct_size < sizeof(snaphash_unxz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_unxz_options.struct_size");
+        if (opt->flags & ~(uint32_t)SNAPHASH_UNXZ_BCJ) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
+        x->unxz_bcj = (opt->flags & SNAPHASH_UNXZ_BCJ) != 0;
+        return SNAPHASH_OK;
+    }
+};
 
 } // namespace
 
@@ -169,6 +221,31 @@ int snaphash_tar_unpack_xz(snaphash_ctx* x, const char* data_tar_xz, const char*
                            snaphash_mismatch* first, uint8_t* archive_digest)
 {
     return tar_unpack_entry(x, kUnxzCodec, data_tar_xz, target_dir, yaml, yaml_len, first, archive_digest);
+}
+
+int snaphash_unxz_buffer_ex(snaphash_ctx* x, const void* xz, size_t n, const snaphash_unxz_options* opt, void** out, size_t* out_len)
+{
+    if (!x) return SNAPHASH_EINVAL;
+    UnxzCall call(x);
+    if (int rc = call.read(opt)) return rc;
+    return decode_to_malloc(x, kUnxzCodec, xz, n, out, out_len);
+}
+
+int snaphash_tar_unpack_xz_ex(snaphash_ctx* x, const char* data_tar_xz, const char* target_dir, const char* yaml, size_t yaml_len,
+                              const snaphash_unxz_options* opt, snaphash_mismatch* first, uint8_t* archive_digest)
+{
+    if (!x) return SNAPHASH_EINVAL;
+    UnxzCall call(x);
+    if (int rc = call.read(opt)) return rc;
+    return tar_unpack_entry(x, kUnxzCodec, data_tar_xz, target_dir, yaml, yaml_len, first, archive_digest);
+}
+
+int snaphash_get_xz_filter_stats(const snaphash_ctx* x, snaphash_xz_filter_stats* out)
+{
+    if (!x || !out || out->struct_size < sizeof(snaphash_xz_filter_stats)) return SNAPHASH_EINVAL;
+    *out = x->xz_filter;
+    out->struct_size = sizeof(snaphash_xz_filter_stats);
+    return SNAPHASH_OK;
 }
 
 int snaphash_get_xz_check_stats(const snaphash_ctx* x, snaphash_xz_check_stats* out)

@@ -38,6 +38,8 @@
 #include <string>
 #include <vector>
 
+#include "bcj_core.h"
+
 namespace snaphash {
 
 // ---- LZMA ------------------------------------------------------------------------------------------------------------
@@ -426,6 +428,8 @@ struct XzBlock {
     uint64_t check_off = 0; // the Check field, in the file
     uint32_t check = 0;     // its id
     uint32_t dict_size = 0;
+    uint32_t bcj = 0;       // the BCJ filter in front of LZMA2 (kBcjX86 / kBcjArm / kBcjThumb), 0: none; only xz_plan(allow_bcj)
+    uint32_t bcj_start = 0; // sets it, with the filter's start_offset
 };
 
 inline uint32_t xz_check_size(uint32_t id) { return id == 0 ? 0 : id <= 3 ? 4 : id <= 6 ? 8 : id <= 9 ? 16 : id <= 12 ? 32 : 64; }
@@ -467,9 +471,11 @@ inline bool xz_vli(const uint8_t* p, uint64_t* at, uint64_t end, uint64_t* v)
 inline uint32_t xz_dict_size(uint32_t b) { return b == 40 ? 0xffffffffu : (2u | (b & 1)) << (b / 2 + 11); }
 
 // A Block header at p[at ..): its size, the sizes it states (or ~0), the dictionary size.  kXzPlanUnsupported with *why
-// for a filter chain other than one LZMA2.
+// for a filter chain other than one LZMA2 -- or, with allow_bcj, other than one LZMA2 or one BCJ filter (x86, ARM, Thumb)
+// in front of one LZMA2: *bcj / *bcj_start then say which (0: none).  Such a filter's properties are 0 bytes or 4 (its
+// start_offset, a multiple of the filter's alignment); liblzma refuses anything else, and so does this: kXzPlanFormat.
 inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t* hdr, uint64_t* csize, uint64_t* usize, uint32_t* dict,
-                           std::string& why)
+                           std::string& why, bool allow_bcj = false, uint32_t* bcj = nullptr, uint32_t* bcj_start = nullptr)
 {
     if (at >= end || p[at] == 0) return kXzPlanFormat;
     const uint64_t hs = ((uint64_t)p[at] + 1) * 4;
@@ -490,11 +496,15 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     bool unsupported = false;
     uint64_t bad_id = 0; // the first filter of the chain that is not LZMA2
     uint32_t dict_byte = 0;
+    uint32_t others = 0; // the filters that are not LZMA2
+    uint64_t first_id = 0, first_ps = 0, first_at = 0;
     for (uint32_t f = 0; f < nf; ++f) {
         uint64_t id, ps;
         if (!xz_vli(p, &q, he, &id) || !xz_vli(p, &q, he, &ps) || ps > he - q) return kXzPlanFormat;
         if (id >= (1ull << 62)) return kXzPlanFormat;
         if (id != 0x21 && !unsupported) { unsupported = true; bad_id = id; }
+        others += id != 0x21;
+        if (f == 0) { first_id = id; first_ps = ps; first_at = q; }
         if (id == 0x21) {
             if (f + 1 != nf || ps != 1) return kXzPlanFormat; // LZMA2 is the last filter and has one byte of properties
             dict_byte = p[q];
@@ -504,6 +514,16 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     }
     for (; q < he; ++q)
         if (p[q]) return kXzPlanFormat;
+    if (bcj) *bcj = *bcj_start = 0;
+    if (unsupported && allow_bcj && bcj && nf == 2 && others == 1 && bcj_filter_valid((uint32_t)first_id)) {
+        // (the second is LZMA2: it is not among `others`)
+        if (first_ps != 0 && first_ps != 4) return kXzPlanFormat;
+        const uint32_t start = first_ps ? xz_le32(p + first_at) : 0;
+        if (start & (bcj_alignment((uint32_t)first_id) - 1)) return kXzPlanFormat;
+        *bcj = (uint32_t)first_id;
+        *bcj_start = start;
+        unsupported = false;
+    }
     if (unsupported) { // (the first one is named: one is enough to hand the file back)
         char b[64];
         snprintf(b, sizeof b, "xz: unsupported filter 0x%02llX", (unsigned long long)bad_id);
@@ -515,8 +535,8 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     return kXzPlanOk;
 }
 
-// Every Block of every Stream of p[0 .. n), in order, and the length of the whole result.
-inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, uint64_t* total, std::string& why)
+// Every Block of every Stream of p[0 .. n), in order, and the length of the whole result.  allow_bcj: as in xz_block_header.
+inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, uint64_t* total, std::string& why, bool allow_bcj = false)
 {
     blocks.clear();
     *total = 0;
@@ -585,7 +605,8 @@ inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, u
         for (const Rec& r : s.recs) {
             uint64_t hdr = 0, hc = 0, hu = 0;
             uint32_t dict = 0;
-            const int e = xz_block_header(p, at, s.index_at, &hdr, &hc, &hu, &dict, why);
+            uint32_t bcj = 0, bcj_start = 0;
+            const int e = xz_block_header(p, at, s.index_at, &hdr, &hc, &hu, &dict, why, allow_bcj, &bcj, &bcj_start);
             if (e) return e;
             if (r.unpadded < hdr + csz + 1) return kXzPlanFormat;
             XzBlock b;
@@ -595,6 +616,8 @@ inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, u
             b.out_len = r.usize;
             b.check = s.check;
             b.dict_size = dict;
+            b.bcj = bcj;
+            b.bcj_start = bcj_start;
             if (hc != ~0ull && hc != b.in_len) return kXzPlanFormat;
             if (hu != ~0ull && hu != b.out_len) return kXzPlanFormat;
             // a chunk yields at most 2 MiB and costs at least 6 bytes: a lying Index must not drive an allocation

@@ -458,13 +458,18 @@ inline void xzenc_stream_header(uint8_t* p, uint32_t check = kXzCheckCrc64)
     p[7] = (uint8_t)check;
     xzenc_le32(p + 8, xz_crc32(p + 6, 2));
 }
-// a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size
-inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, uint32_t dict_byte)
+// a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size.  filter: a BCJ filter in
+// front of LZMA2 (bcj_core.h's ids; 0: none), named without properties: its start_offset is 0
+inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, uint32_t dict_byte, uint32_t filter = 0)
 {
     uint32_t n = 2;
-    p[1] = 0xC0; // one filter; compressed and uncompressed size present
+    p[1] = (uint8_t)(0xC0 | (filter ? 1 : 0)); // one filter or two; compressed and uncompressed size present
     n += xzenc_vli(p + n, csize);
     n += xzenc_vli(p + n, usize);
+    if (filter) {
+        p[n++] = (uint8_t)filter;
+        p[n++] = 0x00;
+    }
     p[n++] = 0x21;
     p[n++] = 0x01;
     p[n++] = (uint8_t)dict_byte;
@@ -473,11 +478,13 @@ inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, u
     xzenc_le32(p + n, xz_crc32(p, n));
     return n + 4;
 }
-inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize)
+inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize, uint32_t filter = 0)
 {
     uint8_t t[kXzEncBlockHeaderMax];
-    return xzenc_block_header(t, csize, usize, 0);
+    return xzenc_block_header(t, csize, usize, 0, filter);
 }
+// the filters this side writes in front of LZMA2 (0: none)
+inline bool xzenc_filter_valid(uint32_t filter) { return filter == 0 || bcj_filter_valid(filter); }
 struct XzEncRecord { uint64_t unpadded, usize; };
 // the Index and the Stream footer behind the last Block
 inline void xzenc_index_footer(const std::vector<XzEncRecord>& recs, std::vector<uint8_t>& out, uint32_t check = kXzCheckCrc64)
@@ -512,7 +519,8 @@ struct XzEncBlockLayout {
     uint64_t total = 0;     // header, data, padding, Check
     uint64_t unpadded = 0;  // the Index record's
 };
-inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst, uint32_t check = kXzCheckCrc64)
+inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst, uint32_t check = kXzCheckCrc64,
+                                           uint32_t filter = 0)
 {
     const uint32_t check_size = xzenc_check_size(check);
     XzEncBlockLayout L;
@@ -523,7 +531,7 @@ inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, ui
         data += xzenc_chunk_bytes(usize, res[k]);
     }
     L.data = data + 1;
-    L.hdr = xzenc_block_header_size(L.data, blen);
+    L.hdr = xzenc_block_header_size(L.data, blen, filter);
     for (uint32_t k = 0; k < nch; ++k) dst[k] += L.hdr;
     L.unpadded = L.hdr + L.data + check_size;
     L.check_at = (L.hdr + L.data + 3) & ~3ull;
@@ -558,7 +566,8 @@ struct XzEncInfo {
 // output, nothing else written).  head: 1 << kXzEncHashBits entries of scratch; probs: kXzEncProbs.
 template <class OPS>
 inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* cand, uint32_t* head, uint16_t* probs,
-                                           uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops, uint32_t check = kXzCheckCrc64)
+                                           uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops, uint32_t check = kXzCheckCrc64,
+                                           uint32_t filter = 0)
 {
     const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
     xzenc_chains_host(blk, blen, prev, head);
@@ -568,7 +577,7 @@ inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, ui
         for (uint32_t i = 0; i < kXzEncProbs; ++i) probs[i] = (uint16_t)kLzmaProbInit;
         res[k] = xzenc_chunk(blk, cs, ce, cand, probs, slots + (size_t)k * kXzEncSlot, kXzEncSlot, ops);
     }
-    return xzenc_block_layout(res, nch, blen, dst, check);
+    return xzenc_block_layout(res, nch, blen, dst, check, filter);
 }
 // what lzma2_concat_kernel writes of a Block that begins at q: chunk headers, bodies and the end byte
 inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t* res, const uint64_t* dst, const uint8_t* slots, uint8_t* q)
@@ -583,9 +592,10 @@ inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t*
     }
 }
 // what the host writes of a Block that begins at q: header, Block Padding, Check (CRC-64, or any Check's field as bytes)
-inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, const uint8_t* field, uint32_t check_size)
+inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, const uint8_t* field, uint32_t check_size,
+                              uint32_t filter = 0)
 {
-    xzenc_block_header(q, L.data, blen, dict_byte);
+    xzenc_block_header(q, L.data, blen, dict_byte, filter);
     for (uint64_t z = L.hdr + L.data; z < L.check_at; ++z) q[z] = 0;
     if (check_size) memcpy(q + L.check_at, field, check_size);
 }
@@ -598,12 +608,14 @@ inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t bl
 
 // The whole file on this thread, through the routines the kernels run, with Check `check` (xzenc_check_valid).
 // field(p, len, out): the Check of a Block's bytes, xzenc_check_size(check) bytes as the file holds them.  false: the
-// block size or the Check is not one the format decisions allow.
+// block size, the Check or the filter is not one the format decisions allow.  filter: a BCJ filter in front of LZMA2 (0:
+// none): every Block is filtered as the kernels filter it (a copy, positions from the Block's first byte) and the steps run
+// over the copy; the Check is over the unfiltered bytes.
 template <class OPS, class FIELD>
 inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uint32_t check, std::vector<uint8_t>& out, OPS& ops, FIELD field,
-                       XzEncInfo* info = nullptr)
+                       XzEncInfo* info = nullptr, uint32_t filter = 0)
 {
-    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check)) return false;
+    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check) || !xzenc_filter_valid(filter)) return false;
     const uint32_t dict_byte = xzenc_dict_byte(block_size), check_size = xzenc_check_size(check);
     out.resize(kXzEncStreamHeader);
     xzenc_stream_header(out.data(), check);
@@ -611,10 +623,16 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uin
     std::vector<uint32_t> prev, cand, head(1u << kXzEncHashBits), res;
     std::vector<uint64_t> dst;
     std::vector<uint16_t> probs(kXzEncProbs);
-    std::vector<uint8_t> slots;
+    std::vector<uint8_t> slots, filtered;
     for (uint64_t b0 = 0; b0 < n; b0 += block_size) {
-        const uint8_t* blk = data + b0;
+        const uint8_t* const raw = data + b0;
+        const uint8_t* blk = raw;
         const uint32_t blen = (uint32_t)std::min<uint64_t>(block_size, n - b0);
+        if (filter) {
+            filtered.assign(raw, raw + blen);
+            bcj_block(filter, true, filtered.data(), blen, 0);
+            blk = filtered.data();
+        }
         const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
         prev.resize(blen);
         cand.resize(blen);
@@ -622,7 +640,7 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uin
         dst.resize(nch);
         slots.resize((size_t)nch * kXzEncSlot);
         const XzEncBlockLayout L = xzenc_block_stages(blk, blen, prev.data(), cand.data(), head.data(), probs.data(), res.data(), dst.data(),
-                                                      slots.data(), ops, check);
+                                                      slots.data(), ops, check, filter);
         if (info)
             for (uint32_t k = 0; k < nch; ++k) {
                 info->chunks++;
@@ -632,8 +650,8 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uin
         const size_t o = out.size();
         out.resize(o + L.total, 0);
         uint8_t f[kXzEncCheckMax] = {0};
-        field(blk, (uint64_t)blen, f);
-        xzenc_block_frame(out.data() + o, L, blen, dict_byte, f, check_size);
+        field(raw, (uint64_t)blen, f);
+        xzenc_block_frame(out.data() + o, L, blen, dict_byte, f, check_size, filter);
         xzenc_block_place(blk, blen, res.data(), dst.data(), slots.data(), out.data() + o);
         recs.push_back(XzEncRecord{L.unpadded, blen});
     }

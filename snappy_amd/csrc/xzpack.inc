@@ -10,7 +10,8 @@
 // none -- come from the kernels the install side uses (crc_kernels.hip, sha256_kernels.hip), over the staged bytes in HBM.
 // The host writes what is left: Block headers, padding, Checks, the Index and the footer.  A Block never spans two staging
 // slots; a slot's last Block may be short.  The file is one the library's own install side (unxz.inc) decodes a Block a
-// thread or a Block a workgroup.
+// thread or a Block a workgroup.  With snaphash_xz_options.filter the LZMA2 kernels read a copy of the slot that
+// bcj_kernels.hip has filtered in place, a range a Block (DESIGN.md sec. 25); everything else reads the staged bytes.
 
 namespace {
 
@@ -32,8 +33,11 @@ struct XzEncoder final : Encoder {
     const uint32_t check;
     std::vector<XzEncRecord> recs;
     XzSelfCheck* const self_check; // null = off, the producer's path without it
-    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr)
-        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc)
+    const uint32_t filter;         // a BCJ filter in front of LZMA2 (DESIGN.md sec. 25), 0 = none, the producer's path without it
+    uint64_t filt_blocks = 0;      // Blocks the BCJ kernels filtered
+    double filt_ms = 0;            // the BCJ kernels' own time, HIP events
+    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr, uint32_t flt = 0)
+        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc), filter(flt)
     {
         if (sc) check_ms = &sc->ms;
     }
@@ -48,6 +52,8 @@ struct XzEncoder final : Encoder {
         if (rc) return rc;
         HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
         if (self_check) HIP_TRY(c, c->xe.ensure_check(slot_bytes));
+        if (filter) HIP_TRY(c, c->xe.ensure_filter(slot_bytes));
+        if (filter && self_check) HIP_TRY(c, c->xe.ensure_filter_check(slot_bytes));
         return SNAPHASH_OK;
     }
     void begin(OutPipe& g) override
@@ -68,9 +74,11 @@ struct XzEncoder final : Encoder {
 // The self-check of a slot, behind lzma2_concat_kernel on the compressor's stream: the chunks' stretches of b.d_out[0 .. total)
 // against the slot's staged bytes.  A stretch begins where the host placed the chunk (b.dst) and ends where the host's
 // Block layouts say -- the next chunk's place, or the end of the Block's LZMA2 data -- not where the chunk's own header says.
-// at[k]: where Block k begins in b.d_out.  Waits for the verdicts; a refused chunk fails the call.
-int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, const std::vector<XzEncBlockLayout>& lay, const std::vector<uint64_t>& at,
-                       uint64_t total)
+// at[k]: where Block k begins in b.d_out.  Waits for the verdicts; a refused chunk fails the call.  src: the bytes the chunks
+// were made from -- the slot's staged bytes, or with a BCJ filter their filtered copy, whose filter is then undone in place
+// and the result compared with the staged bytes by the range-compare kernel, a pair a Block.
+int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, uint64_t n, const std::vector<XzEncBlockLayout>& lay,
+                       const std::vector<uint64_t>& at, uint64_t total)
 {
     DevCtx* c = g.c;
     XzEncBufs& b = c->xe;
@@ -91,7 +99,7 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, const std
         if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
         const EventPair ev = *e;
         HIP_TRY(c, hipEventRecord(ev.a, zs));
-        HIP_TRY(c, launch_lzma2_check(sl.d_buf.data(), n, bs, b.d_out.data(), total, b.dst.d.data(), b.zend.d.data(), c0,
+        HIP_TRY(c, launch_lzma2_check(src, n, bs, b.d_out.data(), total, b.dst.d.data(), b.zend.d.data(), c0,
                                       std::min(kLzCheckLaunchChunks, nch - c0), nch, b.chk.d.data(), zs));
         HIP_TRY(c, hipEventRecord(ev.b, zs));
     }
@@ -105,6 +113,48 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, const std
         // name the wrong Block or chunk)
         return fail(c, SNAPHASH_EDEVICE, lzma2_check_error_text(sc.member, z.recs.size() + i / cpb, g.st.chunks + i, v.status,
                                                                sc.bytes + (uint64_t)i * kXzEncChunk + v.offset));
+    }
+    if (z.filter) {
+        const uint32_t nblk = (uint32_t)lay.size();
+        std::vector<BcjRange> fr(nblk);
+        size_t nc = 0;
+        for (uint32_t k = 0; k < nblk; ++k) {
+            const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
+            fr[k] = BcjRange{b0, blen, 0, z.filter, 0, 0};
+            for (uint64_t off = 0; off < blen; off += kCmpChunk) {
+                if (nc >= b.fcmp.size()) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
+                b.fcmp.h[nc++] = CmpChunk{(uint64_t)(uintptr_t)(b.d_filt.data() + b0 + off), (uint64_t)(uintptr_t)(sl.d_buf.data() + b0 + off),
+                                          (uint32_t)std::min<uint64_t>(kCmpChunk, blen - off), k};
+            }
+        }
+        if (b.feq.size() < nblk) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
+        EventPair* e = next_events(c, 3);
+        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        EventPair fev = *e;
+        const int rc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemsetAsync(b.feq.d.data(), 1, nblk, zs)); // equal until a chunk says otherwise
+        HIP_TRY(c, hipMemcpyAsync(b.fcmp.d.data(), b.fcmp.h.data(), nc * sizeof(CmpChunk), hipMemcpyHostToDevice, zs));
+        HIP_TRY(c, launch_compare(b.fcmp.d.data(), (uint32_t)nc, b.feq.d.data(), zs));
+        HIP_TRY(c, hipMemcpyAsync(b.feq.h.data(), b.feq.d.data(), nblk, hipMemcpyDeviceToHost, zs));
+        HIP_TRY(c, hipStreamSynchronize(zs));
+        float fms = 0;
+        (void)hipEventElapsedTime(&fms, fev.a, fev.b);
+        z.filt_ms += fms;
+        for (uint32_t k = 0; k < nblk; ++k) {
+            if (b.feq.h[k]) continue;
+            // where: the Block's two sides read back (the failing path alone pays for it)
+            const uint64_t b0 = (uint64_t)k * bs, blen = fr[k].len;
+            std::vector<uint8_t> u(blen), v(blen);
+            HIP_TRY(c, hipMemcpy(u.data(), b.d_filt.data() + b0, blen, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(v.data(), sl.d_buf.data() + b0, blen, hipMemcpyDeviceToHost));
+            uint64_t off = 0;
+            while (off < blen && u[off] == v[off]) ++off;
+            char t[256];
+            snprintf(t, sizeof t, "xz self-check: %s: Block %llu: the filter undone differs from the staged bytes at offset %llu of the stream", sc.member,
+                     (unsigned long long)(z.recs.size() + k), (unsigned long long)(sc.bytes + b0 + off));
+            return fail(c, SNAPHASH_EDEVICE, t);
+        }
     }
     sc.chunks += nch;
     sc.bytes += n;
@@ -125,11 +175,28 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     if (n > sl.cap() || b.d_prev.size() < n || b.res.size() < nch || b.cap() < XzEncBufs::out_cap(n))
         return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
     if (ready) HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0));
+    // with a BCJ filter: the slot's bytes once more, filtered in place, a range a Block (positions from the Block's first byte);
+    // the LZMA2 kernels read the copy, the Checks below the staged bytes
+    const uint8_t* src = sl.d_buf.data();
+    EventPair fev{};
+    if (z.filter) {
+        if (b.d_filt.size() < n) return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
+        HIP_TRY(c, hipMemcpyAsync(b.d_filt.data(), sl.d_buf.data(), n, hipMemcpyDeviceToDevice, zs));
+        std::vector<BcjRange> fr(nblk);
+        for (uint32_t k = 0; k < nblk; ++k) fr[k] = BcjRange{(uint64_t)k * bs, std::min<uint64_t>(bs, n - (uint64_t)k * bs), 0, z.filter, 0, 1};
+        EventPair* e = next_events(c, 2);
+        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+        fev = *e;
+        const int frc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        if (frc) return frc;
+        src = b.d_filt.data();
+        z.filt_blocks += nblk;
+    }
     EventPair* evp = next_events(c, 2);
     if (!evp) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     const EventPair ev = *evp; // (by value: the pool may grow)
     HIP_TRY(c, hipEventRecord(ev.a, zs));
-    HIP_TRY(c, launch_lzma_chains(sl.d_buf.data(), n, (uint32_t)bs, b.d_prev.data(), zs));
+    HIP_TRY(c, launch_lzma_chains(src, n, (uint32_t)bs, b.d_prev.data(), zs));
     HIP_TRY(c, hipEventRecord(ev.b, zs));
     // a launch codes what is resident at once, no more: a longer slot goes in several launches (each with its own pair of
     // events: the longest single launch is what DESIGN.md sec. 18 holds against sec. 17's one-second bound)
@@ -139,7 +206,7 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
         if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
         evl.push_back(*e);
         HIP_TRY(c, hipEventRecord(evl.back().a, zs));
-        HIP_TRY(c, launch_lzma2_chunks(sl.d_buf.data(), n, (uint32_t)bs, b.d_prev.data(), b.d_cand.data(), b.d_slots.data(), b.res.d.data(), c0,
+        HIP_TRY(c, launch_lzma2_chunks(src, n, (uint32_t)bs, b.d_prev.data(), b.d_cand.data(), b.d_slots.data(), b.res.d.data(), c0,
                                        std::min(kXzEncLaunchChunks, nch - c0), zs));
         HIP_TRY(c, hipEventRecord(evl.back().b, zs));
     }
@@ -159,7 +226,7 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
             if (!xzenc_res_valid(usize, b.res.h[ch0 + i])) return fail(c, SNAPHASH_EDEVICE, "xz: the chunk kernel reported an impossible size");
             g.st.stored_chunks += b.res.h[ch0 + i] == kXzEncStored;
         }
-        lay[k] = xzenc_block_layout(b.res.h.data() + ch0, cn, blen, b.dst.h.data() + ch0, check);
+        lay[k] = xzenc_block_layout(b.res.h.data() + ch0, cn, blen, b.dst.h.data() + ch0, check, z.filter);
         for (uint32_t i = 0; i < cn; ++i) b.dst.h[ch0 + i] += total;
         at[k] = total;
         offs[k] = b0;
@@ -174,7 +241,7 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     const EventPair ev2 = *evp2;
     HIP_TRY(c, hipEventRecord(ev2.a, zs));
-    HIP_TRY(c, launch_lzma2_concat(sl.d_buf.data(), n, (uint32_t)bs, b.d_slots.data(), b.res.d.data(), b.dst.d.data(), b.d_out.data(), nch, zs));
+    HIP_TRY(c, launch_lzma2_concat(src, n, (uint32_t)bs, b.d_slots.data(), b.res.d.data(), b.dst.d.data(), b.d_out.data(), nch, zs));
     HIP_TRY(c, hipEventRecord(ev2.b, zs));
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), total, hipMemcpyDeviceToHost, zs));
     // the Blocks' Checks, from the staged bytes in HBM by the Check's kernel (each waits for the stream: the piece is back
@@ -197,7 +264,12 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
         HIP_TRY(c, hipStreamSynchronize(zs));
     }
     if (rc) return rc;
-    if (z.self_check && (rc = xz_self_check_slot(g, z, sl, n, lay, at, total)) != SNAPHASH_OK) return rc;
+    float filt_ms = 0;
+    if (z.filter) {
+        (void)hipEventElapsedTime(&filt_ms, fev.a, fev.b); // (the stream has been waited for)
+        z.filt_ms += filt_ms;
+    }
+    if (z.self_check && (rc = xz_self_check_slot(g, z, sl, src, n, lay, at, total)) != SNAPHASH_OK) return rc;
     if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
         float chains = 0, concat = 0, sum = 0, longest = 0;
         (void)hipEventElapsedTime(&chains, ev.a, ev.b);
@@ -211,10 +283,11 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
         fprintf(stderr, "snaphash xz: slot of %llu bytes, %u blocks, %u chunks: chains %.3f ms, chunks %.3f ms in %zu launch(es) (longest %.3f), "
                         "concat %.3f ms, %s %.3f ms\n", (unsigned long long)n, nblk, nch, chains, sum, evl.size(), longest, concat,
                 check == kXzCheckSha256 ? "sha256" : check == kXzCheckCrc32 ? "crc32" : check == kXzCheckNone ? "no check" : "crc64", crc_ms);
+        if (z.filter) fprintf(stderr, "snaphash xz: slot of %llu bytes: filter 0x%02X %.3f ms\n", (unsigned long long)n, z.filter, filt_ms);
     }
     const uint32_t dict_byte = xzenc_dict_byte(bs);
     for (uint32_t k = 0; k < nblk; ++k) {
-        xzenc_block_frame(h + at[k], lay[k], lens[k], dict_byte, fields.data() + (size_t)k * kXzEncCheckMax, check_size);
+        xzenc_block_frame(h + at[k], lay[k], lens[k], dict_byte, fields.data() + (size_t)k * kXzEncCheckMax, check_size, z.filter);
         z.recs.push_back(XzEncRecord{lay[k].unpadded, lens[k]});
     }
     gz_emit(g, h, total, zbuf);
@@ -286,24 +359,26 @@ try {
 
 // What the _ex entries were asked for.  opt == nullptr, or an all-zero struct: what the plain entries write (1 MiB, CRC-64, no
 // self-check); otherwise the struct says its size and every field means what it says (check 0 is "none").
-int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check)
+int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check, uint32_t* filter)
 {
     *block_size = kXzEncBlockDefault;
     *check = kXzCheckCrc64;
     *self_check = false;
+    *filter = 0;
     if (opt && opt->struct_size == 0) {
-        if (opt->flags || opt->block_size || opt->check || opt->reserved) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+        if (opt->flags || opt->block_size || opt->check || opt->filter) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
         return SNAPHASH_OK;
     }
     if (!opt) return SNAPHASH_OK;
     if (opt->struct_size < sizeof(snaphash_xz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
     if (opt->flags & ~(uint32_t)SNAPHASH_XZ_SELF_CHECK) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
-    if (opt->reserved) return fail(x, SNAPHASH_EINVAL, "xz: snaphash_xz_options.reserved is not zero");
+    if (!xzenc_filter_valid(opt->filter)) return fail(x, SNAPHASH_EINVAL, "xz: the filter is 0 (none), 4 (x86), 7 (ARM) or 8 (ARM-Thumb)");
     if (!xzenc_check_valid(opt->check)) return fail(x, SNAPHASH_EINVAL, "xz: the Check is 0 (none), 1 (CRC-32), 4 (CRC-64) or 10 (SHA-256)");
     *block_size = opt->block_size;
     if (!xzenc_block_size(block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
     *check = opt->check;
     *self_check = (opt->flags & SNAPHASH_XZ_SELF_CHECK) != 0;
+    *filter = opt->filter;
     return SNAPHASH_OK;
 }
 
@@ -314,6 +389,16 @@ void xz_keep_selfcheck_stats(snaphash_ctx* x, const XzSelfCheck& sc)
     x->xz_selfcheck.struct_size = sizeof(snaphash_xz_selfcheck_stats);
     x->xz_selfcheck.chunks = sc.chunks;
     x->xz_selfcheck.ms = sc.ms;
+}
+
+// what snaphash_get_xz_filter_stats hands out: of this _ex call
+void xz_keep_filter_stats(snaphash_ctx* x, const XzEncoder& z)
+{
+    x->xz_filter = snaphash_xz_filter_stats{};
+    x->xz_filter.struct_size = sizeof(snaphash_xz_filter_stats);
+    x->xz_filter.filter = z.filter;
+    x->xz_filter.device_blocks = z.filt_blocks;
+    x->xz_filter.device_ms = z.filt_ms;
 }
 
 } // namespace
@@ -328,13 +413,15 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    int rc = xz_read_options(x, opt, &bs, &check, &self);
+    uint32_t filter;
+    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter);
     if (rc) return rc;
     XzSelfCheck sc;
     sc.member = "the buffer";
-    XzEncoder enc(bs, check, self ? &sc : nullptr);
+    XzEncoder enc(bs, check, self ? &sc : nullptr, filter);
     rc = encode_to_malloc(x, enc, data, n, xz_out, xz_len);
     xz_keep_selfcheck_stats(x, sc);
+    xz_keep_filter_stats(x, enc);
     return rc;
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;
@@ -347,14 +434,16 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    int rc = xz_read_options(x, opt, &bs, &check, &self);
+    uint32_t filter;
+    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter);
     if (rc) return rc;
     XzSelfCheck sc;
     const char* base = strrchr(tarname, '/');
     sc.member = base ? base + 1 : tarname;
-    XzEncoder enc(bs, check, self ? &sc : nullptr);
+    XzEncoder enc(bs, check, self ? &sc : nullptr, filter);
     rc = tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
     xz_keep_selfcheck_stats(x, sc);
+    xz_keep_filter_stats(x, enc);
     return rc;
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     return SNAPHASH_ENOMEM;

@@ -24,7 +24,14 @@ GPU) on tools/deflate_corpora.py's text, sources and binaries, 64 MiB each (--qu
             DIR.  On each corpus (8 MiB) one warm call, then five: best / median / worst, as "build": LABEL.  Alternate the
             two checkouts, three runs each:  xz_bench.py --no-flag-ab parent_run1 --tree P --corpora-root P;
             xz_bench.py --no-flag-ab branch_run1 --corpora-root P; ... (profiles/r16_xz_buffer_parent_ab.jsonl)
-usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--out FILE]
+  --filter NAME   instead of the legs above: what a BCJ filter (x86, arm, armthumb) in front of LZMA2 buys and costs (DESIGN.md
+            sec. 25).  On each corpus (8 MiB): the bytes snaphash_xz_buffer writes without and with the filter, beside
+            liblzma's greedy parser (MODE_FAST / MF_HC4 / depth 8) on the same 1 MiB Blocks without and with it -- the gain
+            is held against liblzma's, not against ours; the call without and with the filter, alternating, five of each;
+            the filter kernels' own time (snaphash_get_xz_filter_stats) beside the chains and chunks kernels of the same
+            call (a `snaphash xz -F` child under SNAPHASH_TRACE_XZ=1); and the install side reading the file back.  Then the
+            dense launch: snaphash_bcj_device over 1 MiB of E8, one lane's walk, beside sec. 17's one-second bound.
+usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--filter NAME] [--out FILE]
        tools/xz_bench.py --no-flag-ab LABEL [--tree DIR] [--corpora-root DIR] [--out FILE]   (JSON lines on stdout and in FILE; --out appends here)"""
 import argparse
 import lzma
@@ -185,6 +192,61 @@ def self_check_legs(g, size, total, fh, tmp, reps=5):
           "on_ms_best_median_worst": three(on), "check_kernel_ms_best_median_worst": three(kernel), "xz_bytes": sizes.pop()}, fh)
 
 
+FILTER_LINE = re.compile(r"filter 0x[0-9A-F]+ ([\d.]+) ms")
+
+
+def filter_legs(g, d, name_of_filter, fh, tmp, reps=5):
+    import numpy as np
+    import torch
+    fid = _lib.bcj_filter(name_of_filter)
+    lz_id = {4: lzma.FILTER_X86, 7: lzma.FILTER_ARM, 8: lzma.FILTER_ARMTHUMB}[fid]
+    hc4 = dict(id=lzma.FILTER_LZMA2, dict_size=BLOCK, mode=lzma.MODE_FAST, mf=lzma.MF_HC4, depth=8, nice_len=273, lc=3, lp=0, pb=2)
+
+    def liblzma_blocks(data, chain):
+        with ThreadPoolExecutor(16) as ex:
+            return sum(ex.map(lambda i: len(lzma.compress(data[i:i + BLOCK], format=lzma.FORMAT_RAW, filters=chain)), range(0, len(data), BLOCK)))
+
+    for name, data in corpora(8 << 20).items():
+        g.xz_buffer(data)  # one warm call each: the scratch
+        g.xz_buffer(data, filter=fid)
+        off, on, kernel = [], [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            z0 = g.xz_buffer(data)
+            off.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            z1 = g.xz_buffer(data, filter=fid)
+            on.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(g.xz_filter_stats()["device_ms"])
+        assert lzma.decompress(z0) == data and lzma.decompress(z1) == data
+        src, dst = os.path.join(tmp, "in"), os.path.join(tmp, "out.xz")
+        with open(src, "wb") as f:
+            f.write(data)
+        p = subprocess.run([CLI, "-g", "xz", src, dst, "-F", name_of_filter], env=dict(os.environ, SNAPHASH_TRACE_XZ="1"), stderr=subprocess.PIPE, text=True, check=True)
+        rows = [tuple(float(x) for x in m) for m in TRACE.findall(p.stderr)]
+        t_dec, t_dec_max, out = timed(lambda: d.unxz_buffer(z1, bcj=True), 3)
+        assert out == data and open(dst, "rb").read() == z1
+        fs = d.xz_filter_stats()
+        t_gpu, _, out = timed(lambda: g.unxz_buffer(z1, bcj=True), 3)
+        assert out == data
+        emit({"leg": "filter", "filter": name_of_filter, "corpus": name, "bytes": len(data), "snaphash_xz": len(z0), "snaphash_xz_filter": len(z1),
+              "gain_pct": round(100.0 * (len(z1) - len(z0)) / len(z0), 2), "hc4_depth8_1mib_blocks": liblzma_blocks(data, [hc4]),
+              "hc4_depth8_1mib_blocks_filter": liblzma_blocks(data, [dict(id=lz_id), hc4]), "reps": reps, "off_ms_best_median_worst": three(off),
+              "on_ms_best_median_worst": three(on), "filter_kernels_ms_best_median_worst": three(kernel),
+              "chains_ms": round(sum(r[0] for r in rows), 3), "chunks_ms": round(sum(r[1] for r in rows), 3),
+              "filter_ms_traced": round(sum(float(x) for x in FILTER_LINE.findall(p.stderr)), 3),
+              "unxz_default_ms": round(t_dec * 1e3, 2), "unxz_default_host_blocks": fs["host_blocks"], "unxz_gpu_only_ms": round(t_gpu * 1e3, 2),
+              "unxz_gpu_only_filter_kernels_ms": round(g.xz_filter_stats()["device_ms"], 3)}, fh)
+    n = 1 << 20  # the dense launch: one lane walks a whole range
+    dev = torch.full((n,), 0xE8, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(3):
+        g.bcj_device(fid, True, dev.data_ptr(), np.array([0], dtype=np.uint64), np.array([n], dtype=np.uint64))
+        ms.append(g.stats()["kernel_ms"])
+    emit({"leg": "filter_dense_launch", "filter": name_of_filter, "bytes": n, "kernel_ms_best_median_worst": three(ms), "bound_ms": 1000.0}, fh)
+
+
 def corpora_of(root, size):
     """unpack_bench.corpora with the corpus builders of the checkout at `root`, over that checkout's files."""
     origin = os.path.join(os.path.abspath(root), "tools", "deflate_corpora.py")
@@ -215,6 +277,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--self-check", action="store_true")
     ap.add_argument("--no-flag-ab", metavar="LABEL")
+    ap.add_argument("--filter", metavar="NAME", choices=("x86", "arm", "armthumb"))
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--corpora-root", default=ROOT)
     a = ap.parse_args()
@@ -226,6 +289,10 @@ def main():
         if a.no_flag_ab:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
                 no_flag_ab(g, a.no_flag_ab, a.corpora_root, fh)
+            return
+        if a.filter:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, Context(device=0, flags=0) as d:
+                filter_legs(g, d, a.filter, fh, tmp)
             return
         if a.self_check:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
