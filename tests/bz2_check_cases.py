@@ -13,10 +13,9 @@ the install side's host scan)."""
 import bz2
 import ctypes
 import functools
-import os
-import subprocess
 
 import bz2enc_cases as E
+import hostbuild
 import xz_cases as X
 
 OK, BYTE, LENGTH, BLOCK, CAP, END, CRC, ORIGPTR, TABLE = range(9)
@@ -123,11 +122,10 @@ def header_bits(z, bit):
 
 # ---- the harness -------------------------------------------------------------------------------------------------------------
 
-def load_harness(tmp_dir):
-    here = os.path.dirname(os.path.abspath(__file__))
-    so = os.path.join(str(tmp_dir), "libbz2checkhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(here, "bz2_check_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_harness():
+    """tests/bz2_check_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/bz2_check_host_harness.cpp")
     u64p, u32p, u8p, sz = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_size_t
     L.bc_check.argtypes = [u8p, sz, u64p, u64p, u8p, sz, u64p, u64p, u32p, ctypes.c_uint32, sz, u32p]
     L.bc_check.restype = None

@@ -11,10 +11,10 @@ over every input of xzenc_cases, liblzma itself (each 64 KiB piece compressed al
 does), and a symbol coder of this file's own on xz_cases._RangeEncoder for the chunks neither of them writes.  Every good
 case is decoded by liblzma before it is returned.  The Block size is 128 KiB unless the case says otherwise."""
 import ctypes
+import functools
 import lzma
-import os
-import subprocess
 
+import hostbuild
 import xz_cases as X
 import xzenc_cases as E
 
@@ -61,11 +61,10 @@ def block_ok(case, k):
 
 # ---- the harness -------------------------------------------------------------------------------------------------------------
 
-def load_harness(tmp_dir):
-    here = os.path.dirname(os.path.abspath(__file__))
-    so = os.path.join(str(tmp_dir), "liblzma2checkhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(here, "lzma2_check_host_harness.cpp")])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_harness():
+    """tests/lzma2_check_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/lzma2_check_host_harness.cpp")
     u64p, u8p = ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p
     L.lc_check.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, u8p, ctypes.c_size_t, u64p, u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     L.lc_check.restype = None

@@ -21,23 +21,17 @@ import subprocess
 import pytest
 
 import batch_shapes
-from conftest import GOLDEN, ROOT
+import hostbuild
+from conftest import GOLDEN
 
-HARNESS = os.path.join(ROOT, "tests", "batchplan_host_harness.cpp")
-# the runtime's headers, for the types in sha512_kernels.h alone: the harness is a host program and links none of the runtime
-RUNTIME_HEADERS = ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")]
+HARNESS = "tests/batchplan_host_harness.cpp"
 MiB = 1 << 20
 
 
-def build_harness(exe, *flags):
-    subprocess.check_call(["g++", "-std=c++17", *flags, *RUNTIME_HEADERS, "-o", exe, HARNESS])
-
-
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("batchplan") / "batchplan_host")
-    build_harness(exe, "-O2", "-Wall", "-Wextra", "-Werror")
-    return exe
+def harness():
+    """The harness as a host program: the runtime's headers for the types in sha512_kernels.h alone, none of the runtime linked."""
+    return hostbuild.program([HARNESS], ("-O2", *hostbuild.STRICT, *hostbuild.RUNTIME_HEADERS))
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +40,7 @@ def golden():
         return json.load(f)["shapes"]
 
 
-def plan(exe, tmp_path, source, staging, lens, gpu_lens=None, knobs=None, slot_caps=(0, 0, 0), env=None):
+def plan(exe, tmp_path, source, staging, lens, gpu_lens=None, knobs=None, slot_caps=(0, 0, 0), sanitized=False):
     """Plans one call -> (batches, geometry, summary); the harness fails on any segment out of place."""
     k = dict(batch_shapes.DEFAULT_KNOBS, **(knobs or {}))
     gpu_lens = lens if gpu_lens is None else gpu_lens
@@ -55,7 +49,7 @@ def plan(exe, tmp_path, source, staging, lens, gpu_lens=None, knobs=None, slot_c
         f.write("%d %d %d %d %d\n" % (staging, source == "memory", *slot_caps))
         f.write("%d %d %d %d %d\n%d\n" % (k["new_cap"], k["hold_back"], k["ramp_shift"], k["ramp_first64"], k["ramp_growth_pct"], len(lens)))
         f.write("".join("%d %d\n" % p for p in zip(lens, gpu_lens)))
-    r = subprocess.run([exe, "plan", spec], capture_output=True, text=True, timeout=600, env=env)
+    r = hostbuild.run_sanitized(exe, ["plan", spec]) if sanitized else subprocess.run([exe, "plan", spec], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "plan ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     calls = batch_shapes.parse_batches(r.stdout)
     assert len(calls) == 1
@@ -174,10 +168,8 @@ def test_knobs_from_the_environment(harness):
 
 
 def test_batchplan_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "batchplan_asan")
-    build_harness(exe, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = hostbuild.sanitized([HARNESS], flags=hostbuild.RUNTIME_HEADERS)
     lens = batch_shapes.lengths({"kind": "ragged", "n": 2500, "seed": 11, "top": 1 << 20, "zeros": 9})
     for name in ("mem_5000x256k", "files_5000x8k", "zipf_mem", "ragged_files", "knobs_files", "slots_there"):
-        plan_shape(exe, tmp_path, batch_shapes.SHAPES[name], env=env)
-    plan(exe, tmp_path, "files", 32 * MiB, lens, [(ln // 2) & ~127 for ln in lens], env=env)
+        plan_shape(exe, tmp_path, batch_shapes.SHAPES[name], sanitized=True)
+    plan(exe, tmp_path, "files", 32 * MiB, lens, [(ln // 2) & ~127 for ln in lens], sanitized=True)

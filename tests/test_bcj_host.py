@@ -5,26 +5,23 @@ the host decoder over liblzma's files, the producer's host model with each filte
 a program of its own.  The kernels that run the same header are checked in tests/test_gpu_bcj_edges.py, the entry points
 in tests/test_gpu_xz_bcj.py."""
 import ctypes
+import functools
 import lzma
-import os
-import subprocess
 
 import pytest
 
 import bcj_cases as B
 import xz_cases as X
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "bcj_host_harness.cpp")
 EINVAL, EFORMAT = -1, -9
 PLAN_OK, PLAN_FORMAT, PLAN_UNSUPPORTED = 0, 1, 2
 
 
-@pytest.fixture(scope="module")
-def bh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bh") / "libbcjhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_bcj():
+    """tests/bcj_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/bcj_host_harness.cpp")
     P = ctypes.POINTER
     L.bh_block.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
     L.bh_block.restype = None
@@ -38,6 +35,11 @@ def bh(tmp_path_factory):
     L.bh_encode.restype = ctypes.c_void_p
     L.bh_free.argtypes = [ctypes.c_void_p]
     return L
+
+
+@pytest.fixture(scope="module")
+def bh():
+    return load_bcj()
 
 
 def block(L, filt, encode, data, start=0):
@@ -202,17 +204,12 @@ def test_filter_helps_on_code_like_data(bh):
 
 def test_same_cases_under_asan_ubsan(tmp_path):
     """Host code only, in a program of its own (tests/asan_bcj.cpp): every case from a heap buffer of exactly its size."""
-    exe = str(tmp_path / "asan_bcj")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_bcj.cpp")])
+    exe = hostbuild.sanitized(["tests/asan_bcj.cpp"])
     args = []
     cases = B.all_cases()
     for i, (filt, name, data, start) in enumerate(cases):
         p = tmp_path / ("c%03d" % i)
         p.write_bytes(data)
         args += [str(p), str(filt), str(start)]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe] + args, env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    out = hostbuild.run_sanitized(exe, args)
     assert out.stdout.split() == ["ok"] * len(cases)

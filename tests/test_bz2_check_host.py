@@ -8,19 +8,17 @@ status (and, where the case states one, the offset) it was made for.  And for EV
 safety property: if the check accepts it, libbz2 decodes a stream of the block's stretch alone to exactly the piece.  A bit flip
 the check accepts must therefore be one libbz2 decodes to the same bytes; how many there were is printed, not asserted."""
 import ctypes
-import os
 import struct
-import subprocess
 
 import pytest
 
 import bz2_check_cases as C
-from conftest import ROOT
+import hostbuild
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return C.load_harness(tmp_path_factory.mktemp("bc"))
+def L():
+    return C.load_harness()
 
 
 @pytest.fixture(scope="module")
@@ -108,9 +106,7 @@ def test_stretches_come_from_the_scan(L):
 def test_model_under_asan_and_ubsan(good, damaged, verdicts, tmp_path):
     """Host code only, in a program of its own (tests/asan_bz2_check.cpp): every case, each buffer on the heap at exactly its
     size, then with the buffers cut short and the tables shifted.  Its first pass's verdicts are the harness's."""
-    exe = str(tmp_path / "asan_bz2_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_bz2_check.cpp"), "-pthread"])
+    exe = hostbuild.sanitized(["tests/asan_bz2_check.cpp"])
     cases = good + damaged
     inputs = tmp_path / "cases.bin"
     with open(inputs, "wb") as f:
@@ -119,11 +115,8 @@ def test_model_under_asan_and_ubsan(good, damaged, verdicts, tmp_path):
             for t in (c.z_beg, c.z_end, c.in_off, c.in_len, c.crc):
                 f.write(struct.pack("<%dQ" % c.nb, *t))
     out_file = tmp_path / "verdicts.bin"
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(inputs), str(out_file)], env=env, capture_output=True, text=True, timeout=1800)
+    out = hostbuild.run_sanitized(exe, [inputs, out_file], timeout=1800)
     print(out.stdout[-400:])
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
     assert out.stdout.startswith("%d cases, " % len(cases))
     want = b"".join(struct.pack("<II", *x) for c in cases for x in verdicts[id(c)])
     assert out_file.read_bytes() == want

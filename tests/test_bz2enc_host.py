@@ -10,29 +10,29 @@ Python references of RLE1, the BWT and MTF on bz2enc_cases.edge_cases(), read ba
 and every edge input is what its name says."""
 import bz2
 import ctypes
+import functools
 import glob
 import itertools
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import bz2enc_cases as B
 import xz_cases as X
+import hostbuild
 from conftest import ROOT
 from test_bzip2_host import bh, serial  # noqa: F401  (the decoder harness's fixture)
 
-HARNESS = os.path.join(ROOT, "tests", "bz2enc_host_harness.cpp")
 P = ctypes.POINTER
 INFO = 8  # uint64 a block: be_encode's and be_parse's rows
 
 
-def load_model(so_dir):
-    so = os.path.join(str(so_dir), "libbz2enchost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_model():
+    """tests/bz2enc_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/bz2enc_host_harness.cpp")
     L.be_encode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(ctypes.c_size_t), P(ctypes.c_uint64), ctypes.c_size_t,
                             P(ctypes.c_size_t)]
     L.be_encode.restype = ctypes.c_void_p
@@ -45,6 +45,8 @@ def load_model(so_dir):
     L.be_rle1.restype = ctypes.c_uint32
     L.be_bwt.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
     L.be_bwt.restype = ctypes.c_uint32
+    L.be_mtf.argtypes = [ctypes.c_char_p, ctypes.c_uint32, P(ctypes.c_uint16), P(ctypes.c_uint32)]
+    L.be_mtf.restype = ctypes.c_uint32
     L.be_code_lengths.argtypes = [P(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p]
     L.be_code_lengths.restype = None
     L.be_parse.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_uint64), ctypes.c_size_t, P(ctypes.c_uint32), P(ctypes.c_uint32),
@@ -221,8 +223,8 @@ def naive_bwt(b):
 
 
 @pytest.fixture(scope="module")
-def be(tmp_path_factory):
-    return load_model(tmp_path_factory.mktemp("be"))
+def be():
+    return load_model()
 
 
 def all_cases(be):
@@ -564,9 +566,7 @@ def test_bz2enc_host_model_under_asan_and_ubsan(tmp_path, be):
     """Host code only, in a program of its own (tests/asan_bz2enc.cpp): the model over every input, each from a heap buffer
     of exactly its size, the stage model (be_stages' routines and the slot reader) over the edge inputs that run with a small
     cap, and 2000 random inputs of up to 200 KiB at random levels, decoded with bzip2_core.h."""
-    exe = str(tmp_path / "asan_bz2enc")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_bz2enc.cpp"), "-pthread"])
+    exe = hostbuild.sanitized(["tests/asan_bz2enc.cpp"])
     args = ["2000", "1"]
     cases = [c for c in all_cases(be) if c[2] == 1 or len(c[1]) <= 3000 or c in B.big_cases()]
     for i, (name, data, lv) in enumerate(cases):
@@ -585,8 +585,5 @@ def test_bz2enc_host_model_under_asan_and_ubsan(tmp_path, be):
             p.write_bytes(e.data)
             q.write_text("".join("%d %d\n" % r for r in e.ranges))
         args += ["-l" if e.kind == "last" else "-e", str(p), str(q), str(e.level), str(e.cap), str(e.carry), str(e.carry_bits)]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe] + args, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    out = hostbuild.run_sanitized(exe, args, timeout=900)
     assert out.stdout.split() == ["ok"] * (len(cases) + len(edges)) + ["random", "2000"]

@@ -6,25 +6,22 @@ bz_sample_write, run serially) against the serial walk.  The GPU kernels that ru
 tests/test_gpu_bunzip2.py and tests/test_gpu_bzip2_edges.py."""
 import bz2
 import ctypes
-import os
+import functools
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "bzip2_host_harness.cpp")
 EFORMAT = -9
 BLOCK_MAGIC = 0x314159265359
 
 
-@pytest.fixture(scope="module")
-def bh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bh") / "libbzip2host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_bzip2():
+    """tests/bzip2_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/bzip2_host_harness.cpp")
     P = ctypes.POINTER
     L.bh_serial.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_int), P(ctypes.c_uint64)]
     L.bh_serial.restype = ctypes.c_void_p
@@ -47,6 +44,11 @@ def bh(tmp_path_factory):
     L.bh_ibwt_sampled.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, P(ctypes.c_uint32)]
     L.bh_ibwt_sampled.restype = ctypes.c_int
     return L
+
+
+@pytest.fixture(scope="module")
+def bh():
+    return load_bzip2()
 
 
 def _take(L, p, n):
@@ -251,21 +253,15 @@ def test_crc_is_crc32_bzip2(bh):
 
 
 def test_bzip2_host_code_under_asan_and_ubsan(bh, tmp_path):
-    exe = str(tmp_path / "bh_fuzz")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DBH_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, HARNESS, "-pthread"])
+    exe = hostbuild.sanitized(["tests/bzip2_host_harness.cpp"], defines=["BH_MAIN"])
     d = text(40000, 17) + bytes(range(256)) * 20 + bytes(3000)
     z = bz2.compress(d[:30000], 1) + bz2.compress(d, 9)
     f = tmp_path / "in.bz2"
     f.write_bytes(z)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(f), "3000", "7"], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-4000:]
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    hostbuild.run_sanitized(exe, [f, 3000, 7], timeout=900)
     planted = tmp_path / "planted.bz2"
     planted.write_bytes(z + BLOCK_MAGIC.to_bytes(6, "big") * 5000)
-    out = subprocess.run([exe, str(planted), "40", "8"], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-4000:]
+    hostbuild.run_sanitized(exe, [planted, 40, 8], timeout=900)
 
 
 def run_free(n, seed):

@@ -2,22 +2,43 @@
 shares) compiled as host C++ and checked against the oracle.  CPU only; the
 device build of the same header is checked by the -m gpu parity tests."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import pytest
 
+import hostbuild
 from conftest import ROOT
 
 
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("core") / "libcorehost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so,
-                           os.path.join(ROOT, "tests", "core_host_harness.cpp")])
-    L = ctypes.CDLL(so)
+H8 = ctypes.c_uint64 * 8
+
+
+@functools.lru_cache(maxsize=None)
+def load_core():
+    """tests/core_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/core_host_harness.cpp")
     L.core_sha512.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
     L.core_sha512.restype = None
+    L.core_segment.argtypes = [H8, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    L.core_segment.restype = None
+    L.hostsha_resume_final.argtypes = [H8, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+    L.hostsha_resume_final.restype = None
+    L.hostsha_buffer.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
+    L.hostsha_buffer.restype = None
+    L.hostsha_variants.argtypes = []
+    L.hostsha_blocks_variant.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.hostsha_blocks_variant.restype = None
+    L.hostsha_file.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+    L.hostsha_x8_available.argtypes = []
+    L.hostsha_many.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+                               ctypes.c_uint, ctypes.c_uint64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
+    return L
+
+
+@pytest.fixture(scope="module")
+def core():
+    L = load_core()
 
     def f(data, split=0):
         out = ctypes.create_string_buffer(64)
@@ -85,14 +106,7 @@ def test_segment_from_any_state_and_byte_count(tmp_path):
     digest.  The two length words of the padding are what this is about."""
     import random
     import sha512_ref as ref
-    so = str(tmp_path / "libcorehost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "core_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
-    H8 = ctypes.c_uint64 * 8
-    L.core_segment.argtypes = [H8, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
-    L.core_segment.restype = None
-    L.hostsha_resume_final.argtypes = [H8, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
-    L.hostsha_resume_final.restype = None
+    L = load_core()
     rng = random.Random(512)
     out = ctypes.create_string_buffer(64)
     for total_prev in TOTAL_PREV:
@@ -115,12 +129,7 @@ def test_host_sha512_of_the_hybrid_scheduler(core, tmp_path_factory):
     """snappy_amd/csrc/hostsha.cpp (the library's own host SHA-512, used only when host_threads > 0):
     every tail length, resumed mid-stream from a chaining value, and the file reader's size check."""
     import hashlib
-    so = str(tmp_path_factory.mktemp("core2") / "libcorehost2.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so,
-                           os.path.join(ROOT, "tests", "core_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
-    L.hostsha_buffer.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
-    L.hostsha_file.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+    L = load_core()
     rnd = os.urandom(3000)
     out = ctypes.create_string_buffer(64)
     for n in list(range(0, 300)) + [1000, 2047, 2048, 2049, 3000]:
@@ -128,7 +137,6 @@ def test_host_sha512_of_the_hybrid_scheduler(core, tmp_path_factory):
             L.hostsha_buffer(rnd[:n], n, split, out)
             assert out.raw == hashlib.sha512(rnd[:n]).digest(), (n, split)
     # every spelling of the block function this CPU can run agrees with the portable one, block count by block count
-    L.hostsha_blocks_variant.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     data = os.urandom(128 * 9)
     for nblocks in range(0, 10):
         got = []
@@ -164,11 +172,7 @@ def test_eight_streams_side_by_side_on_one_core(core, tmp_path_factory):
     import hashlib
     import random
     import numpy as np
-    so = str(tmp_path_factory.mktemp("core8") / "libcorehost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "core_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
-    L.hostsha_many.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
-                               ctypes.c_uint, ctypes.c_uint64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
+    L = load_core()
     rng = random.Random(31)
     blob = np.random.default_rng(31).integers(0, 256, size=3 << 20, dtype=np.uint8).tobytes()
     d = tmp_path_factory.mktemp("x8files")
@@ -220,11 +224,7 @@ def test_eight_streams_side_by_side_on_one_core(core, tmp_path_factory):
 
 def test_eight_streams_under_asan_and_ubsan(tmp_path):
     """tests/asan_hostsha_x8.cpp: the lane scheduler and the AVX-512 block function with every read checked."""
-    exe = str(tmp_path / "asan_x8")
-    src = [os.path.join(ROOT, "snappy_amd", "csrc", f) for f in ("hostsha.cpp", "hostsha_x8.cpp")]
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_hostsha_x8.cpp")] + src + ["-pthread"])
+    exe = hostbuild.sanitized(["tests/asan_hostsha_x8.cpp", "snappy_amd/csrc/hostsha.cpp", "snappy_amd/csrc/hostsha_x8.cpp"])
     work = tmp_path / "files"
     work.mkdir()
-    r = subprocess.run([exe, str(work)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0 and b"asan x8 driver ok" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr.decode()[-3000:])
+    assert "asan x8 driver ok" in hostbuild.run_sanitized(exe, [work]).stdout

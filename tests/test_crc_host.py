@@ -2,26 +2,23 @@
 against libbz2 (tests/crc_oracle.py), combine at every split point and with lengths of 0 and of more than 2^32, and the
 kernels' cut of a range into tiles and lane slices run serially.  The kernels themselves: tests/test_gpu_crc_edges.py."""
 import ctypes
-import os
+import functools
 import random
-import subprocess
 import zlib
 
 import pytest
 
 import crc_oracle
-from conftest import ROOT
+import hostbuild
 from crc_oracle import BZIP2, GZIP
 
-HARNESS = os.path.join(ROOT, "tests", "crc_host_harness.cpp")
 KINDS = [GZIP, BZIP2]
 
 
-@pytest.fixture(scope="module")
-def ch(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("ch") / "libcrchost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_ch():
+    """tests/crc_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/crc_host_harness.cpp")
     for f in (L.ch_crc, L.ch_tiled):
         f.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
         f.restype = ctypes.c_uint32
@@ -34,6 +31,11 @@ def ch(tmp_path_factory):
     L.ch_tile_bytes.restype = ctypes.c_uint32
     L.ch_slice_bytes.restype = ctypes.c_uint32
     return L
+
+
+@pytest.fixture(scope="module")
+def ch():
+    return load_ch()
 
 
 @pytest.fixture(scope="module")

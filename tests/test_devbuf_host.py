@@ -2,32 +2,23 @@
 (engine_bufs.h), built with g++ against a fake allocator that fails its k-th call (tests/devbuf_host_harness.cpp).  A
 buffer's pointer and size always agree, and a group whose ensure() fails at any allocation ends empty.  The GPU side of
 the same buffers runs in every -m gpu test."""
-import os
 import subprocess
 
 import pytest
 
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "devbuf_host_harness.cpp")
-# the runtime's headers, for hipError_t and hipEvent_t alone: the harness is a host program and links none of the runtime
-RUNTIME_HEADERS = ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")]
-
-
-def build_harness(exe, *flags):
-    """The harness as a host program (g++), with the given flags."""
-    subprocess.check_call(["g++", "-std=c++17", *flags, *RUNTIME_HEADERS, "-o", exe, HARNESS])
+HARNESS = "tests/devbuf_host_harness.cpp"
 
 
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("devbuf") / "devbuf_host")
-    build_harness(exe, "-O1", "-Wall", "-Wextra", "-Werror")
-    return exe
+def harness():
+    """The harness as a host program: the runtime's headers for hipError_t and hipEvent_t alone, none of the runtime linked."""
+    return hostbuild.program([HARNESS], ("-O1", *hostbuild.STRICT, *hostbuild.RUNTIME_HEADERS))
 
 
-def run(exe, case, env=None):
-    r = subprocess.run([exe, case], capture_output=True, text=True, timeout=600, env=env)
+def run(exe, case, sanitized=False):
+    r = hostbuild.run_sanitized(exe, [case]) if sanitized else subprocess.run([exe, case], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and ("%s ok" % case) in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     return r
 
@@ -53,8 +44,4 @@ def test_review_sequence_sizes_every_member(harness):
 
 
 def test_devbuf_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "devbuf_asan")
-    build_harness(exe, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = run(exe, "all", env=env)
-    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    run(hostbuild.sanitized([HARNESS], flags=hostbuild.RUNTIME_HEADERS), "all", sanitized=True)

@@ -3,6 +3,7 @@ walk and member rules, ustar headers, CRC-32) and a serial model of the DEFLATE 
 token encoder header, same chunk framing) checked against zlib, gzip and tarfile.  The kernel itself is
 checked on the GPU (tests/test_gpu_f3.py)."""
 import ctypes
+import functools
 import gzip
 import io
 import os
@@ -14,31 +15,45 @@ import zlib
 import numpy as np
 import pytest
 
+import hostbuild
 from conftest import ROOT
 
 
-@pytest.fixture(scope="module")
-def f3(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("f3") / "libf3host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so,
-                           os.path.join(ROOT, "tests", "f3_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
-    L.f3_model_gzip.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+@functools.lru_cache(maxsize=None)
+def load_f3():
+    """tests/f3_host_harness.cpp, loaded once a process with every prototype.  One copy serves every module: f3_model_gzip3
+    puts g_model_depth back before it returns, and f3_model_counters reports the last call only."""
+    L = hostbuild.shared("tests/f3_host_harness.cpp")
+    P = ctypes.POINTER
+    L.f3_model_gzip.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_size_t)]
     L.f3_model_gzip.restype = ctypes.c_void_p
-    L.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, P(ctypes.c_size_t)]
     L.f3_model_gzip2.restype = ctypes.c_void_p
-    L.f3_model_gzip3.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t)]
+    L.f3_model_gzip3.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, P(ctypes.c_size_t)]
     L.f3_model_gzip3.restype = ctypes.c_void_p
     L.f3_crc32.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]
     L.f3_crc32.restype = ctypes.c_uint32
     L.f3_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
     L.f3_crc32_combine.restype = ctypes.c_uint32
-    L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, P(ctypes.c_void_p), P(ctypes.c_size_t)]
+    L.f3_tar_stream_slots.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, P(ctypes.c_void_p), P(ctypes.c_size_t), P(ctypes.c_void_p),
+                                      P(ctypes.c_size_t)]
+    L.f3_tar_fill_slot_unfit.argtypes = [ctypes.c_uint64, P(ctypes.c_size_t)]
+    L.f3_tar_header_of.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p]
     L.f3_free.argtypes = [ctypes.c_void_p]
     L.f3_model_counters.argtypes = [ctypes.c_void_p]
     L.f3_model_counters.restype = None
     L.f3_huff_tables.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    L.f3_ilog.argtypes = [ctypes.c_uint32]
+    L.f3_ilog.restype = ctypes.c_uint32
+    L.f3_price.argtypes = [ctypes.c_uint32] * 3
+    L.f3_price.restype = ctypes.c_uint32
     return L
+
+
+@pytest.fixture(scope="module")
+def f3():
+    return load_f3()
 
 
 def sample_inputs():
@@ -138,10 +153,6 @@ def test_price_arithmetic_of_the_parse(f3):
     of two, never decreasing, never above the real logarithm nor 0.35 bits under it (the mantissa is linear, then cut); a price is at least one bit, at
     most its cap, and falls as the symbol gets more frequent."""
     import math
-    f3.f3_ilog.argtypes = [ctypes.c_uint32]
-    f3.f3_ilog.restype = ctypes.c_uint32
-    f3.f3_price.argtypes = [ctypes.c_uint32] * 3
-    f3.f3_price.restype = ctypes.c_uint32
     prev = 0
     for x in list(range(1, 5000)) + [2**k + d for k in range(13, 31) for d in (-1, 0, 1)] + [2**32 - 1]:
         v = f3.f3_ilog(x)
@@ -341,8 +352,6 @@ def slot_tree(f3, tmp_path_factory):
 
 def _stream_in_slots(f3, root, slot_bytes):
     """-> (the stream assembled by tar_fill_slot, its segments as dicts)."""
-    f3.f3_tar_stream_slots.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
-                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
     out, n, segs, nsegs = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p(), ctypes.c_size_t()
     assert f3.f3_tar_stream_slots(root.encode(), None, slot_bytes, ctypes.byref(out), ctypes.byref(n), ctypes.byref(segs), ctypes.byref(nsegs)) == 0
     stream = ctypes.string_at(out.value, n.value)
@@ -402,7 +411,6 @@ def test_tar_fill_slot_returns_the_header_that_does_not_fit(f3):
     """A name that neither the ustar fields nor a PAX record carry (a plan made by hand: tar_plan would add the record):
     tar_header's SNAPHASH_ENAME comes back with mi at that member, whatever the slot size."""
     from snappy_amd import _lib
-    f3.f3_tar_fill_slot_unfit.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_size_t)]
     for slot_bytes in (512, 1024, 1536, 4096, 65536):
         mi = ctypes.c_size_t(99)
         assert f3.f3_tar_fill_slot_unfit(slot_bytes, ctypes.byref(mi)) == _lib.ENAME, slot_bytes
@@ -413,7 +421,6 @@ def test_f3_host_code_under_asan_and_ubsan(tmp_path):
     """tarpack.cpp (walk, ustar headers, CRC-32), hostsha.cpp and the serial model of the DEFLATE kernel under
     AddressSanitizer + UBSan (CPU build; GPU sanitizers are not available on the pool): a tree with every member
     kind, names at the ustar limits, and all the sample inputs."""
-    exe = str(tmp_path / "asan_f3")
     src = tmp_path / "driver.cpp"
     src.write_text(r'''
 #include "%s/tests/f3_host_harness.cpp"
@@ -453,8 +460,7 @@ int main(int argc, char** argv) {
     return 0;
 }
 ''' % (ROOT, ROOT))
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, str(src), "-pthread"])
+    exe = hostbuild.sanitized([src])
     root = str(tmp_path / "src")
     os.makedirs(root)
     _make_tree(root)
@@ -465,5 +471,4 @@ int main(int argc, char** argv) {
     os.symlink("t" * 300, os.path.join(deep, "pax-link"))                      # PAX linkpath record
     os.makedirs(os.path.join(root, "zz-slots"))
     _make_slot_tree(os.path.join(root, "zz-slots"))                            # sizes around the record, PAX data of two records, an empty last member
-    r = subprocess.run([exe, root, root + "/DEBIAN"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0 and b"asan f3 ok" in r.stdout, r.stderr.decode()[-2000:]
+    assert "asan f3 ok" in hostbuild.run_sanitized(exe, [root, root + "/DEBIAN"]).stdout

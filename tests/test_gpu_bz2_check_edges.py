@@ -26,8 +26,8 @@ EINVAL = -1
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return C.load_harness(tmp_path_factory.mktemp("bc"))
+def L():
+    return C.load_harness()
 
 
 @pytest.fixture(scope="module")

@@ -30,8 +30,8 @@ P1 = B.PIECE
 
 
 @pytest.fixture(scope="module")
-def be(tmp_path_factory):
-    return load_model(tmp_path_factory.mktemp("be"))
+def be():
+    return load_model()
 
 
 @pytest.fixture(scope="module")

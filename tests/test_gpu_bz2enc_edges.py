@@ -29,8 +29,8 @@ IMPOSSIBLE = "bzip2: a block's stages reported an impossible result"
 
 
 @pytest.fixture(scope="module")
-def be(tmp_path_factory):
-    return load_model(tmp_path_factory.mktemp("be"))
+def be():
+    return load_model()
 
 
 @pytest.fixture(scope="module")

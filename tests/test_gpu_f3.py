@@ -13,7 +13,7 @@ import pytest
 
 import trees
 from conftest import ROOT
-from test_f3_host import sample_inputs, _make_tree, f3  # noqa: F401  (the CPU model of the kernel's format)
+from test_f3_host import sample_inputs, _make_tree, f3, load_f3  # noqa: F401  (the CPU model of the kernel's format)
 
 pytestmark = pytest.mark.gpu
 
@@ -214,14 +214,8 @@ def test_tar_create_slot_boundaries_random_trees(built_lib, oracle, tmp_path):
     import shutil
     from snappy_amd import Context
     rng = np.random.default_rng(21)
-    so = str(tmp_path / "libf3host.so")
-    import subprocess
-    from conftest import ROOT
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp")])
-    L = ctypes.CDLL(so)
-    L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-    L.f3_free.argtypes = [ctypes.c_void_p]
-    ctxs = [Context(staging_bytes=s) for s in (1 << 16, (1 << 16) + (1 << 14), 3 << 16)]
+    L = load_f3()
+    ctxs =[Context(staging_bytes=s) for s in (1 << 16, (1 << 16) + (1 << 14), 3 << 16)]
     try:
         for it in range(24):
             build = str(tmp_path / ("t%d" % it))
@@ -266,16 +260,9 @@ def test_first_slot_goes_to_the_compressor_in_parts(built_lib, oracle, tmp_path)
     the bytes must equal the serial CPU model's over the same tar stream, inflate to it, and not depend on what the
     staging buffer held before (a different tree goes through the same ctx in between)."""
     import ctypes
-    import subprocess
     from snappy_amd import Context
     rng = np.random.default_rng(77)
-    so = str(tmp_path / "libf3host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp")])
-    L = ctypes.CDLL(so)
-    L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-    L.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    L.f3_model_gzip2.restype = ctypes.c_void_p
-    L.f3_free.argtypes = [ctypes.c_void_p]
+    L = load_f3()
     MiB = 1 << 20
     words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 10)), dtype=np.uint8)) for _ in range(500)]
     text = b" ".join(words[int(i)] for i in rng.zipf(1.3, size=300000) % 500)

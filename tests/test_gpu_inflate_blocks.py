@@ -13,7 +13,7 @@ import pytest
 
 from snappy_amd import Context, _lib, getHashes
 
-from test_inflate_blocks_host import build_harness, scan
+from test_inflate_blocks_host import load_blocks, scan
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +35,8 @@ def split_ctx(**kw):
 
 
 @pytest.fixture(scope="module")
-def bh(tmp_path_factory):
-    return build_harness(tmp_path_factory.mktemp("bh"))
+def bh():
+    return load_blocks()
 
 
 def test_plain_streams_decode_in_parallel(snaphash_mode):

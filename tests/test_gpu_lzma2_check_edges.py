@@ -21,8 +21,8 @@ SLOT = 65600
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return C.load_harness(tmp_path_factory.mktemp("lc"))
+def L():
+    return C.load_harness()
 
 
 @pytest.fixture(scope="module")

@@ -53,10 +53,10 @@ def check(c, buf, ranges):
     assert not bad, bad[:5]
 
 
-def test_units_are_the_kernels(tmp_path_factory):
+def test_units_are_the_kernels():
     """The constants this file names are the ones the kernel is built from."""
     from test_sha256_host import load_sha
-    L = load_sha(tmp_path_factory.mktemp("shu"))
+    L = load_sha()
     assert (L.sh_block_bytes(), L.sh_load_bytes(), L.sh_step_bytes(), L.sh_tile_row_bytes()) == (BLOCK, LOAD, STEP, TILE_ROW)
 
 

@@ -26,8 +26,8 @@ DEVICE_KEYS = ("device_crc32", "device_crc64", "device_sha256")
 
 
 @pytest.fixture(scope="module")
-def sh(tmp_path_factory):
-    return load_sha(tmp_path_factory.mktemp("shx"))
+def sh():
+    return load_sha()
 
 
 def decode(c, mode, z, plain, sha_blocks, host_checks=0, crc32_blocks=0):

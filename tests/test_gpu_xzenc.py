@@ -30,8 +30,8 @@ CLI = os.path.join(ROOT, "snappy_amd", "bin", "snaphash")
 
 
 @pytest.fixture(scope="module")
-def xe(tmp_path_factory):
-    return load_enc(tmp_path_factory.mktemp("xe"))
+def xe():
+    return load_enc()
 
 
 @pytest.fixture(scope="module")

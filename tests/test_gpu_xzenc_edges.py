@@ -27,8 +27,8 @@ WIDTHS = (1, 2, 3, 7, 0)
 
 
 @pytest.fixture(scope="module")
-def xe(tmp_path_factory):
-    return load_enc(tmp_path_factory.mktemp("xe"))
+def xe():
+    return load_enc()
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,7 @@ import stat
 import numpy as np
 import pytest
 
+import hostbuild
 from conftest import GOLDEN, ROOT
 import trees
 
@@ -312,34 +313,20 @@ def test_a_big_hashes_yaml_is_parsed_in_ranges_and_comes_out_the_same(built_lib)
 
 def test_hostpass_under_asan_and_ubsan(tmp_path):
     """hostpass.cpp (walk, emitter, parser of untrusted hashes.yaml, LPT) built with
-    -fsanitize=address,undefined and driven with 20 000 mutated documents."""
-    import subprocess
-    exe = str(tmp_path / "asan_hostpass")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(ROOT, "tests", "asan_hostpass.cpp"),
-                           os.path.join(ROOT, "snappy_amd", "csrc", "hostpass.cpp"),
-                           os.path.join(ROOT, "snappy_amd", "csrc", "yamlscalar.cpp"),
-                           os.path.join(ROOT, "snappy_amd", "csrc", "walk.cpp"),
-                           os.path.join(ROOT, "snappy_amd", "csrc", "hostfill.cpp"),
-                           os.path.join(ROOT, "snappy_amd", "csrc", "planner.cpp"), "-pthread"])
+    AddressSanitizer + UBSan and driven with 20 000 mutated documents."""
+    exe = hostbuild.sanitized(["tests/asan_hostpass.cpp"] + ["snappy_amd/csrc/" + f for f in
+                              ("hostpass.cpp", "yamlscalar.cpp", "walk.cpp", "hostfill.cpp", "planner.cpp")])
     build, tar = trees.make_synthetic_tree(str(tmp_path / "t"), [5, 0, 300, 70000, 12, 1, 2, 3])
-    r = subprocess.run([exe, build, os.path.join(GOLDEN, "hashes_simple.yaml")], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stderr.decode()[-3000:])
-    assert b"asan driver ok" in r.stdout
+    assert "asan driver ok" in hostbuild.run_sanitized(exe, [build, os.path.join(GOLDEN, "hashes_simple.yaml")]).stdout
 
 
 
 def test_threaded_host_code_under_tsan(tmp_path):
     """What the library runs on more than one host thread -- the level-wise walk, the ranged YAML emitter, the pool of
-    staging-fill threads, the read-ahead reader of a long host-hashed file -- built with -fsanitize=thread
+    staging-fill threads, the read-ahead reader of a long host-hashed file -- built with ThreadSanitizer
     (tests/tsan_host.cpp): no report, every result equal to the single-threaded one."""
-    import subprocess
-    exe = str(tmp_path / "tsan_host")
-    src = [os.path.join(ROOT, "snappy_amd", "csrc", f) for f in
-           ("hostpass.cpp", "yamlscalar.cpp", "walk.cpp", "hostfill.cpp", "hostsha.cpp", "planner.cpp")]
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-o", exe,
-                           os.path.join(ROOT, "tests", "tsan_host.cpp")] + src + ["-pthread"])
+    exe = hostbuild.sanitized(["tests/tsan_host.cpp"] + ["snappy_amd/csrc/" + f for f in
+                              ("hostpass.cpp", "yamlscalar.cpp", "walk.cpp", "hostfill.cpp", "hostsha.cpp", "planner.cpp")], sanitize="thread")
     build = tmp_path / "build"
     for d in range(40):
         for e in range(3):
@@ -349,14 +336,7 @@ def test_threaded_host_code_under_tsan(tmp_path):
                 (p / ("f%03d" % f)).write_bytes(b"x" * (f * 13))
     big = tmp_path / "big.bin"
     big.write_bytes(os.urandom(1 << 20) * 40)
-    cmd = [exe, str(build), str(big)]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    if r.returncode != 0 and b"unexpected memory mapping" in r.stderr:  # the sanitizer runtime against this kernel's ASLR
-        r = subprocess.run(["setarch", "x86_64", "-R"] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-        if r.returncode != 0 and b"ThreadSanitizer: data race" not in r.stderr and b"tsan driver" not in r.stdout and b"unexpected memory mapping" in r.stderr:
-            pytest.skip("ThreadSanitizer cannot map its shadow on this kernel")
-    assert r.returncode == 0 and b"WARNING: ThreadSanitizer" not in r.stderr, (r.returncode, r.stderr.decode()[-4000:])
-    assert b"tsan driver ok" in r.stdout
+    assert "tsan driver ok" in hostbuild.run_sanitized(exe, [build, big], sanitize="thread").stdout
 
 
 _UNLISTABLE_CHILD = r'''

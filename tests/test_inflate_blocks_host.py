@@ -4,18 +4,18 @@ walk that records every block, and the whole block mode run serially (tests/infl
 every candidate into a hole slot, link, fill, the host taking a block where the chain breaks) against Python's zlib.
 The GPU kernels that run the same code are checked in tests/test_gpu_inflate_blocks.py."""
 import ctypes
+import functools
 import gzip
 import os
 import random
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import hostbuild
 from conftest import ROOT
 
-HARNESS = os.path.join(ROOT, "tests", "inflate_blocks_harness.cpp")
 EFORMAT = -9
 K_BLOCK, K_FINAL, K_OVERFLOW, K_TRUNCATED = 5, 0, 3, 2
 NO_STOP = (1 << 64) - 1
@@ -29,10 +29,10 @@ class BlockStats(ctypes.Structure):
     _fields_ = [(f, u64) for f in ("pieces", "candidates", "linked", "linked_from_block", "host_blocks", "host_bytes")]
 
 
-def build_harness(out_dir):
-    so = os.path.join(str(out_dir), "libinflateblocks.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_blocks():
+    """tests/inflate_blocks_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/inflate_blocks_harness.cpp")
     cp, sz = ctypes.c_char_p, ctypes.c_size_t
     L.ibh_dynamic_ref.argtypes = [cp, sz, u64]
     L.ibh_dynamic_ok.argtypes = [cp, sz, u64]
@@ -49,8 +49,8 @@ def build_harness(out_dir):
 
 
 @pytest.fixture(scope="module")
-def bh(tmp_path_factory):
-    return build_harness(tmp_path_factory.mktemp("bh"))
+def bh():
+    return load_blocks()
 
 
 def raw_deflate(data, level=9, strategy=zlib.Z_DEFAULT_STRATEGY, mem=8):

@@ -4,27 +4,27 @@ own with holes, then the holes filled) against the serial decode.  The GPU kerne
 in tests/test_gpu_unpack.py and, at its edges, in tests/test_gpu_inflate_edges.py (streams: tests/inflate_edge_streams.py,
 their shape on the CPU: tests/test_inflate_edges_host.py)."""
 import ctypes
+import functools
 import gzip
 import os
 import random
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import hostbuild
 from conftest import ROOT
 
-HARNESS = os.path.join(ROOT, "tests", "inflate_host_harness.cpp")
+HARNESS = "tests/inflate_host_harness.cpp"
 EFORMAT = -9
 
 
-@pytest.fixture(scope="module")
-def ih(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("ih") / "libinflatehost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_ih():
+    """tests/inflate_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared(HARNESS)
     P = ctypes.POINTER
     L.ih_gunzip.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_int)]
     L.ih_gunzip.restype = ctypes.c_void_p
@@ -40,6 +40,11 @@ def ih(tmp_path_factory):
     L.ih_candidates.restype = ctypes.c_size_t
     L.ih_free.argtypes = [ctypes.c_void_p]
     return L
+
+
+@pytest.fixture(scope="module")
+def ih():
+    return load_ih()
 
 
 def _take(L, p, n):
@@ -258,16 +263,11 @@ def test_concatenated_members_and_every_header_field(ih):
     assert gunzip(ih, member(a, 0) + b"\x00")[0] == EFORMAT  # trailing bytes that are no member
 
 
-def test_f3_model_archives(ih, tmp_path):
+def test_f3_model_archives(ih):
     """The compressor's CPU model (tests/deflate_model.h through the f3 harness): its archives decode, and their flush
     points cut them into segments that decode on their own."""
-    so = str(tmp_path / "libf3host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so,
-                           os.path.join(ROOT, "tests", "f3_host_harness.cpp"), "-pthread"])
-    f3 = ctypes.CDLL(so)
-    f3.f3_model_gzip.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    f3.f3_model_gzip.restype = ctypes.c_void_p
-    f3.f3_free.argtypes = [ctypes.c_void_p]
+    from test_f3_host import load_f3
+    f3 = load_f3()
     c = corpora()
     for name in ("prose", "sources", "zeros", "random", "mixed"):
         data = c[name] * 2
@@ -334,15 +334,10 @@ def test_truncated_and_mutated_streams_are_refused(ih):
 
 
 def test_inflate_host_code_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "ih_fuzz")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DIH_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, HARNESS, "-pthread"])
+    exe = hostbuild.sanitized([HARNESS], defines=["IH_MAIN"])
     c = corpora()
     data = c["prose"][:20000] + c["random"][:3000] + bytes(3000)
     raw, _ = raw_deflate(data, 6, flushes=[4000, 9000, 15000, 21000])
     gzf = tmp_path / "in.gz"
     gzf.write_bytes(b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + raw + struct.pack("<II", zlib.crc32(data), len(data)))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(gzf), "20000", "7"], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-4000:]
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    hostbuild.run_sanitized(exe, [gzf, 20000, 7], timeout=900)

@@ -9,19 +9,17 @@ walker accepts all its chunks, liblzma decodes the concatenated stretches as raw
 and reports the end.  A bit flip the walker accepts must therefore be one liblzma decodes to the same bytes; how many
 there were is printed."""
 import ctypes
-import os
 import struct
-import subprocess
 
 import pytest
 
 import lzma2_check_cases as C
-from conftest import ROOT
+import hostbuild
 
 
 @pytest.fixture(scope="module")
-def L(tmp_path_factory):
-    return C.load_harness(tmp_path_factory.mktemp("lc"))
+def L():
+    return C.load_harness()
 
 
 @pytest.fixture(scope="module")
@@ -108,9 +106,7 @@ def test_stretch_ends_come_from_the_layout(L):
 def test_walker_under_asan_and_ubsan(L, good, damaged, tmp_path):
     """Host code only, in a program of its own (tests/asan_lzma2_check.cpp): every case, each buffer on the heap at exactly
     its size, then with the buffers cut short and the tables shifted.  Its first pass's verdicts are the harness's."""
-    exe = str(tmp_path / "asan_lzma2_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_lzma2_check.cpp")])
+    exe = hostbuild.sanitized(["tests/asan_lzma2_check.cpp"])
     cases = good + damaged
     inputs = tmp_path / "streams.bin"
     with open(inputs, "wb") as f:
@@ -118,11 +114,8 @@ def test_walker_under_asan_and_ubsan(L, good, damaged, tmp_path):
             f.write(struct.pack("<QQQQ", len(c.data), len(c.z), c.nch, c.bs) + c.data + c.z + struct.pack("<%dQ" % c.nch, *c.z_beg) +
                     struct.pack("<%dQ" % c.nch, *c.z_end))
     verdicts = tmp_path / "verdicts.bin"
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(inputs), str(verdicts)], env=env, capture_output=True, text=True, timeout=900)
+    out = hostbuild.run_sanitized(exe, [inputs, verdicts], timeout=900)
     print(out.stdout[-400:])
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
     assert out.stdout.startswith("%d streams, " % len(cases))
     got = verdicts.read_bytes()
     want = b"".join(struct.pack("<II", *x) for c in cases for x in C.host_verdicts(L, c))

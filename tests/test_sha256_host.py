@@ -3,24 +3,23 @@ tail takes one block or two, the kernel's lane routine run serially -- the align
 tail at every start alignment, with every fetched word counted -- and the .xz writer's host model with each Check, read by
 liblzma.  The kernel itself: tests/test_gpu_sha256_edges.py; both sides of the library: tests/test_gpu_xz_sha256.py."""
 import ctypes
+import functools
 import hashlib
 import lzma
-import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "sha256_host_harness.cpp")
 CHECKS = {0: 0, 1: 4, 4: 8, 10: 32}  # Check id -> bytes of the field
 
 
-def load_sha(so_dir):
-    so = str(so_dir / "libsha256host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_sha(opt="-O2"):
+    """tests/sha256_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls).
+    opt: tools/sha256_bench.py times it at -O3."""
+    L = hostbuild.shared("tests/sha256_host_harness.cpp", opt)
     L.sh_sha256.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
     L.sh_sha256.restype = None
     L.sh_lane.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -47,8 +46,8 @@ def model_xz(L, data, block_size, check=None):
 
 
 @pytest.fixture(scope="module")
-def sh(tmp_path_factory):
-    return load_sha(tmp_path_factory.mktemp("sh"))
+def sh():
+    return load_sha()
 
 
 @pytest.fixture(scope="module")

@@ -3,29 +3,31 @@ every shape it refuses, ar's even-offset padding both ways, first-member and pre
 reference's ".xz" message, and the order in which the audit reports mismatches.  Everything that needs a ctx -- open,
 the decodes, audit and unpack on real packages -- is in tests/test_gpu_snap.py (snaphash_init needs a device)."""
 import ctypes
+import functools
 import hashlib
-import os
-import subprocess
 
 import pytest
 
 import snap_cases
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "snap_host_harness.cpp")
 EINVAL, EFORMAT = -1, -9
 
 
-@pytest.fixture(scope="module")
-def sh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sh") / "libsnaphost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_snap():
+    """tests/snap_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/snap_host_harness.cpp")
     L.sh_ar_parse.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
     L.sh_ar_pick.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int),
                              ctypes.c_char_p, ctypes.c_size_t]
     L.sh_audit.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     return L
+
+
+@pytest.fixture(scope="module")
+def sh():
+    return load_snap()
 
 
 def parse(L, data):

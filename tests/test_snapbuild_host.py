@@ -14,16 +14,14 @@ match one byte farther": the bound min(32 768, bytes in front) is held at 32 769
 (df_check_distance_ok) and, in streams, at its other arm -- distance 32 768 with 32 767 bytes in front is refused, with
 32 768 in front accepted -- and at distance 4 with 3 in front."""
 import ctypes
-import os
+import functools
 import struct
-import subprocess
 
 import pytest
 
 import deflate_check_streams as S
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "snapbuild_host_harness.cpp")
 EINVAL = -1
 
 HAND = S.hand_built()
@@ -31,11 +29,10 @@ VALID = S.valid_cases()
 DAMAGED = S.damaged_cases()
 
 
-@pytest.fixture(scope="module")
-def sb(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sb") / "libsnapbuildhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_sb():
+    """tests/snapbuild_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/snapbuild_host_harness.cpp")
     u64p = ctypes.POINTER(ctypes.c_uint64)
     L.sb_ar_write.argtypes = [ctypes.c_char_p, u64p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_char_p,
                               ctypes.c_size_t, u64p]
@@ -45,6 +42,11 @@ def sb(tmp_path_factory):
     L.sb_deflate_check.restype = None
     L.sb_distance_ok.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     return L
+
+
+@pytest.fixture(scope="module")
+def sb():
+    return load_sb()
 
 
 # ---- the ar writer ----------------------------------------------------------------------------------------------------
@@ -220,18 +222,13 @@ def test_table_entries_outside_the_buffer(sb):
 def test_walker_under_asan_and_ubsan(tmp_path):
     """Host code only, in a program of its own (tests/asan_deflate_check.cpp): every case, each buffer on the heap at
     exactly its size."""
-    exe = str(tmp_path / "asan_deflate_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_deflate_check.cpp")])
+    exe = hostbuild.sanitized(["tests/asan_deflate_check.cpp"])
     cases = S.all_cases()
     blob = bytearray()
     for name, data, z, z_off, final, good in cases:
         blob += struct.pack("<QQQQ", len(data), len(z), len(z_off) - 1, 1 if final else 0) + data + z + struct.pack("<%dQ" % len(z_off), *z_off)
     inputs = tmp_path / "streams.bin"
     inputs.write_bytes(bytes(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(inputs)], env=env, capture_output=True, text=True, timeout=600)
+    out = hostbuild.run_sanitized(exe, [inputs])
     print(out.stdout[-400:])
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
     assert out.stdout.startswith("%d streams, " % len(cases))

@@ -9,16 +9,14 @@ negative base-256 value in any field.
 
 The same streams through the device entry points are in tests/test_gpu_tar_edges.py."""
 import ctypes
-import os
+import functools
 import struct
-import subprocess
 
 import pytest
 
 import tar_cases as T
-from conftest import ROOT
+import hostbuild
 
-HARNESS = os.path.join(ROOT, "tests", "tar_host_harness.cpp")
 INVARIANT_BROKEN = 77
 SWEEP_CAP = 1500000  # runs of tar_read in the mutation sweep (a run is about a microsecond)
 
@@ -26,16 +24,20 @@ GOOD = T.good_cases()
 BAD = T.bad_cases()
 
 
-@pytest.fixture(scope="module")
-def th(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("th") / "libtarhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_th():
+    """tests/tar_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/tar_host_harness.cpp")
     L.th_tar_read.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
     L.th_sweep.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_uint64,
                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.th_go_clean.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t]
     return L
+
+
+@pytest.fixture(scope="module")
+def th():
+    return load_th()
 
 
 def tar_read(L, tar):
@@ -146,15 +148,10 @@ def test_go_clean_against_normpath(th):
 def test_tar_read_under_asan_and_ubsan(tmp_path):
     """Host code only, in a program of its own (tests/asan_tarread.cpp): every case, and the sweep's field values on every
     block of every case, each stream in a heap buffer of exactly its size."""
-    exe = str(tmp_path / "asan_tarread")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_tarread.cpp")])
+    exe = hostbuild.sanitized(["tests/asan_tarread.cpp"])
     inputs = tmp_path / "archives.bin"
     archives = [c[1] for c in BAD + GOOD]
     inputs.write_bytes(b"".join(struct.pack("<Q", len(a)) + a for a in archives))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(inputs)], env=env, capture_output=True, text=True, timeout=600)
+    out = hostbuild.run_sanitized(exe, [inputs])
     print(out.stdout[-400:])
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
     assert out.stdout.startswith("%d archives, " % len(archives)) and out.stdout.rstrip().endswith(" 0 broke the invariant")

@@ -5,14 +5,15 @@ histogram showing that each edge shape really occurred; the kernel's wave-copy i
 CRC-64 core against the bitwise routine; and the bad cases once more under ASan/UBSan.  The GPU kernel that runs the same
 header is checked in tests/test_gpu_unxz.py and tests/test_gpu_xz_edges.py."""
 import ctypes
+import functools
 import hashlib
 import os
 import random
-import subprocess
 
 import pytest
 
 import xz_cases as X
+import hostbuild
 from conftest import ROOT
 
 HARNESS = os.path.join(ROOT, "tests", "xz_host_harness.cpp")
@@ -23,11 +24,10 @@ H_LC, H_LP, H_PB, H_CHUNK_1, H_CHUNK_2M, H_CHUNK_BIG, H_N = 282, 287, 292, 297, 
 POLY = 0xC96C5795D7870F42
 
 
-@pytest.fixture(scope="module")
-def xh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("xh") / "libxzhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_xh():
+    """tests/xz_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared(HARNESS)
     P = ctypes.POINTER
     L.xh_decode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint, P(ctypes.c_size_t), P(ctypes.c_int)]
     L.xh_decode.restype = ctypes.c_void_p
@@ -41,6 +41,11 @@ def xh(tmp_path_factory):
         getattr(L, f).restype = ctypes.c_uint64
     L.xh_sha256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
     return L
+
+
+@pytest.fixture(scope="module")
+def xh():
+    return load_xh()
 
 
 def decode(L, z, threads=4):
@@ -164,12 +169,11 @@ def test_sha256(xh):
 def test_xz_host_code_under_asan_and_ubsan(tmp_path):
     """Host code only: every bad and unsupported file and the small good ones through an instrumented build, each from a
     heap buffer of exactly its size."""
-    exe = str(tmp_path / "xh_asan")
     main = tmp_path / "main.cpp"
     main.write_text('#include "%s"\n#include <stdio.h>\nint main(int argc, char** argv) { for (int i = 1; i < argc; ++i) { FILE* f = fopen(argv[i], "rb"); '
                     'std::vector<uint8_t> z(1 << 22); size_t n = fread(z.data(), 1, z.size(), f); fclose(f); z.resize(n); std::vector<uint8_t> exact(z); '
                     'size_t ol; int rc; void* p = xh_decode(exact.data(), exact.size(), 2, &ol, &rc); xh_free(p); printf("%%d\\n", rc); } return 0; }\n' % HARNESS)
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, str(main), "-pthread"])
+    exe = hostbuild.sanitized([main])
     files, want = [], []
     cases = [(n, z, EFORMAT) for n, z, _ in X.bad_cases()] + [(n, z, EINVAL) for n, z in X.unsupported_cases()]
     cases += [(n, z, 0) for n, z, _ in X.good_cases() if len(z) < 100000]
@@ -178,8 +182,5 @@ def test_xz_host_code_under_asan_and_ubsan(tmp_path):
         p.write_bytes(z)
         files.append(str(p))
         want.append(rc)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe] + files, env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-4000:]
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    out = hostbuild.run_sanitized(exe, files)
     assert [int(x) for x in out.stdout.split()] == want

@@ -9,6 +9,7 @@ tests/test_gpu_xzenc_edges.py; the tests from test_the_models_stages_make_the_mo
 that (last Blocks of a few bytes, tiles of many hash groups, two values of one hash, distances up to a 4 MiB Block's
 end, chunks on the stored / LZMA line at both places that decide it) are what their names say."""
 import ctypes
+import functools
 import lzma
 import os
 import random
@@ -20,10 +21,9 @@ import pytest
 
 import xz_cases as X
 import xzenc_cases as E
-from conftest import ROOT
+import hostbuild
+from test_xz_host import load_xh
 
-ENC_HARNESS = os.path.join(ROOT, "tests", "xzenc_host_harness.cpp")
-DEC_HARNESS = os.path.join(ROOT, "tests", "xz_host_harness.cpp")
 # the decoder harness's histogram (xz_host_harness.cpp, test_xz_host.py)
 H_LIT, H_MATCHED_LIT, H_MATCH, H_REP, H_SHORT_REP, H_COPY, H_CTL, H_N = 0, 1, 2, 3, 7, 10, 26, 300
 # the encoder harness's statistics (xzenc_host_harness.cpp)
@@ -35,10 +35,10 @@ FILL = 0xA5          # what stages() puts where the encoder writes nothing
 P = ctypes.POINTER
 
 
-def load_enc(so_dir):
-    so = os.path.join(str(so_dir), "libxzenchost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, ENC_HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
+@functools.lru_cache(maxsize=None)
+def load_enc():
+    """tests/xzenc_host_harness.cpp, loaded once a process with every prototype (it keeps no state between calls)."""
+    L = hostbuild.shared("tests/xzenc_host_harness.cpp")
     L.xe_encode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64, P(ctypes.c_size_t), P(ctypes.c_int)]
     L.xe_encode.restype = ctypes.c_void_p
     L.xe_free.argtypes = [ctypes.c_void_p]
@@ -141,20 +141,13 @@ def controls(raw):
 
 
 @pytest.fixture(scope="module")
-def xe(tmp_path_factory):
-    return load_enc(tmp_path_factory.mktemp("xe"))
+def xe():
+    return load_enc()
 
 
 @pytest.fixture(scope="module")
-def xh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("xh") / "libxzhost.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, DEC_HARNESS, "-pthread"])
-    L = ctypes.CDLL(so)
-    L.xh_decode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint, P(ctypes.c_size_t), P(ctypes.c_int)]
-    L.xh_decode.restype = ctypes.c_void_p
-    L.xh_free.argtypes = [ctypes.c_void_p]
-    L.xh_hist.argtypes = [ctypes.c_char_p, ctypes.c_size_t, P(ctypes.c_uint64)]
-    return L
+def xh():
+    return load_xh()
 
 
 @pytest.fixture(scope="module")
@@ -362,18 +355,13 @@ def test_range_encoder_against_the_python_one(xe):
 def test_xzenc_host_model_under_asan_and_ubsan(tmp_path):
     """Host code only, in a program of its own (tests/asan_xzenc.cpp): the model over every input, each from a heap
     buffer of exactly its size, and the host decoder over what it wrote."""
-    exe = str(tmp_path / "asan_xzenc")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(ROOT, "tests", "asan_xzenc.cpp"), "-pthread"])
+    exe = hostbuild.sanitized(["tests/asan_xzenc.cpp"])
     args = []
     for i, (name, data, bs) in enumerate(E.cases()):
         p = tmp_path / ("c%02d" % i)
         p.write_bytes(data)
         args += [str(p), str(bs)]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe] + args, env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
+    out = hostbuild.run_sanitized(exe, args)
     assert out.stdout.split() == ["ok"] * len(E.cases())
 
 

@@ -2,7 +2,6 @@
 """GPU DEFLATE against its CPU model, sample by sample: sizes, first differing byte, whether zlib inflates either."""
 import ctypes
 import os
-import subprocess
 import sys
 import zlib
 
@@ -12,13 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context  # noqa: E402
+from test_f3_host import load_f3, sample_inputs  # noqa: E402
 
-so = "/tmp/f3_harness.so"
-subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp"), "-pthread"])
-f3 = ctypes.CDLL(so)
-f3.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-f3.f3_model_gzip2.restype = ctypes.c_void_p
-f3.f3_free.argtypes = [ctypes.c_void_p]
+f3 = load_f3()
 
 rng = np.random.default_rng(7)
 words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 9)), dtype=np.uint8)) for _ in range(500)]
@@ -27,7 +22,6 @@ samples = {"one": b"x", "three": b"abc", "abcabc": b"abcabcabcabc", "64 x": b"x"
            "prose 100": prose[:100], "prose 4000": prose[:4000], "prose 4200": prose[:4200], "prose 9000": prose[:9000],
            "prose 65536": prose[:65536], "prose 70000": prose[:70000], "prose 200000": prose[:200000],
            "random 50000": rng.integers(0, 256, size=50000, dtype=np.uint8).tobytes()}
-from test_f3_host import sample_inputs  # noqa: E402
 samples = dict(sample_inputs())
 samples["3 MiB mixed"] = (b"snappy " * 100000 + rng.integers(0, 256, size=1 << 20, dtype=np.uint8).tobytes() + bytes(1 << 20))[:3 << 20]
 with Context(staging_bytes=1 << 20) as c:

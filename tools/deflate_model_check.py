@@ -3,23 +3,18 @@
 use, twice (run-to-run determinism).  usage: tools/deflate_model_check.py [MiB]"""
 import ctypes
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context  # noqa: E402
+from test_f3_host import load_f3  # noqa: E402
 
 mib = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-so = os.path.join(tempfile.mkdtemp(), "libf3host.so")
-subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp")])
-L = ctypes.CDLL(so)
-L.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-L.f3_model_gzip2.restype = ctypes.c_void_p
-L.f3_free.argtypes = [ctypes.c_void_p]
+L = load_f3()
 rng = np.random.default_rng(5)
 words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 10)), dtype=np.uint8)) for _ in range(2000)]
 block = b" ".join(words[int(i)] for i in rng.zipf(1.3, size=(4 << 20) // 5 + 16) % 2000)[:4 << 20]

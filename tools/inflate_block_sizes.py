@@ -8,7 +8,6 @@ import argparse
 import json
 import os
 import sys
-import tempfile
 import zlib
 
 import numpy as np
@@ -16,7 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from test_inflate_blocks_host import blocks, build_harness  # noqa: E402
+from test_inflate_blocks_host import blocks, load_blocks  # noqa: E402
 from unpack_bench import corpora  # noqa: E402
 
 
@@ -26,7 +25,7 @@ def main():
     ap.add_argument("--out")
     a = ap.parse_args()
     fh = open(a.out, "w") if a.out else None
-    L = build_harness(tempfile.mkdtemp())
+    L = load_blocks()
     for name, data in corpora(64 << 20).items():
         data = data[: a.size << 20]
         for level in (1, 6, 9):

@@ -16,9 +16,7 @@ import ctypes
 import hashlib
 import lzma
 import os
-import subprocess
 import sys
-import tempfile
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -31,6 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context, _lib  # noqa: E402
 from unpack_bench import corpora, emit  # noqa: E402
 import xz_cases  # noqa: E402
+from test_sha256_host import load_sha  # noqa: E402
 
 SHAPES = ((16, 4 << 20), (64, 1 << 20), (1024, 64 << 10))
 
@@ -45,22 +44,13 @@ def best(fn, reps):
     return min(t), max(t), out
 
 
-def host_sha256(tmp):
-    so = os.path.join(tmp, "libsha256host.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "sha256_host_harness.cpp"), "-pthread"])
-    L = ctypes.CDLL(so)
-    L.sh_sha256.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
-    L.sh_sha256.restype = None
-    return L
-
-
-def kernel_leg(g, size, reps, fh, tmp):
+def kernel_leg(g, size, reps, fh):
     import torch
     host = np.random.default_rng(1).integers(0, 256, size, dtype=np.uint8)
     data = host.tobytes()
     dev = torch.from_numpy(host).cuda()
     torch.cuda.synchronize()
-    L = host_sha256(tmp)
+    L = load_sha("-O3")
     out = ctypes.create_string_buffer(32)
     t_py, t_py_max, want = best(lambda: hashlib.sha256(data).digest(), reps)
     t_host, t_host_max, _ = best(lambda: L.sh_sha256(data, len(data), out), reps)
@@ -131,9 +121,9 @@ def main():
     fh = open(a.out, "w") if a.out else None
     legs = a.legs.split(",")
     size = (8 << 20) if a.quick else (64 << 20)
-    with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, tempfile.TemporaryDirectory(prefix="sha256bench") as tmp:
+    with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
         if "kernel" in legs:
-            kernel_leg(g, size, a.reps, fh, tmp)
+            kernel_leg(g, size, a.reps, fh)
         if "unxz" in legs or "xz" in legs:
             data = corpora(size)["text"]
             if "unxz" in legs:

@@ -6,7 +6,6 @@ serial CPU model byte for byte.  The workgroup's pipeline hands tiles out from q
 race would show here as a rare mismatch.  usage: tools/soak_deflate.py [seconds]"""
 import ctypes
 import os
-import subprocess
 import sys
 import time
 import zlib
@@ -15,17 +14,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context  # noqa: E402
+from test_f3_host import load_f3  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-so = "/tmp/f3_harness_soak.so"
-subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp"), "-pthread"])
-f3 = ctypes.CDLL(so)
-f3.f3_model_gzip2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-f3.f3_model_gzip2.restype = ctypes.c_void_p
-f3.f3_model_gzip3.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t)]
-f3.f3_model_gzip3.restype = ctypes.c_void_p
-f3.f3_free.argtypes = [ctypes.c_void_p]
+f3 = load_f3()
 rng = np.random.default_rng(int(os.environ.get("SOAK_SEED", "1")))
 
 

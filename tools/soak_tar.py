@@ -5,23 +5,20 @@ the archive inflates to the tar stream the host model lays out, archive digest =
 usage: tools/soak_tar.py [seconds=240] [seed=1] [mixed]
 "mixed" (round 5): small packages (0.05-40 MiB, what most snaps are) between the large ones, in ONE ctx: the producer's buffers are
 sized for the job and grow when a later one needs more, and long members are hashed by host threads out of the staging slots."""
-import ctypes, gzip, hashlib, os, shutil, subprocess, sys, tempfile, time
+import ctypes, gzip, hashlib, os, shutil, sys, tempfile, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from snappy_amd import Context  # noqa: E402
 from oracle import oracle  # noqa: E402  (the checker)
+from test_f3_host import load_f3  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 mixed = len(sys.argv) > 3 and sys.argv[3] == "mixed"
 tmp = tempfile.mkdtemp(prefix="snaphash_soaktar_", dir="/dev/shm")
-sodir = tempfile.mkdtemp(prefix="snaphash_soaktar_so_")  # (/dev/shm is mounted noexec on the GPU box)
-so = os.path.join(sodir, "libf3host.so")
-subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "f3_host_harness.cpp")])
-L = ctypes.CDLL(so)
-L.f3_tar_stream.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-L.f3_free.argtypes = [ctypes.c_void_p]
+L = load_f3()
 MiB = 1 << 20
 pool = rng.integers(0, 256, size=64 * MiB, dtype=np.uint8)
 words = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 10)), dtype=np.uint8)) for _ in range(400)]
@@ -75,4 +72,3 @@ try:
           "digest = hashlib, hashes.yaml = the oracle's" % (it, total / 2**30, "0.05-40 MiB and 70-400 MiB mixed in one ctx" if mixed else "70-400 MiB each"))
 finally:
     shutil.rmtree(tmp, ignore_errors=True)
-    shutil.rmtree(sodir, ignore_errors=True)
