@@ -535,7 +535,8 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
     if (n == 0) return SNAPHASH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t job_bytes = 0;
-    for (const Source& sc : src) job_bytes += sc.gpu_len;
+    bool empty_files = false; // a file of no bytes has no segment to read, but it is opened and probed like any other (below)
+    for (const Source& sc : src) { job_bytes += sc.gpu_len; empty_files |= sc.len == 0 && sc.path != nullptr; }
     const bool from_memory = src[0].mem != nullptr;
     const uint64_t slot_caps[3] = {c->slot[0].cap(), c->slot[1].cap(), c->slot[2].cap()};
     const BatchGeometry g = batch_geometry(job_bytes, n, c->staging, slot_caps, from_memory);
@@ -576,6 +577,14 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         c->stats.blocks += b.blocks;
         static const bool trace_batches = getenv("SNAPHASH_TRACE_BATCHES") != nullptr; // (read once, not once a batch)
         if (trace_batches) trace_batch(stderr, c->index, batch, b, sl.jobs.h.data(), (uint64_t)(uintptr_t)sl_d, plan.active.size());
+        // The reference's loop opens an empty file too (os.Open, io.Copy to EOF): one that is gone, a directory now or no longer
+        // empty fails the call.  The planner gives it one segment of no bytes and no read; its open and its probe for a first
+        // byte join the batch's reads here (a read of length 0 that goes to EOF).
+        if (empty_files)
+            for (size_t k = 0; k < b.nj; ++k) {
+                const Job& j = sl.jobs.h[k];
+                if (j.nbytes == 0 && src[j.idx].len == 0 && src[j.idx].path) ops.push_back(ReadOp{j.idx, 0, 0, sl_h, true});
+            }
         const double tb2 = now_ms();
         t_plan += tb2 - tb1;
 
@@ -843,8 +852,10 @@ void begin_top(snaphash_ctx* x)
 
 bool keep_on_device_planned(const snaphash_ctx* x, size_t nd) { return nd > 1 || (x->flags & SNAPHASH_FLAG_FORCE_GATHER); }
 
-int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests, int32_t* status)
+// bad_out (may be NULL): the index of the source the call failed at (SNAPHASH_EIO), or -1.
+int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests, int32_t* status, int64_t* bad_out = nullptr)
 {
+    if (bad_out) *bad_out = -1;
     const size_t n = src.size();
     if (status) for (size_t i = 0; i < n; ++i) status[i] = 0;
     if (n == 0) return SNAPHASH_OK;
@@ -1038,6 +1049,7 @@ int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests
     if (bad_rc) {
         if (bad_dev) x->last_error = bad_dev->last_error;
         if (status && bad >= 0 && bad < (int64_t)n) status[bad] = bad_errno;
+        if (bad_out && bad >= 0 && bad < (int64_t)n) *bad_out = bad;
         merge_stats(x);
         return bad_rc;
     }
@@ -1065,7 +1077,9 @@ int hash_sources_top(snaphash_ctx* x, std::vector<Source>& src, uint8_t* digests
 // is read fails the call (io.Copy reads to EOF: the record's size and digest must describe the same bytes).
 // os.Open follows symlinks (helpers.go:189); a directory opens but its read fails with EISDIR.  The first path
 // (in list order) that cannot be hashed, or -1; what the reference's serial loop would have stopped at.
-static int64_t first_bad_path(const char* const* paths, size_t n, int* err)
+// src (may be NULL): the lengths the pass read with; a file whose length is another now is what io.Copy would have
+// tripped over (EIO, as do_read_op reports it).
+static int64_t first_bad_path(const char* const* paths, size_t n, int* err, const Source* src = nullptr)
 {
     for (size_t i = 0; i < n; ++i) {
         struct stat st;
@@ -1073,6 +1087,7 @@ static int64_t first_bad_path(const char* const* paths, size_t n, int* err)
         if (stat(paths[i], &st) != 0) e = errno;
         else if (S_ISDIR(st.st_mode)) e = EISDIR;
         else if (access(paths[i], R_OK) != 0) e = errno;
+        else if (src && S_ISREG(st.st_mode) && (uint64_t)st.st_size != src[i].len) e = EIO;
         if (e) { *err = e; return (int64_t)i; }
     }
     return -1;
@@ -1115,12 +1130,15 @@ int hash_paths(snaphash_ctx* x, const char* const* paths, size_t n, const int64_
             return fail(x, SNAPHASH_EIO, std::string(paths[b]) + ": " + strerror(err));
         }
     }
-    const int rc = hash_sources_top(x, src, digests, status);
+    int64_t tripped = -1;
+    const int rc = hash_sources_top(x, src, digests, status, &tripped);
     if (rc == SNAPHASH_EIO) {
-        // Which file a parallel pass trips over first is a matter of timing; the reference's serial loop stops at the
-        // first one in order.  Name that one, if an ordered look finds it.
+        // Which file a parallel pass trips over first is a matter of timing (a long file that lost its last byte fails in
+        // its last batch, a missing one behind it in the batch that begins it); the reference's serial loop stops at the
+        // first one in order.  Name that one, if an ordered look over the files in front of the one that failed finds it:
+        // gone, a directory, unreadable, or of another length than the pass read with.  On this path only.
         int err = 0;
-        const int64_t bad = first_bad_path(paths, n, &err);
+        const int64_t bad = first_bad_path(paths, tripped >= 0 ? std::min(n, (size_t)tripped + 1) : n, &err, src.data());
         if (bad >= 0) {
             if (status) { for (size_t k = 0; k < n; ++k) status[k] = 0; status[bad] = err; }
             return fail(x, SNAPHASH_EIO, std::string(paths[bad]) + ": " + strerror(err));

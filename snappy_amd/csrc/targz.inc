@@ -667,6 +667,9 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
         }
         for (const TarSegment& sg : segs) {
             if (sg.n) ops.push_back(ReadOp{sg.member, sg.file_off, sg.n, sl.h_buf.data() + sg.slot_off, sg.fin});
+            // an empty member is opened and probed all the same (os.Open, io.Copy to EOF): gone, a directory now or no longer
+            // empty, it fails the pass like any other; no byte is read, the address (its header's) only keeps the list in order
+            else ops.push_back(ReadOp{sg.member, 0, 0, sl.h_buf.data() + (sg.slot_off >= 512 ? sg.slot_off - 512 : 0), true});
             if (fused && hosted_of[sg.member] != 0xffffffffu) {
                 host_tasks.push_back(MemberHashers::Task{hosted_of[sg.member], sl.h_buf.data() + (sg.n ? sg.slot_off : 0), sg.n, sg.first, sg.fin, slot_no});
             } else if (fused && stream_of[sg.member] != 0xffffffffu) {

@@ -5,6 +5,7 @@
 //   batchplan_host plan SPEC    SPEC is a text file:  staging from_memory cap0 cap1 cap2
 //                                                     new_cap hold_back ramp_shift ramp_first64 ramp_growth_pct
 //                                                     n, then n lines "len gpu_len"
+//   batchplan_host segments SPEC  the same, and a line "seg BATCH STREAM TOTAL_PREV NBYTES FLAGS" for every segment
 //   batchplan_host knobs        prints BatchKnobs::from_env()
 #include <inttypes.h>
 #include <stdio.h>
@@ -27,7 +28,7 @@ using namespace snaphash;
         }                                                                      \
     } while (0)
 
-static int plan(const char* spec)
+static int plan(const char* spec, bool segments)
 {
     FILE* f = fopen(spec, "r");
     CHECK(f, "cannot open %s", spec);
@@ -105,7 +106,8 @@ static int plan(const char* spec)
             if (!last) CHECK(j.nbytes > 0 && j.nbytes % 128 == 0, "batch %u stream %u: a segment that is not the last is whole blocks (%" PRIu64 ")", batch, j.idx, j.nbytes);
             if (j.nbytes == 0) CHECK(s.gpu_len == 0 && s.len == 0, "batch %u stream %u: an empty segment of a non-empty stream", batch, j.idx);
             blocks += padded_blocks(j.nbytes, fin);
-            if (j.nbytes) { // its read
+            if (segments) printf("seg %u %u %" PRIu64 " %" PRIu64 " %u\n", batch, j.idx, j.total_prev, j.nbytes, j.flags);
+            if (j.nbytes) { // its read (the PLANNER's reads: the engine adds an open-and-probe of its own for an empty file, hash_sources)
                 CHECK(op < ops.size(), "batch %u: a segment without a read", batch);
                 const ReadOp& r = ops[op++];
                 CHECK(r.src == j.idx && r.off == j.total_prev && r.n == j.nbytes && (uint64_t)(uintptr_t)r.dst == h_base + at, "batch %u stream %u: read", batch, j.idx);
@@ -141,12 +143,13 @@ static int plan(const char* spec)
 
 int main(int argc, char** argv)
 {
-    if (argc == 3 && !strcmp(argv[1], "plan")) return plan(argv[2]);
+    if (argc == 3 && !strcmp(argv[1], "plan")) return plan(argv[2], false);
+    if (argc == 3 && !strcmp(argv[1], "segments")) return plan(argv[2], true);
     if (argc == 2 && !strcmp(argv[1], "knobs")) {
         const BatchKnobs k = BatchKnobs::from_env();
         printf("new_cap %zu hold_back %d ramp_shift %u ramp_first64 %u ramp_growth_pct %u\nknobs ok\n", k.new_cap, (int)k.hold_back, k.ramp_shift, k.ramp_first64, k.ramp_growth_pct);
         return 0;
     }
-    fprintf(stderr, "usage: %s plan SPEC | knobs\n", argv[0]);
+    fprintf(stderr, "usage: %s plan SPEC | segments SPEC | knobs\n", argv[0]);
     return 2;
 }

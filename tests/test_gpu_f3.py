@@ -151,7 +151,7 @@ def test_fused_build_pass_reads_once_and_matches_writehashes(built_lib, oracle, 
 
 def test_tar_create_error_paths_leave_no_archive_and_a_usable_ctx(built_lib, oracle, tmp_path):
     """tarCreate's error behaviour (clickdeb/deb.go:286-289, 331-339: the first Lstat/Open/Copy error ends the walk
-    and is returned) through the pipelined producer: an unreadable file in a later staging slot, an output that
+    and is returned) through the pipelined producer: a file that is gone when its staging slot is filled, an output that
     cannot be written (the writer thread's ENOSPC), a name the ustar header cannot hold, an empty tree -- after each
     failure no partial archive is left behind and the same ctx still produces a correct one."""
     from snappy_amd import Context, _lib
@@ -163,13 +163,24 @@ def test_tar_create_error_paths_leave_no_archive_and_a_usable_ctx(built_lib, ora
         good_yaml, _ = c.tar_create(out, build, build + "/DEBIAN", with_hashes=True)
         assert good_yaml == oracle.hashes_yaml(build, out)
         os.unlink(out)
-        # 1. a file that cannot be opened (skipped when running as root, who can read anything)
+        # 1. a file that cannot be opened any more when the pipeline gets to it, in a later staging slot: it is unlinked from the
+        # keep callback, which runs after the walk has Lstat'ed everything and before the output is opened or a byte is read
+        # (root can read anything, so a chmod would not do; the other mutations: tests/test_gpu_changed_files.py)
         victim = sorted(p for p in (os.path.join(dp, f) for dp, _, fs in os.walk(build) for f in fs))[-1]
-        os.chmod(victim, 0)
-        if os.geteuid() != 0:
-            with pytest.raises(_lib.SnaphashError) as ei:
-                c.tar_create(out, build, build + "/DEBIAN", with_hashes=True)
-            assert ei.value.code == _lib.EIO and os.path.basename(victim) in str(ei.value) and not os.path.exists(out)
+        saved, fired = open(victim, "rb").read(), []
+
+        def keep(path):
+            if path == build:  # the root is asked first
+                os.unlink(victim)
+                fired.append(path)
+            return path != build + "/DEBIAN"
+        good_yaml, _ = c.tar_create(out, build, build + "/DEBIAN", with_hashes=True)  # a good archive lies at the path
+        with pytest.raises(_lib.SnaphashError) as ei:
+            c.tar_create_fn(out, build, keep, with_hashes=True)
+        assert fired == [build]
+        assert ei.value.code == _lib.EIO and victim in str(ei.value) and "No such file" in str(ei.value) and not os.path.exists(out)
+        with open(victim, "wb") as f:
+            f.write(saved)
         os.chmod(victim, 0o644)
         # 2. the output cannot take the bytes: the writer thread's error comes back, with errno's text
         full = str(tmp_path / "full.tar.gz")
