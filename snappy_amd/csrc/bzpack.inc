@@ -56,30 +56,24 @@ int bz2_check_run(DevCtx* c, const uint8_t* d_z, uint64_t n_z, const uint8_t* d_
     if (count == 0) return SNAPHASH_OK;
     HIP_TRY(c, c->bz.ensure(0, std::min(count, kBz2CheckGroup), c->numa_node));
     Bzip2Bufs& z = c->bz;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    if (stage_ms)
-        for (hipEvent_t& e : ev) HIP_TRY(c, hipEventCreate(&e));
+    StageClock<4> clk; // (off without stage_ms: its marks do nothing then)
+    if (stage_ms) HIP_TRY(c, clk.enable());
     for (uint32_t g0 = 0; g0 < count; g0 += kBz2CheckGroup) {
         const uint32_t nb = std::min(kBz2CheckGroup, count - g0);
         if (nb > z.nslots()) return fail(c, SNAPHASH_EDEVICE, "bzip2: the self-check's scratch is smaller than its group");
-        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[0], s));
+        HIP_TRY(c, clk.mark(0, s));
         HIP_TRY(c, launch_bz2_check_symbols(d_z, n_z, n_in, d_jobs + g0, level, nb, z.d_slots.data(), z.d_res.data(), s));
-        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[1], s));
+        HIP_TRY(c, clk.mark(1, s));
         HIP_TRY(c, launch_bz2_check_link(z.d_res.data(), d_jobs + g0, n_z, n_in, level, nb, z.d_blk.data(), d_verdicts + g0, s));
-        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[2], s));
+        HIP_TRY(c, clk.mark(2, s));
         HIP_TRY(c, launch_bz_ibwt(z.d_slots.data(), z.d_tt.data(), z.d_blk.data(), nb, s));
         HIP_TRY(c, launch_bz_rle1_count(z.d_slots.data(), z.d_blk.data(), z.d_chunks.data(), nb, s));
-        if (stage_ms) HIP_TRY(c, hipEventRecord(ev[3], s));
+        HIP_TRY(c, clk.mark(3, s));
         HIP_TRY(c, launch_bz2_check_compare(z.d_slots.data(), z.d_blk.data(), z.d_chunks.data(), d_in, d_jobs + g0, nb, d_verdicts + g0, s));
         if (stage_ms) {
-            HIP_TRY(c, hipEventRecord(ev[4], s));
+            HIP_TRY(c, clk.mark(4, s));
             HIP_TRY(c, hipStreamSynchronize(s));
-            for (int i = 0; i < 4; ++i) {
-                float ms = 0;
-                (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-                stage_ms[i] += ms;
-            }
+            for (int i = 0; i < 4; ++i) stage_ms[i] += clk.ms(i);
         }
     }
     return SNAPHASH_OK;
@@ -142,15 +136,13 @@ int bz_self_check_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, uint32_t 
     for (uint32_t k = 0; k < nblk; ++k) b.ckjobs.h[k] = Bz2CheckJob{b.dst.h[k], k + 1 < nblk ? b.dst.h[k + 1] : at, offs[k], lens[k], crcs[k], 0};
     HIP_TRY(c, hipMemcpyAsync(b.ckjobs.d.data(), b.ckjobs.h.data(), (size_t)nblk * sizeof(Bz2CheckJob), hipMemcpyHostToDevice, zs));
     HIP_TRY(c, hipMemsetAsync(b.chk.d.data(), 0xff, (size_t)nblk * sizeof(Bz2Verdict), zs)); // (a verdict that is not written is a refusal)
-    EventPair* e = next_events(c, 3);
-    if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const EventPair ev = *e;
     float stage_ms[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipEventRecord(ev.a, zs));
-    const int rc = bz2_check_run(c, (const uint8_t*)b.d_out.data(), out_words * 4, sl.d_buf.data(), n, b.ckjobs.d.data(), nblk, z.level, b.chk.d.data(),
+    Span ev;
+    int rc = span_begin(c, Ev::Check, zs, &ev);
+    if (!rc) rc = bz2_check_run(c, (const uint8_t*)b.d_out.data(), out_words * 4, sl.d_buf.data(), n, b.ckjobs.d.data(), nblk, z.level, b.chk.d.data(),
                                  zs, trace ? stage_ms : nullptr);
+    if (!rc) rc = span_end(c, ev, zs);
     if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(ev.b, zs));
     HIP_TRY(c, hipMemcpyAsync(b.chk.h.data(), b.chk.d.data(), (size_t)nblk * sizeof(Bz2Verdict), hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
     if (trace)
@@ -196,16 +188,12 @@ int bz_process_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     const BzEncScratch s = b.scratch();
     HIP_TRY(c, hipMemcpyAsync(b.jobs.d.data(), b.jobs.h.data(), (size_t)nblk * sizeof(BzEncJob), hipMemcpyHostToDevice, zs));
     const bool trace = getenv("SNAPHASH_TRACE_BZ2") != nullptr; // the stages one by one (tools/bzip2_enc_bench.py reads the line)
-    hipEvent_t stage_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{stage_ev};
-    if (trace)
-        for (hipEvent_t& e : stage_ev) HIP_TRY(c, hipEventCreate(&e));
-    EventPair* evp = next_events(c, 2);
-    if (!evp) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const EventPair ev = *evp; // (by value: the pool may grow)
-    HIP_TRY(c, hipEventRecord(ev.a, zs));
-    HIP_TRY(c, launch_bzenc_blocks(sl.d_buf.data(), b.jobs.d.data(), s, nblk, zs, trace ? stage_ev : nullptr));
-    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    StageClock<4> stages; // (launch_bzenc_blocks records them itself, between its kernels)
+    if (trace) HIP_TRY(c, stages.enable());
+    Span ev, ev2;
+    if ((rc = span_begin(c, Ev::Codec, zs, &ev))) return rc;
+    HIP_TRY(c, launch_bzenc_blocks(sl.d_buf.data(), b.jobs.d.data(), s, nblk, zs, stages.raw()));
+    if ((rc = span_end(c, ev, zs))) return rc;
     HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nblk * sizeof(BzEncRes), hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
     // where every block goes: behind the bits the last slot left
@@ -223,19 +211,14 @@ int bz_process_slot(OutPipe& g, BzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
     uint8_t* h = b.h_out[zbuf].data();
     HIP_TRY(c, hipMemcpyAsync(b.dst.d.data(), b.dst.h.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, zs));
-    EventPair* evp2 = next_events(c, 2);
-    if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const EventPair ev2 = *evp2;
-    HIP_TRY(c, hipEventRecord(ev2.a, zs));
+    if ((rc = span_begin(c, Ev::Codec, zs, &ev2))) return rc;
     HIP_TRY(c, launch_bzenc_concat(s, b.dst.d.data(), nblk, b.d_out.data(), out_words, z.carry, zs));
-    HIP_TRY(c, hipEventRecord(ev2.b, zs));
+    if ((rc = span_end(c, ev2, zs))) return rc;
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), (size_t)out_words * 4, hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
     if (z.self_check && (rc = bz_self_check_slot(g, z, sl, n, nblk, at, out_words, offs, lens, crcs, trace)) != SNAPHASH_OK) return rc;
     if (trace) {
-        float ms[4] = {0, 0, 0, 0}, cat = 0;
-        for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], stage_ev[i], stage_ev[i + 1]);
-        (void)hipEventElapsedTime(&cat, ev2.a, ev2.b);
+        const float ms[4] = {stages.ms(0), stages.ms(1), stages.ms(2), stages.ms(3)}, cat = span_ms(ev2);
         fprintf(stderr, "snaphash bz2: slot of %llu bytes, %u blocks: crc %.3f ms, rle1 %.3f ms, bwt %.3f ms, mtf %.3f ms, code %.3f ms, concat %.3f ms\n",
                 (unsigned long long)n, nblk, crc_ms, ms[0], ms[1], ms[2], ms[3], cat);
     }

@@ -15,6 +15,7 @@
 #include "deflate_check_kernels.h"
 #include "deflate_kernels.h"
 #include "devbuf.h"
+#include "gpu_handles.h"
 #include "inflate_core.h"
 #include "inflate_kernels.h"
 #include "lzma2_check_kernels.h"
@@ -52,8 +53,8 @@ struct Slot {
     HostBuf<uint8_t> h_buf;
     DevBuf<uint8_t> d_buf;
     JobBufs jobs;
-    hipEvent_t done = nullptr;   // kernel of the batch staged in this slot has finished
-    hipEvent_t copied = nullptr; // H2D of this slot's data + jobs has finished
+    Event done;   // kernel of the batch staged in this slot has finished
+    Event copied; // H2D of this slot's data + jobs has finished
     bool busy = false;
     uint64_t cap() const { return h_buf.size(); } // bytes both hold (the engine's staging size, or less while only small jobs have come by)
     hipError_t ensure(uint64_t bytes, int node)
@@ -72,8 +73,8 @@ struct Slot {
 // copy and kernel are three stages of equal length and only many small batches in flight keep all three busy.
 struct SubSlot {
     JobBufs jobs;
-    hipEvent_t done = nullptr;   // kernel of the batch staged here has finished
-    hipEvent_t copied = nullptr; // H2D of this batch's jobs has finished
+    Event done;   // kernel of the batch staged here has finished
+    Event copied; // H2D of this batch's jobs has finished
     bool busy = false;
 };
 

@@ -58,7 +58,7 @@ int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool k
         DecodedStream ds(c, t.tar, keep_dev);
         // under SNAPHASH_FLAG_GPU_ONLY the stream reaches HBM before host memory: the CRCs are taken there
         t.rc = kSnapCodecs[codec]->decode(x, c, z, zn, ds, t.st, x->gpu_only ? CrcAt::Device : CrcAt::Host, &s->tally);
-        c->ev_used = 0;
+        scratch_spans_done(c);
     }
     (&t == &s->data ? s->stats.data_decodes : s->stats.control_decodes)++;
     s->stats.device_crc_ranges = s->tally.device_ranges;

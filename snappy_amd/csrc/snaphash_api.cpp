@@ -40,6 +40,7 @@
 
 #include "batchplan.h"
 #include "engine_bufs.h"
+#include "gpu_handles.h"
 #include "hostfill.h"
 #include "hostpass.h"
 #include "hostsha.h"
@@ -58,8 +59,6 @@ namespace {
 
 constexpr uint64_t kDefaultStaging = 256ull << 20;
 
-struct EventPair { hipEvent_t a = nullptr, b = nullptr; int kind = 0; }; // kind 0 SHA-512 kernels, 1 h2d, 2 deflate kernels
-
 double now_ms()
 {
     using namespace std::chrono;
@@ -75,9 +74,8 @@ struct snaphash_ctx;
 struct DevCtx {
     int device = 0;
     int index = 0; // position in snaphash_ctx::dev
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipStream_t copy_stream = nullptr; // H2D of batch k+1 overlaps the kernel of batch k
+    Stream stream; // the engine's own, or the caller's (snaphash_config.stream), adopted
+    Stream copy_stream; // H2D of batch k+1 overlaps the kernel of batch k
     uint64_t staging = kDefaultStaging;
     uint32_t kernel_pref = SNAPHASH_KERNEL_AUTO;
     uint32_t deflate_depth = 0; // hash-chain links the DEFLATE search walks per position (snaphash_config.deflate_depth; 0 = kDfDepth)
@@ -90,25 +88,24 @@ struct DevCtx {
     HashBufs hash;
     Twin<CmpChunk> cmp; // the range comparison's chunk tables, in two halves (ensure_chunks)
     DeflateBufs z;
-    hipStream_t z_stream = nullptr;          // the compressor's stream
-    hipStream_t z2_stream = nullptr;         // concatenation of a finished piece and its way back to the host
-    std::vector<hipEvent_t> z_ev;            // "the sizes of piece k are on the host"
-    std::vector<hipEvent_t> z_part_ev;       // "part k of the pass's first slot is in HBM" (targz.inc)
+    Stream z_stream;                    // the compressor's stream
+    Stream z2_stream;                   // concatenation of a finished piece and its way back to the host
+    std::vector<Event> z_ev;            // "the sizes of piece k are on the host"
+    std::vector<Event> z_part_ev;       // "part k of the pass's first slot is in HBM" (targz.inc)
     InflateBufs inf;
     Bzip2Bufs bz;
     CrcBufs crc;
     Sha256Bufs sha256;
     BcjBufs bcj; // the BCJ filter kernels' (both sides of .xz)
-    EventPair bcj_ev;               // around the install side's filter launch (unxz.inc; the pool's pairs are reused by the Check calls behind it)
+    Event bcj_ev[2];                // around the install side's filter launch (unxz.inc; the ledger's pairs are reused by the Check calls behind it)
     hipStream_t bcj_busy = nullptr; // the stream that last read bcj's pinned table (bcj_ranges_dev waits for it before a rewrite)
     XzBufs xz;
     XzEncBufs xe; // the .xz producer's (xzpack.inc)
     BzEncBufs be; // the .bz2 producer's (bzpack.inc)
-    hipStream_t f_stream = nullptr; // the inflate's and the bzip2 decode's stream
+    Stream f_stream;                // the inflate's and the bzip2 decode's stream
     uint64_t fout_gen = 0;          // counts the decodes that wrote inf.d_out: a .snap session knows by it whether its stream is still there
 
-    std::vector<EventPair> ev_pool;
-    size_t ev_used = 0;
+    EventLedger ledger; // the timed spans of the call in progress (span_begin; collect_events or scratch_spans_done end it)
     bool pending = false;
 
     // host side of the staging (hostfill.h): the GPU's NUMA node, the pool of fill threads that lives there
@@ -222,38 +219,59 @@ unsigned call_cpus(const snaphash_ctx* x) { return std::max(1u, x->cpus_call ? x
                         std::string(#expr) + ": " + hipGetErrorString(e_));                          \
     } while (0)
 
-EventPair* next_events(DevCtx* c, int kind)
+// A span of the engine's ledger: span_begin takes a pair and records its first event on s, span_end records the second
+// behind what the span times.  Spans nest, and one may end on another path than it began.
+int span_take(DevCtx* c, Ev kind, Span* sp) // (the pair alone, for a launcher that records both itself: bcj_ranges_dev)
 {
-    if (c->ev_used == c->ev_pool.size()) {
-        EventPair p;
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(p);
-    }
-    EventPair* p = &c->ev_pool[c->ev_used++];
-    p->kind = kind;
-    return p;
+    return c->ledger.take(kind, sp) == hipSuccess ? SNAPHASH_OK : fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
 }
+int span_begin(DevCtx* c, Ev kind, hipStream_t s, Span* sp)
+{
+    if (int rc = span_take(c, kind, sp)) return rc;
+    HIP_TRY(c, hipEventRecord(sp->a, s));
+    return SNAPHASH_OK;
+}
+int span_end(DevCtx* c, const Span& sp, hipStream_t s)
+{
+    HIP_TRY(c, hipEventRecord(sp.b, s));
+    return SNAPHASH_OK;
+}
+// a finished span's time; 0 where the runtime does not know it
+float span_ms(const Span& sp) { float ms = 0; return hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess ? ms : 0; }
+// A call that read its spans where they ended (span_ms) keeps no ledger: the pairs were scratch, the next call starts clean.
+void scratch_spans_done(DevCtx* c) { c->ledger.clear(); }
 
-void collect_events(DevCtx* c)
+// The ledger of a call whose streams have drained, summed by kind: hashing and copies go to the engine's stats, the
+// caller adds what the codecs' and the self-check's launches took where it reports them.  The next call starts clean.
+SpanSums collect_events(DevCtx* c, bool hash_pass = true) // (a producer's call has no trace line)
 {
     static const bool trace = getenv("SNAPHASH_TRACE_EVENTS") != nullptr; // the GPU side of a call, batch by batch
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) == hipSuccess) {
-            if (c->ev_pool[i].kind == 0) c->stats.kernel_ms += ms;
-            else if (c->ev_pool[i].kind == 1) c->stats.h2d_ms += ms;
-        }
-        if (trace && c->ev_used > 1) {
+    const SpanSums sums = sum_spans(c->ledger, [](const Span& sp, float* ms) { return hipEventElapsedTime(ms, sp.a, sp.b) == hipSuccess; });
+    c->stats.kernel_ms += sums.hash;
+    c->stats.h2d_ms += sums.h2d;
+    if (trace && hash_pass && c->ledger.used() > 1) {
+        hipEvent_t first = nullptr;
+        c->ledger.each([&](Ev kind, const Span& sp) {
+            if (!first) first = sp.a;
             float t0 = 0, t1 = 0;
-            (void)hipEventElapsedTime(&t0, c->ev_pool[0].a, c->ev_pool[i].a);
-            (void)hipEventElapsedTime(&t1, c->ev_pool[0].a, c->ev_pool[i].b);
-            fprintf(stderr, "snaphash engine %d: %s %7.2f .. %7.2f ms\n", c->index, c->ev_pool[i].kind == 0 ? "kernel" : c->ev_pool[i].kind == 1 ? "h2d   " : "other ", t0, t1);
-        }
+            (void)hipEventElapsedTime(&t0, first, sp.a);
+            (void)hipEventElapsedTime(&t1, first, sp.b);
+            fprintf(stderr, "snaphash engine %d: %s %7.2f .. %7.2f ms\n", c->index, kind == Ev::Hash ? "kernel" : kind == Ev::H2d ? "h2d   " : "other ", t0, t1);
+        });
     }
-    c->ev_used = 0;
+    c->ledger.clear();
+    return sums;
 }
 
 } // namespace
+
+hipError_t snaphash::gpu_event_create(hipEvent_t* e, unsigned flags) { return flags == hipEventDefault ? hipEventCreate(e) : hipEventCreateWithFlags(e, flags); }
+void snaphash::gpu_event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+hipError_t snaphash::gpu_stream_create(hipStream_t* s, unsigned flags, int priority)
+{
+    return priority == kStreamDefaultPriority ? hipStreamCreateWithFlags(s, flags) : hipStreamCreateWithPriority(s, flags, priority);
+}
+void snaphash::gpu_stream_destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
 
 // The library's allocator for devbuf.h.  Pinned host memory for an engine goes on the GPU's NUMA node when it is known
 // (the calling thread's memory policy prefers that node for the duration of the allocation and hipHostMallocNumaUser
@@ -288,10 +306,10 @@ int ensure_slots(DevCtx* c, int nslots = 2, uint64_t want = 0)
         Slot& s = c->slot[k];
         HIP_TRY(c, s.ensure(want, c->numa_node));
         if (c->staging_node < 0) { s.h_buf[0] = 0; c->staging_node = numa_node_of_address(s.h_buf.data()); }
-        if (!s.done) HIP_TRY(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        if (!s.copied) HIP_TRY(c, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+        HIP_TRY(c, s.done.ensure(hipEventDisableTiming));
+        HIP_TRY(c, s.copied.ensure(hipEventDisableTiming));
     }
-    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    HIP_TRY(c, c->copy_stream.ensure(hipStreamNonBlocking));
     return SNAPHASH_OK;
 }
 
@@ -362,14 +380,13 @@ int launch_jobs(DevCtx* c, Job* h_jobs, Job* d_jobs, size_t n, uint8_t* d_digest
     }
     uint32_t k_head, k_tail;
     const size_t head = plan_kernels(c, h_jobs, n, &k_head, &k_tail);
-    EventPair* ev = next_events(c, 0);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, c->stream));
+    Span ev;
+    if (int rc = span_begin(c, Ev::Hash, c->stream, &ev)) return rc;
     const bool staged = copied != nullptr; // the job table came through a staging slot
     hipError_t e = launch_kernel(k_head, d_jobs, head, c, d_digests, staged);
     if (e == hipSuccess && head < n) e = launch_kernel(k_tail, d_jobs + head, n - head, c, d_digests, staged);
     if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(c, hipEventRecord(ev->b, c->stream));
+    if (int rc = span_end(c, ev, c->stream)) return rc;
     c->stats.launches += (head < n) ? 2 : 1;
     c->stats.kernel_used = k_head;
     c->pending = true;
@@ -378,7 +395,7 @@ int launch_jobs(DevCtx* c, Job* h_jobs, Job* d_jobs, size_t n, uint8_t* d_digest
 
 int sync_ctx(DevCtx* c)
 {
-    if (!c->pending && c->ev_used == 0) return SNAPHASH_OK;
+    if (!c->pending && c->ledger.used() == 0) return SNAPHASH_OK;
     if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     collect_events(c);
@@ -504,18 +521,18 @@ EngineSpans engine_spans(DevCtx* c)
     EngineSpans sp;
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamSynchronize(c->stream);
-    size_t first_copy = c->ev_used, last_copy = 0, last_kernel = 0;
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        float ms = 0;
-        if (c->ev_pool[i].kind == 1) {
-            if (first_copy == c->ev_used) first_copy = i;
-            last_copy = i;
-            if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) == hipSuccess) sp.copy_busy += ms;
-        } else if (c->ev_pool[i].kind == 0) last_kernel = i;
-    }
-    if (first_copy < c->ev_used) {
-        (void)hipEventElapsedTime(&sp.gpu, c->ev_pool[first_copy].a, c->ev_pool[last_kernel].b);
-        (void)hipEventElapsedTime(&sp.copy, c->ev_pool[first_copy].a, c->ev_pool[last_copy].b);
+    Span first_copy, last_copy, last_kernel, first; // (no kernel: the call's first span stands in, as it always did)
+    c->ledger.each([&](Ev kind, const Span& s) {
+        if (!first.a) first = s;
+        if (kind == Ev::H2d) {
+            if (!first_copy.a) first_copy = s;
+            last_copy = s;
+            sp.copy_busy += span_ms(s);
+        } else if (kind == Ev::Hash) last_kernel = s;
+    });
+    if (first_copy.a) {
+        (void)hipEventElapsedTime(&sp.gpu, first_copy.a, (last_kernel.b ? last_kernel : first).b);
+        (void)hipEventElapsedTime(&sp.copy, first_copy.a, last_copy.b);
     }
     return sp;
 }
@@ -546,8 +563,8 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
     if (c->sub.size() < g.nsub) c->sub.resize(g.nsub);
     for (unsigned q = 0; q < g.nsub; ++q) {
         SubSlot& ss = c->sub[q];
-        if (!ss.done) HIP_TRY(c, hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
-        if (!ss.copied) HIP_TRY(c, hipEventCreateWithFlags(&ss.copied, hipEventDisableTiming));
+        HIP_TRY(c, ss.done.ensure(hipEventDisableTiming));
+        HIP_TRY(c, ss.copied.ensure(hipEventDisableTiming));
         ss.busy = false;
     }
 
@@ -599,11 +616,10 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
         if (b.used) { // copy stream: the slot's previous kernel was already waited for above
             if (batch == 0) t_first_copy = now_ms() - t_engine0;
             ++n_copies;
-            EventPair* ev = next_events(c, 1);
-            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(ev->a, c->copy_stream));
+            Span ev;
+            if ((rc = span_begin(c, Ev::H2d, c->copy_stream, &ev))) return rc;
             HIP_TRY(c, hipMemcpyAsync(sl_d, sl_h, b.used, hipMemcpyHostToDevice, c->copy_stream));
-            HIP_TRY(c, hipEventRecord(ev->b, c->copy_stream));
+            if ((rc = span_end(c, ev, c->copy_stream))) return rc;
         }
         rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), b.nj, c->hash.d_digests.data(), sl.copied);
         if (rc) return rc;
@@ -614,7 +630,7 @@ int hash_sources(DevCtx* c, const std::vector<Source>& src, uint8_t* digests, ui
 
     const double ts0 = now_ms();
     static const bool trace_tree = getenv("SNAPHASH_TRACE_TREE") != nullptr;
-    const EngineSpans sp = trace_tree && c->ev_used > 1 ? engine_spans(c) : EngineSpans{};
+    const EngineSpans sp = trace_tree && c->ledger.used() > 1 ? engine_spans(c) : EngineSpans{};
     rc = sync_ctx(c);
     if (trace_tree)
         fprintf(stderr, "snaphash engine %d: %u batches; waiting for a slot %.1f ms, planning %.1f ms, reads %.1f ms, enqueue %.1f ms, drain %.1f ms; "
@@ -1172,25 +1188,7 @@ static void destroy_dev(DevCtx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    c->each_buf(Release());
-    for (Slot& s : c->slot) {
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-    }
-    for (SubSlot& q : c->sub) {
-        if (q.done) (void)hipEventDestroy(q.done);
-        if (q.copied) (void)hipEventDestroy(q.copied);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->z_stream) (void)hipStreamDestroy(c->z_stream);
-    if (c->z2_stream) (void)hipStreamDestroy(c->z2_stream);
-    if (c->f_stream) (void)hipStreamDestroy(c->f_stream);
-    for (hipEvent_t e : c->z_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->z_part_ev) (void)hipEventDestroy(e);
-    for (EventPair& p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    if (c->bcj_ev.a) (void)hipEventDestroy(c->bcj_ev.a);
-    if (c->bcj_ev.b) (void)hipEventDestroy(c->bcj_ev.b);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    c->each_buf(Release()); // (the engine's events and streams go after the buffers, with the DevCtx that owns them)
 }
 
 // The constant of the planner's model that differs most from box to box, measured where the ctx is made (~1 ms): what the
@@ -1209,22 +1207,20 @@ static void calibrate_at_init(snaphash_ctx* x)
     if (ensure_slots(c, 1, kProbe) != SNAPHASH_OK) { c->last_error.clear(); (void)hipGetLastError(); return; }
     Slot& s = c->slot[0];
     const size_t big = (size_t)kProbe, small = big / 4;
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    bool ok = true;
-    for (hipEvent_t& ev : e) ok = ok && hipEventCreate(&ev) == hipSuccess;
+    StageClock<2> clk;
+    bool ok = clk.enable() == hipSuccess;
     if (ok) {
         ok = hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess; // warm: the first copy of a stream pays for its set-up
-        ok = ok && hipEventRecord(e[0], c->copy_stream) == hipSuccess;
+        ok = ok && clk.mark(0, c->copy_stream) == hipSuccess;
         ok = ok && hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), small, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
-        ok = ok && hipEventRecord(e[1], c->copy_stream) == hipSuccess;
+        ok = ok && clk.mark(1, c->copy_stream) == hipSuccess;
         ok = ok && hipMemcpyAsync(s.d_buf.data(), s.h_buf.data(), big, hipMemcpyHostToDevice, c->copy_stream) == hipSuccess;
-        ok = ok && hipEventRecord(e[2], c->copy_stream) == hipSuccess;
+        ok = ok && clk.mark(2, c->copy_stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(c->copy_stream) == hipSuccess;
-        float t_small = 0, t_big = 0;
-        ok = ok && hipEventElapsedTime(&t_small, e[0], e[1]) == hipSuccess && hipEventElapsedTime(&t_big, e[1], e[2]) == hipSuccess;
+        const float t_small = ok ? clk.ms(0) : 0, t_big = ok ? clk.ms(1) : 0;
+        ok = ok && t_small > 0 && t_big > 0; // (0: the runtime does not know an event's time)
         if (ok && t_big > t_small) x->calib.observe_dma((double)(big - small), (double)(t_big - t_small) * 1e-3);
     }
-    for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev);
     if (!ok) (void)hipGetLastError();
 }
 
@@ -1338,7 +1334,7 @@ try {
                     e = hipSuccess;
                     why = "SNAPHASH_KERNEL_QUAD is not in this build (make QUAD=1)";
                 }
-                if (cfg->stream) c->stream = (hipStream_t)cfg->stream;
+                if (cfg->stream) c->stream.adopt((hipStream_t)cfg->stream);
             }
         }
         if (!rc) {
@@ -1361,10 +1357,7 @@ try {
                 cpus = numa_cpus_of_node(sysfs, c->numa_node);
             }
             c->pool.configure(256, cpus); // threads are created as batches ask for them (run_reads caps the count)
-            if (!c->stream) {
-                if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { rc = SNAPHASH_EDEVICE; why = "hipStreamCreateWithFlags"; }
-                else c->own_stream = true;
-            }
+            if ((e = c->stream.ensure(hipStreamNonBlocking)) != hipSuccess) { rc = SNAPHASH_EDEVICE; why = "hipStreamCreateWithFlags"; }
         }
         if (rc) {
             for (auto& d : x->dev) destroy_dev(d.get());
@@ -2202,11 +2195,10 @@ int batch_flush(snaphash_batch* b)
     Slot& sl = cur_slot(b);
     if (b->nj == 0) return SNAPHASH_OK;
     if (b->used) {
-        EventPair* ev = next_events(c, 1);
-        if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(ev->a, c->copy_stream));
+        Span ev;
+        if (int rc = span_begin(c, Ev::H2d, c->copy_stream, &ev)) return rc;
         HIP_TRY(c, hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), b->used, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipEventRecord(ev->b, c->copy_stream));
+        if (int rc = span_end(c, ev, c->copy_stream)) return rc;
     }
     int rc = launch_jobs(c, sl.jobs.h.data(), sl.jobs.d.data(), b->nj, c->hash.d_digests.data(), sl.copied);
     if (rc) return rc;
@@ -2423,14 +2415,13 @@ int crc_ranges_dev(DevCtx* c, int kind, const uint8_t* d_base, const uint64_t* o
     HIP_TRY(c, hipMemcpyAsync(c->crc.offs.d.data(), c->crc.offs.h.data(), n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(c->crc.lens.d.data(), c->crc.lens.h.data(), n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(c->crc.tile0.d.data(), c->crc.tile0.h.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
     const uint64_t* d_offs = c->crc.offs.d.data();
     const uint64_t* d_lens = c->crc.lens.d.data();
     const uint32_t* d_tile0 = c->crc.tile0.d.data();
     Twin<Crc>& res = c->crc.template result<Crc>();
     Crc* d_partial = c->crc.template partial<Crc>().data();
-    HIP_TRY(c, hipEventRecord(ev->a, s));
+    Span ev;
+    if (int rc = span_begin(c, Ev::Codec, s, &ev)) return rc;
     if constexpr (sizeof(Crc) == 8) {
         HIP_TRY(c, launch_crc64_ranges(d_base, d_offs, d_lens, d_tile0, (uint32_t)n, t, d_partial, s));
         HIP_TRY(c, launch_crc64_fold(d_lens, d_tile0, (uint32_t)n, d_partial, res.d.data(), s));
@@ -2438,11 +2429,10 @@ int crc_ranges_dev(DevCtx* c, int kind, const uint8_t* d_base, const uint64_t* o
         HIP_TRY(c, launch_crc_ranges(kind, d_base, d_offs, d_lens, d_tile0, (uint32_t)n, t, d_partial, s));
         HIP_TRY(c, launch_crc_fold(kind, d_lens, d_tile0, (uint32_t)n, d_partial, res.d.data(), s));
     }
-    HIP_TRY(c, hipEventRecord(ev->b, s));
+    if (int rc = span_end(c, ev, s)) return rc;
     HIP_TRY(c, hipMemcpyAsync(res.h.data(), res.d.data(), n * sizeof(Crc), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    float f = 0;
-    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
+    if (ms) *ms += span_ms(ev);
     memcpy(crcs, res.h.data(), n * sizeof(Crc));
     return SNAPHASH_OK;
 }
@@ -2458,7 +2448,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     double ms = 0;
     const int rc = crc_ranges_dev(c, kind, (const uint8_t*)d_base, offsets, lens, n, crcs, c->stream, &ms);
-    c->ev_used = 0;
+    scratch_spans_done(c);
     x->stats.kernel_ms = ms;
     x->stats.launches = n ? 2 : 0;
     end_top(x, t_top0_);
@@ -2485,15 +2475,13 @@ int sha256_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, co
     for (size_t i = 0; i < n; ++i) r[i] = Sha256Range{offs[i], lens[i], (uint32_t)i, 0};
     std::stable_sort(r, r + n, [](const Sha256Range& a, const Sha256Range& b) { return sha256_blocks(a.len) > sha256_blocks(b.len); });
     HIP_TRY(c, hipMemcpyAsync(c->sha256.ranges.d.data(), r, n * sizeof(Sha256Range), hipMemcpyHostToDevice, s));
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, s));
+    Span ev;
+    if (int rc = span_begin(c, Ev::Codec, s, &ev)) return rc;
     HIP_TRY(c, launch_sha256_ranges(d_base, c->sha256.ranges.d.data(), (uint32_t)n, c->sha256.digests.d.data(), s));
-    HIP_TRY(c, hipEventRecord(ev->b, s));
+    if (int rc = span_end(c, ev, s)) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->sha256.digests.h.data(), c->sha256.digests.d.data(), n * kSha256Digest, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    float f = 0;
-    if (ms && hipEventElapsedTime(&f, ev->a, ev->b) == hipSuccess) *ms += f;
+    if (ms) *ms += span_ms(ev);
     memcpy(digests, c->sha256.digests.h.data(), n * kSha256Digest);
     return SNAPHASH_OK;
 }
@@ -2502,7 +2490,7 @@ int sha256_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, co
 // len, filter, start and encode as the caller set them (unit0 is filled in here).  *ev: the pair of events around the
 // kernels, for the caller to read once it has waited for s.  The table lies in c->bcj until the stream has passed it: a
 // second call before that waits for s first.
-int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStream_t s, EventPair* ev)
+int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStream_t s, const Span* ev)
 {
     const size_t n = r.size();
     if (n == 0) return SNAPHASH_OK;
@@ -2549,17 +2537,18 @@ try {
         r[i] = BcjRange{offsets[i], lens[i], 0, filter, start_offset, encode ? 1u : 0u};
         any_x86 |= lens[i] != 0 && filter == kBcjX86;
     }
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(x, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    int rc = bcj_ranges_dev(c, (uint8_t*)d_base, r, c->stream, ev);
+    Span ev;
+    int rc = span_take(c, Ev::Codec, &ev);
+    if (rc) return lift(x, c, rc);
+    rc = bcj_ranges_dev(c, (uint8_t*)d_base, r, c->stream, &ev);
     const hipError_t e = hipStreamSynchronize(c->stream);
-    c->ev_used = 0;
+    scratch_spans_done(c);
     if (rc) return lift(x, c, rc);
     HIP_TRY(c, e);
     float ms = 0;
     bool ran = false;
     for (size_t i = 0; i < n; ++i) ran |= lens[i] != 0;
-    if (ran) (void)hipEventElapsedTime(&ms, ev->a, ev->b);
+    if (ran) (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     x->stats.kernel_ms = ms;
     x->stats.launches = ran ? (any_x86 ? 2 : 1) : 0;
     end_top(x, t_top0_);
@@ -2576,7 +2565,7 @@ try {
     HIP_TRY(c, hipSetDevice(c->device));
     double ms = 0;
     const int rc = sha256_ranges_dev(c, (const uint8_t*)d_base, offsets, lens, n, digests, c->stream, &ms);
-    c->ev_used = 0;
+    scratch_spans_done(c);
     x->stats.kernel_ms = ms;
     x->stats.launches = n ? 1 : 0;
     end_top(x, t_top0_);
@@ -2644,12 +2633,11 @@ int launch_compare_ranges(DevCtx* c, const std::vector<uint64_t>& a, const std::
         }
     HIP_TRY(c, hipMemsetAsync(d_equal, 1, n, c->stream)); // equal until a chunk says otherwise
     HIP_TRY(c, hipMemcpyAsync(d_tab, h_tab, nchunks * sizeof(CmpChunk), hipMemcpyHostToDevice, c->stream));
-    EventPair* ev = next_events(c, 0);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, c->stream));
+    Span ev;
+    if ((rc = span_begin(c, Ev::Hash, c->stream, &ev))) return rc;
     hipError_t e = launch_compare(d_tab, (uint32_t)nchunks, d_equal, c->stream);
     if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("compare launch: ") + hipGetErrorString(e));
-    HIP_TRY(c, hipEventRecord(ev->b, c->stream));
+    if ((rc = span_end(c, ev, c->stream))) return rc;
     c->stats.launches++;
     c->pending = true;
     return SNAPHASH_OK;
@@ -2745,7 +2733,7 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
         std::vector<uint8_t> ok;
         HostBuf<uint8_t> h_res;
         DevBuf<uint8_t> d_eq;
-        hipEvent_t done = nullptr, copied = nullptr;
+        Event done, copied;
         bool busy = false;
     } hf[2];
     auto retire = [&](Half& h) -> int {
@@ -2755,12 +2743,6 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
             if (!h.ok[i] || !h.h_res[i]) equal[todo[h.segs[i].t].idx] = 0;
         h.busy = false;
         return SNAPHASH_OK;
-    };
-    auto cleanup = [&]() {
-        for (Half& h : hf) {
-            if (h.done) (void)hipEventDestroy(h.done);
-            if (h.copied) (void)hipEventDestroy(h.copied);
-        }
     };
     size_t first = 0;
     unsigned batch = 0;
@@ -2797,17 +2779,16 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
             rc = fail(c, SNAPHASH_ENOMEM, "allocation of the verdict buffers failed");
             break;
         }
-        if (!h.done && (hipEventCreateWithFlags(&h.done, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&h.copied, hipEventDisableTiming) != hipSuccess)) {
+        if (h.done.ensure(hipEventDisableTiming) != hipSuccess || h.copied.ensure(hipEventDisableTiming) != hipSuccess) {
             rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
             break;
         }
-        EventPair* ev = next_events(c, 1);
-        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-        if (hipEventRecord(ev->a, c->copy_stream) != hipSuccess ||
+        Span ev; // (recorded in the chain below: its failures keep this call's own text)
+        if ((rc = span_take(c, Ev::H2d, &ev))) break;
+        if (hipEventRecord(ev.a, c->copy_stream) != hipSuccess ||
             hipMemcpyAsync(c->slot[0].d_buf.data() + base, c->slot[0].h_buf.data() + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
             hipMemcpyAsync(c->slot[1].d_buf.data() + base, c->slot[1].h_buf.data() + base, used, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
-            hipEventRecord(ev->b, c->copy_stream) != hipSuccess || hipEventRecord(h.copied, c->copy_stream) != hipSuccess ||
+            hipEventRecord(ev.b, c->copy_stream) != hipSuccess || hipEventRecord(h.copied, c->copy_stream) != hipSuccess ||
             hipStreamWaitEvent(c->stream, h.copied, 0) != hipSuccess) {
             rc = fail(c, SNAPHASH_EDEVICE, "H2D of a comparison batch failed");
             break;
@@ -2835,9 +2816,7 @@ int files_equal_impl(DevCtx* c, const char* const* a, const char* const* b, size
         if (!rc) rc = r2;
     }
     const int r3 = sync_ctx(c);
-    if (!rc) rc = r3;
-    cleanup();
-    return rc;
+    return rc ? rc : r3;
 }
 
 } // namespace

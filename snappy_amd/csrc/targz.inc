@@ -99,7 +99,7 @@ struct GzipEncoder final : Encoder {
     // the slot in the compressor (gz_slot_begin / _launch / _consume)
     std::vector<std::pair<uint32_t, uint32_t>> z_pieces; // (first chunk, count)
     uint32_t z_nch = 0, z_launched = 0;
-    EventPair z_evpair{};
+    Span z_evpair{};
     // the self-check (snapbuild.inc, SNAPHASH_BUILD_CHECK): null = off, the compressor's path without it
     GzCheck* const check;
     explicit GzipEncoder(GzCheck* chk = nullptr) : Encoder(".gz", nullptr), check(chk)
@@ -135,9 +135,9 @@ int ensure_producer_streams(DevCtx* c)
     if (!c->z_stream) { // the compressor's own stream, below the hashing kernels in priority: they are the longer chain
         int least = 0, greatest = 0;
         HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(c, hipStreamCreateWithPriority(&c->z_stream, hipStreamNonBlocking, least));
+        HIP_TRY(c, c->z_stream.ensure(hipStreamNonBlocking, least));
     }
-    if (!c->z2_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->z2_stream, hipStreamNonBlocking)); // concatenation + the way back
+    HIP_TRY(c, c->z2_stream.ensure(hipStreamNonBlocking)); // concatenation + the way back
     return SNAPHASH_OK;
 }
 
@@ -297,16 +297,9 @@ int gz_slot_begin(OutPipe& g, GzipEncoder& z, uint64_t n, bool is_first, bool is
     z.z_nch = (uint32_t)((n + kDeflateChunk - 1) / kDeflateChunk);
     zp.cut(z.z_nch, is_first, is_last, z.z_pieces);
     z.z_launched = 0;
-    while (c->z_ev.size() < z.z_pieces.size()) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->z_ev.push_back(e);
-    }
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    z.z_evpair = *ev;
-    HIP_TRY(c, hipEventRecord(z.z_evpair.a, c->z_stream));
-    return SNAPHASH_OK;
+    if (c->z_ev.size() < z.z_pieces.size()) c->z_ev.resize(z.z_pieces.size());
+    for (size_t k = 0; k < z.z_pieces.size(); ++k) HIP_TRY(c, c->z_ev[k].ensure(hipEventDisableTiming));
+    return span_begin(c, Ev::Codec, c->z_stream, &z.z_evpair); // (ends behind the slot's last piece: gz_slot_launch)
 }
 
 // launches, in order, every piece that ends at or before bytes_ready (bytes_ready >= n: all that are left); `ready`
@@ -324,7 +317,7 @@ int gz_slot_launch(OutPipe& g, GzipEncoder& z, Slot& sl, uint64_t n, uint64_t by
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("deflate launch: ") + hipGetErrorString(e));
         HIP_TRY(c, hipMemcpyAsync(c->z.h_sizes.data() + c0, c->z.d_sizes.data() + c0, (size_t)cnt * 4, hipMemcpyDeviceToHost, zs));
         HIP_TRY(c, hipEventRecord(c->z_ev[z.z_launched], zs));
-        if (++z.z_launched == z.z_pieces.size()) HIP_TRY(c, hipEventRecord(z.z_evpair.b, zs));
+        if (++z.z_launched == z.z_pieces.size()) return span_end(c, z.z_evpair, zs);
     }
     return SNAPHASH_OK;
 }
@@ -353,20 +346,17 @@ int gz_slot_consume(OutPipe& g, GzipEncoder& z, Slot& sl, uint64_t n, int zbuf)
             total += c->z.h_sizes[i];
         }
         HIP_TRY(c, hipMemcpyAsync(c->z.d_prefix.data() + c0, c->z.h_prefix.data() + c0, (size_t)cnt * 8, hipMemcpyHostToDevice, z2));
-        EventPair* ev2 = next_events(c, 2);
-        if (!ev2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(ev2->a, z2));
+        Span ev2, ev3;
+        if (int rc = span_begin(c, Ev::Codec, z2, &ev2)) return rc;
         const hipError_t e = launch_deflate_compact(c->z.d_slots.data(), c->z.d_sizes.data(), c->z.d_prefix.data(), c->z.d_out.data(), c0, cnt, z2);
         if (e != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("compact launch: ") + hipGetErrorString(e));
-        HIP_TRY(c, hipEventRecord(ev2->b, z2));
+        if (int rc = span_end(c, ev2, z2)) return rc;
         if (z.check) { // behind the compaction: the piece's stretches of d_out against the slot's staged bytes
-            EventPair* ev3 = next_events(c, 3);
-            if (!ev3) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(ev3->a, z2));
+            if (int rc = span_begin(c, Ev::Check, z2, &ev3)) return rc;
             const hipError_t ec = launch_deflate_check(sl.d_buf.data(), n, c->z.d_out.data(), total, c->z.d_prefix.data(), c->z.d_sizes.data(), c0, cnt,
                                                        z.z_nch, false, c->z.chk.d.data(), z2);
             if (ec != hipSuccess) return fail(c, SNAPHASH_EDEVICE, std::string("check launch: ") + hipGetErrorString(ec));
-            HIP_TRY(c, hipEventRecord(ev3->b, z2));
+            if (int rc = span_end(c, ev3, z2)) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->z.chk.h.data() + c0, c->z.chk.d.data() + c0, (size_t)cnt * sizeof(DfCheckVerdict), hipMemcpyDeviceToHost, z2));
         }
         HIP_TRY(c, hipMemcpyAsync(c->z.h_out[zbuf].data() + base, c->z.d_out.data() + base, total - base, hipMemcpyDeviceToHost, z2));
@@ -441,17 +431,12 @@ int GzipEncoder::finish(OutPipe& g, uint8_t archive_digest[64])
 
 void gz_abort(OutPipe& g) { gz_join(g); }
 
-void collect_targz_events(DevCtx* c, snaphash_targz_stats& st, double* check_ms)
+// a producer's ledger at the end of its call: every codec's, CRC's and SHA-256's launch is its deflate_ms, the self-check's its own
+void collect_producer_events(DevCtx* c, OutPipe& g, const Encoder& enc)
 {
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) != hipSuccess) continue;
-        if (c->ev_pool[i].kind == 0) c->stats.kernel_ms += ms;
-        else if (c->ev_pool[i].kind == 1) c->stats.h2d_ms += ms;
-        else if (c->ev_pool[i].kind == 3) { if (check_ms) *check_ms += ms; }
-        else st.deflate_ms += ms;
-    }
-    c->ev_used = 0;
+    const SpanSums ev = collect_events(c, false);
+    g.st.deflate_ms += ev.codec;
+    if (enc.check_ms) *enc.check_ms += ev.check;
 }
 
 // A whole buffer through an encoder into memory the caller frees: the body of the snaphash_*_buffer entry points of the
@@ -477,18 +462,18 @@ int encode_to_malloc(snaphash_ctx* x, Encoder& enc, const void* data, size_t n, 
     for (uint64_t off = 0; off < n && !rc; off += S) {
         const uint64_t take = std::min<uint64_t>(S, n - off);
         memcpy(sl.h_buf.data(), (const uint8_t*)data + off, take);
-        EventPair* ev = next_events(c, 1);
-        if (!ev) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-        if (hipEventRecord(ev->a, c->z_stream) != hipSuccess ||
+        Span ev; // (recorded in the chain below: its failures keep this call's own text)
+        if ((rc = span_take(c, Ev::H2d, &ev))) break;
+        if (hipEventRecord(ev.a, c->z_stream) != hipSuccess ||
             hipMemcpyAsync(sl.d_buf.data(), sl.h_buf.data(), take, hipMemcpyHostToDevice, c->z_stream) != hipSuccess ||
-            hipEventRecord(ev->b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
+            hipEventRecord(ev.b, c->z_stream) != hipSuccess) { rc = fail(c, SNAPHASH_EDEVICE, "H2D failed"); break; }
         rc = enc.slot(g, sl, take, nullptr, 0, off == 0, off + take >= n);
     }
     if (!rc && enc.finish(g, nullptr)) rc = fail(c, SNAPHASH_EIO, "write failed");
     if (rc) gz_abort(g);
     (void)hipStreamSynchronize(c->z_stream);
     (void)hipStreamSynchronize(c->z2_stream);
-    collect_targz_events(c, g.st, enc.check_ms);
+    collect_producer_events(c, g, enc);
     g.st.tar_bytes = n;
     g.st.gz_bytes = out.size();
     g.st.wall_ms = now_ms() - t0;
@@ -652,7 +637,7 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
     // fill and copy (~11 ms); a chunk's output depends on no byte behind its own end (deflate_kernels.hip: matches are
     // cut at the chunk's end, the hash takes three bytes), so what lies beyond a part that has arrived may be anything.
     const uint64_t kPart = (uint64_t)kZPiece * kDeflateChunk;
-    auto fill = [&](Slot& sl, uint64_t s0, uint64_t n, EventPair ev, bool in_parts) { // (the pair by value: the pool it comes from may grow meanwhile)
+    auto fill = [&](Slot& sl, uint64_t s0, uint64_t n, Span ev, bool in_parts) { // (its span by value, taken by the calling thread: a fill on a thread of its own never touches the ledger)
         Filled f;
         const double tf0 = now_ms();
         std::vector<ReadOp> ops;
@@ -697,11 +682,8 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
                 while (o < ops.size() && (uint64_t)(ops[o].dst - sl.h_buf.data()) < e) part.push_back(ops[o++]); // (a member that straddles e is read whole: its rest travels with the next part)
                 run_reads(c, srcs, part, first_err, first_err_src);
                 if (first_err.load()) break;
-                while (c->z_part_ev.size() <= k) {
-                    hipEvent_t pe = nullptr;
-                    if (hipEventCreateWithFlags(&pe, hipEventDisableTiming) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "hipEventCreate failed"; return f; }
-                    c->z_part_ev.push_back(pe);
-                }
+                if (c->z_part_ev.size() <= k) c->z_part_ev.resize(k + 1);
+                if (c->z_part_ev[k].ensure(hipEventDisableTiming) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "hipEventCreate failed"; return f; }
                 if (hipMemcpyAsync(sl.d_buf.data() + b, sl.h_buf.data() + b, e - b, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
                     hipEventRecord(c->z_part_ev[k], c->copy_stream) != hipSuccess) { f.rc = SNAPHASH_EDEVICE; f.err = "H2D failed"; return f; }
                 f.rc = gz_slot_launch(g, *enc.parts, sl, n, e, c->z_part_ev[k]);
@@ -729,17 +711,17 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
     try { // no C++ exception (thread creation, allocation) may cross the C boundary
     // (Short first slots -- an eighth, a quarter, half a buffer -- were tried and dropped: what they save at the start
     // they cost in hashing launches, each as long as its longest file whatever the slot holds.)
-    EventPair* ev_next = (!rc && plan.total) ? next_events(c, 1) : nullptr;
-    if (!rc && plan.total && !ev_next) rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+    Span ev_next;
+    if (!rc && plan.total) rc = span_take(c, Ev::H2d, &ev_next);
     const bool first_in_parts = enc.parts && std::min<uint64_t>(S, plan.total) > kPart;
     if (!rc && plan.total && !first_in_parts)
-        next = std::async(std::launch::async, fill, std::ref(c->slot[0]), (uint64_t)0, std::min<uint64_t>(S, plan.total), *ev_next, false);
+        next = std::async(std::launch::async, fill, std::ref(c->slot[0]), (uint64_t)0, std::min<uint64_t>(S, plan.total), ev_next, false);
     unsigned k = 0;
     for (uint64_t s0 = 0, n = 0; s0 < plan.total && !rc; s0 += n, ++k) {
         n = std::min<uint64_t>(S, plan.total - s0);
         Slot& sl = c->slot[k & 1u];
         const bool parts = k == 0 && first_in_parts;
-        const Filled f = parts ? fill(sl, s0, n, *ev_next, true) : next.get();
+        const Filled f = parts ? fill(sl, s0, n, ev_next, true) : next.get();
         if (s0 == 0) t_first_fill = now_ms();
         if (f.rc) { rc = fail(c, f.rc, f.err); break; }
         if (first_err.load()) break;
@@ -757,9 +739,8 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
         // The other slot's host buffer is free (its H2D completed before its slot's compression was waited for) and its
         // HBM is only touched again by that fill's own H2D, which waits for the slot's hashing kernels: fill it now.
         if (s0 + n < plan.total) {
-            ev_next = next_events(c, 1);
-            if (!ev_next) { rc = fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed"); break; }
-            next = std::async(std::launch::async, fill, std::ref(c->slot[(k + 1) & 1u]), s0 + n, std::min<uint64_t>(S, plan.total - s0 - n), *ev_next, false);
+            if ((rc = span_take(c, Ev::H2d, &ev_next))) break;
+            next = std::async(std::launch::async, fill, std::ref(c->slot[(k + 1) & 1u]), s0 + n, std::min<uint64_t>(S, plan.total - s0 - n), ev_next, false);
         }
         rc = parts ? gz_slot_consume(g, *enc.parts, sl, n, (int)(k & 1u)) : enc.slot(g, sl, n, sl.copied, (int)(k & 1u), s0 == 0, s0 + n >= plan.total);
     }
@@ -792,7 +773,7 @@ static int tar_create_impl(snaphash_ctx* x, Encoder& enc, const char* tarname, c
     (void)hipStreamSynchronize(c->z_stream);
     (void)hipStreamSynchronize(c->z2_stream);
     (void)hipStreamSynchronize(c->stream);
-    collect_targz_events(c, g.st, enc.check_ms);
+    collect_producer_events(c, g, enc);
     c->pending = false;
     std::vector<uint8_t> dig(nstreams * 64 + 64);
     if (!rc && nstreams && hipMemcpy(dig.data(), c->hash.d_digests.data(), nstreams * 64, hipMemcpyDeviceToHost) != hipSuccess)

@@ -33,20 +33,16 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
                   float& kms, CrcAt crc_at, CrcTally* tally)
 {
     std::vector<uint8_t>& out = ds.out;
-    auto timed = [&](EventPair* ev) {
-        float ms = 0;
-        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
-    };
     HIP_TRY(c, hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
-    EventPair* ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    Span ev;
+    int rc = span_begin(c, Ev::Codec, c->f_stream, &ev);
+    if (rc) return rc;
     HIP_TRY(c, launch_bz_ibwt(c->bz.d_slots.data(), c->bz.d_tt.data(), c->bz.d_blk.data(), nb, c->f_stream));
     HIP_TRY(c, launch_bz_rle1_count(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->f_stream));
-    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+    if ((rc = span_end(c, ev, c->f_stream))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->bz.h_blk.data(), c->bz.d_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
     HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-    timed(ev);
+    kms += span_ms(ev);
     const size_t o0 = out.size();
     const uint64_t base = ds.dev_base(o0);
     uint64_t total = 0;
@@ -56,19 +52,17 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         c->bz.h_blk[i].out_off = base + total;
         total += c->bz.h_blk[i].out_len;
     }
-    int rc = ds.reserve_dev(c, base + total, base);
+    rc = ds.reserve_dev(c, base + total, base);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->bz.d_blk.data(), c->bz.h_blk.data(), (size_t)nb * sizeof(BzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
-    ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
     HIP_TRY(c, launch_bz_rle1_write(c->bz.d_slots.data(), c->bz.d_blk.data(), c->bz.d_chunks.data(), nb, c->inf.d_out.data(), c->f_stream));
-    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+    if ((rc = span_end(c, ev, c->f_stream))) return rc;
     out.resize(o0 + total);
     rc = ds.fetch(o0, o0, o0 + total);
     if (!rc) rc = ds.sync();
     if (rc) return rc;
-    timed(ev);
+    kms += span_ms(ev);
     if (crc_at == CrcAt::Device) {
         std::vector<uint64_t> offs(nb), lens(nb);
         for (uint32_t i = 0; i < nb; ++i) { offs[i] = c->bz.h_blk[i].out_off; lens[i] = c->bz.h_blk[i].out_len; }
@@ -80,7 +74,7 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
         if (got != crcs) return fail(c, SNAPHASH_EFORMAT, "bzip2: block CRC mismatch");
         st.segments += nb;
         st.gpu_segments += nb;
-        c->ev_used = 0;
+        scratch_spans_done(c);
         return SNAPHASH_OK;
     }
     if (tally) tally->host_ranges += nb;
@@ -103,7 +97,7 @@ int bunzip2_batch(snaphash_ctx* x, DevCtx* c, uint32_t nb, const std::vector<uin
     if (bad.load()) return fail(c, SNAPHASH_EFORMAT, "bzip2: block CRC mismatch");
     st.segments += nb;
     st.gpu_segments += nb;
-    c->ev_used = 0;
+    scratch_spans_done(c);
     return SNAPHASH_OK;
 }
 
@@ -139,10 +133,6 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, Deco
     if (rc) return rc;
     std::unique_ptr<BzScratch> hs; // the host decoder's, for a block the kernels do not take
     float kms = 0;
-    auto timed = [&](EventPair* ev) {
-        float ms = 0;
-        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
-    };
     auto host_block = [&]() -> int { // the block at cur.bit by the host decoder
         if (!hs) hs.reset(new BzScratch);
         const size_t o0 = out.size();
@@ -166,14 +156,13 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, Deco
         std::vector<uint64_t> cand;
         if (!chain_order) {
             HIP_TRY(c, hipMemsetAsync(c->bz.d_count.data(), 0, 4, c->f_stream));
-            EventPair* ev = next_events(c, 2);
-            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            Span ev;
+            if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
             HIP_TRY(c, launch_bz_scan(c->bz.d_in.data(), pn, c->bz.d_cand.data(), c->bz.d_count.data(), (uint32_t)c->bz.cand_cap(), c->f_stream));
-            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            if ((rc = span_end(c, ev, c->f_stream))) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->bz.h_count.data(), c->bz.d_count.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
             HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-            timed(ev);
+            kms += span_ms(ev);
             if (c->bz.h_count[0] > c->bz.cand_cap()) {
                 chain_order = true;
             } else if (c->bz.h_count[0]) {
@@ -199,14 +188,13 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, Deco
             if (rc) return rc;
             memcpy(c->bz.h_cand.data(), cand.data() + idx, (size_t)K * 8);
             HIP_TRY(c, hipMemcpyAsync(c->bz.d_cand.data(), c->bz.h_cand.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->f_stream));
-            EventPair* ev = next_events(c, 2);
-            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            Span ev;
+            if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
             HIP_TRY(c, launch_bz_symbols(c->bz.d_in.data(), pn, c->bz.d_cand.data(), K, c->bz.d_slots.data(), c->bz.d_res.data(), c->f_stream));
-            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            if ((rc = span_end(c, ev, c->f_stream))) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->bz.h_res.data(), c->bz.d_res.data(), (size_t)K * sizeof(BzBlockRes), hipMemcpyDeviceToHost, c->f_stream));
             HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-            timed(ev);
+            kms += span_ms(ev);
             const uint64_t* lc = cand.data() + idx;
             for (;;) { // link what this launch decoded, then run the linked blocks through the later stages
                 uint32_t nb = 0;
@@ -249,7 +237,7 @@ int bunzip2_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* bz, size_t n, Deco
         }
         if (finished) break;
     }
-    c->ev_used = 0;
+    scratch_spans_done(c);
     st.inflate_ms += kms;
     return SNAPHASH_OK;
 }

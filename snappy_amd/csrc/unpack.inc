@@ -27,7 +27,7 @@ struct DecodedStream {
 
     static int stream(DevCtx* c)
     {
-        if (!c->f_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->f_stream, hipStreamNonBlocking));
+        HIP_TRY(c, c->f_stream.ensure(hipStreamNonBlocking));
         return SNAPHASH_OK;
     }
     // d_out of `end` bytes or more; `keep` bytes of what is there are kept when it grows
@@ -131,7 +131,7 @@ constexpr uint64_t kBlockPiecePerSlot = 16u << 10;    // compressed bytes a slot
 // in order) and their symbols laid end to end into the decoded bytes: appended to ds.out and, with keep_dev, left in HBM.
 // 1: holes are left (cannot happen after the ordered sweep: the caller falls back to the host decoder).
 int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, DecodedStream& ds, size_t m0, bool trace,
-                    const std::function<void(EventPair*)>& timed)
+                    float& kms)
 {
     std::vector<uint8_t>& out = ds.out;
     const size_t o0 = out.size();
@@ -139,21 +139,19 @@ int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, 
     if (wlen) HIP_TRY(c, hipMemcpyAsync(c->inf.d_win.data(), out.data() + o0 - wlen, wlen, hipMemcpyHostToDevice, c->f_stream));
     HIP_TRY(c, hipMemcpyAsync(c->inf.d_links.data(), c->inf.h_links.data(), (size_t)nl * sizeof(InflateLink), hipMemcpyHostToDevice, c->f_stream));
     bool filled = false;
-    EventPair* ev = nullptr;
+    Span ev;
     for (int pass = 0; pass < 2 && !filled; ++pass) {
         HIP_TRY(c, hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
-        ev = next_events(c, 2);
-        if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+        if (int rc = span_begin(c, Ev::Codec, c->f_stream, &ev)) return rc;
         if (pass == 1)
             for (uint32_t j = 0; j < nl; ++j)
                 if (c->inf.h_links[j].hole_end) HIP_TRY(c, launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), j, 1, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
         if (pass == 1) HIP_TRY(c, hipMemsetAsync(c->inf.d_flags.data(), 0, 8, c->f_stream));
         HIP_TRY(c, launch_inflate_fill(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), 0, nl, c->inf.d_win.data(), wlen, c->inf.d_flags.data(), c->f_stream));
-        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        if (int rc = span_end(c, ev, c->f_stream)) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->inf.h_flags.data(), c->inf.d_flags.data(), 8, hipMemcpyDeviceToHost, c->f_stream));
         HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-        timed(ev);
+        kms += span_ms(ev);
         if (c->inf.h_flags[1]) return fail(c, SNAPHASH_EFORMAT, "gzip: a back-reference before the start of the member");
         filled = c->inf.h_flags[0] == 0;
         if (trace) fprintf(stderr, "snaphash inflate: fill pass %d: %u holes left\n", pass, c->inf.h_flags[0]);
@@ -161,16 +159,14 @@ int gpu_fill_concat(DevCtx* c, uint32_t nl, uint64_t total, uint32_t slot_syms, 
     if (!filled) return 1;
     int rc = ds.reserve_dev(c, ds.dev_base(o0) + total, ds.dev_base(o0));
     if (rc) return rc;
-    ev = next_events(c, 2);
-    if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+    if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
     HIP_TRY(c, launch_inflate_concat(c->inf.d_slots.data(), slot_syms, c->inf.d_links.data(), nl, c->inf.d_out.data() + ds.dev_base(o0), c->f_stream));
-    HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+    if ((rc = span_end(c, ev, c->f_stream))) return rc;
     out.resize(o0 + total);
     rc = ds.fetch(o0, o0, o0 + total);
     if (!rc) rc = ds.sync();
     if (rc) return rc;
-    timed(ev);
+    kms += span_ms(ev);
     return 0;
 }
 
@@ -198,11 +194,6 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, Dec
                             host_mode ? kHostBlockSlots : 0);
     if (rc) return rc;
     const uint32_t slots = host_mode ? kHostBlockSlots : c->inf.nslots(kInflateBlockSlotSyms);
-    auto timed = [&](EventPair* ev) {
-        float ms = 0;
-        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
-    };
-    const std::function<void(EventPair*)> timed_f = timed;
     uint16_t* hsl = c->inf.h_bslots.data(); // host mode: the slots (symbols) and the bytes narrowed from them
     uint8_t* hby = c->inf.h_bbytes.data();
     std::vector<InflateSegRes> hres(host_mode ? kHostBlockSlots : 0);
@@ -215,22 +206,17 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, Dec
         HIP_TRY(c, hipMemcpyAsync(c->inf.d_in.data(), z + b0, pn, hipMemcpyHostToDevice, c->f_stream));
         HIP_TRY(c, hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
         HIP_TRY(c, hipMemsetAsync(c->inf.d_bcand.data(), 0, 4, c->f_stream));
-        // (both pairs taken before either is used: taking one may grow the pool and move the other)
-        if (!next_events(c, 2) || !next_events(c, 2)) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        EventPair* ev = &c->ev_pool[c->ev_used - 2];
-        EventPair* evb = &c->ev_pool[c->ev_used - 1];
-        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+        Span ev, evb; // the block scan's own time, within both scans'
+        if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
         HIP_TRY(c, launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
-        HIP_TRY(c, hipEventRecord(evb->a, c->f_stream));
+        if ((rc = span_begin(c, Ev::Codec, c->f_stream, &evb))) return rc;
         HIP_TRY(c, launch_inflate_block_scan(c->inf.d_in.data(), pn, c->inf.d_bcand.data() + 1, c->inf.d_bcand.data(), (uint32_t)c->inf.bcand_cap(), c->f_stream));
-        HIP_TRY(c, hipEventRecord(evb->b, c->f_stream));
-        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        if ((rc = span_end(c, evb, c->f_stream)) || (rc = span_end(c, ev, c->f_stream))) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
         HIP_TRY(c, hipMemcpyAsync(c->inf.h_bcand.data(), c->inf.d_bcand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
         HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-        timed(ev);
-        float sms = 0;
-        if (hipEventElapsedTime(&sms, evb->a, evb->b) == hipSuccess) bs.scan_ms += sms;
+        kms += span_ms(ev);
+        bs.scan_ms += span_ms(evb);
         const uint64_t ns = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
         const uint64_t nb = std::min<uint64_t>(c->inf.h_bcand[0], c->inf.bcand_cap());
         if (ns) HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ns * 4, hipMemcpyDeviceToHost, c->f_stream));
@@ -309,14 +295,12 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, Dec
         } else {
             memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
             HIP_TRY(c, hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
-            ev = next_events(c, 2);
-            if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+            if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
             HIP_TRY(c, launch_inflate_decode_blocks(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
-            HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+            if ((rc = span_end(c, ev, c->f_stream))) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
             HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-            timed(ev);
+            kms += span_ms(ev);
             uint64_t off = 0;
             for (;;) {
                 const auto it = std::lower_bound(cand.begin(), cand.end(), (uint32_t)pos);
@@ -337,7 +321,7 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, Dec
                 if (pos >= pn * 8) break;
             }
             if (nl) {
-                rc = gpu_fill_concat(c, nl, off, kInflateBlockSlotSyms, ds, m0, trace, timed_f);
+                rc = gpu_fill_concat(c, nl, off, kInflateBlockSlotSyms, ds, m0, trace, kms);
                 if (rc < 0) return rc;
                 if (rc) { nl = 0; fin = false; } // (holes left: the host decoder takes over from the piece's start)
                 else st.gpu_segments += nl;
@@ -350,7 +334,7 @@ int gunzip_blocks(snaphash_ctx* x, DevCtx* c, const uint8_t* z, uint64_t zn, Dec
         bs.linked += from_block;
         bs.unreached += c->inf.h_bcand[0] - from_block;
         st.segments += nl;
-        c->ev_used = 0;
+        scratch_spans_done(c);
         if (fin) return 0;
         if (nl) {
             cur = b0 * 8 + pos;
@@ -399,11 +383,6 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
     std::vector<uint16_t> hslots;
     std::vector<uint8_t> hbytes;
     float kms = 0;
-    auto timed = [&](EventPair* ev) {
-        float ms = 0;
-        if (ev && hipEventElapsedTime(&ms, ev->a, ev->b) == hipSuccess) kms += ms;
-    };
-    const std::function<void(EventPair*)> timed_f = timed;
     if (n >= 18) { // the output in one allocation: ISIZE of the last member (exact for a single member under 4 GiB)
         const uint64_t isize = gz[n - 4] | (uint64_t)gz[n - 3] << 8 | (uint64_t)gz[n - 2] << 16 | (uint64_t)gz[n - 1] << 24;
         if (isize <= (uint64_t)n * 1032) out.reserve(out.size() + (size_t)isize);
@@ -445,14 +424,13 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
             } else {
                 HIP_TRY(c, hipMemcpyAsync(c->inf.d_in.data(), z + cur, pn, hipMemcpyHostToDevice, c->f_stream));
                 HIP_TRY(c, hipMemsetAsync(c->inf.d_cand.data(), 0, 4, c->f_stream));
-                EventPair* ev = next_events(c, 2);
-                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-                HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+                Span ev;
+                if (int erc = span_begin(c, Ev::Codec, c->f_stream, &ev)) return erc;
                 HIP_TRY(c, launch_inflate_scan(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, c->inf.d_cand.data(), (uint32_t)c->inf.cand_cap(), c->f_stream));
-                HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+                if (int erc = span_end(c, ev, c->f_stream)) return erc;
                 HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data(), c->inf.d_cand.data(), 4, hipMemcpyDeviceToHost, c->f_stream));
                 HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-                timed(ev);
+                kms += span_ms(ev);
                 const uint64_t ncand = std::min<uint64_t>(c->inf.h_cand[0], c->inf.cand_cap());
                 if (ncand) {
                     HIP_TRY(c, hipMemcpyAsync(c->inf.h_cand.data() + 1, c->inf.d_cand.data() + 1, ncand * 4, hipMemcpyDeviceToHost, c->f_stream));
@@ -539,14 +517,13 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
             } else {
                 memcpy(c->inf.h_cand.data() + 1, cand.data(), (size_t)K * 4);
                 HIP_TRY(c, hipMemcpyAsync(c->inf.d_cand.data() + 1, c->inf.h_cand.data() + 1, (size_t)K * 4, hipMemcpyHostToDevice, c->f_stream));
-                EventPair* ev = next_events(c, 2);
-                if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-                HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+                Span ev;
+                if (int erc = span_begin(c, Ev::Codec, c->f_stream, &ev)) return erc;
                 HIP_TRY(c, launch_inflate_decode(c->inf.d_in.data(), pn, c->inf.d_cand.data() + 1, K, c->inf.d_slots.data(), c->inf.d_res.data(), c->f_stream));
-                HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+                if (int erc = span_end(c, ev, c->f_stream)) return erc;
                 HIP_TRY(c, hipMemcpyAsync(c->inf.h_res.data(), c->inf.d_res.data(), (size_t)K * sizeof(InflateSegRes), hipMemcpyDeviceToHost, c->f_stream));
                 HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-                timed(ev);
+                kms += span_ms(ev);
             }
             // link: from the piece's start, each segment where the one before ended
             uint32_t nl = 0;
@@ -580,7 +557,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
                 if (rc) return rc;
                 continue;
             }
-            rc = gpu_fill_concat(c, nl, off, kInflateSlotSyms, ds, m0, trace, timed_f);
+            rc = gpu_fill_concat(c, nl, off, kInflateSlotSyms, ds, m0, trace, kms);
             if (rc < 0) return rc;
             if (rc) { // (cannot happen after the ordered sweep; the host decodes the piece's first segment if it does)
                 rc = host_run();
@@ -591,9 +568,9 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
             st.gpu_segments += nl;
             if (fin) ended = true;
             else cur += pos;
-            c->ev_used = 0;
+            scratch_spans_done(c);
         }
-        c->ev_used = 0;
+        scratch_spans_done(c);
         uint32_t crc;
         const size_t tr = (size_t)((final_bit + 7) >> 3);
         if (dev_crc && tr + 8 <= zn) { // the stored value now (the trailer's place and ISIZE are still checked here), the bytes' own below
@@ -615,7 +592,7 @@ int gunzip_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* gz, size_t n, Decod
         std::vector<uint32_t> got(m_off.size());
         double ms = 0;
         rc = crc_ranges_dev(c, kCrcGzip, c->inf.d_out.data(), m_off.data(), m_len.data(), m_off.size(), got.data(), c->f_stream, &ms);
-        c->ev_used = 0;
+        scratch_spans_done(c);
         if (rc) return rc;
         if (tally) { tally->device_ranges += m_off.size(); tally->device_ms += ms; }
         if (got != m_crc) return fail(c, SNAPHASH_EFORMAT, "gzip: CRC-32 or ISIZE mismatch");
@@ -807,7 +784,7 @@ try {
     const bool want_verify = yaml != nullptr;
     DecodedStream ds(c, tar, want_verify);
     int rc = codec.decode(x, c, gz.data(), gz.size(), ds, st, CrcAt::Host, nullptr);
-    c->ev_used = 0;
+    scratch_spans_done(c);
     st.tar_bytes = tar.size();
     std::vector<TarEntry> ents;
     std::string why;
@@ -844,7 +821,7 @@ try {
     std::vector<uint8_t> o;
     DecodedStream ds(c, o, false);
     const int rc = codec.decode(x, c, (const uint8_t*)in, n, ds, st, CrcAt::Host, nullptr);
-    c->ev_used = 0;
+    scratch_spans_done(c);
     st.tar_bytes = o.size();
     st.wall_ms = now_ms() - t_top0_;
     x->unpack = st;

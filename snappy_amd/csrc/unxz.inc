@@ -75,16 +75,15 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             c->xz.blk.h[k] = XzGpuBlock{b.in_off, b.in_len, base + b.out_off, b.out_len, b.dict_size, (uint32_t)kXzBad};
         }
         HIP_TRY(c, hipMemcpyAsync(c->xz.blk.d.data(), c->xz.blk.h.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyHostToDevice, c->f_stream));
-        EventPair* ev = next_events(c, 2);
-        if (!ev) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(ev->a, c->f_stream));
+        Span ev;
+        if ((rc = span_begin(c, Ev::Codec, c->f_stream, &ev))) return rc;
         HIP_TRY(c, launch_lzma2_blocks(c->xz.d_in.data(), c->inf.d_out.data(), c->xz.blk.d.data(), (uint32_t)gpu.size(), c->f_stream));
-        HIP_TRY(c, hipEventRecord(ev->b, c->f_stream));
+        if ((rc = span_end(c, ev, c->f_stream))) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->xz.blk.h.data(), c->xz.blk.d.data(), gpu.size() * sizeof(XzGpuBlock), hipMemcpyDeviceToHost, c->f_stream));
         HIP_TRY(c, hipStreamSynchronize(c->f_stream));
-        (void)hipEventElapsedTime(&kms, ev->a, ev->b);
+        kms = span_ms(ev);
         st.inflate_ms += kms;
-        c->ev_used = 0;
+        scratch_spans_done(c);
         // the Checks of what the kernel decoded, in HBM, a range a Block
         std::vector<uint32_t> ok, k32, k64, k256;
         for (size_t k = 0; k < gpu.size(); ++k) {
@@ -102,11 +101,9 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
                 fr.push_back(BcjRange{base + blocks[i].out_off, blocks[i].out_len, 0, blocks[i].bcj, blocks[i].bcj_start, 0});
                 fs.filter = blocks[i].bcj;
             }
-        EventPair fev{};
         if (!fr.empty()) {
-            if ((!c->bcj_ev.a && hipEventCreate(&c->bcj_ev.a) != hipSuccess) || (!c->bcj_ev.b && hipEventCreate(&c->bcj_ev.b) != hipSuccess))
-                return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            fev = c->bcj_ev;
+            if (c->bcj_ev[0].ensure() != hipSuccess || c->bcj_ev[1].ensure() != hipSuccess) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
+            const Span fev{c->bcj_ev[0], c->bcj_ev[1]};
             rc = bcj_ranges_dev(c, c->inf.d_out.data(), fr, c->f_stream, &fev);
             if (rc) return rc;
             fs.device_blocks = fr.size();
@@ -131,7 +128,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             ranges(k32);
             std::vector<uint32_t> got(k32.size());
             rc = crc_ranges_dev(c, kCrcGzip, c->inf.d_out.data(), offs.data(), lens.data(), k32.size(), got.data(), c->f_stream, &cms);
-            c->ev_used = 0;
+            scratch_spans_done(c);
             if (rc) return rc;
             for (size_t k = 0; k < k32.size(); ++k) bad |= got[k] != xz_le32(xz + blocks[k32[k]].check_off);
         }
@@ -139,7 +136,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             ranges(k64);
             std::vector<uint64_t> got(k64.size());
             rc = crc_ranges_dev(c, 0, c->inf.d_out.data(), offs.data(), lens.data(), k64.size(), got.data(), c->f_stream, &cms);
-            c->ev_used = 0;
+            scratch_spans_done(c);
             if (rc) return rc;
             for (size_t k = 0; k < k64.size(); ++k) {
                 const uint8_t* f = xz + blocks[k64[k]].check_off;
@@ -150,15 +147,14 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             ranges(k256);
             std::vector<uint8_t> got(k256.size() * kSha256Digest);
             rc = sha256_ranges_dev(c, c->inf.d_out.data(), offs.data(), lens.data(), k256.size(), got.data(), c->f_stream, &cms);
-            c->ev_used = 0;
+            scratch_spans_done(c);
             if (rc) return rc;
             for (size_t k = 0; k < k256.size(); ++k) bad |= memcmp(got.data() + k * kSha256Digest, xz + blocks[k256[k]].check_off, kSha256Digest) != 0;
         }
         HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the Check calls waited on the same stream, but there may be none)
         st.inflate_ms += cms;
         if (!fr.empty()) {
-            float fms = 0;
-            (void)hipEventElapsedTime(&fms, fev.a, fev.b);
+            const float fms = span_ms(Span{c->bcj_ev[0], c->bcj_ev[1]});
             fs.device_ms = fms;
             st.inflate_ms += fms;
         }

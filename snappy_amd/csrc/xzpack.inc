@@ -95,13 +95,11 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, u
     HIP_TRY(c, hipMemcpyAsync(b.zend.d.data(), b.zend.h.data(), (size_t)nch * 8, hipMemcpyHostToDevice, zs));
     HIP_TRY(c, hipMemsetAsync(b.chk.d.data(), 0xff, (size_t)nch * sizeof(Lzma2Verdict), zs)); // (a verdict that is not written is a refusal)
     for (uint32_t c0 = 0; c0 < nch; c0 += kLzCheckLaunchChunks) {
-        EventPair* e = next_events(c, 3);
-        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        const EventPair ev = *e;
-        HIP_TRY(c, hipEventRecord(ev.a, zs));
+        Span ev;
+        if (int rc = span_begin(c, Ev::Check, zs, &ev)) return rc;
         HIP_TRY(c, launch_lzma2_check(src, n, bs, b.d_out.data(), total, b.dst.d.data(), b.zend.d.data(), c0,
                                       std::min(kLzCheckLaunchChunks, nch - c0), nch, b.chk.d.data(), zs));
-        HIP_TRY(c, hipEventRecord(ev.b, zs));
+        if (int rc = span_end(c, ev, zs)) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(b.chk.h.data(), b.chk.d.data(), (size_t)nch * sizeof(Lzma2Verdict), hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
@@ -128,19 +126,16 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, u
             }
         }
         if (b.feq.size() < nblk) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
-        EventPair* e = next_events(c, 3);
-        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        EventPair fev = *e;
-        const int rc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        Span fev;
+        int rc = span_take(c, Ev::Check, &fev);
+        if (!rc) rc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
         if (rc) return rc;
         HIP_TRY(c, hipMemsetAsync(b.feq.d.data(), 1, nblk, zs)); // equal until a chunk says otherwise
         HIP_TRY(c, hipMemcpyAsync(b.fcmp.d.data(), b.fcmp.h.data(), nc * sizeof(CmpChunk), hipMemcpyHostToDevice, zs));
         HIP_TRY(c, launch_compare(b.fcmp.d.data(), (uint32_t)nc, b.feq.d.data(), zs));
         HIP_TRY(c, hipMemcpyAsync(b.feq.h.data(), b.feq.d.data(), nblk, hipMemcpyDeviceToHost, zs));
         HIP_TRY(c, hipStreamSynchronize(zs));
-        float fms = 0;
-        (void)hipEventElapsedTime(&fms, fev.a, fev.b);
-        z.filt_ms += fms;
+        z.filt_ms += span_ms(fev);
         for (uint32_t k = 0; k < nblk; ++k) {
             if (b.feq.h[k]) continue;
             // where: the Block's two sides read back (the failing path alone pays for it)
@@ -178,37 +173,31 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     // with a BCJ filter: the slot's bytes once more, filtered in place, a range a Block (positions from the Block's first byte);
     // the LZMA2 kernels read the copy, the Checks below the staged bytes
     const uint8_t* src = sl.d_buf.data();
-    EventPair fev{};
+    Span fev, ev, ev2;
     if (z.filter) {
         if (b.d_filt.size() < n) return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
         HIP_TRY(c, hipMemcpyAsync(b.d_filt.data(), sl.d_buf.data(), n, hipMemcpyDeviceToDevice, zs));
         std::vector<BcjRange> fr(nblk);
         for (uint32_t k = 0; k < nblk; ++k) fr[k] = BcjRange{(uint64_t)k * bs, std::min<uint64_t>(bs, n - (uint64_t)k * bs), 0, z.filter, 0, 1};
-        EventPair* e = next_events(c, 2);
-        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        fev = *e;
-        const int frc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        int frc = span_take(c, Ev::Codec, &fev);
+        if (!frc) frc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
         if (frc) return frc;
         src = b.d_filt.data();
         z.filt_blocks += nblk;
     }
-    EventPair* evp = next_events(c, 2);
-    if (!evp) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const EventPair ev = *evp; // (by value: the pool may grow)
-    HIP_TRY(c, hipEventRecord(ev.a, zs));
+    int rc = span_begin(c, Ev::Codec, zs, &ev);
+    if (rc) return rc;
     HIP_TRY(c, launch_lzma_chains(src, n, (uint32_t)bs, b.d_prev.data(), zs));
-    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    if ((rc = span_end(c, ev, zs))) return rc;
     // a launch codes what is resident at once, no more: a longer slot goes in several launches (each with its own pair of
     // events: the longest single launch is what DESIGN.md sec. 18 holds against sec. 17's one-second bound)
-    std::vector<EventPair> evl;
+    std::vector<Span> evl;
     for (uint32_t c0 = 0; c0 < nch; c0 += kXzEncLaunchChunks) {
-        EventPair* e = next_events(c, 2);
-        if (!e) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-        evl.push_back(*e);
-        HIP_TRY(c, hipEventRecord(evl.back().a, zs));
+        evl.emplace_back();
+        if ((rc = span_begin(c, Ev::Codec, zs, &evl.back()))) return rc;
         HIP_TRY(c, launch_lzma2_chunks(src, n, (uint32_t)bs, b.d_prev.data(), b.d_cand.data(), b.d_slots.data(), b.res.d.data(), c0,
                                        std::min(kXzEncLaunchChunks, nch - c0), zs));
-        HIP_TRY(c, hipEventRecord(evl.back().b, zs));
+        if ((rc = span_end(c, evl.back(), zs))) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nch * 4, hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
@@ -237,17 +226,13 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     gz_wait_buf(g, zbuf); // the consumers have let go of what this buffer held two slots ago
     uint8_t* h = b.h_out[zbuf].data();
     HIP_TRY(c, hipMemcpyAsync(b.dst.d.data(), b.dst.h.data(), (size_t)nch * 8, hipMemcpyHostToDevice, zs));
-    EventPair* evp2 = next_events(c, 2);
-    if (!evp2) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-    const EventPair ev2 = *evp2;
-    HIP_TRY(c, hipEventRecord(ev2.a, zs));
+    if ((rc = span_begin(c, Ev::Codec, zs, &ev2))) return rc;
     HIP_TRY(c, launch_lzma2_concat(src, n, (uint32_t)bs, b.d_slots.data(), b.res.d.data(), b.dst.d.data(), b.d_out.data(), nch, zs));
-    HIP_TRY(c, hipEventRecord(ev2.b, zs));
+    if ((rc = span_end(c, ev2, zs))) return rc;
     HIP_TRY(c, hipMemcpyAsync(h, b.d_out.data(), total, hipMemcpyDeviceToHost, zs));
     // the Blocks' Checks, from the staged bytes in HBM by the Check's kernel (each waits for the stream: the piece is back
     // when it returns; with no Check the stream is waited for here)
     double crc_ms = 0;
-    int rc = SNAPHASH_OK;
     if (check == kXzCheckCrc64) {
         std::vector<uint64_t> crcs(nblk);
         rc = crc_ranges_dev(c, 0, sl.d_buf.data(), offs.data(), lens.data(), nblk, crcs.data(), zs, &crc_ms);
@@ -266,17 +251,15 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     if (rc) return rc;
     float filt_ms = 0;
     if (z.filter) {
-        (void)hipEventElapsedTime(&filt_ms, fev.a, fev.b); // (the stream has been waited for)
+        filt_ms = span_ms(fev); // (the stream has been waited for)
         z.filt_ms += filt_ms;
     }
     if (z.self_check && (rc = xz_self_check_slot(g, z, sl, src, n, lay, at, total)) != SNAPHASH_OK) return rc;
     if (getenv("SNAPHASH_TRACE_XZ")) { // the kernels of this slot, one by one (tools/xz_bench.py reads the line)
-        float chains = 0, concat = 0, sum = 0, longest = 0;
-        (void)hipEventElapsedTime(&chains, ev.a, ev.b);
-        (void)hipEventElapsedTime(&concat, ev2.a, ev2.b);
-        for (const EventPair& e : evl) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, e.a, e.b);
+        const float chains = span_ms(ev), concat = span_ms(ev2);
+        float sum = 0, longest = 0;
+        for (const Span& e : evl) {
+            const float ms = span_ms(e);
             sum += ms;
             longest = std::max(longest, ms);
         }
