@@ -389,6 +389,11 @@ typedef struct snaphash_xz_options {
     uint32_t check;       /* as in snaphash_xz_buffer_check: 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256 */
     uint32_t filter;      /* a BCJ filter in front of LZMA2, by the format's id: 0 none, 4 x86, 7 ARM, 8 ARM-Thumb; anything
                            * else is SNAPHASH_EINVAL.  (The field was `reserved`, 0, at this offset and size.)  See below. */
+    uint32_t level;       /* 0: the greedy parse, one candidate a position (what every entry without a level writes, byte for
+                           * byte); 1: several candidates a position and a price-based shortest-path parse:
+                           * smaller files for more kernel time.  Anything else is SNAPHASH_EINVAL.  Read when struct_size >= 32;
+                           * a struct_size of 24, the struct before this field, means level 0. */
+    uint32_t reserved2;   /* 0; anything else is SNAPHASH_EINVAL */
 } snaphash_xz_options;
 typedef struct snaphash_xz_selfcheck_stats {
     uint32_t struct_size; /* set by the caller */
@@ -397,8 +402,11 @@ typedef struct snaphash_xz_selfcheck_stats {
     double ms;            /* the check kernel's own time, HIP events */
 } snaphash_xz_selfcheck_stats;
 /* opt == NULL, or a struct that is all zero (struct_size included): byte for byte what snaphash_xz_buffer /
- * snaphash_tar_create_xz write (1 MiB Blocks, CRC-64, no self-check).  Otherwise struct_size says the struct's size and
- * every field means what it says.  SNAPHASH_EINVAL: an unknown flag, a refused Block size, an unknown Check id. */
+ * snaphash_tar_create_xz write (1 MiB Blocks, CRC-64, no self-check, level 0).  Otherwise struct_size says the struct's size
+ * -- 24 (the struct without level and reserved2) or at least 32 -- and every field means what it says.  SNAPHASH_EINVAL: any
+ * other struct_size, an unknown flag, a refused Block size, an unknown Check id, a level above 1, a nonzero reserved2.  A
+ * refused call touches nothing.  At any level the bytes are a function of (data, the options) alone, and the file differs
+ * from level 0's only in the LZMA2 chunks' contents: the self-check, the filters and the install side take it as it is. */
 int snaphash_xz_buffer_ex(snaphash_ctx *ctx, const void *data, size_t n, const snaphash_xz_options *opt, void **xz_out,
                           size_t *xz_len);
 int snaphash_tar_create_xz_ex(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
@@ -470,6 +478,12 @@ int snaphash_deflate_codes_device(snaphash_ctx *ctx, const void *d_freq, size_t 
 int snaphash_xzenc_stages_device(snaphash_ctx *ctx, const void *d_in, size_t n, uint64_t block_size, uint32_t launch_chunks,
                                  void *d_prev, void *d_cand, void *d_slots, void *d_res, void *d_dst, void *d_out, size_t out_cap,
                                  uint64_t *block_total);
+/* The same at a level (snaphash_xz_options.level; above 1: SNAPHASH_EINVAL): level 0 is the entry above, byte for byte.  At
+ * level 1 the chunks are coded by lzma2_chunks_priced_kernel and d_cand holds 4 uint32 per byte of the piece, 4 n in all: a
+ * position's candidates nearest first, lengths strictly rising, 0 behind the last; launch_chunks 0 is then the producer's 768. */
+int snaphash_xzenc_stages_device_ex(snaphash_ctx *ctx, const void *d_in, size_t n, uint64_t block_size, uint32_t launch_chunks,
+                                    void *d_prev, void *d_cand, void *d_slots, void *d_res, void *d_dst, void *d_out, size_t out_cap,
+                                    uint64_t *block_total, uint32_t level);
 
 /* ---- the data.tar.bz2 producer (the one format ClickDeb.Unpack reads, deb.go:185, and tarCreate refuses to write) ---- */
 

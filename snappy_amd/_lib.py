@@ -54,6 +54,7 @@ EXPORTS = [
     "snaphash_deflate_codes_device",
     # the .xz encoder's kernels alone
     "snaphash_xzenc_stages_device",
+    "snaphash_xzenc_stages_device_ex",
     # a SHA-512 kernel alone, over a caller's job table
     "snaphash_sha512_jobs_device",
     # the data.tar.bz2 producer, its BWT stage alone, and its stages on a caller's arrays
@@ -154,7 +155,7 @@ class XzCheckStats(ctypes.Structure):
 
 class XzOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("block_size", ctypes.c_uint64),
-                ("check", ctypes.c_uint32), ("filter", ctypes.c_uint32)]
+                ("check", ctypes.c_uint32), ("filter", ctypes.c_uint32), ("level", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
 
 
 class UnxzOptions(ctypes.Structure):
@@ -334,6 +335,7 @@ def lib():
     L.snaphash_snap_build.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(SnapBuildOptions), ctypes.c_char_p, ctypes.c_char_p,
                                       ctypes.POINTER(SnapBuildStats)]
     L.snaphash_deflate_check_device.argtypes = [vp, vp, sz, vp, u64p, sz, ctypes.c_int, vp]
+    L.snaphash_xzenc_stages_device_ex.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, sz, u64p, ctypes.c_uint32]
     L.snaphash_xz_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(XzOptions), ctypes.POINTER(vp), ctypes.POINTER(sz)]
     L.snaphash_tar_create_xz_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(XzOptions), ctypes.POINTER(vp),
                                             ctypes.POINTER(sz), ctypes.c_char_p]
@@ -524,18 +526,20 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def xz_buffer(self, data, block_size=0, check=None, self_check=False, filter=None):
+    def xz_buffer(self, data, block_size=0, check=None, self_check=False, filter=None, level=0):
         """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU.  check: the Blocks'
         Check id -- 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256, each taken in HBM; None: CRC-64 through the entry point that
         takes no Check.  self_check: every LZMA2 chunk is walked against the bytes it was made from before it leaves HBM
         (snaphash_xz_buffer_ex with SNAPHASH_XZ_SELF_CHECK; xz_selfcheck_stats() tells what was walked); the bytes are
         the same.  filter: a BCJ filter in front of LZMA2 in every Block -- "x86", "arm", "armthumb" or the format's id
-        (4, 7, 8), applied in HBM (snaphash_xz_buffer_ex; xz_filter_stats() tells what ran); None or 0: none."""
+        (4, 7, 8), applied in HBM (snaphash_xz_buffer_ex; xz_filter_stats() tells what ran); None or 0: none.  level: 0 the
+        greedy parse, 1 several candidates a position and a price-based parse (snaphash_xz_buffer_ex): a smaller file for
+        more kernel time."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
         filter = bcj_filter(filter)
-        if self_check or filter:
-            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, 4 if check is None else check, filter)
+        if self_check or filter or level:
+            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, 4 if check is None else check, filter, level)
             self._check(lib().snaphash_xz_buffer_ex(self._h, ctypes.addressof(buf), len(data), ctypes.byref(opt), ctypes.byref(p), ctypes.byref(n)))
         elif check is None:
             self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
@@ -618,15 +622,15 @@ class Context:
                                                        ctypes.byref(total)))
         return total.value
 
-    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False, filter=None):
+    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False, filter=None, level=0):
         """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.  With the defaults:
         snaphash_tar_create_xz (1 MiB Blocks, CRC-64).  Anything else goes through snaphash_tar_create_xz_ex: block_size
-        check, self_check and filter as in xz_buffer (hashes.yaml and the Blocks' Checks are of the unfiltered bytes).
+        check, self_check, filter and level as in xz_buffer (hashes.yaml and the Blocks' Checks are of the unfiltered bytes).
         -> (yaml bytes or None, archive digest (64 bytes))."""
         filter = bcj_filter(filter)
-        if block_size == 0 and check == 4 and not self_check and not filter:
+        if block_size == 0 and check == 4 and not self_check and not filter and not level:
             return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
-        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, filter)
+        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, filter, level)
         return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz_ex", _opt=opt)
 
     def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create", _opt=None):
@@ -763,12 +767,17 @@ class Context:
         xz = bytes(xz)
         self._check(lib().snaphash_unxz_block_device(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz), block, d_dst, dst_len))
 
-    def xzenc_stages_device(self, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst, d_out, out_cap):
+    def xzenc_stages_device(self, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst, d_out, out_cap, level=None):
         """The .xz encoder's chain, chunk and concatenation kernels over d_in[0..n) in the caller's HBM (device addresses
         as ints; sizes as snaphash.h states them), the chunks in launches of launch_chunks (0: the producer's).  Block
-        headers, padding and Checks are not written.  -> every Block's total bytes in d_out."""
+        headers, padding and Checks are not written.  level: None for the plain entry; 0 or 1 for
+        snaphash_xzenc_stages_device_ex (at level 1 d_cand holds 4 words a byte).  -> every Block's total bytes in d_out."""
         bs = block_size or 1 << 20
         tot = (ctypes.c_uint64 * max((n + bs - 1) // bs, 1))()
+        if level is not None:
+            self._check(lib().snaphash_xzenc_stages_device_ex(self._h, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst,
+                                                              d_out, out_cap, tot, level))
+            return list(tot[:(n + bs - 1) // bs])
         self._check(lib().snaphash_xzenc_stages_device(self._h, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst,
                                                        d_out, out_cap, tot))
         return list(tot[:(n + bs - 1) // bs])

@@ -7,7 +7,7 @@
  *                                      Build's data step fused (clickdeb/deb.go:261-344 + snappy/build.go:517-520):
  *                                      data.tar.gz of BUILD_DIR without DEBIAN/, every file read once, then
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
- *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] BUILD_DIR OUT.tar.xz
+ *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] [-L 0|1] BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB (or -B), Check
  *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU; -F: a BCJ
  *                                      filter in front of LZMA2, applied on the GPU (what xz writes when XZ_OPT names one)
@@ -17,7 +17,7 @@
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
  *   snaphash [options] bzip2 [-L LEVEL] [-c] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9); -c: the .bz2
  *                                                self-check on the GPU (-s prints what it checked)
- *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb]
+ *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] [-L 0|1]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
  *                                                Blocks' Check as named (default crc64), taken on the GPU; -c: the LZMA2
  *                                                self-check on the GPU (-s prints what it walked); -F: a BCJ filter
@@ -66,10 +66,10 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
-                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] DIR OUT.tar.xz |\n"
+                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] [-L 0|1] DIR OUT.tar.xz |\n"
                     "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
                     "       (in front of their names build-bz2 also takes [-c] [-L LEVEL] and bzip2 [-c]: -c is the .bz2 self-check)\n"
-                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] [-L 0|1] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz [-F] IN.xz OUT |\n"
                     "       unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
@@ -104,6 +104,12 @@ static int xz_check_id(const char *w)
 static uint32_t xz_filter_id(const char *w)
 {
     return !strcmp(w, "x86") ? 4u : !strcmp(w, "arm") ? 7u : !strcmp(w, "armthumb") ? 8u : 0u;
+}
+
+/* the .xz commands' -L: the level, 0 or 1, or -1 */
+static int xz_level(const char *w)
+{
+    return !strcmp(w, "0") ? 0 : !strcmp(w, "1") ? 1 : -1;
 }
 
 /* -s after an .xz call with -F: what the BCJ filters did */
@@ -274,6 +280,7 @@ int main(int argc, char **argv)
                 argv += 2; argc -= 2;
             } else if (!strcmp(argv[2], "-C") && argc > 5 && (id = xz_check_id(argv[3])) >= 0) { xo.check = (uint32_t)id; argv += 2; argc -= 2; }
             else if (!strcmp(argv[2], "-F") && argc > 5 && (xo.filter = xz_filter_id(argv[3])) != 0) { argv += 2; argc -= 2; }
+            else if (!strcmp(argv[2], "-L") && argc > 5 && xz_level(argv[3]) >= 0) { xo.level = (uint32_t)xz_level(argv[3]); argv += 2; argc -= 2; }
             else bad = 1;
             xz_ex = 1;
         }
@@ -362,7 +369,7 @@ int main(int argc, char **argv)
         size_t len = 0, zl = 0;
         uint64_t block = 0;
         int have_block = 0, check = -1, self = 0; /* -1: no -C, the entry point that takes no Check */
-        uint32_t filter = 0;
+        uint32_t filter = 0, level = 0;
         for (int i = 4; i < argc;) {
             if (!strcmp(argv[i], "-c")) { self = 1; i += 1; continue; }
             if (i + 1 >= argc) { snaphash_destroy(c); return usage(); }
@@ -371,6 +378,7 @@ int main(int argc, char **argv)
                 have_block = 1;
             } else if (!strcmp(argv[i], "-C") && xz_check_id(argv[i + 1]) >= 0) check = xz_check_id(argv[i + 1]);
             else if (!strcmp(argv[i], "-F") && xz_filter_id(argv[i + 1]) != 0) filter = xz_filter_id(argv[i + 1]);
+            else if (!strcmp(argv[i], "-L") && xz_level(argv[i + 1]) >= 0) level = (uint32_t)xz_level(argv[i + 1]);
             else { snaphash_destroy(c); return usage(); }
             i += 2;
         }
@@ -381,11 +389,12 @@ int main(int argc, char **argv)
         xo.block_size = block;
         xo.check = check < 0 ? 4u : (uint32_t)check;
         xo.filter = filter;
+        xo.level = level;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
         void *z = NULL;
         rc = (have_block && block == 0) ? SNAPHASH_EINVAL
-             : self || filter           ? snaphash_xz_buffer_ex(c, in, len, &xo, &z, &zl)
+             : self || filter || level  ? snaphash_xz_buffer_ex(c, in, len, &xo, &z, &zl)
              : check < 0                ? snaphash_xz_buffer(c, in, len, block, &z, &zl)
                                         : snaphash_xz_buffer_check(c, in, len, block, (uint32_t)check, &z, &zl);
         if (rc) ret = die(c, rc, "xz");

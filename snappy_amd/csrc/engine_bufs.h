@@ -308,6 +308,13 @@ struct XzEncBufs {
     DevBuf<uint8_t> d_filt;    // a BCJ filter's: the slot's bytes filtered, a byte per staged byte: allocated by the call that
     Twin<CmpChunk> fcmp;       // asks for a filter; with the self-check too, the range-compare kernel's table and its verdicts,
     Twin<uint8_t> feq;         // a byte a Block
+    DevBuf<uint32_t> d_cand_set; // level 1's: kXzEncCands words per staged byte: allocated by the call that asks for level 1
+    hipError_t ensure_level(uint64_t slot_bytes)
+    {
+        const hipError_t e = d_cand_set.reserve(slot_bytes * kXzEncCands);
+        if (e) each(Release()); // (none of it is left behind)
+        return e;
+    }
     hipError_t ensure_filter(uint64_t slot_bytes) { return d_filt.reserve(slot_bytes + 16); } // (the compare kernel loads 16 bytes at a time)
     hipError_t ensure_filter_check(uint64_t slot_bytes)
     {
@@ -341,7 +348,7 @@ struct XzEncBufs {
         if (e) each(Release()); // (none of it is left behind)
         return e;
     }
-    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); zend.each(f); chk.each(f); f(d_filt); fcmp.each(f); feq.each(f); }
+    template <class F> void each(F&& f) { f(d_prev); f(d_cand); f(d_slots); f(d_out); res.each(f); dst.each(f); f(h_out[0]); f(h_out[1]); zend.each(f); chk.each(f); f(d_filt); fcmp.each(f); feq.each(f); f(d_cand_set); }
 };
 
 // GPU bzip2 encoder (bzpack.inc), for `blocks` blocks a launch of up to `cap` bytes each after RLE1: the sort's scratch

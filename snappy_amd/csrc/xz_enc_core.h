@@ -22,6 +22,9 @@
 //                                            longest kept, the nearest among equals, every compare cut at the chunk's end
 //   xzenc_chunk                              the parse (greedy, one step of lazy evaluation, rep0-3 first, short reps),
 //                                            the symbol coder and the adaptive range encoder, one serial pass
+// At level 1 (the level is then part of what the bytes are a function of) the last two are
+//   xzenc_find_set                           up to kXzEncCands candidates at p: kXzEncDepthHigh links, lengths strictly rising
+//   xzenc_chunk_priced                       a price-based shortest-path parse over windows, relaxed by all lanes; the same coder
 #pragma once
 #include <algorithm>
 
@@ -406,6 +409,403 @@ XZE_HD uint32_t xzenc_chunk_bytes(uint32_t usize, uint32_t res) { return res == 
 // a result the kernel may report for a chunk of usize bytes
 XZE_HD bool xzenc_res_valid(uint32_t usize, uint32_t res) { return res == kXzEncStored || (res >= 5 && xzenc_is_lzma(res, usize)); }
 
+// ---- level 1: several candidates a position, prices, a shortest-path parse ------------------------------
+//
+// The chunk's bytes stay a pure function of (the Block's bytes, the chunk's bounds, the level).  xzenc_chunk_priced is ONE
+// function for the host model and the kernel; what differs is LN, the lanes: the kernel's 256 threads with a barrier, or
+// a loop over 256 lane numbers on the host, in ascending or descending order.  The contract that keeps the two byte for
+// byte equal:
+//   - A window of at most kXzEncWindow positions is parsed at a time, with prices taken from the probabilities as they
+//     stand at its start.  Node t is "t bytes into the window"; the edges out of node cur are, in this order of index:
+//     0 the literal, 1 the short rep, 2..5 rep0..rep3, 6..6+K-1 the candidates nearest first; a rep or candidate of
+//     length n gives an edge of every length 2..n, cut at the chunk's end and at the window's.
+//   - The edges of ONE node are relaxed side by side, a lane a target: lane i owns the targets cur + 2 + i and
+//     cur + 2 + i + 256, lane 0 the target cur + 1 as well.  Only the owner writes a target's node, so no two lanes meet.
+//     Among the edges into one target from one node the lowest price wins, and of equal prices the lower edge index; an
+//     edge from a later node replaces what an earlier node left only when it is strictly cheaper.  No step depends on
+//     the order in which the lanes run.
+//   - The window closes where every path has come together (no edge reaches past the node in hand), when it is full, or
+//     in front of a position where a match of 273 bytes starts; such a match at the window's first position is taken as
+//     it is, the lowest rep that has it before a candidate.
+//   - Then lane 0 walks the chosen edges back, codes them with the lzmaenc_* routines above (the probabilities adapt),
+//     and the next window opens.  The give-up of xzenc_chunk and xzenc_is_lzma hold as at level 0.
+constexpr uint32_t kXzEncDepthHigh = 32;  // chain links examined per position at level 1
+constexpr uint32_t kXzEncCands = 4;       // K: candidates kept per position
+constexpr uint32_t kXzEncWindow = 1024;   // W: positions of a window
+constexpr uint32_t kXzEncLanes = 256;     // lanes that relax a node's edges
+constexpr uint32_t kXzEncLevelMax = 1;
+constexpr uint32_t kXzEncPriceInf = 1u << 30;
+constexpr uint32_t kXzEncSlots = 44;      // distance slots a Block of at most 4 MiB can need
+enum : uint32_t { kXzEdgeLit = 0, kXzEdgeShortRep = 1, kXzEdgeRep = 2, kXzEdgeMatch = 6 };
+
+// Up to K candidates at position p, into out[0 .. K): lengths strictly rising and for each length the nearest distance
+// (the chain is walked nearest first, kXzEncDepthHigh links), packed as xzenc_find packs one, 0 behind the last.  Of
+// more than K the longest K are kept.  Every compare is cut at the chunk's end.
+XZE_HD void xzenc_find_set(const uint8_t* blk, const uint32_t* prev, uint32_t p, uint32_t ce, uint32_t* out)
+{
+    static_assert(kXzEncCands == 4, "four names, not an array: they stay in registers on the device");
+    uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, n = 0;
+    const uint32_t maxlen = ce - p < kLzmaMatchMax ? ce - p : kLzmaMatchMax;
+    if (maxlen >= 2) {
+        uint32_t best_len = 1;
+        uint32_t c = prev[p];
+        for (uint32_t d = 0; d < kXzEncDepthHigh && c < p; ++d) { // (kXzEncNone fails c < p)
+            const uint32_t l = xzenc_common(blk + c, blk + p, maxlen);
+            if (l > best_len) {
+                best_len = l;
+                a0 = a1; a1 = a2; a2 = a3;
+                a3 = l << 22 | (p - c - 1);
+                if (n < kXzEncCands) ++n;
+                if (l == maxlen) break;
+            }
+            c = prev[c];
+        }
+    }
+    for (uint32_t i = n; i < kXzEncCands; ++i) { a0 = a1; a1 = a2; a2 = a3; a3 = 0; } // to the front
+    out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
+}
+
+// round(-16 log2(p / 2048)) for 1 <= p < 2048, in integers: the whole part of log2 from the leading bit, five more bits
+// by squaring (the last one rounds)
+XZE_HD uint32_t xzenc_price_of(uint32_t p)
+{
+    const uint32_t msb = 31 - (uint32_t)__builtin_clz(p);
+    uint64_t x = (uint64_t)p << (31 - msb); // p / 2^msb in [1, 2), 31 bits behind the point
+    uint32_t l32 = msb;
+    for (int i = 0; i < 5; ++i) {
+        x = (x * x) >> 31;
+        l32 <<= 1;
+        if (x >> 32) { l32 |= 1; x >>= 1; }
+    }
+    return (705 - 2 * l32) >> 2; // 16 * 11 - (l32 + 1/2) / 2, to the nearest
+}
+
+struct XzEncNode {
+    uint32_t price;
+    uint32_t dist;   // a match's distance - 1
+    uint16_t len;    // of the edge that arrives here: the node it left is len in front
+    uint8_t kind;    // kXzEdge*: for a rep kXzEdgeRep + k
+    uint8_t state;   // the coder's here, and its rep distances: set when the node is visited
+    uint32_t rep[4];
+};
+// What the parse keeps beside the probabilities: LDS in the kernel.  28 700 + 2 050 + 256 + 4 352 + 352 + 32 + 8 bytes.
+struct XzEncWork {
+    XzEncNode node[kXzEncWindow + 1];
+    uint16_t next[kXzEncWindow + 1];                          // lane 0's: the chosen edges, forwards
+    uint16_t ptab[128];                                       // a bit's price by probability >> 4
+    uint16_t lenp[2 * 4 * (kLzmaMatchMax - 1)];               // [new match, rep][pos_state][len - 2]
+    uint16_t slotp[4 * kXzEncSlots];                          // [len state][slot]
+    uint16_t alignp[16];
+    uint32_t flag, res;                                       // lane 0 tells the others: gave up; the chunk's result
+};
+
+XZE_HD uint32_t xzp_bit(const uint16_t* ptab, uint32_t prob, uint32_t bit) { return ptab[((bit ? 2048 - prob : prob) >> 4) & 127]; }
+XZE_HD uint32_t xzp_tree(const uint16_t* ptab, const uint16_t* p, uint32_t bits, uint32_t value)
+{
+    uint32_t m = 1, sum = 0;
+    for (uint32_t i = bits; i-- > 0;) {
+        const uint32_t b = (value >> i) & 1;
+        sum += xzp_bit(ptab, p[m], b);
+        m = (m << 1) | b;
+    }
+    return sum;
+}
+XZE_HD uint32_t xzp_tree_rev(const uint16_t* ptab, const uint16_t* p, uint32_t bits, uint32_t value)
+{
+    uint32_t m = 1, sum = 0;
+    for (uint32_t i = 0; i < bits; ++i) {
+        const uint32_t b = (value >> i) & 1;
+        sum += xzp_bit(ptab, p[m], b);
+        m = (m << 1) | b;
+    }
+    return sum;
+}
+// what lzmaenc_len would pay; p: probs + kPLen or kPRepLen
+XZE_HD uint32_t xzp_len(const uint16_t* ptab, const uint16_t* p, uint32_t len, uint32_t pos_state)
+{
+    const uint32_t l = len - 2;
+    if (l < 8) return xzp_bit(ptab, p[kLenChoice], 0) + xzp_tree(ptab, p + kLenLow + (pos_state << 3), 3, l);
+    if (l < 16) return xzp_bit(ptab, p[kLenChoice], 1) + xzp_bit(ptab, p[kLenChoice2], 0) + xzp_tree(ptab, p + kLenMid + (pos_state << 3), 3, l - 8);
+    return xzp_bit(ptab, p[kLenChoice], 1) + xzp_bit(ptab, p[kLenChoice2], 1) + xzp_tree(ptab, p + kLenHigh, 8, l - 16);
+}
+// what lzmaenc_literal would pay for the byte at pos in state `state` with rep0
+XZE_HD uint32_t xzp_literal(const uint16_t* ptab, const uint16_t* probs, const uint8_t* blk, uint32_t pos, uint32_t state, uint32_t rep0)
+{
+    const uint32_t b = blk[pos];
+    const uint16_t* p = probs + kLzmaLitBase + 0x300u * ((pos ? blk[pos - 1] : 0u) >> 5);
+    if (state < 7) return xzp_tree(ptab, p, 8, b);
+    uint32_t mb = blk[pos - rep0 - 1], offs = 0x100, sym = 1, sum = 0;
+    for (uint32_t i = 8; i-- > 0;) {
+        mb <<= 1;
+        const uint32_t mbit = mb & offs;
+        const uint32_t bit = (b >> i) & 1;
+        sum += xzp_bit(ptab, p[offs + mbit + sym], bit);
+        sym = (sym << 1) | bit;
+        offs &= bit ? mbit : ~mbit;
+    }
+    return sum;
+}
+// what lzmaenc_match would pay for the distance dist1 + 1 behind a length of len, from the tables
+XZE_HD uint32_t xzp_dist(const XzEncWork& w, const uint16_t* probs, uint32_t dist1, uint32_t len)
+{
+    const uint32_t slot = lzmaenc_dist_slot(dist1);
+    uint32_t sum = w.slotp[(len < 6 ? len - 2 : 3) * kXzEncSlots + slot];
+    if (slot >= 4) {
+        const uint32_t nb = (slot >> 1) - 1;
+        const uint32_t base = (2 | (slot & 1)) << nb;
+        const uint32_t rest = dist1 - base;
+        if (slot < 14) sum += xzp_tree_rev(w.ptab, probs + kPSpecPos + base - slot - 1, nb, rest);
+        else sum += 16 * (nb - 4) + w.alignp[rest & 15];
+    }
+    return sum;
+}
+// entry i of the tables behind ptab, i < kXzEncTableEntries: lengths, slots, align
+constexpr uint32_t kXzEncLenEntries = 2 * 4 * (kLzmaMatchMax - 1);
+constexpr uint32_t kXzEncTableEntries = kXzEncLenEntries + 4 * kXzEncSlots + 16;
+XZE_HD void xzenc_table_entry(XzEncWork& w, const uint16_t* probs, uint32_t i)
+{
+    if (i < kXzEncLenEntries) {
+        const uint32_t which = i / (4 * (kLzmaMatchMax - 1)), r = i % (4 * (kLzmaMatchMax - 1));
+        w.lenp[i] = (uint16_t)xzp_len(w.ptab, probs + (which ? kPRepLen : kPLen), 2 + r % (kLzmaMatchMax - 1), r / (kLzmaMatchMax - 1));
+    } else if (i < kXzEncLenEntries + 4 * kXzEncSlots) {
+        const uint32_t j = i - kXzEncLenEntries;
+        w.slotp[j] = (uint16_t)xzp_tree(w.ptab, probs + kPPosSlot + ((j / kXzEncSlots) << 6), 6, j % kXzEncSlots);
+    } else {
+        const uint32_t j = i - kXzEncLenEntries - 4 * kXzEncSlots;
+        w.alignp[j] = (uint16_t)xzp_tree_rev(w.ptab, probs + kPAlign, 4, j);
+    }
+}
+
+// the coder's state and rep distances behind an edge
+XZE_HD void xzenc_apply(uint32_t kind, uint32_t dist, uint32_t& s, uint32_t& r0, uint32_t& r1, uint32_t& r2, uint32_t& r3)
+{
+    if (kind == kXzEdgeLit) {
+        s = s < 4 ? 0 : s < 10 ? s - 3 : s - 6;
+    } else if (kind == kXzEdgeShortRep) {
+        s = s < 7 ? 9 : 11;
+    } else if (kind == kXzEdgeMatch) {
+        r3 = r2; r2 = r1; r1 = r0; r0 = dist;
+        s = s < 7 ? 7 : 10;
+    } else {
+        const uint32_t k = kind - kXzEdgeRep;
+        if (k == 1) { const uint32_t d = r1; r1 = r0; r0 = d; }
+        else if (k == 2) { const uint32_t d = r2; r2 = r1; r1 = r0; r0 = d; }
+        else if (k == 3) { const uint32_t d = r3; r3 = r2; r2 = r1; r1 = r0; r0 = d; }
+        s = s < 7 ? 8 : 11;
+    }
+}
+
+// The lanes of the host model: a loop.  first(): lane 0's part runs once; sync(): the kernel's barrier.
+struct XzEncHostLanes {
+    bool descending = false;
+    template <class F> void each(F&& f)
+    {
+        if (!descending) for (uint32_t i = 0; i < kXzEncLanes; ++i) f(i);
+        else for (uint32_t i = kXzEncLanes; i-- > 0;) f(i);
+    }
+    bool first() const { return true; }
+    void sync() {}
+};
+
+// xzenc_chunk at level 1.  cand: kXzEncCands words a Block position (xzenc_find_set); w: scratch, any contents.  Every
+// lane calls it with the same arguments and gets the same result; only lane 0 writes out.
+template <class OPS, class LN>
+XZE_HD uint32_t xzenc_chunk_priced(const uint8_t* blk, uint32_t cs, uint32_t ce, const uint32_t* cand, uint16_t* probs, XzEncWork& w, uint8_t* out,
+                                  uint32_t cap, OPS& ops, LN& ln)
+{
+    const uint32_t usize = ce - cs;
+    LzmaEnc e; // (lane 0's is the coder; the others carry state and reps along, which every lane derives alike)
+    xzrc_init(e.rc, out, cap);
+    e.state = 0;
+    e.rep0 = e.rep1 = e.rep2 = e.rep3 = 0;
+    ln.each([&](uint32_t lane) {
+        if (lane < 128) w.ptab[lane] = (uint16_t)xzenc_price_of(16 * lane + 8);
+    });
+    uint32_t pos = cs, st = 0, w0 = 0, w1 = 0, w2 = 0, w3 = 0; // the window's start: position, state, reps
+    while (pos < ce) {
+        const uint32_t wmax = ce - pos < kXzEncWindow ? ce - pos : kXzEncWindow;
+        if (ln.first()) {
+            XzEncNode& z = w.node[0];
+            z.price = 0; z.dist = 0; z.len = 0; z.kind = 0;
+            z.state = (uint8_t)st;
+            z.rep[0] = w0; z.rep[1] = w1; z.rep[2] = w2; z.rep[3] = w3;
+        }
+        uint32_t len_end = 0, cur = 0;
+        uint32_t s = st, r0 = w0, r1 = w1, r2 = w2, r3 = w3; // the node in hand
+        for (;; ++cur) {
+            ln.sync(); // what the lanes left in the nodes (and, at a window's start, lane 0 in the probabilities) is there
+            uint32_t price = 0;
+            if (cur > 0) {
+                const XzEncNode& z = w.node[cur];
+                const XzEncNode& f = w.node[cur - z.len];
+                price = z.price;
+                s = f.state; r0 = f.rep[0]; r1 = f.rep[1]; r2 = f.rep[2]; r3 = f.rep[3];
+                xzenc_apply(z.kind, z.dist, s, r0, r1, r2, r3);
+                if (cur == len_end) break;
+                if (ln.first()) {
+                    XzEncNode& zz = w.node[cur];
+                    zz.state = (uint8_t)s;
+                    zz.rep[0] = r0; zz.rep[1] = r1; zz.rep[2] = r2; zz.rep[3] = r3;
+                }
+            }
+            const uint32_t p = pos + cur, ps = p & 3;
+            uint32_t maxlen = ce - p < kLzmaMatchMax ? ce - p : kLzmaMatchMax;
+            if (maxlen > wmax - cur) maxlen = wmax - cur;
+            // what leaves this node: the reps (none before the Block's first byte) and the candidates, cut to maxlen
+            uint32_t l0 = 0, l1 = 0, l2 = 0, l3 = 0;
+            bool rep0_byte = false;
+            if (p > 0) {
+                if (r0 + 1 <= p) {
+                    rep0_byte = blk[p - r0 - 1] == blk[p];
+                    if (maxlen >= 2) l0 = xzenc_common(blk + p - r0 - 1, blk + p, maxlen);
+                }
+                if (maxlen >= 2) {
+                    if (r1 + 1 <= p) l1 = xzenc_common(blk + p - r1 - 1, blk + p, maxlen);
+                    if (r2 + 1 <= p) l2 = xzenc_common(blk + p - r2 - 1, blk + p, maxlen);
+                    if (r3 + 1 <= p) l3 = xzenc_common(blk + p - r3 - 1, blk + p, maxlen);
+                }
+            }
+            const uint32_t* cp = cand + (size_t)p * kXzEncCands;
+            const uint32_t c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
+            uint32_t m0 = xzenc_cand_len(c0), m1 = xzenc_cand_len(c1), m2 = xzenc_cand_len(c2), m3 = xzenc_cand_len(c3);
+            const bool maximal = m0 == kLzmaMatchMax || m1 == kLzmaMatchMax || m2 == kLzmaMatchMax || m3 == kLzmaMatchMax ||
+                                 l0 == kLzmaMatchMax || l1 == kLzmaMatchMax || l2 == kLzmaMatchMax || l3 == kLzmaMatchMax;
+            if (m0 > maxlen) m0 = maxlen;
+            if (m1 > maxlen) m1 = maxlen;
+            if (m2 > maxlen) m2 = maxlen;
+            if (m3 > maxlen) m3 = maxlen;
+            if (maxlen < 2) m0 = m1 = m2 = m3 = 0;
+            uint32_t longest = l0;
+            if (l1 > longest) longest = l1;
+            if (l2 > longest) longest = l2;
+            if (l3 > longest) longest = l3;
+            if (m0 > longest) longest = m0;
+            if (m1 > longest) longest = m1;
+            if (m2 > longest) longest = m2;
+            if (m3 > longest) longest = m3;
+            if (longest < 2) longest = 0;
+            if (maximal && maxlen == kLzmaMatchMax) {
+                if (cur > 0) { // the window closes in front of it
+                    len_end = cur;
+                    break;
+                }
+                // the window's first position: the match as it is
+                uint32_t kind = kXzEdgeMatch, dist = 0;
+                if (l0 == kLzmaMatchMax) kind = kXzEdgeRep;
+                else if (l1 == kLzmaMatchMax) kind = kXzEdgeRep + 1;
+                else if (l2 == kLzmaMatchMax) kind = kXzEdgeRep + 2;
+                else if (l3 == kLzmaMatchMax) kind = kXzEdgeRep + 3;
+                else dist = xzenc_cand_dist1(m0 == kLzmaMatchMax ? c0 : m1 == kLzmaMatchMax ? c1 : m2 == kLzmaMatchMax ? c2 : c3);
+                if (ln.first()) {
+                    XzEncNode& z = w.node[kLzmaMatchMax];
+                    z.price = 0; z.dist = dist; z.len = (uint16_t)kLzmaMatchMax; z.kind = (uint8_t)kind;
+                }
+                xzenc_apply(kind, dist, s, r0, r1, r2, r3);
+                len_end = kLzmaMatchMax;
+                break;
+            }
+            if (cur == 0 && longest) { // the tables, from the probabilities as they stand now (a window of one byte needs none)
+                ln.each([&](uint32_t lane) {
+                    for (uint32_t i = lane; i < kXzEncTableEntries; i += kXzEncLanes) xzenc_table_entry(w, probs, i);
+                });
+                ln.sync();
+            }
+            const uint32_t old_end = len_end;
+            if (cur + (longest ? longest : 1) > len_end) len_end = cur + (longest ? longest : 1);
+            const uint32_t pm1 = price + xzp_bit(w.ptab, probs[kPIsMatch + (s << 4) + ps], 1);
+            const uint32_t prep = pm1 + xzp_bit(w.ptab, probs[kPIsRep + s], 1);
+            const uint32_t pg0 = xzp_bit(w.ptab, probs[kPIsRepG0 + s], 0);
+            if (ln.first()) { // edges 0 and 1, to the next node
+                uint32_t best = cur + 1 <= old_end ? w.node[cur + 1].price : kXzEncPriceInf;
+                uint32_t kind = 0xff;
+                const uint32_t plit = price + xzp_bit(w.ptab, probs[kPIsMatch + (s << 4) + ps], 0) + xzp_literal(w.ptab, probs, blk, p, s, r0);
+                if (plit < best) { best = plit; kind = kXzEdgeLit; }
+                if (rep0_byte) {
+                    const uint32_t psr = prep + pg0 + xzp_bit(w.ptab, probs[kPIsRep0Long + (s << 4) + ps], 0);
+                    if (psr < best) { best = psr; kind = kXzEdgeShortRep; }
+                }
+                if (kind != 0xff) {
+                    XzEncNode& z = w.node[cur + 1];
+                    z.price = best; z.dist = 0; z.len = 1; z.kind = (uint8_t)kind;
+                }
+            }
+            if (longest) {
+                const uint32_t pg0_1 = xzp_bit(w.ptab, probs[kPIsRepG0 + s], 1);
+                const uint32_t pg1_1 = xzp_bit(w.ptab, probs[kPIsRepG1 + s], 1);
+                const uint32_t b0 = prep + pg0 + xzp_bit(w.ptab, probs[kPIsRep0Long + (s << 4) + ps], 1);
+                const uint32_t b1 = prep + pg0_1 + xzp_bit(w.ptab, probs[kPIsRepG1 + s], 0);
+                const uint32_t b2 = prep + pg0_1 + pg1_1 + xzp_bit(w.ptab, probs[kPIsRepG2 + s], 0);
+                const uint32_t b3 = prep + pg0_1 + pg1_1 + xzp_bit(w.ptab, probs[kPIsRepG2 + s], 1);
+                const uint32_t pnew = pm1 + xzp_bit(w.ptab, probs[kPIsRep + s], 0);
+                const uint16_t* lrep = w.lenp + (4 + ps) * (kLzmaMatchMax - 1);
+                const uint16_t* lnew = w.lenp + ps * (kLzmaMatchMax - 1);
+                ln.each([&](uint32_t lane) {
+                    for (uint32_t L = 2 + lane; L <= longest; L += kXzEncLanes) {
+                        const uint32_t t = cur + L;
+                        uint32_t best = t <= old_end ? w.node[t].price : kXzEncPriceInf;
+                        uint32_t kind = 0xff, dist = 0;
+                        const uint32_t lr = lrep[L - 2], lm = pnew + lnew[L - 2];
+                        if (l0 >= L && b0 + lr < best) { best = b0 + lr; kind = kXzEdgeRep; }
+                        if (l1 >= L && b1 + lr < best) { best = b1 + lr; kind = kXzEdgeRep + 1; }
+                        if (l2 >= L && b2 + lr < best) { best = b2 + lr; kind = kXzEdgeRep + 2; }
+                        if (l3 >= L && b3 + lr < best) { best = b3 + lr; kind = kXzEdgeRep + 3; }
+                        if (m0 >= L) { const uint32_t q = lm + xzp_dist(w, probs, xzenc_cand_dist1(c0), L); if (q < best) { best = q; kind = kXzEdgeMatch; dist = xzenc_cand_dist1(c0); } }
+                        if (m1 >= L) { const uint32_t q = lm + xzp_dist(w, probs, xzenc_cand_dist1(c1), L); if (q < best) { best = q; kind = kXzEdgeMatch; dist = xzenc_cand_dist1(c1); } }
+                        if (m2 >= L) { const uint32_t q = lm + xzp_dist(w, probs, xzenc_cand_dist1(c2), L); if (q < best) { best = q; kind = kXzEdgeMatch; dist = xzenc_cand_dist1(c2); } }
+                        if (m3 >= L) { const uint32_t q = lm + xzp_dist(w, probs, xzenc_cand_dist1(c3), L); if (q < best) { best = q; kind = kXzEdgeMatch; dist = xzenc_cand_dist1(c3); } }
+                        if (kind != 0xff) {
+                            XzEncNode& z = w.node[t];
+                            z.price = best; z.dist = dist; z.len = (uint16_t)L; z.kind = (uint8_t)kind;
+                        }
+                    }
+                });
+            }
+        }
+        // lane 0: the chosen edges forwards, coded; (s, r0..r3) is the state behind them on every lane
+        if (ln.first()) {
+            for (uint32_t t = len_end; t;) {
+                const uint32_t L = w.node[t].len;
+                w.next[t - L] = (uint16_t)L;
+                t -= L;
+            }
+            uint32_t gave = 0;
+            for (uint32_t t = 0; t < len_end;) {
+                if (e.rc.n + e.rc.cache_size >= usize) { // (the flush adds four bytes at least)
+                    gave = 1;
+                    break;
+                }
+                const uint32_t L = w.next[t], q = pos + t;
+                const XzEncNode& z = w.node[t + L];
+                if (z.kind == kXzEdgeLit) {
+                    ops.lit(e.state >= 7);
+                    lzmaenc_literal(e, probs, blk, q, q ? blk[q - 1] : 0);
+                } else if (z.kind == kXzEdgeShortRep) {
+                    ops.short_rep(q);
+                    lzmaenc_short_rep(e, probs, q);
+                } else if (z.kind == kXzEdgeMatch) {
+                    ops.match(q, z.dist + 1, L);
+                    lzmaenc_match(e, probs, q, z.dist, L);
+                } else {
+                    ops.rep(q, z.kind - kXzEdgeRep, L);
+                    lzmaenc_rep(e, probs, q, z.kind - kXzEdgeRep, L);
+                }
+                t += L;
+            }
+            w.flag = gave;
+        }
+        ln.sync();
+        if (w.flag) return kXzEncStored;
+        pos += len_end;
+        st = s; w0 = r0; w1 = r1; w2 = r2; w3 = r3;
+    }
+    if (ln.first()) {
+        const uint32_t csize = xzrc_finish(e.rc);
+        w.res = xzenc_is_lzma(csize, usize) ? csize : kXzEncStored;
+    }
+    ln.sync();
+    return w.res;
+}
+
 // ---- the container (host only) -------------------------------------------------------------------------------------------
 
 // 0 = the default; a multiple of 64 KiB from 64 KiB to kXzEncBlockMax
@@ -561,20 +961,28 @@ struct XzEncInfo {
     std::vector<uint32_t> res; // every chunk's result, in order
 };
 
-// One Block through the three steps, as the kernels leave their arrays: prev and cand (blen words each, Block-relative),
+// One Block through the three steps, as the kernels leave their arrays: prev and cand (blen words each, Block-relative; at
+// level 1 cand holds kXzEncCands words a position and the lanes run in the order lanes_descending says),
 // res and dst (a word a chunk; dst relative to the Block's first byte) and slots (kXzEncSlot bytes a chunk: the coder's
 // output, nothing else written).  head: 1 << kXzEncHashBits entries of scratch; probs: kXzEncProbs.
 template <class OPS>
 inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* cand, uint32_t* head, uint16_t* probs,
                                            uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops, uint32_t check = kXzCheckCrc64,
-                                           uint32_t filter = 0)
+                                           uint32_t filter = 0, uint32_t level = 0, bool lanes_descending = false)
 {
     const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
     xzenc_chains_host(blk, blen, prev, head);
+    std::vector<XzEncWork> work(level ? 1 : 0);
     for (uint32_t k = 0; k < nch; ++k) {
         const uint32_t cs = k * kXzEncChunk, ce = std::min(blen, cs + kXzEncChunk);
-        for (uint32_t p = cs; p < ce; ++p) cand[p] = xzenc_find(blk, prev, p, ce);
         for (uint32_t i = 0; i < kXzEncProbs; ++i) probs[i] = (uint16_t)kLzmaProbInit;
+        if (level) {
+            for (uint32_t p = cs; p < ce; ++p) xzenc_find_set(blk, prev, p, ce, cand + (size_t)p * kXzEncCands);
+            XzEncHostLanes ln{lanes_descending};
+            res[k] = xzenc_chunk_priced(blk, cs, ce, cand, probs, work[0], slots + (size_t)k * kXzEncSlot, kXzEncSlot, ops, ln);
+            continue;
+        }
+        for (uint32_t p = cs; p < ce; ++p) cand[p] = xzenc_find(blk, prev, p, ce);
         res[k] = xzenc_chunk(blk, cs, ce, cand, probs, slots + (size_t)k * kXzEncSlot, kXzEncSlot, ops);
     }
     return xzenc_block_layout(res, nch, blen, dst, check, filter);
@@ -613,9 +1021,9 @@ inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t bl
 // over the copy; the Check is over the unfiltered bytes.
 template <class OPS, class FIELD>
 inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uint32_t check, std::vector<uint8_t>& out, OPS& ops, FIELD field,
-                       XzEncInfo* info = nullptr, uint32_t filter = 0)
+                       XzEncInfo* info = nullptr, uint32_t filter = 0, uint32_t level = 0, bool lanes_descending = false)
 {
-    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check) || !xzenc_filter_valid(filter)) return false;
+    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check) || !xzenc_filter_valid(filter) || level > kXzEncLevelMax) return false;
     const uint32_t dict_byte = xzenc_dict_byte(block_size), check_size = xzenc_check_size(check);
     out.resize(kXzEncStreamHeader);
     xzenc_stream_header(out.data(), check);
@@ -635,12 +1043,12 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uin
         }
         const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
         prev.resize(blen);
-        cand.resize(blen);
+        cand.resize((size_t)blen * (level ? kXzEncCands : 1));
         res.resize(nch);
         dst.resize(nch);
         slots.resize((size_t)nch * kXzEncSlot);
         const XzEncBlockLayout L = xzenc_block_stages(blk, blen, prev.data(), cand.data(), head.data(), probs.data(), res.data(), dst.data(),
-                                                      slots.data(), ops, check, filter);
+                                                      slots.data(), ops, check, filter, level, lanes_descending);
         if (info)
             for (uint32_t k = 0; k < nch; ++k) {
                 info->chunks++;

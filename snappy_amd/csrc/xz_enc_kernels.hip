@@ -13,6 +13,13 @@
 //                        runs) with the probabilities in LDS, reset by all lanes.  Budget: 7 990 probabilities = 15 980
 //                        bytes of LDS and nothing else there, eight workgroups a CU and more; the serial loop keeps its
 //                        coder registers (low, range, cache, four reps, state) in VGPRs: 32 of them, no scratch.
+//   lzma2_chunks_priced_kernel   level 1, the same grid: all lanes leave kXzEncCands candidates per
+//                        position in HBM (kXzEncDepthHigh links), then all lanes run xzenc_chunk_priced: a window's nodes are
+//                        relaxed a lane a target length, lane 0 prices the literal, walks the chosen edges back and codes them.
+//                        Budget: the probabilities (15 980 bytes), the window's 1 025 nodes of 28 bytes (28 700), their
+//                        forward links (2 050) and the price tables (4 992) = 51 730 bytes of LDS with the two flag words:
+//                        three workgroups a CU of 160 KiB.  The chunks of a launch need not all be resident: no workgroup
+//                        waits for another.  One barrier a position, three a window.
 //   lzma2_concat_kernel  a workgroup a chunk: header and body to their place in the Block's data.
 //
 // Bytes that one lane stores and another reads -- the candidates the waves leave for lane 0, the heads one tile leaves
@@ -91,6 +98,41 @@ __global__ __launch_bounds__(kChunkLanes) void lzma2_chunks_kernel(const uint8_t
     }
 }
 
+// the kernel's lanes for xzenc_chunk_priced: a thread a lane, the workgroup's barrier between what one stores and another loads
+struct XzEncGroupLanes {
+    template <class F> __device__ __forceinline__ void each(F&& f) { f(threadIdx.x); }
+    __device__ __forceinline__ bool first() const { return threadIdx.x == 0; }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+static_assert(kChunkLanes == kXzEncLanes, "a thread a lane of the parse");
+
+// Level 1: kXzEncCands candidates a position by all lanes, then xzenc_chunk_priced, the function the host model runs, by
+// all lanes: the relaxation of a node's edges a lane a target length, the coder on lane 0.
+__global__ __launch_bounds__(kChunkLanes) void lzma2_chunks_priced_kernel(const uint8_t* in, uint64_t n, uint32_t bsize, const uint32_t* prev,
+                                                                           uint32_t* cand, uint8_t* slots, uint32_t* res, uint32_t c0, uint32_t count)
+{
+    __shared__ uint16_t probs[kXzEncProbs];
+    __shared__ XzEncWork work;
+    if (blockIdx.x >= count) return;
+    const uint32_t ci = c0 + blockIdx.x;
+    const uint64_t at = (uint64_t)ci * kXzEncChunk;
+    if (at >= n) return;
+    const uint64_t base = at - at % bsize; // the chunk's Block
+    const uint32_t blen = (uint32_t)(n - base < bsize ? n - base : bsize);
+    const uint32_t cs = (uint32_t)(at - base);
+    const uint32_t ce = cs + kXzEncChunk < blen ? cs + kXzEncChunk : blen;
+    const uint8_t* blk = in + base;
+    const uint32_t* pv = prev + base;
+    uint32_t* cd = cand + base * kXzEncCands;
+    for (uint32_t i = threadIdx.x; i < kXzEncProbs; i += kChunkLanes) probs[i] = (uint16_t)kLzmaProbInit;
+    for (uint32_t p = cs + threadIdx.x; p < ce; p += kChunkLanes) xzenc_find_set(blk, pv, p, ce, cd + (uint64_t)p * kXzEncCands);
+    __syncthreads();
+    NoEncOps ops;
+    XzEncGroupLanes ln;
+    const uint32_t r = xzenc_chunk_priced(blk, cs, ce, cd, probs, work, slots + (uint64_t)ci * kXzEncSlot, kXzEncSlot, ops, ln);
+    if (threadIdx.x == 0) res[ci] = r;
+}
+
 __global__ __launch_bounds__(kChunkLanes) void lzma2_concat_kernel(const uint8_t* in, uint64_t n, uint32_t bsize, const uint8_t* slots,
                                                                     const uint32_t* res, const uint64_t* dst, uint8_t* out, uint32_t nch)
 {
@@ -129,12 +171,13 @@ hipError_t launch_lzma_chains(const uint8_t* d_in, uint64_t n, uint32_t bsize, u
 }
 
 hipError_t launch_lzma2_chunks(const uint8_t* d_in, uint64_t n, uint32_t bsize, const uint32_t* d_prev, uint32_t* d_cand, uint8_t* d_slots,
-                               uint32_t* d_res, uint32_t c0, uint32_t count, hipStream_t s)
+                               uint32_t* d_res, uint32_t c0, uint32_t count, hipStream_t s, uint32_t level)
 {
     if (count == 0) return hipSuccess;
-    if (bsize == 0 || bsize % kXzEncChunk || bsize > kXzEncBlockMax || count > kXzEncLaunchChunks) return hipErrorInvalidValue;
+    if (bsize == 0 || bsize % kXzEncChunk || bsize > kXzEncBlockMax || count > kXzEncLaunchChunks || level > kXzEncLevelMax) return hipErrorInvalidValue;
     if (((uint64_t)c0 + count - 1) * kXzEncChunk >= n) return hipErrorInvalidValue; // a chunk behind the piece
-    hipLaunchKernelGGL(lzma2_chunks_kernel, dim3(count), dim3(kChunkLanes), 0, s, d_in, n, bsize, d_prev, d_cand, d_slots, d_res, c0, count);
+    if (level) hipLaunchKernelGGL(lzma2_chunks_priced_kernel, dim3(count), dim3(kChunkLanes), 0, s, d_in, n, bsize, d_prev, d_cand, d_slots, d_res, c0, count);
+    else hipLaunchKernelGGL(lzma2_chunks_kernel, dim3(count), dim3(kChunkLanes), 0, s, d_in, n, bsize, d_prev, d_cand, d_slots, d_res, c0, count);
     return hipGetLastError();
 }
 

@@ -36,8 +36,9 @@ struct XzEncoder final : Encoder {
     const uint32_t filter;         // a BCJ filter in front of LZMA2 (DESIGN.md sec. 25), 0 = none, the producer's path without it
     uint64_t filt_blocks = 0;      // Blocks the BCJ kernels filtered
     double filt_ms = 0;            // the BCJ kernels' own time, HIP events
-    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr, uint32_t flt = 0)
-        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc), filter(flt)
+    const uint32_t level;          // 0: the greedy parse; 1: candidates, prices and a shortest-path parse (DESIGN.md sec. 27)
+    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr, uint32_t flt = 0, uint32_t lvl = 0)
+        : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc), filter(flt), level(lvl)
     {
         if (sc) check_ms = &sc->ms;
     }
@@ -51,6 +52,7 @@ struct XzEncoder final : Encoder {
         const int rc = ensure_producer_streams(c);
         if (rc) return rc;
         HIP_TRY(c, c->xe.ensure(slot_bytes, c->numa_node)); // (a failure leaves none of it)
+        if (level) HIP_TRY(c, c->xe.ensure_level(slot_bytes));
         if (self_check) HIP_TRY(c, c->xe.ensure_check(slot_bytes));
         if (filter) HIP_TRY(c, c->xe.ensure_filter(slot_bytes));
         if (filter && self_check) HIP_TRY(c, c->xe.ensure_filter_check(slot_bytes));
@@ -169,6 +171,8 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
     if (n > sl.cap() || b.d_prev.size() < n || b.res.size() < nch || b.cap() < XzEncBufs::out_cap(n))
         return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
+    if (z.level && b.d_cand_set.size() < n * kXzEncCands) return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
+    uint32_t* const d_cand = z.level ? b.d_cand_set.data() : b.d_cand.data();
     if (ready) HIP_TRY(c, hipStreamWaitEvent(zs, ready, 0));
     // with a BCJ filter: the slot's bytes once more, filtered in place, a range a Block (positions from the Block's first byte);
     // the LZMA2 kernels read the copy, the Checks below the staged bytes
@@ -192,11 +196,12 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     // a launch codes what is resident at once, no more: a longer slot goes in several launches (each with its own pair of
     // events: the longest single launch is what DESIGN.md sec. 18 holds against sec. 17's one-second bound)
     std::vector<Span> evl;
-    for (uint32_t c0 = 0; c0 < nch; c0 += kXzEncLaunchChunks) {
+    const uint32_t width = z.level ? kXzEncLaunchChunksPriced : kXzEncLaunchChunks;
+    for (uint32_t c0 = 0; c0 < nch; c0 += width) {
         evl.emplace_back();
         if ((rc = span_begin(c, Ev::Codec, zs, &evl.back()))) return rc;
-        HIP_TRY(c, launch_lzma2_chunks(src, n, (uint32_t)bs, b.d_prev.data(), b.d_cand.data(), b.d_slots.data(), b.res.d.data(), c0,
-                                       std::min(kXzEncLaunchChunks, nch - c0), zs));
+        HIP_TRY(c, launch_lzma2_chunks(src, n, (uint32_t)bs, b.d_prev.data(), d_cand, b.d_slots.data(), b.res.d.data(), c0,
+                                       std::min(width, nch - c0), zs, z.level));
         if ((rc = span_end(c, evl.back(), zs))) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(b.res.h.data(), b.res.d.data(), (size_t)nch * 4, hipMemcpyDeviceToHost, zs));
@@ -284,9 +289,9 @@ int XzEncoder::slot(OutPipe& g, Slot& sl, uint64_t n, hipEvent_t ready, int zbuf
 }
 
 // The producer's kernel sequence once more, for snaphash_xzenc_stages_device: xz_process_slot's steps in its order on a
-// caller's buffers, without its events and its trace line.  (A copy, not a shared routine: with the sequence shared, the
+// caller's buffers (at level 1 d_cand holds kXzEncCands words a byte), without its events and its trace line.  (A copy, not a shared routine: with the sequence shared, the
 // producer's call measured above the spread of its parent's on one of three corpora -- DESIGN.md sec. 18 -- so its loop
-// stays as it was.)  h_res / h_dst: a word a chunk of host memory.  launch_chunks: 0 for kXzEncLaunchChunks.  The concat
+// stays as it was.)  h_res / h_dst: a word a chunk of host memory.  launch_chunks: 0 for the producer's width at the level.  The concat
 // kernel is queued on zs, not waited for.
 struct XzEncStageBufs {
     uint32_t *d_prev, *d_cand;
@@ -297,14 +302,14 @@ struct XzEncStageBufs {
     uint64_t out_cap;
 };
 int xz_encode_stages(DevCtx* c, const uint8_t* d_in, uint64_t n, uint64_t bs, uint32_t launch_chunks, const XzEncStageBufs& b, hipStream_t zs,
-                     std::vector<XzEncBlockLayout>& lay)
+                     std::vector<XzEncBlockLayout>& lay, uint32_t level)
 {
-    if (launch_chunks == 0) launch_chunks = kXzEncLaunchChunks;
+    if (launch_chunks == 0) launch_chunks = level ? kXzEncLaunchChunksPriced : kXzEncLaunchChunks;
     const uint32_t nch = (uint32_t)((n + kXzEncChunk - 1) / kXzEncChunk), cpb = (uint32_t)(bs / kXzEncChunk);
     const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
     HIP_TRY(c, launch_lzma_chains(d_in, n, (uint32_t)bs, b.d_prev, zs));
     for (uint32_t c0 = 0; c0 < nch; c0 += launch_chunks)
-        HIP_TRY(c, launch_lzma2_chunks(d_in, n, (uint32_t)bs, b.d_prev, b.d_cand, b.d_slots, b.d_res, c0, std::min(launch_chunks, nch - c0), zs));
+        HIP_TRY(c, launch_lzma2_chunks(d_in, n, (uint32_t)bs, b.d_prev, b.d_cand, b.d_slots, b.d_res, c0, std::min(launch_chunks, nch - c0), zs, level));
     HIP_TRY(c, hipMemcpyAsync(b.h_res, b.d_res, (size_t)nch * 4, hipMemcpyDeviceToHost, zs));
     HIP_TRY(c, hipStreamSynchronize(zs));
     lay.resize(nblk);
@@ -340,20 +345,31 @@ try {
     return SNAPHASH_ENOMEM;
 }
 
+constexpr uint32_t kXzOptionsSizeV1 = 24; // snaphash_xz_options before level and reserved2
+
 // What the _ex entries were asked for.  opt == nullptr, or an all-zero struct: what the plain entries write (1 MiB, CRC-64, no
 // self-check); otherwise the struct says its size and every field means what it says (check 0 is "none").
-int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check, uint32_t* filter)
+int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check, uint32_t* filter,
+                    uint32_t* level)
 {
+    static_assert(sizeof(snaphash_xz_options) == 32 && offsetof(snaphash_xz_options, level) == kXzOptionsSizeV1, "level and reserved2 behind the 24 bytes");
     *block_size = kXzEncBlockDefault;
     *check = kXzCheckCrc64;
     *self_check = false;
     *filter = 0;
-    if (opt && opt->struct_size == 0) {
+    *level = 0;
+    if (opt && opt->struct_size == 0) { // (the plain entry: only the 24 bytes every caller has are looked at)
         if (opt->flags || opt->block_size || opt->check || opt->filter) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
         return SNAPHASH_OK;
     }
     if (!opt) return SNAPHASH_OK;
-    if (opt->struct_size < sizeof(snaphash_xz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+    // 24: the struct before it had a level (level 0); 32 and more: with level and reserved2
+    if (opt->struct_size != kXzOptionsSizeV1 && opt->struct_size < sizeof(snaphash_xz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+    if (opt->struct_size >= sizeof(snaphash_xz_options)) {
+        if (opt->level > kXzEncLevelMax) return fail(x, SNAPHASH_EINVAL, "xz: the level is 0 (greedy parse) or 1 (priced parse)");
+        if (opt->reserved2) return fail(x, SNAPHASH_EINVAL, "xz: snaphash_xz_options.reserved2 is not 0");
+        *level = opt->level;
+    }
     if (opt->flags & ~(uint32_t)SNAPHASH_XZ_SELF_CHECK) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
     if (!xzenc_filter_valid(opt->filter)) return fail(x, SNAPHASH_EINVAL, "xz: the filter is 0 (none), 4 (x86), 7 (ARM) or 8 (ARM-Thumb)");
     if (!xzenc_check_valid(opt->check)) return fail(x, SNAPHASH_EINVAL, "xz: the Check is 0 (none), 1 (CRC-32), 4 (CRC-64) or 10 (SHA-256)");
@@ -396,12 +412,12 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    uint32_t filter;
-    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter);
+    uint32_t filter, level;
+    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter, &level);
     if (rc) return rc;
     XzSelfCheck sc;
     sc.member = "the buffer";
-    XzEncoder enc(bs, check, self ? &sc : nullptr, filter);
+    XzEncoder enc(bs, check, self ? &sc : nullptr, filter, level);
     rc = encode_to_malloc(x, enc, data, n, xz_out, xz_len);
     xz_keep_selfcheck_stats(x, sc);
     xz_keep_filter_stats(x, enc);
@@ -417,13 +433,13 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    uint32_t filter;
-    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter);
+    uint32_t filter, level;
+    int rc = xz_read_options(x, opt, &bs, &check, &self, &filter, &level);
     if (rc) return rc;
     XzSelfCheck sc;
     const char* base = strrchr(tarname, '/');
     sc.member = base ? base + 1 : tarname;
-    XzEncoder enc(bs, check, self ? &sc : nullptr, filter);
+    XzEncoder enc(bs, check, self ? &sc : nullptr, filter, level);
     rc = tar_create_impl(x, enc, tarname, source_dir, exclude_prefix, nullptr, nullptr, yaml_out, yaml_len, archive_digest);
     xz_keep_selfcheck_stats(x, sc);
     xz_keep_filter_stats(x, enc);
@@ -488,7 +504,15 @@ int snaphash_xz_buffer_check(snaphash_ctx* x, const void* data, size_t n, uint64
 
 int snaphash_xzenc_stages_device(snaphash_ctx* x, const void* d_in, size_t n, uint64_t block_size, uint32_t launch_chunks, void* d_prev,
                                  void* d_cand, void* d_slots, void* d_res, void* d_dst, void* d_out, size_t out_cap, uint64_t* block_total)
+{
+    return snaphash_xzenc_stages_device_ex(x, d_in, n, block_size, launch_chunks, d_prev, d_cand, d_slots, d_res, d_dst, d_out, out_cap, block_total, 0);
+}
+
+int snaphash_xzenc_stages_device_ex(snaphash_ctx* x, const void* d_in, size_t n, uint64_t block_size, uint32_t launch_chunks, void* d_prev,
+                                    void* d_cand, void* d_slots, void* d_res, void* d_dst, void* d_out, size_t out_cap, uint64_t* block_total,
+                                    uint32_t level)
 try {
+    if (level > kXzEncLevelMax) return fail(x, SNAPHASH_EINVAL, "xz: the level is 0 (greedy parse) or 1 (priced parse)");
     if (!x || (n && (!d_in || !d_prev || !d_cand || !d_slots || !d_res || !d_dst || !d_out))) return fail(x, SNAPHASH_EINVAL, "bad argument");
     if (!xzenc_block_size(&block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
     if (launch_chunks > kXzEncLaunchChunks) return fail(x, SNAPHASH_EINVAL, "xz: a launch holds at most 2048 chunks");
@@ -504,7 +528,7 @@ try {
     const XzEncStageBufs sb = {(uint32_t*)d_prev, (uint32_t*)d_cand, (uint8_t*)d_slots, (uint32_t*)d_res, h_res.data(),
                                (uint64_t*)d_dst, h_dst.data(), (uint8_t*)d_out, out_cap};
     std::vector<XzEncBlockLayout> lay;
-    const int rc = xz_encode_stages(c, (const uint8_t*)d_in, n, block_size, launch_chunks, sb, c->stream, lay);
+    const int rc = xz_encode_stages(c, (const uint8_t*)d_in, n, block_size, launch_chunks, sb, c->stream, lay, level);
     const hipError_t e = hipStreamSynchronize(c->stream); // (h_dst is read by a copy still in flight)
     if (rc) return lift(x, c, rc);
     HIP_TRY(c, e);

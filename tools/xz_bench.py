@@ -31,7 +31,14 @@ GPU) on tools/deflate_corpora.py's text, sources and binaries, 64 MiB each (--qu
             the filter kernels' own time (snaphash_get_xz_filter_stats) beside the chains and chunks kernels of the same
             call (a `snaphash xz -F` child under SNAPHASH_TRACE_XZ=1); and the install side reading the file back.  Then the
             dense launch: snaphash_bcj_device over 1 MiB of E8, one lane's walk, beside sec. 17's one-second bound.
-usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--filter NAME] [--out FILE]
+  --level N   instead of the legs above: what level N (1: several candidates a position and a priced parse)
+            buys and costs beside level 0.  On each corpus (--quick: 8 MiB) in 1 MiB Blocks: the bytes at both levels beside
+            liblzma on the same Blocks -- MODE_FAST / MF_HC4 / depth 8 / nice 273 (the shape of level 0), MODE_NORMAL / MF_HC4 at the
+            level's depth / nice 273 (the shape of level 1) and preset 6 (`xz -6 --block-size=1MiB` where the program is installed,
+            Python's lzma otherwise): the gain level 0 -> 1 is read against liblzma's own FAST -> NORMAL; the call at both levels,
+            alternating, five of each after a warm one; and the chunks kernel's own time and longest launch at both levels
+            (a `snaphash xz -L` child under SNAPHASH_TRACE_XZ=1).
+usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--filter NAME] [--level N] [--out FILE]
        tools/xz_bench.py --no-flag-ab LABEL [--tree DIR] [--corpora-root DIR] [--out FILE]   (JSON lines on stdout and in FILE; --out appends here)"""
 import argparse
 import lzma
@@ -247,6 +254,53 @@ def filter_legs(g, d, name_of_filter, fh, tmp, reps=5):
     emit({"leg": "filter_dense_launch", "filter": name_of_filter, "bytes": n, "kernel_ms_best_median_worst": three(ms), "bound_ms": 1000.0}, fh)
 
 
+LEVEL_DEPTH = {1: 32}  # kXzEncDepthHigh
+
+
+def level_legs(g, level, size, fh, tmp, reps=5):
+    def liblzma_blocks(data, **kw):
+        f = dict(id=lzma.FILTER_LZMA2, dict_size=BLOCK, lc=3, lp=0, pb=2, **kw)
+        with ThreadPoolExecutor(16) as ex:
+            return sum(ex.map(lambda i: len(lzma.compress(data[i:i + BLOCK], format=lzma.FORMAT_RAW, filters=[f])), range(0, len(data), BLOCK)))
+
+    def traced(data, lvl):
+        src, dst = os.path.join(tmp, "in"), os.path.join(tmp, "out.xz")
+        with open(src, "wb") as f:
+            f.write(data)
+        p = subprocess.run([CLI, "-g", "xz", src, dst, "-L", str(lvl)], env=dict(os.environ, SNAPHASH_TRACE_XZ="1"), stderr=subprocess.PIPE, text=True, check=True)
+        rows = [tuple(float(x) for x in m) for m in TRACE.findall(p.stderr)]
+        assert rows
+        return open(dst, "rb").read(), round(sum(r[1] for r in rows), 3), round(max(r[3] for r in rows), 3), round(sum(r[0] for r in rows), 3)
+
+    for name, data in corpora(size).items():
+        g.xz_buffer(data)  # one warm call each: the scratch
+        g.xz_buffer(data, level=level)
+        t0s, t1s = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            z0 = g.xz_buffer(data)
+            t0s.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            z1 = g.xz_buffer(data, level=level)
+            t1s.append((time.perf_counter() - t0) * 1e3)
+        assert lzma.decompress(z0) == data and lzma.decompress(z1) == data
+        f0, chunks0, longest0, chains0 = traced(data, 0)
+        f1, chunks1, longest1, chains1 = traced(data, level)
+        assert f0 == z0 and f1 == z1
+        fast = liblzma_blocks(data, mode=lzma.MODE_FAST, mf=lzma.MF_HC4, depth=8, nice_len=273)
+        normal = liblzma_blocks(data, mode=lzma.MODE_NORMAL, mf=lzma.MF_HC4, depth=LEVEL_DEPTH[level], nice_len=273)
+        blk = xz_tool(data, "-6", "--block-size=1MiB")
+        six = blk[0] if blk else liblzma_blocks(data, preset=6)
+        emit({"leg": "level", "level": level, "corpus": name, "bytes": len(data), "snaphash_xz_level0": len(z0), "snaphash_xz_level": len(z1),
+              "gain_pct": round(100.0 * (len(z1) - len(z0)) / len(z0), 2), "liblzma_fast_hc4_8_273": fast,
+              "liblzma_normal_hc4_%d_273" % LEVEL_DEPTH[level]: normal, "liblzma_gain_pct": round(100.0 * (normal - fast) / fast, 2),
+              "preset6_1mib_blocks": six, "preset6_from": "xz" if blk else "python lzma, raw LZMA2 a Block",
+              "over_preset6_pct_level0": round(100.0 * (len(z0) - six) / six, 2), "over_preset6_pct_level": round(100.0 * (len(z1) - six) / six, 2),
+              "reps": reps, "level0_ms_best_median_worst": three(t0s), "level_ms_best_median_worst": three(t1s),
+              "chains_ms": chains1, "chunks_ms_level0": chunks0, "chunks_ms_level": chunks1, "longest_launch_ms_level0": longest0,
+              "longest_launch_ms_level": longest1, "bound_ms": 1000.0}, fh)
+
+
 def corpora_of(root, size):
     """unpack_bench.corpora with the corpus builders of the checkout at `root`, over that checkout's files."""
     origin = os.path.join(os.path.abspath(root), "tools", "deflate_corpora.py")
@@ -278,6 +332,7 @@ def main():
     ap.add_argument("--self-check", action="store_true")
     ap.add_argument("--no-flag-ab", metavar="LABEL")
     ap.add_argument("--filter", metavar="NAME", choices=("x86", "arm", "armthumb"))
+    ap.add_argument("--level", type=int, choices=(1,))
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--corpora-root", default=ROOT)
     a = ap.parse_args()
@@ -293,6 +348,10 @@ def main():
         if a.filter:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, Context(device=0, flags=0) as d:
                 filter_legs(g, d, a.filter, fh, tmp)
+            return
+        if a.level:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
+                level_legs(g, a.level, size, fh, tmp)
             return
         if a.self_check:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
