@@ -411,7 +411,7 @@ int snaphash_xz_buffer_ex(snaphash_ctx *ctx, const void *data, size_t n, const s
                           size_t *xz_len);
 int snaphash_tar_create_xz_ex(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
                               const snaphash_xz_options *opt, char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
-/* of the most recent of the two _ex calls above */
+/* of the most recent call among the two _ex calls above and snaphash_snap_build with a data.tar.xz (the data member's) */
 int snaphash_get_xz_selfcheck_stats(const snaphash_ctx *ctx, snaphash_xz_selfcheck_stats *out);
 /* snaphash_xz_options.filter.  A snap's data member is mostly machine code; a BCJ (branch-call-jump)
  * filter rewrites the relative targets of calls and jumps as absolute ones, so that calls of one function become equal
@@ -572,7 +572,7 @@ int snaphash_bzip2_buffer_ex(snaphash_ctx *ctx, const void *data, size_t n, cons
                              size_t *bz_len);
 int snaphash_tar_create_bz2_ex(snaphash_ctx *ctx, const char *tarname, const char *source_dir, const char *exclude_prefix,
                                const snaphash_bz2_options *opt, char **yaml_out, size_t *yaml_len, uint8_t *archive_digest);
-/* of the most recent of the two _ex calls above */
+/* of the most recent call among the two _ex calls above and snaphash_snap_build with a data.tar.bz2 (the data member's) */
 int snaphash_get_bz2_selfcheck_stats(const snaphash_ctx *ctx, snaphash_bz2_selfcheck_stats *out);
 
 typedef struct snaphash_bz2_verdict {
@@ -736,7 +736,8 @@ int snaphash_tar_unpack_xz_ex(snaphash_ctx *ctx, const char *data_tar_xz, const 
 int snaphash_bcj_device(snaphash_ctx *ctx, uint32_t filter, int encode, void *d_base, const uint64_t *offsets,
                         const uint64_t *lens, size_t n, uint32_t start_offset);
 /* What the BCJ filters did in the most recent call of this ctx among snaphash_xz_buffer_ex, snaphash_tar_create_xz_ex,
- * snaphash_unxz_buffer(_ex) and snaphash_tar_unpack_xz(_ex). */
+ * snaphash_snap_build with a data.tar.xz, snaphash_unxz_buffer(_ex), snaphash_tar_unpack_xz(_ex) and a .snap session's decode
+ * of an .xz member. */
 typedef struct snaphash_xz_filter_stats {
     uint32_t struct_size;   /* set by the caller */
     uint32_t filter;        /* the producer's filter; on the install side the filter of the last filtered Block; 0: none */
@@ -762,7 +763,8 @@ int snaphash_crc64_device(snaphash_ctx *ctx, const void *d_base, const uint64_t 
 int snaphash_sha256_device(snaphash_ctx *ctx, const void *d_base, const uint64_t *offsets, const uint64_t *lens, size_t n,
                            uint8_t *digests);
 
-/* Who took the Blocks' Checks in the most recent .xz decode (buffer or tar unpack) of this ctx. */
+/* Who took the Blocks' Checks in the most recent .xz decode (buffer, tar unpack, or an .xz member of a .snap session, whose
+ * snaphash_snap_stats add them up over the session) of this ctx. */
 typedef struct snaphash_xz_check_stats {
     uint32_t struct_size;
     uint32_t reserved;
@@ -788,15 +790,29 @@ int snaphash_crc32_device(snaphash_ctx *ctx, int kind, const void *d_base, const
  * supported.  SNAPHASH_EFORMAT: a wrong magic or fmag, a size field that is not digits then spaces, a header or a member
  * the end of the file cuts off.
  * Member lookup is skipToArMember's (deb.go:408-441): the FIRST member whose name starts with "control.tar" /
- * "data.tar"; ".gz" takes the gzip engine, ".bz2" the bzip2 engine, ".xz" (which the session does not route to
- * snaphash_tar_unpack_xz's engine yet) and anything else SNAPHASH_EINVAL with the
- * reference's text "Can not handle NAME" (as snaphash_tar_create answers a name that is not ".gz"); no such member is
- * SNAPHASH_EFORMAT with the prefix in the message.
+ * "data.tar" -- a later member of the prefix is never looked at, whatever its suffix; ".gz" takes the gzip engine, ".bz2"
+ * the bzip2 engine, and ".xz" snaphash_tar_unpack_xz's engine in a session opened by snaphash_snap_open_ex with
+ * SNAPHASH_SNAP_XZ.  In a session opened by snaphash_snap_open ".xz" is, like any other suffix, SNAPHASH_EINVAL with the
+ * reference's text "Can not handle NAME" (as snaphash_tar_create answers a name that is not ".gz"): callers and tests rely
+ * on that refusal, so the .xz route is asked for.  No member of the prefix is SNAPHASH_EFORMAT with the prefix in the message.
+ * An ".xz" member (control.tar.xz as well as data.tar.xz) may be any number of Streams with Stream Padding, Checks none,
+ * CRC-32, CRC-64 or SHA-256, every Block LZMA2 alone or one x86, ARM or ARM-Thumb filter in front of LZMA2 -- what
+ * SNAPHASH_UNXZ_BCJ takes, what the xz tool the reference pipes the member through reads, and what snaphash_snap_build can
+ * write.  Every other chain is SNAPHASH_EINVAL "xz: unsupported filter 0xNN", every other Check id SNAPHASH_EINVAL; like
+ * any failed decode it is remembered for that tar, and the other tar stays readable.
  * open reads the file once and decodes nothing.  Each of the two tars is decoded at most once per session, by the
  * first call that needs it; the decoded stream and its member list stay in the session (the reference decodes
  * data.tar.gz once per MetaMember call and once more in Unpack). */
 typedef struct snaphash_snap snaphash_snap;
 int  snaphash_snap_open(snaphash_ctx *ctx, const char *snap_path, snaphash_snap **out);   /* ClickDeb.Open */
+enum { SNAPHASH_SNAP_XZ = 1 }; /* snaphash_snap_open_options.flags: route ".xz" members to the .xz engine (see above) */
+typedef struct snaphash_snap_open_options {
+    uint32_t struct_size; /* sizeof(snaphash_snap_open_options) */
+    uint32_t flags;       /* SNAPHASH_SNAP_*; an unknown bit is SNAPHASH_EINVAL */
+} snaphash_snap_open_options;
+/* opt == NULL, or a struct that is all zero: snaphash_snap_open.  Otherwise a struct_size below the struct's is
+ * SNAPHASH_EINVAL. */
+int  snaphash_snap_open_ex(snaphash_ctx *ctx, const char *snap_path, const snaphash_snap_open_options *opt, snaphash_snap **out);
 void snaphash_snap_close(snaphash_snap *s);
 size_t snaphash_snap_members(const snaphash_snap *s);
 /* name: owned by the session; offset: of the member's data in the file */
@@ -812,8 +828,10 @@ int  snaphash_snap_meta_member(snaphash_snap *s, const char *name, void **conten
 int  snaphash_snap_unpack(snaphash_snap *s, const char *target_dir, int verify, snaphash_mismatch *first, uint8_t *archive_digest);
 /* Nothing is written: every check the package carries, made on the decoded bytes.  These semantics are this library's
  * (the reference checks nothing of the kind at install time), the first failure in this order:
- *   1. decoding: every gzip member's CRC-32 and ISIZE, every bzip2 block CRC and combined CRC, the tar framing:
- *      SNAPHASH_EFORMAT (SNAPHASH_ECONTENT for what unpack would refuse);
+ *   1. decoding: every gzip member's CRC-32 and ISIZE, every bzip2 block CRC and combined CRC; of an .xz member every
+ *      Stream header, every Block header, the CRC-32 of every Index and footer, the Index against its Blocks and every
+ *      Block's Check (as snaphash_unxz_buffer); the tar framing: SNAPHASH_EFORMAT (SNAPHASH_ECONTENT for what unpack
+ *      would refuse);
  *   2. archive-sha512 against the data.tar.* member's bytes: SNAPHASH_EMISMATCH kind 6;
  *   3. the records of hashes.yaml in yaml order, each against the LAST tar member of its name (names after filepath.Clean,
  *      which drops a leading "./"; an EARLIER member of the name is not looked at, though an unpack would keep the mode
@@ -822,7 +840,8 @@ int  snaphash_snap_unpack(snaphash_snap *s, const char *target_dir, int verify, 
  *   4. the tar members in tar order: one without a record is kind 2 (the root entry "." is not one).
  * A package without hashes.yaml: kind 1, name "hashes.yaml".  Under SNAPHASH_FLAG_GPU_ONLY the CRCs of (1) are taken by the
  * CRC kernels out of the decoded stream in HBM (a range per gzip member / per bzip2 block; the bzip2 combined CRC is
- * folded from them on the host) and the digests by the SHA-512 kernels out of the same buffer; in the default
+ * folded from them on the host; a range per .xz Block that lzma2_blocks_kernel decoded, by the CRC-32, CRC-64 or SHA-256
+ * kernel its Check names) and the digests by the SHA-512 kernels out of the same buffer; in the default
  * configuration the CRCs stay on host threads.  The verdict is the same in both. */
 int  snaphash_snap_audit(snaphash_snap *s, snaphash_mismatch *first, uint8_t *archive_digest);
 
@@ -831,9 +850,9 @@ typedef struct snaphash_snap_stats { /* of the session so far */
     uint32_t reserved;
     uint64_t data_decodes;      /* times data.tar.* was decoded (at most 1) */
     uint64_t control_decodes;   /* times control.tar.* was decoded (at most 1) */
-    uint64_t device_crc_ranges; /* CRCs the CRC kernels took (gzip members, bzip2 blocks) */
-    uint64_t host_crc_ranges;   /* CRCs host threads took */
-    double device_crc_ms;       /* the CRC kernels, HIP events */
+    uint64_t device_crc_ranges; /* CRCs the CRC kernels took (gzip members, bzip2 blocks, .xz Blocks' Checks of any kind) */
+    uint64_t host_crc_ranges;   /* CRCs host threads took (an .xz Block without a Check is counted nowhere) */
+    double device_crc_ms;       /* the CRC (for .xz: Check) kernels, HIP events */
 } snaphash_snap_stats;
 int snaphash_snap_get_stats(const snaphash_snap *s, snaphash_snap_stats *out);
 
@@ -842,7 +861,10 @@ int snaphash_snap_get_stats(const snaphash_snap *s, snaphash_snap_stats *out);
 enum { /* snaphash_snap_build_options.flags */
     SNAPHASH_BUILD_NO_HASHES = 1, /* the reference's nil dataTarFinishedCallback: DEBIAN/hashes.yaml is neither computed nor
                                      written (the data member is still hashed for archive_digest) */
-    SNAPHASH_BUILD_CHECK = 2      /* the self-check: every 64 KiB chunk of both tars' DEFLATE streams is decoded again in HBM
+    SNAPHASH_BUILD_CHECK = 2      /* "check what you wrote".  With data_codec xz or bz2 the data member is checked by its own
+                                     producer's self-check instead (SNAPHASH_XZ_SELF_CHECK / SNAPHASH_BZ2_SELF_CHECK, which
+                                     inside the passed options have the same effect for the data member), control.tar.gz
+                                     as follows.  The DEFLATE self-check: every 64 KiB chunk of both tars' DEFLATE streams is decoded again in HBM
                                      by deflate_check_kernel and compared with the staged bytes it was made from, before the
                                      bytes travel to the host; a chunk that does not is SNAPHASH_EDEVICE, last_error naming
                                      the member, the chunk and the offset in the tar stream.  It covers the DEFLATE blocks
@@ -851,23 +873,33 @@ enum { /* snaphash_snap_build_options.flags */
                                      written are the same with and without it. */
 };
 
+enum { SNAPHASH_DATA_GZ = 0, SNAPHASH_DATA_BZ2 = 1, SNAPHASH_DATA_XZ = 2 }; /* snaphash_snap_build_options.data_codec */
+
 typedef struct snaphash_snap_build_options {
-    uint32_t struct_size; /* sizeof(snaphash_snap_build_options) */
+    uint32_t struct_size; /* sizeof(snaphash_snap_build_options); 16 -- the struct before it named a codec -- means gzip */
     uint32_t flags;       /* SNAPHASH_BUILD_* */
     int64_t mtime;        /* of the four ar members, seconds since the epoch; negative = now */
+    /* ---- read when struct_size covers them (a struct_size between 16 and the whole struct is SNAPHASH_EINVAL) ---- */
+    uint32_t data_codec;  /* SNAPHASH_DATA_*: the member is data.tar.gz, data.tar.bz2 or data.tar.xz; anything else is
+                             SNAPHASH_EINVAL.  control.tar.gz stays gzip, as in the reference. */
+    uint32_t reserved;    /* must be 0 */
+    const snaphash_xz_options *xz;   /* the .xz producer's options as snaphash_tar_create_xz_ex reads them (its refusals and
+                                        their texts included); NULL: its defaults.  Not NULL with another codec: SNAPHASH_EINVAL */
+    const snaphash_bz2_options *bz2; /* the same for the .bz2 producer and snaphash_tar_create_bz2_ex */
 } snaphash_snap_build_options;
 
 typedef struct snaphash_snap_build_stats {
     uint32_t struct_size;   /* in: sizeof(snaphash_snap_build_stats) */
     uint32_t reserved;
     uint64_t snap_bytes;    /* the file written */
-    uint64_t data_bytes;    /* its data.tar.gz member */
+    uint64_t data_bytes;    /* its data.tar.* member */
     uint64_t control_bytes; /* its control.tar.gz member */
     uint64_t tar_bytes;     /* the data member's uncompressed tar stream */
     uint64_t members;       /* tar members of the data member */
-    uint64_t check_chunks;  /* SNAPHASH_BUILD_CHECK: chunks the check kernel walked (both tars), all accepted */
-    double check_ms;        /* ... and the kernel's own time, HIP events */
-    double data_ms;         /* the fused pass over source_dir (tar, DEFLATE, hashes.yaml, archive digest) */
+    uint64_t check_chunks;  /* the self-checks: DEFLATE chunks the check kernel walked (control.tar.gz, and a data.tar.gz), plus
+                               the LZMA2 chunks of a data.tar.xz or the bzip2 blocks of a data.tar.bz2, all accepted */
+    double check_ms;        /* ... and the checks' kernels' own time, HIP events, summed */
+    double data_ms;         /* the fused pass over source_dir (tar, the codec, hashes.yaml, archive digest) */
     double control_ms;      /* the pass over source_dir/DEBIAN */
     double ar_ms;           /* writing the container and hashing it */
     double wall_ms;
@@ -891,7 +923,14 @@ typedef struct snaphash_snap_build_stats {
  * temporary file beside the target (<snap_path>.data.tar.gz; control likewise), and copied into the container once the control member
  * is known; both temporaries are removed on every way out.  snap_digest (may be NULL): the SHA-512 of the file written, the
  * store's download_sha512, taken while the container is written.  archive_digest (may be NULL): of the data member.
- * opt may be NULL (no flags, mtime now); stats may be NULL.  On failure snap_path is unlinked. */
+ * opt may be NULL (no flags, mtime now); stats may be NULL.  On failure snap_path is unlinked.
+ * With opt->data_codec the data member is written by the .xz or the .bz2 producer instead: data.tar.xz / data.tar.bz2, byte
+ * for byte what snaphash_tar_create_xz_ex / snaphash_tar_create_bz2_ex write for the same tree with exclude_prefix
+ * <source_dir>/DEBIAN and the same options on the same ctx, from the same single pass that yields hashes.yaml and
+ * archive_digest; the temporary is <snap_path>.data.tar.xz / .bz2 and the ar member has that name (snaphash_snap_open_ex with
+ * SNAPHASH_SNAP_XZ reads a data.tar.xz back).  A chunk or block the member's self-check refuses fails the build with the
+ * producer's error.  snaphash_get_xz_selfcheck_stats, snaphash_get_xz_filter_stats and snaphash_get_bz2_selfcheck_stats then
+ * describe the data member.  With opt == NULL or a struct_size of 16 the file is what it always was. */
 int snaphash_snap_build(snaphash_ctx *ctx, const char *source_dir, const char *snap_path, const snaphash_snap_build_options *opt,
                         uint8_t *archive_digest, uint8_t *snap_digest, snaphash_snap_build_stats *stats);
 

@@ -67,8 +67,13 @@ EXPORTS = [
     "snaphash_unxz_buffer_ex", "snaphash_tar_unpack_xz_ex", "snaphash_bcj_device", "snaphash_get_xz_filter_stats",
     # the .bz2 producer with options and its self-check, and that check's kernels alone
     "snaphash_bzip2_buffer_ex", "snaphash_tar_create_bz2_ex", "snaphash_get_bz2_selfcheck_stats", "snaphash_bz2_check_device",
+    # the .snap session with ".xz" members routed to the .xz engine
+    "snaphash_snap_open_ex",
 ]
 BUILD_NO_HASHES, BUILD_CHECK = 1, 2
+SNAP_XZ = 1
+DATA_CODECS = {"gz": 0, "bz2": 1, "xz": 2}  # snaphash_snap_build_options.data_codec
+XZ_CHECK_NAMES = {"none": 0, "crc32": 1, "crc64": 4, "sha256": 10}
 XZ_SELF_CHECK = 1
 UNXZ_BCJ = 1
 BCJ_X86, BCJ_ARM, BCJ_ARMTHUMB = 4, 7, 8  # the .xz format's filter ids
@@ -198,8 +203,14 @@ class SnapStats(ctypes.Structure):
                 ("device_crc_ms", ctypes.c_double)]
 
 
+class SnapOpenOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class SnapBuildOptions(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("mtime", ctypes.c_int64)]
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("mtime", ctypes.c_int64),
+                ("data_codec", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("xz", ctypes.POINTER(XzOptions)),
+                ("bz2", ctypes.POINTER(Bz2Options))]
 
 
 class SnapBuildStats(ctypes.Structure):
@@ -322,6 +333,7 @@ def lib():
     L.snaphash_xzenc_stages_device.argtypes = [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, sz, u64p]
     L.snaphash_sha512_jobs_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(Sha512Job), sz, sz, vp, vp]
     L.snaphash_snap_open.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.snaphash_snap_open_ex.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(SnapOpenOptions), ctypes.POINTER(vp)]
     L.snaphash_snap_close.argtypes = [vp]
     L.snaphash_snap_close.restype = None
     L.snaphash_snap_members.argtypes = [vp]
@@ -593,8 +605,8 @@ class Context:
         return [(v[2 * k], v[2 * k + 1]) for k in range(nb)]
 
     def bz2_selfcheck_stats(self):
-        """The self-check of the last bzip2_buffer / tar_create_bz2 that went through an _ex entry: blocks decoded again,
-        the check's kernels' milliseconds."""
+        """The self-check of the last bzip2_buffer / tar_create_bz2 that went through an _ex entry, or of the data.tar.bz2 of
+        the last snap_build: blocks decoded again, the check's kernels' milliseconds."""
         s = Bz2SelfCheckStats()
         s.struct_size = ctypes.sizeof(Bz2SelfCheckStats)
         self._check(lib().snaphash_get_bz2_selfcheck_stats(self._h, ctypes.byref(s)))
@@ -832,12 +844,32 @@ class Context:
         self._check(lib().snaphash_get_xz_check_stats(self._h, ctypes.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in XzCheckStats._fields_ if f[0] not in ("struct_size", "reserved")}
 
-    def snap_build(self, source_dir, snap_path, hashes=True, check=False, mtime=-1):
+    def snap_build(self, source_dir, snap_path, hashes=True, check=False, mtime=-1, codec="gz", **codec_options):
         """ClickDeb.Build with snappy.Build's callback: source_dir (with its DEBIAN/) -> the .snap at snap_path, every
         source file read once.  hashes=False is the reference's nil callback (no DEBIAN/hashes.yaml); check=True runs
-        the self-check kernel over both tars' DEFLATE streams; mtime < 0: now.
+        the self-check kernels over what is written (control.tar.gz's DEFLATE stream, and the data member's by its
+        producer's own check); mtime < 0: now.  codec: the data member -- "gz" (data.tar.gz, what the reference writes),
+        "xz" or "bz2" (or snaphash_snap_build_options.data_codec's number).  codec_options go to the member's producer as
+        tar_create_xz / tar_create_bz2 take them: block_size, xz_check (the Blocks' Check: an id or "none", "crc32",
+        "crc64", "sha256"), filter and level for "xz"; level for "bz2"; self_check for either.  Options of a codec that
+        is not chosen are refused by the library (EINVAL), as are the producers' own refusals.
         -> (archive digest, digest of the .snap written, stats dict)."""
-        opt = SnapBuildOptions(ctypes.sizeof(SnapBuildOptions), (0 if hashes else BUILD_NO_HASHES) | (BUILD_CHECK if check else 0), int(mtime))
+        unknown = set(codec_options) - {"block_size", "xz_check", "filter", "level", "self_check"}
+        if unknown:
+            raise TypeError("snap_build: unknown codec option %s" % sorted(unknown))
+        codec = DATA_CODECS.get(codec, codec)
+        opt = SnapBuildOptions(ctypes.sizeof(SnapBuildOptions), (0 if hashes else BUILD_NO_HASHES) | (BUILD_CHECK if check else 0), int(mtime),
+                               int(codec))
+        xz_only = {k: codec_options[k] for k in ("block_size", "xz_check", "filter") if k in codec_options}
+        shared = {k: codec_options[k] for k in ("level", "self_check") if k in codec_options}
+        if xz_only or (shared and codec != DATA_CODECS["bz2"]):  # (with "gz" or an unknown codec too: the library refuses them)
+            chk = xz_only.get("xz_check", 4)
+            xo = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if shared.get("self_check") else 0, xz_only.get("block_size", 0),
+                           XZ_CHECK_NAMES[chk] if isinstance(chk, str) else int(chk), bcj_filter(xz_only.get("filter")), shared.get("level", 0))
+            opt.xz = ctypes.pointer(xo)
+        elif shared:
+            bo = Bz2Options(ctypes.sizeof(Bz2Options), BZ2_SELF_CHECK if shared.get("self_check") else 0, shared.get("level", 0))
+            opt.bz2 = ctypes.pointer(bo)
         st = SnapBuildStats()
         st.struct_size = ctypes.sizeof(SnapBuildStats)
         adig, sdig = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
@@ -869,16 +901,17 @@ class Context:
         return [(v[2 * c], v[2 * c + 1]) for c in range(nch)]
 
     def xz_selfcheck_stats(self):
-        """The self-check of the last xz_buffer / tar_create_xz that went through an _ex entry: chunks walked, the check
-        kernel's milliseconds."""
+        """The self-check of the last xz_buffer / tar_create_xz that went through an _ex entry, or of the data.tar.xz of the
+        last snap_build: chunks walked, the check kernel's milliseconds."""
         s = XzSelfCheckStats()
         s.struct_size = ctypes.sizeof(XzSelfCheckStats)
         self._check(lib().snaphash_get_xz_selfcheck_stats(self._h, ctypes.byref(s)))
         return {"chunks": s.chunks, "ms": s.ms}
 
-    def snap_open(self, snap_path):
-        """A session on a .snap file (ClickDeb.Open): see Snap."""
-        return Snap(self, snap_path)
+    def snap_open(self, snap_path, xz=False):
+        """A session on a .snap file (ClickDeb.Open): see Snap.  xz: ".xz" members are read too (snaphash_snap_open_ex with
+        SNAPHASH_SNAP_XZ); without it they are refused with the reference's "Can not handle" text."""
+        return Snap(self, snap_path, xz=xz)
 
     def unpack_stats(self):
         s = UnpackStats()
@@ -989,10 +1022,14 @@ class Context:
 class Snap:
     """snaphash_snap_*: one .snap file read once, its ar members, and its two tars decoded at most once each."""
 
-    def __init__(self, ctx, snap_path):
+    def __init__(self, ctx, snap_path, xz=False, _opt=None):
         self._ctx = ctx
         h = ctypes.c_void_p()
-        ctx._check(lib().snaphash_snap_open(ctx._h, os.fsencode(snap_path), ctypes.byref(h)))
+        if xz or _opt is not None:  # (_opt: a SnapOpenOptions as it is, for the tests of the entry's refusals)
+            opt = _opt if _opt is not None else SnapOpenOptions(ctypes.sizeof(SnapOpenOptions), SNAP_XZ)
+            ctx._check(lib().snaphash_snap_open_ex(ctx._h, os.fsencode(snap_path), ctypes.byref(opt), ctypes.byref(h)))
+        else:
+            ctx._check(lib().snaphash_snap_open(ctx._h, os.fsencode(snap_path), ctypes.byref(h)))
         self._h = h
 
     def close(self):

@@ -37,9 +37,14 @@
  *   snaphash [options] snap audit FILE.snap      every check the package carries, nothing written; exit 1 on mismatch
  *   snaphash [options] snap unpack DIR FILE.snap ClickDeb.Unpack + Verify against the package's own hashes.yaml;
  *                                      exit 1 on mismatch; -s prints the unpack and session statistics
- *   snaphash [options] snap build [-c] DIR OUT.snap   ClickDeb.Build with writeHashes fused in: DIR (with its DEBIAN/) -> the
+ *   snaphash [options] snap -x VERB ...          the five verbs above on a package with control.tar.xz / data.tar.xz members
+ *                                      (SNAPHASH_SNAP_XZ); without -x such a member is "Can not handle NAME"
+ *   snaphash [options] snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F x86|arm|armthumb] [-C none|crc32|crc64|sha256] [-B KiB] DIR OUT.snap
+ *                                      ClickDeb.Build with writeHashes fused in: DIR (with its DEBIAN/) -> the
  *                                      package, DIR/DEBIAN/hashes.yaml written on the way; prints the SHA-512 of the file
- *                                      (the store's download_sha512); -c: the DEFLATE self-check on the GPU
+ *                                      (the store's download_sha512); -c: the self-checks on the GPU; -Z: the data member's
+ *                                      codec (default gz, what the reference writes), -L -F -C -B as build-xz and build-bz2
+ *                                      take them for that codec; -s names the member written
  *   snaphash [options] cmp A B [A B ...]         helpers.FilesAreEqual per pair; exit 1 if any pair differs
  *   snaphash [options] dirupdated DIR_A DIR_B [PREFIX]   helpers.DirUpdated
  * options: -d DEV[,DEV...]  engines (default: the current device; -1 = all visible)
@@ -74,7 +79,8 @@ static int usage(void)
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz [-F] IN.xz OUT |\n"
                     "       unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
                     "       (-F on the two .xz decoding commands: also take Blocks with a BCJ filter in front of LZMA2)\n"
-                    "       snap {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap | snap build [-c] DIR OUT.snap |\n"
+                    "       snap [-x] {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap  (-x: .xz members are read too) |\n"
+                    "       snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F x86|arm|armthumb] [-C none|crc32|crc64|sha256] [-B BLOCK_KiB] DIR OUT.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
                     "       -b: gunzip / unpack also split streams without flush points at their blocks (SNAPHASH_FLAG_SPLIT_BLOCKS)\n"
@@ -103,7 +109,7 @@ static int xz_check_id(const char *w)
 /* -F's word -> the filter id, or 0 */
 static uint32_t xz_filter_id(const char *w)
 {
-    return !strcmp(w, "x86") ? 4u : !strcmp(w, "arm") ? 7u : !strcmp(w, "armthumb") ? 8u : 0u;
+    return !strcmp(w, "x86") ? 4u : !strcmp(w, "arm") ? 7u : (!strcmp(w, "armthumb") || !strcmp(w, "thumb")) ? 8u : 0u;
 }
 
 /* the .xz commands' -L: the level, 0 or 1, or -1 */
@@ -450,32 +456,66 @@ int main(int argc, char **argv)
         }
         free(y);
     } else if (!strcmp(argv[1], "snap") && argc >= 4 && !strcmp(argv[2], "build")) {
-        const int check = argc == 6 && !strcmp(argv[3], "-c");
-        if (argc != (check ? 6 : 5)) ret = usage();
+        /* the options in front of the two names; -L -F -C -B go to the producer -Z names, and the library refuses what is not its */
+        snaphash_snap_build_options opt;
+        snaphash_xz_options xo;
+        snaphash_bz2_options bo;
+        memset(&opt, 0, sizeof opt);
+        memset(&xo, 0, sizeof xo);
+        memset(&bo, 0, sizeof bo);
+        opt.struct_size = sizeof opt;
+        opt.mtime = -1;
+        xo.struct_size = sizeof xo;
+        xo.check = 4;
+        bo.struct_size = sizeof bo;
+        int bad = 0, xz_opts = 0;
+        const char *level = NULL;
+        while (argc > 5 && !bad) {
+            int id = -1;
+            if (!strcmp(argv[3], "-c")) { opt.flags |= SNAPHASH_BUILD_CHECK; argv++; argc--; continue; }
+            if (argc < 7) { bad = 1; break; }
+            if (!strcmp(argv[3], "-Z")) {
+                opt.data_codec = !strcmp(argv[4], "gz") ? SNAPHASH_DATA_GZ : !strcmp(argv[4], "bz2") ? SNAPHASH_DATA_BZ2 : !strcmp(argv[4], "xz") ? SNAPHASH_DATA_XZ : 99u;
+                bad = opt.data_codec == 99u;
+            } else if (!strcmp(argv[3], "-L")) level = argv[4];
+            else if (!strcmp(argv[3], "-B")) { xo.block_size = (uint64_t)strtoull(argv[4], NULL, 10) * 1024u; bad = xo.block_size == 0; xz_opts = 1; }
+            else if (!strcmp(argv[3], "-C") && (id = xz_check_id(argv[4])) >= 0) { xo.check = (uint32_t)id; xz_opts = 1; }
+            else if (!strcmp(argv[3], "-F") && (xo.filter = xz_filter_id(argv[4])) != 0) xz_opts = 1;
+            else bad = 1;
+            argv += 2; argc -= 2;
+        }
+        if (level && opt.data_codec == SNAPHASH_DATA_BZ2) { bo.level = bz2_level(level); bad |= bo.level == 0; opt.bz2 = &bo; }
+        else if (level) { bad |= xz_level(level) < 0; xo.level = (uint32_t)(xz_level(level) > 0); xz_opts = 1; }
+        if (xz_opts) opt.xz = &xo; /* (with another codec: the library's refusal) */
+        if (bad || argc != 5) ret = usage();
         else {
-            snaphash_snap_build_options opt = {sizeof opt, check ? SNAPHASH_BUILD_CHECK : 0, -1};
             snaphash_snap_build_stats bs;
             uint8_t adig[64], sdig[64];
             bs.struct_size = sizeof bs;
             rc = snaphash_snap_build(c, argv[argc - 2], argv[argc - 1], &opt, adig, sdig, &bs);
             if (rc) ret = die(c, rc, "snap build");
             else {
+                const char *member = opt.data_codec == SNAPHASH_DATA_XZ ? "data.tar.xz" : opt.data_codec == SNAPHASH_DATA_BZ2 ? "data.tar.bz2" : "data.tar.gz";
                 for (int i = 0; i < 64; i++) printf("%02x", sdig[i]);
                 printf("  %s\n", argv[argc - 1]);
                 if (show_stats)
-                    fprintf(stderr, "snap build: %llu bytes (data.tar.gz %llu of %llu tar bytes, %llu members; control.tar.gz %llu); data %.1f ms, control %.1f ms, "
+                    fprintf(stderr, "snap build: %llu bytes (%s %llu of %llu tar bytes, %llu members; control.tar.gz %llu); data %.1f ms, control %.1f ms, "
                                     "container %.1f ms, wall %.1f ms; self-check: %llu chunks, %.3f ms\n",
-                            (unsigned long long)bs.snap_bytes, (unsigned long long)bs.data_bytes, (unsigned long long)bs.tar_bytes, (unsigned long long)bs.members,
+                            (unsigned long long)bs.snap_bytes, member, (unsigned long long)bs.data_bytes, (unsigned long long)bs.tar_bytes, (unsigned long long)bs.members,
                             (unsigned long long)bs.control_bytes, bs.data_ms, bs.control_ms, bs.ar_ms, bs.wall_ms, (unsigned long long)bs.check_chunks, bs.check_ms);
+                if (show_stats && opt.data_codec == SNAPHASH_DATA_XZ && xo.filter) print_xz_filter(c, "snap build");
             }
         }
     } else if (!strcmp(argv[1], "snap") && argc >= 4) {
+        /* -x in front of the verb: the session routes .xz members to the .xz engine */
+        snaphash_snap_open_options so = {sizeof so, 0};
+        if (!strcmp(argv[2], "-x")) { so.flags = SNAPHASH_SNAP_XZ; argv++; argc--; }
         const char *verb = argv[2], *file = argv[argc - 1];
         const int takes_arg = !strcmp(verb, "cat-control") || !strcmp(verb, "cat-meta") || !strcmp(verb, "unpack");
         const int known = takes_arg || !strcmp(verb, "ls") || !strcmp(verb, "audit");
         snaphash_snap *sn = NULL;
         if (!known || argc != (takes_arg ? 5 : 4)) ret = usage();
-        else if ((rc = snaphash_snap_open(c, file, &sn)) != 0) ret = die(c, rc, "snap");
+        else if ((rc = snaphash_snap_open_ex(c, file, &so, &sn)) != 0) ret = die(c, rc, "snap");
         else if (!strcmp(verb, "ls")) {
             for (size_t i = 0; i < snaphash_snap_members(sn); i++) {
                 const char *nm;

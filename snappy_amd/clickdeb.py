@@ -65,8 +65,10 @@ class ClickDeb:
         self._snap = snap
 
     @classmethod
-    def open(cls, path, ctx=None):
-        return cls((ctx or default_context()).snap_open(path))
+    def open(cls, path, ctx=None, xz=False):
+        """xz: control.tar.xz / data.tar.xz members are read too, through the library's .xz engine (the reference pipes them
+        through the xz tool); without it they raise SnaphashError EINVAL "Can not handle ...", as they always did."""
+        return cls((ctx or default_context()).snap_open(path, xz=xz))
 
     @classmethod
     def create(cls, path, ctx=None):
@@ -116,13 +118,17 @@ class ClickDebWriter:
         self._ctx = ctx
         self.archive_digest = self.snap_digest = self.build_stats = None
 
-    def build(self, sourceDir, hashes=True, check=False, mtime=-1):
-        """ClickDeb.Build(sourceDir, callback): data.tar.gz from one read of the tree, DEBIAN/hashes.yaml from the same
-        pass (hashes=False: the nil callback), control.tar.gz, the ar container.  check=True: every DEFLATE chunk is
-        decoded again in HBM and compared with what it was made from before it is written.  Raises SnaphashError and
-        leaves no file on failure.  -> self; archive_digest, snap_digest (the store's download_sha512) and build_stats
-        are set."""
-        self.archive_digest, self.snap_digest, self.build_stats = self._ctx.snap_build(sourceDir, self.path, hashes, check, mtime)
+    def build(self, sourceDir, hashes=True, check=False, mtime=-1, codec="gz", **codec_options):
+        """ClickDeb.Build(sourceDir, callback): the data member from one read of the tree, DEBIAN/hashes.yaml from the same
+        pass (hashes=False: the nil callback), control.tar.gz, the ar container.  codec: "gz" (data.tar.gz, what the
+        reference hard-codes), "xz" or "bz2" -- the member is then what tarCreate's producer of that name writes;
+        codec_options: block_size, xz_check, filter, level for "xz", level for "bz2" (Context.snap_build).  check=True:
+        what was compressed is decoded again in HBM and compared with what it was made from before it is written -- the
+        DEFLATE chunks of control.tar.gz and of a data.tar.gz, the LZMA2 chunks of a data.tar.xz, the blocks of a
+        data.tar.bz2.  Raises SnaphashError and leaves no file on failure.  -> self; archive_digest, snap_digest (the
+        store's download_sha512) and build_stats are set.  ClickDeb.open(path, xz=True) reads a data.tar.xz back."""
+        self.archive_digest, self.snap_digest, self.build_stats = self._ctx.snap_build(sourceDir, self.path, hashes, check, mtime, codec,
+                                                                                       **codec_options)
         return self
 
     def close(self):

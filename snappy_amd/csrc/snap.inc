@@ -7,7 +7,9 @@
 // tars at most once: the decoded stream and its member list stay in the session, the data.tar stream in c->inf.d_out too
 // for the in-pass Verify and the audit.  Another decode on the ctx may take that buffer (control.tar.* after a
 // MetaMember call does): the engine counts the decodes that wrote it (DevCtx::fout_gen), and a session whose stream is no
-// longer there copies it up again from host memory -- it is never decoded twice.
+// longer there copies it up again from host memory -- it is never decoded twice.  All of this is blind to the codec: a
+// member goes to the decoder its suffix names (kSnapCodecs), ".xz" only in a session opened with SNAPHASH_SNAP_XZ
+// (snaphash_snap_open_ex), which then takes the chains SNAPHASH_UNXZ_BCJ takes (DESIGN.md sec. 28).
 
 #include "tar_core.h"
 
@@ -16,6 +18,7 @@ struct snaphash_snap {
     std::string path;
     std::vector<uint8_t> file;
     std::vector<ArMember> mem;
+    bool xz = false; // SNAPHASH_SNAP_XZ: ".xz" members go to kUnxzCodec
     struct Tar {
         bool tried = false;
         int rc = 0;            // of the decode and tar_read
@@ -33,8 +36,8 @@ struct snaphash_snap {
 
 namespace {
 
-const UnpackCodec* const kSnapCodecs[] = {&kGunzipCodec, &kBunzip2Codec}; // by ar_pick's codec (snap_core.h)
-static_assert(kSnapGz == 0 && kSnapBz2 == 1, "kSnapCodecs is indexed by ar_pick's codec");
+const UnpackCodec* const kSnapCodecs[] = {&kGunzipCodec, &kBunzip2Codec, &kUnxzCodec}; // by ar_pick_ex's codec (snap_core.h)
+static_assert(kSnapGz == 0 && kSnapBz2 == 1 && kSnapXz == 2, "kSnapCodecs is indexed by ar_pick_ex's codec");
 
 // The tar behind `prefix`, decoded once: t.rc / t.err keep what came of it for every later call.
 int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool keep_dev)
@@ -45,7 +48,7 @@ int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool k
     t.tried = true;
     int codec = 0;
     std::string why;
-    t.rc = ar_pick(s->mem, prefix, &t.member, &codec, why);
+    t.rc = ar_pick_ex(s->mem, prefix, s->xz, &t.member, &codec, why);
     if (t.rc) { t.err = why; return fail(x, t.rc, t.err); }
     const uint8_t* z = s->file.data() + s->mem[t.member].off;
     const size_t zn = (size_t)s->mem[t.member].size;
@@ -56,6 +59,8 @@ int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool k
     {
         DigestThread dig_th(z, zn, t.adig);
         DecodedStream ds(c, t.tar, keep_dev);
+        UnxzCall xz_call(x); // an .xz member: one BCJ filter in front of LZMA2 is taken, as the xz tool the reference pipes through takes it
+        if (codec == kSnapXz) xz_call.allow_bcj();
         // under SNAPHASH_FLAG_GPU_ONLY the stream reaches HBM before host memory: the CRCs are taken there
         t.rc = kSnapCodecs[codec]->decode(x, c, z, zn, ds, t.st, x->gpu_only ? CrcAt::Device : CrcAt::Host, &s->tally);
         scratch_spans_done(c);
@@ -125,12 +130,21 @@ int snap_data_on_device(snaphash_snap* s)
 
 extern "C" {
 
-int snaphash_snap_open(snaphash_ctx* x, const char* snap_path, snaphash_snap** out)
+int snaphash_snap_open(snaphash_ctx* x, const char* snap_path, snaphash_snap** out) { return snaphash_snap_open_ex(x, snap_path, nullptr, out); }
+
+int snaphash_snap_open_ex(snaphash_ctx* x, const char* snap_path, const snaphash_snap_open_options* opt, snaphash_snap** out)
 try {
     if (!x || !snap_path || !out) return fail(x, SNAPHASH_EINVAL, "bad argument");
     *out = nullptr;
+    uint32_t flags = 0;
+    if (opt && (opt->struct_size || opt->flags)) { // (all zero: snaphash_snap_open)
+        if (opt->struct_size < sizeof(snaphash_snap_open_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_snap_open_options.struct_size");
+        if (opt->flags & ~(uint32_t)SNAPHASH_SNAP_XZ) return fail(x, SNAPHASH_EINVAL, "snap: unknown flag");
+        flags = opt->flags;
+    }
     std::unique_ptr<snaphash_snap> s(new snaphash_snap);
     s->x = x;
+    s->xz = (flags & SNAPHASH_SNAP_XZ) != 0;
     s->path = snap_path;
     s->stats.struct_size = sizeof s->stats;
     int rc = read_whole(x, snap_path, s->file);

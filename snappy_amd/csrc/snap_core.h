@@ -111,13 +111,14 @@ inline int ar_write(const std::vector<ArInput>& mem, int64_t mtime, uint32_t mod
     return 0;
 }
 
-enum : int { kSnapGz = 0, kSnapBz2 = 1 };
+enum : int { kSnapGz = 0, kSnapBz2 = 1, kSnapXz = 2 };
 
 // skipToArMember: the FIRST member whose name starts with prefix; its suffix picks the decoder.  0 with *index and *codec;
 // SNAPHASH_EFORMAT when there is none (the reference: io.EOF from the ar reader); SNAPHASH_EINVAL -- what
-// snaphash_tar_create answers to a name that is not ".gz" -- with the reference's text for ".xz" (an external tool
-// upstream) and any other suffix.
-inline int ar_pick(const std::vector<ArMember>& mem, const std::string& prefix, size_t* index, int* codec, std::string& why)
+// snaphash_tar_create answers to a name that is not ".gz" -- with the reference's text for any other suffix, and for ".xz"
+// (an external tool upstream) unless xz_allowed: a session opened with SNAPHASH_SNAP_XZ takes it, codec kSnapXz.  Allowed or
+// not, the first match decides: a ".xz" member in front of a ".gz" one is the member looked at.
+inline int ar_pick_ex(const std::vector<ArMember>& mem, const std::string& prefix, bool xz_allowed, size_t* index, int* codec, std::string& why)
 {
     for (size_t i = 0; i < mem.size(); ++i) {
         const std::string& nm = mem[i].name;
@@ -126,11 +127,18 @@ inline int ar_pick(const std::vector<ArMember>& mem, const std::string& prefix, 
         auto ends = [&](const char* s) { const size_t l = strlen(s); return nm.size() >= l && nm.compare(nm.size() - l, l, s) == 0; };
         if (ends(".gz")) { *codec = kSnapGz; return 0; }
         if (ends(".bz2")) { *codec = kSnapBz2; return 0; }
+        if (xz_allowed && ends(".xz")) { *codec = kSnapXz; return 0; }
         why = "Can not handle " + nm;
         return SNAPHASH_EINVAL;
     }
     why = "ar: no " + prefix + " member";
     return SNAPHASH_EFORMAT;
+}
+
+// what snaphash_snap_open's sessions ask: ".xz" is refused
+inline int ar_pick(const std::vector<ArMember>& mem, const std::string& prefix, size_t* index, int* codec, std::string& why)
+{
+    return ar_pick_ex(mem, prefix, false, index, codec, why);
 }
 
 // ---- the audit's comparison ----------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// snapbuild.inc -- writing the .snap, textually part of snaphash_api.cpp (after targz.inc, whose producer it drives, and
-// snap.inc, whose container it writes).
+// snapbuild.inc -- writing the .snap, textually part of snaphash_api.cpp (after targz.inc, xzpack.inc and bzpack.inc, whose
+// producers it drives, and snap.inc, whose container it writes).
 //
 // ClickDeb.Build (reference clickdeb/deb.go:346-406) runs tarCreate over the tree into a temporary data.tar.gz, calls
 // snappy.Build's callback -- writeHashes (snappy/build.go:216-270), which reads the archive and every file a second time --
@@ -9,9 +9,14 @@
 // comes before data.tar.gz in the container and holds the data member's digest, so the data member waits in a temporary
 // file beside the target -- not in host memory: a member is as large as the package, and the file's pages are the
 // page cache's to keep or drop -- until the control member is known; the copy into the container feeds the file's own
-// SHA-512 (the store's download_sha512), so the .snap is not read back for it.
+// SHA-512 (the store's download_sha512), so the .snap is not read back for it.  The reference hard-codes data.tar.gz "for
+// distros like trusty that does not support xz yet" (deb.go:359); here the data member's Encoder is the caller's choice
+// (snaphash_snap_build_options.data_codec: GzipEncoder, XzEncoder or BzEncoder through the same tar_create_impl), the
+// control member stays gzip (DESIGN.md sec. 28).
 
 namespace {
+
+constexpr uint32_t kSnapBuildOptionsSizeV1 = 16; // snaphash_snap_build_options before data_codec, reserved, xz and bz2
 
 struct SnapBuildTemps { // removed on every way out
     std::string data, control;
@@ -73,8 +78,17 @@ int snap_put_member(snaphash_ctx* x, SnapOut& out, const char* name, int64_t mti
     return SNAPHASH_OK;
 }
 
+// The data member of one build: its producer, made by the entry with the call's options, its name -- the ar member's, and
+// behind "<snap_path>." the temporary's -- and what the producer's self-check counts (DEFLATE chunks, LZMA2 chunks, bzip2 blocks).
+struct SnapDataMember {
+    Encoder& enc;
+    const char* name;
+    const uint64_t& check_units;
+    const double& check_ms;
+};
+
 int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_path, uint32_t flags, int64_t mtime, uint8_t* archive_digest,
-                    uint8_t* snap_digest, snaphash_snap_build_stats& st)
+                    uint8_t* snap_digest, snaphash_snap_build_stats& st, const SnapDataMember& dm)
 {
     const double t0 = now_ms();
     const bool hashes = !(flags & SNAPHASH_BUILD_NO_HASHES);
@@ -84,20 +98,19 @@ int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_pa
     out.fd = open(snap_path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (out.fd < 0) return fail(x, SNAPHASH_EIO, std::string(snap_path) + ": " + strerror(errno));
     host_sha512_init(out.sha);
-    tmp.data = std::string(snap_path) + ".data.tar.gz";
+    tmp.data = std::string(snap_path) + "." + dm.name;
     tmp.control = std::string(snap_path) + ".control.tar.gz";
     const std::string debian = go_clean(std::string(source_dir) + "/DEBIAN"); // filepath.Join(sourceDir, "DEBIAN")
 
-    GzCheck chk_data, chk_control;
-    chk_data.member = "data.tar.gz";
+    GzCheck chk_control;
     chk_control.member = "control.tar.gz";
     const bool check = (flags & SNAPHASH_BUILD_CHECK) != 0;
     uint8_t adig[64];
     char* yaml = nullptr;
     size_t yaml_len = 0;
     struct Free { char*& p; ~Free() { free(p); } } free_yaml{yaml};
-    GzipEncoder enc_data(check ? &chk_data : nullptr), enc_control(check ? &chk_control : nullptr);
-    int rc = tar_create_impl(x, enc_data, tmp.data.c_str(), source_dir, debian.c_str(), nullptr, nullptr, hashes ? &yaml : nullptr, &yaml_len, adig);
+    GzipEncoder enc_control(check ? &chk_control : nullptr);
+    int rc = tar_create_impl(x, dm.enc, tmp.data.c_str(), source_dir, debian.c_str(), nullptr, nullptr, hashes ? &yaml : nullptr, &yaml_len, adig);
     if (rc) return rc;
     st.data_ms = x->targz.wall_ms;
     st.tar_bytes = x->targz.tar_bytes;
@@ -111,8 +124,8 @@ int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_pa
     if (rc) return rc;
     st.control_ms = x->targz.wall_ms;
     st.control_bytes = x->targz.gz_bytes;
-    st.check_chunks = chk_data.chunks + chk_control.chunks;
-    st.check_ms = chk_data.ms + chk_control.ms;
+    st.check_chunks = dm.check_units + chk_control.chunks;
+    st.check_ms = dm.check_ms + chk_control.ms;
 
     const double t_ar = now_ms();
     const int en = out.put((const uint8_t*)kArMagic, 8);
@@ -120,7 +133,7 @@ int snap_build_impl(snaphash_ctx* x, const char* source_dir, const char* snap_pa
     rc = snap_put_member(x, out, "debian-binary", mtime, (const uint8_t*)"2.0\n", 4, nullptr);
     if (!rc) rc = snap_put_member(x, out, "_click-binary", mtime, (const uint8_t*)"0.4\n", 4, nullptr);
     if (!rc) rc = snap_put_member(x, out, "control.tar.gz", mtime, nullptr, 0, tmp.control.c_str());
-    if (!rc) rc = snap_put_member(x, out, "data.tar.gz", mtime, nullptr, 0, tmp.data.c_str());
+    if (!rc) rc = snap_put_member(x, out, dm.name, mtime, nullptr, 0, tmp.data.c_str());
     if (rc) return rc;
     const int fd = out.fd;
     out.fd = -1;
@@ -143,17 +156,66 @@ int snaphash_snap_build(snaphash_ctx* x, const char* source_dir, const char* sna
                         uint8_t* archive_digest, uint8_t* snap_digest, snaphash_snap_build_stats* stats)
 try {
     if (!x || !source_dir || !snap_path || !*snap_path) return fail(x, SNAPHASH_EINVAL, "bad argument");
-    if (opt && opt->struct_size < sizeof(snaphash_snap_build_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_snap_build_options.struct_size");
+    static_assert(offsetof(snaphash_snap_build_options, data_codec) == kSnapBuildOptionsSizeV1, "the codec and its options behind the 16 bytes");
+    // 16: the struct before it named a codec (gzip); the whole struct and more: with data_codec, reserved, xz and bz2
+    if (opt && opt->struct_size != kSnapBuildOptionsSizeV1 && opt->struct_size < sizeof(snaphash_snap_build_options))
+        return fail(x, SNAPHASH_EINVAL, "snaphash_snap_build_options.struct_size");
     if (stats && stats->struct_size < sizeof(snaphash_snap_build_stats)) return fail(x, SNAPHASH_EINVAL, "snaphash_snap_build_stats.struct_size");
     const uint32_t flags = opt ? opt->flags : 0;
     if (flags & ~(uint32_t)(SNAPHASH_BUILD_NO_HASHES | SNAPHASH_BUILD_CHECK)) return fail(x, SNAPHASH_EINVAL, "unknown build flag");
     const int64_t mtime = (opt && opt->mtime >= 0) ? opt->mtime : (int64_t)time(nullptr);
+    uint32_t codec = SNAPHASH_DATA_GZ;
+    const snaphash_xz_options* xo = nullptr;
+    const snaphash_bz2_options* bo = nullptr;
+    if (opt && opt->struct_size >= sizeof(snaphash_snap_build_options)) {
+        codec = opt->data_codec;
+        xo = opt->xz;
+        bo = opt->bz2;
+        if (codec > SNAPHASH_DATA_XZ) return fail(x, SNAPHASH_EINVAL, "snap build: data_codec is 0 (gz), 1 (bz2) or 2 (xz)");
+        if (opt->reserved) return fail(x, SNAPHASH_EINVAL, "snap build: snaphash_snap_build_options.reserved is not 0");
+        if ((xo && codec != SNAPHASH_DATA_XZ) || (bo && codec != SNAPHASH_DATA_BZ2))
+            return fail(x, SNAPHASH_EINVAL, "snap build: options for a codec that is not data_codec");
+    }
+    const bool check = (flags & SNAPHASH_BUILD_CHECK) != 0;
     snaphash_snap_build_stats st{};
     st.struct_size = sizeof st;
-    const int rc = snap_build_impl(x, source_dir, snap_path, flags, mtime, archive_digest, snap_digest, st);
-    if (rc) (void)unlink(snap_path);
-    if (stats) *stats = st;
-    return rc;
+    auto build = [&](const SnapDataMember& dm) {
+        const int rc = snap_build_impl(x, source_dir, snap_path, flags, mtime, archive_digest, snap_digest, st, dm);
+        if (rc) (void)unlink(snap_path);
+        if (stats) *stats = st;
+        return rc;
+    };
+    // the data member's encoder is this call's own, made with this call's options: nothing of it outlives the call
+    if (codec == SNAPHASH_DATA_XZ) {
+        uint64_t bs;
+        uint32_t chk, filter, level;
+        bool self;
+        int rc = xz_read_options(x, xo, &bs, &chk, &self, &filter, &level);
+        if (rc) return rc;
+        XzSelfCheck sc;
+        sc.member = "data.tar.xz";
+        XzEncoder enc(bs, chk, (self || check) ? &sc : nullptr, filter, level);
+        rc = build(SnapDataMember{enc, "data.tar.xz", sc.chunks, sc.ms});
+        xz_keep_selfcheck_stats(x, sc);
+        xz_keep_filter_stats(x, enc);
+        return rc;
+    }
+    if (codec == SNAPHASH_DATA_BZ2) {
+        uint32_t level;
+        bool self;
+        int rc = bz2_read_options(x, bo, &level, &self);
+        if (rc) return rc;
+        BzSelfCheck sc;
+        sc.member = "data.tar.bz2";
+        BzEncoder enc(level, (self || check) ? &sc : nullptr);
+        rc = build(SnapDataMember{enc, "data.tar.bz2", sc.blocks, sc.ms});
+        bz2_keep_selfcheck_stats(x, sc);
+        return rc;
+    }
+    GzCheck chk_data;
+    chk_data.member = "data.tar.gz";
+    GzipEncoder enc(check ? &chk_data : nullptr);
+    return build(SnapDataMember{enc, "data.tar.gz", chk_data.chunks, chk_data.ms});
 } catch (...) { // allocation or thread-creation failure: no C++ exception crosses the C boundary
     if (snap_path) (void)unlink(snap_path);
     return SNAPHASH_ENOMEM;

@@ -13,10 +13,25 @@
 namespace {
 
 // Decodes every Stream of xz[0..n) and appends the bytes to ds.out; keep_dev: the whole decoded stream also stays in
-// c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.  The two CRC arguments of a codec's
-// decoder are not read: under SNAPHASH_FLAG_GPU_ONLY the Checks are taken in HBM whoever calls, on host threads otherwise.
-int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, DecodedStream& ds, snaphash_unpack_stats& st, CrcAt, CrcTally*)
+// c->inf.d_out[0..out.size()) for Verify's device hashing, as gunzip_engine leaves it.  Where a codec's decoder is told to
+// take its CRCs is not read: under SNAPHASH_FLAG_GPU_ONLY the Checks are taken in HBM whoever calls, on host threads
+// otherwise.  tally (may be null; the .snap session's): the Blocks' Checks of this decode are added to it on every way out,
+// a range a Block, from what snaphash_get_xz_check_stats hands out.
+int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, DecodedStream& ds, snaphash_unpack_stats& st, CrcAt, CrcTally* tally)
 {
+    struct TallyChecks {
+        CrcTally* const t;
+        const snaphash_xz_check_stats& ck;
+        bool armed = false; // once ck is this decode's
+        ~TallyChecks()
+        {
+            if (!t || !armed) return;
+            t->device_ranges += ck.device_crc32 + ck.device_crc64 + ck.device_sha256;
+            t->host_ranges += ck.host_checks;
+            t->device_ms += ck.device_check_ms;
+        }
+    } tally_checks{tally, x->xz_check};
+
     std::vector<uint8_t>& out = ds.out;
     std::vector<XzBlock> blocks;
     uint64_t total = 0;
@@ -36,6 +51,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
     snaphash_xz_check_stats& ck = x->xz_check; // who took the Checks of this decode
     ck = snaphash_xz_check_stats{};
     ck.struct_size = sizeof ck;
+    tally_checks.armed = true;
     auto host_checked = [&](const std::vector<uint32_t>* which) {
         const size_t K = which ? which->size() : blocks.size();
         for (size_t k = 0; k < K; ++k) ck.host_checks += blocks[which ? (*which)[k] : k].check != kXzCheckNone;
@@ -194,6 +210,7 @@ struct UnxzCall {
     snaphash_ctx* const x;
     explicit UnxzCall(snaphash_ctx* x_) : x(x_) {}
     ~UnxzCall() { x->unxz_bcj = false; }
+    void allow_bcj() { x->unxz_bcj = true; } // (a .snap session opened with SNAPHASH_SNAP_XZ, snap.inc)
     int read(const snaphash_unxz_options* opt)
     {
         if (!opt || (opt->struct_size == 0 && opt->flags == 0)) return SNAPHASH_OK;
