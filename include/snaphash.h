@@ -394,6 +394,17 @@ typedef struct snaphash_xz_options {
                            * smaller files for more kernel time.  Anything else is SNAPHASH_EINVAL.  Read when struct_size >= 32;
                            * a struct_size of 24, the struct before this field, means level 0. */
     uint32_t reserved2;   /* 0; anything else is SNAPHASH_EINVAL */
+    uint32_t chain_len;   /* 0 .. 3: the filters in front of LZMA2 when they are more than `filter` can say.
+                           * Read, with chain, when struct_size >= 48; sizes 24 and 32 .. 47 mean what they meant. */
+    uint32_t chain[3];    /* chain[k] = id | param << 8, the Block header's first filter first: id 3 Delta with param its
+                           * distance 1 .. 256, ids 4 x86, 5 PowerPC, 6 IA64, 7 ARM, 8 ARM-Thumb, 9 SPARC with param 0 (their
+                           * start_offset is 0).  Any order, repeats allowed.  SNAPHASH_EINVAL, touching nothing: chain_len
+                           * above 3, an id outside 3 .. 9, a distance of 0 or above 256, a param on a BCJ id, `filter` and
+                           * chain_len both nonzero (`filter` itself keeps to 0, 4, 7, 8).  chain = {4} writes byte for byte
+                           * what filter = 4 writes.  Delta is named with its one property byte, the others with none; the
+                           * Checks, the members' SHA-512 and hashes.yaml stay over the unfiltered bytes; the self-check walks
+                           * the chunks against the filtered bytes, undoes the whole chain in place and compares with the
+                           * staged bytes.  snaphash_unxz_buffer_ex with SNAPHASH_UNXZ_CHAINS reads the file back. */
 } snaphash_xz_options;
 typedef struct snaphash_xz_selfcheck_stats {
     uint32_t struct_size; /* set by the caller */
@@ -712,6 +723,14 @@ enum { SNAPHASH_UNXZ_BCJ = 1 }; /* accept, Block by Block, the chain of one BCJ 
                                  * liblzma 5.2.5 does not know) stays SNAPHASH_EINVAL with the plain entries' text.
                                  * SNAPHASH_EFORMAT: properties of any other size, or a start_offset liblzma refuses (not a
                                  * multiple of 4 for ARM, of 2 for Thumb). */
+enum { SNAPHASH_UNXZ_CHAINS = 4 }; /* accept, Block by Block, every chain liblzma 5.2.5 reads: up to three
+                                    * filters out of Delta (0x03, one property byte: the distance less one), x86, PowerPC
+                                    * (0x05), IA64 (0x06), ARM, ARM-Thumb and SPARC (0x09), in any order, repeats allowed, in
+                                    * front of LZMA2 -- everything SNAPHASH_UNXZ_BCJ accepts and the rest.  ARM64 (0x0A), RISC-V
+                                    * (0x0B) and unknown ids stay SNAPHASH_EINVAL, the text naming the first such filter.
+                                    * SNAPHASH_EFORMAT: Delta properties of another size, BCJ properties as above (the
+                                    * alignments: 1, 4, 16, 4, 2, 4 for ids 4 .. 9).  Without this flag every answer and every
+                                    * text is what it was.  Bit value 2 is not a flag. */
 typedef struct snaphash_unxz_options {
     uint32_t struct_size; /* sizeof(snaphash_unxz_options) */
     uint32_t flags;       /* SNAPHASH_UNXZ_*; an unknown bit is SNAPHASH_EINVAL */
@@ -720,7 +739,10 @@ typedef struct snaphash_unxz_options {
  * With SNAPHASH_UNXZ_BCJ a Block's filter is undone behind its LZMA2 decode and in front of its Check (the Check is over the
  * unfiltered bytes): by the host thread that decoded the Block in the default configuration; under SNAPHASH_FLAG_GPU_ONLY
  * by one launch of the BCJ kernels over the ranges of the Blocks lzma2_blocks_kernel decoded, in front of the Check
- * kernels (Blocks that went to a host thread are filtered there).  snaphash_get_xz_filter_stats tells who did what. */
+ * kernels (Blocks that went to a host thread are filtered there).  snaphash_get_xz_filter_stats tells who did what.  With
+ * SNAPHASH_UNXZ_CHAINS a chain of k filters is undone the same way, the filter nearest LZMA2 first: k stages of the filter
+ * kernels over the table of Blocks (a Block with a shorter chain is skipped at the later stages); in the stats `filter` is
+ * the id a Block's header names first, and a Block counts once however long its chain. */
 int snaphash_unxz_buffer_ex(snaphash_ctx *ctx, const void *xz, size_t n, const snaphash_unxz_options *opt, void **out,
                             size_t *out_len);
 int snaphash_tar_unpack_xz_ex(snaphash_ctx *ctx, const char *data_tar_xz, const char *target_dir, const char *yaml,
@@ -735,6 +757,16 @@ int snaphash_tar_unpack_xz_ex(snaphash_ctx *ctx, const char *data_tar_xz, const 
  * Synchronous; stats.kernel_ms = the kernels (HIP events), stats.launches = their number. */
 int snaphash_bcj_device(snaphash_ctx *ctx, uint32_t filter, int encode, void *d_base, const uint64_t *offsets,
                         const uint64_t *lens, size_t n, uint32_t start_offset);
+/* The same for every filter liblzma 5.2.5 takes in front of LZMA2: id 3 Delta, 4 x86, 5 PowerPC, 6 IA64,
+ * 7 ARM, 8 ARM-Thumb, 9 SPARC.  param: Delta's distance, 1 .. 256 (encode: out[i] = in[i] - in[i - distance], decode its
+ * inverse, bytes modulo 256, the bytes in front of a range 0); 0 for every other id.  start_offset: a multiple of the BCJ
+ * filter's alignment (1, 4, 16, 4, 2, 4 for ids 4 .. 9); 0 for Delta.  An incomplete last word (PowerPC, SPARC) or 16-byte
+ * bundle (IA64) is left as it is.  Delta runs a workgroup a 64 KiB tile of a range, in two launches (encode) or three
+ * (decode), none of which waits for another workgroup.  SNAPHASH_EINVAL, touching nothing: any other id (0x0A ARM64 and
+ * 0x0B RISC-V among them), a distance of 0 or above 256, a param on a BCJ id, a start_offset off the alignment.  Stats as
+ * snaphash_bcj_device's, which is unchanged and keeps to its three ids. */
+int snaphash_xz_filter_device(snaphash_ctx *ctx, uint32_t id, uint32_t param, int encode, void *d_base,
+                              const uint64_t *offsets, const uint64_t *lens, size_t n, uint32_t start_offset);
 /* What the BCJ filters did in the most recent call of this ctx among snaphash_xz_buffer_ex, snaphash_tar_create_xz_ex,
  * snaphash_snap_build with a data.tar.xz, snaphash_unxz_buffer(_ex), snaphash_tar_unpack_xz(_ex) and a .snap session's decode
  * of an .xz member. */
@@ -806,6 +838,8 @@ int snaphash_crc32_device(snaphash_ctx *ctx, int kind, const void *d_base, const
 typedef struct snaphash_snap snaphash_snap;
 int  snaphash_snap_open(snaphash_ctx *ctx, const char *snap_path, snaphash_snap **out);   /* ClickDeb.Open */
 enum { SNAPHASH_SNAP_XZ = 1 }; /* snaphash_snap_open_options.flags: route ".xz" members to the .xz engine (see above) */
+enum { SNAPHASH_SNAP_XZ_CHAINS = 4 }; /* with SNAPHASH_SNAP_XZ only (alone: SNAPHASH_EINVAL): ".xz" members may carry every chain
+                                       * SNAPHASH_UNXZ_CHAINS takes.  Bit value 2 is not a flag. */
 typedef struct snaphash_snap_open_options {
     uint32_t struct_size; /* sizeof(snaphash_snap_open_options) */
     uint32_t flags;       /* SNAPHASH_SNAP_*; an unknown bit is SNAPHASH_EINVAL */

@@ -69,6 +69,8 @@ EXPORTS = [
     "snaphash_bzip2_buffer_ex", "snaphash_tar_create_bz2_ex", "snaphash_get_bz2_selfcheck_stats", "snaphash_bz2_check_device",
     # the .snap session with ".xz" members routed to the .xz engine
     "snaphash_snap_open_ex",
+    # every filter liblzma takes in front of LZMA2, the kernels alone
+    "snaphash_xz_filter_device",
 ]
 BUILD_NO_HASHES, BUILD_CHECK = 1, 2
 SNAP_XZ = 1
@@ -76,8 +78,11 @@ DATA_CODECS = {"gz": 0, "bz2": 1, "xz": 2}  # snaphash_snap_build_options.data_c
 XZ_CHECK_NAMES = {"none": 0, "crc32": 1, "crc64": 4, "sha256": 10}
 XZ_SELF_CHECK = 1
 UNXZ_BCJ = 1
+UNXZ_CHAINS = 4  # (2 is not a flag)
+SNAP_XZ_CHAINS = 4
 BCJ_X86, BCJ_ARM, BCJ_ARMTHUMB = 4, 7, 8  # the .xz format's filter ids
 BCJ_NAMES = {"x86": BCJ_X86, "arm": BCJ_ARM, "armthumb": BCJ_ARMTHUMB}
+XZ_FILTER_NAMES = dict(BCJ_NAMES, delta=3, powerpc=5, ia64=6, sparc=9)  # what snaphash_xz_filter_device takes
 
 
 def bcj_filter(f):
@@ -161,6 +166,35 @@ class XzCheckStats(ctypes.Structure):
 class XzOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("block_size", ctypes.c_uint64),
                 ("check", ctypes.c_uint32), ("filter", ctypes.c_uint32), ("level", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
+
+
+class XzOptionsChain(XzOptions):
+    """snaphash_xz_options with the fields behind its first 32 bytes: the filter chain (struct_size 48)."""
+    _fields_ = [("chain_len", ctypes.c_uint32), ("chain", ctypes.c_uint32 * 3)]
+
+
+def xz_chain_words(chain):
+    """[("delta", 4), "x86", 9] -> snaphash_xz_options.chain's words, id | param << 8"""
+    out = []
+    for f in chain:
+        f, param = f if isinstance(f, tuple) else (f, 0)
+        fid = XZ_FILTER_NAMES.get(f, f) if isinstance(f, str) else f
+        if not isinstance(fid, int):
+            raise ValueError("unknown .xz filter %r" % (f,))
+        out.append(fid | int(param) << 8)
+    return out
+
+
+def xz_options(flags, block_size, check, filter, level, chain=None):
+    """snaphash_xz_options: the 32-byte struct, or with a chain the 48-byte one"""
+    if not chain:
+        return XzOptions(ctypes.sizeof(XzOptions), flags, block_size, check, filter, level)
+    words = xz_chain_words(chain)
+    o = XzOptionsChain(ctypes.sizeof(XzOptionsChain), flags, block_size, check, filter, level)
+    o.chain_len = len(words)
+    for k, w in enumerate(words[:3]):
+        o.chain[k] = w
+    return o
 
 
 class UnxzOptions(ctypes.Structure):
@@ -356,6 +390,7 @@ def lib():
     L.snaphash_tar_unpack_xz_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.POINTER(UnxzOptions),
                                             ctypes.POINTER(Mismatch), ctypes.c_char_p]
     L.snaphash_bcj_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, vp, vp, sz, ctypes.c_uint32]
+    L.snaphash_xz_filter_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, vp, vp, vp, sz, ctypes.c_uint32]
     L.snaphash_get_xz_filter_stats.argtypes = [vp, ctypes.POINTER(XzFilterStats)]
     L.snaphash_lzma2_check_device.argtypes = [vp, vp, sz, ctypes.c_uint64, vp, sz, u64p, u64p, sz, ctypes.c_uint32, vp]
     L.snaphash_bzip2_buffer_ex.argtypes = [vp, vp, sz, ctypes.POINTER(Bz2Options), ctypes.POINTER(vp), ctypes.POINTER(sz)]
@@ -538,7 +573,7 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def xz_buffer(self, data, block_size=0, check=None, self_check=False, filter=None, level=0):
+    def xz_buffer(self, data, block_size=0, check=None, self_check=False, filter=None, level=0, chain=None):
         """One .xz Stream of `data`, a Block per `block_size` bytes (0: 1 MiB), LZMA2 on the GPU.  check: the Blocks'
         Check id -- 0 none, 1 CRC-32, 4 CRC-64, 10 SHA-256, each taken in HBM; None: CRC-64 through the entry point that
         takes no Check.  self_check: every LZMA2 chunk is walked against the bytes it was made from before it leaves HBM
@@ -546,12 +581,14 @@ class Context:
         the same.  filter: a BCJ filter in front of LZMA2 in every Block -- "x86", "arm", "armthumb" or the format's id
         (4, 7, 8), applied in HBM (snaphash_xz_buffer_ex; xz_filter_stats() tells what ran); None or 0: none.  level: 0 the
         greedy parse, 1 several candidates a position and a price-based parse (snaphash_xz_buffer_ex): a smaller file for
-        more kernel time."""
+        more kernel time.  chain: up to three filters in front of LZMA2, the Block header's first filter first, e.g.
+        [("delta", 4), "x86"] -- names or ids of "delta" (with its distance, 1 .. 256), "x86", "powerpc", "ia64", "arm",
+        "armthumb", "sparc"; not together with filter.  unxz_buffer(chains=True) reads such a file back."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         buf = (ctypes.c_char * max(len(data), 1)).from_buffer_copy(data if len(data) else b"\0")
         filter = bcj_filter(filter)
-        if self_check or filter or level:
-            opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, 4 if check is None else check, filter, level)
+        if self_check or filter or level or chain:
+            opt = xz_options(XZ_SELF_CHECK if self_check else 0, block_size, 4 if check is None else check, filter, level, chain)
             self._check(lib().snaphash_xz_buffer_ex(self._h, ctypes.addressof(buf), len(data), ctypes.byref(opt), ctypes.byref(p), ctypes.byref(n)))
         elif check is None:
             self._check(lib().snaphash_xz_buffer(self._h, ctypes.addressof(buf), len(data), block_size, ctypes.byref(p), ctypes.byref(n)))
@@ -634,15 +671,17 @@ class Context:
                                                        ctypes.byref(total)))
         return total.value
 
-    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False, filter=None, level=0):
+    def tar_create_xz(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, block_size=0, check=4, self_check=False, filter=None, level=0,
+                      chain=None):
         """tarCreate's ".xz" branch (clickdeb/deb.go:272-273): tar_create with the .xz producer.  With the defaults:
         snaphash_tar_create_xz (1 MiB Blocks, CRC-64).  Anything else goes through snaphash_tar_create_xz_ex: block_size
-        check, self_check, filter and level as in xz_buffer (hashes.yaml and the Blocks' Checks are of the unfiltered bytes).
+        check, self_check, filter, level and chain as in xz_buffer (hashes.yaml and the Blocks' Checks are of the unfiltered
+        bytes).
         -> (yaml bytes or None, archive digest (64 bytes))."""
         filter = bcj_filter(filter)
-        if block_size == 0 and check == 4 and not self_check and not filter and not level:
+        if block_size == 0 and check == 4 and not self_check and not filter and not level and not chain:
             return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz")
-        opt = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if self_check else 0, block_size, check, filter, level)
+        opt = xz_options(XZ_SELF_CHECK if self_check else 0, block_size, check, filter, level, chain)
         return self.tar_create(tarname, source_dir, exclude_prefix, with_hashes, _entry="snaphash_tar_create_xz_ex", _opt=opt)
 
     def tar_create(self, tarname, source_dir, exclude_prefix=None, with_hashes=False, _entry="snaphash_tar_create", _opt=None):
@@ -738,14 +777,15 @@ class Context:
         uint32 (trees built before one fitted max_bits)."""
         self._check(lib().snaphash_deflate_codes_device(self._h, d_freq, n_tables, n_syms, max_bits, d_lens, d_codes, d_rounds))
 
-    def unxz_buffer(self, xz, bcj=False):
+    def unxz_buffer(self, xz, bcj=False, chains=False):
         """Every Stream of `xz` (.xz) decoded, Blocks side by side (host threads, or the GPU kernel with FLAG_GPU_ONLY).
         bcj: also take Blocks with an x86, ARM or ARM-Thumb filter in front of LZMA2 (snaphash_unxz_buffer_ex with
-        SNAPHASH_UNXZ_BCJ); without it such a file is SNAPHASH_EINVAL."""
+        SNAPHASH_UNXZ_BCJ); without it such a file is SNAPHASH_EINVAL.  chains: every chain liblzma reads, up to three of
+        Delta, x86, PowerPC, IA64, ARM, ARM-Thumb, SPARC in front of LZMA2 (SNAPHASH_UNXZ_CHAINS)."""
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         xz = bytes(xz)
-        if bcj:
-            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), UNXZ_BCJ)
+        if bcj or chains:
+            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), (UNXZ_BCJ if bcj else 0) | (UNXZ_CHAINS if chains else 0))
             self._check(lib().snaphash_unxz_buffer_ex(self._h, ctypes.cast(ctypes.c_char_p(xz), ctypes.c_void_p), len(xz), ctypes.byref(opt),
                                                       ctypes.byref(p), ctypes.byref(n)))
         else:
@@ -756,14 +796,14 @@ class Context:
         finally:
             lib().snaphash_free(p)
 
-    def tar_unpack_xz(self, data_tar_xz, target_dir, yaml_bytes=None, bcj=False):
-        """tar_unpack for a data.tar.xz; bcj as in unxz_buffer (snaphash_tar_unpack_xz_ex).
+    def tar_unpack_xz(self, data_tar_xz, target_dir, yaml_bytes=None, bcj=False, chains=False):
+        """tar_unpack for a data.tar.xz; bcj and chains as in unxz_buffer (snaphash_tar_unpack_xz_ex).
         -> (None or (kind, name) of the first mismatch, archive digest (64 bytes))."""
         m = Mismatch()
         dig = ctypes.create_string_buffer(64)
         ylen = len(yaml_bytes) if yaml_bytes is not None else 0
-        if bcj:
-            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), UNXZ_BCJ)
+        if bcj or chains:
+            opt = UnxzOptions(ctypes.sizeof(UnxzOptions), (UNXZ_BCJ if bcj else 0) | (UNXZ_CHAINS if chains else 0))
             rc = lib().snaphash_tar_unpack_xz_ex(self._h, os.fsencode(data_tar_xz), os.fsencode(target_dir), yaml_bytes, ylen, ctypes.byref(opt),
                                                  ctypes.byref(m), dig)
         else:
@@ -819,6 +859,19 @@ class Context:
         self._check(lib().snaphash_bcj_device(self._h, bcj_filter(filter), 1 if encode else 0, d_base, offsets.ctypes.data if n else None,
                                               lens.ctypes.data if n else None, n, start_offset))
 
+    def xz_filter_device(self, filter, encode, d_base, offsets, lens, start_offset=0, param=0):
+        """Any filter liblzma takes in front of LZMA2, in place over byte ranges resident in HBM, each range a Block of its own
+        (snaphash_xz_filter_device).  filter: "delta", "x86", "powerpc", "ia64", "arm", "armthumb", "sparc", a pair
+        ("delta", distance), or an id 3 .. 9; param: Delta's distance, 1 .. 256; the rest as bcj_device."""
+        if isinstance(filter, tuple):
+            filter, param = filter
+        fid = XZ_FILTER_NAMES.get(filter, filter) if isinstance(filter, str) else filter
+        if not isinstance(fid, int):
+            raise ValueError("unknown .xz filter %r" % (filter,))
+        n = len(offsets)
+        self._check(lib().snaphash_xz_filter_device(self._h, fid, param, 1 if encode else 0, d_base, offsets.ctypes.data if n else None,
+                                                    lens.ctypes.data if n else None, n, start_offset))
+
     def xz_filter_stats(self):
         """What the BCJ filters did in the last .xz call of either side: the filter, Blocks filtered by the kernels and on
         host threads, the kernels' milliseconds."""
@@ -851,22 +904,23 @@ class Context:
         producer's own check); mtime < 0: now.  codec: the data member -- "gz" (data.tar.gz, what the reference writes),
         "xz" or "bz2" (or snaphash_snap_build_options.data_codec's number).  codec_options go to the member's producer as
         tar_create_xz / tar_create_bz2 take them: block_size, xz_check (the Blocks' Check: an id or "none", "crc32",
-        "crc64", "sha256"), filter and level for "xz"; level for "bz2"; self_check for either.  Options of a codec that
+        "crc64", "sha256"), filter, chain and level for "xz"; level for "bz2"; self_check for either.  Options of a codec that
         is not chosen are refused by the library (EINVAL), as are the producers' own refusals.
         -> (archive digest, digest of the .snap written, stats dict)."""
-        unknown = set(codec_options) - {"block_size", "xz_check", "filter", "level", "self_check"}
+        unknown = set(codec_options) - {"block_size", "xz_check", "filter", "chain", "level", "self_check"}
         if unknown:
             raise TypeError("snap_build: unknown codec option %s" % sorted(unknown))
         codec = DATA_CODECS.get(codec, codec)
         opt = SnapBuildOptions(ctypes.sizeof(SnapBuildOptions), (0 if hashes else BUILD_NO_HASHES) | (BUILD_CHECK if check else 0), int(mtime),
                                int(codec))
-        xz_only = {k: codec_options[k] for k in ("block_size", "xz_check", "filter") if k in codec_options}
+        xz_only = {k: codec_options[k] for k in ("block_size", "xz_check", "filter", "chain") if k in codec_options}
         shared = {k: codec_options[k] for k in ("level", "self_check") if k in codec_options}
         if xz_only or (shared and codec != DATA_CODECS["bz2"]):  # (with "gz" or an unknown codec too: the library refuses them)
             chk = xz_only.get("xz_check", 4)
-            xo = XzOptions(ctypes.sizeof(XzOptions), XZ_SELF_CHECK if shared.get("self_check") else 0, xz_only.get("block_size", 0),
-                           XZ_CHECK_NAMES[chk] if isinstance(chk, str) else int(chk), bcj_filter(xz_only.get("filter")), shared.get("level", 0))
-            opt.xz = ctypes.pointer(xo)
+            xo = xz_options(XZ_SELF_CHECK if shared.get("self_check") else 0, xz_only.get("block_size", 0),
+                            XZ_CHECK_NAMES[chk] if isinstance(chk, str) else int(chk), bcj_filter(xz_only.get("filter")), shared.get("level", 0),
+                            xz_only.get("chain"))
+            opt.xz = ctypes.cast(ctypes.pointer(xo), ctypes.POINTER(XzOptions))  # (xo lives to the end of this call)
         elif shared:
             bo = Bz2Options(ctypes.sizeof(Bz2Options), BZ2_SELF_CHECK if shared.get("self_check") else 0, shared.get("level", 0))
             opt.bz2 = ctypes.pointer(bo)
@@ -908,10 +962,11 @@ class Context:
         self._check(lib().snaphash_get_xz_selfcheck_stats(self._h, ctypes.byref(s)))
         return {"chunks": s.chunks, "ms": s.ms}
 
-    def snap_open(self, snap_path, xz=False):
+    def snap_open(self, snap_path, xz=False, chains=False):
         """A session on a .snap file (ClickDeb.Open): see Snap.  xz: ".xz" members are read too (snaphash_snap_open_ex with
-        SNAPHASH_SNAP_XZ); without it they are refused with the reference's "Can not handle" text."""
-        return Snap(self, snap_path, xz=xz)
+        SNAPHASH_SNAP_XZ); without it they are refused with the reference's "Can not handle" text.  chains (with xz): their
+        Blocks may carry every chain unxz_buffer(chains=True) takes (SNAPHASH_SNAP_XZ_CHAINS)."""
+        return Snap(self, snap_path, xz=xz, chains=chains)
 
     def unpack_stats(self):
         s = UnpackStats()
@@ -1022,11 +1077,12 @@ class Context:
 class Snap:
     """snaphash_snap_*: one .snap file read once, its ar members, and its two tars decoded at most once each."""
 
-    def __init__(self, ctx, snap_path, xz=False, _opt=None):
+    def __init__(self, ctx, snap_path, xz=False, _opt=None, chains=False):
         self._ctx = ctx
         h = ctypes.c_void_p()
-        if xz or _opt is not None:  # (_opt: a SnapOpenOptions as it is, for the tests of the entry's refusals)
-            opt = _opt if _opt is not None else SnapOpenOptions(ctypes.sizeof(SnapOpenOptions), SNAP_XZ)
+        if xz or chains or _opt is not None:  # (_opt: a SnapOpenOptions as it is, for the tests of the entry's refusals)
+            flags = (SNAP_XZ if xz else 0) | (SNAP_XZ_CHAINS if chains else 0)
+            opt = _opt if _opt is not None else SnapOpenOptions(ctypes.sizeof(SnapOpenOptions), flags)
             ctx._check(lib().snaphash_snap_open_ex(ctx._h, os.fsencode(snap_path), ctypes.byref(opt), ctypes.byref(h)))
         else:
             ctx._check(lib().snaphash_snap_open(ctx._h, os.fsencode(snap_path), ctypes.byref(h)))

@@ -7,7 +7,7 @@
  *                                      Build's data step fused (clickdeb/deb.go:261-344 + snappy/build.go:517-520):
  *                                      data.tar.gz of BUILD_DIR without DEBIAN/, every file read once, then
  *                                      BUILD_DIR/DEBIAN/hashes.yaml with the archive's digest
- *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] [-L 0|1] BUILD_DIR OUT.tar.xz
+ *   snaphash [options] build-xz [-c] [-B KiB] [-C none|crc32|crc64|sha256] [-F FILTERS] [-L 0|1] BUILD_DIR OUT.tar.xz
  *                                      the same with data.tar.xz (tarCreate's ".xz" branch): Blocks of 1 MiB (or -B), Check
  *                                      CRC-64 (or -C), LZMA2 on the GPU; -c: the LZMA2 self-check on the GPU; -F: a BCJ
  *                                      filter in front of LZMA2, applied on the GPU (what xz writes when XZ_OPT names one)
@@ -17,7 +17,7 @@
  *   snaphash [options] gzip IN OUT.gz            the compressor alone, one gzip member
  *   snaphash [options] bzip2 [-L LEVEL] [-c] IN OUT.bz2   the bzip2 compressor alone, level 1..9 (default 9); -c: the .bz2
  *                                                self-check on the GPU (-s prints what it checked)
- *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] [-L 0|1]
+ *   snaphash [options] xz IN OUT.xz [-B KiB] [-C none|crc32|crc64|sha256] [-c] [-F FILTERS] [-L 0|1]
  *                                                the .xz compressor alone, a Block per KiB of input (default 1024), the
  *                                                Blocks' Check as named (default crc64), taken on the GPU; -c: the LZMA2
  *                                                self-check on the GPU (-s prints what it walked); -F: a BCJ filter
@@ -26,9 +26,10 @@
  *   snaphash [options] unpack DATA_TAR_GZ DIR [HASHES_YAML]
  *   snaphash [options] bunzip2 IN.bz2 OUT        every bzip2 stream decoded (blocks side by side)
  *   snaphash [options] unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML]
- *   snaphash [options] unxz [-F] IN.xz OUT       every .xz Stream decoded (Blocks side by side); -F: Blocks with an x86, ARM
- *                                                or ARM-Thumb filter in front of LZMA2 are taken too (SNAPHASH_UNXZ_BCJ)
- *   snaphash [options] unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML]
+ *   snaphash [options] unxz [-F|-A] IN.xz OUT    every .xz Stream decoded (Blocks side by side); -F: Blocks with an x86, ARM
+ *                                                or ARM-Thumb filter in front of LZMA2 are taken too (SNAPHASH_UNXZ_BCJ);
+ *                                                -A: Blocks with any chain liblzma reads (SNAPHASH_UNXZ_CHAINS)
+ *   snaphash [options] unpack-xz [-F|-A] DATA_TAR_XZ DIR [HASHES_YAML]
  *                                      ClickDeb.Unpack (clickdeb/deb.go:188-203) into DIR; with HASHES_YAML also the
  *                                      install-time Verify from the decoded bytes; exit 1 on mismatch
  *   snaphash [options] snap ls FILE.snap         the ar members of the package: size, offset, name
@@ -38,8 +39,12 @@
  *   snaphash [options] snap unpack DIR FILE.snap ClickDeb.Unpack + Verify against the package's own hashes.yaml;
  *                                      exit 1 on mismatch; -s prints the unpack and session statistics
  *   snaphash [options] snap -x VERB ...          the five verbs above on a package with control.tar.xz / data.tar.xz members
- *                                      (SNAPHASH_SNAP_XZ); without -x such a member is "Can not handle NAME"
- *   snaphash [options] snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F x86|arm|armthumb] [-C none|crc32|crc64|sha256] [-B KiB] DIR OUT.snap
+ *                                      (SNAPHASH_SNAP_XZ); without -x such a member is "Can not handle NAME"; -x -A: their
+ *                                      Blocks may carry any filter chain (SNAPHASH_SNAP_XZ_CHAINS)
+ *   FILTERS (-F of build-xz, xz, snap build): x86 | arm | armthumb (the `filter` field), or a comma list of up to three of
+ *                                      delta:N (N = 1 .. 256), x86, powerpc, ia64, arm, armthumb, sparc: the chain in front of
+ *                                      LZMA2, the Block header's first filter first
+ *   snaphash [options] snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F FILTERS] [-C none|crc32|crc64|sha256] [-B KiB] DIR OUT.snap
  *                                      ClickDeb.Build with writeHashes fused in: DIR (with its DEBIAN/) -> the
  *                                      package, DIR/DEBIAN/hashes.yaml written on the way; prints the SHA-512 of the file
  *                                      (the store's download_sha512); -c: the self-checks on the GPU; -Z: the data member's
@@ -71,16 +76,18 @@ static int usage(void)
 {
     fprintf(stderr, "usage: snaphash [-d DEV,...] [-t HOST_THREADS] [-g] [-b] [-z DEPTH] [-s] hash FILE... | tree DIR TAR | write DIR TAR |\n"
                     "       verify DIR YAML [TAR] | build DIR OUT.tar.gz | gzip IN OUT.gz | gunzip IN.gz OUT |\n"
-                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-F x86|arm|armthumb] [-L 0|1] DIR OUT.tar.xz |\n"
+                    "       build-xz [-c] [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-F FILTERS] [-L 0|1] DIR OUT.tar.xz |\n"
                     "       build-bz2 DIR OUT.tar.bz2 | bzip2 [-L LEVEL] IN OUT.bz2 |\n"
                     "       (in front of their names build-bz2 also takes [-c] [-L LEVEL] and bzip2 [-c]: -c is the .bz2 self-check)\n"
-                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] [-F x86|arm|armthumb] [-L 0|1] |\n"
+                    "       xz IN OUT.xz [-B BLOCK_KiB] [-C none|crc32|crc64|sha256] [-c] [-F FILTERS] [-L 0|1] |\n"
                     "       unpack DATA_TAR_GZ DIR [HASHES_YAML] | bunzip2 IN.bz2 OUT |\n"
                     "       unpack-bz2 DATA_TAR_BZ2 DIR [HASHES_YAML] | unxz [-F] IN.xz OUT |\n"
                     "       unpack-xz [-F] DATA_TAR_XZ DIR [HASHES_YAML] | cmp A B [A B ...] |\n"
-                    "       (-F on the two .xz decoding commands: also take Blocks with a BCJ filter in front of LZMA2)\n"
+                    "       (-F on the two .xz decoding commands: also take Blocks with a BCJ filter in front of LZMA2; -A: with any chain)\n"
+                    "       (FILTERS: x86 | arm | armthumb, or a comma list of up to three of delta:N powerpc ia64 sparc and those)\n"
+                    "       (snap -x -A VERB: .xz members with any filter chain)\n"
                     "       snap [-x] {ls | cat-control NAME | cat-meta NAME | audit | unpack DIR} FILE.snap  (-x: .xz members are read too) |\n"
-                    "       snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F x86|arm|armthumb] [-C none|crc32|crc64|sha256] [-B BLOCK_KiB] DIR OUT.snap |\n"
+                    "       snap build [-c] [-Z gz|xz|bz2] [-L LEVEL] [-F FILTERS] [-C none|crc32|crc64|sha256] [-B BLOCK_KiB] DIR OUT.snap |\n"
                     "       dirupdated DIR_A DIR_B [PREFIX] | plan FILE... (what the planner would do; no device needed)\n"
                     "       -g: every byte through the HIP kernels (SNAPHASH_FLAG_GPU_ONLY); default: every call is planned\n"
                     "       -b: gunzip / unpack also split streams without flush points at their blocks (SNAPHASH_FLAG_SPLIT_BLOCKS)\n"
@@ -110,6 +117,39 @@ static int xz_check_id(const char *w)
 static uint32_t xz_filter_id(const char *w)
 {
     return !strcmp(w, "x86") ? 4u : !strcmp(w, "arm") ? 7u : (!strcmp(w, "armthumb") || !strcmp(w, "thumb")) ? 8u : 0u;
+}
+
+/* -F's word into the options: one of x86 / arm / armthumb sets `filter`, as it always did; anything else is a comma list of up
+ * to three of delta:N (N = 1 .. 256), x86, powerpc, ia64, arm, armthumb, sparc and sets the chain.  0: not such a word */
+static int xz_filter_arg(const char *w, snaphash_xz_options *xo)
+{
+    if ((xo->filter = xz_filter_id(w)) != 0) return 1;
+    uint32_t n = 0;
+    while (*w) {
+        char word[16];
+        size_t len = strcspn(w, ",");
+        if (len == 0 || len >= sizeof word || n == 3) return 0;
+        memcpy(word, w, len);
+        word[len] = 0;
+        uint32_t id = xz_filter_id(word), param = 0;
+        if (!id) id = !strcmp(word, "powerpc") ? 5u : !strcmp(word, "ia64") ? 6u : !strcmp(word, "sparc") ? 9u : 0u;
+        if (!id && !strncmp(word, "delta:", 6)) {
+            char *end = NULL;
+            const unsigned long d = strtoul(word + 6, &end, 10);
+            if (!word[6] || *end || d < 1 || d > 256) return 0;
+            id = 3;
+            param = (uint32_t)d;
+        }
+        if (!id) return 0;
+        xo->chain[n++] = id | param << 8;
+        w += len;
+        if (*w == ',') {
+            if (!w[1]) return 0;
+            w++;
+        }
+    }
+    xo->chain_len = n;
+    return n != 0;
 }
 
 /* the .xz commands' -L: the level, 0 or 1, or -1 */
@@ -197,9 +237,9 @@ int main(int argc, char **argv)
     /* unxz / unpack-xz -F, in front of their names: the _ex entries with SNAPHASH_UNXZ_BCJ */
     snaphash_unxz_options uo;
     memset(&uo, 0, sizeof uo);
-    if ((!strcmp(argv[1], "unxz") || !strcmp(argv[1], "unpack-xz")) && !strcmp(argv[2], "-F")) {
+    if ((!strcmp(argv[1], "unxz") || !strcmp(argv[1], "unpack-xz")) && (!strcmp(argv[2], "-F") || !strcmp(argv[2], "-A"))) {
         uo.struct_size = sizeof uo;
-        uo.flags = SNAPHASH_UNXZ_BCJ;
+        uo.flags = !strcmp(argv[2], "-A") ? SNAPHASH_UNXZ_CHAINS : SNAPHASH_UNXZ_BCJ; /* -A: any chain liblzma reads */
         for (int i = 2; i + 1 < argc; i++) argv[i] = argv[i + 1];
         argc--;
         if (argc < 3) return usage();
@@ -285,7 +325,7 @@ int main(int argc, char **argv)
                 if (xo.block_size == 0) bad = 1;
                 argv += 2; argc -= 2;
             } else if (!strcmp(argv[2], "-C") && argc > 5 && (id = xz_check_id(argv[3])) >= 0) { xo.check = (uint32_t)id; argv += 2; argc -= 2; }
-            else if (!strcmp(argv[2], "-F") && argc > 5 && (xo.filter = xz_filter_id(argv[3])) != 0) { argv += 2; argc -= 2; }
+            else if (!strcmp(argv[2], "-F") && argc > 5 && xz_filter_arg(argv[3], &xo)) { argv += 2; argc -= 2; }
             else if (!strcmp(argv[2], "-L") && argc > 5 && xz_level(argv[3]) >= 0) { xo.level = (uint32_t)xz_level(argv[3]); argv += 2; argc -= 2; }
             else bad = 1;
             xz_ex = 1;
@@ -321,7 +361,7 @@ int main(int argc, char **argv)
         if (rc) ret = die(c, rc, cmd);
         else {
             if (show_stats && (xo.flags & SNAPHASH_XZ_SELF_CHECK)) print_xz_selfcheck(c, cmd);
-            if (show_stats && xo.filter) print_xz_filter(c, cmd);
+            if (show_stats && (xo.filter || xo.chain_len)) print_xz_filter(c, cmd);
             if (show_stats && (bo.flags & SNAPHASH_BZ2_SELF_CHECK)) print_bz2_selfcheck(c, cmd);
             (void)mkdir(excl, 0755); /* os.MkdirAll(debianDir, 0755), error ignored (build.go:218-219) */
             FILE *f = fopen(ypath, "wb");
@@ -375,7 +415,9 @@ int main(int argc, char **argv)
         size_t len = 0, zl = 0;
         uint64_t block = 0;
         int have_block = 0, check = -1, self = 0; /* -1: no -C, the entry point that takes no Check */
-        uint32_t filter = 0, level = 0;
+        uint32_t level = 0;
+        snaphash_xz_options xo;
+        memset(&xo, 0, sizeof xo);
         for (int i = 4; i < argc;) {
             if (!strcmp(argv[i], "-c")) { self = 1; i += 1; continue; }
             if (i + 1 >= argc) { snaphash_destroy(c); return usage(); }
@@ -383,18 +425,16 @@ int main(int argc, char **argv)
                 block = (uint64_t)strtoull(argv[i + 1], NULL, 10) * 1024u;
                 have_block = 1;
             } else if (!strcmp(argv[i], "-C") && xz_check_id(argv[i + 1]) >= 0) check = xz_check_id(argv[i + 1]);
-            else if (!strcmp(argv[i], "-F") && xz_filter_id(argv[i + 1]) != 0) filter = xz_filter_id(argv[i + 1]);
+            else if (!strcmp(argv[i], "-F") && xz_filter_arg(argv[i + 1], &xo)) ;
             else if (!strcmp(argv[i], "-L") && xz_level(argv[i + 1]) >= 0) level = (uint32_t)xz_level(argv[i + 1]);
             else { snaphash_destroy(c); return usage(); }
             i += 2;
         }
-        snaphash_xz_options xo;
-        memset(&xo, 0, sizeof xo);
+        const int filter = xo.filter || xo.chain_len;
         xo.struct_size = sizeof xo;
         xo.flags = self ? SNAPHASH_XZ_SELF_CHECK : 0;
         xo.block_size = block;
         xo.check = check < 0 ? 4u : (uint32_t)check;
-        xo.filter = filter;
         xo.level = level;
         char *in = slurp(argv[2], &len);
         if (!in) { snaphash_destroy(c); return 2; }
@@ -480,7 +520,7 @@ int main(int argc, char **argv)
             } else if (!strcmp(argv[3], "-L")) level = argv[4];
             else if (!strcmp(argv[3], "-B")) { xo.block_size = (uint64_t)strtoull(argv[4], NULL, 10) * 1024u; bad = xo.block_size == 0; xz_opts = 1; }
             else if (!strcmp(argv[3], "-C") && (id = xz_check_id(argv[4])) >= 0) { xo.check = (uint32_t)id; xz_opts = 1; }
-            else if (!strcmp(argv[3], "-F") && (xo.filter = xz_filter_id(argv[4])) != 0) xz_opts = 1;
+            else if (!strcmp(argv[3], "-F") && xz_filter_arg(argv[4], &xo)) xz_opts = 1;
             else bad = 1;
             argv += 2; argc -= 2;
         }
@@ -503,13 +543,14 @@ int main(int argc, char **argv)
                                     "container %.1f ms, wall %.1f ms; self-check: %llu chunks, %.3f ms\n",
                             (unsigned long long)bs.snap_bytes, member, (unsigned long long)bs.data_bytes, (unsigned long long)bs.tar_bytes, (unsigned long long)bs.members,
                             (unsigned long long)bs.control_bytes, bs.data_ms, bs.control_ms, bs.ar_ms, bs.wall_ms, (unsigned long long)bs.check_chunks, bs.check_ms);
-                if (show_stats && opt.data_codec == SNAPHASH_DATA_XZ && xo.filter) print_xz_filter(c, "snap build");
+                if (show_stats && opt.data_codec == SNAPHASH_DATA_XZ && (xo.filter || xo.chain_len)) print_xz_filter(c, "snap build");
             }
         }
     } else if (!strcmp(argv[1], "snap") && argc >= 4) {
         /* -x in front of the verb: the session routes .xz members to the .xz engine */
         snaphash_snap_open_options so = {sizeof so, 0};
         if (!strcmp(argv[2], "-x")) { so.flags = SNAPHASH_SNAP_XZ; argv++; argc--; }
+        if (so.flags && argc >= 4 && !strcmp(argv[2], "-A")) { so.flags |= SNAPHASH_SNAP_XZ_CHAINS; argv++; argc--; } /* -x -A: any chain */
         const char *verb = argv[2], *file = argv[argc - 1];
         const int takes_arg = !strcmp(verb, "cat-control") || !strcmp(verb, "cat-meta") || !strcmp(verb, "unpack");
         const int known = takes_arg || !strcmp(verb, "ls") || !strcmp(verb, "audit");

@@ -47,13 +47,13 @@ def UnpackBz2(dataTarBz2, targetDir, hashesYaml=None, ctx=None):
     return mismatch
 
 
-def UnpackXz(dataTarXz, targetDir, hashesYaml=None, ctx=None, bcj=False):
+def UnpackXz(dataTarXz, targetDir, hashesYaml=None, ctx=None, bcj=False, chains=False):
     """ClickDeb.Unpack of a package whose data member is data.tar.xz (skipToArMember's ".xz" branch, clickdeb/deb.go:
     408-441): the same rules, errors and Verify as Unpack, from the xz-decoded stream.  A filter chain or Check the
     decoder does not take raises SnaphashError with code EINVAL.  bcj: Blocks with an x86, ARM or ARM-Thumb filter in front
-    of LZMA2 are taken too (what tarCreate(..., filter=) writes).
+    of LZMA2 are taken too (what tarCreate(..., filter=) writes); chains: every chain liblzma reads.
     -> None, or (kind, name) of the first mismatch against hashesYaml."""
-    mismatch, _ = (ctx or default_context()).tar_unpack_xz(dataTarXz, targetDir, hashesYaml, bcj=bcj)
+    mismatch, _ = (ctx or default_context()).tar_unpack_xz(dataTarXz, targetDir, hashesYaml, bcj=bcj, chains=chains)
     return mismatch
 
 
@@ -65,10 +65,11 @@ class ClickDeb:
         self._snap = snap
 
     @classmethod
-    def open(cls, path, ctx=None, xz=False):
+    def open(cls, path, ctx=None, xz=False, chains=False):
         """xz: control.tar.xz / data.tar.xz members are read too, through the library's .xz engine (the reference pipes them
-        through the xz tool); without it they raise SnaphashError EINVAL "Can not handle ...", as they always did."""
-        return cls((ctx or default_context()).snap_open(path, xz=xz))
+        through the xz tool); without it they raise SnaphashError EINVAL "Can not handle ...", as they always did.  chains
+        (with xz): their Blocks may carry any filter chain liblzma reads, Delta, PowerPC, IA64 and SPARC among them."""
+        return cls((ctx or default_context()).snap_open(path, xz=xz, chains=chains))
 
     @classmethod
     def create(cls, path, ctx=None):

@@ -1,4 +1,5 @@
-// bcj_kernels.hip -- the .xz format's BCJ filters (x86, ARM, ARM-Thumb) over byte ranges resident in HBM, for gfx950.
+// bcj_kernels.hip -- the .xz format's BCJ filters (x86, PowerPC, IA64, ARM, ARM-Thumb, SPARC) over byte ranges resident in
+// HBM, for gfx950, and the launcher of one stage of a filter chain (Delta's kernels: delta_kernels.hip).
 //
 // On the build side the filter stands between the staging copy and lzma_chains_kernel (xzpack.inc); on the install side,
 // under SNAPHASH_FLAG_GPU_ONLY, between lzma2_blocks_kernel and the Check kernels (unxz.inc).  A range is a Block: positions
@@ -8,7 +9,7 @@
 //                       in front hold no 0xE8 / 0xE9), or none.  Reads only.
 //   bcj_apply_kernel    a lane a stretch.  x86: a stretch with a point owns the walk from it to the next owner's point
 //                       (found by reading the points of the stretches behind; every gap is read by one owner, so the work
-//                       is linear); a stretch without one returns.  ARM, Thumb: the stretch's words, each by its own bytes.
+//                       is linear); a stretch without one returns.  The other five: the stretch's words (IA64: bundles), each by its own bytes.
 //                       In place: no walk writes at or past the next owner's point, and a word's conversion leaves the
 //                       bits its neighbours test as they are.
 // Two launches, because the second writes what the first reads across stretch borders.
@@ -59,19 +60,36 @@ __global__ __launch_bounds__(kBcjLanes) void bcj_apply_kernel(uint8_t* base, con
 
 } // namespace
 
-hipError_t launch_bcj_ranges(uint8_t* d_base, const BcjRange* d_ranges, uint32_t n, uint32_t units, uint32_t* d_points, bool any_x86,
-                             hipStream_t s)
+hipError_t launch_xz_filter_stage(const XzFilterStage& t, bool encode, hipStream_t s)
 {
-    if (n == 0 || units == 0) return hipSuccess;
-    const uint32_t tiles = (units + kBcjLanes - 1) / kBcjLanes;
-    const uint32_t grid = tiles < 4096 ? tiles : 4096; // 256 CUs x 16 workgroups; the rest by the grid-stride loops
-    if (any_x86) {
-        hipLaunchKernelGGL(bcj_points_kernel, dim3(grid), dim3(kBcjLanes), 0, s, d_base, d_ranges, n, units, d_points);
+    if (t.n == 0 || t.units == 0) return hipSuccess;
+    if (t.any_bcj) {
+        const uint32_t tiles = (t.units + kBcjLanes - 1) / kBcjLanes;
+        const uint32_t grid = tiles < 4096 ? tiles : 4096; // 256 CUs x 16 workgroups; the rest by the grid-stride loops
+        if (t.any_x86) {
+            hipLaunchKernelGGL(bcj_points_kernel, dim3(grid), dim3(kBcjLanes), 0, s, t.d_base, t.d_ranges, t.n, t.units, t.d_points);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(bcj_apply_kernel, dim3(grid), dim3(kBcjLanes), 0, s, t.d_base, t.d_ranges, t.n, t.units, t.d_points);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(bcj_apply_kernel, dim3(grid), dim3(kBcjLanes), 0, s, d_base, d_ranges, n, units, d_points);
-    return hipGetLastError();
+    return launch_delta_ranges(t, encode, s); // (a range is one or the other: the two sets of kernels touch different ranges)
+}
+
+hipError_t launch_bcj_ranges(uint8_t* d_base, const BcjRange* d_ranges, uint32_t n, uint32_t units, uint32_t* d_points, bool any_x86,
+                             hipStream_t s)
+{
+    XzFilterStage t{};
+    t.d_base = d_base;
+    t.d_ranges = d_ranges;
+    t.n = n;
+    t.units = units;
+    t.d_points = d_points;
+    t.any_x86 = any_x86;
+    t.any_bcj = true;
+    return launch_xz_filter_stage(t, false, s); // (no Delta range: the direction is each range's own)
 }
 
 } // namespace snaphash

@@ -271,6 +271,8 @@ struct Sha256Bufs {
 struct BcjBufs {
     Twin<BcjRange> ranges;
     DevBuf<uint32_t> d_points;
+    Twin<uint32_t> tile0;     // Delta's: the ranges' first tiles, and kDeltaTail bytes a tile (ensure_delta; empty otherwise)
+    DevBuf<uint8_t> d_delta;
     hipError_t ensure(size_t n, size_t units)
     {
         hipError_t e = ranges.ensure(n + 1);
@@ -278,7 +280,14 @@ struct BcjBufs {
         if (e) each(Release());
         return e;
     }
-    template <class F> void each(F&& f) { ranges.each(f); f(d_points); }
+    hipError_t ensure_delta(size_t n, size_t tiles)
+    {
+        hipError_t e = tile0.ensure(n + 1);
+        if (!e) e = d_delta.reserve(std::max<size_t>(tiles, 1) * kDeltaTail);
+        if (e) each(Release());
+        return e;
+    }
+    template <class F> void each(F&& f) { ranges.each(f); f(d_points); tile0.each(f); f(d_delta); }
 };
 
 // GPU LZMA2 (unxz.inc): the whole .xz file and the Blocks the kernel takes

@@ -19,6 +19,7 @@ struct snaphash_snap {
     std::vector<uint8_t> file;
     std::vector<ArMember> mem;
     bool xz = false; // SNAPHASH_SNAP_XZ: ".xz" members go to kUnxzCodec
+    bool xz_chains = false; // SNAPHASH_SNAP_XZ_CHAINS: and may carry every chain SNAPHASH_UNXZ_CHAINS takes
     struct Tar {
         bool tried = false;
         int rc = 0;            // of the decode and tar_read
@@ -61,6 +62,7 @@ int snap_tar(snaphash_snap* s, snaphash_snap::Tar& t, const char* prefix, bool k
         DecodedStream ds(c, t.tar, keep_dev);
         UnxzCall xz_call(x); // an .xz member: one BCJ filter in front of LZMA2 is taken, as the xz tool the reference pipes through takes it
         if (codec == kSnapXz) xz_call.allow_bcj();
+        if (codec == kSnapXz && s->xz_chains) xz_call.allow_chains();
         // under SNAPHASH_FLAG_GPU_ONLY the stream reaches HBM before host memory: the CRCs are taken there
         t.rc = kSnapCodecs[codec]->decode(x, c, z, zn, ds, t.st, x->gpu_only ? CrcAt::Device : CrcAt::Host, &s->tally);
         scratch_spans_done(c);
@@ -139,12 +141,14 @@ try {
     uint32_t flags = 0;
     if (opt && (opt->struct_size || opt->flags)) { // (all zero: snaphash_snap_open)
         if (opt->struct_size < sizeof(snaphash_snap_open_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_snap_open_options.struct_size");
-        if (opt->flags & ~(uint32_t)SNAPHASH_SNAP_XZ) return fail(x, SNAPHASH_EINVAL, "snap: unknown flag");
+        if (opt->flags & ~(uint32_t)(SNAPHASH_SNAP_XZ | SNAPHASH_SNAP_XZ_CHAINS)) return fail(x, SNAPHASH_EINVAL, "snap: unknown flag");
+        if ((opt->flags & SNAPHASH_SNAP_XZ_CHAINS) && !(opt->flags & SNAPHASH_SNAP_XZ)) return fail(x, SNAPHASH_EINVAL, "snap: SNAPHASH_SNAP_XZ_CHAINS needs SNAPHASH_SNAP_XZ");
         flags = opt->flags;
     }
     std::unique_ptr<snaphash_snap> s(new snaphash_snap);
     s->x = x;
     s->xz = (flags & SNAPHASH_SNAP_XZ) != 0;
+    s->xz_chains = (flags & SNAPHASH_SNAP_XZ_CHAINS) != 0;
     s->path = snap_path;
     s->stats.struct_size = sizeof s->stats;
     int rc = read_whole(x, snap_path, s->file);

@@ -188,7 +188,8 @@ try {
     // the data member's encoder is this call's own, made with this call's options: nothing of it outlives the call
     if (codec == SNAPHASH_DATA_XZ) {
         uint64_t bs;
-        uint32_t chk, filter, level;
+        uint32_t chk, level;
+        XzEncChain filter;
         bool self;
         int rc = xz_read_options(x, xo, &bs, &chk, &self, &filter, &level);
         if (rc) return rc;

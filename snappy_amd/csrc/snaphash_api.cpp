@@ -184,6 +184,7 @@ struct snaphash_ctx {
     snaphash_xz_selfcheck_stats xz_selfcheck{}; // of the most recent snaphash_xz_buffer_ex / snaphash_tar_create_xz_ex (xzpack.inc)
     snaphash_xz_filter_stats xz_filter{}; // of the most recent .xz call of either side that knows filters (xzpack.inc, unxz.inc)
     bool unxz_bcj = false; // SNAPHASH_UNXZ_BCJ of the _ex decode in progress (unxz.inc)
+    bool unxz_chains = false; // SNAPHASH_UNXZ_CHAINS of it
     snaphash_bz2_selfcheck_stats bz2_selfcheck{}; // of the most recent snaphash_bzip2_buffer_ex / snaphash_tar_create_bz2_ex (bzpack.inc)
     snaphash_block_scan_stats block_scan{};
     std::string last_error;
@@ -2486,24 +2487,34 @@ int sha256_ranges_dev(DevCtx* c, const uint8_t* d_base, const uint64_t* offs, co
     return SNAPHASH_OK;
 }
 
-// A BCJ filter over n ranges of d_base, each a Block of its own, in place, queued on stream s and NOT waited for: r[i]'s off,
-// len, filter, start and encode as the caller set them (unit0 is filled in here).  *ev: the pair of events around the
-// kernels, for the caller to read once it has waited for s.  The table lies in c->bcj until the stream has passed it: a
-// second call before that waits for s first.
-int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStream_t s, const Span* ev)
+const char kXzFilterArgs[] = "xz filter: the id is 3 (Delta, its distance 1 .. 256) or 4 .. 9 (a BCJ filter, its start_offset a multiple of 1, 4, 16, 4, 2, 4)";
+bool xz_filter_args_valid(uint32_t id, uint32_t param) // param: Delta's distance, a BCJ filter's start_offset
+{
+    return id == kXzDelta ? delta_dist_valid(param) : xz_filter_valid(id) && (param & (bcj_alignment(id) - 1)) == 0;
+}
+
+// One stage of a filter chain over n ranges of d_base, each a Block of its own, in place, queued on stream s and NOT waited
+// for: r[i]'s off, len, filter, start (a Delta range's distance) and encode as the caller set them (unit0 is filled in here);
+// filter 0: the range has nothing at this stage.  Every Delta range runs in `encode`'s direction.  *ev and the table: as
+// bcj_ranges_dev's.  *launches: the kernels queued.
+int xz_filter_stage_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, bool encode, hipStream_t s, const Span* ev, uint32_t* launches)
 {
     const size_t n = r.size();
+    if (launches) *launches = 0;
     if (n == 0) return SNAPHASH_OK;
-    if (n >= 0xffffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
-    uint64_t units = 0;
-    bool any_x86 = false;
+    if (n >= 0x7fffffffull) return fail(c, SNAPHASH_EINVAL, "too many ranges");
+    uint64_t units = 0, tiles = 0;
+    XzFilterStage t{};
     for (size_t i = 0; i < n; ++i) {
         if (r[i].len > ~0ull - r[i].off) return fail(c, SNAPHASH_EINVAL, "a range wraps around the address space");
-        if (!bcj_filter_valid(r[i].filter) || (r[i].start & (bcj_alignment(r[i].filter) - 1))) return fail(c, SNAPHASH_EINVAL, "bcj: the filter is 4 (x86), 7 (ARM) or 8 (ARM-Thumb), its start_offset a multiple of 1, 4 or 2");
+        if (r[i].filter && !xz_filter_args_valid(r[i].filter, r[i].start)) return fail(c, SNAPHASH_EINVAL, kXzFilterArgs);
         r[i].unit0 = (uint32_t)units;
         units += (r[i].len + kBcjStretch - 1) / kBcjStretch;
         if (units > (1ull << 32) - 1) return fail(c, SNAPHASH_EINVAL, "bcj: more than 2^40 bytes in one call");
-        any_x86 |= r[i].filter == kBcjX86;
+        if (r[i].len == 0) continue;
+        t.any_x86 |= r[i].filter == kBcjX86;
+        t.any_bcj |= r[i].filter != 0 && r[i].filter != kXzDelta;
+        t.any_delta |= r[i].filter == kXzDelta;
     }
     if (c->bcj_busy) HIP_TRY(c, hipStreamSynchronize(c->bcj_busy));
     HIP_TRY(c, c->bcj.ensure(n, (size_t)units));
@@ -2512,10 +2523,39 @@ int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStre
     h[n] = BcjRange{0, 0, (uint32_t)units, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(c->bcj.ranges.d.data(), h, (n + 1) * sizeof(BcjRange), hipMemcpyHostToDevice, s));
     c->bcj_busy = s;
+    if (t.any_delta) {
+        for (size_t i = 0; i < n; ++i) tiles += (r[i].len + kDeltaTile - 1) / kDeltaTile; // (units fit 32 bits: so do these)
+        HIP_TRY(c, c->bcj.ensure_delta(n, (size_t)tiles));
+        uint32_t* t0 = c->bcj.tile0.h.data();
+        uint64_t at = 0;
+        for (size_t i = 0; i < n; ++i) {
+            t0[i] = (uint32_t)at;
+            at += (r[i].len + kDeltaTile - 1) / kDeltaTile;
+        }
+        t0[n] = (uint32_t)at;
+        HIP_TRY(c, hipMemcpyAsync(c->bcj.tile0.d.data(), t0, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        t.d_tile0 = c->bcj.tile0.d.data();
+        t.tiles = (uint32_t)tiles;
+        t.d_delta = c->bcj.d_delta.data();
+    }
+    t.d_base = d_base;
+    t.d_ranges = c->bcj.ranges.d.data();
+    t.n = (uint32_t)n;
+    t.units = (uint32_t)units;
+    t.d_points = c->bcj.d_points.data();
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, s));
-    HIP_TRY(c, launch_bcj_ranges(d_base, c->bcj.ranges.d.data(), (uint32_t)n, (uint32_t)units, c->bcj.d_points.data(), any_x86, s));
+    HIP_TRY(c, launch_xz_filter_stage(t, encode, s));
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, s));
+    if (launches) *launches = units ? xz_filter_stage_launches(t, encode) : 0;
     return SNAPHASH_OK;
+}
+
+// A BCJ filter of sec. 25 (x86, ARM, ARM-Thumb) over n ranges: xz_filter_stage_dev with the callers' ids held to those three.
+int bcj_ranges_dev(DevCtx* c, uint8_t* d_base, std::vector<BcjRange>& r, hipStream_t s, const Span* ev)
+{
+    for (const BcjRange& x : r)
+        if (!bcj_filter_valid(x.filter) || (x.start & (bcj_alignment(x.filter) - 1))) return fail(c, SNAPHASH_EINVAL, "bcj: the filter is 4 (x86), 7 (ARM) or 8 (ARM-Thumb), its start_offset a multiple of 1, 4 or 2");
+    return xz_filter_stage_dev(c, d_base, r, false, s, ev, nullptr);
 }
 
 } // namespace
@@ -2551,6 +2591,36 @@ try {
     if (ran) (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     x->stats.kernel_ms = ms;
     x->stats.launches = ran ? (any_x86 ? 2 : 1) : 0;
+    end_top(x, t_top0_);
+    return SNAPHASH_OK;
+} catch (...) { // allocation failure: no C++ exception crosses the C boundary
+    return SNAPHASH_ENOMEM;
+}
+
+int snaphash_xz_filter_device(snaphash_ctx* x, uint32_t id, uint32_t param, int encode, void* d_base, const uint64_t* offsets, const uint64_t* lens,
+                              size_t n, uint32_t start_offset)
+try {
+    if (!x || (n && (!d_base || !offsets || !lens))) return fail(x, SNAPHASH_EINVAL, "bad argument");
+    if (id == kXzDelta ? !delta_dist_valid(param) || start_offset != 0 : param != 0 || !xz_filter_args_valid(id, start_offset))
+        return fail(x, SNAPHASH_EINVAL, kXzFilterArgs);
+    TOP_ENTER(x);
+    DevCtx* c = x->d0(); // resident data lives on one device: the ctx's first engine
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<BcjRange> r(n);
+    for (size_t i = 0; i < n; ++i) r[i] = BcjRange{offsets[i], lens[i], 0, id, id == kXzDelta ? param : start_offset, encode ? 1u : 0u};
+    Span ev;
+    int rc = span_take(c, Ev::Codec, &ev);
+    if (rc) return lift(x, c, rc);
+    uint32_t launches = 0;
+    rc = xz_filter_stage_dev(c, (uint8_t*)d_base, r, encode != 0, c->stream, &ev, &launches);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    scratch_spans_done(c);
+    if (rc) return lift(x, c, rc);
+    HIP_TRY(c, e);
+    float ms = 0;
+    if (launches) (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    x->stats.kernel_ms = ms;
+    x->stats.launches = launches;
     end_top(x, t_top0_);
     return SNAPHASH_OK;
 } catch (...) { // allocation failure: no C++ exception crosses the C boundary

@@ -9,6 +9,8 @@
 // the decoded stream goes through the same unpack and in-pass Verify as data.tar.gz.  The _ex entries' SNAPHASH_UNXZ_BCJ
 // also takes Blocks with an x86, ARM or ARM-Thumb filter in front of LZMA2 (DESIGN.md sec. 25): the filter is undone behind
 // the Block's decode and in front of its Check, by the Block's host thread or by bcj_kernels.hip over what the kernel decoded.
+// SNAPHASH_UNXZ_CHAINS takes every chain liblzma 5.2.5 reads (sec. 29): up to three of Delta and the six BCJ filters, undone
+// the same way, a stage of the filter kernels a place in the chain.
 
 namespace {
 
@@ -37,7 +39,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
     uint64_t total = 0;
     std::string why;
     x->xz_filter = snaphash_xz_filter_stats{};
-    const int pe = xz_plan(xz, n, blocks, &total, why, x->unxz_bcj); // (the _ex entries' SNAPHASH_UNXZ_BCJ: a BCJ filter a Block)
+    const int pe = xz_plan(xz, n, blocks, &total, why, x->unxz_chains ? kXzChainAny : x->unxz_bcj ? kXzChainBcj : kXzChainNone); // (the _ex entries' flags)
     if (pe) return fail(c, pe == kXzPlanUnsupported ? SNAPHASH_EINVAL : SNAPHASH_EFORMAT, why);
     c->fout_gen++;
     snaphash_xz_filter_stats& fs = x->xz_filter; // who undid the Blocks' filters
@@ -45,7 +47,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
         const size_t K = which ? which->size() : blocks.size();
         for (size_t k = 0; k < K; ++k) {
             const XzBlock& b = blocks[which ? (*which)[k] : k];
-            if (b.bcj) { fs.host_blocks++; fs.filter = b.bcj; }
+            if (b.nfilt) { fs.host_blocks++; fs.filter = b.filt[0]; } // (a Block counts once, by the filter its header names first)
         }
     };
     snaphash_xz_check_stats& ck = x->xz_check; // who took the Checks of this decode
@@ -109,20 +111,32 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
             if (blocks[gpu[k]].check == kXzCheckCrc64) k64.push_back(gpu[k]);
             if (blocks[gpu[k]].check == kXzCheckSha256) k256.push_back(gpu[k]);
         }
-        // the filters of what the kernel decoded, undone in HBM in one launch of the BCJ kernels, a range a Block: in front of
-        // the Checks, which are over the unfiltered bytes, and of the copies back
-        std::vector<BcjRange> fr;
-        for (uint32_t i : ok)
-            if (blocks[i].bcj) {
-                fr.push_back(BcjRange{base + blocks[i].out_off, blocks[i].out_len, 0, blocks[i].bcj, blocks[i].bcj_start, 0});
-                fs.filter = blocks[i].bcj;
-            }
-        if (!fr.empty()) {
+        // the filters of what the kernel decoded, undone in HBM, a range a Block: in front of the Checks, which are over the
+        // unfiltered bytes, and of the copies back.  A chain of k filters is k stages over the table (sec. 29), the filter
+        // nearest LZMA2 first; a Block whose chain is shorter has no filter at the later stages and is skipped there
+        uint32_t stages = 0;
+        size_t filtered = 0;
+        for (uint32_t i : ok) {
+            stages = std::max(stages, blocks[i].nfilt);
+            if (blocks[i].nfilt) { filtered++; fs.filter = blocks[i].filt[0]; }
+        }
+        if (stages) {
             if (c->bcj_ev[0].ensure() != hipSuccess || c->bcj_ev[1].ensure() != hipSuccess) return fail(c, SNAPHASH_EDEVICE, "hipEventCreate failed");
-            const Span fev{c->bcj_ev[0], c->bcj_ev[1]};
-            rc = bcj_ranges_dev(c, c->inf.d_out.data(), fr, c->f_stream, &fev);
-            if (rc) return rc;
-            fs.device_blocks = fr.size();
+            HIP_TRY(c, hipEventRecord(c->bcj_ev[0], c->f_stream));
+            std::vector<BcjRange> fr;
+            for (uint32_t j = 0; j < stages; ++j) {
+                fr.clear();
+                for (uint32_t i : ok) {
+                    const XzBlock& b = blocks[i];
+                    if (!b.nfilt) continue;
+                    const bool has = b.nfilt > j;
+                    fr.push_back(BcjRange{base + b.out_off, b.out_len, 0, has ? b.filt[b.nfilt - 1 - j] : 0u, has ? b.fparam[b.nfilt - 1 - j] : 0u, 0});
+                }
+                rc = xz_filter_stage_dev(c, c->inf.d_out.data(), fr, false, c->f_stream, nullptr, nullptr);
+                if (rc) return rc;
+            }
+            HIP_TRY(c, hipEventRecord(c->bcj_ev[1], c->f_stream));
+            fs.device_blocks = filtered;
         }
         // the bytes of the Blocks the kernel decoded on their way back (neighbours in one copy), beside the Check kernels;
         // what a host thread will decode is not moved
@@ -169,7 +183,7 @@ int unxz_engine(snaphash_ctx* x, DevCtx* c, const uint8_t* xz, size_t n, Decoded
         }
         HIP_TRY(c, hipStreamSynchronize(c->f_stream)); // (the bytes are back: the Check calls waited on the same stream, but there may be none)
         st.inflate_ms += cms;
-        if (!fr.empty()) {
+        if (stages) {
             const float fms = span_ms(Span{c->bcj_ev[0], c->bcj_ev[1]});
             fs.device_ms = fms;
             st.inflate_ms += fms;
@@ -209,14 +223,16 @@ const UnpackCodec kUnxzCodec = {"xz", unxz_engine};
 struct UnxzCall {
     snaphash_ctx* const x;
     explicit UnxzCall(snaphash_ctx* x_) : x(x_) {}
-    ~UnxzCall() { x->unxz_bcj = false; }
+    ~UnxzCall() { x->unxz_bcj = x->unxz_chains = false; }
     void allow_bcj() { x->unxz_bcj = true; } // (a .snap session opened with SNAPHASH_SNAP_XZ, snap.inc)
+    void allow_chains() { x->unxz_chains = true; } // (and with SNAPHASH_SNAP_XZ_CHAINS)
     int read(const snaphash_unxz_options* opt)
     {
         if (!opt || (opt->struct_size == 0 && opt->flags == 0)) return SNAPHASH_OK;
         if (opt->struct_size < sizeof(snaphash_unxz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_unxz_options.struct_size");
-        if (opt->flags & ~(uint32_t)SNAPHASH_UNXZ_BCJ) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
+        if (opt->flags & ~(uint32_t)(SNAPHASH_UNXZ_BCJ | SNAPHASH_UNXZ_CHAINS)) return fail(x, SNAPHASH_EINVAL, "xz: unknown flag");
         x->unxz_bcj = (opt->flags & SNAPHASH_UNXZ_BCJ) != 0;
+        x->unxz_chains = (opt->flags & SNAPHASH_UNXZ_CHAINS) != 0;
         return SNAPHASH_OK;
     }
 };

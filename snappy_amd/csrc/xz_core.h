@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "bcj_core.h"
+#include "delta_core.h"
 
 namespace snaphash {
 
@@ -430,7 +431,24 @@ struct XzBlock {
     uint32_t dict_size = 0;
     uint32_t bcj = 0;       // the BCJ filter in front of LZMA2 (kBcjX86 / kBcjArm / kBcjThumb), 0: none; only xz_plan(allow_bcj)
     uint32_t bcj_start = 0; // sets it, with the filter's start_offset
+    // the chain in front of LZMA2 as the header names it, first filter first (xz_plan with kXzChainBcj: at most the one above;
+    // with kXzChainAny: up to three of Delta and the six BCJ filters).  fparam: a BCJ filter's start_offset, Delta's distance
+    uint32_t nfilt = 0;
+    uint32_t filt[3] = {0, 0, 0};
+    uint32_t fparam[3] = {0, 0, 0};
 };
+
+// which filter chains xz_block_header and xz_plan take beside one LZMA2 (a bool converts: false / true are the first two)
+enum : int { kXzChainNone = 0, kXzChainBcj = 1, kXzChainAny = 2 };
+
+// A Block's chain undone on one thread, in place: the filter nearest LZMA2 first
+inline void xz_chain_undo(const XzBlock& b, uint8_t* out)
+{
+    for (uint32_t k = b.nfilt; k-- > 0;) {
+        if (b.filt[k] == kXzDelta) delta_block(false, out, b.out_len, b.fparam[k]);
+        else bcj_block(b.filt[k], false, out, b.out_len, b.fparam[k]);
+    }
+}
 
 inline uint32_t xz_check_size(uint32_t id) { return id == 0 ? 0 : id <= 3 ? 4 : id <= 6 ? 8 : id <= 9 ? 16 : id <= 12 ? 32 : 64; }
 
@@ -474,8 +492,12 @@ inline uint32_t xz_dict_size(uint32_t b) { return b == 40 ? 0xffffffffu : (2u | 
 // for a filter chain other than one LZMA2 -- or, with allow_bcj, other than one LZMA2 or one BCJ filter (x86, ARM, Thumb)
 // in front of one LZMA2: *bcj / *bcj_start then say which (0: none).  Such a filter's properties are 0 bytes or 4 (its
 // start_offset, a multiple of the filter's alignment); liblzma refuses anything else, and so does this: kXzPlanFormat.
+// With chains == kXzChainAny (and chain != nullptr) every chain liblzma 5.2.5 reads: up to three of Delta (0x03, one byte of
+// properties: the distance less one) and the BCJ filters 0x04 .. 0x09 in any order in front of one LZMA2; *chain's nfilt,
+// filt and fparam then hold it (with kXzChainBcj too), and *bcj / *bcj_start a chain of one of x86, ARM, Thumb as before.
 inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t* hdr, uint64_t* csize, uint64_t* usize, uint32_t* dict,
-                           std::string& why, bool allow_bcj = false, uint32_t* bcj = nullptr, uint32_t* bcj_start = nullptr)
+                           std::string& why, int chains = kXzChainNone, uint32_t* bcj = nullptr, uint32_t* bcj_start = nullptr,
+                           XzBlock* chain = nullptr)
 {
     if (at >= end || p[at] == 0) return kXzPlanFormat;
     const uint64_t hs = ((uint64_t)p[at] + 1) * 4;
@@ -498,6 +520,7 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     uint32_t dict_byte = 0;
     uint32_t others = 0; // the filters that are not LZMA2
     uint64_t first_id = 0, first_ps = 0, first_at = 0;
+    uint64_t ids[4] = {0, 0, 0, 0}, pss[4] = {0, 0, 0, 0}, ats[4] = {0, 0, 0, 0};
     for (uint32_t f = 0; f < nf; ++f) {
         uint64_t id, ps;
         if (!xz_vli(p, &q, he, &id) || !xz_vli(p, &q, he, &ps) || ps > he - q) return kXzPlanFormat;
@@ -505,6 +528,7 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
         if (id != 0x21 && !unsupported) { unsupported = true; bad_id = id; }
         others += id != 0x21;
         if (f == 0) { first_id = id; first_ps = ps; first_at = q; }
+        ids[f] = id; pss[f] = ps; ats[f] = q;
         if (id == 0x21) {
             if (f + 1 != nf || ps != 1) return kXzPlanFormat; // LZMA2 is the last filter and has one byte of properties
             dict_byte = p[q];
@@ -515,13 +539,38 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     for (; q < he; ++q)
         if (p[q]) return kXzPlanFormat;
     if (bcj) *bcj = *bcj_start = 0;
-    if (unsupported && allow_bcj && bcj && nf == 2 && others == 1 && bcj_filter_valid((uint32_t)first_id)) {
+    if (chain) chain->nfilt = 0;
+    if (unsupported && chains == kXzChainAny && bcj && chain && others == nf - 1) { // (LZMA2 is there, and the loop held it to the last place)
+        bool known = true;
+        for (uint32_t f = 0; f + 1 < nf && known; ++f)
+            if (!xz_filter_valid((uint32_t)(ids[f] < 64 ? ids[f] : 0))) { known = false; bad_id = ids[f]; } // (the first one this library lacks is named)
+        if (known) {
+            for (uint32_t f = 0; f + 1 < nf; ++f) {
+                uint32_t param;
+                if (ids[f] == kXzDelta) {
+                    if (pss[f] != 1) return kXzPlanFormat;
+                    param = (uint32_t)p[ats[f]] + 1;
+                } else {
+                    if (pss[f] != 0 && pss[f] != 4) return kXzPlanFormat;
+                    param = pss[f] ? xz_le32(p + ats[f]) : 0;
+                    if (param & (bcj_alignment((uint32_t)ids[f]) - 1)) return kXzPlanFormat;
+                }
+                chain->filt[f] = (uint32_t)ids[f];
+                chain->fparam[f] = param;
+            }
+            chain->nfilt = nf - 1;
+            if (nf == 2 && bcj_filter_valid(chain->filt[0])) { *bcj = chain->filt[0]; *bcj_start = chain->fparam[0]; }
+            unsupported = false;
+        }
+    }
+    if (unsupported && chains == kXzChainBcj && bcj && nf == 2 && others == 1 && bcj_filter_valid((uint32_t)first_id)) {
         // (the second is LZMA2: it is not among `others`)
         if (first_ps != 0 && first_ps != 4) return kXzPlanFormat;
         const uint32_t start = first_ps ? xz_le32(p + first_at) : 0;
         if (start & (bcj_alignment((uint32_t)first_id) - 1)) return kXzPlanFormat;
         *bcj = (uint32_t)first_id;
         *bcj_start = start;
+        if (chain) { chain->nfilt = 1; chain->filt[0] = *bcj; chain->fparam[0] = start; }
         unsupported = false;
     }
     if (unsupported) { // (the first one is named: one is enough to hand the file back)
@@ -535,8 +584,8 @@ inline int xz_block_header(const uint8_t* p, uint64_t at, uint64_t end, uint64_t
     return kXzPlanOk;
 }
 
-// Every Block of every Stream of p[0 .. n), in order, and the length of the whole result.  allow_bcj: as in xz_block_header.
-inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, uint64_t* total, std::string& why, bool allow_bcj = false)
+// Every Block of every Stream of p[0 .. n), in order, and the length of the whole result.  chains: as in xz_block_header.
+inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, uint64_t* total, std::string& why, int chains = kXzChainNone)
 {
     blocks.clear();
     *total = 0;
@@ -606,10 +655,10 @@ inline int xz_plan(const uint8_t* p, uint64_t n, std::vector<XzBlock>& blocks, u
             uint64_t hdr = 0, hc = 0, hu = 0;
             uint32_t dict = 0;
             uint32_t bcj = 0, bcj_start = 0;
-            const int e = xz_block_header(p, at, s.index_at, &hdr, &hc, &hu, &dict, why, allow_bcj, &bcj, &bcj_start);
+            XzBlock b;
+            const int e = xz_block_header(p, at, s.index_at, &hdr, &hc, &hu, &dict, why, chains, &bcj, &bcj_start, &b);
             if (e) return e;
             if (r.unpadded < hdr + csz + 1) return kXzPlanFormat;
-            XzBlock b;
             b.in_off = at + hdr;
             b.in_len = r.unpadded - hdr - csz;
             b.out_off = out_off;

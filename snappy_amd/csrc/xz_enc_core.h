@@ -858,17 +858,52 @@ inline void xzenc_stream_header(uint8_t* p, uint32_t check = kXzCheckCrc64)
     p[7] = (uint8_t)check;
     xzenc_le32(p + 8, xz_crc32(p + 6, 2));
 }
-// a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size.  filter: a BCJ filter in
-// front of LZMA2 (bcj_core.h's ids; 0: none), named without properties: its start_offset is 0
-inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, uint32_t dict_byte, uint32_t filter = 0)
+// The filters a Block names in front of LZMA2, the header's first filter first: none, one BCJ filter (a plain id converts: the
+// `filter` of DESIGN.md sec. 25), or up to three of Delta and the six BCJ filters (sec. 29).  param: Delta's distance; a BCJ
+// filter is named without properties, its start_offset 0.
+struct XzEncChain {
+    uint32_t n = 0;
+    uint32_t id[3] = {0, 0, 0};
+    uint32_t param[3] = {0, 0, 0};
+    XzEncChain() = default;
+    bool plain = false; // made from a plain id: held to the three ids the `filter` field takes
+    XzEncChain(uint32_t filter) : n(filter ? 1 : 0), plain(true) { id[0] = filter; }
+    explicit operator bool() const { return n != 0; }
+    uint32_t first() const { return n ? id[0] : 0; }
+};
+// a chain this side writes: every filter one liblzma knows, a distance of 1 .. 256, no parameter on a BCJ filter
+inline bool xzenc_chain_valid(const XzEncChain& c)
+{
+    if (c.n > 3) return false;
+    if (c.plain) return c.id[0] == 0 || bcj_filter_valid(c.id[0]);
+    for (uint32_t k = 0; k < c.n; ++k)
+        if (!xz_filter_valid(c.id[k]) || (c.id[k] == kXzDelta ? !delta_dist_valid(c.param[k]) : c.param[k] != 0)) return false;
+    return true;
+}
+// the chain applied to a Block on one thread, in place, as the kernels apply it stage by stage
+inline void xzenc_chain_apply(const XzEncChain& c, uint8_t* b, uint64_t len)
+{
+    for (uint32_t k = 0; k < c.n; ++k) {
+        if (c.id[k] == kXzDelta) delta_block(true, b, len, c.param[k]);
+        else bcj_block(c.id[k], true, b, len, 0);
+    }
+}
+// a Block header that states both sizes, into p (kXzEncBlockHeaderMax bytes of room): its size.  chain: the filters in front
+// of LZMA2 -- Delta with its one property byte, a BCJ filter (bcj_core.h's ids) without properties
+inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, uint32_t dict_byte, const XzEncChain& chain = XzEncChain())
 {
     uint32_t n = 2;
-    p[1] = (uint8_t)(0xC0 | (filter ? 1 : 0)); // one filter or two; compressed and uncompressed size present
+    p[1] = (uint8_t)(0xC0 | chain.n); // 1 + chain.n filters; compressed and uncompressed size present
     n += xzenc_vli(p + n, csize);
     n += xzenc_vli(p + n, usize);
-    if (filter) {
-        p[n++] = (uint8_t)filter;
-        p[n++] = 0x00;
+    for (uint32_t k = 0; k < chain.n; ++k) {
+        p[n++] = (uint8_t)chain.id[k];
+        if (chain.id[k] == kXzDelta) {
+            p[n++] = 0x01;
+            p[n++] = (uint8_t)(chain.param[k] - 1);
+        } else {
+            p[n++] = 0x00;
+        }
     }
     p[n++] = 0x21;
     p[n++] = 0x01;
@@ -878,12 +913,12 @@ inline uint32_t xzenc_block_header(uint8_t* p, uint64_t csize, uint64_t usize, u
     xzenc_le32(p + n, xz_crc32(p, n));
     return n + 4;
 }
-inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize, uint32_t filter = 0)
+inline uint32_t xzenc_block_header_size(uint64_t csize, uint64_t usize, const XzEncChain& chain = XzEncChain())
 {
     uint8_t t[kXzEncBlockHeaderMax];
-    return xzenc_block_header(t, csize, usize, 0, filter);
+    return xzenc_block_header(t, csize, usize, 0, chain);
 }
-// the filters this side writes in front of LZMA2 (0: none)
+// the filters this side writes in front of LZMA2 through the `filter` field (0: none)
 inline bool xzenc_filter_valid(uint32_t filter) { return filter == 0 || bcj_filter_valid(filter); }
 struct XzEncRecord { uint64_t unpadded, usize; };
 // the Index and the Stream footer behind the last Block
@@ -920,7 +955,7 @@ struct XzEncBlockLayout {
     uint64_t unpadded = 0;  // the Index record's
 };
 inline XzEncBlockLayout xzenc_block_layout(const uint32_t* res, uint32_t nch, uint64_t blen, uint64_t* dst, uint32_t check = kXzCheckCrc64,
-                                           uint32_t filter = 0)
+                                           const XzEncChain& filter = XzEncChain())
 {
     const uint32_t check_size = xzenc_check_size(check);
     XzEncBlockLayout L;
@@ -968,7 +1003,7 @@ struct XzEncInfo {
 template <class OPS>
 inline XzEncBlockLayout xzenc_block_stages(const uint8_t* blk, uint32_t blen, uint32_t* prev, uint32_t* cand, uint32_t* head, uint16_t* probs,
                                            uint32_t* res, uint64_t* dst, uint8_t* slots, OPS& ops, uint32_t check = kXzCheckCrc64,
-                                           uint32_t filter = 0, uint32_t level = 0, bool lanes_descending = false)
+                                           const XzEncChain& filter = XzEncChain(), uint32_t level = 0, bool lanes_descending = false)
 {
     const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;
     xzenc_chains_host(blk, blen, prev, head);
@@ -1001,7 +1036,7 @@ inline void xzenc_block_place(const uint8_t* blk, uint32_t blen, const uint32_t*
 }
 // what the host writes of a Block that begins at q: header, Block Padding, Check (CRC-64, or any Check's field as bytes)
 inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t blen, uint32_t dict_byte, const uint8_t* field, uint32_t check_size,
-                              uint32_t filter = 0)
+                              const XzEncChain& filter = XzEncChain())
 {
     xzenc_block_header(q, L.data, blen, dict_byte, filter);
     for (uint64_t z = L.hdr + L.data; z < L.check_at; ++z) q[z] = 0;
@@ -1016,14 +1051,14 @@ inline void xzenc_block_frame(uint8_t* q, const XzEncBlockLayout& L, uint64_t bl
 
 // The whole file on this thread, through the routines the kernels run, with Check `check` (xzenc_check_valid).
 // field(p, len, out): the Check of a Block's bytes, xzenc_check_size(check) bytes as the file holds them.  false: the
-// block size, the Check or the filter is not one the format decisions allow.  filter: a BCJ filter in front of LZMA2 (0:
-// none): every Block is filtered as the kernels filter it (a copy, positions from the Block's first byte) and the steps run
+// block size, the Check or the chain is not one the format decisions allow.  filter: the chain in front of LZMA2 (a plain id:
+// one BCJ filter; 0: none): every Block is filtered as the kernels filter it (a copy, positions from the Block's first byte) and the steps run
 // over the copy; the Check is over the unfiltered bytes.
 template <class OPS, class FIELD>
 inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uint32_t check, std::vector<uint8_t>& out, OPS& ops, FIELD field,
-                       XzEncInfo* info = nullptr, uint32_t filter = 0, uint32_t level = 0, bool lanes_descending = false)
+                       XzEncInfo* info = nullptr, const XzEncChain& filter = XzEncChain(), uint32_t level = 0, bool lanes_descending = false)
 {
-    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check) || !xzenc_filter_valid(filter) || level > kXzEncLevelMax) return false;
+    if (!xzenc_block_size(&block_size) || !xzenc_check_valid(check) || !xzenc_chain_valid(filter) || level > kXzEncLevelMax) return false;
     const uint32_t dict_byte = xzenc_dict_byte(block_size), check_size = xzenc_check_size(check);
     out.resize(kXzEncStreamHeader);
     xzenc_stream_header(out.data(), check);
@@ -1038,7 +1073,7 @@ inline bool xzenc_host(const uint8_t* data, uint64_t n, uint64_t block_size, uin
         const uint32_t blen = (uint32_t)std::min<uint64_t>(block_size, n - b0);
         if (filter) {
             filtered.assign(raw, raw + blen);
-            bcj_block(filter, true, filtered.data(), blen, 0);
+            xzenc_chain_apply(filter, filtered.data(), blen);
             blk = filtered.data();
         }
         const uint32_t nch = (blen + kXzEncChunk - 1) / kXzEncChunk;

@@ -51,7 +51,7 @@ int xz_block_host(const uint8_t* p, const XzBlock& b, uint8_t* out, uint16_t* pr
 {
     NoOps ops;
     if (lzma2_block_host(p + b.in_off, b.in_len, out, b.out_len, b.dict_size, probs, ops) != kXzOk) return kXzBad;
-    if (b.bcj) bcj_block(b.bcj, false, out, b.out_len, b.bcj_start); // (the Check is over the unfiltered bytes)
+    xz_chain_undo(b, out); // (the Check is over the unfiltered bytes)
     return xz_check_block(p, b, out) ? kXzOk : kXzBad;
 }
 
@@ -89,11 +89,11 @@ int xz_blocks_host(const uint8_t* p, const std::vector<XzBlock>& blocks, const s
     return bad.load() ? SNAPHASH_EFORMAT : 0;
 }
 
-int xz_decode_host(const uint8_t* p, size_t n, std::vector<uint8_t>& out, unsigned threads, uint64_t* nblocks, std::string& why, bool allow_bcj)
+int xz_decode_host(const uint8_t* p, size_t n, std::vector<uint8_t>& out, unsigned threads, uint64_t* nblocks, std::string& why, int chains)
 {
     std::vector<XzBlock> blocks;
     uint64_t total = 0;
-    const int e = xz_plan(p, n, blocks, &total, why, allow_bcj);
+    const int e = xz_plan(p, n, blocks, &total, why, chains);
     if (e) return e == kXzPlanUnsupported ? SNAPHASH_EINVAL : SNAPHASH_EFORMAT;
     const size_t o0 = out.size();
     out.resize(o0 + total);

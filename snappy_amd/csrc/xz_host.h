@@ -19,7 +19,7 @@ void xz_sha256(const uint8_t* p, uint64_t n, uint8_t* out); // 32 bytes
 // The Check field of Block b (in the file p) against the Block's decoded bytes: true when it matches (or there is none).
 bool xz_check_block(const uint8_t* p, const XzBlock& b, const uint8_t* bytes);
 
-// One Block of the file p into out[0 .. b.out_len) on this thread, its BCJ filter undone (b.bcj) and its Check included:
+// One Block of the file p into out[0 .. b.out_len) on this thread, its filter chain undone (xz_chain_undo) and its Check included:
 // kXzOk or kXzBad.
 int xz_block_host(const uint8_t* p, const XzBlock& b, uint8_t* out, uint16_t* probs);
 
@@ -28,8 +28,8 @@ int xz_block_host(const uint8_t* p, const XzBlock& b, uint8_t* out, uint16_t* pr
 int xz_blocks_host(const uint8_t* p, const std::vector<XzBlock>& blocks, const std::vector<uint32_t>* which, uint8_t* out, unsigned threads);
 
 // A whole .xz buffer: plan and decode.  0, SNAPHASH_EFORMAT or SNAPHASH_EINVAL (a filter chain or Check this does not
-// take; why says which).  *nblocks (may be null) = the Blocks.  allow_bcj: xz_plan's.
+// take; why says which).  *nblocks (may be null) = the Blocks.  chains: xz_plan's (kXzChainNone / Bcj / Any).
 int xz_decode_host(const uint8_t* p, size_t n, std::vector<uint8_t>& out, unsigned threads, uint64_t* nblocks, std::string& why,
-                   bool allow_bcj = false);
+                   int chains = kXzChainNone);
 
 } // namespace snaphash

@@ -33,11 +33,11 @@ struct XzEncoder final : Encoder {
     const uint32_t check;
     std::vector<XzEncRecord> recs;
     XzSelfCheck* const self_check; // null = off, the producer's path without it
-    const uint32_t filter;         // a BCJ filter in front of LZMA2 (DESIGN.md sec. 25), 0 = none, the producer's path without it
+    const XzEncChain filter;       // the filters in front of LZMA2 (DESIGN.md sec. 25, 29), none = the producer's path without them
     uint64_t filt_blocks = 0;      // Blocks the BCJ kernels filtered
     double filt_ms = 0;            // the BCJ kernels' own time, HIP events
     const uint32_t level;          // 0: the greedy parse; 1: candidates, prices and a shortest-path parse (DESIGN.md sec. 27)
-    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr, uint32_t flt = 0, uint32_t lvl = 0)
+    explicit XzEncoder(uint64_t bs = kXzEncBlockDefault, uint32_t chk = kXzCheckCrc64, XzSelfCheck* sc = nullptr, XzEncChain flt = XzEncChain(), uint32_t lvl = 0)
         : Encoder(".xz", "xz: the block size is larger than the engine's staging size"), block_size(bs), check(chk), self_check(sc), filter(flt), level(lvl)
     {
         if (sc) check_ms = &sc->ms;
@@ -72,6 +72,24 @@ struct XzEncoder final : Encoder {
         return pipe_finish(g, tail.data(), tail.size(), archive_digest);
     }
 };
+
+// The encoder's chain over the first n bytes of d, a range a Block of bs bytes (positions from the Block's first byte), in
+// place, queued on zs between ev's two events: a stage of the filter kernels a filter -- encode: the header's first filter
+// first; undo: the one nearest LZMA2 first.
+int xz_chain_stages(DevCtx* c, const XzEncChain& ch, uint8_t* d, uint64_t n, uint64_t bs, bool encode, hipStream_t zs, const Span& ev)
+{
+    const uint32_t nblk = (uint32_t)((n + bs - 1) / bs);
+    std::vector<BcjRange> fr(nblk);
+    HIP_TRY(c, hipEventRecord(ev.a, zs));
+    for (uint32_t j = 0; j < ch.n; ++j) {
+        const uint32_t f = encode ? j : ch.n - 1 - j;
+        for (uint32_t k = 0; k < nblk; ++k)
+            fr[k] = BcjRange{(uint64_t)k * bs, std::min<uint64_t>(bs, n - (uint64_t)k * bs), 0, ch.id[f], ch.id[f] == kXzDelta ? ch.param[f] : 0u, encode ? 1u : 0u};
+        if (int rc = xz_filter_stage_dev(c, d, fr, encode, zs, nullptr, nullptr)) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(ev.b, zs));
+    return SNAPHASH_OK;
+}
 
 // The self-check of a slot, behind lzma2_concat_kernel on the compressor's stream: the chunks' stretches of b.d_out[0 .. total)
 // against the slot's staged bytes.  A stretch begins where the host placed the chunk (b.dst) and ends where the host's
@@ -116,11 +134,9 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, u
     }
     if (z.filter) {
         const uint32_t nblk = (uint32_t)lay.size();
-        std::vector<BcjRange> fr(nblk);
         size_t nc = 0;
         for (uint32_t k = 0; k < nblk; ++k) {
             const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
-            fr[k] = BcjRange{b0, blen, 0, z.filter, 0, 0};
             for (uint64_t off = 0; off < blen; off += kCmpChunk) {
                 if (nc >= b.fcmp.size()) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
                 b.fcmp.h[nc++] = CmpChunk{(uint64_t)(uintptr_t)(b.d_filt.data() + b0 + off), (uint64_t)(uintptr_t)(sl.d_buf.data() + b0 + off),
@@ -130,7 +146,7 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, u
         if (b.feq.size() < nblk) return fail(c, SNAPHASH_EDEVICE, "xz: the self-check's tables are smaller than the slot");
         Span fev;
         int rc = span_take(c, Ev::Check, &fev);
-        if (!rc) rc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        if (!rc) rc = xz_chain_stages(c, z.filter, b.d_filt.data(), n, bs, false, zs, fev); // the whole chain undone
         if (rc) return rc;
         HIP_TRY(c, hipMemsetAsync(b.feq.d.data(), 1, nblk, zs)); // equal until a chunk says otherwise
         HIP_TRY(c, hipMemcpyAsync(b.fcmp.d.data(), b.fcmp.h.data(), nc * sizeof(CmpChunk), hipMemcpyHostToDevice, zs));
@@ -141,7 +157,7 @@ int xz_self_check_slot(OutPipe& g, XzEncoder& z, Slot& sl, const uint8_t* src, u
         for (uint32_t k = 0; k < nblk; ++k) {
             if (b.feq.h[k]) continue;
             // where: the Block's two sides read back (the failing path alone pays for it)
-            const uint64_t b0 = (uint64_t)k * bs, blen = fr[k].len;
+            const uint64_t b0 = (uint64_t)k * bs, blen = std::min<uint64_t>(bs, n - b0);
             std::vector<uint8_t> u(blen), v(blen);
             HIP_TRY(c, hipMemcpy(u.data(), b.d_filt.data() + b0, blen, hipMemcpyDeviceToHost));
             HIP_TRY(c, hipMemcpy(v.data(), sl.d_buf.data() + b0, blen, hipMemcpyDeviceToHost));
@@ -181,10 +197,8 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
     if (z.filter) {
         if (b.d_filt.size() < n) return fail(c, SNAPHASH_EDEVICE, "xz: the encoder's buffers are smaller than the slot");
         HIP_TRY(c, hipMemcpyAsync(b.d_filt.data(), sl.d_buf.data(), n, hipMemcpyDeviceToDevice, zs));
-        std::vector<BcjRange> fr(nblk);
-        for (uint32_t k = 0; k < nblk; ++k) fr[k] = BcjRange{(uint64_t)k * bs, std::min<uint64_t>(bs, n - (uint64_t)k * bs), 0, z.filter, 0, 1};
         int frc = span_take(c, Ev::Codec, &fev);
-        if (!frc) frc = bcj_ranges_dev(c, b.d_filt.data(), fr, zs, &fev);
+        if (!frc) frc = xz_chain_stages(c, z.filter, b.d_filt.data(), n, bs, true, zs, fev);
         if (frc) return frc;
         src = b.d_filt.data();
         z.filt_blocks += nblk;
@@ -271,7 +285,7 @@ int xz_process_slot(OutPipe& g, XzEncoder& z, Slot& sl, uint64_t n, hipEvent_t r
         fprintf(stderr, "snaphash xz: slot of %llu bytes, %u blocks, %u chunks: chains %.3f ms, chunks %.3f ms in %zu launch(es) (longest %.3f), "
                         "concat %.3f ms, %s %.3f ms\n", (unsigned long long)n, nblk, nch, chains, sum, evl.size(), longest, concat,
                 check == kXzCheckSha256 ? "sha256" : check == kXzCheckCrc32 ? "crc32" : check == kXzCheckNone ? "no check" : "crc64", crc_ms);
-        if (z.filter) fprintf(stderr, "snaphash xz: slot of %llu bytes: filter 0x%02X %.3f ms\n", (unsigned long long)n, z.filter, filt_ms);
+        if (z.filter) fprintf(stderr, "snaphash xz: slot of %llu bytes: filter 0x%02X %.3f ms\n", (unsigned long long)n, z.filter.first(), filt_ms);
     }
     const uint32_t dict_byte = xzenc_dict_byte(bs);
     for (uint32_t k = 0; k < nblk; ++k) {
@@ -346,26 +360,30 @@ try {
 }
 
 constexpr uint32_t kXzOptionsSizeV1 = 24; // snaphash_xz_options before level and reserved2
+constexpr uint32_t kXzOptionsSizeV2 = 32; // before chain_len and chain
+constexpr uint32_t kXzOptionsSizeV3 = 48;
 
 // What the _ex entries were asked for.  opt == nullptr, or an all-zero struct: what the plain entries write (1 MiB, CRC-64, no
 // self-check); otherwise the struct says its size and every field means what it says (check 0 is "none").
-int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check, uint32_t* filter,
+int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* block_size, uint32_t* check, bool* self_check, XzEncChain* filter,
                     uint32_t* level)
 {
-    static_assert(sizeof(snaphash_xz_options) == 32 && offsetof(snaphash_xz_options, level) == kXzOptionsSizeV1, "level and reserved2 behind the 24 bytes");
+    static_assert(sizeof(snaphash_xz_options) == kXzOptionsSizeV3 && offsetof(snaphash_xz_options, level) == kXzOptionsSizeV1 &&
+                      offsetof(snaphash_xz_options, chain_len) == kXzOptionsSizeV2,
+                  "level and reserved2 behind the 24 bytes, the chain behind the 32");
     *block_size = kXzEncBlockDefault;
     *check = kXzCheckCrc64;
     *self_check = false;
-    *filter = 0;
+    *filter = XzEncChain();
     *level = 0;
     if (opt && opt->struct_size == 0) { // (the plain entry: only the 24 bytes every caller has are looked at)
         if (opt->flags || opt->block_size || opt->check || opt->filter) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
         return SNAPHASH_OK;
     }
     if (!opt) return SNAPHASH_OK;
-    // 24: the struct before it had a level (level 0); 32 and more: with level and reserved2
-    if (opt->struct_size != kXzOptionsSizeV1 && opt->struct_size < sizeof(snaphash_xz_options)) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
-    if (opt->struct_size >= sizeof(snaphash_xz_options)) {
+    // 24: the struct before it had a level (level 0); 32 and more: with level and reserved2; 48 and more: with a chain
+    if (opt->struct_size != kXzOptionsSizeV1 && opt->struct_size < kXzOptionsSizeV2) return fail(x, SNAPHASH_EINVAL, "snaphash_xz_options.struct_size");
+    if (opt->struct_size >= kXzOptionsSizeV2) {
         if (opt->level > kXzEncLevelMax) return fail(x, SNAPHASH_EINVAL, "xz: the level is 0 (greedy parse) or 1 (priced parse)");
         if (opt->reserved2) return fail(x, SNAPHASH_EINVAL, "xz: snaphash_xz_options.reserved2 is not 0");
         *level = opt->level;
@@ -377,7 +395,19 @@ int xz_read_options(snaphash_ctx* x, const snaphash_xz_options* opt, uint64_t* b
     if (!xzenc_block_size(block_size)) return fail(x, SNAPHASH_EINVAL, "xz: the block size is a multiple of 64 KiB from 64 KiB to 4 MiB, or 0");
     *check = opt->check;
     *self_check = (opt->flags & SNAPHASH_XZ_SELF_CHECK) != 0;
-    *filter = opt->filter;
+    *filter = XzEncChain(opt->filter);
+    if (opt->struct_size >= kXzOptionsSizeV3 && opt->chain_len) {
+        XzEncChain ch;
+        ch.n = opt->chain_len;
+        for (uint32_t k = 0; k < 3 && k < ch.n; ++k) {
+            ch.id[k] = opt->chain[k] & 0xff;
+            ch.param[k] = opt->chain[k] >> 8;
+        }
+        if (opt->filter) return fail(x, SNAPHASH_EINVAL, "xz: filter and chain_len are both set");
+        if (!xzenc_chain_valid(ch))
+            return fail(x, SNAPHASH_EINVAL, "xz: the chain is up to 3 filters, each an id 3 .. 9, Delta (3) with a distance of 1 .. 256 in the bits above the id, the others with 0");
+        *filter = ch;
+    }
     return SNAPHASH_OK;
 }
 
@@ -395,7 +425,7 @@ void xz_keep_filter_stats(snaphash_ctx* x, const XzEncoder& z)
 {
     x->xz_filter = snaphash_xz_filter_stats{};
     x->xz_filter.struct_size = sizeof(snaphash_xz_filter_stats);
-    x->xz_filter.filter = z.filter;
+    x->xz_filter.filter = z.filter.first(); // (the id the header names first)
     x->xz_filter.device_blocks = z.filt_blocks;
     x->xz_filter.device_ms = z.filt_ms;
 }
@@ -412,7 +442,8 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    uint32_t filter, level;
+    XzEncChain filter;
+    uint32_t level;
     int rc = xz_read_options(x, opt, &bs, &check, &self, &filter, &level);
     if (rc) return rc;
     XzSelfCheck sc;
@@ -433,7 +464,8 @@ try {
     uint64_t bs;
     uint32_t check;
     bool self;
-    uint32_t filter, level;
+    XzEncChain filter;
+    uint32_t level;
     int rc = xz_read_options(x, opt, &bs, &check, &self, &filter, &level);
     if (rc) return rc;
     XzSelfCheck sc;

@@ -38,7 +38,12 @@ GPU) on tools/deflate_corpora.py's text, sources and binaries, 64 MiB each (--qu
             Python's lzma otherwise): the gain level 0 -> 1 is read against liblzma's own FAST -> NORMAL; the call at both levels,
             alternating, five of each after a warm one; and the chunks kernel's own time and longest launch at both levels
             (a `snaphash xz -L` child under SNAPHASH_TRACE_XZ=1).
-usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--filter NAME] [--level N] [--out FILE]
+  --chain FILTERS instead of the legs above: what a filter chain in front of LZMA2 buys and costs, e.g.
+            delta:2 or delta:3,x86,sparc.  On each corpus (8 MiB) and on a generated 16-bit sample ramp: the bytes without and
+            with the chain beside liblzma's with the same chain on the same 1 MiB Blocks, the call without and with the
+            chain, alternating, five of each, the filter kernels' own time in both directions.  --chain kernels: the filter
+            kernels alone, each new filter in both directions, Delta at distances 1, 3 and 256.
+usage: tools/xz_bench.py [--quick] [--reps N] [--legs size,time,install,build] [--self-check] [--filter NAME] [--chain FILTERS] [--level N] [--out FILE]
        tools/xz_bench.py --no-flag-ab LABEL [--tree DIR] [--corpora-root DIR] [--out FILE]   (JSON lines on stdout and in FILE; --out appends here)"""
 import argparse
 import lzma
@@ -254,6 +259,80 @@ def filter_legs(g, d, name_of_filter, fh, tmp, reps=5):
     emit({"leg": "filter_dense_launch", "filter": name_of_filter, "bytes": n, "kernel_ms_best_median_worst": three(ms), "bound_ms": 1000.0}, fh)
 
 
+def parse_chain(word):
+    """"delta:2,x86" -> [("delta", 2), "x86"]"""
+    return [("delta", int(w[6:])) if w.startswith("delta:") else w for w in word.split(",")]
+
+
+def sample_ramp(n):
+    """16-bit little-endian samples of a slow sweep with a little noise: what Delta at distance 2 is for"""
+    import numpy as np
+    t = np.arange(n // 2, dtype=np.float64)
+    v = 12000.0 * np.sin(t / 900.0) + 3000.0 * np.sin(t / 37.0) + np.random.default_rng(5).integers(-3, 4, n // 2)
+    return v.astype("<i2").tobytes()
+
+
+def chain_legs(g, d, chain, fh, reps=5):
+    """What a filter chain in front of LZMA2 buys and costs, at sec. 25's shape: 8 MiB a corpus in 1 MiB
+    Blocks, five alternating calls; the size gain beside liblzma's gain with the same chain on the same Blocks; and on a
+    generated 16-bit sample ramp."""
+    lz = {"delta": lzma.FILTER_DELTA, "x86": lzma.FILTER_X86, "powerpc": lzma.FILTER_POWERPC, "ia64": lzma.FILTER_IA64, "arm": lzma.FILTER_ARM,
+          "armthumb": lzma.FILTER_ARMTHUMB, "sparc": lzma.FILTER_SPARC}
+    theirs = [dict(id=lzma.FILTER_DELTA, dist=f[1]) if isinstance(f, tuple) else dict(id=lz[f]) for f in chain]
+    hc4 = dict(id=lzma.FILTER_LZMA2, dict_size=BLOCK, mode=lzma.MODE_FAST, mf=lzma.MF_HC4, depth=8, nice_len=273, lc=3, lp=0, pb=2)
+    label = ",".join("delta:%d" % f[1] if isinstance(f, tuple) else f for f in chain)
+
+    def liblzma_blocks(data, filters):
+        with ThreadPoolExecutor(16) as ex:
+            return sum(ex.map(lambda i: len(lzma.compress(data[i:i + BLOCK], format=lzma.FORMAT_RAW, filters=filters)), range(0, len(data), BLOCK)))
+
+    sets = dict(corpora(8 << 20))
+    sets["sample_ramp"] = sample_ramp(8 << 20)
+    for name, data in sets.items():
+        g.xz_buffer(data)  # one warm call each: the scratch
+        g.xz_buffer(data, chain=chain)
+        off, on, kernel = [], [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            z0 = g.xz_buffer(data)
+            off.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            z1 = g.xz_buffer(data, chain=chain)
+            on.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(g.xz_filter_stats()["device_ms"])
+        assert lzma.decompress(z0) == data and lzma.decompress(z1) == data
+        t_dec, _, out = timed(lambda: d.unxz_buffer(z1, chains=True), 3)
+        assert out == data
+        t_gpu, _, out = timed(lambda: g.unxz_buffer(z1, chains=True), 3)
+        assert out == data
+        undo_ms = g.xz_filter_stats()["device_ms"]
+        plain, filt = liblzma_blocks(data, [hc4]), liblzma_blocks(data, theirs + [hc4])
+        emit({"leg": "chain", "chain": label, "corpus": name, "bytes": len(data), "snaphash_xz": len(z0), "snaphash_xz_chain": len(z1),
+              "gain_pct": round(100.0 * (len(z1) - len(z0)) / len(z0), 2), "hc4_depth8_1mib_blocks": plain, "hc4_depth8_1mib_blocks_chain": filt,
+              "liblzma_gain_pct": round(100.0 * (filt - plain) / plain, 2), "reps": reps, "off_ms_best_median_worst": three(off),
+              "on_ms_best_median_worst": three(on), "encode_filter_kernels_ms_best_median_worst": three(kernel),
+              "unxz_default_ms": round(t_dec * 1e3, 2), "unxz_gpu_only_ms": round(t_gpu * 1e3, 2), "decode_filter_kernels_ms": round(undo_ms, 3)}, fh)
+
+
+def filter_kernel_legs(g, fh, reps=5):
+    """The filter kernels alone (snaphash_xz_filter_device): each new filter in both directions over 8 MiB in 1 MiB ranges."""
+    import numpy as np
+    import torch
+    n = 8 << 20
+    data = corpora(n)["binaries"]
+    offs, lens = np.arange(0, n, BLOCK, dtype=np.uint64), np.full(n // BLOCK, BLOCK, dtype=np.uint64)
+    for filt, param in (("delta", 1), ("delta", 3), ("delta", 256), ("powerpc", 0), ("ia64", 0), ("sparc", 0)):
+        for enc in (True, False):
+            ms = []
+            for _ in range(reps):
+                dev = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+                torch.cuda.synchronize()
+                g.xz_filter_device(filt, enc, dev.data_ptr(), offs, lens, param=param)
+                ms.append(g.stats()["kernel_ms"])
+            emit({"leg": "filter_kernels", "filter": filt, "param": param, "direction": "encode" if enc else "decode", "bytes": n, "ranges": len(offs),
+                  "launches": g.stats()["launches"], "kernel_ms_best_median_worst": three(ms), "bound_ms": 1000.0}, fh)
+
+
 LEVEL_DEPTH = {1: 32}  # kXzEncDepthHigh
 
 
@@ -332,6 +411,7 @@ def main():
     ap.add_argument("--self-check", action="store_true")
     ap.add_argument("--no-flag-ab", metavar="LABEL")
     ap.add_argument("--filter", metavar="NAME", choices=("x86", "arm", "armthumb"))
+    ap.add_argument("--chain", metavar="FILTERS", help="e.g. delta:2 or delta:3,x86,sparc; 'kernels': the filter kernels alone")
     ap.add_argument("--level", type=int, choices=(1,))
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--corpora-root", default=ROOT)
@@ -348,6 +428,13 @@ def main():
         if a.filter:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, Context(device=0, flags=0) as d:
                 filter_legs(g, d, a.filter, fh, tmp)
+            return
+        if a.chain:
+            with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g, Context(device=0, flags=0) as d:
+                if a.chain == "kernels":
+                    filter_kernel_legs(g, fh)
+                else:
+                    chain_legs(g, d, parse_chain(a.chain), fh)
             return
         if a.level:
             with Context(device=0, flags=_lib.FLAG_GPU_ONLY) as g:
